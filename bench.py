@@ -8,6 +8,9 @@ the HBM-resident assembly, polished sequences copied to the host.  The contigs g
 launch per pipeline step for a group of contigs (csrc/np2_batch.cpp), the way the CLI streams an assembly.
 With --gpus N every rank polishes its own assembly (weak scaling, no data-path collective) and the polished sequences
 are all-gathered over RCCL inside the timed step.  `--workload ecoli` reproduces the round-1 line (configs[1]).
+A plain run sets up, warms up, times --steps steps once and prints the line; --full adds what else the line used to carry
+(repeated timed regions, the exclusive roofline steps, host-buffer and files -> FASTA paths, the CPU oracle baseline and
+its comparison, the strong sub-result of a multi-rank run).  --dump-outputs DIR writes the last timed step's results.
 """
 import argparse
 import json
@@ -45,6 +48,28 @@ KERNEL_TIME = {"yeast": {"roofline_kernel_us": 145.7, "kernel_sum_us": 3258.5, "
                "ecoli": {"roofline_kernel_us": 47.9, "kernel_sum_us": 720.1, "dominant_by_time": "copies of the result to the host (rocclr copyBuffer)", "dominant_by_time_us": 96.2,
                          "source": "profiles/r06_ecoli_kernels_per_step.txt (the table's total less k_yak_insert)"}}
 PMC_TRAFFIC = {"yeast": int((2 * 26312.2 + 33996.6) * 1024), "ecoli": int((2 * 38836.5 + 31654.1) * 1024)}
+DUMP_BYTES = 64 << 20  # budget of --dump-outputs over all its files
+
+
+def dump_outputs(d, bases, spans, budget=DUMP_BYTES):
+    """--dump-outputs: what a caller of the timed path receives from its last step, as .npy files in d —
+    polished_bases.npy (float32 of the bases' ASCII codes, every contig's one after the other), contig_lengths.npy and
+    spans.npy (float64; first and last reference position per contig).  Bases beyond the budget: a fixed sample (seed 0)
+    of them, polished_bases_index.npy (float64) saying which."""
+    os.makedirs(d, exist_ok=True)
+    lengths = np.array([len(b) for b in bases], dtype=np.float64)
+    spans = np.array([[int(x[0]), int(x[1])] for x in spans], dtype=np.float64).reshape(-1, 2)
+    flat = np.concatenate([np.asarray(b).view(np.uint8).ravel() for b in bases]) if bases else np.zeros(0, np.uint8)
+    room = budget - lengths.nbytes - spans.nbytes - 4 * 128  # (.npy headers)
+    index = None
+    if flat.size * 4 > room:  # a sampled base costs 4 B of value + 8 B of index
+        index = np.unique(np.random.default_rng(0).integers(0, flat.size, size=room // 12))
+        flat = flat[index]
+    np.save(os.path.join(d, "polished_bases.npy"), flat.astype(np.float32))
+    np.save(os.path.join(d, "contig_lengths.npy"), lengths)
+    np.save(os.path.join(d, "spans.npy"), spans)
+    if index is not None:
+        np.save(os.path.join(d, "polished_bases_index.npy"), index.astype(np.float64))
 
 
 def make_assembly(lengths, depth, seed0, diploid):
@@ -522,7 +547,8 @@ def main_strong(a):
     if setup[1] != a.gpus:
         raise SystemExit(f"--gpus {a.gpus} but WORLD_SIZE={setup[1]}")
     import torch.distributed as dist
-    out_line = strong_measure(a, setup, a.contig_mb * a.scale, a.steps, a.warmup, not a.haploid, cpu_base=not a.no_cpu_baseline)
+    out_line = strong_measure(a, setup, a.contig_mb * a.scale, a.steps, a.warmup, not a.haploid,
+                              cpu_base=a.full and not a.no_cpu_baseline, dump=a.dump_outputs)
     if setup[0] == 0:
         print(json.dumps(out_line), flush=True)
     if "RANK" in os.environ:
@@ -531,13 +557,14 @@ def main_strong(a):
     return 0
 
 
-def strong_measure(a, setup, contig_mb, steps, warmup, diploid, cpu_base=False):
+def strong_measure(a, setup, contig_mb, steps, warmup, diploid, cpu_base=False, dump=None):
     """Strong scaling: ONE contig, 30x simulated HiFi (15x per haplotype when diploid), k21 + k31, cut into one reference
     interval per rank (np2_shard_*; nextpolish2_amd.dist.polish_sharded).  The shards are resident in HBM before the timed
     region; a step = the whole hot path of the contig: every rank's dense pass, its phasing pass, the votes gathered onto
     rank 0 (RCCL), the contig-wide decision there, the removed reads broadcast, the final pass, the strips around the cuts
     exchanged and checked, the owned slices gathered from the device buffers onto rank 0 (RCCL over xGMI) and landed in one
-    host array there.  Returns the JSON object of the line (complete on rank 0)."""
+    host array there.  dump: directory for dump_outputs of the last timed step (rank 0).  Returns the JSON object of the
+    line (complete on rank 0)."""
     import torch
     import torch.distributed as dist
     from nextpolish2_amd import Opts, Polisher
@@ -590,6 +617,8 @@ def strong_measure(a, setup, contig_mb, steps, warmup, diploid, cpu_base=False):
     sync()
     dt = time.perf_counter() - t0
     gc.enable()
+    if dump and rank == 0:
+        dump_outputs(dump, [last[0][0]], [last[0][1]])
     stages = None
     if os.environ.get("NP2_BENCH_STAGES"):  # one more, untimed step with every stage timer armed: where a step's time goes
         pol.set_timing(True)
@@ -685,9 +714,18 @@ def main():
     ap.add_argument("--haploid", action="store_true", help="--scaling strong: a haploid contig (no phasing vote to decide)")
     ap.add_argument("--strong-mb", type=float, default=62.0,
                     help="--gpus N > 1: length of the diploid contig behind the 'strong' sub-result of the weak line (0: none)")
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="timed regions of --steps steps each: the first is the line's value, all of them its median / min / max")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of --steps steps each: the first is the line's value, all of them its median / min / max "
+                         "(default 5 with --full, else 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: repeated timed regions, the exclusive "
+                         "roofline steps, host-buffer and files -> FASTA paths, the CPU oracle baseline and its comparison, "
+                         "the strong sub-result of a multi-rank run (the --no-* switches above apply to these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's polished sequences and spans to DIR/*.npy (rank 0)")
     a = ap.parse_args()
+    if a.repeats is None:
+        a.repeats = 5 if a.full else 1
     if a.scaling == "strong":
         a.workload = "chr1"
     if a.workload == "chr1":
@@ -772,7 +810,8 @@ def main():
     if single:
         for _ in range(a.warmup):
             out = step_single()
-        drain_single(out)
+        if a.warmup:
+            drain_single(out)
     elif a.warmup:
         groups.run(opts, a.warmup, after, stage=stage, sink=sink)
     groups.set_timing(True)  # HIP events around the batched k_diff_reads launches, on the batch streams
@@ -815,6 +854,8 @@ def main():
             e[0] += 1
             e[1] += d / 1e9
     flush_log = [] if single else [b.flush_log() for b in groups.bps]
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, [o[0] for o in out], [o[1] for o in out])
     # the same region again (--repeats - 1 times, after the one the line's value comes from): boxes of the pool differ by
     # several per cent and a region is tens of milliseconds, so the line also carries the median and the spread
     region_dt = [dt]
@@ -831,7 +872,7 @@ def main():
         region_dt.append(time.perf_counter() - t1)
     gc.enable()
     excl = None
-    if not single and len(groups.bps) > 1 and not a.no_exclusive:  # the roofline kernel without other groups' kernels next to it (untimed)
+    if a.full and not single and len(groups.bps) > 1 and not a.no_exclusive:  # the roofline kernel without other groups' kernels next to it (untimed)
         _, ms_x, k_x, _ = groups.run(opts, 2, None, exclusive=True)
         excl = (ms_x, k_x)
     groups.set_timing(False)
@@ -911,7 +952,7 @@ def main():
         out_line["roofline_exclusive"] = {"achieved": round(ach_x, 2), "frac": round(ach_x / HBM_PEAK_GBS, 5), "unit": "GB/s",
                                           "avg_launch_ms": round(excl[0] / max(1, excl[1]), 4), "launches_per_step": excl[1],
                                           "note": "one batch group at a time, outside the timed region"}
-    if rank == 0 and world == 1 and not a.no_end_to_end:  # (N = 1 only; before the CPU baseline: its hundreds of threads leave the host noisy)
+    if a.full and rank == 0 and world == 1 and not a.no_end_to_end:  # (N = 1 only; before the CPU baseline: its hundreds of threads leave the host noisy)
         import tempfile
         with tempfile.TemporaryDirectory() as td:
             mid = sorted(range(len(syn)), key=lambda i: lengths[i])[len(syn) // 2]
@@ -919,7 +960,7 @@ def main():
             out_line["end_to_end"] = end_to_end(pol, syn[mid], yaks, opts, td, bases[mid])
             if not single and a.scale == 1.0:
                 out_line["end_to_end_assembly"] = end_to_end_assembly(syn, yaks, td, bases, spans)
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:  # (the host-side baseline is reported at N = 1 only)
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:  # (the host-side baseline is reported at N = 1 only)
         # CPU baseline: the oracle (a port of the reference algorithm; the Rust reference cannot be built here)
         cb, oracle_out = cpu_baseline(syn, yaks, opts, a.cpu_threads)
         out_line["cpu_baseline"] = cb
@@ -942,7 +983,7 @@ def main():
                                              "pass front: k_pf_tile keeps nodes, scores and the walk back in LDS; what passes between "
                                              "kernels per pass is 2 B/bp of per-tile consensus slots and 7 B/bp of consensus arrays "
                                              "(position, base, class, chain flag) - 18 B/bp per step, not counted in B"}
-    if world > 1 and a.strong_mb > 0:
+    if a.full and world > 1 and a.strong_mb > 0:
         # north_star's other curve — ONE assembly over the N GPUs: a diploid contig cut into N reference intervals, on the same
         # ranks, after the weak line's timed region (its own barrier + synchronize brackets; untouched by the value above)
         out_line["strong"] = strong_measure(a, setup, a.strong_mb, max(2, a.steps // 4), 1, True)

@@ -42,7 +42,7 @@ def test_bench_under_torchrun_with_one_rank():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-                        "--gpus", "1", "--steps", "4", "--warmup", "1", "--scale", "0.05", "--cpu-threads", "8"],
+                        "--gpus", "1", "--steps", "4", "--warmup", "1", "--scale", "0.05", "--cpu-threads", "8", "--full"],
                        capture_output=True, env=env, cwd=ROOT, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     line = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")][-1]
@@ -66,7 +66,7 @@ def test_bench_gpus_2_rehearsed_with_gloo_on_one_gpu():
     going through host memory — the code paths (shard protocol over two ranks, staged assembly all-gather, max-over-ranks
     timing, the line with n_gpus == 2) are the ones the driver's SCALE run takes; results must equal the one-rank run."""
     gloo = {"NP2_BENCH_BACKEND": "gloo"}
-    common = ["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-end-to-end"]
+    common = ["--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-end-to-end"]
     strong = ["--scaling", "strong", "--contig-mb", "2", "--haploid"] + common
     one = _bench_line(["--gpus", "1"] + strong)
     two = _bench_line(["--gpus", "2"] + strong, gloo)
@@ -93,6 +93,30 @@ def test_bench_gpus_2_rehearsed_with_gloo_on_one_gpu():
     # one E. coli-sized contig per rank: the single-contig branch (deferred fetch + gather from the device result buffer)
     two = _bench_line(["--gpus", "2", "--workload", "ecoli", "--scale", "0.1"] + common, gloo)
     assert two["n_gpus"] == 2 and two["polished_equals_truth_contigs"] == 1
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """A plain `bench.py` run (no --full) times --steps steps once and carries none of --full's legs; --dump-outputs writes
+    the last timed step's polished sequences, which are the ones the line's checksum covers and the same from run to run."""
+    import zlib
+    lines, dumps = [], []
+    for rep in range(2):
+        d = tmp_path / f"run{rep}"
+        lines.append(_bench_line(["--gpus", "1", "--steps", "3", "--warmup", "1", "--scale", "0.05", "--dump-outputs", str(d)]))
+        dumps.append({f: np.load(d / f"{f}.npy") for f in ("polished_bases", "contig_lengths", "spans")})
+    out = lines[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in out
+    assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["value"] > 0
+    assert out["ms_per_step_regions"]["n"] == 1
+    for k in ("cpu_baseline", "end_to_end", "kernel_path_host_buffers", "roofline_exclusive", "fasta_identical_to_oracle"):
+        assert k not in out
+    got = dumps[0]
+    assert got["polished_bases"].dtype == np.float32 and got["spans"].dtype == np.float64
+    assert got["contig_lengths"].shape == (17,) and got["spans"].shape == (17, 2)
+    assert int(got["contig_lengths"].sum()) == got["polished_bases"].size
+    assert zlib.crc32(got["polished_bases"].astype(np.uint8).tobytes()) == out["output_crc32"]
+    assert all(np.array_equal(got[k], dumps[1][k]) for k in got) and lines[1]["output_crc32"] == out["output_crc32"]
 
 
 def test_deferred_output_fetch_overlaps_the_next_contig():

@@ -1,13 +1,14 @@
 #!/bin/bash
-# Collects the rocprofv3 evidence of one round on a GPU box (run through gpurun from the repo root):
-#   tools/collect_profiles.sh <tag> [bench args...]   ->  gpurun_out/<tag>_*  (copy what you want judged into profiles/)
+# Collects the rocprofv3 evidence of one round on a GPU box (run from the repo root):
+#   tools/collect_profiles.sh <tag> [bench args...]   ->  $OUT/<tag>_*, OUT=bench_out by default (copy what you want judged into profiles/)
 # Counter passes are separate runs with --kernel-trace only (never combined with the sys / hip / hsa trace domains).
 set -u
 TAG=$1; shift
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-OUT=gpurun_out
+OUT=${OUT:-bench_out}
+mkdir -p "$OUT"
 ARGS="--no-cpu-baseline --no-end-to-end --no-exclusive --repeats 1 --steps 10 --warmup 2 $*"
-python bench.py --no-cpu-baseline --no-end-to-end "$@" > $OUT/${TAG}_bench_line.json 2> $OUT/${TAG}_bench.err
+python bench.py --full --no-cpu-baseline --no-end-to-end "$@" > $OUT/${TAG}_bench_line.json 2> $OUT/${TAG}_bench.err
 rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_kt -o kt --output-format csv -- python bench.py $ARGS > $OUT/${TAG}_kt.log 2>&1
 cp $OUT/${TAG}_kt/kt_kernel_stats.csv $OUT/${TAG}_bench_kernel_stats.csv
 python tools/kstats.py $OUT/${TAG}_bench_kernel_stats.csv 12 > $OUT/${TAG}_kernels_per_step.txt
