@@ -99,67 +99,6 @@ __device__ __forceinline__ void k_scan_lb_popc(const uint32_t np2_bid, const uin
     scan_lb_excl_body<true>(np2_bid, np2_nb, lb, n_blocks, in, out, n, write_end, err);
 }
 
-// Long exclusive sums (one element per contig position / consensus base / band slot): reduce-then-scan.  Tiles of 4096
-// elements: (1) tile sums, (2) a single-block scan of the tile sums (k_scan_small), (3) tile-local scans seeded with
-// the tile offsets.  12 B of traffic per element, three launches whatever the number of contigs in the batch, no
-// inter-block waiting (a chained look-back over thousands of tiles measured 100x slower here).
-static constexpr uint32_t SCAN3_ITEMS = 16;
-static constexpr uint32_t SCAN3_TILE = 256 * SCAN3_ITEMS;
-__device__ __forceinline__ void scan3_load(const uint32_t *__restrict__ in, uint32_t i0, uint32_t n, uint32_t (&v)[SCAN3_ITEMS]) {
-    if (i0 + SCAN3_ITEMS <= n) {
-#pragma unroll
-        for (uint32_t q = 0; q < SCAN3_ITEMS / 4; ++q) {
-            const uint4 w = *reinterpret_cast<const uint4 *>(in + i0 + 4 * q);
-            v[4 * q] = w.x, v[4 * q + 1] = w.y, v[4 * q + 2] = w.z, v[4 * q + 3] = w.w;
-        }
-    } else {
-#pragma unroll
-        for (uint32_t k = 0; k < SCAN3_ITEMS; ++k) v[k] = i0 + k < n ? in[i0 + k] : 0u;
-    }
-}
-__device__ __forceinline__ void k_scan3_part(const uint32_t np2_bid, const uint32_t np2_nb, const uint32_t *__restrict__ in, uint32_t n,
-                                             uint32_t *__restrict__ part) {
-    __shared__ uint32_t sh[4];
-    uint32_t v[SCAN3_ITEMS], sum = 0;
-    scan3_load(in, np2_bid * SCAN3_TILE + threadIdx.x * SCAN3_ITEMS, n, v);
-#pragma unroll
-    for (uint32_t k = 0; k < SCAN3_ITEMS; ++k) sum += v[k];
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0) part[np2_bid] = sh[0] + sh[1] + sh[2] + sh[3];
-}
-__device__ __forceinline__ void k_scan3_apply(const uint32_t np2_bid, const uint32_t np2_nb, const uint32_t *__restrict__ in, uint32_t *__restrict__ out,
-                                              uint32_t n, const uint32_t *__restrict__ part_off, bool write_end) {
-    __shared__ uint32_t sh[4];
-    const uint32_t i0 = np2_bid * SCAN3_TILE + threadIdx.x * SCAN3_ITEMS;
-    uint32_t v[SCAN3_ITEMS], sum = 0;
-    scan3_load(in, i0, n, v);
-#pragma unroll
-    for (uint32_t k = 0; k < SCAN3_ITEMS; ++k) sum += v[k];
-    uint32_t total;
-    uint32_t run = part_off[np2_bid] + block_excl_scan<OpAdd, 4>(sum, sh, total);
-    if (i0 + SCAN3_ITEMS <= n) {
-#pragma unroll
-        for (uint32_t q = 0; q < SCAN3_ITEMS / 4; ++q) {
-            uint4 w;
-            w.x = run, run += v[4 * q];
-            w.y = run, run += v[4 * q + 1];
-            w.z = run, run += v[4 * q + 2];
-            w.w = run, run += v[4 * q + 3];
-            *reinterpret_cast<uint4 *>(out + i0 + 4 * q) = w;
-        }
-        if (write_end && i0 + SCAN3_ITEMS == n) out[n] = run;
-    } else {
-#pragma unroll
-        for (uint32_t k = 0; k < SCAN3_ITEMS; ++k) {
-            if (i0 + k < n) out[i0 + k] = run;
-            run += v[k];
-            if (write_end && i0 + k + 1 == n) out[n] = run;
-        }
-    }
-}
-
 // ------------------------------------------------------------------------------------------------------
 // candidate decode
 // ------------------------------------------------------------------------------------------------------
@@ -479,13 +418,8 @@ __device__ __forceinline__ uint32_t wave_excl(uint32_t v) { // exclusive prefix 
 // A region the shortcut does not cover (its window leaves its tile, the contig has a non-ACGT letter there, more than
 // 64 reads over the tile, no record index) decodes every pair the old way.
 // ------------------------------------------------------------------------------------------------------
-#ifndef NP2_RM_WAVES
-#define NP2_RM_WAVES 8 // floor on k_region_measure's resident waves per SIMD
-#endif
-#ifndef NP2_RM_RPW
-#define NP2_RM_RPW 4
-#endif
-static constexpr uint32_t RM_RPW = NP2_RM_RPW;       // regions per wavefront (a multiple of 4: the offsets go by groups of 4 regions)
+static constexpr uint32_t RM_WAVES = 8;              // floor on k_region_measure's resident waves per SIMD
+static constexpr uint32_t RM_RPW = 4;                // regions per wavefront (a multiple of 4: the offsets go by groups of 4 regions)
 static_assert(RM_RPW % 4 == 0 && RM_RPW <= 16, "regions per wavefront");
 static constexpr uint32_t RM_REG = 4 * RM_RPW;       // regions per 256-thread block
 static constexpr uint32_t CAND_CLEAN = 0xFFFFFFFFu;  // kept_col of a candidate that is the contig's own string
@@ -960,20 +894,11 @@ void launch_scan_lb_excl(hipStream_t s, const Lookback &lb, const uint32_t *in, 
     const uint32_t nb = scan_lb_blocks(n);
     NP2_LAUNCH(k_scan_lb_excl, dim3(nb), SCAN_LB_THREADS, s, lb, nb, in, out, n, write_end, err);
 }
-uint32_t scan3_tiles(uint32_t n) { return (n + SCAN3_TILE - 1) / SCAN3_TILE; }
 void launch_scan_lb_popc(hipStream_t s, const Lookback &lb, const uint32_t *bits, uint32_t *out, uint32_t n_words, uint32_t *err) {
     const uint32_t nb = scan_lb_blocks((uint64_t)n_words + 1);
     NP2_LAUNCH(k_scan_lb_popc, dim3(nb), SCAN_LB_THREADS, s, lb, nb, bits, out, n_words + 1, false, err);
 }
 uint32_t scan_lb_blocks(uint64_t n) { return (uint32_t)std::max<uint64_t>(1, (n + SCAN_LB_BLOCK - 1) / SCAN_LB_BLOCK); }
-void launch_scan3_excl(hipStream_t s, const uint32_t *in, uint32_t *out, uint32_t n, uint32_t *part, uint32_t *part_off,
-                       bool write_end) {
-    if (!n) return;
-    const uint32_t nt = scan3_tiles(n);
-    NP2_LAUNCH(k_scan3_part, nt, 256, s, in, n, part);
-    NP2_LAUNCH(k_scan_small<0>, 1, 1024, s, (const uint32_t *)part, part_off, nt, (const uint32_t *)nullptr, (uint32_t *)nullptr, false);
-    NP2_LAUNCH(k_scan3_apply, nt, 256, s, in, out, n, (const uint32_t *)part_off, write_end);
-}
 void launch_scan_small_incl(hipStream_t s, const int32_t *in, int32_t *out, uint32_t n, const uint32_t *n_dev) {
     NP2_LAUNCH(k_scan_small<1>, dim3(1), 1024, s, (const uint32_t *)in, (uint32_t *)out, n, n_dev, (uint32_t *)nullptr, false);
 }
@@ -989,7 +914,7 @@ void launch_region_measure(hipStream_t s, const CandPtrs &c, uint32_t n_reg, uin
                            uint32_t *kept_col, uint32_t *reg_ncand, uint32_t *reg_bytes, uint32_t *reg_maxlen,
                            uint32_t *blk_sum) {
     if (n_reg)
-        NP2_LAUNCH_WAVES(k_region_measure, NP2_RM_WAVES, dim3((n_reg + RM_REG - 1) / RM_REG), 256, s, // (65 registers without the floor: 7 waves)
+        NP2_LAUNCH_WAVES(k_region_measure, RM_WAVES, dim3((n_reg + RM_REG - 1) / RM_REG), 256, s, // (65 registers without the floor: 7 waves)
                          mk_cand(c), n_reg, kept_read, kept_len, kept_col, reg_ncand, reg_bytes, reg_maxlen, blk_sum);
 }
 uint32_t cand_offsets_blocks(uint32_t n_reg) { return ((n_reg + 3) / 4 + 1023) / 1024; }

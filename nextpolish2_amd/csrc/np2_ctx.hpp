@@ -359,19 +359,16 @@ struct PinnedBuf {
     }
 };
 
-// Streams, events and the host-mapped mailbox of a context, kept when the context goes: creating three streams is
-// ~9 ms (more when several threads do it at once), destroying them ~6 ms, and the command line makes a handful of
+// Streams, events and the host-mapped mailbox of a context, kept when the context goes: creating the streams takes
+// milliseconds (more when several threads do it at once), destroying them too, and the command line makes a handful of
 // contexts per run.  A released set has been synchronised; at most 32 idle sets are kept per device.
 struct CtxDeviceState {
-    hipStream_t stream = nullptr, stream2 = nullptr, stream_out = nullptr;
-    hipEvent_t ev_out = nullptr, ev_fork = nullptr, ev_join = nullptr;
+    hipStream_t stream = nullptr, stream_out = nullptr;
+    hipEvent_t ev_out = nullptr;
     uint32_t *mbox_host = nullptr, *mbox_dev = nullptr;
     void destroy() {
         if (ev_out) (void)hipEventDestroy(ev_out);
-        if (ev_fork) (void)hipEventDestroy(ev_fork);
-        if (ev_join) (void)hipEventDestroy(ev_join);
         if (stream_out) (void)hipStreamDestroy(stream_out);
-        if (stream2) (void)hipStreamDestroy(stream2);
         if (stream) (void)hipStreamDestroy(stream);
         if (mbox_host) (void)hipHostFree(mbox_host);
         *this = CtxDeviceState();
@@ -456,8 +453,6 @@ struct np2_contig {
 struct np2_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
-    hipStream_t stream2 = nullptr; // side stream for kernels that can overlap the main one (fork / join by events)
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     // deferred output (np2_result_fetch_begin / _end): device snapshot, two pinned host buffers, their own stream
     hipStream_t stream_out = nullptr;
     hipEvent_t ev_out = nullptr;
@@ -507,7 +502,6 @@ struct np2_ctx {
     DevBuf<uint8_t> cand_seq;
     DevBuf<uint16_t> kscore;
     DevBuf<uint32_t> scal; // device scalars: see enum below
-    DevBuf<uint32_t> scan_part, scan_poff; // tile sums / offsets of the long scans
     // decoupled look-back state (np2_lookback.hpp): status words per block, ticket counter, launch epoch
     DevBuf<uint64_t> lb_status;
     DevBuf<uint32_t> lb_ticket;
@@ -547,7 +541,7 @@ struct np2_ctx {
     DevBuf<ReadInfo> rinfo;      // per read and pass: descriptor + checkpoint offset + region interval in one line
     DevBuf<uint32_t> lqc, lqoff; // low-quality bases written per dirty run, and their exclusive scan
     DevBuf<uint8_t> pflag;               // per contig position: has exception nodes | coverage below 2
-    DevBuf<uint32_t> dp_list; // runs the short-run DP kernel left to the long-run kernels (batch driver: one stream)
+    DevBuf<uint32_t> dp_list; // runs the short-run DP kernel left to the long-run kernels
     DevBuf<uint16_t> pf_slots; // fused pass front: per-tile consensus entries
     DevBuf<uint32_t> pf_bad, pf_bad2; // ... tiles listed for the middle / the big variant
     DevBuf<uint64_t> pf_prof;  // ... phase timers (NP2_PF_PROF)
@@ -556,7 +550,7 @@ struct np2_ctx {
     // racing with setenv elsewhere in the process; a stray variable silently forcing a slow branch for good).  A test sets
     // its variables before it creates its context.
     struct Hooks {
-        bool front_unfused = false, pf_prof = false, cand_decode_all = false, edge_sort = false, dp_fork = false;
+        bool front_unfused = false, pf_prof = false, edge_sort = false;
         bool test_misspeculate = false, shard_spec_log = false, phase_profile = false, exact_grow = false, no_speculate = false;
         bool has_grow_guess = false;
         uint32_t grow_guess = 0;
@@ -567,8 +561,8 @@ struct np2_ctx {
             auto u32 = [](const char *n, bool &has, uint32_t &v) {
                 if (const char *e = getenv(n)) has = true, v = (uint32_t)atol(e);
             };
-            front_unfused = on("NP2_FRONT_UNFUSED"), pf_prof = on("NP2_PF_PROF"), cand_decode_all = on("NP2_CAND_DECODE_ALL");
-            edge_sort = on("NP2_EDGE_SORT"), dp_fork = on("NP2_DP_FORK"), test_misspeculate = on("NP2_TEST_MISSPECULATE");
+            front_unfused = on("NP2_FRONT_UNFUSED"), pf_prof = on("NP2_PF_PROF"), edge_sort = on("NP2_EDGE_SORT");
+            test_misspeculate = on("NP2_TEST_MISSPECULATE");
             shard_spec_log = on("NP2_SHARD_SPEC_LOG"), phase_profile = on("NP2_PHASE_PROFILE"), exact_grow = on("NP2_EXACT_GROW");
             no_speculate = on("NP2_NO_SPECULATE");
             u32("NP2_TEST_GROW_GUESS", has_grow_guess, grow_guess);
@@ -707,8 +701,8 @@ inline void op_copy_d2d(np2_ctx *cx, void *dst, const void *src, size_t bytes) {
 static constexpr size_t KERNEL_COPY_MAX = 1u << 20;
 // (device -> host: round 2 sent everything beyond 64 KiB through hipMemcpyAsync — which on this stack is a blit KERNEL
 // per transfer anyway, with a 12 us submission gap between two of them: 37 transfers per assembly step.  One merged copy
-// kernel for all contigs of a batch has no gaps: +6 % with one batch group, +3 % with four.  NP2_KERNEL_D2H_MAX for A/B.)
-static const size_t KERNEL_D2H_MAX = getenv("NP2_KERNEL_D2H_MAX") ? (size_t)atol(getenv("NP2_KERNEL_D2H_MAX")) : (size_t)(4u << 20);
+// kernel for all contigs of a batch has no gaps: +6 % with one batch group, +3 % with four.)
+static constexpr size_t KERNEL_D2H_MAX = 4u << 20;
 inline void op_d2h(np2_ctx *cx, void *pinned_dst, const void *src, size_t bytes) {
     if (!bytes) return;
     if (Recorder *r = tl_recorder()) {
@@ -839,19 +833,11 @@ template <class F> inline void prim_op(np2_ctx *cx, F f) {
 // Exclusive sums of host-known length, any length: ONE kernel, blocks of 8192 elements chained by the decoupled
 // look-back (k_scan_lb_excl, np2_cand.hip).  Not a choice by length: a threshold had the contigs of a batch pick
 // different kernels for the same step, their queues fell out of step and every later stage went out in more, smaller
-// launches.  NP2_SCAN3=1 brings back the three-launch reduce-then-scan for long arrays (A/B measurements).
+// launches.
 inline void scan_large_excl(np2_ctx *cx, const uint32_t *in, uint32_t *out, size_t n, bool write_end = false) {
     if (n >= 0xFFFFF000ull) throw Np2Error(NP2_E_NOMEM, "scan over more than 2^32 elements");
-    static const bool scan3 = getenv("NP2_SCAN3") != nullptr;
-    if (!scan3 || n <= SCAN_SMALL_MAX) {
-        launch_scan_lb_excl(cx->stream, next_lookback(cx, scan_lb_blocks(n)), in, out, (uint32_t)n, write_end,
-                            cx->scal.p + S_ERR);
-        return;
-    }
-    const uint32_t nt = scan3_tiles((uint32_t)n);
-    cx->scan_part.ensure((size_t)nt + 2);
-    cx->scan_poff.ensure((size_t)nt + 2);
-    launch_scan3_excl(cx->stream, in, out, (uint32_t)n, cx->scan_part.p, cx->scan_poff.p, write_end);
+    launch_scan_lb_excl(cx->stream, next_lookback(cx, scan_lb_blocks(n)), in, out, (uint32_t)n, write_end,
+                        cx->scal.p + S_ERR);
 }
 
 inline uint32_t exclusive_total(np2_ctx *cx, const uint32_t *in, uint32_t *out, size_t n_plus1) {

@@ -36,10 +36,7 @@ struct DenseChunk { // what phase 2 needs to know about a chunk of the block (LD
     uint32_t read, ts, c0, ncols, first_chunk, aln_t_e, nck, pad;
 };
 static_assert(sizeof(DenseChunk) == 48, "DenseChunk mirrors the head of ChunkDesc");
-#ifndef NP2_DENSE_CPW
-#define NP2_DENSE_CPW 2
-#endif
-static constexpr uint32_t DENSE_CPW = NP2_DENSE_CPW;     // chunks per wavefront: their loads are all in flight together
+static constexpr uint32_t DENSE_CPW = 2;                 // chunks per wavefront: their loads are all in flight together
 static constexpr uint32_t DENSE_CHUNKS = 4 * DENSE_CPW;  // chunks per 256-thread block
 static constexpr uint32_t DENSE_HALVES = DENSE_COLS / 32; // 32-column pieces of a chunk: phase 2's unit (two per lane)
 static constexpr uint32_t DENSE_TSLOTS = DENSE_CPW > 2 ? 128 : 64; // tile table of a block (a chunk's columns lie in <= 5 tiles)
@@ -92,9 +89,7 @@ __device__ __forceinline__ void k_diff_reads(const uint32_t np2_bid, const uint3
     const uint32_t *__restrict__ refw32, const uint8_t *__restrict__ refnib, const uint8_t *__restrict__ refeo, uint32_t eo_stride, uint32_t L,
     uint64_t *__restrict__ out_keys, uint32_t *__restrict__ out_vals, uint32_t *__restrict__ tile_cur, uint32_t n_tiles,
     uint32_t bucket_cap, uint64_t ovf_base, uint32_t ovf_cap, uint32_t *__restrict__ ovf_cnt,
-    uint32_t *__restrict__ ckpt, uint64_t *__restrict__ chunk_st, uint32_t epoch, uint32_t *__restrict__ err, uint32_t probe) {
-    // (probe != 0: a timing experiment — tools/dense_probe.sh — that stops after a part of the kernel; launched after the
-    // real pass, it rewrites what that one wrote and nothing else)
+    uint32_t *__restrict__ ckpt, uint64_t *__restrict__ chunk_st, uint32_t epoch, uint32_t *__restrict__ err) {
     const uint32_t lane = threadIdx.x & 63;
     // Which chunks a block takes: workgroups go round the 8 XCDs in turn, each with an L2 of its own, and the reads lie
     // in contig order — taken in launch order every XCD would pull the whole contig (three copies of it) through its L2 and
@@ -117,10 +112,6 @@ __device__ __forceinline__ void k_diff_reads(const uint32_t np2_bid, const uint3
     __shared__ uint2 s_stage[DENSE_STAGE];            // phase 2: records of a round, grouped by tile: {t_pos, piece | column << 10 | tile slot << 15}
     const uint32_t blk_first = lb * DENSE_CHUNKS;
     if (threadIdx.x == 0) s_nq = 0;
-#ifdef NP2_DENSE_PAD_LDS // (occupancy experiment: fewer resident blocks per CU)
-    __shared__ uint32_t s_pad[NP2_DENSE_PAD_LDS / 4];
-    if (probe == 77) s_pad[threadIdx.x] = epoch, atomicOr(err, s_pad[(threadIdx.x * 7) & 255]);
-#endif
     // A wave's time is a chain of memory round trips on top of its instructions: everything that can be requested together
     // is.  Round trip 1: the descriptors of the wave's chunks (scalar loads); 2: the chunks' 32 bytes per lane; 3 (after
     // the block-wide exchange of the chunk totals): the status words of chunks in earlier blocks, where a read started
@@ -207,7 +198,6 @@ __device__ __forceinline__ void k_diff_reads(const uint32_t np2_bid, const uint3
         nA_[it] = nA, nB_[it] = nB, total_[it] = total;
         exA_[it] = (incl & 0xFFFFu) - nA, exB_[it] = totA + (incl >> 16) - nB; // non-insertion columns of the chunk before the piece
     }
-    if (probe == 1) return;
     __syncthreads();
     // ---- phase B: t_pos, contig codes, compare; clean pieces finish here, dirty ones are queued ---------------------------
     uint32_t carry_[DENSE_CPW];
@@ -309,10 +299,8 @@ __device__ __forceinline__ void k_diff_reads(const uint32_t np2_bid, const uint3
             uint32_t *const ckb = ckpt + (dd[it].ckbase - ck_first);
             const uint32_t nck = s_desc[ch - blk_first].nck;
             const uint32_t tsA = (tA + CKPT - 1) & ~(CKPT - 1), tsB = (tB + CKPT - 1) & ~(CKPT - 1);
-            if (probe != 2) {
-                if (okA && nA == 32u && (tsA >> CKPT_SHIFT) - (uint32_t)ck_first < nck) ckb[tsA >> CKPT_SHIFT] = lcA + (tsA - tA);
-                if (okB && nB == 32u && (tsB >> CKPT_SHIFT) - (uint32_t)ck_first < nck) ckb[tsB >> CKPT_SHIFT] = lcB + (tsB - tB);
-            }
+            if (okA && nA == 32u && (tsA >> CKPT_SHIFT) - (uint32_t)ck_first < nck) ckb[tsA >> CKPT_SHIFT] = lcA + (tsA - tA);
+            if (okB && nB == 32u && (tsB >> CKPT_SHIFT) - (uint32_t)ck_first < nck) ckb[tsB >> CKPT_SHIFT] = lcB + (tsB - tB);
         }
         // the piece before piece A of lane l is A of lane l - 1 (lane 0: the previous chunk's last piece), before B of lane l
         // B of lane l - 1 (lane 0: A of lane 63)
@@ -324,10 +312,6 @@ __device__ __forceinline__ void k_diff_reads(const uint32_t np2_bid, const uint3
         const bool dirtyA = oA != 0 || ((pb & 1u) != 0 && nvA_[it] != 0) || (lcA == 0 && ts != 0);
         const bool dirtyB = oB != 0 || ((pb & 2u) != 0 && nvB_[it] != 0);
         const uint64_t dmA = __ballot(dirtyA), dmB = __ballot(dirtyB);
-        if (probe == 2 || probe == 3) { // (keep the comparison alive)
-            if ((dmA ^ dmB) == 0x123456789ABCDEFull && lane == 0) atomicOr(err, 0x80000000u);
-            continue;
-        }
         if (dmA | dmB) {
             const uint32_t cA = (uint32_t)__builtin_popcountll(dmA);
             uint32_t qb = 0;
@@ -353,7 +337,6 @@ __device__ __forceinline__ void k_diff_reads(const uint32_t np2_bid, const uint3
             }
         }
     }
-    if (probe == 2 || probe == 3 || probe == 4) return;
     __syncthreads();
     // ---- phase 2: one thread per dirty piece --------------------------------------------------------------------------------
     // Records go into the bucket of their contig tile; the block reserves its place in a bucket ONCE per tile (a tile
@@ -497,10 +480,6 @@ __device__ __forceinline__ void k_diff_reads(const uint32_t np2_bid, const uint3
                 loc_hi = atomicAdd(&s_cnt[sl_hi], cnt - n_lo);
             }
         }
-        if (probe == 5) { // (everything up to the reservation; keep the counts alive)
-            if (cnt == 0x7FFFFFFFu) atomicOr(err, 0x80000000u);
-            return;
-        }
         __syncthreads();
         // The block's place in every bucket, ONE atomic per tile — whose round trip to memory (agent scope: past the L2s)
         // nobody waits for: the records are formed meanwhile, into an LDS stage grouped by tile, and leave it as whole
@@ -604,9 +583,9 @@ void launch_chunk_counts(hipStream_t s, const ChunkDesc *descs, uint32_t n_chunk
 void launch_diff_reads(hipStream_t s, const ChunkDesc *descs, uint32_t n_chunks, const uint8_t *nib,
                        const uint64_t *refw, const uint8_t *refnib, const uint8_t *refeo, uint32_t eo_stride, uint32_t L, uint64_t *keys, uint32_t *vals,
                        uint32_t *tile_cur, uint32_t n_tiles, uint32_t bucket_cap, uint64_t ovf_base, uint32_t ovf_cap,
-                       uint32_t *ovf_cnt, uint32_t *ckpt, uint64_t *chunk_st, uint32_t epoch, uint32_t *err, uint32_t probe) {
+                       uint32_t *ovf_cnt, uint32_t *ckpt, uint64_t *chunk_st, uint32_t epoch, uint32_t *err) {
     if (n_chunks)
-        NP2_LAUNCH(k_diff_reads, dim3((n_chunks + DENSE_CHUNKS - 1) / DENSE_CHUNKS), 256, s, descs, n_chunks, nib, (const uint32_t *)refw, refnib, refeo, eo_stride, L, keys, vals, tile_cur, n_tiles, bucket_cap, ovf_base, ovf_cap, ovf_cnt, ckpt, chunk_st, epoch, err, probe);
+        NP2_LAUNCH(k_diff_reads, dim3((n_chunks + DENSE_CHUNKS - 1) / DENSE_CHUNKS), 256, s, descs, n_chunks, nib, (const uint32_t *)refw, refnib, refeo, eo_stride, L, keys, vals, tile_cur, n_tiles, bucket_cap, ovf_base, ovf_cap, ovf_cnt, ckpt, chunk_st, epoch, err);
 }
 
 } // namespace np2

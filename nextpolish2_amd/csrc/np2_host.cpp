@@ -661,13 +661,6 @@ void run_diff(np2_ctx *cx, np2_contig *c, uint32_t &T) {
                               cx->keys_raw.p, cx->vals_raw.p, cx->tile_cur.p, n_tiles, bcap, buckets, (uint32_t)ovf_cap,
                               cx->scal.p + S_M3, c->ckpt.p, cx->chunk_st.p, cx->chunk_epoch, cx->scal.p + S_ERR);
         }
-        static const uint32_t probe = getenv("NP2_DENSE_PROBE") ? (uint32_t)atoi(getenv("NP2_DENSE_PROBE")) : 0u;
-        if (probe) { // (timing experiment: a part of the dense pass once more, tools/dense_probe.sh)
-            EventTimer t(cx, "diff_probe", true);
-            launch_diff_reads(s, c->descs.p, NCH, c->nib.p, (const uint64_t *)c->refnib.p, c->refnib.p, c->refnib.p + c->ref_stride, c->ref_stride, L,
-                              cx->keys_raw.p, cx->vals_raw.p, cx->tile_cur.p, n_tiles, bcap, buckets, (uint32_t)ovf_cap,
-                              cx->scal.p + S_M3, c->ckpt.p, cx->chunk_st.p, cx->chunk_epoch, cx->scal.p + S_ERR, probe);
-        }
         {
             EventTimer t(cx, "sort_exceptions");
             // per-tile counts / layouts + the counters the host needs, all in the mailbox: S_M0 = T, S_M1 = largest
@@ -892,34 +885,15 @@ void consensus_and_regions_issue(np2_ctx *cx, np2_contig *c, uint32_t n_nodes, u
     {
         EventTimer t(cx, "dp_backtrack");
         // (scalars were zeroed by build_graph; S_GAIN already holds the clean-position gains)
-        // long runs on the second stream, short runs on the main one: the kernels touch disjoint runs and the long
-        // kernel is a latency chain (a few lanes walking runs of dozens of positions) that would otherwise sit alone
-        // on the device for as long as the short kernel takes
         // The short kernel goes first and lists the runs it leaves alone, so that the long-run kernels walk that list
         // instead of classifying every run again.
-        // (NP2_DP_FORK: the earlier scheme — short and long-run kernels side by side on two streams, each classifying
-        // the runs itself; measured ~1 % slower on the E. coli-sized contig once the short kernel had become the
-        // shorter of the two; kept as a tested alternative)
-        const bool forked = tl_recorder() == nullptr && cx->hooks.dp_fork;
-        uint32_t *dp_list = nullptr, *n_dp_list = nullptr;
-        if (forked) {
-            HIPCHK(hipEventRecord(cx->ev_fork, s));
-            HIPCHK(hipStreamWaitEvent(cx->stream2, cx->ev_fork, 0));
-        } else {
-            cx->dp_list.ensure((size_t)n_runs + 2);
-            dp_list = cx->dp_list.p, n_dp_list = cx->scal.p + S_NDPLIST; // (zeroed with the per-pass scalars)
-            launch_dp_short(s, gp, c->refnib.p, cx->run_start.p, cx->scal.p + S_NRUNS, n_runs, cx->run_end.p,
-                            cx->run_gain.p, cx->emit.p, cx->scal.p + S_PATHBEGIN, cx->bt_path.p, dp_list, n_dp_list);
-        }
-        launch_dp_long(forked ? cx->stream2 : s, gp, cx->run_start.p, cx->scal.p + S_NRUNS, n_runs, cx->nrec.p, cx->nscore.p,
-                       cx->nbesti.p, cx->n0_besti.p, cx->run_end.p, (int64_t *)(cx->scal.p + S_LAST0), cx->run_gain.p,
-                       cx->emit.p, cx->scal.p + S_PATHBEGIN, cx->bt_path.p, cx->run_flag.p, dp_list, n_dp_list);
-        if (forked) {
-            HIPCHK(hipEventRecord(cx->ev_join, cx->stream2));
-            launch_dp_short(s, gp, c->refnib.p, cx->run_start.p, cx->scal.p + S_NRUNS, n_runs, cx->run_end.p,
-                            cx->run_gain.p, cx->emit.p, cx->scal.p + S_PATHBEGIN, cx->bt_path.p, nullptr, nullptr);
-            HIPCHK(hipStreamWaitEvent(s, cx->ev_join, 0));
-        }
+        cx->dp_list.ensure((size_t)n_runs + 2);
+        uint32_t *const dp_list = cx->dp_list.p, *const n_dp_list = cx->scal.p + S_NDPLIST; // (zeroed with the per-pass scalars)
+        launch_dp_short(s, gp, c->refnib.p, cx->run_start.p, cx->scal.p + S_NRUNS, n_runs, cx->run_end.p, cx->run_gain.p,
+                        cx->emit.p, cx->scal.p + S_PATHBEGIN, cx->bt_path.p, dp_list, n_dp_list);
+        launch_dp_long(s, gp, cx->run_start.p, n_runs, cx->nrec.p, cx->nscore.p, cx->nbesti.p, cx->n0_besti.p,
+                       cx->run_end.p, (int64_t *)(cx->scal.p + S_LAST0), cx->run_gain.p, cx->emit.p,
+                       cx->scal.p + S_PATHBEGIN, cx->bt_path.p, cx->run_flag.p, dp_list, n_dp_list);
         launch_dp_finish(s, gp, cx->run_start.p, cx->scal.p + S_NRUNS, cx->nscore.p, cx->nbesti.p, cx->n0_besti.p,
                          (const int64_t *)(cx->scal.p + S_LAST0), (unsigned long long *)(cx->scal.p + S_GAIN0),
                          cx->scal.p + S_DUP /* block counter: reset with the per-pass scalars */, cx->scal.p + S_BEST,
@@ -1096,7 +1070,7 @@ void extract_candidates(np2_ctx *cx, np2_contig *c, uint32_t n_reg, uint16_t min
     CandPtrs cp{c->reads.p,   c->nib.p,   c->ck_off.p,      c->ckpt.p,    cx->lq_start.p, cx->lq_end.p, cx->pj.p,
                 cx->pcount.p, cx->alive.p, cx->rinfo.p, c->tile_rd_off.p, c->tile_rd.p, c->n_tiles, cx->yaks[0].k,
                 cx->keys_raw.p, cx->vals_raw.p, cx->tile_n.p,
-                (cx->pidx_valid && cx->bucket_cap && !cx->hooks.cand_decode_all) ? cx->tile_pidx.p : nullptr, cx->bucket_cap,
+                (cx->pidx_valid && cx->bucket_cap) ? cx->tile_pidx.p : nullptr, cx->bucket_cap,
                 (const uint32_t *)c->refnib.p, c->L};
     {
         EventTimer t(cx, "candidates");
@@ -1670,25 +1644,22 @@ static void destroy_streams(np2_ctx *cx) {
     }
     if (cx->borrowed_state) { // (streams and mailbox are the batch driver's)
         if (cx->ev_out) (void)hipEventDestroy(cx->ev_out);
-        if (cx->ev_fork) (void)hipEventDestroy(cx->ev_fork);
-        if (cx->ev_join) (void)hipEventDestroy(cx->ev_join);
-        cx->stream = cx->stream2 = cx->stream_out = nullptr;
-        cx->ev_out = cx->ev_fork = cx->ev_join = nullptr;
+        cx->stream = cx->stream_out = nullptr;
+        cx->ev_out = nullptr;
         cx->mbox_host = cx->mbox_dev = nullptr;
         return;
     }
     CtxDeviceState st;
-    st.stream = cx->stream, st.stream2 = cx->stream2, st.stream_out = cx->stream_out;
-    st.ev_out = cx->ev_out, st.ev_fork = cx->ev_fork, st.ev_join = cx->ev_join;
+    st.stream = cx->stream, st.stream_out = cx->stream_out;
+    st.ev_out = cx->ev_out;
     st.mbox_host = cx->mbox_host, st.mbox_dev = cx->mbox_dev;
-    cx->stream = cx->stream2 = cx->stream_out = nullptr;
-    cx->ev_out = cx->ev_fork = cx->ev_join = nullptr;
+    cx->stream = cx->stream_out = nullptr;
+    cx->ev_out = nullptr;
     cx->mbox_host = cx->mbox_dev = nullptr;
-    const bool complete = st.stream && st.stream2 && st.stream_out && st.ev_out && st.ev_fork && st.ev_join && st.mbox_host;
+    const bool complete = st.stream && st.stream_out && st.ev_out && st.mbox_host;
     bool idle = complete;
     if (complete) // (nothing of this context may still be running on a set the next context takes over)
-        idle = hipStreamSynchronize(st.stream) == hipSuccess && hipStreamSynchronize(st.stream2) == hipSuccess &&
-               hipStreamSynchronize(st.stream_out) == hipSuccess;
+        idle = hipStreamSynchronize(st.stream) == hipSuccess && hipStreamSynchronize(st.stream_out) == hipSuccess;
     if (idle)
         ctx_state_pool().put(cx->device, st);
     else
@@ -1707,22 +1678,17 @@ static void init_ctx_device(np2_ctx *cx, int device, hipStream_t borrow = nullpt
     CtxDeviceState st;
     if (borrow) {
         cx->borrowed_state = true;
-        cx->stream = cx->stream2 = cx->stream_out = borrow;
+        cx->stream = cx->stream_out = borrow;
         cx->mbox_host = mbox_host, cx->mbox_dev = mbox_dev;
         HIPCHK(hipEventCreateWithFlags(&cx->ev_out, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&cx->ev_fork, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&cx->ev_join, hipEventDisableTiming));
     } else if (ctx_state_pool().get(device, st)) {
-        cx->stream = st.stream, cx->stream2 = st.stream2, cx->stream_out = st.stream_out;
-        cx->ev_out = st.ev_out, cx->ev_fork = st.ev_fork, cx->ev_join = st.ev_join;
+        cx->stream = st.stream, cx->stream_out = st.stream_out;
+        cx->ev_out = st.ev_out;
         cx->mbox_host = st.mbox_host, cx->mbox_dev = st.mbox_dev;
     } else {
         HIPCHK(hipStreamCreateWithFlags(&cx->stream, hipStreamNonBlocking));
-        HIPCHK(hipStreamCreateWithFlags(&cx->stream2, hipStreamNonBlocking));
         HIPCHK(hipStreamCreateWithFlags(&cx->stream_out, hipStreamNonBlocking));
         HIPCHK(hipEventCreateWithFlags(&cx->ev_out, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&cx->ev_fork, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&cx->ev_join, hipEventDisableTiming));
         HIPCHK(hipHostMalloc((void **)&cx->mbox_host, 64 * sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent));
         HIPCHK(hipHostGetDevicePointer((void **)&cx->mbox_dev, cx->mbox_host, 0));
     }
@@ -1831,7 +1797,7 @@ np2_ctx *np2h::ctx_create_slot(np2_ctx *parent, hipStream_t s, uint32_t *mbox_ho
     return cx;
 }
 void np2h::ctx_slot_set_stream(np2_ctx *cx, hipStream_t s) {
-    if (cx->borrowed_state) cx->stream = cx->stream2 = cx->stream_out = s;
+    if (cx->borrowed_state) cx->stream = cx->stream_out = s;
 }
 extern "C" {
 
@@ -1841,7 +1807,6 @@ void np2_ctx_destroy(np2_ctx_t *cx) {
     const double t0 = now_ms();
     (void)hipSetDevice(cx->device);
     if (cx->stream) (void)hipStreamSynchronize(cx->stream);
-    if (cx->stream2) (void)hipStreamSynchronize(cx->stream2);
     if (cx->stream_out) (void)hipStreamSynchronize(cx->stream_out);
     const double t1 = now_ms();
     destroy_streams(cx);
@@ -1908,14 +1873,12 @@ int np2_polish_resident(np2_ctx_t *cx, np2_contig_t *c, const np2_opts_t *opts, 
         flush_timings(cx);
     } catch (const Np2Error &e) {
         (void)hipStreamSynchronize(cx->stream);
-        if (cx->stream2) (void)hipStreamSynchronize(cx->stream2); // (a failure between fork and join leaves work there)
         flush_timings(cx);
         if (r.bases) pinned_pool().put(r.bases);
         if (r.pos) pinned_pool().put(r.pos);
         return fail(cx, e);
     } catch (const std::exception &ex) {
         (void)hipStreamSynchronize(cx->stream);
-        if (cx->stream2) (void)hipStreamSynchronize(cx->stream2); // (a failure between fork and join leaves work there)
         flush_timings(cx);
         if (r.bases) pinned_pool().put(r.bases);
         if (r.pos) pinned_pool().put(r.pos);
@@ -2217,7 +2180,6 @@ struct PinnedBlock {
         __VA_ARGS__                                                                                  \
     } catch (const Np2Error &e) {                                                                    \
         (void)hipStreamSynchronize((cxp)->stream);                                                   \
-        if ((cxp)->stream2) (void)hipStreamSynchronize((cxp)->stream2);                              \
         return fail((cxp), e);                                                                       \
     } catch (const std::exception &ex) {                                                             \
         (void)hipStreamSynchronize((cxp)->stream);                                                   \

@@ -24,7 +24,7 @@ static constexpr uint32_t WALK_EARLY_END = 16u; // the contig's records ended be
 // status[b] = np2inf::Status of block b; *n_bad += blocks that failed (both zeroed by the caller)
 // prof (optional): 8 words per block — clocks of the block, of the wide step's decode, of its chain, of its match copies, tokens, matches
 void launch_bgzf_inflate(hipStream_t s, const InfBlock *blk, uint32_t n_blk, const uint8_t *comp, uint8_t *out, uint32_t *status, uint32_t *n_bad,
-                         unsigned long long *prof = nullptr, uint32_t probe = 0);
+                         unsigned long long *prof = nullptr);
 // starts[0 .. n_chains): stream offsets of record starts, ascending; the last chain ends at a record of another reference or at `end`
 // zone [zone_lo, zone_hi): (0, L) for the whole contig, a shard's reference interval otherwise; cig_src[i] = stream offset of
 // record i's CIGAR words (the record starts 36 + l_read_name bytes before: its BGZF virtual offset follows from that)

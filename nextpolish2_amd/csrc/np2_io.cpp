@@ -1613,9 +1613,9 @@ int np2_ctx_create_from_files(np2_ctx_t **out, int device, const char *const *pa
     if (rc != NP2_OK) return io_fail(rc, "np2_ctx_create failed (see stderr)");
     {
         std::vector<std::thread> th;
-        hipStream_t own[3] = {cx->stream, cx->stream2, cx->stream_out}; // idle until the context's first call
+        hipStream_t own[2] = {cx->stream, cx->stream_out}; // idle until the context's first call
         for (size_t i = 1; i < files.size(); ++i)
-            th.emplace_back([&, i] { yak_file_to_table(*files[i], device, i < 3 ? own[i] : nullptr); });
+            th.emplace_back([&, i] { yak_file_to_table(*files[i], device, i < 2 ? own[i] : nullptr); });
         if (!files.empty()) yak_file_to_table(*files[0], device, own[0]);
         for (auto &t : th) t.join();
     }
@@ -2295,7 +2295,7 @@ int np2_bgzf_inflate_device(np2_ctx_t *cx, const uint8_t *bgzf, uint64_t n, uint
             HIPCHK(hipMemsetAsync(d_prof.p, 0, tb.size() * 64, s));
         }
         np2::launch_bgzf_inflate(s, g.d_blk.p, (uint32_t)tb.size(), g.d_comp.p, g.d_inf.p, g.d_status.p, g.d_status.p + tb.size(),
-                                 kprof ? (unsigned long long *)d_prof.p : nullptr, getenv("NP2_INF_PROBE") ? (uint32_t)atoi(getenv("NP2_INF_PROBE")) : 0u);
+                                 kprof ? (unsigned long long *)d_prof.p : nullptr);
         HIPCHK(hipEventRecord(e1, s));
         if (kprof) {
             std::vector<uint64_t> pr(tb.size() * 8);

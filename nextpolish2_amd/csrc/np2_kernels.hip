@@ -189,9 +189,8 @@ __device__ __forceinline__ int64_t early_run_base(const Graph &g, uint32_t a) {
 // (inside the contig) and at most RW_N exception nodes: k_dp_bt_short scores and backtracks it entirely on chip, with
 // 16-bit coverages / counts and 32-bit scores relative to the run's left neighbour — which is why a pass that has a
 // position covered 65536x or more (Graph::deep, set by k_tile_write) has no short runs at all.  Everything else (long
-// or node-rich runs, the run that reaches the contig end) goes to the eight-lane kernel.  The kernels either classify
-// for themselves from the node offsets (no hand-over: they can run side by side on two streams) or the short kernel
-// lists what it leaves alone (batch driver: one stream).
+// or node-rich runs, the run that reaches the contig end) goes to the eight-lane kernel: the short kernel lists what it
+// leaves alone, and the long-run kernels walk that list after it.
 static constexpr uint32_t RW_P = 13; // positions of a short run kept on chip: up to 12 dirty ones + the closing clean one
 static constexpr uint32_t RW_N = 8;  // exception nodes of a short run kept on chip (149 bytes of LDS per run: 16 waves per CU; 12 nodes / 12 waves measured slower)
 struct __attribute__((packed, aligned(4))) U32x4 {
@@ -259,22 +258,12 @@ __device__ __forceinline__ void dp_bt_long_run(uint32_t r, const uint32_t *__res
                                                uint32_t *__restrict__ run_end, int64_t *__restrict__ last_n0_score,
                                                int64_t *__restrict__ run_gain, uint32_t *__restrict__ emit,
                                                uint32_t *__restrict__ path_begin, uint64_t *__restrict__ path,
-                                               const uint8_t *__restrict__ run_flag, bool listed,
-                                               uint4 (*s_node)[DP_BLOCK]) {
+                                               const uint8_t *__restrict__ run_flag, uint4 (*s_node)[DP_BLOCK]) {
+    // r comes from k_dp_bt_short's list of the runs it left alone
     const uint32_t t = threadIdx.x;
     const uint32_t a = run_start[r], L = g.L;
-    uint32_t o0, o1;
-    if (listed) { // the run comes from k_dp_bt_short's list of runs it left alone
-        if (!run_flag[r]) return; // done by k_dp_bt_oct
-        o0 = g.node_off[a], o1 = g.node_off[a + 1];
-    } else {
-        uint32_t off[RW_P + 1];
-        load_run_offsets(g.node_off, a, off);
-        const uint32_t len = short_run_len(off, a, L);
-        if (len < RW_P && run_is_short(len, off[len] - off[0], *g.deep != 0)) return; // a short run: k_dp_bt_short's
-        if (!run_flag[r]) return;                              // done by k_dp_bt_oct
-        o0 = off[0], o1 = off[1];
-    }
+    if (!run_flag[r]) return; // done by k_dp_bt_oct
+    uint32_t o0 = g.node_off[a], o1 = g.node_off[a + 1];
     const uint32_t o_first = o0;
     int64_t cov = g.cov[a];
     uint8_t c2 = a >= 2 ? ref_code(g.refnib, a - 2) : 0, c1 = a >= 1 ? ref_code(g.refnib, a - 1) : 0;
@@ -478,7 +467,7 @@ __device__ __forceinline__ bool pred_ok(uint16_t vb, uint16_t vd, uint32_t want,
 }
 
 __device__ __forceinline__ void k_dp_bt_oct(const uint32_t np2_bid, const uint32_t np2_nb, const uint32_t *__restrict__ run_start,
-                                                  const uint32_t *__restrict__ n_runs, Graph g,
+                                                  Graph g,
                                                   const uint2 *__restrict__ nrec, int64_t *__restrict__ nscore,
                                                   uint32_t *__restrict__ nbesti, uint32_t *__restrict__ n0_besti,
                                                   uint32_t *__restrict__ run_end, int64_t *__restrict__ last_n0_score,
@@ -488,22 +477,12 @@ __device__ __forceinline__ void k_dp_bt_oct(const uint32_t np2_bid, const uint32
                                                   const uint32_t *__restrict__ dp_list,
                                                   const uint32_t *__restrict__ n_dp_list) {
     const uint32_t j = threadIdx.x & 7;
-    // dp_list: the runs k_dp_bt_short left alone (it ran before this kernel); without it every octet classifies its runs
-    // itself from the node offsets (the two kernels then run side by side on two streams)
-    const uint32_t nr = dp_list ? *n_dp_list : *n_runs, L = g.L;
+    // dp_list: the runs k_dp_bt_short left alone (it ran before this kernel)
+    const uint32_t nr = *n_dp_list, L = g.L;
     for (uint32_t i = np2_bid * 8 + (threadIdx.x >> 3); i < nr; i += np2_nb * 8) { // (uniform per octet)
-        const uint32_t r = dp_list ? dp_list[i] : i;
+        const uint32_t r = dp_list[i];
         const uint32_t a = run_start[r];
-        uint32_t o0, o1;
-        if (dp_list) {
-            o0 = g.node_off[a], o1 = g.node_off[a + 1];
-        } else {
-            uint32_t off[RW_P + 1];
-            load_run_offsets(g.node_off, a, off);
-            const uint32_t len = short_run_len(off, a, L);
-            if (len < RW_P && run_is_short(len, off[len] - off[0], *g.deep != 0)) continue; // a short run: k_dp_bt_short's
-            o0 = off[0], o1 = off[1];
-        }
+        uint32_t o0 = g.node_off[a], o1 = g.node_off[a + 1];
         const uint32_t o_first = o0;
         int64_t cov = g.cov[a];
         uint8_t c2 = a >= 2 ? ref_code(g.refnib, a - 2) : 0, c1 = a >= 1 ? ref_code(g.refnib, a - 1) : 0;
@@ -633,7 +612,7 @@ __device__ __forceinline__ void k_dp_bt_oct(const uint32_t np2_bid, const uint32
 
 // (grid-stride over a capped grid, see k_dp_bt_short)
 __device__ __forceinline__ void k_dp_bt_long(const uint32_t np2_bid, const uint32_t np2_nb, const uint32_t *__restrict__ run_start,
-                                                      const uint32_t *__restrict__ n_runs, Graph g,
+                                                      Graph g,
                                                       const uint2 *__restrict__ nrec, int64_t *__restrict__ nscore,
                                                       uint32_t *__restrict__ nbesti, uint32_t *__restrict__ n0_besti,
                                                       uint32_t *__restrict__ run_end,
@@ -646,10 +625,10 @@ __device__ __forceinline__ void k_dp_bt_long(const uint32_t np2_bid, const uint3
     // one 16-byte LDS word per cached node: {key, count, score lo, score hi} (a node is read as a whole: the DP chain
     // is bound by LDS round trips, not by bytes)
     __shared__ uint4 s_node[2 * DP_NR][DP_BLOCK];
-    const uint32_t nr = dp_list ? *n_dp_list : *n_runs;
+    const uint32_t nr = *n_dp_list;
     for (uint32_t i = np2_bid * DP_BLOCK + threadIdx.x; i < nr; i += np2_nb * DP_BLOCK)
-        dp_bt_long_run(dp_list ? dp_list[i] : i, run_start, g, nrec, nscore, nbesti, n0_besti, run_end, last_n0_score,
-                       run_gain, emit, path_begin, path, run_flag, dp_list != nullptr, s_node);
+        dp_bt_long_run(dp_list[i], run_start, g, nrec, nscore, nbesti, n0_besti, run_end, last_n0_score, run_gain, emit,
+                       path_begin, path, run_flag, s_node);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -871,15 +850,14 @@ __device__ __forceinline__ void k_dp_bt_short(const uint32_t np2_bid, const uint
         const uint32_t r = r0 + lane;
         const bool left = r < nr && !dp_bt_short_run(r, run_start, g, refw32, run_end, run_gain, emit, path_begin, path, deep,
                                                      s_off, s_cov, s_ks, s_cb, s_n0bi);
-        if (dp_list) { // the runs left to the long-run kernels, in no particular order: one reservation per wave
-            const uint64_t m = __ballot(left);
-            if (m) {
-                const uint32_t lead = (uint32_t)__builtin_ctzll(m);
-                uint32_t base = 0;
-                if (lane == lead) base = atomicAdd(n_dp_list, (uint32_t)__builtin_popcountll(m));
-                base = __shfl(base, lead);
-                if (left) dp_list[base + (uint32_t)__builtin_popcountll(m & ((1ULL << lane) - 1ULL))] = r;
-            }
+        // the runs left to the long-run kernels, in no particular order: one reservation per wave
+        const uint64_t m = __ballot(left);
+        if (m) {
+            const uint32_t lead = (uint32_t)__builtin_ctzll(m);
+            uint32_t base = 0;
+            if (lane == lead) base = atomicAdd(n_dp_list, (uint32_t)__builtin_popcountll(m));
+            base = __shfl(base, lead);
+            if (left) dp_list[base + (uint32_t)__builtin_popcountll(m & ((1ULL << lane) - 1ULL))] = r;
         }
     }
 }
@@ -1628,16 +1606,15 @@ void launch_dp_short(hipStream_t s, const GraphPtrs &gp, const void *refw, const
     if (max_runs)
         NP2_LAUNCH(k_dp_bt_short, dim3(std::min<uint32_t>((max_runs + 63) / 64, DP_GRID_CAP)), 64, s, run_start, n_runs, mk_graph(gp), (const uint32_t *)refw, run_end, run_gain, emit, path_begin, path, dp_list, n_dp_list);
 }
-void launch_dp_long(hipStream_t s, const GraphPtrs &gp, const uint32_t *run_start, const uint32_t *n_runs,
-                    uint32_t max_runs, const uint2 *nrec, int64_t *nscore, uint32_t *nbesti, uint32_t *n0_besti,
-                    uint32_t *run_end, int64_t *last_n0_score, int64_t *run_gain, uint32_t *emit, uint32_t *path_begin,
-                    uint64_t *path, uint8_t *run_flag, const uint32_t *dp_list, const uint32_t *n_dp_list) {
+void launch_dp_long(hipStream_t s, const GraphPtrs &gp, const uint32_t *run_start, uint32_t max_runs, const uint2 *nrec,
+                    int64_t *nscore, uint32_t *nbesti, uint32_t *n0_besti, uint32_t *run_end, int64_t *last_n0_score,
+                    int64_t *run_gain, uint32_t *emit, uint32_t *path_begin, uint64_t *path, uint8_t *run_flag,
+                    const uint32_t *dp_list, const uint32_t *n_dp_list) {
     if (!max_runs) return;
-    // with the short kernel's list the grids only have to keep the chip busy (grid-stride over the listed runs)
-    const uint32_t oct_cap = dp_list ? 2048u : 4 * DP_GRID_CAP, long_cap = dp_list ? 512u : DP_GRID_CAP;
-    NP2_LAUNCH(k_dp_bt_oct, dim3(std::min<uint32_t>((max_runs + 7) / 8, oct_cap)), 64, s, run_start, n_runs, mk_graph(gp), nrec, nscore, nbesti, n0_besti, run_end, last_n0_score, run_gain, emit, path_begin, path, run_flag, dp_list, n_dp_list);
+    // the grids only have to keep the chip busy (grid-stride over the short kernel's list of runs)
+    NP2_LAUNCH(k_dp_bt_oct, dim3(std::min<uint32_t>((max_runs + 7) / 8, 2048u)), 64, s, run_start, mk_graph(gp), nrec, nscore, nbesti, n0_besti, run_end, last_n0_score, run_gain, emit, path_begin, path, run_flag, dp_list, n_dp_list);
     // runs with a position of more than 8 exception nodes (deep pileups): the per-thread kernel
-    NP2_LAUNCH(k_dp_bt_long, dim3(std::min<uint32_t>((max_runs + DP_BLOCK - 1) / DP_BLOCK, long_cap)), DP_BLOCK, s, run_start, n_runs, mk_graph(gp), nrec, nscore, nbesti, n0_besti, run_end, last_n0_score, run_gain, emit, path_begin, path, run_flag, dp_list, n_dp_list);
+    NP2_LAUNCH(k_dp_bt_long, dim3(std::min<uint32_t>((max_runs + DP_BLOCK - 1) / DP_BLOCK, 512u)), DP_BLOCK, s, run_start, mk_graph(gp), nrec, nscore, nbesti, n0_besti, run_end, last_n0_score, run_gain, emit, path_begin, path, run_flag, dp_list, n_dp_list);
 }
 void launch_dp_finish(hipStream_t s, const GraphPtrs &gp, const uint32_t *run_start, const uint32_t *n_runs,
                       const int64_t *nscore, const uint32_t *nbesti, const uint32_t *n0_besti, const int64_t *last_n0_score,

@@ -96,7 +96,7 @@ void launch_chunk_counts(hipStream_t s, const ChunkDesc *descs, uint32_t n_chunk
 void launch_diff_reads(hipStream_t s, const ChunkDesc *descs, uint32_t n_chunks, const uint8_t *nib, const uint64_t *refw,
                        const uint8_t *refnib, const uint8_t *refeo, uint32_t eo_stride, uint32_t L, uint64_t *keys, uint32_t *vals, uint32_t *tile_cur,
                        uint32_t n_tiles, uint32_t bucket_cap, uint64_t ovf_base, uint32_t ovf_cap, uint32_t *ovf_cnt,
-                       uint32_t *ckpt, uint64_t *chunk_st, uint32_t epoch, uint32_t *err, uint32_t probe = 0);
+                       uint32_t *ckpt, uint64_t *chunk_st, uint32_t epoch, uint32_t *err);
 void launch_post(hipStream_t s, uint32_t *scal, uint32_t n_scal, uint32_t *mbox, uint32_t seq, uint32_t *d0 = nullptr,
                  const uint32_t *s0 = nullptr, uint32_t *d1 = nullptr, const uint32_t *s1 = nullptr, uint32_t *d2 = nullptr,
                  const uint32_t *s2 = nullptr, uint32_t *d3 = nullptr, const uint32_t *s3 = nullptr,
@@ -110,16 +110,16 @@ void launch_init_alive(hipStream_t s, const np2_read_t *reads, uint32_t R, uint8
 void launch_kill_reads(hipStream_t s, const uint32_t *ids, uint32_t n, uint8_t *alive);
 void launch_revive_reads(hipStream_t s, const uint32_t *ids, uint32_t n, uint8_t *alive); // alive[ids[i]] = 1 (np2_shard_apply)
 void launch_kill_flagged(hipStream_t s, const uint8_t *flag, uint32_t n, uint8_t *alive); // alive[i] = 0 where flag[i]
-// DP + backtrack of the dirty runs.  Short runs: one fused on-chip kernel; long runs and the run reaching the contig end:
-// the generic kernel (independent of the first: the two may run on different streams); finish: score total, best end
-// node, backtrack of the contig-end run, emission fix-up left of the path start.
+// DP + backtrack of the dirty runs.  Short runs: one fused on-chip kernel, which lists the runs it leaves alone
+// (dp_list, n_dp_list); long runs and the run reaching the contig end: the generic kernels over that list, launched
+// after it; finish: score total, best end node, backtrack of the contig-end run, emission fix-up left of the path start.
 void launch_dp_short(hipStream_t s, const GraphPtrs &gp, const void *refw, const uint32_t *run_start,
                      const uint32_t *n_runs, uint32_t max_runs, uint32_t *run_end, int64_t *run_gain, uint32_t *emit,
                      uint32_t *path_begin, uint64_t *path, uint32_t *dp_list, uint32_t *n_dp_list);
-void launch_dp_long(hipStream_t s, const GraphPtrs &gp, const uint32_t *run_start, const uint32_t *n_runs,
-                    uint32_t max_runs, const uint2 *nrec, int64_t *nscore, uint32_t *nbesti, uint32_t *n0_besti,
-                    uint32_t *run_end, int64_t *last_n0_score, int64_t *run_gain, uint32_t *emit, uint32_t *path_begin,
-                    uint64_t *path, uint8_t *run_flag, const uint32_t *dp_list, const uint32_t *n_dp_list);
+void launch_dp_long(hipStream_t s, const GraphPtrs &gp, const uint32_t *run_start, uint32_t max_runs, const uint2 *nrec,
+                    int64_t *nscore, uint32_t *nbesti, uint32_t *n0_besti, uint32_t *run_end, int64_t *last_n0_score,
+                    int64_t *run_gain, uint32_t *emit, uint32_t *path_begin, uint64_t *path, uint8_t *run_flag,
+                    const uint32_t *dp_list, const uint32_t *n_dp_list);
 void launch_dp_finish(hipStream_t s, const GraphPtrs &gp, const uint32_t *run_start, const uint32_t *n_runs,
                       const int64_t *nscore, const uint32_t *nbesti, const uint32_t *n0_besti, const int64_t *last_n0_score,
                       unsigned long long *total_gain, uint32_t *blocks_done, uint32_t *best_idx, const int64_t *run_gain,
@@ -180,11 +180,7 @@ void launch_pair_count(hipStream_t s, const np2_read_t *reads, uint32_t R, const
                        uint32_t *pj, uint32_t *pcount, const uint64_t *ck_off, ReadInfo *rinfo);
 void launch_scan_lb_excl(hipStream_t s, const Lookback &lb, const uint32_t *in, uint32_t *out, uint32_t n, bool write_end,
                           uint32_t *err);
-// exclusive sums of any length (reduce-then-scan over 4096-element tiles); part / part_off: scan3_tiles(n) + 1 words each
-uint32_t scan3_tiles(uint32_t n);
 uint32_t scan_lb_blocks(uint64_t n); // blocks of launch_scan_lb_excl over n elements (its look-back descriptor is sized by this)
-void launch_scan3_excl(hipStream_t s, const uint32_t *in, uint32_t *out, uint32_t n, uint32_t *part, uint32_t *part_off,
-                       bool write_end);
 void launch_scan_small_excl(hipStream_t s, const uint32_t *in, uint32_t *out, uint32_t n, const uint32_t *n_dev,
                             uint32_t *total_out, bool write_end); // write_end: also out[n] = total
 void launch_scan_small_incl(hipStream_t s, const int32_t *in, int32_t *out, uint32_t n, const uint32_t *n_dev);

@@ -44,18 +44,13 @@ def test_golden_fixtures(name):
     assert np.array_equal(gb, exp_b) and np.array_equal(gp, exp_p)
 
 
-@pytest.mark.parametrize("seed,diploid,ks", [(31, False, [21]), (32, True, [21, 31]), (33, True, [21]), (34, False, [17, 21, 31])])
+@pytest.mark.parametrize("seed,diploid,ks", [(31, False, [21]), (32, True, [21, 31]), (33, True, [21]), (34, False, [17, 21, 31]),
+                                             (35, True, [21])])
 def test_stage_parity_synthetic(seed, diploid, ks):
-    s = Synth(50000, depth=30, seed=seed, diploid=diploid, read_len_mean=8000.0, read_len_sd=1500.0)
+    # seed 35: a longer contig with noisier reads (more and longer dirty runs for the DP kernels)
+    L, read_err_rate = (60000, 0.01) if seed == 35 else (50000, 0.002)
+    s = Synth(L, depth=30, seed=seed, diploid=diploid, read_len_mean=8000.0, read_len_sd=1500.0, read_err_rate=read_err_rate)
     check_all_stages(s.pileup, [s.yak(k) for k in ks], Opts())
-
-
-def test_dp_two_stream_variant(monkeypatch):
-    # NP2_DP_FORK: short-run and long-run DP kernels side by side on two streams, each classifying the runs itself
-    # (the default lets the short kernel list what it leaves to the others)
-    monkeypatch.setenv("NP2_DP_FORK", "1")
-    s = Synth(60000, depth=30, seed=35, diploid=True, read_len_mean=8000.0, read_len_sd=1500.0, read_err_rate=0.01)
-    check_all_stages(s.pileup, [s.yak(21)], Opts())
 
 
 @pytest.mark.parametrize("opts", [Opts(iter_count=1), Opts(iter_count=3), Opts(model="len"), Opts(use_all_reads=True),

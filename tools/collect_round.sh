@@ -14,7 +14,6 @@ NP2_PHASE_PROFILE=1 timeout 600 python bench.py --scaling strong --workload chr1
 NP2_IO_PROFILE=1 timeout 300 python tools/bench_frontend.py 4641652 > $OUT/${R}_frontend_ecoli_size.log 2>&1
 timeout 600 python tools/inflate_probe.py > $OUT/${R}_device_read_extraction_ecoli_size.log 2>&1
 NP2_INF_PROF=1 timeout 300 python tools/inflate_only.py 20000 1200000 4641652 > $OUT/${R}_inflate_kernel_sizes.log 2>&1
-for p in 1 2 4; do echo "NP2_INF_PROBE=$p"; NP2_INF_PROBE=$p timeout 300 python tools/inflate_only.py 4641652 2>&1 | grep "^L"; done > $OUT/${R}_inflate_kernel_probe.log 2>&1
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 rocprofv3 --pmc SQ_WAVES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAIT_INST_ANY SQ_WAVE_CYCLES --kernel-trace -d $OUT/inf_ps -o s --output-format csv -- python tools/inflate_only.py 4641652 > /dev/null 2>&1
 python tools/pmc_sq.py $OUT/inf_ps/s_counter_collection.csv | grep -i "inflate\|^kernel" > $OUT/${R}_inflate_pmc_sq.txt; rm -rf $OUT/inf_ps
