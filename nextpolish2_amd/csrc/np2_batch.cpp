@@ -359,6 +359,11 @@ void worker_main(np2_batch *b, int slot) {
     }
 }
 
+// abi_guard's sink for the batch entry points (np2_batch_last_error)
+auto batch_sink(np2_batch *b) {
+    return [b](int, const std::string &msg) { b->err = msg; };
+}
+
 } // namespace
 
 extern "C" {
@@ -366,10 +371,10 @@ extern "C" {
 int np2_batch_create(np2_batch_t **out, np2_ctx_t *parent, int n_slots) {
     if (!out || !parent || n_slots < 1 || n_slots > 256) return NP2_E_ARG;
     *out = nullptr;
-    np2_batch *b = new np2_batch();
-    b->parent = parent;
-    b->device = parent->device;
-    try {
+    return abi_guard([&] {
+        std::unique_ptr<np2_batch, void (*)(np2_batch_t *)> b(new np2_batch(), np2_batch_destroy); // (joins the workers started)
+        b->parent = parent;
+        b->device = parent->device;
         HIPCHK(hipSetDevice(b->device));
         HIPCHK(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
         // one host-mapped block: the completion word of the flushes, then a 64-word mailbox per slot
@@ -383,19 +388,14 @@ int np2_batch_create(np2_batch_t **out, np2_ctx_t *parent, int n_slots) {
             // streams and a pinned block of its own)
             np2_ctx *cx = ctx_create_slot(parent, b->stream, b->done_host + 64 * (size_t)(i + 1), b->done_dev + 64 * (size_t)(i + 1));
             b->slots.push_back(cx);
-            b->recs[i].group = b;
+            b->recs[i].group = b.get();
             b->recs[i].slot = i;
             b->recs[i].sync_fn = &group_sync;
         }
-        for (int i = 0; i < n_slots; ++i) b->workers.emplace_back(worker_main, b, i);
-    } catch (const Np2Error &e) {
-        parent->err = e.what();
-        int code = e.code;
-        np2_batch_destroy(b);
-        return code;
-    }
-    *out = b;
-    return NP2_OK;
+        for (int i = 0; i < n_slots; ++i) b->workers.emplace_back(worker_main, b.get(), i);
+        *out = b.release();
+        return NP2_OK;
+    }, [parent](int, const std::string &msg) { parent->err = msg; });
 }
 
 void np2_batch_destroy(np2_batch_t *b) {
@@ -426,7 +426,7 @@ void np2_batch_destroy(np2_batch_t *b) {
 // in their host phases together.  Alternating priorities keep the groups out of step.
 int np2_batch_set_priority(np2_batch_t *b, int high) {
     if (!b) return NP2_E_ARG;
-    try {
+    return abi_guard([&] {
         HIPCHK(hipSetDevice(b->device));
         int least = 0, greatest = 0;
         HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
@@ -436,11 +436,8 @@ int np2_batch_set_priority(np2_batch_t *b, int high) {
         (void)hipStreamDestroy(b->stream);
         b->stream = s;
         for (np2_ctx *cx : b->slots) ctx_slot_set_stream(cx, s);
-    } catch (const Np2Error &e) {
-        b->err = e.what();
-        return e.code;
-    }
-    return NP2_OK;
+        return NP2_OK;
+    }, batch_sink(b));
 }
 
 int np2_batch_slots(np2_batch_t *b) { return b ? (int)b->slots.size() : 0; }
@@ -458,62 +455,64 @@ int np2_batch_set_sink(np2_batch_t *b, int slot, void *device_ptr, uint64_t cap)
 int np2_batch_polish(np2_batch_t *b, np2_contig_t *const *contigs, int n, const np2_opts_t *opts, uint8_t **out_bases,
                      uint32_t **out_pos, uint64_t *out_len, uint32_t *out_span, int *rcs) {
     if (!b || !contigs || n < 0 || !opts || !out_len || !rcs) return NP2_E_ARG;
-    const int S = (int)b->slots.size();
-    int worst = NP2_OK;
-    b->diff_used = 0;
-    b->flush_log.clear();
-    b->t_last_end = now_ms();
-    const double t_call0 = b->t_last_end;
-    for (int w0 = 0; w0 < n; w0 += S) { // waves of at most S contigs; contig w0 + i runs on slot i
-        const int m = std::min(S, n - w0);
-        {
-            std::lock_guard<std::mutex> l(b->mu);
-            for (int i = 0; i < S; ++i) {
-                Job j;
-                if (i < m) {
-                    j.contig = contigs[w0 + i];
-                    j.opts = opts;
-                    j.out_bases = out_bases ? &out_bases[w0 + i] : nullptr;
-                    j.out_pos = out_pos ? &out_pos[w0 + i] : nullptr;
-                    j.out_len = &out_len[w0 + i];
-                    j.out_span = out_span ? &out_span[2 * (w0 + i)] : nullptr;
-                    j.rc = &rcs[w0 + i];
-                }
-                b->jobs[i] = j;
-            }
-            b->n_running = m;
+    return abi_guard([&] {
+        const int S = (int)b->slots.size();
+        int worst = NP2_OK;
+        b->diff_used = 0;
+        b->flush_log.clear();
+        b->t_last_end = now_ms();
+        const double t_call0 = b->t_last_end;
+        for (int w0 = 0; w0 < n; w0 += S) { // waves of at most S contigs; contig w0 + i runs on slot i
+            const int m = std::min(S, n - w0);
             {
-                std::lock_guard<std::mutex> l2(b->sync_mu);
-                b->n_active = m;
-                b->n_waiting = 0;
-                b->failed.store(false);
+                std::lock_guard<std::mutex> l(b->mu);
+                for (int i = 0; i < S; ++i) {
+                    Job j;
+                    if (i < m) {
+                        j.contig = contigs[w0 + i];
+                        j.opts = opts;
+                        j.out_bases = out_bases ? &out_bases[w0 + i] : nullptr;
+                        j.out_pos = out_pos ? &out_pos[w0 + i] : nullptr;
+                        j.out_len = &out_len[w0 + i];
+                        j.out_span = out_span ? &out_span[2 * (w0 + i)] : nullptr;
+                        j.rc = &rcs[w0 + i];
+                    }
+                    b->jobs[i] = j;
+                }
+                b->n_running = m;
+                {
+                    std::lock_guard<std::mutex> l2(b->sync_mu);
+                    b->n_active = m;
+                    b->n_waiting = 0;
+                    b->failed.store(false);
+                }
+                ++b->job_gen;
             }
-            ++b->job_gen;
-        }
-        b->cv_start.notify_all();
-        {
-            std::unique_lock<std::mutex> l(b->mu);
-            b->cv_done.wait(l, [&] { return b->n_running == 0; });
-        }
-        for (int i = 0; i < m; ++i)
-            if (rcs[w0 + i] != NP2_OK) {
-                worst = rcs[w0 + i];
-                b->err = std::string("contig ") + std::to_string(w0 + i) + ": " + np2_last_error(b->slots[i]);
+            b->cv_start.notify_all();
+            {
+                std::unique_lock<std::mutex> l(b->mu);
+                b->cv_done.wait(l, [&] { return b->n_running == 0; });
             }
-    }
-    b->call_ms = now_ms() - t_call0;
-    b->tail_ms = now_ms() - b->t_last_end;
-    if (b->time_diff) {
-        b->last_diff_ms = 0;
-        b->last_diff_launches = (int)b->diff_used;
-        for (size_t i = 0; i < b->diff_used; ++i) {
-            float ms = 0;
-            (void)hipEventSynchronize(b->diff_events[i].second);
-            (void)hipEventElapsedTime(&ms, b->diff_events[i].first, b->diff_events[i].second);
-            b->last_diff_ms += ms;
+            for (int i = 0; i < m; ++i)
+                if (rcs[w0 + i] != NP2_OK) {
+                    worst = rcs[w0 + i];
+                    b->err = std::string("contig ") + std::to_string(w0 + i) + ": " + np2_last_error(b->slots[i]);
+                }
         }
-    }
-    return worst;
+        b->call_ms = now_ms() - t_call0;
+        b->tail_ms = now_ms() - b->t_last_end;
+        if (b->time_diff) {
+            b->last_diff_ms = 0;
+            b->last_diff_launches = (int)b->diff_used;
+            for (size_t i = 0; i < b->diff_used; ++i) {
+                float ms = 0;
+                (void)hipEventSynchronize(b->diff_events[i].second);
+                (void)hipEventElapsedTime(&ms, b->diff_events[i].first, b->diff_events[i].second);
+                b->last_diff_ms += ms;
+            }
+        }
+        return worst;
+    }, batch_sink(b));
 }
 
 void np2_batch_set_timing(np2_batch_t *b, int enable) {

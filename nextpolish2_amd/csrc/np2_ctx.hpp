@@ -1,6 +1,7 @@
 // Internal shared definitions of the np2 host driver (context, device buffers, transfer helpers).
 #pragma once
 #include "../../include/np2.h"
+#include "np2_abi.hpp"
 #include "np2_common.hpp"
 #include "np2_kernels.hpp"
 #include "np2_hostcpu.hpp"
@@ -23,10 +24,6 @@ namespace np2h {
 using namespace np2;
 
 
-struct Np2Error : std::runtime_error {
-    int code;
-    Np2Error(int c, const std::string &m) : std::runtime_error(m), code(c) {}
-};
 #define HIPCHK(x)                                                                                  \
     do {                                                                                           \
         hipError_t e_ = (x);                                                                       \
@@ -662,6 +659,15 @@ inline void flush_timings(np2_ctx *cx) {
     }
     cx->timing.joined.push_back('\0');
 }
+// abi_guard's sink for an entry point on a context: the stream drained (the failed call's work may still be in flight),
+// the stage timers flushed where the call reports them, the message kept for np2_last_error
+inline auto ctx_sink(np2_ctx *cx, bool timings = false) {
+    return [cx, timings](int, const std::string &msg) {
+        (void)hipStreamSynchronize(cx->stream);
+        if (timings) flush_timings(cx);
+        cx->err = msg;
+    };
+}
 
 // ---- stream operations of the per-contig pipeline ------------------------------------------------------------------
 // Issued on the context's stream, or recorded when this thread runs under the batch driver (np2_launch.hpp): fills and
@@ -875,6 +881,5 @@ inline void exclusive_total_n(np2_ctx *cx, uint32_t *in, uint32_t *out, size_t n
 // reads (host copy given) and nibble buffer are already resident
 void finish_contig(np2_ctx *cx, np2_contig *c, const np2_read_t *reads, uint32_t n_reads, uint32_t L,
                    uint64_t nib_bytes);
-int fail(np2_ctx *cx, const Np2Error &e);
 
 } // namespace np2h

@@ -1130,6 +1130,10 @@ struct ResultOut {
     uint64_t len = 0;
     bool want_pos = true;
     bool want_bases = true; // false: the sequence stays on the device (np2_last_result_device / np2_result_fetch_begin)
+    void release() { // the pinned result blocks go back to the pool (a result that is not handed to the caller)
+        if (bases) pinned_pool().put(bases), bases = nullptr;
+        if (pos) pinned_pool().put(pos), pos = nullptr;
+    }
 };
 // M_cap: what the host knows the length is at most (the device buffers hold that many elements).  The sequence is copied
 // out up to that bound in the SAME wait that brings the length back (one device round trip per contig less than
@@ -1345,8 +1349,7 @@ void run_final_pass(PolishRun &r, ResultOut &result, bool exact_grow = false) {
         fetch_result(cx, cur.pos, cur.base, cur.M_p, cur.M_cap, result, guessed ? r.M + r.grow_prev : r.M + pc.grow);
     } catch (const GrowRetry &) {
         if (!guessed) throw;
-        if (result.bases) pinned_pool().put(result.bases), result.bases = nullptr;
-        if (result.pos) pinned_pool().put(result.pos), result.pos = nullptr;
+        result.release();
         op_fill(cx, cx->scal.p + S_ERR, 0, 4); // (every other bit of the word would have been reported first)
         r.reuse = false;
         run_final_pass(r, result, true);
@@ -1455,8 +1458,7 @@ void polish_impl(np2_ctx *cx, np2_contig *c, const np2_opts_t *o, ResultOut &res
     for (;;) {
         run_final_pass(r, result);
         if (settle()) break;
-        if (result.bases) pinned_pool().put(result.bases), result.bases = nullptr;
-        if (result.pos) pinned_pool().put(result.pos), result.pos = nullptr;
+        result.release();
     }
 }
 
@@ -1510,11 +1512,6 @@ void shard_check_stuck(ShardRun *sr) {
 
 
 namespace np2h {
-int fail(np2_ctx *cx, const Np2Error &e) {
-    if (cx) cx->err = e.what();
-    return e.code;
-}
-
 void finish_contig(np2_ctx *cx, np2_contig *c, const np2_read_t *reads, uint32_t n_reads, uint32_t L,
                    uint64_t nib_bytes) {
     if (reads[0].aln_t_s != 0 || reads[0].n_cols != L || reads[0].aln_t_e != L - 1 ||
@@ -1700,13 +1697,22 @@ static void init_ctx_device(np2_ctx *cx, int device, hipStream_t borrow = nullpt
         cx->deep_min = (uint32_t)std::min<long>(65536, std::max<long>(1, atol(e)));
 }
 
+// a context being made: released with its streams unless it is handed out
+struct CtxDrop {
+    void operator()(np2_ctx *cx) const {
+        destroy_streams(cx);
+        delete cx;
+    }
+};
+using CtxPtr = std::unique_ptr<np2_ctx, CtxDrop>;
+
 int np2_ctx_create(np2_ctx_t **out, int device, const np2_yak_t *yaks, int n_yak) {
     if (!out) return NP2_E_ARG;
     *out = nullptr;
-    np2_ctx *cx = new np2_ctx();
-    try {
+    return abi_guard([&] {
+        CtxPtr cx(new np2_ctx());
         const double t_c0 = now_ms();
-        init_ctx_device(cx, device);
+        init_ctx_device(cx.get(), device);
         if (getenv("NP2_CTX_PROFILE")) fprintf(stderr, "np2_ctx_create: streams, events, mailbox %.2f ms\n", now_ms() - t_c0);
         // the final pass runs one splice round + one per yak table; their per-round device counters live in fixed slots
         if (n_yak < 0 || n_yak > NP2_MAX_YAK || (n_yak && !yaks))
@@ -1734,9 +1740,9 @@ int np2_ctx_create(np2_ctx_t **out, int device, const np2_yak_t *yaks, int n_yak
             doff.ensure(1025);
             HIPCHK(hipMemcpyAsync(dw.p, y.words, y.n_words * 8, hipMemcpyHostToDevice, cx->stream));
             HIPCHK(hipMemcpyAsync(doff.p, y.bucket_off, 1025 * 8, hipMemcpyHostToDevice, cx->stream));
-            zero32(cx, cx->scal.p, S_COUNT);
+            zero32(cx.get(), cx->scal.p, S_COUNT);
             launch_yak_insert(cx->stream, dw.p, doff.p, 1024, mx, t.table->p, cl, cx->scal.p + S_DUP);
-            auto sc = d2h(cx, cx->scal.p, S_COUNT);
+            auto sc = d2h(cx.get(), cx->scal.p, S_COUNT);
             if (sc[S_DUP]) { // a repeated key (yak writes none): a slot per word, the winner chosen at lookup (kmer.rs:148-167)
                 t.ord = std::make_shared<DevBuf<uint32_t>>();
                 t.ord->ensure(slots);
@@ -1745,56 +1751,32 @@ int np2_ctx_create(np2_ctx_t **out, int device, const np2_yak_t *yaks, int n_yak
                 HIPCHK(hipStreamSynchronize(cx->stream)); // (dw / doff are released at the end of this scope)
             }
         }
-    } catch (const Np2Error &e) {
-        fprintf(stderr, "np2_ctx_create: %s\n", e.what());
-        int code = e.code;
-        destroy_streams(cx);
-        delete cx;
-        return code;
-    } catch (const std::exception &ex) {
-        fprintf(stderr, "np2_ctx_create: %s\n", ex.what());
-        int code = NP2_E_NOMEM;
-        destroy_streams(cx);
-        delete cx;
-        return code;
-    }
-    *out = cx;
-    return NP2_OK;
+        *out = cx.release();
+        return NP2_OK;
+    }, [](int, const std::string &msg) { fprintf(stderr, "np2_ctx_create: %s\n", msg.c_str()); });
 }
 
 int np2_ctx_create_shared(np2_ctx_t **out, np2_ctx_t *parent) {
     if (!out || !parent) return NP2_E_ARG;
     *out = nullptr;
-    np2_ctx *cx = new np2_ctx();
-    try {
-        init_ctx_device(cx, parent->device);
+    return abi_guard([&] {
+        CtxPtr cx(new np2_ctx());
+        init_ctx_device(cx.get(), parent->device);
         cx->yaks = parent->yaks; // the HBM tables are reference-counted: freed with the last context using them
         cx->tile_cap = parent->tile_cap;
-    } catch (const Np2Error &e) {
-        fprintf(stderr, "np2_ctx_create_shared: %s\n", e.what());
-        int code = e.code;
-        destroy_streams(cx);
-        delete cx;
-        return code;
-    }
-    *out = cx;
-    return NP2_OK;
+        *out = cx.release();
+        return NP2_OK;
+    }, [](int, const std::string &msg) { fprintf(stderr, "np2_ctx_create_shared: %s\n", msg.c_str()); });
 }
 
 } // extern "C"
 // a batch driver's slot: the tables shared with `parent`, the stream and the mailbox the driver's (np2_batch.cpp)
 np2_ctx *np2h::ctx_create_slot(np2_ctx *parent, hipStream_t s, uint32_t *mbox_host, uint32_t *mbox_dev) {
-    np2_ctx *cx = new np2_ctx();
-    try {
-        init_ctx_device(cx, parent->device, s, mbox_host, mbox_dev);
-        cx->yaks = parent->yaks;
-        cx->tile_cap = parent->tile_cap;
-    } catch (...) {
-        destroy_streams(cx);
-        delete cx;
-        throw;
-    }
-    return cx;
+    CtxPtr cx(new np2_ctx());
+    init_ctx_device(cx.get(), parent->device, s, mbox_host, mbox_dev);
+    cx->yaks = parent->yaks;
+    cx->tile_cap = parent->tile_cap;
+    return cx.release();
 }
 void np2h::ctx_slot_set_stream(np2_ctx *cx, hipStream_t s) {
     if (cx->borrowed_state) cx->stream = cx->stream_out = s;
@@ -1832,27 +1814,20 @@ int np2_contig_upload(np2_ctx_t *cx, const uint8_t *ref, uint32_t L, const np2_r
                       const uint8_t *nibbles, uint64_t nib_bytes, np2_contig_t **out) {
     if (!cx || !out) return NP2_E_ARG;
     *out = nullptr;
-    np2_contig *c = new np2_contig();
-    try {
+    std::unique_ptr<np2_contig> c; // (freed after the sink's sync: the nibble upload may still be in flight)
+    return abi_guard([&] {
         (void)ref;
         HIPCHK(hipSetDevice(cx->device));
         if (L < 3 || n_reads < 1 || !reads || !nibbles) throw Np2Error(NP2_E_ARG, "bad contig arguments");
+        c.reset(new np2_contig());
         c->nib.ensure(nib_bytes + 64);
         // (the caller's pageable buffer in one call: the runtime locks its pages and copies at the link's rate — 56 GB/s for
         // 32 MiB and more, tools/ubench_h2d.hip; a ring of pinned blocks filled by helper threads measured 38-51)
         HIPCHK(hipMemcpyAsync(c->nib.p, nibbles, nib_bytes, hipMemcpyHostToDevice, cx->stream));
-        finish_contig(cx, c, reads, n_reads, L, nib_bytes);
-    } catch (const Np2Error &e) {
-        (void)hipStreamSynchronize(cx->stream); // (the nibble upload may still be in flight: the blocks go back to the cache)
-        delete c;
-        return fail(cx, e);
-    } catch (const std::exception &ex) {
-        (void)hipStreamSynchronize(cx->stream);
-        delete c;
-        return fail(cx, Np2Error(NP2_E_NOMEM, std::string("unexpected exception: ") + ex.what()));
-    }
-    *out = c;
-    return NP2_OK;
+        finish_contig(cx, c.get(), reads, n_reads, L, nib_bytes);
+        *out = c.release();
+        return NP2_OK;
+    }, ctx_sink(cx));
 }
 void np2_contig_free(np2_ctx_t *cx, np2_contig_t *c) {
     if (cx) (void)hipSetDevice(cx->device);
@@ -1866,23 +1841,16 @@ int np2_polish_resident(np2_ctx_t *cx, np2_contig_t *c, const np2_opts_t *opts, 
     r.want_pos = out_pos != nullptr;
     r.want_bases = out_bases != nullptr;
     const double t_wall0 = now_ms(), t_cpu0 = thread_cpu_ms();
-    try {
+    const int rc = abi_guard([&] {
         polish_impl(cx, c, opts, r);
         cx->timing.host.push_back({"wall_polish", (float)(now_ms() - t_wall0)});
         cx->timing.host.push_back({"cpu_polish", (float)(thread_cpu_ms() - t_cpu0)});
         flush_timings(cx);
-    } catch (const Np2Error &e) {
-        (void)hipStreamSynchronize(cx->stream);
-        flush_timings(cx);
-        if (r.bases) pinned_pool().put(r.bases);
-        if (r.pos) pinned_pool().put(r.pos);
-        return fail(cx, e);
-    } catch (const std::exception &ex) {
-        (void)hipStreamSynchronize(cx->stream);
-        flush_timings(cx);
-        if (r.bases) pinned_pool().put(r.bases);
-        if (r.pos) pinned_pool().put(r.pos);
-        return fail(cx, Np2Error(NP2_E_NOMEM, std::string("unexpected exception: ") + ex.what()));
+        return NP2_OK;
+    }, ctx_sink(cx, true));
+    if (rc != NP2_OK) {
+        r.release();
+        return rc;
     }
     *out_len = r.len;
     if (out_bases) *out_bases = r.bases;
@@ -1892,7 +1860,7 @@ int np2_polish_resident(np2_ctx_t *cx, np2_contig_t *c, const np2_opts_t *opts, 
 
 int np2_result_fetch_begin(np2_ctx_t *cx) {
     if (!cx || !cx->last_dbase || cx->out_pending) return NP2_E_ARG;
-    try {
+    return abi_guard([&] {
         HIPCHK(hipSetDevice(cx->device));
         const size_t n = cx->last_len;
         cx->out_snap.ensure(n + 1);
@@ -1914,24 +1882,20 @@ int np2_result_fetch_begin(np2_ctx_t *cx) {
         HIPCHK(hipMemcpyAsync(host, cx->out_snap.p, n, hipMemcpyDeviceToHost, cx->stream_out));
         cx->out_len = n;
         cx->out_pending = true;
-    } catch (const Np2Error &e) {
-        return fail(cx, e);
-    }
-    return NP2_OK;
+        return NP2_OK;
+    }, ctx_sink(cx));
 }
 
 int np2_result_fetch_end(np2_ctx_t *cx, const uint8_t **bases, uint64_t *len) {
     if (!cx || !bases || !len || !cx->out_pending) return NP2_E_ARG;
-    try {
+    return abi_guard([&] {
         HIPCHK(hipStreamSynchronize(cx->stream_out));
-    } catch (const Np2Error &e) {
-        return fail(cx, e);
-    }
-    *bases = cx->out_host[cx->out_slot];
-    *len = cx->out_len;
-    cx->out_slot ^= 1;
-    cx->out_pending = false;
-    return NP2_OK;
+        *bases = cx->out_host[cx->out_slot];
+        *len = cx->out_len;
+        cx->out_slot ^= 1;
+        cx->out_pending = false;
+        return NP2_OK;
+    }, ctx_sink(cx));
 }
 
 int np2_polish_contig(np2_ctx_t *cx, const uint8_t *ref, uint32_t L, const np2_read_t *reads, uint32_t n_reads,
@@ -1952,7 +1916,7 @@ void np2_free(void *p) {
 int np2_score_strings(np2_ctx_t *cx, int yak_idx, const uint8_t *strs, const uint64_t *off, uint64_t n,
                       uint16_t min_kmer_count, uint16_t *scores) {
     if (!cx || yak_idx < 0 || (size_t)yak_idx >= cx->yaks.size()) return NP2_E_ARG;
-    try {
+    return abi_guard([&] {
         HIPCHK(hipSetDevice(cx->device));
         std::vector<uint8_t> blob(strs, strs + off[n]);
         blob.resize(blob.size() + 8, 0);
@@ -1961,18 +1925,14 @@ int np2_score_strings(np2_ctx_t *cx, int yak_idx, const uint8_t *strs, const uin
         gpu_score_strings(cx, yak_idx, blob, o, min_kmer_count, sc);
         memcpy(scores, sc.data(), n * 2);
         flush_timings(cx);
-    } catch (const Np2Error &e) {
-        return fail(cx, e);
-    } catch (const std::exception &ex) {
-        return fail(cx, Np2Error(NP2_E_NOMEM, std::string("unexpected exception: ") + ex.what()));
-    }
-    return NP2_OK;
+        return NP2_OK;
+    }, ctx_sink(cx));
 }
 
 int np2_lookup_hashes(np2_ctx_t *cx, int yak_idx, const uint64_t *hashes, uint64_t n, uint16_t min_kmer_count,
                       uint16_t *counts) {
     if (!cx || yak_idx < 0 || (size_t)yak_idx >= cx->yaks.size()) return NP2_E_ARG;
-    try {
+    return abi_guard([&] {
         HIPCHK(hipSetDevice(cx->device));
         cx->soff.ensure(n + 1);
         cx->sscore.ensure(n + 1);
@@ -1980,12 +1940,8 @@ int np2_lookup_hashes(np2_ctx_t *cx, int yak_idx, const uint64_t *hashes, uint64
         launch_lookup(cx->stream, cx->yaks[yak_idx].dev(), cx->soff.p, n, min_kmer_count, cx->sscore.p);
         HIPCHK(hipMemcpyAsync(counts, cx->sscore.p, n * 2, hipMemcpyDeviceToHost, cx->stream));
         HIPCHK(hipStreamSynchronize(cx->stream));
-    } catch (const Np2Error &e) {
-        return fail(cx, e);
-    } catch (const std::exception &ex) {
-        return fail(cx, Np2Error(NP2_E_NOMEM, std::string("unexpected exception: ") + ex.what()));
-    }
-    return NP2_OK;
+        return NP2_OK;
+    }, ctx_sink(cx));
 }
 
 int np2_last_span(np2_ctx_t *cx, uint32_t *first_pos, uint32_t *last_pos) {
@@ -2007,60 +1963,62 @@ int np2_phase_vote(const uint32_t *keys, uint32_t n_keys, const uint32_t *pa, co
                    uint64_t n_pairs, const uint32_t *ref_ids, const float *ref_w, uint32_t n_ref, int has_ref,
                    uint32_t *out_ids, uint32_t *n_out) {
     if (!keys || !out_ids || !n_out) return NP2_E_ARG;
-    try {
-    uint32_t mx = 0;
-    for (uint32_t i = 0; i < n_keys; ++i) mx = std::max(mx, keys[i]);
-    for (uint32_t i = 0; i < n_ref; ++i) mx = std::max(mx, ref_ids[i]);
-    phase::Graph g;
-    g.reserve_ids(mx + 1);
-    for (uint32_t i = 0; i < n_keys; ++i) g.add_key(keys[i]);
-    if (!g.add_edges(n_pairs, [&](uint64_t i) { return pa[i]; }, [&](uint64_t i) { return pb[i]; },
-                     [&](uint64_t i) { return pw[i]; }))
-        return NP2_E_ARG;
-    std::vector<float> rw(mx + 1, 0.f);
-    std::vector<uint8_t> rs(mx + 1, 0);
-    for (uint32_t i = 0; i < n_ref; ++i) {
-        rw[ref_ids[i]] = ref_w[i];
-        rs[ref_ids[i]] = 1;
-    }
-    std::vector<uint32_t> losers;
-    if (!phase::losing_reads(std::move(g), has_ref != 0, rw, rs, losers)) return NP2_E_REFPANIC;
-    std::sort(losers.begin(), losers.end());
-    losers.erase(std::unique(losers.begin(), losers.end()), losers.end());
-    *n_out = (uint32_t)losers.size();
-    for (size_t i = 0; i < losers.size(); ++i) out_ids[i] = losers[i];
-    } catch (const std::exception &) {
-        return NP2_E_NOMEM;
-    }
-    return NP2_OK;
+    return abi_guard([&] {
+        uint32_t mx = 0;
+        for (uint32_t i = 0; i < n_keys; ++i) mx = std::max(mx, keys[i]);
+        for (uint32_t i = 0; i < n_ref; ++i) mx = std::max(mx, ref_ids[i]);
+        phase::Graph g;
+        g.reserve_ids(mx + 1);
+        for (uint32_t i = 0; i < n_keys; ++i) g.add_key(keys[i]);
+        if (!g.add_edges(n_pairs, [&](uint64_t i) { return pa[i]; }, [&](uint64_t i) { return pb[i]; },
+                         [&](uint64_t i) { return pw[i]; }))
+            return NP2_E_ARG;
+        std::vector<float> rw(mx + 1, 0.f);
+        std::vector<uint8_t> rs(mx + 1, 0);
+        for (uint32_t i = 0; i < n_ref; ++i) {
+            rw[ref_ids[i]] = ref_w[i];
+            rs[ref_ids[i]] = 1;
+        }
+        std::vector<uint32_t> losers;
+        if (!phase::losing_reads(std::move(g), has_ref != 0, rw, rs, losers)) return NP2_E_REFPANIC;
+        std::sort(losers.begin(), losers.end());
+        losers.erase(std::unique(losers.begin(), losers.end()), losers.end());
+        *n_out = (uint32_t)losers.size();
+        for (size_t i = 0; i < losers.size(); ++i) out_ids[i] = losers[i];
+        return NP2_OK;
+    });
 }
 
 // host-only test hook: iteration order of the product's SwissTable order model (np2_phase_host.hpp) after a script of
 // op 0 = insert(key), 1 = remove(key), 2 = entry(key).or_insert — checked against hand-traced vectors
 int np2_swiss_order(const uint32_t *ops, const uint32_t *keys, uint32_t n, uint32_t *out, uint32_t *n_out) {
     if (!ops || !keys || !out || !n_out) return NP2_E_ARG;
-    phase::SwissOrderMap<int> m;
-    for (uint32_t i = 0; i < n; ++i) {
-        if (ops[i] == 0)
-            m.put(keys[i], 0);
-        else if (ops[i] == 1)
-            m.take(keys[i], nullptr);
-        else if (!m.has(keys[i]))
-            m.put_vacant(keys[i], 0);
-    }
-    uint32_t c = 0;
-    m.each([&](uint32_t k, const int &) { out[c++] = k; });
-    *n_out = c;
-    return NP2_OK;
+    return abi_guard([&] {
+        phase::SwissOrderMap<int> m;
+        for (uint32_t i = 0; i < n; ++i) {
+            if (ops[i] == 0)
+                m.put(keys[i], 0);
+            else if (ops[i] == 1)
+                m.take(keys[i], nullptr);
+            else if (!m.has(keys[i]))
+                m.put_vacant(keys[i], 0);
+        }
+        uint32_t c = 0;
+        m.each([&](uint32_t k, const int &) { out[c++] = k; });
+        *n_out = c;
+        return NP2_OK;
+    });
 }
 
 int np2_trace_get(np2_ctx_t *cx, int pass, const char *name, const void **data, uint64_t *nbytes) {
     if (!cx) return NP2_E_ARG;
-    auto it = cx->trace_items.find(std::to_string(pass) + ":" + name);
-    if (it == cx->trace_items.end()) return NP2_E_ARG;
-    *data = it->second.data();
-    *nbytes = it->second.size();
-    return NP2_OK;
+    return abi_guard([&] {
+        auto it = cx->trace_items.find(std::to_string(pass) + ":" + name);
+        if (it == cx->trace_items.end()) return NP2_E_ARG;
+        *data = it->second.data();
+        *nbytes = it->second.size();
+        return NP2_OK;
+    }, ctx_sink(cx));
 }
 
 int np2_last_timings(np2_ctx_t *cx, const char **names, const float **ms, int *n) {
@@ -2110,7 +2068,7 @@ int np2_shard_upload(np2_ctx_t *cx, const uint8_t *ref, uint32_t L, const np2_re
                      const uint8_t *nibbles, uint64_t nib_bytes, const np2_shard_plan_t *pl, np2_contig_t **out) {
     if (!cx || !ref || !reads || !nibbles || !pl || !out) return NP2_E_ARG;
     *out = nullptr;
-    try {
+    return abi_guard([&] {
         if (pl->sub_hi > L || pl->sub_lo >= pl->sub_hi || pl->read_hi > n_reads || pl->read_lo < 1 || pl->read_lo > pl->read_hi)
             throw Np2Error(NP2_E_ARG, "shard plan does not fit the contig");
         const uint32_t Ls = pl->sub_hi - pl->sub_lo, n = 1 + (pl->read_hi - pl->read_lo);
@@ -2154,11 +2112,7 @@ int np2_shard_upload(np2_ctx_t *cx, const uint8_t *ref, uint32_t L, const np2_re
             d.nib_off = ref_bytes + (g.nib_off - lo);
         }
         return np2_contig_upload(cx, ref + pl->sub_lo, Ls, rds.data(), n, host.data(), total, out);
-    } catch (const Np2Error &e) {
-        return fail(cx, e);
-    } catch (const std::exception &ex) {
-        return fail(cx, Np2Error(NP2_E_NOMEM, std::string("unexpected exception: ") + ex.what()));
-    }
+    }, ctx_sink(cx));
 }
 
 // a block of the process-wide pinned pool for one read-back
@@ -2175,39 +2129,24 @@ struct PinnedBlock {
     PinnedBlock &operator=(const PinnedBlock &) = delete;
 };
 
-#define NP2_SHARD_TRY(cxp, ...)                                                                      \
-    try {                                                                                            \
-        __VA_ARGS__                                                                                  \
-    } catch (const Np2Error &e) {                                                                    \
-        (void)hipStreamSynchronize((cxp)->stream);                                                   \
-        return fail((cxp), e);                                                                       \
-    } catch (const std::exception &ex) {                                                             \
-        (void)hipStreamSynchronize((cxp)->stream);                                                   \
-        return fail((cxp), Np2Error(NP2_E_NOMEM, std::string("unexpected exception: ") + ex.what())); \
-    }
-
 int np2_shard_begin(np2_ctx_t *cx, np2_contig_t *c, const np2_shard_plan_t *pl, const np2_opts_t *opts, uint32_t verify,
                     np2_shard_run_t **out) {
     if (!cx || !c || !pl || !opts || !out) return NP2_E_ARG;
     *out = nullptr;
-    ShardRun *sr = new ShardRun();
-    sr->plan = *pl;
-    sr->verify = verify;
-    sr->run.cx = cx, sr->run.c = c, sr->run.o = *opts;
-    sr->run.own_lo = pl->own_lo - pl->sub_lo;
-    sr->run.own_hi = pl->own_hi - pl->sub_lo;
-    sr->run.wide_votes = true; // (exported as np2_vote_t and merged with the other shards')
-    try {
+    return abi_guard([&] {
+        std::unique_ptr<ShardRun> sr(new ShardRun());
+        sr->plan = *pl;
+        sr->verify = verify;
+        sr->run.cx = cx, sr->run.c = c, sr->run.o = *opts;
+        sr->run.own_lo = pl->own_lo - pl->sub_lo;
+        sr->run.own_hi = pl->own_hi - pl->sub_lo;
+        sr->run.wide_votes = true; // (exported as np2_vote_t and merged with the other shards')
         if (c->L != pl->sub_hi - pl->sub_lo || c->R != 1 + (pl->read_hi - pl->read_lo))
             throw Np2Error(NP2_E_ARG, "contig is not the upload of this shard plan");
         run_begin(sr->run);
-    } catch (const Np2Error &e) {
-        delete sr;
-        (void)hipStreamSynchronize(cx->stream);
-        return fail(cx, e);
-    }
-    *out = (np2_shard_run_t *)sr;
-    return NP2_OK;
+        *out = (np2_shard_run_t *)sr.release();
+        return NP2_OK;
+    }, ctx_sink(cx));
 }
 void np2_shard_end(np2_shard_run_t *h) { delete (ShardRun *)h; }
 int np2_shard_passes_left(np2_shard_run_t *h) {
@@ -2219,7 +2158,7 @@ int np2_shard_vote(np2_shard_run_t *h, np2_vote_t *out) {
     ShardRun *sr = (ShardRun *)h;
     if (!sr || !out || sr->run.final_pass()) return NP2_E_ARG;
     np2_ctx *cx = sr->run.cx;
-    NP2_SHARD_TRY(cx, {
+    return abi_guard([&] {
         VoteData vd;
         const np2_shard_plan_t &pl = sr->plan;
         // (local read i >= 1 is contig read read_lo + i - 1 and read 0 never enters a pair: one 64-bit add renumbers both
@@ -2298,14 +2237,14 @@ int np2_shard_vote(np2_shard_run_t *h, np2_vote_t *out) {
         }
         if (cx->hooks.shard_spec_log)
             fprintf(stderr, "[np2 shard] vote: any %d, flags on the device %d, early start %d (%zu flagged)\n", (int)vd.any, vd.d_bad != nullptr, (int)sr->spec, sr->spec_n_bad);
-    })
-    return NP2_OK;
+        return NP2_OK;
+    }, ctx_sink(cx));
 }
 
 int np2_vote_decide(const np2_vote_t *votes, int n_votes, uint32_t n_reads_total, const np2_opts_t *opts, uint32_t *losers,
                     uint32_t *n_losers) {
     if (!votes || n_votes < 1 || !opts || !losers || !n_losers) return NP2_E_ARG;
-    try {
+    return abi_guard([&] {
         VoteData vd;
         vd.R = n_reads_total;
         vd.first_key.assign(n_reads_total, 0xFFFFFFFFu);
@@ -2431,19 +2370,15 @@ int np2_vote_decide(const np2_vote_t *votes, int n_votes, uint32_t n_reads_total
         std::vector<uint32_t> ls = vote_decide(nullptr, vd, opts->use_all_reads != 0);
         *n_losers = (uint32_t)ls.size();
         for (size_t i = 0; i < ls.size(); ++i) losers[i] = ls[i];
-    } catch (const Np2Error &e) {
-        return e.code;
-    } catch (const std::exception &) {
-        return NP2_E_NOMEM;
-    }
-    return NP2_OK;
+        return NP2_OK;
+    });
 }
 
 int np2_shard_apply(np2_shard_run_t *h, const uint32_t *losers, uint32_t n) {
     ShardRun *sr = (ShardRun *)h;
     if (!sr || (n && !losers) || (sr->run.final_pass() && !sr->spec)) return NP2_E_ARG; // (a pass started early has advanced the counter)
     np2_ctx *cx = sr->run.cx;
-    NP2_SHARD_TRY(cx, {
+    return abi_guard([&] {
         std::vector<uint32_t> local;
         const np2_shard_plan_t &pl = sr->plan;
         for (uint32_t i = 0; i < n; ++i) {
@@ -2490,8 +2425,8 @@ int np2_shard_apply(np2_shard_run_t *h, const uint32_t *losers, uint32_t n) {
         run_apply_losers(sr->run, local);
         if (n) sr->run.reuse = false;
         (void)n_reg;
-    })
-    return NP2_OK;
+        return NP2_OK;
+    }, ctx_sink(cx));
 }
 
 int np2_shard_final(np2_shard_run_t *h, uint8_t **out_bases, uint32_t **out_pos, uint64_t *out_len) {
@@ -2499,16 +2434,7 @@ int np2_shard_final(np2_shard_run_t *h, uint8_t **out_bases, uint32_t **out_pos,
     if (!sr || !out_bases || !out_pos || !out_len || !sr->run.final_pass()) return NP2_E_ARG;
     np2_ctx *cx = sr->run.cx;
     ResultOut r;
-    struct PutBack { // the pinned result blocks go back to the pool unless they are handed to the caller
-        ResultOut &r;
-        bool keep = false;
-        ~PutBack() {
-            if (keep) return;
-            if (r.bases) pinned_pool().put(r.bases);
-            if (r.pos) pinned_pool().put(r.pos);
-        }
-    } guard{r};
-    NP2_SHARD_TRY(cx, {
+    const int rc = abi_guard([&] {
         run_final_pass(sr->run, r);
         const np2_shard_plan_t &pl = sr->plan;
         shard_check_stuck(sr);
@@ -2524,8 +2450,12 @@ int np2_shard_final(np2_shard_run_t *h, uint8_t **out_bases, uint32_t **out_pos,
             ++w;
         }
         r.len = w;
-    })
-    guard.keep = true;
+        return NP2_OK;
+    }, ctx_sink(cx));
+    if (rc != NP2_OK) {
+        r.release();
+        return rc;
+    }
     *out_bases = r.bases;
     *out_pos = r.pos;
     *out_len = r.len;
@@ -2540,17 +2470,8 @@ int np2_shard_final_device(np2_shard_run_t *h, np2_shard_piece_t *out) {
     if (!sr || !out || !sr->run.final_pass()) return NP2_E_ARG;
     np2_ctx *cx = sr->run.cx;
     memset(out, 0, sizeof *out);
-    void *blocks[4] = {nullptr, nullptr, nullptr, nullptr};
-    struct PutBack {
-        void **b;
-        bool keep = false;
-        ~PutBack() {
-            if (!keep)
-                for (int i = 0; i < 4; ++i)
-                    if (b[i]) pinned_pool().put(b[i]);
-        }
-    } guard{blocks};
-    NP2_SHARD_TRY(cx, {
+    void *blocks[4] = {nullptr, nullptr, nullptr, nullptr}; // (the pinned strips: given back unless handed out)
+    const int rc = abi_guard([&] {
         ResultOut r;
         r.want_bases = false, r.want_pos = false; // the polished sub-contig stays on the device
         run_final_pass(sr->run, r);
@@ -2596,16 +2517,19 @@ int np2_shard_final_device(np2_shard_run_t *h, np2_shard_piece_t *out) {
         for (uint32_t i = 0; i < out->lo_len; ++i) out->lo_pos[i] += pl.sub_lo;
         for (uint32_t i = 0; i < out->hi_len; ++i) out->hi_pos[i] += pl.sub_lo;
         flush_timings(cx); // (np2_last_timings: the stage timers of the whole run, the dense pass of np2_shard_begin included)
-    })
-    guard.keep = true;
-    return NP2_OK;
+        return NP2_OK;
+    }, ctx_sink(cx));
+    if (rc != NP2_OK)
+        for (void *p : blocks)
+            if (p) pinned_pool().put(p);
+    return rc;
 }
 
 int np2_shard_fetch(np2_shard_run_t *h, uint8_t *dst_bases, uint32_t *dst_pos) {
     ShardRun *sr = (ShardRun *)h;
     if (!sr || !dst_bases || !sr->have_piece) return NP2_E_ARG;
     np2_ctx *cx = sr->run.cx;
-    NP2_SHARD_TRY(cx, {
+    return abi_guard([&] {
         HIPCHK(hipSetDevice(cx->device));
         if (!cx->last_dbase) throw Np2Error(NP2_E_ARG, "the shard's device result is gone (another call used its context)");
         if (sr->own_len) {
@@ -2618,7 +2542,7 @@ int np2_shard_fetch(np2_shard_run_t *h, uint8_t *dst_bases, uint32_t *dst_pos) {
                     for (uint64_t i = 0; i < sr->own_len; ++i) dst_pos[i] += add;
             }
         }
-    })
-    return NP2_OK;
+        return NP2_OK;
+    }, ctx_sink(cx));
 }
 }

@@ -555,6 +555,19 @@ struct BgzfBatch {
 uint32_t le32(const uint8_t *p) { return p[0] | (p[1] << 8) | (p[2] << 16) | ((uint32_t)p[3] << 24); }
 uint64_t le64(const uint8_t *p) { return (uint64_t)le32(p) | ((uint64_t)le32(p + 4) << 32); }
 
+// reference bases a CIGAR of n operations covers (M, D, N, =, X); given as words or as a record's little-endian bytes
+inline uint32_t cigar_word(const uint32_t *cigar, uint32_t k) { return cigar[k]; }
+inline uint32_t cigar_word(const uint8_t *cigar, uint32_t k) { return le32(cigar + 4 * k); }
+template <class T>
+uint64_t ref_span(const T *cigar, uint32_t n) {
+    uint64_t span = 0;
+    for (uint32_t k = 0; k < n; ++k) {
+        const uint32_t w = cigar_word(cigar, k), op = w & 15;
+        if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) span += w >> 4;
+    }
+    return span;
+}
+
 } // namespace
 
 // std::vector storage in pinned host memory: the SEQ bytes gathered from the BAM go to the GPU by DMA straight from
@@ -608,6 +621,9 @@ struct PinnedBytes {
 
 struct np2_fasta {
     Fasta f;
+    ~np2_fasta() {
+        if (f.f) gzclose(f.f);
+    }
 };
 struct SecSeq { // SEQ of a primary alignment in read orientation (4-bit BAM codes, high nibble first)
     std::vector<uint8_t> seq4;
@@ -1181,12 +1197,7 @@ void fetch_records(np2_bam *bam, int tid, uint32_t L, uint32_t zone_lo, uint32_t
                         const uint32_t nc = rec[12] | (rec[13] << 8);
                         const uint8_t *pc0 = rec + 32 + rec[8];
                         if ((size_t)32 + rec[8] + (size_t)nc * 4 > bs) throw np2h::Np2Error(NP2_E_ARG, "BAM/SAM parsing failed!");
-                        uint64_t span = 0;
-                        for (uint32_t k = 0; k < nc; ++k) {
-                            const uint32_t w = le32(pc0 + 4 * k), op = w & 15;
-                            if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) span += w >> 4;
-                        }
-                        take = (uint64_t)pos + span > zone_lo;
+                        take = (uint64_t)pos + ref_span(pc0, nc) > zone_lo;
                     }
                     if (take) {
                         RecRef r;
@@ -1332,112 +1343,84 @@ const char *np2_io_last_error(void) { return g_io_err.c_str(); }
 
 // ---- FASTA ---------------------------------------------------------------------------------------
 int np2_fasta_open(const char *path, np2_fasta_t **out) {
-    np2_fasta *h = new np2_fasta();
-    h->f.f = gzopen(path, "rb");
-    if (!h->f.f) {
-        delete h;
-        return io_fail(NP2_E_ARG, std::string("cannot open ") + path);
-    }
-    gzbuffer(h->f.f, 1 << 20);
-    h->f.buf.resize(1 << 16);
-    std::string line;
-    while (h->f.getline(line)) // skip to the first header
-        if (!line.empty() && line[0] == '>') {
-            h->f.pending = line;
-            break;
+    return np2h::abi_guard([&] {
+        std::unique_ptr<np2_fasta> h(new np2_fasta());
+        h->f.f = gzopen(path, "rb");
+        if (!h->f.f) return io_fail(NP2_E_ARG, std::string("cannot open ") + path);
+        gzbuffer(h->f.f, 1 << 20);
+        h->f.buf.resize(1 << 16);
+        std::string line;
+        while (h->f.getline(line)) // skip to the first header
+            if (!line.empty() && line[0] == '>') {
+                h->f.pending = line;
+                break;
+            }
+        *out = h.release();
+        return NP2_OK;
+    }, io_fail);
+}
+int np2_fasta_next(np2_fasta_t *h, const char **name, const uint8_t **seq, uint64_t *len) {
+    return np2h::abi_guard([&] {
+        Fasta &f = h->f;
+        if (f.pending.empty()) return 0;
+        size_t e = 1;
+        while (e < f.pending.size() && !isspace((unsigned char)f.pending[e])) ++e;
+        f.name = f.pending.substr(1, e - 1);
+        f.pending.clear();
+        f.seq.clear();
+        std::string line;
+        while (f.getline(line)) {
+            if (!line.empty() && line[0] == '>') {
+                f.pending = line;
+                break;
+            }
+            f.seq += line;
         }
-    *out = h;
-    return NP2_OK;
+        *name = f.name.c_str();
+        *seq = (const uint8_t *)f.seq.data();
+        *len = f.seq.size();
+        return 1;
+    }, io_fail);
 }
-int np2_fasta_next(np2_fasta_t *h, const char **name, const uint8_t **seq, uint64_t *len) try {
-    Fasta &f = h->f;
-    if (f.pending.empty()) return 0;
-    size_t e = 1;
-    while (e < f.pending.size() && !isspace((unsigned char)f.pending[e])) ++e;
-    f.name = f.pending.substr(1, e - 1);
-    f.pending.clear();
-    f.seq.clear();
-    std::string line;
-    while (f.getline(line)) {
-        if (!line.empty() && line[0] == '>') {
-            f.pending = line;
-            break;
-        }
-        f.seq += line;
-    }
-    *name = f.name.c_str();
-    *seq = (const uint8_t *)f.seq.data();
-    *len = f.seq.size();
-    return 1;
-} catch (const std::exception &ex) {
-    return io_fail(NP2_E_NOMEM, std::string("unexpected exception: ") + ex.what());
-}
-void np2_fasta_close(np2_fasta_t *h) {
-    if (!h) return;
-    if (h->f.f) gzclose(h->f.f);
-    delete h;
-}
+void np2_fasta_close(np2_fasta_t *h) { delete h; }
 
 // ---- yak v2 (kmer.rs:72-170) -----------------------------------------------------------------------
-int np2_yak_load(const char *path, np2_yak_t *out) try {
-    FILE *f = fopen(path, "rb");
-    if (!f) return io_fail(NP2_E_ARG, std::string("cannot open ") + path);
-    uint8_t hd[16];
-    if (fread(hd, 1, 16, f) != 16 || memcmp(hd, "YAK\2", 4) != 0) {
-        fclose(f);
-        return io_fail(NP2_E_ARG, "The input binary k-mer dump file is incompatible.");
-    }
-    const uint32_t k = le32(hd + 4), pre = le32(hd + 8), cbits = le32(hd + 12);
-    if (cbits != 10) {
-        fclose(f);
-        return io_fail(NP2_E_ARG, "different YAK_COUNTER_BITS");
-    }
-    if (pre > 20) {
-        fclose(f);
-        return io_fail(NP2_E_UNSUPPORTED, "yak prefix bits too large");
-    }
-    const size_t nb = (size_t)1 << pre;
-    // every word of the file is read ONCE, straight into the array that is handed out (the file's size bounds it): a
-    // human-scale dump is tens of GB, and the command line loads its dumps while the first contigs are being read
-    struct stat st;
-    if (fstat(fileno(f), &st) != 0) {
-        fclose(f);
-        return io_fail(NP2_E_ARG, std::string("cannot stat ") + path);
-    }
-    const size_t max_words = (size_t)st.st_size / 8 + 1;
-    uint64_t *w = (uint64_t *)malloc(max_words * 8);
-    uint64_t *off = (uint64_t *)malloc((nb + 1) * 8);
-    if (!w || !off) {
-        fclose(f);
-        free(w);
-        free(off);
-        return io_fail(NP2_E_NOMEM, "out of memory loading the k-mer dump");
-    }
-    off[0] = 0;
-    size_t have = 0;
-    for (size_t b = 0; b < nb; ++b) {
-        uint8_t h8[8];
-        if (fread(h8, 1, 8, f) != 8) {
-            fclose(f);
-            free(off);
-            free(w);
-            return io_fail(NP2_E_ARG, "Failed to parse the dump file");
+int np2_yak_load(const char *path, np2_yak_t *out) {
+    return np2h::abi_guard([&] {
+        std::unique_ptr<FILE, int (*)(FILE *)> f(fopen(path, "rb"), fclose);
+        if (!f) return io_fail(NP2_E_ARG, std::string("cannot open ") + path);
+        uint8_t hd[16];
+        if (fread(hd, 1, 16, f.get()) != 16 || memcmp(hd, "YAK\2", 4) != 0)
+            return io_fail(NP2_E_ARG, "The input binary k-mer dump file is incompatible.");
+        const uint32_t k = le32(hd + 4), pre = le32(hd + 8), cbits = le32(hd + 12);
+        if (cbits != 10) return io_fail(NP2_E_ARG, "different YAK_COUNTER_BITS");
+        if (pre > 20) return io_fail(NP2_E_UNSUPPORTED, "yak prefix bits too large");
+        const size_t nb = (size_t)1 << pre;
+        // every word of the file is read ONCE, straight into the array that is handed out (the file's size bounds it): a
+        // human-scale dump is tens of GB, and the command line loads its dumps while the first contigs are being read
+        struct stat st;
+        if (fstat(fileno(f.get()), &st) != 0) return io_fail(NP2_E_ARG, std::string("cannot stat ") + path);
+        const size_t max_words = (size_t)st.st_size / 8 + 1;
+        std::unique_ptr<uint64_t, void (*)(void *)> w((uint64_t *)malloc(max_words * 8), free), off((uint64_t *)malloc((nb + 1) * 8), free);
+        if (!w || !off) return io_fail(NP2_E_NOMEM, "out of memory loading the k-mer dump");
+        off.get()[0] = 0;
+        size_t have = 0;
+        for (size_t b = 0; b < nb; ++b) {
+            uint8_t h8[8];
+            if (fread(h8, 1, 8, f.get()) != 8) return io_fail(NP2_E_ARG, "Failed to parse the dump file");
+            const uint32_t n = le32(h8 + 4); // first u32 (capacity bits) is ignored like the reference (kmer.rs:143-147)
+            const size_t want = std::min<size_t>(n, max_words - have);
+            const size_t got = fread(w.get() + have, 8, want, f.get());
+            have += got; // UnexpectedEof ends the bucket (kmer.rs:151-155)
+            off.get()[b + 1] = have;
         }
-        const uint32_t n = le32(h8 + 4); // first u32 (capacity bits) is ignored like the reference (kmer.rs:143-147)
-        const size_t want = std::min<size_t>(n, max_words - have);
-        const size_t got = fread(w + have, 8, want, f);
-        have += got; // UnexpectedEof ends the bucket (kmer.rs:151-155)
-        off[b + 1] = have;
-    }
-    fclose(f);
-    out->k = k;
-    out->pre = pre;
-    out->n_words = have;
-    out->words = w;
-    out->bucket_off = off;
-    return NP2_OK;
-} catch (const std::exception &ex) {
-    return io_fail(NP2_E_NOMEM, std::string("unexpected exception: ") + ex.what());
+        out->k = k;
+        out->pre = pre;
+        out->n_words = have;
+        out->words = w.release();
+        out->bucket_off = off.release();
+        return NP2_OK;
+    }, io_fail);
 }
 void np2_yak_free(np2_yak_t *y) {
     if (!y) return;
@@ -1585,60 +1568,56 @@ void yak_file_to_table(YakFile &yf, int device, hipStream_t given) {
 }
 } // namespace
 
-int np2_ctx_create_from_files(np2_ctx_t **out, int device, const char *const *paths, int n_paths) try {
+int np2_ctx_create_from_files(np2_ctx_t **out, int device, const char *const *paths, int n_paths) {
     if (!out) return NP2_E_ARG;
     *out = nullptr;
-    if (n_paths < 0 || n_paths > NP2_MAX_YAK || (n_paths && !paths)) return io_fail(NP2_E_ARG, "n_yak must be in [0, 15]");
-    std::vector<std::unique_ptr<YakFile>> files;
-    for (int i = 0; i < n_paths; ++i) {
-        std::unique_ptr<YakFile> yf(new YakFile());
-        yf->path = paths[i];
-        yf->fd = open(paths[i], O_RDONLY);
-        if (yf->fd < 0) return io_fail(NP2_E_ARG, std::string("cannot open ") + paths[i]);
-        struct stat st;
-        uint8_t hd[16];
-        if (fstat(yf->fd, &st) != 0) return io_fail(NP2_E_ARG, std::string("cannot stat ") + paths[i]);
-        yf->size = (size_t)st.st_size;
-        if (pread(yf->fd, hd, 16, 0) != 16 || memcmp(hd, "YAK\2", 4) != 0)
-            return io_fail(NP2_E_ARG, "The input binary k-mer dump file is incompatible.");
-        yf->k = le32(hd + 4), yf->pre = le32(hd + 8);
-        if (le32(hd + 12) != 10) return io_fail(NP2_E_ARG, "different YAK_COUNTER_BITS");
-        if (yf->k >= 32 || yf->k < 2) return io_fail(NP2_E_UNSUPPORTED, "yak k must be in [2, 32) (main.rs:1433-1434)");
-        if (yf->pre != 10) return io_fail(NP2_E_UNSUPPORTED, "yak pre must be 10 (kmer.rs:52-54,123-125)");
-        files.push_back(std::move(yf));
-    }
-    std::stable_sort(files.begin(), files.end(), [](const std::unique_ptr<YakFile> &a, const std::unique_ptr<YakFile> &b) { return a->k < b->k; }); // option.rs:238
-    np2_ctx_t *cx = nullptr;
-    const int rc = np2_ctx_create(&cx, device, nullptr, 0);
-    if (rc != NP2_OK) return io_fail(rc, "np2_ctx_create failed (see stderr)");
-    {
-        std::vector<std::thread> th;
-        hipStream_t own[2] = {cx->stream, cx->stream_out}; // idle until the context's first call
-        for (size_t i = 1; i < files.size(); ++i)
-            th.emplace_back([&, i] { yak_file_to_table(*files[i], device, i < 2 ? own[i] : nullptr); });
-        if (!files.empty()) yak_file_to_table(*files[0], device, own[0]);
-        for (auto &t : th) t.join();
-    }
-    for (auto &yf : files)
-        if (yf->code != NP2_OK) {
-            const int code = yf->code;
-            const std::string msg = yf->path + ": " + yf->msg;
-            files.clear(); // (tables released before the context's device state goes)
-            np2_ctx_destroy(cx);
-            return io_fail(code, msg);
+    return np2h::abi_guard([&] {
+        if (n_paths < 0 || n_paths > NP2_MAX_YAK || (n_paths && !paths)) return io_fail(NP2_E_ARG, "n_yak must be in [0, 15]");
+        std::unique_ptr<np2_ctx, void (*)(np2_ctx_t *)> cx(nullptr, np2_ctx_destroy);
+        std::vector<std::unique_ptr<YakFile>> files; // (after the context: its tables are released before its device state goes)
+        for (int i = 0; i < n_paths; ++i) {
+            std::unique_ptr<YakFile> yf(new YakFile());
+            yf->path = paths[i];
+            yf->fd = open(paths[i], O_RDONLY);
+            if (yf->fd < 0) return io_fail(NP2_E_ARG, std::string("cannot open ") + paths[i]);
+            struct stat st;
+            uint8_t hd[16];
+            if (fstat(yf->fd, &st) != 0) return io_fail(NP2_E_ARG, std::string("cannot stat ") + paths[i]);
+            yf->size = (size_t)st.st_size;
+            if (pread(yf->fd, hd, 16, 0) != 16 || memcmp(hd, "YAK\2", 4) != 0)
+                return io_fail(NP2_E_ARG, "The input binary k-mer dump file is incompatible.");
+            yf->k = le32(hd + 4), yf->pre = le32(hd + 8);
+            if (le32(hd + 12) != 10) return io_fail(NP2_E_ARG, "different YAK_COUNTER_BITS");
+            if (yf->k >= 32 || yf->k < 2) return io_fail(NP2_E_UNSUPPORTED, "yak k must be in [2, 32) (main.rs:1433-1434)");
+            if (yf->pre != 10) return io_fail(NP2_E_UNSUPPORTED, "yak pre must be 10 (kmer.rs:52-54,123-125)");
+            files.push_back(std::move(yf));
         }
-    for (auto &yf : files) cx->yaks.push_back(yf->table);
-    *out = cx;
-    return NP2_OK;
-} catch (const std::exception &ex) {
-    return io_fail(NP2_E_NOMEM, std::string("unexpected exception: ") + ex.what());
+        std::stable_sort(files.begin(), files.end(), [](const std::unique_ptr<YakFile> &a, const std::unique_ptr<YakFile> &b) { return a->k < b->k; }); // option.rs:238
+        np2_ctx_t *made = nullptr;
+        const int rc = np2_ctx_create(&made, device, nullptr, 0);
+        if (rc != NP2_OK) return io_fail(rc, "np2_ctx_create failed (see stderr)");
+        cx.reset(made);
+        {
+            std::vector<std::thread> th;
+            hipStream_t own[2] = {cx->stream, cx->stream_out}; // idle until the context's first call
+            for (size_t i = 1; i < files.size(); ++i)
+                th.emplace_back([&, i] { yak_file_to_table(*files[i], device, i < 2 ? own[i] : nullptr); });
+            if (!files.empty()) yak_file_to_table(*files[0], device, own[0]);
+            for (auto &t : th) t.join();
+        }
+        for (auto &yf : files)
+            if (yf->code != NP2_OK) return io_fail(yf->code, yf->path + ": " + yf->msg);
+        for (auto &yf : files) cx->yaks.push_back(yf->table);
+        *out = cx.release();
+        return NP2_OK;
+    }, io_fail);
 }
 
 // ---- BAM ---------------------------------------------------------------------------------------------
 int np2_bam_open(const char *path, np2_bam_t **out) {
-    np2_bam *b = new np2_bam();
-    b->z.f = fopen(path, "rb");
-    try {
+    return np2h::abi_guard([&] {
+        std::unique_ptr<np2_bam> b(new np2_bam());
+        b->z.f = fopen(path, "rb");
         if (!b->z.f) throw np2h::Np2Error(NP2_E_ARG, std::string("cannot open ") + path);
         fseeko(b->z.f, 0, SEEK_SET);
         b->z.block.clear();
@@ -1675,21 +1654,15 @@ int np2_bam_open(const char *path, np2_bam_t **out) {
         // index: <path>.bai or <stem>.bai
         std::string p1 = std::string(path) + ".bai", p2 = path;
         if (p2.size() > 4 && p2.substr(p2.size() - 4) == ".bam") p2 = p2.substr(0, p2.size() - 4) + ".bai";
-        FILE *fi = fopen(p1.c_str(), "rb");
-        if (!fi) fi = fopen(p2.c_str(), "rb");
+        std::unique_ptr<FILE, int (*)(FILE *)> fi(fopen(p1.c_str(), "rb"), fclose);
+        if (!fi) fi.reset(fopen(p2.c_str(), "rb"));
         if (!fi) throw np2h::Np2Error(NP2_E_ARG, "Faield random access BAM/SAM! (no .bai index)");
         std::vector<uint8_t> idx;
-        {
-            fseeko(fi, 0, SEEK_END);
-            const size_t sz = (size_t)ftello(fi);
-            fseeko(fi, 0, SEEK_SET);
-            idx.resize(sz);
-            if (fread(idx.data(), 1, sz, fi) != sz) {
-                fclose(fi);
-                throw np2h::Np2Error(NP2_E_ARG, "cannot read the .bai index");
-            }
-            fclose(fi);
-        }
+        fseeko(fi.get(), 0, SEEK_END);
+        idx.resize((size_t)ftello(fi.get()));
+        fseeko(fi.get(), 0, SEEK_SET);
+        if (fread(idx.data(), 1, idx.size(), fi.get()) != idx.size()) throw np2h::Np2Error(NP2_E_ARG, "cannot read the .bai index");
+        fi.reset();
         if (idx.size() < 8 || memcmp(idx.data(), "BAI\1", 4) != 0) throw np2h::Np2Error(NP2_E_ARG, "bad .bai magic");
         size_t p = 4;
         const uint32_t n_ref_i = le32(idx.data() + p);
@@ -1718,26 +1691,11 @@ int np2_bam_open(const char *path, np2_bam_t **out) {
             p += (size_t)n_intv * 8;
             b->ref_start[r] = best;
         }
-    } catch (const np2h::Np2Error &e) {
-        if (b->map) munmap(const_cast<uint8_t *>(b->map), b->map_len);
-        if (b->z.f) fclose(b->z.f);
-        delete b;
-        return io_fail(e.code, e.what());
-    } catch (const std::exception &ex) {
-        if (b->map) munmap(const_cast<uint8_t *>(b->map), b->map_len);
-        if (b->z.f) fclose(b->z.f);
-        delete b;
-        return io_fail(NP2_E_NOMEM, std::string("unexpected exception: ") + ex.what());
-    }
-    *out = b;
-    return NP2_OK;
+        *out = b.release();
+        return NP2_OK;
+    }, io_fail);
 }
-void np2_bam_close(np2_bam_t *b) {
-    if (!b) return;
-    if (b->map) munmap(const_cast<uint8_t *>(b->map), b->map_len);
-    if (b->z.f) fclose(b->z.f);
-    delete b;
-}
+void np2_bam_close(np2_bam_t *b) { delete b; }
 int np2_bam_n_refs(np2_bam_t *b) { return b ? (int)b->ref_names.size() : 0; }
 const char *np2_bam_ref_name(np2_bam_t *b, int tid, uint32_t *len) {
     if (!b || tid < 0 || (size_t)tid >= b->ref_names.size()) return nullptr;
@@ -1750,21 +1708,13 @@ int np2_contig_from_records(np2_ctx_t *cx, const uint8_t *ref, uint32_t L, const
                             np2_contig_t **out) {
     if (!cx || !ref || !opts || !out) return NP2_E_ARG;
     *out = nullptr;
-    try {
+    return np2h::abi_guard([&] {
         uint64_t sbytes = 0;
         for (uint32_t i = 0; i < n_recs; ++i) sbytes = std::max<uint64_t>(sbytes, recs[i].seq_off + ((uint64_t)recs[i].l_seq + 1) / 2);
         contig_from_records(cx, ref, L, recs, n_recs, cigar, seq4, sbytes, opts, out);
         np2h::flush_timings(cx);
-    } catch (const np2h::Np2Error &e) {
-        (void)hipStreamSynchronize(cx->stream);
-        np2h::flush_timings(cx);
-        return np2h::fail(cx, e);
-    } catch (const std::exception &ex) {
-        (void)hipStreamSynchronize(cx->stream);
-        np2h::flush_timings(cx);
-        return np2h::fail(cx, np2h::Np2Error(NP2_E_NOMEM, std::string("unexpected exception: ") + ex.what()));
-    }
-    return NP2_OK;
+        return NP2_OK;
+    }, np2h::ctx_sink(cx, true));
 }
 
 struct GBlk { // a BGZF block of the file
@@ -1854,9 +1804,19 @@ struct GpuFetch {
         }
     }
 };
-np2_bam::~np2_bam() { delete gpu; }
+np2_bam::~np2_bam() {
+    delete gpu;
+    if (map) munmap(const_cast<uint8_t *>(map), map_len);
+    if (z.f) fclose(z.f);
+}
 
 namespace {
+// index of the reference called `name` in the BAM's header (the last one of that name)
+int ref_id(const np2_bam *bam, const char *name) {
+    for (size_t i = bam->ref_names.size(); i-- > 0;)
+        if (bam->ref_names[i] == name) return (int)i;
+    throw np2h::Np2Error(NP2_E_ARG, std::string("Faield random access BAM/SAM! (contig not in the BAM header: ") + name + ")");
+}
 bool gpu_fetch_wanted(const np2_bam *bam, int tid) { // (read per contig, not per pass: a tool may switch between two reads of the same file)
     if (const char *e = getenv("NP2_INFLATE")) return !strcmp(e, "gpu");
     static const bool few_cpus = np2h::usable_cpus() / std::max(1u, np2h::local_ranks()) < 12u;
@@ -2260,7 +2220,7 @@ int np2_bgzf_inflate_device(np2_ctx_t *cx, const uint8_t *bgzf, uint64_t n, uint
                             float *kernel_ms) {
     if (!cx || (!bgzf && n) || !out_len || (!out && out_cap)) return NP2_E_ARG;
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    try {
+    return np2h::abi_guard([&] {
         HIPCHK(hipSetDevice(cx->device));
         hipStream_t s = cx->stream;
         BgzfBatch hdr;
@@ -2318,27 +2278,21 @@ int np2_bgzf_inflate_device(np2_ctx_t *cx, const uint8_t *bgzf, uint64_t n, uint
         e0 = e1 = nullptr;
         for (size_t i = 0; i < tb.size(); ++i)
             if (st[i]) throw np2h::Np2Error(NP2_E_ARG, "BGZF inflate failed (block " + std::to_string(i) + ", status " + std::to_string(st[i]) + ")");
-    } catch (const np2h::Np2Error &e) {
+        return NP2_OK;
+    }, [&](int code, const std::string &msg) {
         if (e0) (void)hipEventDestroy(e0);
         if (e1) (void)hipEventDestroy(e1);
         (void)hipStreamSynchronize(cx->stream);
-        return io_fail(e.code, e.what());
-    } catch (const std::exception &ex) {
-        (void)hipStreamSynchronize(cx->stream);
-        return io_fail(NP2_E_NOMEM, ex.what());
-    }
-    return NP2_OK;
+        io_fail(code, msg);
+    });
 }
 
 int np2_contig_from_bam(np2_ctx_t *cx, np2_bam_t *bam, const char *name, const uint8_t *ref, uint32_t L,
                         const np2_front_opts_t *opts, np2_contig_t **out) {
     if (!cx || !bam || !name || !ref || !opts || !out) return NP2_E_ARG;
     *out = nullptr;
-    try {
-        int tid = -1;
-        for (size_t i = 0; i < bam->ref_names.size(); ++i)
-            if (bam->ref_names[i] == name) tid = (int)i;
-        if (tid < 0) throw np2h::Np2Error(NP2_E_ARG, std::string("Faield random access BAM/SAM! (contig not in the BAM header: ") + name + ")");
+    return np2h::abi_guard([&] {
+        const int tid = ref_id(bam, name);
         std::vector<np2_bamrec_t> recs;
         std::vector<uint32_t> cigar;
         PinnedBytes &seq4 = bam->seq4;
@@ -2374,16 +2328,8 @@ int np2_contig_from_bam(np2_ctx_t *cx, np2_bam_t *bam, const char *name, const u
                     name, t_p1 - t_p0, bam->batch.ms_read, Inflater::get().name(), bam->batch.ms_inflate, bam->batch.ms_drop,
                     bam->batch.ms_walk, bam->batch.ms_size, bam->batch.ms_copy, recs.size(), (size_t)seq_bytes, np2h::now_ms() - t_p1);
         np2h::flush_timings(cx);
-    } catch (const np2h::Np2Error &e) {
-        (void)hipStreamSynchronize(cx->stream);
-        np2h::flush_timings(cx);
-        return np2h::fail(cx, e);
-    } catch (const std::exception &ex) {
-        (void)hipStreamSynchronize(cx->stream);
-        np2h::flush_timings(cx);
-        return np2h::fail(cx, np2h::Np2Error(NP2_E_NOMEM, std::string("unexpected exception: ") + ex.what()));
-    }
-    return NP2_OK;
+        return NP2_OK;
+    }, np2h::ctx_sink(cx, true));
 }
 
 // ---- a reference-interval shard straight from the BAM -----------------------------------------------------------------
@@ -2407,14 +2353,12 @@ int np2_shard_bam_begin(np2_ctx_t *cx, np2_bam_t *bam, const char *name, const u
     if (!cx || !bam || !name || !ref || !opts || !out || !own_voffsets || !n_own || own_lo >= own_hi || own_hi > L)
         return NP2_E_ARG;
     *out = nullptr;
-    np2_shard_io *io = new np2_shard_io();
-    io->cx = cx;
-    io->L = L;
-    try {
-        int tid = -1;
-        for (size_t i = 0; i < bam->ref_names.size(); ++i)
-            if (bam->ref_names[i] == name) tid = (int)i;
-        if (tid < 0) throw np2h::Np2Error(NP2_E_ARG, std::string("Faield random access BAM/SAM! (contig not in the BAM header: ") + name + ")");
+    std::unique_ptr<np2_shard_io> io; // (freed after the sink's sync)
+    return np2h::abi_guard([&] {
+        io.reset(new np2_shard_io());
+        io->cx = cx;
+        io->L = L;
+        const int tid = ref_id(bam, name);
         np2_shard_plan_t &pl = io->plan;
         pl.own_lo = own_lo, pl.own_hi = own_hi;
         pl.zone_lo = own_lo > halo ? own_lo - halo : 0u;
@@ -2439,11 +2383,7 @@ int np2_shard_bam_begin(np2_ctx_t *cx, np2_bam_t *bam, const char *name, const u
         // the sub-contig: from the first start to the last reference end among the fetched records
         uint32_t slo = pl.zone_lo, shi = pl.zone_hi;
         for (const np2_bamrec_t &r : recs) {
-            uint64_t span = 0;
-            for (uint32_t k = 0; k < r.n_cigar; ++k) {
-                const uint32_t w = cigar_p[r.cigar_off + k], op = w & 15;
-                if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) span += w >> 4;
-            }
+            const uint64_t span = ref_span(cigar_p + r.cigar_off, r.n_cigar);
             if (r.pos >= 0) slo = std::min<uint32_t>(slo, (uint32_t)r.pos);
             shi = (uint32_t)std::min<uint64_t>(L, std::max<uint64_t>(shi, (uint64_t)r.pos + span));
         }
@@ -2458,19 +2398,11 @@ int np2_shard_bam_begin(np2_ctx_t *cx, np2_bam_t *bam, const char *name, const u
             if ((uint32_t)r.pos >= own_lo && (uint32_t)r.pos < own_hi) io->own_voff.push_back(io->rec_voff[io->fw.rec_of[i]]);
         }
         np2h::flush_timings(cx);
-    } catch (const np2h::Np2Error &e) {
-        (void)hipStreamSynchronize(cx->stream);
-        delete io;
-        return np2h::fail(cx, e);
-    } catch (const std::exception &ex) {
-        (void)hipStreamSynchronize(cx->stream);
-        delete io;
-        return np2h::fail(cx, np2h::Np2Error(NP2_E_NOMEM, std::string("unexpected exception: ") + ex.what()));
-    }
-    *own_voffsets = io->own_voff.data();
-    *n_own = io->own_voff.size();
-    *out = io;
-    return NP2_OK;
+        *own_voffsets = io->own_voff.data();
+        *n_own = io->own_voff.size();
+        *out = io.release();
+        return NP2_OK;
+    }, np2h::ctx_sink(cx));
 }
 
 void np2_shard_bam_abort(np2_shard_io_t *io) { delete io; }
@@ -2478,10 +2410,10 @@ void np2_shard_bam_abort(np2_shard_io_t *io) { delete io; }
 int np2_shard_bam_finish(np2_shard_io_t *io, const uint64_t *all_voffsets, uint64_t n_all, np2_shard_plan_t *plan,
                          np2_contig_t **contig, uint32_t *n_reads_total) {
     if (!io || (n_all && !all_voffsets) || !plan || !contig || !n_reads_total) return NP2_E_ARG;
+    std::unique_ptr<np2_shard_io> owned(io); // (freed after the sink's sync, whatever the outcome)
     np2_ctx *cx = io->cx;
     *contig = nullptr;
-    int rc = NP2_OK;
-    try {
+    return np2h::abi_guard([&] {
         FrontWork &fw = io->fw;
         // contig-wide number of every pushed record this shard fetched
         const size_t n = fw.reads.size();
@@ -2518,21 +2450,14 @@ int np2_shard_bam_finish(np2_shard_io_t *io, const uint64_t *all_voffsets, uint6
         *plan = pl;
         *n_reads_total = 1 + (uint32_t)n_all;
         np2h::flush_timings(cx);
-    } catch (const np2h::Np2Error &e) {
-        (void)hipStreamSynchronize(cx->stream);
-        rc = np2h::fail(cx, e);
-    } catch (const std::exception &ex) {
-        (void)hipStreamSynchronize(cx->stream);
-        rc = np2h::fail(cx, np2h::Np2Error(NP2_E_NOMEM, std::string("unexpected exception: ") + ex.what()));
-    }
-    delete io;
-    return rc;
+        return NP2_OK;
+    }, np2h::ctx_sink(cx));
 }
 
 int np2_contig_export(np2_ctx_t *cx, np2_contig_t *c, np2_read_t **reads, uint32_t *n_reads, uint8_t **nibbles,
                       uint64_t *nib_bytes) {
     if (!cx || !c || !reads || !n_reads || !nibbles || !nib_bytes) return NP2_E_ARG;
-    try {
+    return np2h::abi_guard([&] {
         HIPCHK(hipSetDevice(cx->device));
         *reads = (np2_read_t *)malloc((size_t)c->R * sizeof(np2_read_t));
         *nibbles = (uint8_t *)malloc(c->nib_bytes);
@@ -2540,11 +2465,7 @@ int np2_contig_export(np2_ctx_t *cx, np2_contig_t *c, np2_read_t **reads, uint32
         HIPCHK(hipMemcpy(*nibbles, c->nib.p, c->nib_bytes, hipMemcpyDeviceToHost));
         *n_reads = c->R;
         *nib_bytes = c->nib_bytes;
-    } catch (const np2h::Np2Error &e) {
-        return np2h::fail(cx, e);
-    } catch (const std::exception &ex) {
-        return np2h::fail(cx, np2h::Np2Error(NP2_E_NOMEM, std::string("unexpected exception: ") + ex.what()));
-    }
-    return NP2_OK;
+        return NP2_OK;
+    }, np2h::ctx_sink(cx));
 }
 }

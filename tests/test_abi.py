@@ -104,3 +104,84 @@ def test_product_phasing_vote_agrees_with_the_oracle_on_random_signed_graphs():
                 phase_vote(keys, plist, ref)
             continue
         assert phase_vote(keys, plist, ref) == exp, trial
+
+
+def test_abi_guard_turns_every_exception_into_a_status(tmp_path):
+    """csrc/np2_abi.hpp (host-only) built on its own: a returned code passes through, an Np2Error keeps its code and
+    message, any other exception becomes NP2_E_NOMEM with "unexpected exception", and the sink runs only after a throw."""
+    import subprocess
+    exe = str(tmp_path / "abi_guard_test")
+    r = subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-o", exe,
+                        os.path.join(ROOT, "tests", "tools", "abi_guard_test.cpp")], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and r.stdout.strip() == "ok", r.stderr[-3000:]
+
+
+def _bgzf_file(path, payload):
+    from nextpolish2_amd.bamio import _Bgzf
+    with open(path, "wb") as f:
+        z = _Bgzf(f)
+        z.write(payload, atomic=False)
+        z.close()
+
+
+def test_device_free_entry_points_report_bad_input_as_status(tmp_path):
+    """Bad input to the entry points that need no device comes back as an NP2_E_* status with its message (the same
+    codes and texts the command line and the Python layer have always relayed), never as an abort."""
+    import struct
+    import numpy as np
+    from nextpolish2_amd import bamio, io
+    from nextpolish2_amd._types import READ_DTYPE, Pileup
+    E_ARG, E_REFPANIC = -1, -5
+
+    missing = str(tmp_path / "missing.fa")
+    with pytest.raises(api.Np2Error) as e:
+        list(io.read_fasta(missing))
+    assert e.value.code == E_ARG and "cannot open" in str(e.value) and missing in str(e.value)
+    with pytest.raises(api.Np2Error) as e:
+        io.polisher_from_yak_files([str(tmp_path / "missing.yak")])
+    assert e.value.code == E_ARG and "cannot open" in str(e.value)
+
+    bad_magic = tmp_path / "bad.yak"
+    bad_magic.write_bytes(b"KAY\2" + struct.pack("<III", 21, 10, 10))
+    with pytest.raises(api.Np2Error) as e:
+        io.load_yak(str(bad_magic))
+    assert e.value.code == E_ARG and "incompatible" in str(e.value)
+    cut_short = tmp_path / "short.yak"  # a valid header, then 3 of the 1024 bucket headers
+    cut_short.write_bytes(b"YAK\2" + struct.pack("<III", 21, 10, 10) + struct.pack("<II", 0, 0) * 3)
+    with pytest.raises(api.Np2Error) as e:
+        io.load_yak(str(cut_short))
+    assert e.value.code == E_ARG and "Failed to parse" in str(e.value)
+
+    text = tmp_path / "text.bam"
+    text.write_bytes(b"@HD\tVN:1.6\n")
+    with pytest.raises(api.Np2Error) as e:
+        io.Bam(str(text))
+    assert e.value.code == E_ARG and "not a BGZF block" in str(e.value)
+    junk = str(tmp_path / "junk.bam")
+    _bgzf_file(junk, b"SAM\1" + bytes(64))
+    with pytest.raises(api.Np2Error) as e:
+        io.Bam(junk)
+    assert e.value.code == E_ARG and "not a BAM file" in str(e.value)
+    unindexed = str(tmp_path / "unindexed.bam")
+    bamio.write_bam(unindexed, [("ctg", 100)], [])
+    os.remove(unindexed + ".bai")
+    with pytest.raises(api.Np2Error) as e:
+        io.Bam(unindexed)
+    assert e.value.code == E_ARG and "Faield random access BAM/SAM!" in str(e.value)
+
+    L = 3000  # room for three 1024-aligned shards at most
+    reads = np.zeros(1, dtype=READ_DTYPE)
+    reads[0] = (0, L - 1, 0, L, 0)
+    pileup = Pileup(b"A" * L, reads, np.zeros(L // 2 + 32, np.uint8))
+    assert len(api.shard_plan(pileup, 2)) == 2
+    with pytest.raises(api.Np2Error) as e:
+        api.shard_plan(pileup, 4)
+    assert e.value.code == E_ARG
+
+    # a NaN weight: the net weight between two final communities is neither zero nor negative (louvain.rs's conflict
+    # check panics on it)
+    with pytest.raises(api.Np2Error) as e:
+        api.phase_vote([1, 2, 3], [(1, 2, -1.0), (1, 3, -1.0), (2, 3, float("nan"))])
+    assert e.value.code == E_REFPANIC
