@@ -218,3 +218,47 @@ def test_waiting_by_naps_or_by_spinning_changes_nothing(env):
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     last = r.stdout.decode().strip().splitlines()[-1]
     assert last.startswith("batch cases 3 bad 0"), r.stdout.decode()[-2000:]
+
+
+@pytest.fixture(scope="module")
+def many_small_contigs():
+    """72 contigs of 2-12 kb, haploid and diploid, some without a low-quality region and one whose pileup holds nothing
+    but the contig's own row 0; with their per-contig results (np2_polish_resident, want_pos) and the oracle's"""
+    from nextpolish2_amd._types import Pileup
+    rng = np.random.default_rng(72)
+    syn = []
+    for i in range(72):
+        L = int(rng.integers(2000, 12001))
+        kw = dict(depth=int(rng.choice([8, 20, 30])), seed=500 + i, diploid=i % 3 == 1, read_len_mean=min(3000.0, L / 2),
+                  read_len_sd=min(500.0, L / 12), read_len_min=min(500, L // 4), name=f"s{i}")
+        if i % 9 == 4:  # no low-quality region
+            kw.update(diploid=False, asm_err_rate=0.0, read_err_rate=0.0)
+        syn.append(Synth(L, **kw))
+    pus = [s.pileup for s in syn]
+    pus[37] = Pileup(pus[37].ref, pus[37].reads[:1].copy(), pus[37].nibbles)  # row 0 only
+    yaks = [Synth.yak_assembly(syn, 21), Synth.yak_assembly(syn, 31)]
+    o = orc.Oracle(yaks)
+    want = [o.polish(pu, Opts()) for pu in pus]
+    pol = Polisher(yaks)
+    contigs = [pol.upload(pu) for pu in pus]
+    single = [pol.polish_resident(c, Opts()) for c in contigs]
+    for (ob, op), (sb, sp) in zip(want, single):
+        assert np.array_equal(ob, sb) and np.array_equal(op, sp)
+    return pol, contigs, single
+
+
+@pytest.mark.parametrize("n_slots", [40, 70])
+def test_batch_wider_than_one_launch(many_small_contigs, n_slots):
+    """more slots than one batched launch takes (MAXB = 32, fewer for kernels with large argument packs: 23 for
+    k_diff_reads): every merged step goes out as several launches.  72 contigs: waves of 40 + 32, or 70 + 2."""
+    pol, contigs, single = many_small_contigs
+    bp = BatchPolisher(pol, n_slots)
+    out = bp.polish(contigs, Opts(), want_pos=True)
+    for i, ((b, p), (sb, sp)) in enumerate(zip(out, single)):
+        assert np.array_equal(b, sb) and np.array_equal(p, sp), i
+    spans = bp.polish(contigs, Opts())
+    for i, ((b, span), (sb, sp)) in enumerate(zip(spans, single)):
+        assert np.array_equal(b, sb) and span == (int(sp[0]), int(sp[-1])), i
+    st = bp.stats()
+    assert st["launches"] < st["commands"]
+    bp.close()

@@ -20,10 +20,16 @@ STAGES = ["graph.off", "graph.bases", "graph.delta", "graph.count", "cns_raw.pos
           "rech1.kscore", "rech1.lable", "rech1.sudo", "cns_rech1.pos", "cns_rech1.base"]
 
 
-def check_all_stages(pu, yaks, opts):
+def oracle_traced(pu, yaks, opts):
     o = orc.Oracle(yaks)
     o.set_trace(True)
     ob, op = o.polish(pu, opts)
+    return o, ob, op
+
+
+def check_all_stages(pu, yaks, opts, ref=None):
+    # ref: oracle_traced(pu, yaks, opts) of an earlier call, to compare several device runs with one oracle run
+    o, ob, op = ref or oracle_traced(pu, yaks, opts)
     g = Polisher(yaks)
     g.set_trace(True)
     gb, gp = g.polish(pu, opts)
@@ -316,6 +322,41 @@ def test_identical_pass_reuse_and_bases_only_output(small_haploid, small_diploid
         b4, _ = g.polish_resident(c, Opts(iter_count=4))
         ob, _ = orc.Oracle(yaks).polish(s.pileup, Opts(iter_count=4))
         assert np.array_equal(b4, ob)
+
+
+# (contig length asked of the generator, seed) -> a contig of exactly 2047, 2048 and 2049 tiles of 1024 positions: from
+# 2048 tiles on, k_tile_layout, and k_tile_offsets in both pass fronts, are the look-back kernels (np2_host.cpp: `wide`);
+# 2049 tiles = 3 look-back blocks
+WIDE_SWITCH = {2047 * 1024: (2_096_106, 41), 2047 * 1024 + 1: (2_096_156, 42), 2048 * 1024 + 1: (2_097_140, 43)}
+
+
+def wide_synth(L, diploid=False):
+    L_in, seed = (2_097_190, 44) if diploid else WIDE_SWITCH[L]
+    s = Synth(L_in, depth=30, seed=seed, diploid=diploid)
+    assert len(s.pileup.ref) == L
+    return s
+
+
+@pytest.mark.parametrize("L", sorted(WIDE_SWITCH))
+def test_stage_parity_at_the_wide_tile_scan_switch(monkeypatch, L):
+    """every stage at 2047, 2048 and 2049 tiles, through the fused pass front and the unfused one (a context reads
+    NP2_FRONT_UNFUSED when it is made); at 2049 tiles also with 64-record buckets (spills and the device-wide sort on
+    top of the wide layout)"""
+    s = wide_synth(L)
+    yaks = [s.yak(21)]
+    ref = oracle_traced(s.pileup, yaks, Opts())
+    check_all_stages(s.pileup, yaks, Opts(), ref)
+    monkeypatch.setenv("NP2_FRONT_UNFUSED", "1")
+    check_all_stages(s.pileup, yaks, Opts(), ref)
+    if L == 2048 * 1024 + 1:
+        monkeypatch.delenv("NP2_FRONT_UNFUSED")
+        monkeypatch.setenv("NP2_TILE_CAP", "64")
+        check_all_stages(s.pileup, yaks, Opts(), ref)
+
+
+def test_stage_parity_at_the_wide_tile_scan_switch_diploid():
+    s = wide_synth(2048 * 1024 + 1, diploid=True)
+    check_all_stages(s.pileup, [s.yak(21), s.yak(31)], Opts())
 
 
 def test_phasing_vote_at_moderate_scale():
