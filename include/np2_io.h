@@ -100,6 +100,13 @@ void np2_shard_bam_abort(np2_shard_io_t *io);
  * measuring the kernel; the reference's counterpart is rust-htslib's bgzf reader (main.rs:1745-1757). */
 int np2_bgzf_inflate_device(np2_ctx_t *ctx, const uint8_t *bgzf, uint64_t n, uint8_t *out, uint64_t out_cap, uint64_t *out_len,
                             float *kernel_ms);
+/* CRC-32 (gzip) of n_pieces pieces of `data` — piece i = data[off[i], off[i+1]), each at most 65536 bytes — by the kernel the
+ * read paths check every inflated BGZF block with (the block's CRC32 word; a mismatch is NP2_E_ARG "BGZF CRC32 mismatch
+ * (block at file offset N)" on every path, host pool and device; NP2_BGZF_CRC=0, read once per process, switches the check
+ * off for A/B timing).  kernel_ms (optional): that kernel alone (HIP events).  A piece longer than 65536 bytes, descending
+ * offsets or off[n_pieces] > n: NP2_E_ARG.  The reference's counterpart: htslib's bgzf reader checks each block's CRC. */
+int np2_crc32_device(np2_ctx_t *ctx, const uint8_t *data, uint64_t n, const uint64_t *off, uint32_t n_pieces,
+                     uint32_t *crc_out, float *kernel_ms);
 /* copy a resident packed pileup back to the host (parity tests / debugging); free both with np2_free */
 int np2_contig_export(np2_ctx_t *ctx, np2_contig_t *c, np2_read_t **reads, uint32_t *n_reads,
                       uint8_t **nibbles, uint64_t *nib_bytes);

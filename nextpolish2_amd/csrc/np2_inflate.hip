@@ -8,11 +8,13 @@
 //   same values (bit buffer, positions, symbols pinned to scalar registers by v_readfirstlane: the chain is scalar
 //   arithmetic + one LDS table read per symbol), and the lanes differ only where the work is wide: staging 2 KiB of input
 //   (32 bytes a lane), building the decode tables (a symbol per lane), copying a match (a byte per lane, all 64 lanes of a
-//   258-byte QUAL run), flushing 4 KiB of output (64 bytes a lane, coalesced).  The last 8 KiB of output live in LDS as a
+//   258-byte QUAL run), flushing 2 KiB of output (32 bytes a lane, coalesced).  The last 8 KiB of output live in LDS as a
 //   ring — a near back-reference costs an LDS round trip; a far one (beyond 8 KiB, up to DEFLATE's 32 KiB) reads the flushed
-//   output back from L2 — next to a 4 KiB input window and the tables: 19.1 KB per wavefront, eight wavefronts per CU,
+//   output back from L2 — next to a 4 KiB input window and the tables: 18.7 KB per wavefront, eight wavefronts per CU,
 //   ~2000 blocks in flight.  (The whole 32 KiB window in LDS was four wavefronts per CU, one per SIMD, and a chain of LDS
 //   and scalar latencies with nothing to hide them behind: 15.5 ms for the 4267 blocks of an E. coli-sized contig.)
+// (k_bgzf_crc32, np2_crc32.hip, runs behind it on the same stream: the CRC-32 of every inflated block against the block's
+//   CRC32 word, a mismatch reported through the same status words.)
 // k_bam_chain_count / k_bam_chain_write — the record walk.  A BAM stream is a chain (a record's length says where the
 //   next one starts), but the .bai linear index names a record START every 16 kb of reference: a thread per index entry
 //   walks its ~30 records to the next entry — 15 k chains for a human chromosome — counting, then (after a scan of the

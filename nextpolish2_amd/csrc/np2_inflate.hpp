@@ -1,4 +1,4 @@
-// GPU read extraction (np2_inflate.hip): BGZF inflate, one wavefront per block, and the record walk over the inflated BAM
+// GPU read extraction (np2_inflate.hip, np2_crc32.hip): BGZF inflate and CRC check, one wavefront per block, and the record walk over the inflated BAM
 // stream along the .bai linear index.  Host side: np2_io.cpp (GpuFetch).
 #pragma once
 #include <cstdint>
@@ -25,6 +25,12 @@ static constexpr uint32_t WALK_EARLY_END = 16u; // the contig's records ended be
 // prof (optional): 8 words per block — clocks of the block, of the wide step's decode, of its chain, of its match copies, tokens, matches
 void launch_bgzf_inflate(hipStream_t s, const InfBlock *blk, uint32_t n_blk, const uint8_t *comp, uint8_t *out, uint32_t *status, uint32_t *n_bad,
                          unsigned long long *prof = nullptr);
+// CRC-32 of the inflated blocks (np2_crc32.hip), behind launch_bgzf_inflate on the same stream: a block whose status is ST_OK
+// and whose bytes data[out_off, out_off + isize) do not give want[b] (the block's stored CRC32 word) gets ST_CRC_MISMATCH and
+// counts in *n_bad.  status == nullptr: every block is taken; want == nullptr: nothing is compared; crc_out (optional): the
+// CRCs themselves (np2_crc32_device).
+void launch_bgzf_crc32(hipStream_t s, const InfBlock *blk, uint32_t n_blk, const uint32_t *want, const uint8_t *data, uint32_t *status, uint32_t *n_bad,
+                       uint32_t *crc_out = nullptr);
 // starts[0 .. n_chains): stream offsets of record starts, ascending; the last chain ends at a record of another reference or at `end`
 // zone [zone_lo, zone_hi): (0, L) for the whole contig, a shard's reference interval otherwise; cig_src[i] = stream offset of
 // record i's CIGAR words (the record starts 36 + l_read_name bytes before: its BGZF virtual offset follows from that)

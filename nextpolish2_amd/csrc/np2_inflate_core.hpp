@@ -35,6 +35,7 @@ enum Status : uint32_t {
     ST_OUT_SHORT = 8,      // stream ended before ISIZE bytes
     ST_IN_OVERRUN = 9,     // stream ran past the block's compressed bytes
     ST_NO_END_CODE = 10,   // literal / length code without symbol 256
+    ST_CRC_MISMATCH = 11,  // inflated to ISIZE bytes whose CRC-32 is not the block's (set by k_bgzf_crc32, np2_crc32.hip)
 };
 static constexpr uint32_t FAST_END_OF_BLOCK = 0xFFFFFFFEu; // Machine::fast consumed the end-of-block code
 

@@ -36,6 +36,8 @@ struct Inflater {
     typedef void *(*alloc_fn)(void);
     typedef int (*dec_fn)(void *, const void *, size_t, void *, size_t, size_t *);
     typedef void (*free_fn)(void *);
+    typedef uint32_t (*crc_fn)(uint32_t, const void *, size_t);
+    crc_fn crc_ld = nullptr; // libdeflate_crc32 (several bytes a clock; zlib's crc32 otherwise)
     alloc_fn alloc = nullptr;
     dec_fn dec = nullptr;
     free_fn fre = nullptr;
@@ -48,6 +50,7 @@ struct Inflater {
         dec = (dec_fn)dlsym(h, "libdeflate_deflate_decompress");
         fre = (free_fn)dlsym(h, "libdeflate_free_decompressor");
         if (!alloc || !dec || !fre) alloc = nullptr, dec = nullptr, fre = nullptr;
+        else crc_ld = (crc_fn)dlsym(h, "libdeflate_crc32");
     }
     static Inflater &get() {
         static Inflater *i = new Inflater();
@@ -82,7 +85,21 @@ struct Inflater {
         inflateEnd(&zs);
         return rc == Z_STREAM_END && zs.avail_out == 0;
     }
+    // CRC-32 (gzip) of n bytes: what a BGZF block's CRC32 word must equal for its inflated bytes
+    uint32_t crc(const uint8_t *d, size_t n) const {
+        if (crc_ld) return crc_ld(0u, d, n);
+        return (uint32_t)crc32(crc32(0L, Z_NULL, 0), d, (uInt)n);
+    }
 };
+// Every BGZF block a path inflates must carry the CRC-32 of its inflated bytes (htslib checks it; DEFLATE itself has no
+// checksum, and most single-bit flips inside a payload still inflate to ISIZE bytes).  NP2_BGZF_CRC=0, read once per
+// process, switches the check off on every path, host and device: it exists to time the check, not to read damaged files.
+bool bgzf_crc_on() {
+    static const bool on = !(getenv("NP2_BGZF_CRC") && !strcmp(getenv("NP2_BGZF_CRC"), "0"));
+    return on;
+}
+std::string crc_msg(uint64_t file_off) { return "BGZF CRC32 mismatch (block at file offset " + std::to_string(file_off) + ")"; }
+uint32_t le32(const uint8_t *p) { return p[0] | (p[1] << 8) | (p[2] << 16) | ((uint32_t)p[3] << 24); }
 
 thread_local std::string g_io_err;
 int io_fail(int code, const std::string &m) {
@@ -152,6 +169,7 @@ struct Bgzf {
         block.resize(isize);
         if (isize && !Inflater::get().run(cdata.data(), clen, block.data(), isize))
             throw np2h::Np2Error(NP2_E_ARG, "BGZF inflate failed");
+        if (bgzf_crc_on() && Inflater::get().crc(block.data(), isize) != le32(cdata.data() + clen)) throw np2h::Np2Error(NP2_E_ARG, crc_msg(block_off));
         return true;
     }
     void seek(uint64_t voffset) {
@@ -389,7 +407,7 @@ struct BgzfBatch {
     size_t map_len = 0, fpos = 0;
     struct Blk {
         const uint8_t *c = nullptr; // raw deflate payload (inside the mapping)
-        uint32_t clen = 0, isize = 0;
+        uint32_t clen = 0, isize = 0, crc = 0; // (crc: the block's CRC32 word)
         size_t out_off = 0;
         uint64_t file_off = 0; // offset of the block in the file
     };
@@ -440,6 +458,7 @@ struct BgzfBatch {
         b.c = hd + 12 + xlen;
         b.clen = (uint32_t)clen;
         const uint8_t *tail = b.c + clen;
+        b.crc = le32(tail);
         b.isize = tail[4] | (tail[5] << 8) | (tail[6] << 16) | ((uint32_t)tail[7] << 24);
         fpos += bsize;
         return true;
@@ -516,11 +535,25 @@ struct BgzfBatch {
         cur_base = base, ready_bi = 0, ready_end = base;
         if (skip) pos = std::min<size_t>(skip, buf.size()), skip = 0;
         const double t_f2 = np2h::now_ms();
-        std::atomic<int> bad{0};
+        // 0: none; otherwise the first block (in file order) that failed: index + 1 in the low bits, bit 63 = its CRC (not its inflate)
+        std::atomic<uint64_t> bad{0};
         const Inflater &inf = Inflater::get();
+        const bool check_crc = bgzf_crc_on();
         auto one = [&](size_t i) {
-            if (blks[i].isize && !inf.run(blks[i].c, blks[i].clen, buf.data() + base + blks[i].out_off, blks[i].isize)) bad.store(1);
+            uint8_t *dst = buf.data() + base + blks[i].out_off;
+            uint64_t why = 0;
+            if (blks[i].isize && !inf.run(blks[i].c, blks[i].clen, dst, blks[i].isize)) why = i + 1;
+            else if (check_crc && inf.crc(dst, blks[i].isize) != blks[i].crc) why = (i + 1) | (1ull << 63);
+            if (why) {
+                uint64_t seen = bad.load();
+                while ((!seen || (seen & ~(1ull << 63)) > i + 1) && !bad.compare_exchange_weak(seen, why)) {}
+            }
             blk_done[i].store(1, std::memory_order_release); // (also after a failure: a reader must not wait forever)
+        };
+        auto throw_bad = [&]() {
+            const uint64_t why = bad.load();
+            if (why >> 63) throw np2h::Np2Error(NP2_E_ARG, crc_msg(blks[(size_t)(why & ~(1ull << 63)) - 1].file_off));
+            throw np2h::Np2Error(NP2_E_ARG, "BGZF inflate failed");
         };
         const unsigned nt = (unsigned)std::max<size_t>(1, blks.size() / 2);
         try {
@@ -530,11 +563,11 @@ struct BgzfBatch {
                 IoPool::get().parallel_for(blks.size(), nt, one);
         } catch (...) {
             ready_end = buf.size();
-            if (bad.load()) throw np2h::Np2Error(NP2_E_ARG, "BGZF inflate failed"); // (what the reader tripped over)
+            if (bad.load()) throw_bad(); // (what the reader tripped over)
             throw;
         }
         ready_bi = blks.size(), ready_end = buf.size();
-        if (bad.load()) throw np2h::Np2Error(NP2_E_ARG, "BGZF inflate failed");
+        if (bad.load()) throw_bad();
         ms_drop += t_f1 - t_f0, ms_read += t_f2 - t_f1, ms_inflate += np2h::now_ms() - t_f2;
     }
     // pointer to n contiguous bytes (nullptr on clean EOF before the first byte)
@@ -552,7 +585,6 @@ struct BgzfBatch {
     }
 };
 
-uint32_t le32(const uint8_t *p) { return p[0] | (p[1] << 8) | (p[2] << 16) | ((uint32_t)p[3] << 24); }
 uint64_t le64(const uint8_t *p) { return (uint64_t)le32(p) | ((uint64_t)le32(p + 4) << 32); }
 
 // reference bases a CIGAR of n operations covers (M, D, N, =, X); given as words or as a record's little-endian bytes
@@ -1722,6 +1754,7 @@ struct GBlk { // a BGZF block of the file
     uint32_t hdr_len;  // 12 + XLEN: the raw DEFLATE payload starts there
     uint32_t clen, isize;
     uint32_t bsize;    // the whole block
+    uint32_t crc;      // its CRC32 word (of the inflated bytes)
 };
 // The whole file inflated on the device, once per process and device, for BAMs of many references and moderate size (an
 // assembly's: yeast 96 MB -> 600 MB): ONE inflate launch over every block — a block's decode latency, 2 - 3 ms, is paid once
@@ -1833,6 +1866,10 @@ struct GpuRecs {
     const uint8_t *d_stream = nullptr;
     uint64_t stream_bytes = 0;
 };
+// The block table of an inflate launch as it goes to the device in one copy: n InfBlock, then the blocks' n CRC32 words
+// (k_bgzf_crc32 reads them there: d_blk.p + n).
+size_t blk_table_bytes(size_t n) { return n * sizeof(np2::InfBlock) + n * 4; }
+size_t blk_table_slots(size_t n) { return (blk_table_bytes(n) + sizeof(np2::InfBlock) - 1) / sizeof(np2::InfBlock) + 1; }
 // File bytes [c_lo, read_end) -> pinned pieces (pread on the pool's threads: the page cache is copied from, no mapping of the
 // file is faulted in — through the mmap the same 2 GB of a chromosome's BAM took 0.08 to 2.7 s) -> g.d_comp; the 18-byte block
 // headers are parsed out of each piece while it is there.  blks: the blocks that lie wholly inside the range; eof: nothing
@@ -1904,6 +1941,7 @@ void read_blocks_to_device(GpuFetch &g, int fd, size_t file_len, size_t c_lo, si
             if (tail + 8 > p1) small_read(tail, tb8, 8), tp = tb8;
             GBlk b;
             b.file_off = hdr_at, b.hdr_len = 12 + xlen, b.clen = bsize - 12 - xlen - 8, b.bsize = bsize;
+            b.crc = le32(tp);
             b.isize = tp[4] | (tp[5] << 8) | (tp[6] << 16) | ((uint32_t)tp[7] << 24);
             blks.push_back(b);
             hdr_at += bsize;
@@ -1964,22 +2002,26 @@ ResidentBam *resident_for(np2_bam *bam, GpuFetch &g, hipStream_t s) {
         const uint64_t total = rb->out_off[n_blk];
         const double t1 = np2h::now_ms();
         rb->d_inf.ensure(total + 128);
-        g.d_blk.ensure(n_blk + 1);
+        g.d_blk.ensure(blk_table_slots(n_blk));
         g.d_status.ensure(n_blk + 8);
-        std::vector<np2::InfBlock> tb(n_blk);
-        for (size_t i = 0; i < n_blk; ++i) tb[i] = np2::InfBlock{rb->blks[i].file_off + rb->blks[i].hdr_len - c_lo, rb->out_off[i], rb->blks[i].clen, rb->blks[i].isize};
-        np2::InfBlock *h_tb = (np2::InfBlock *)g.host_block(g.h_cigar, g.h_cigar_cap, n_blk * sizeof(np2::InfBlock));
-        memcpy(h_tb, tb.data(), n_blk * sizeof(np2::InfBlock));
-        HIPCHK(hipMemcpyAsync(g.d_blk.p, h_tb, n_blk * sizeof(np2::InfBlock), hipMemcpyHostToDevice, s));
+        np2::InfBlock *h_tb = (np2::InfBlock *)g.host_block(g.h_cigar, g.h_cigar_cap, blk_table_bytes(n_blk));
+        uint32_t *h_crc = (uint32_t *)(h_tb + n_blk); // (the blocks' CRC32 words travel behind the table, in the same copy)
+        for (size_t i = 0; i < n_blk; ++i) {
+            h_tb[i] = np2::InfBlock{rb->blks[i].file_off + rb->blks[i].hdr_len - c_lo, rb->out_off[i], rb->blks[i].clen, rb->blks[i].isize};
+            h_crc[i] = rb->blks[i].crc;
+        }
+        HIPCHK(hipMemcpyAsync(g.d_blk.p, h_tb, blk_table_bytes(n_blk), hipMemcpyHostToDevice, s));
         const size_t w_bad = (n_blk + 1) & ~(size_t)1;
         HIPCHK(hipMemsetAsync(g.d_status.p, 0, (w_bad + 4) * 4, s));
         HIPCHK(hipMemsetAsync(rb->d_inf.p + total, 0, 128, s)); // (the columnariser loads whole words behind the last SEQ)
         np2::launch_bgzf_inflate(s, g.d_blk.p, (uint32_t)n_blk, g.d_comp.p, rb->d_inf.p, g.d_status.p, g.d_status.p + w_bad);
+        // (a CRC mismatch counts like a block that does not inflate: no resident stream, and the per-reference path names the block)
+        if (bgzf_crc_on()) np2::launch_bgzf_crc32(s, g.d_blk.p, (uint32_t)n_blk, (const uint32_t *)(g.d_blk.p + n_blk), rb->d_inf.p, g.d_status.p, g.d_status.p + w_bad);
         uint32_t n_bad = 0;
         HIPCHK(hipMemcpyAsync(h_tb, g.d_status.p + w_bad, 4, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         memcpy(&n_bad, h_tb, 4);
-        if (n_bad) throw np2h::Np2Error(NP2_E_ARG, "BGZF inflate failed");
+        if (n_bad) throw np2h::Np2Error(NP2_E_ARG, "BGZF inflate failed"); // (or its CRC: caught below either way)
         g.d_comp.release(); // (the file's bytes are not needed again)
         rb->built = true;
         rb->failed = false;
@@ -2036,10 +2078,15 @@ bool fetch_records_gpu(np2_bam *bam, int tid, uint32_t L, uint32_t zone_lo, uint
     std::vector<uint64_t> out_off;
     size_t extra = 0; // bytes read beyond the index's end of the reference (an index that understates it costs a second round)
     ResidentBam *res = resident_for(bam, g, s); // the whole file on the device already (or now), or nullptr
+    // A block that does not inflate, or not to bytes of its CRC, may lie in what is read AHEAD of the reference's last record
+    // (64 KiB and more: another reference's blocks, which htslib would never open for this one).  The first such block ends
+    // the range instead: the round is repeated up to it, and the error is raised only if the walk then wants to go on.
+    size_t cap_end = file_len;
+    std::string held_err;
     for (int round = 0;; ++round) {
         if (round > 40) throw np2h::Np2Error(NP2_E_ARG, "BAM/SAM parsing failed!");
         blks.clear();
-        const size_t read_end = std::min(file_len, c_hi + 65536 + extra);
+        const size_t read_end = std::min(std::min(file_len, c_hi + 65536 + extra), cap_end);
         const size_t c_bytes = read_end - c_lo;
         bool eof = false;
         const uint8_t *inf = nullptr; // the inflated stream of the blocks taken
@@ -2095,23 +2142,29 @@ bool fetch_records_gpu(np2_bam *bam, int tid, uint32_t L, uint32_t zone_lo, uint
                 return false;
             }
             inf = g.d_inf.p;
-            g.d_blk.ensure(n_blk + 1);
+            g.d_blk.ensure(blk_table_slots(n_blk));
             g.d_status.ensure(n_blk + 8);
             if (prof) {
                 HIPCHK(hipStreamSynchronize(s));
                 t_up = np2h::now_ms();
             }
         }
-        np2::InfBlock *h_tb = (np2::InfBlock *)g.host_block(g.h_cigar, g.h_cigar_cap, std::max<size_t>(n_blk * sizeof(np2::InfBlock), 64)); // (free until the records come back)
+        np2::InfBlock *h_tb = (np2::InfBlock *)g.host_block(g.h_cigar, g.h_cigar_cap, std::max<size_t>(blk_table_bytes(n_blk), 64)); // (free until the records come back)
         // status words: [0, n_blk) per block, then n_bad, walk flags, (pad), tail_at (64-bit, 8-byte aligned)
         const size_t w_bad = (n_blk + 1) & ~(size_t)1, w_flags = w_bad + 1, w_tail = w_bad + 2;
         HIPCHK(hipMemsetAsync(g.d_status.p, 0, (w_tail + 2) * 4, s));
         HIPCHK(hipMemsetAsync(g.d_status.p + w_tail, 0xFF, 8, s));
         if (!res) {
-            for (size_t i = 0; i < n_blk; ++i) h_tb[i] = np2::InfBlock{blks[i].file_off + blks[i].hdr_len - c_lo, out_off[i], blks[i].clen, blks[i].isize};
-            HIPCHK(hipMemcpyAsync(g.d_blk.p, h_tb, n_blk * sizeof(np2::InfBlock), hipMemcpyHostToDevice, s));
+            uint32_t *h_crc = (uint32_t *)(h_tb + n_blk); // (the blocks' CRC32 words travel behind the table, in the same copy)
+            for (size_t i = 0; i < n_blk; ++i) {
+                h_tb[i] = np2::InfBlock{blks[i].file_off + blks[i].hdr_len - c_lo, out_off[i], blks[i].clen, blks[i].isize};
+                h_crc[i] = blks[i].crc;
+            }
+            HIPCHK(hipMemcpyAsync(g.d_blk.p, h_tb, blk_table_bytes(n_blk), hipMemcpyHostToDevice, s));
             HIPCHK(hipMemsetAsync(g.d_inf.p + total, 0, 64, s)); // (the columnariser loads whole words behind the last SEQ)
             np2::launch_bgzf_inflate(s, g.d_blk.p, (uint32_t)n_blk, g.d_comp.p, g.d_inf.p, g.d_status.p, g.d_status.p + w_bad);
+            // every block's CRC-32 over what the inflate left, reported through the same status words (no wait of its own)
+            if (bgzf_crc_on()) np2::launch_bgzf_crc32(s, g.d_blk.p, (uint32_t)n_blk, (const uint32_t *)(g.d_blk.p + n_blk), g.d_inf.p, g.d_status.p, g.d_status.p + w_bad);
             if (prof) {
                 HIPCHK(hipStreamSynchronize(s));
                 t_inf = np2h::now_ms();
@@ -2156,13 +2209,21 @@ bool fetch_records_gpu(np2_bam *bam, int tid, uint32_t L, uint32_t zone_lo, uint
         if (tailw[0]) { // which block, and why
             std::vector<uint32_t> stv(n_blk);
             HIPCHK(hipMemcpy(stv.data(), g.d_status.p, n_blk * 4, hipMemcpyDeviceToHost));
-            for (size_t i = 0; i < n_blk; ++i)
-                if (stv[i]) throw np2h::Np2Error(NP2_E_ARG, "BGZF inflate failed (block at file offset " + std::to_string(blks[i].file_off) + ", status " + std::to_string(stv[i]) + ")");
+            size_t i = 0;
+            while (i < n_blk && !stv[i]) ++i;
+            if (i < n_blk) {
+                const std::string msg = stv[i] == np2inf::ST_CRC_MISMATCH ? crc_msg(blks[i].file_off)
+                                                                           : "BGZF inflate failed (block at file offset " + std::to_string(blks[i].file_off) + ", status " + std::to_string(stv[i]) + ")";
+                if (i == 0 || !held_err.empty()) throw np2h::Np2Error(NP2_E_ARG, msg);
+                held_err = msg, cap_end = (size_t)blks[i].file_off; // (the blocks before it once more, by themselves)
+                continue;
+            }
         }
         const uint32_t flags = tailw[1];
         if (flags & np2::WALK_BAD) throw np2h::Np2Error(NP2_E_ARG, "BAM/SAM parsing failed!");
         if (flags & np2::WALK_MISALIGNED) return false;
         if ((flags & (np2::WALK_TAIL | np2::WALK_AT_END)) && !eof) { // the reference's records go on beyond the index's end: further
+            if (!held_err.empty()) throw np2h::Np2Error(NP2_E_ARG, held_err); // (into the damaged block)
             extra = std::max<size_t>((size_t)1 << 20, extra * 2 + c_bytes / 4);
             continue;
         }
@@ -2226,11 +2287,13 @@ int np2_bgzf_inflate_device(np2_ctx_t *cx, const uint8_t *bgzf, uint64_t n, uint
         BgzfBatch hdr;
         hdr.map = bgzf, hdr.map_len = (size_t)n, hdr.fpos = 0;
         std::vector<np2::InfBlock> tb;
+        std::vector<uint32_t> crcs;
         uint64_t total = 0;
         for (;;) {
             BgzfBatch::Blk b;
             if (!hdr.read_raw(b)) break;
             tb.push_back(np2::InfBlock{(uint64_t)(b.c - bgzf), total, b.clen, b.isize});
+            crcs.push_back(b.crc);
             total += b.isize;
         }
         *out_len = total;
@@ -2239,10 +2302,11 @@ int np2_bgzf_inflate_device(np2_ctx_t *cx, const uint8_t *bgzf, uint64_t n, uint
         GpuFetch g;
         g.d_comp.ensure(n + 64);
         g.d_inf.ensure(total + 64);
-        g.d_blk.ensure(tb.size() + 1);
+        g.d_blk.ensure(blk_table_slots(tb.size()));
         g.d_status.ensure(tb.size() + 8);
         g.upload(bgzf, (size_t)n, g.d_comp.p, s);
         HIPCHK(hipMemcpyAsync(g.d_blk.p, tb.data(), tb.size() * sizeof(np2::InfBlock), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(g.d_blk.p + tb.size(), crcs.data(), crcs.size() * 4, hipMemcpyHostToDevice, s));
         HIPCHK(hipMemsetAsync(g.d_status.p, 0, (tb.size() + 4) * 4, s));
         HIPCHK(hipStreamSynchronize(s)); // (tb is pageable: the copy must have read it before it goes)
         HIPCHK(hipEventCreate(&e0));
@@ -2256,7 +2320,8 @@ int np2_bgzf_inflate_device(np2_ctx_t *cx, const uint8_t *bgzf, uint64_t n, uint
         }
         np2::launch_bgzf_inflate(s, g.d_blk.p, (uint32_t)tb.size(), g.d_comp.p, g.d_inf.p, g.d_status.p, g.d_status.p + tb.size(),
                                  kprof ? (unsigned long long *)d_prof.p : nullptr);
-        HIPCHK(hipEventRecord(e1, s));
+        HIPCHK(hipEventRecord(e1, s)); // (kernel_ms is the inflate kernel alone: the CRC check goes behind it)
+        if (bgzf_crc_on()) np2::launch_bgzf_crc32(s, g.d_blk.p, (uint32_t)tb.size(), (const uint32_t *)(g.d_blk.p + tb.size()), g.d_inf.p, g.d_status.p, g.d_status.p + tb.size());
         if (kprof) {
             std::vector<uint64_t> pr(tb.size() * 8);
             HIPCHK(hipMemcpyAsync(pr.data(), d_prof.p, pr.size() * 8, hipMemcpyDeviceToHost, s));
@@ -2277,7 +2342,51 @@ int np2_bgzf_inflate_device(np2_ctx_t *cx, const uint8_t *bgzf, uint64_t n, uint
         (void)hipEventDestroy(e0), (void)hipEventDestroy(e1);
         e0 = e1 = nullptr;
         for (size_t i = 0; i < tb.size(); ++i)
-            if (st[i]) throw np2h::Np2Error(NP2_E_ARG, "BGZF inflate failed (block " + std::to_string(i) + ", status " + std::to_string(st[i]) + ")");
+            if (st[i] == np2inf::ST_CRC_MISMATCH) throw np2h::Np2Error(NP2_E_ARG, "BGZF CRC32 mismatch (block " + std::to_string(i) + ")");
+            else if (st[i]) throw np2h::Np2Error(NP2_E_ARG, "BGZF inflate failed (block " + std::to_string(i) + ", status " + std::to_string(st[i]) + ")");
+        return NP2_OK;
+    }, [&](int code, const std::string &msg) {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+        (void)hipStreamSynchronize(cx->stream);
+        io_fail(code, msg);
+    });
+}
+
+int np2_crc32_device(np2_ctx_t *cx, const uint8_t *data, uint64_t n, const uint64_t *off, uint32_t n_pieces, uint32_t *crc_out, float *kernel_ms) {
+    if (!cx || (!data && n) || (n_pieces && (!off || !crc_out))) return NP2_E_ARG;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    return np2h::abi_guard([&] {
+        if (!n_pieces) {
+            if (kernel_ms) *kernel_ms = 0.f;
+            return NP2_OK;
+        }
+        std::vector<np2::InfBlock> tb(n_pieces);
+        for (uint32_t i = 0; i < n_pieces; ++i) {
+            if (off[i + 1] < off[i]) throw np2h::Np2Error(NP2_E_ARG, "np2_crc32_device: descending offsets");
+            if (off[i + 1] - off[i] > 65536u) throw np2h::Np2Error(NP2_E_ARG, "np2_crc32_device: a piece longer than 65536 bytes");
+            tb[i] = np2::InfBlock{0, off[i], 0, (uint32_t)(off[i + 1] - off[i])};
+        }
+        if (off[n_pieces] > n) throw np2h::Np2Error(NP2_E_ARG, "np2_crc32_device: offsets beyond the data");
+        HIPCHK(hipSetDevice(cx->device));
+        hipStream_t s = cx->stream;
+        GpuFetch g;
+        g.d_inf.ensure(n + 64);
+        g.d_blk.ensure((size_t)n_pieces + 1);
+        g.d_status.ensure((size_t)n_pieces + 8);
+        if (n) g.upload(data, (size_t)n, g.d_inf.p, s);
+        HIPCHK(hipMemcpyAsync(g.d_blk.p, tb.data(), tb.size() * sizeof(np2::InfBlock), hipMemcpyHostToDevice, s));
+        HIPCHK(hipStreamSynchronize(s)); // (tb is pageable: the copy must have read it before it goes)
+        HIPCHK(hipEventCreate(&e0));
+        HIPCHK(hipEventCreate(&e1));
+        HIPCHK(hipEventRecord(e0, s));
+        np2::launch_bgzf_crc32(s, g.d_blk.p, n_pieces, nullptr, g.d_inf.p, nullptr, nullptr, g.d_status.p);
+        HIPCHK(hipEventRecord(e1, s));
+        HIPCHK(hipMemcpyAsync(crc_out, g.d_status.p, (size_t)n_pieces * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (kernel_ms) HIPCHK(hipEventElapsedTime(kernel_ms, e0, e1));
+        (void)hipEventDestroy(e0), (void)hipEventDestroy(e1);
+        e0 = e1 = nullptr;
         return NP2_OK;
     }, [&](int code, const std::string &msg) {
         if (e0) (void)hipEventDestroy(e0);

@@ -12,7 +12,7 @@ assert BAMREC_DTYPE.itemsize == 40
 
 IO_SYMBOLS = ["np2_fasta_open", "np2_fasta_next", "np2_fasta_close", "np2_yak_load", "np2_yak_free", "np2_bam_open",
               "np2_bam_close", "np2_bam_n_refs", "np2_bam_ref_name", "np2_io_last_error", "np2_contig_from_records",
-              "np2_contig_from_bam", "np2_contig_export", "np2_ctx_create_from_files", "np2_bgzf_inflate_device"]
+              "np2_contig_from_bam", "np2_contig_export", "np2_ctx_create_from_files", "np2_bgzf_inflate_device", "np2_crc32_device"]
 
 
 class np2_front_opts_t(C.Structure):
@@ -78,6 +78,7 @@ def _bind_locked(L):
         L.np2_contig_from_bam.argtypes = [vp, vp, C.c_char_p, vp, C.c_uint32, C.POINTER(np2_front_opts_t), C.POINTER(vp)]
         L.np2_contig_export.argtypes = [vp, vp, C.POINTER(vp), C.POINTER(C.c_uint32), C.POINTER(vp), C.POINTER(C.c_uint64)]
         L.np2_bgzf_inflate_device.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_float)]
+        L.np2_crc32_device.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, vp, C.POINTER(C.c_float)]
         _bind_shard(L)
 
 
@@ -304,3 +305,19 @@ def bgzf_inflate_device(pol, data):
     if rc != 0:
         raise Np2Error(rc, "np2_bgzf_inflate_device: " + (L.np2_io_last_error() or b"").decode())
     return out[: n.value].copy(), float(ms.value)
+
+
+def crc32_device(pol, data, offsets):
+    """np2_crc32_device: CRC-32 (gzip) of the pieces data[offsets[i]:offsets[i + 1]] (each at most 65536 bytes) on the
+    polisher's device, by the kernel that checks every inflated BGZF block -> (uint32 array, kernel milliseconds)."""
+    L = _bind()
+    src = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else data, dtype=np.uint8)
+    off = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n_pieces = max(0, len(off) - 1)
+    out = np.zeros(max(1, n_pieces), dtype=np.uint32)
+    ms = C.c_float()
+    rc = L.np2_crc32_device(pol._h, src.ctypes.data if len(src) else None, len(src), off.ctypes.data if len(off) else None, n_pieces,
+                            out.ctypes.data, C.byref(ms))
+    if rc != 0:
+        raise Np2Error(rc, "np2_crc32_device: " + (L.np2_io_last_error() or b"").decode())
+    return out[:n_pieces].copy(), float(ms.value)

@@ -1,9 +1,12 @@
 #!/usr/bin/env python3
-"""Throughput of the BGZF inflate kernel and of a contig's front end through the device against the host pool:
-    python tools/inflate_probe.py [L] [depth]          (run through gpurun; taskset -c 0-1 ... for a rank's share of a node)
+"""Throughput of the BGZF inflate kernel, of the CRC-32 kernel behind it, and of a contig's front end through the device
+against the host pool:
+    python tools/inflate_probe.py [L] [depth] [--kernels]      (taskset -c 0-1 ... for a rank's share of a node)
 Writes a synthetic BAM of one contig (no qualities: QUAL = 0xFF), inflates the whole file on the device
-(np2_bgzf_inflate_device: kernel time by HIP events), then builds the resident pileup from the BAM with NP2_INFLATE=gpu and
-with the host pool, three times each in fresh processes (the switch is read once per process)."""
+(np2_bgzf_inflate_device: kernel time by HIP events; the CRC check runs behind it, outside that time), sums the inflated
+blocks with the CRC kernel (np2_crc32_device: kernel time by HIP events), then — unless --kernels — builds the resident
+pileup from the BAM with NP2_INFLATE=gpu and with the host pool, four times each in fresh processes (the switch is read once
+per process)."""
 import os, subprocess, sys, tempfile, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -12,8 +15,10 @@ from nextpolish2_amd import io as np2io
 from nextpolish2_amd.bamio import write_bam_raw
 from nextpolish2_amd.synth import Synth
 
-L = int(sys.argv[1]) if len(sys.argv) > 1 else 4641652
-depth = int(sys.argv[2]) if len(sys.argv) > 2 else 30
+kernels_only = "--kernels" in sys.argv
+argv = [a for a in sys.argv[1:] if a != "--kernels"]
+L = int(argv[0]) if len(argv) > 0 else 4641652
+depth = int(argv[1]) if len(argv) > 1 else 30
 td = tempfile.mkdtemp()
 s = Synth(L, depth=depth, seed=5)
 t = time.time()
@@ -28,7 +33,19 @@ for i in range(3):
     out, ms = np2io.bgzf_inflate_device(pol, data)
     print(f"inflate kernel: {len(data) / 1e6:.1f} MB -> {len(out) / 1e6:.1f} MB in {ms:.2f} ms = {len(out) / ms / 1e6:.1f} GB/s inflated "
           f"({len(data) / ms / 1e6:.1f} GB/s of file); call {1e3 * (time.time() - t):.1f} ms", flush=True)
-import zlib
+# the CRC kernel on the same blocks: piece i = block i's inflated bytes
+isz, p = [], 0
+while p < len(data):
+    bsize = int(data[p + 16]) + (int(data[p + 17]) << 8) + 1
+    isz.append(int.from_bytes(data[p + bsize - 4:p + bsize].tobytes(), "little"))
+    p += bsize
+off = np.concatenate([[0], np.cumsum(isz)]).astype(np.uint64)
+for i in range(3):
+    crc, cms = np2io.crc32_device(pol, out, off)
+    print(f"crc32 kernel: {len(isz)} blocks, {len(out) / 1e6:.1f} MB in {cms:.3f} ms = {len(out) / cms / 1e6:.1f} GB/s; "
+          f"{100 * cms / ms:.1f} % of the inflate kernel's {ms:.2f} ms", flush=True)
+if kernels_only:
+    sys.exit(0)
 code = ("import sys, time, numpy as np; sys.path.insert(0, %r)\n"
         "from nextpolish2_amd import io as np2io\n"
         "pol = np2io.polisher_from_yak_files([sys.argv[3]])\n"
