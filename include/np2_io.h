@@ -111,6 +111,42 @@ int np2_crc32_device(np2_ctx_t *ctx, const uint8_t *data, uint64_t n, const uint
 int np2_contig_export(np2_ctx_t *ctx, np2_contig_t *c, np2_read_t **reads, uint32_t *n_reads,
                       uint8_t **nibbles, uint64_t *nib_bytes);
 
+/* ---- k-mer counting: short reads -> yak tables (the `yak count` half of the reference workflow, README steps 2-3) ----
+ * Canonical k-mers of FASTA / FASTQ / one-sequence-per-line files (plain or gzip) counted on the device, with the
+ * semantics of the reference's lookup side (kmer.rs:255-287 iter2kmer, 102-110 to_hash, 52-58 file word): for every k-mer
+ * of the reads, KmerInfo::get on the result returns min(occurrences, 1023).  Words inside a bucket are written in
+ * ascending order.  Errors: np2_io_last_error().  Arguments (k, paths, options) are checked before the first device call:
+ * k >= 32 or k < 2 is NP2_E_UNSUPPORTED, a file that cannot be opened or a damaged / truncated gzip NP2_E_ARG.
+ * Test hooks, read once per call: NP2_KCOUNT_TEST_CAP_LOG2 (initial sub-table capacity), NP2_KCOUNT_TEST_PIECE (piece size
+ * in bytes), NP2_KCOUNT_TEST_PASSES (bucket-range passes). */
+typedef struct np2_kcount_opts {
+    uint16_t min_count; /* words below it are not emitted (an exact threshold); 0 and 1: everything */
+    uint64_t mem_bytes; /* device memory for the counting tables of all k together; 0: half of what is free at the call.
+                         * A run that would outgrow it counts in several passes over bucket ranges, reading its input again
+                         * for each (an input that cannot be read again, a pipe, is NP2_E_ARG in that case only) */
+} np2_kcount_opts_t;
+/* sequence files -> one table per ks[i]; out[i] released with np2_yak_free */
+int np2_kcount_files(int device, const char *const *paths, int n_paths, const uint32_t *ks, int n_k,
+                     const np2_kcount_opts_t *opts, np2_yak_t *out /* [n_k] */);
+/* the same over a separator stream in host memory: the reads' bytes with one '\n' (any non-base byte) between reads */
+int np2_kcount_bytes(int device, const uint8_t *seq, uint64_t n, const uint32_t *ks, int n_k,
+                     const np2_kcount_opts_t *opts, np2_yak_t *out);
+/* straight to yak v2 dumps on disk, bucket by bucket (no host copy of a whole table) */
+int np2_kcount_files_to_dumps(int device, const char *const *paths, int n_paths, const uint32_t *ks, int n_k,
+                              const np2_kcount_opts_t *opts, const char *const *out_paths);
+/* straight to a polish context: the tables never leave HBM (ordered by k).  Single-pass runs only: a run that would need
+ * passes returns NP2_E_NOMEM and says so */
+int np2_ctx_create_from_reads(np2_ctx_t **out, int device, const char *const *paths, int n_paths,
+                              const uint32_t *ks, int n_k, const np2_kcount_opts_t *opts);
+/* statistics of the last successful counting call on this thread (any pointer may be NULL): k-mers hashed and slots
+ * claimed (summed over the k values), hashes that went through the spill list, table growths, passes, ms in the count
+ * kernel (HIP events), ms the counting thread waited for its reader threads */
+int np2_kcount_last_stats(uint64_t *kmers, uint64_t *distinct, uint64_t *spilled, uint32_t *growths, uint32_t *passes,
+                          float *kernel_ms, float *read_ms);
+/* host only, no device: the separator stream the reader makes of one sequence file (every read followed by one '\n');
+ * release with np2_free */
+int np2_seqfile_stream(const char *path, uint8_t **out, uint64_t *n);
+
 #ifdef __cplusplus
 }
 #endif

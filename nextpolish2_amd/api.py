@@ -34,6 +34,8 @@ IO_ABI_SYMBOLS = [
     "np2_bam_n_refs", "np2_bam_ref_name", "np2_io_last_error", "np2_contig_from_records", "np2_contig_from_bam",
     "np2_contig_export", "np2_shard_bam_begin", "np2_shard_bam_finish", "np2_shard_bam_abort", "np2_ctx_create_from_files",
     "np2_bgzf_inflate_device", "np2_crc32_device",
+    "np2_kcount_files", "np2_kcount_bytes", "np2_kcount_files_to_dumps", "np2_ctx_create_from_reads", "np2_kcount_last_stats",
+    "np2_seqfile_stream",
 ]
 
 ERRORS = {-1: "NP2_E_ARG", -2: "NP2_E_DEVICE", -3: "NP2_E_NOMEM", -4: "NP2_E_UNSUPPORTED", -5: "NP2_E_REFPANIC"}

@@ -47,7 +47,12 @@ def build_parser():
     p = argparse.ArgumentParser(prog="nextPolish2", description="Repeat-aware polishing genomes assembled using HiFi long reads")
     p.add_argument("bam", type=_existing, metavar="HiFi.map.bam", help="HiFi-to-ref mapping file in sorted BAM format")
     p.add_argument("fa", type=_existing, metavar="genome.fa[.gz]", help="genome assembly file in [GZIP] FASTA format")
-    p.add_argument("yak", type=_existing, nargs="+", metavar="short.read.yak", help="one or more k-mer dataset in yak format")
+    p.add_argument("yak", type=_existing, nargs="*", metavar="short.read.yak", help="one or more k-mer dataset in yak format")
+    p.add_argument("--sr", type=_existing, action="append", default=[], metavar="FILE",
+                   help="short reads (FASTA / FASTQ[.gz]; may repeat): count their k-mers on the GPU instead of reading yak dumps")
+    p.add_argument("--sr_k", default="21,31", metavar="K[,K...]", help="k-mer sizes counted from --sr [21,31]")
+    p.add_argument("--sr_min_count", type=int, default=None, metavar="N",
+                   help="drop k-mers of --sr counted fewer than N times [2, or -k/--min_kmer_count where that is smaller]")
     p.add_argument("-o", "--out", default=None, metavar="FILE", help="output file [stdout]")
     p.add_argument("-u", "--uppercase", action="store_true", help="output in uppercase sequences")
     p.add_argument("--out_pos", action="store_true", help=argparse.SUPPRESS)
@@ -216,7 +221,21 @@ def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     t0 = time.time()
     cpu0 = _cpu_seconds()  # (main() may run inside a longer-lived process: report this call's CPU time, not the process's)
-    a = build_parser().parse_args(argv)
+    parser = build_parser()
+    a = parser.parse_args(argv)
+    if not a.sr and not a.yak:  # (what nargs="+" said before --sr made the positional optional)
+        parser.error("the following arguments are required: short.read.yak")
+    if a.sr and a.yak:
+        parser.error("give either short.read.yak files or --sr reads, not both")
+    if a.sr:
+        try:
+            a.sr_ks = sorted(int(k) for k in a.sr_k.split(","))
+        except ValueError:
+            parser.error("--sr_k takes comma-separated integers")
+        if not a.sr_ks or any(k < 2 or k >= 32 for k in a.sr_ks):
+            parser.error("--sr_k: only 2 <= k < 32 is supported")
+        if a.sr_min_count is None:  # no word the polish would look at is ever dropped
+            a.sr_min_count = max(1, min(2, a.min_kmer_count))
     if a.model.lower() not in ("ref", "len"):
         raise SystemExit("error: invalid value for --model (ref|len)")
     for y in a.yak:  # (before the output file exists: a broken dump must not leave a partial output behind)
@@ -254,6 +273,8 @@ def main(argv=None):
 
     def load_yaks():
         t_y = time.time()
+        if a.sr:  # (under torch.distributed.run every rank counts for itself: the tables are replicated per GPU anyway)
+            return np2io.count_kmers(a.sr, a.sr_ks, min_count=a.sr_min_count, device=a.device)
         with ThreadPoolExecutor(max_workers=max(1, len(a.yak))) as ex:  # (the loader runs outside the GIL: one thread per dump)
             ys = sorted(ex.map(np2io.load_yak, a.yak), key=lambda y: y.k)  # option.rs:238
         if prof:
@@ -292,7 +313,10 @@ def main(argv=None):
         t_b = time.time()
         if prof:
             print(f"[np2 profile] k-mer dumps: start at +{t_b - t0:.3f} s", file=sys.stderr)
-        pol = np2io.polisher_from_yak_files(a.yak, device=a.device)
+        if a.sr:  # reads -> HBM tables that never visit the host (np2_ctx_create_from_reads)
+            pol = np2io.polisher_from_reads(a.sr, a.sr_ks, min_count=a.sr_min_count, device=a.device)
+        else:
+            pol = np2io.polisher_from_yak_files(a.yak, device=a.device)
         if prof:
             print(f"[np2 profile] k-mer dumps read + tables in HBM {time.time() - t_b:.3f} s (at +{time.time() - t0:.3f} s)", file=sys.stderr)
         return pol
@@ -455,7 +479,7 @@ def main(argv=None):
             out.flush()
             if prof:
                 print(f"[np2 profile] last record written at +{time.time() - t0:.3f} s", file=sys.stderr)
-        if not base_future:
+        if not base_future and not a.sr:
             load_yaks()  # (an assembly of pass-through contigs only: a broken dump must still be reported)
         if prof:
             print(f"[np2 profile] contexts released at +{time.time() - t0:.3f} s", file=sys.stderr)

@@ -26,6 +26,7 @@
 
 #include "np2_inflate.hpp"
 #include "np2_inflate_core.hpp"
+#include "np2_kcount.hpp"
 namespace {
 
 // Raw-deflate decoder for BGZF blocks (each block is one complete deflate stream of known inflated size): libdeflate's
@@ -106,6 +107,11 @@ int io_fail(int code, const std::string &m) {
     g_io_err = m;
     return code;
 }
+
+} // namespace
+// (the message slot for the entry points of other translation units: np2_kcount_host.cpp)
+int np2h::io_set_error(int code, const std::string &m) { return io_fail(code, m); }
+namespace {
 
 // ---------------------------------------------------------------------------------------------
 // FASTA[.gz] (kseq semantics: name = header up to the first whitespace, sequence lines concatenated)

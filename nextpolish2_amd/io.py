@@ -1,5 +1,6 @@
 """ctypes binding of include/np2_io.h: FASTA[.gz] / yak / indexed BAM readers and the GPU columnariser."""
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -12,13 +13,19 @@ assert BAMREC_DTYPE.itemsize == 40
 
 IO_SYMBOLS = ["np2_fasta_open", "np2_fasta_next", "np2_fasta_close", "np2_yak_load", "np2_yak_free", "np2_bam_open",
               "np2_bam_close", "np2_bam_n_refs", "np2_bam_ref_name", "np2_io_last_error", "np2_contig_from_records",
-              "np2_contig_from_bam", "np2_contig_export", "np2_ctx_create_from_files", "np2_bgzf_inflate_device", "np2_crc32_device"]
+              "np2_contig_from_bam", "np2_contig_export", "np2_ctx_create_from_files", "np2_bgzf_inflate_device", "np2_crc32_device",
+              "np2_kcount_files", "np2_kcount_bytes", "np2_kcount_files_to_dumps", "np2_ctx_create_from_reads", "np2_kcount_last_stats",
+              "np2_seqfile_stream"]
 
 
 class np2_front_opts_t(C.Structure):
     _fields_ = [("min_read_len", C.c_uint32), ("min_map_len", C.c_uint32), ("min_map_fra", C.c_float),
                 ("min_map_qual", C.c_int16), ("max_clip_len", C.c_uint32), ("use_supplementary", C.c_uint8),
                 ("use_secondary", C.c_uint8)]
+
+
+class np2_kcount_opts_t(C.Structure):
+    _fields_ = [("min_count", C.c_uint16), ("mem_bytes", C.c_uint64)]
 
 
 class FrontOpts:
@@ -80,6 +87,7 @@ def _bind_locked(L):
         L.np2_bgzf_inflate_device.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_float)]
         L.np2_crc32_device.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, vp, C.POINTER(C.c_float)]
         _bind_shard(L)
+        _bind_kcount(L)
 
 
 def _bind_shard(L):
@@ -89,6 +97,16 @@ def _bind_shard(L):
     L.np2_shard_bam_finish.argtypes = [vp, vp, C.c_uint64, C.POINTER(np2_shard_plan_t), C.POINTER(vp), C.POINTER(C.c_uint32)]
     L.np2_shard_bam_abort.argtypes = [vp]
     L.np2_shard_bam_abort.restype = None
+
+
+def _bind_kcount(L):
+    vp, ko, cpp = C.c_void_p, C.POINTER(np2_kcount_opts_t), C.POINTER(C.c_char_p)
+    L.np2_kcount_files.argtypes = [C.c_int, cpp, C.c_int, vp, C.c_int, ko, C.POINTER(np2_yak_t)]
+    L.np2_kcount_bytes.argtypes = [C.c_int, vp, C.c_uint64, vp, C.c_int, ko, C.POINTER(np2_yak_t)]
+    L.np2_kcount_files_to_dumps.argtypes = [C.c_int, cpp, C.c_int, vp, C.c_int, ko, cpp]
+    L.np2_ctx_create_from_reads.argtypes = [C.POINTER(vp), C.c_int, cpp, C.c_int, vp, C.c_int, ko]
+    L.np2_kcount_last_stats.argtypes = [C.POINTER(C.c_uint64)] * 3 + [C.POINTER(C.c_uint32)] * 2 + [C.POINTER(C.c_float)] * 2
+    L.np2_seqfile_stream.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_uint64)]
 
 
 def _io_check(rc):
@@ -162,6 +180,94 @@ def polisher_from_yak_files(paths, device=0):
     p._h = h
     p.device = device
     return p
+
+
+def _paths(paths):
+    paths = [paths] if isinstance(paths, (str, os.PathLike)) else list(paths)
+    return (C.c_char_p * len(paths))(*[os.fspath(p).encode() for p in paths]), len(paths)
+
+
+def _ks(ks):
+    return np.ascontiguousarray(list(ks), dtype=np.uint32)
+
+
+def seqfile_stream(path):
+    """np2_seqfile_stream (host only): the separator stream the counter's reader makes of one FASTA / FASTQ /
+    one-sequence-per-line file, plain or gzip: every read's bytes followed by one newline."""
+    L = _bind()
+    p, n = C.c_void_p(), C.c_uint64()
+    _io_check(L.np2_seqfile_stream(os.fspath(path).encode(), C.byref(p), C.byref(n)))
+    try:
+        return C.string_at(p.value, n.value) if n.value else b""
+    finally:
+        L.np2_free(p)
+
+
+def count_kmers(inputs, ks, min_count=1, device=0, mem_bytes=0):
+    """Canonical k-mers of short reads counted on the device -> one Yak per k (np2_kcount_files / np2_kcount_bytes).
+    `inputs`: sequence file paths (FASTA / FASTQ / one sequence per line, plain or gzip), or ONE bytes object holding a
+    separator stream (the reads' bytes with a newline, or any non-base byte, between reads).  Words with a count below
+    `min_count` are left out (an exact threshold); counts saturate at 1023."""
+    import weakref
+    L = _bind()
+    kk = _ks(ks)
+    o = np2_kcount_opts_t(min_count, mem_bytes)
+    out = (np2_yak_t * max(1, len(kk)))()
+    if isinstance(inputs, (bytes, bytearray, memoryview)):
+        buf = np.frombuffer(inputs, dtype=np.uint8)
+        _io_check(L.np2_kcount_bytes(device, buf.ctypes.data if len(buf) else None, len(buf), kk.ctypes.data, len(kk), C.byref(o), out))
+    else:
+        arr, n = _paths(inputs)
+        _io_check(L.np2_kcount_files(device, arr, n, kk.ctypes.data, len(kk), C.byref(o), out))
+    yaks = []
+    for i in range(len(kk)):
+        y = np2_yak_t.from_buffer_copy(out[i])
+        off = np.ctypeslib.as_array(y.bucket_off, shape=((1 << y.pre) + 1,)).copy()
+        base = np.ctypeslib.as_array(y.words, shape=(max(int(y.n_words), 1),))
+        yk = Yak(y.k, base[: int(y.n_words)], off, pre=y.pre)
+        weakref.finalize(yk, L.np2_yak_free, y)  # (as in load_yak: the words are used where the library put them)
+        yaks.append(yk)
+    return yaks
+
+
+def count_kmers_to_files(paths, ks, out_paths, min_count=1, device=0, mem_bytes=0):
+    """np2_kcount_files_to_dumps: sequence files -> one yak v2 dump per k, written bucket by bucket."""
+    L = _bind()
+    kk = _ks(ks)
+    if len(out_paths) != len(kk):
+        raise ValueError("one output path per k")
+    arr, n = _paths(paths)
+    outs, _ = _paths(out_paths)
+    o = np2_kcount_opts_t(min_count, mem_bytes)
+    _io_check(L.np2_kcount_files_to_dumps(device, arr, n, kk.ctypes.data, len(kk), C.byref(o), outs))
+
+
+def polisher_from_reads(paths, ks, min_count=1, device=0, mem_bytes=0):
+    """np2_ctx_create_from_reads: a Polisher whose HBM k-mer tables are counted from the reads and never visit the host
+    (tables ordered by k, option.rs:238).  Single-pass runs only."""
+    from .api import Polisher
+    L = _bind()
+    kk = _ks(ks)
+    arr, n = _paths(paths)
+    o = np2_kcount_opts_t(min_count, mem_bytes)
+    h = C.c_void_p()
+    _io_check(L.np2_ctx_create_from_reads(C.byref(h), device, arr, n, kk.ctypes.data, len(kk), C.byref(o)))
+    p = Polisher.__new__(Polisher)
+    p._yaks = []
+    p._h = h
+    p.device = device
+    return p
+
+
+def kcount_last_stats():
+    """np2_kcount_last_stats: figures of the last successful counting call on this thread."""
+    L = _bind()
+    a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    g, p = C.c_uint32(), C.c_uint32()
+    km, rm = C.c_float(), C.c_float()
+    L.np2_kcount_last_stats(C.byref(a), C.byref(b), C.byref(c), C.byref(g), C.byref(p), C.byref(km), C.byref(rm))
+    return {"kmers": a.value, "distinct": b.value, "spilled": c.value, "growths": g.value, "passes": p.value,
+            "kernel_ms": km.value, "read_ms": rm.value}
 
 
 def write_yak(path, yak):

@@ -1,0 +1,252 @@
+"""The k-mer counter on the device (np2_kcount_*, np2_ctx_create_from_reads, python -m nextpolish2_amd.count, the command
+line's --sr) against the numpy counter of tests/test_kcount_cpu.py and the committed dumps.
+
+Fixture: tests/golden/ref_bundle/sr.seq.{0,1,2}.gz, the sequence lines of the reference's two test read files (see
+test_kcount_cpu.py).  Every case is one bounded subprocess or in-process call."""
+import gzip
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from nextpolish2_amd import Opts, Polisher, api
+from nextpolish2_amd import io as np2io
+from nextpolish2_amd._types import Yak
+from test_kcount_cpu import BUNDLE, FIXTURE, fixture_stream, numpy_count, stream_hashes
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ASM = os.path.join(ROOT, "tests", "golden", "ref_test_asm.fa.gz")
+BAM = os.path.join(BUNDLE, "hifi.map.sort.bam")
+ENV = dict(os.environ, PYTHONPATH=ROOT)
+KS = [2, 15, 16, 21, 31]
+
+
+def committed(k):
+    return open(os.path.join(BUNDLE, f"k{k}.yak"), "rb").read()
+
+
+def same_tables(yaks, stream, ks, min_count):
+    for y, k in zip(yaks, ks):
+        words, off = numpy_count(stream, k, min_count)
+        assert y.k == k and y.pre == 10
+        assert np.array_equal(y.bucket_off, off), (k, min_count)
+        assert np.array_equal(y.words, words), (k, min_count)
+
+
+# ---- 4. golden ------------------------------------------------------------------------------------------------------
+def test_golden_dumps_from_the_fixture(tmp_path):
+    outs = [str(tmp_path / "k21.yak"), str(tmp_path / "k31.yak")]
+    np2io.count_kmers_to_files(FIXTURE, [21, 31], outs, min_count=2)
+    assert open(outs[0], "rb").read() == committed(21)
+    assert open(outs[1], "rb").read() == committed(31)
+    st = np2io.kcount_last_stats()
+    assert st["kmers"] == 8605480 + 7943520 and st["distinct"] == 456279 + 593788 and st["passes"] == 1
+
+
+def test_golden_dumps_through_the_count_module(tmp_path):
+    outs = [str(tmp_path / "a.yak"), str(tmp_path / "b.yak")]
+    r = subprocess.run([sys.executable, "-m", "nextpolish2_amd.count", "-k", "21", "-o", outs[0], "-k", "31", "-o", outs[1], "-m", "2"] + FIXTURE,
+                       capture_output=True, env=ENV, timeout=600)
+    assert r.returncode == 0, r.stderr.decode()
+    assert open(outs[0], "rb").read() == committed(21) and open(outs[1], "rb").read() == committed(31)
+
+
+# ---- 5. end to end ----------------------------------------------------------------------------------------------------
+def test_cli_polishes_from_reads(tmp_path):
+    cmd = [sys.executable, "-m", "nextpolish2_amd.cli", "-t", "5", "-L", "1000", BAM, ASM]
+    for p in FIXTURE:
+        cmd += ["--sr", p]
+    r = subprocess.run(cmd, capture_output=True, env=ENV, timeout=600)
+    assert r.returncode == 0, r.stderr.decode()
+    assert r.stdout == gzip.open(os.path.join(BUNDLE, "expected.fa.gz"), "rb").read()
+
+
+# ---- 6. random reads ---------------------------------------------------------------------------------------------------
+def random_reads(seed=3, n_reads=6000):
+    """Reads of both strands of the Synth haplotypes with substitutions and indels, N runs, lower case, U, reads shorter
+    than k, a 3 000-base homopolymer and a tandem repeat (both past saturation) -> separator stream."""
+    from nextpolish2_amd.synth import Synth
+    s = Synth(40000, depth=4, seed=seed, diploid=True, read_len_mean=3000.0, read_len_sd=500.0)
+    haps = [np.frombuffer(h, dtype=np.uint8) for h in (s.hap1, s.hap2)]
+    assert all(set(h.tobytes()) <= set(b"ACGT") and len(h) >= 30000 for h in haps)
+    rng = np.random.default_rng(seed)
+    comp = np.zeros(256, np.uint8)
+    for a, b in zip(b"ACGTNacgtn", b"TGCANtgcan"):
+        comp[a] = b
+    reads = []
+    for i in range(n_reads):
+        n = int(rng.integers(5, 40)) if i % 50 == 0 else int(rng.integers(100, 251))
+        hap = haps[int(rng.integers(0, 2))]
+        at = int(rng.integers(0, len(hap) - n))
+        r = hap[at:at + n].copy()
+        if i % 2:
+            r = comp[r[::-1]]
+        sub = rng.random(n) < 0.01
+        r[sub] = rng.choice(np.frombuffer(b"ACGT", dtype=np.uint8), size=int(sub.sum()))
+        r = r[rng.random(n) >= 0.002]  # deletions
+        ins = np.flatnonzero(rng.random(len(r)) < 0.002)
+        r = np.insert(r, ins, rng.choice(np.frombuffer(b"ACGT", dtype=np.uint8), size=len(ins)))
+        if i % 37 == 0 and len(r) > 20:
+            r[10:10 + int(rng.integers(1, 8))] = ord("N")
+        if i % 11 == 0:
+            r = np.frombuffer(r.tobytes().lower(), dtype=np.uint8)
+        if i % 13 == 0:
+            r = np.frombuffer(r.tobytes().replace(b"T", b"U").replace(b"t", b"u"), dtype=np.uint8)
+        reads.append(r.tobytes())
+    reads += [b"A" * 3000, b"ACGGT" * 700, b"AATT", b"", b"C"]
+    return b"\n".join(reads) + b"\n"
+
+
+@pytest.mark.parametrize("min_count", [1, 2, 5])
+def test_random_reads_equal_the_numpy_counter(min_count):
+    stream = random_reads()
+    assert max(np.unique(stream_hashes(stream, 21), return_counts=True)[1]) > 1023  # (saturation does occur)
+    same_tables(np2io.count_kmers(stream, KS, min_count=min_count), stream, KS, min_count)
+
+
+def test_random_reads_from_files_equal_the_in_memory_stream(tmp_path):
+    stream = random_reads(seed=4, n_reads=1500)
+    reads = stream.split(b"\n")[:-1]
+    fq, fa = tmp_path / "a.fq.gz", tmp_path / "b.fa"
+    half = len(reads) // 2
+    fq.write_bytes(gzip.compress(b"".join(b"@r%d\n%s\n+\n%s\n" % (i, r, b"@" * len(r)) for i, r in enumerate(reads[:half]))))
+    fa.write_bytes(b"".join(b">r%d\n%s\n%s\n" % (i, r[:60], r[60:]) for i, r in enumerate(reads[half:])))
+    same_tables(np2io.count_kmers([str(fq), str(fa)], [16, 31], min_count=1), stream, [16, 31], 1)
+
+
+# ---- 7. piece boundaries ----------------------------------------------------------------------------------------------
+def _count_in_child(tmp_path, stream, ks, min_count, env_extra, tag):
+    """count_kmers in a fresh process (the hooks are read per call, the environment is the child's): words, offsets, stats"""
+    src = tmp_path / f"{tag}.bin"
+    src.write_bytes(stream)
+    out = tmp_path / f"{tag}.npz"
+    code = ("import sys, numpy as np\nfrom nextpolish2_amd import io\n"
+            f"ys = io.count_kmers(open({str(src)!r}, 'rb').read(), {ks!r}, min_count={min_count})\n"
+            "st = io.kcount_last_stats()\n"
+            f"np.savez({str(out)!r}, **{{f'w{{i}}': y.words for i, y in enumerate(ys)}}, **{{f'o{{i}}': y.bucket_off for i, y in enumerate(ys)}}, "
+            "growths=st['growths'], spilled=st['spilled'], passes=st['passes'])\n")
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, env=dict(ENV, **env_extra), timeout=600)
+    assert r.returncode == 0, r.stderr.decode()[-3000:]
+    return np.load(out)
+
+
+@pytest.mark.parametrize("piece", [4096, 4097, 65521])
+def test_piece_boundaries_lose_and_double_nothing(tmp_path, piece):
+    stream = random_reads(seed=7, n_reads=2500)
+    got = _count_in_child(tmp_path, stream, [16, 31], 1, {"NP2_KCOUNT_TEST_PIECE": str(piece)}, f"p{piece}")
+    for i, k in enumerate([16, 31]):
+        words, off = numpy_count(stream, k, 1)
+        assert np.array_equal(got[f"w{i}"], words) and np.array_equal(got[f"o{i}"], off), (piece, k)
+
+
+# ---- 8. growth and spill ------------------------------------------------------------------------------------------------
+def certain_spill(stream, k, piece, cap_log2):
+    """The host's sizing rule replayed with the numpy counter: before a piece of n bytes the sub-table capacity doubles
+    until claimed + n <= 1024 * cap / 2; True as soon as some bucket holds more distinct k-mers than a sub-table has slots
+    (a lane must then have found its sub-table full).  Exact up to the first spill, which is all that is asked."""
+    data = stream + b"\n"  # (the in-memory source closes its stream with a separator)
+    cap, seen = 1 << cap_log2, np.zeros(0, np.uint64)
+    for a in range(0, len(data), piece):
+        n = min(piece, len(data) - a)
+        while len(seen) + n > 1024 * cap // 2:
+            cap *= 2
+        seen = np.union1d(seen, stream_hashes(data[max(0, a - (k - 1)):a + n], k))  # the k-mers that END in the piece
+        if np.bincount((seen & np.uint64(1023)).astype(np.int64), minlength=1024).max() > cap:
+            return True
+    return False
+
+
+def test_growth_and_spill(tmp_path):
+    """16 slots per sub-table and pieces of 512 bytes: the table as a whole always has room for the next piece, yet at
+    a mean of up to 8 words per 16-slot sub-table the fullest of 1 024 overflows (the Poisson tail): its k-mers go through
+    the spill list, the table grows and the list is replayed."""
+    stream = random_reads(seed=9, n_reads=2500)
+    assert certain_spill(stream, 16, 512, 4) and certain_spill(stream, 31, 512, 4)
+    got = _count_in_child(tmp_path, stream, [16, 31], 2, {"NP2_KCOUNT_TEST_CAP_LOG2": "4", "NP2_KCOUNT_TEST_PIECE": "512"}, "g")
+    for i, k in enumerate([16, 31]):
+        words, off = numpy_count(stream, k, 2)
+        assert np.array_equal(got[f"w{i}"], words) and np.array_equal(got[f"o{i}"], off), k
+    assert int(got["growths"]) >= 1
+    assert int(got["spilled"]) > 0
+
+
+# ---- 9. passes -----------------------------------------------------------------------------------------------------------
+def test_three_passes_equal_one(tmp_path):
+    stream = random_reads(seed=11, n_reads=2500)
+    got = _count_in_child(tmp_path, stream, [15, 21], 2, {"NP2_KCOUNT_TEST_PASSES": "3"}, "m")
+    assert int(got["passes"]) == 3
+    for i, k in enumerate([15, 21]):
+        words, off = numpy_count(stream, k, 2)
+        assert np.array_equal(got[f"w{i}"], words) and np.array_equal(got[f"o{i}"], off), k
+    code = ("from nextpolish2_amd import io, api\n"
+            "try:\n"
+            f"    io.polisher_from_reads({FIXTURE[:1]!r}, [21])\n"
+            "except api.Np2Error as e:\n"
+            "    print(e.code, e)\n")
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=dict(ENV, NP2_KCOUNT_TEST_PASSES="3"), timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert r.stdout.startswith("-3 ") and "one pass" in r.stdout
+
+
+# ---- 10. resident tables ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("min_count", [1, 2])
+def test_resident_tables_answer_like_uploaded_ones(min_count):
+    stream = fixture_stream()
+    ks = [21, 31]
+    ref_yaks = [Yak(k, *numpy_count(stream, k, min_count)) for k in ks]
+    pol = np2io.polisher_from_reads(FIXTURE, ks, min_count=min_count)
+    ref = Polisher(ref_yaks)
+    rng = np.random.default_rng(1)
+    reads = stream.split(b"\n")
+    subs = []
+    for _ in range(1000):
+        r = reads[int(rng.integers(0, 66196))]
+        a = int(rng.integers(0, 100))
+        subs.append(r[a:a + int(rng.integers(31, 51))])
+    for i, k in enumerate(ks):
+        present = np.unique(stream_hashes(stream, k))
+        absent = rng.integers(0, 1 << (2 * k), size=len(present), dtype=np.uint64)
+        absent = absent[~np.isin(absent, present)]
+        hs = np.concatenate([present, absent])
+        for mk in (1, 2, 5, 1023):
+            assert np.array_equal(pol.lookup_hashes(i, hs, mk), ref.lookup_hashes(i, hs, mk)), (k, mk)
+        cnt = pol.lookup_hashes(i, present, 1)
+        words, _ = numpy_count(stream, k, 1)
+        full = dict(zip(*[a.tolist() for a in np.unique(stream_hashes(stream, k), return_counts=True)]))
+        exp = np.array([min(full[h], 1023) if min(full[h], 1023) >= min_count else 0 for h in present.tolist()], dtype=np.uint16)
+        assert np.array_equal(cnt, exp), k
+        assert np.array_equal(pol.score_strings(i, subs, 1), ref.score_strings(i, subs, 1))
+        assert np.array_equal(pol.score_strings(i, subs, 5), ref.score_strings(i, subs, 5))
+
+
+def test_resident_path_matches_oracle_with_tables_from_reads():
+    """test_ref_bundle.py::test_resident_path_matches_oracle_on_the_bundle's comparison, once, with a polisher whose
+    tables were counted from the reads at min_count = 2 (the committed dumps' threshold)."""
+    from test_frontend_cpu import same_pileup
+    from test_ref_bundle import bundle, oracle_fasta
+    name, ref, recs, yaks = bundle()
+    o, fo = Opts(), np2io.FrontOpts()
+    pu, fa = oracle_fasta(name, ref, recs, yaks, o, fo)
+    pol = np2io.polisher_from_reads(FIXTURE, [21, 31], min_count=2)
+    bam = np2io.Bam(BAM)
+    c = np2io.contig_from_bam(pol, bam, name, ref, fo)
+    assert same_pileup(np2io.export_contig(pol, c, np.frombuffer(ref, dtype=np.uint8)), pu)
+    b, p = pol.polish_resident(c, o)
+    assert b">%s start:%d end:%d\n%s\n" % (name.encode(), p[0], p[-1], b.tobytes()) == fa
+
+
+# ---- 11. determinism ---------------------------------------------------------------------------------------------------------
+def test_two_runs_give_identical_bytes(tmp_path):
+    outs = [[str(tmp_path / f"r{r}k{k}.yak") for k in (21, 31)] for r in range(2)]
+    for o in outs:
+        np2io.count_kmers_to_files(FIXTURE, [21, 31], o, min_count=1)
+    for a, b in zip(*outs):
+        assert open(a, "rb").read() == open(b, "rb").read()
+    stream = fixture_stream()
+    words, off = numpy_count(stream, 21, 1)
+    y = np2io.load_yak(outs[0][0])
+    assert np.array_equal(y.words, words) and np.array_equal(y.bucket_off, off) and int((words & np.uint64(1023)).max()) == 1023
