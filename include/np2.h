@@ -130,6 +130,29 @@ int np2_score_strings(np2_ctx_t *ctx, int yak_idx, const uint8_t *strs, const ui
 int np2_lookup_hashes(np2_ctx_t *ctx, int yak_idx, const uint64_t *hashes, uint64_t n,
                       uint16_t min_kmer_count, uint16_t *counts);
 
+/* K-mer QV of sequences against yak table `yak_idx` (the `yak qv` / Merqury measurement): per sequence the number of
+ * k-mers (every position counts; ACGTUacgtu are bases, any other byte resets the run; no k-mer spans two sequences) and
+ * of ABSENT ones.  count(k-mer) is the table's answer as the polish sees it (kmer.rs:123-125 after
+ * retrieve_kmers(min_count)): the stored count if it is >= min_count, else 0; absent means count == 0; min_count 0 and
+ * 1 both mean "present at all".  A table counted with a threshold of its own (--sr_min_count 2, yak count -b 37) holds
+ * no singletons: they are absent by construction.
+ * QV (Merqury): P = 1 - n_absent / n_kmers, E = 1 - P^(1/k), QV = -10 log10(E).
+ * hist (1024 counters, or NULL): hist[c] = k-mers with count c.
+ * absent_bits (or NULL): one bitmap per sequence, byte-aligned per sequence (sequence i starts at byte
+ * sum over j < i of ceil(len_j / 8)), least significant bit first; bit e is set exactly when the k-mer ENDING at base e
+ * (bases e - k + 1 .. e) is valid and absent.
+ * kernel_ms (or NULL): HIP-event time of the scan kernel alone.
+ * NP2_E_ARG, before anything is launched and with a message in np2_last_error: yak_idx out of range, descending off,
+ * out == NULL, a NULL pointer with a non-zero length.  n == 0 and empty sequences are fine. */
+typedef struct np2_qv { uint64_t n_kmers, n_absent; } np2_qv_t;
+/* sequences strs[off[i] .. off[i+1]), i < n; streamed in pieces of fixed size: any total length */
+int np2_qv_strings(np2_ctx_t *ctx, int yak_idx, const uint8_t *strs, const uint64_t *off, uint64_t n, uint16_t min_count,
+                   np2_qv_t *out, uint64_t *hist, uint8_t *absent_bits, float *kernel_ms);
+/* one sequence already on ctx's device (np2_last_result_device of this context; a sequence another context or stream
+ * wrote must be complete before the call); any alignment, nothing around it is read as a base */
+int np2_qv_device(np2_ctx_t *ctx, int yak_idx, const uint8_t *dev_seq, uint64_t len, uint16_t min_count, np2_qv_t *out,
+                  uint64_t *hist, uint8_t *absent_bits, float *kernel_ms);
+
 /* Stage-level exports for kernel parity tests and profiling.
  * After np2_polish_resident with tracing enabled, np2_trace_get returns a pointer to a
  * host copy of intermediate `name` of pass `pass` (valid until the next polish call). */

@@ -26,6 +26,7 @@ ABI_SYMBOLS = [
     "np2_shard_begin", "np2_shard_passes_left", "np2_shard_vote", "np2_vote_decide", "np2_shard_apply", "np2_shard_final",
     "np2_shard_final_device", "np2_shard_fetch", "np2_alloc_pinned", "np2_trim_device_cache",
     "np2_shard_end", "np2_swiss_order", "np2_batch_set_timing", "np2_batch_set_priority", "np2_batch_last_diff_ms", "np2_batch_stats", "np2_batch_last_call_ms",
+    "np2_qv_strings", "np2_qv_device",
 ]
 
 # include/np2_io.h (input side; bound by nextpolish2_amd.io)
@@ -82,6 +83,8 @@ def _lib_locked():
         L.np2_free.argtypes = [vp]
         L.np2_score_strings.argtypes = [vp, C.c_int, vp, vp, u64, u16, vp]
         L.np2_lookup_hashes.argtypes = [vp, C.c_int, vp, u64, u16, vp]
+        L.np2_qv_strings.argtypes = [vp, C.c_int, vp, vp, u64, u16, vp, vp, vp, C.POINTER(C.c_float)]
+        L.np2_qv_device.argtypes = [vp, C.c_int, vp, u64, u16, vp, vp, vp, C.POINTER(C.c_float)]
         L.np2_ctx_set_trace.argtypes = [vp, C.c_int]
         L.np2_ctx_set_timing.argtypes = [vp, C.c_int]
         L.np2_ctx_set_timing.restype = None
@@ -163,6 +166,25 @@ def _owned(ptr, n, ctype):
     base = np.asarray(_Raw(ptr.value, max(n, 1), _TYPESTR[ctype]))
     weakref.finalize(base, lib().np2_free, C.c_void_p(ptr.value))
     return base[:n]
+
+
+class QvStats:
+    """What np2_qv_strings / np2_qv_device return.  stats: uint64 array (n, 2) of (n_kmers, n_absent) per sequence;
+    hist: uint64[1024] (hist[c] = k-mers with count c) or None; bits: one uint8 array per sequence (ceil(len / 8) bytes,
+    least significant bit first, bit e = the k-mer ending at base e is valid and absent) or None; kernel_ms: HIP-event time
+    of the scan kernel alone."""
+    __slots__ = ("stats", "hist", "bits", "kernel_ms")
+
+    def __init__(self, stats, hist, bits, kernel_ms):
+        self.stats, self.hist, self.bits, self.kernel_ms = stats, hist, bits, kernel_ms
+
+    @property
+    def n_kmers(self):
+        return int(self.stats[:, 0].sum())
+
+    @property
+    def n_absent(self):
+        return int(self.stats[:, 1].sum())
 
 
 class ResidentContig:
@@ -330,6 +352,40 @@ class Polisher:
         self._check(lib().np2_lookup_hashes(self._h, yak_idx, h.ctypes.data, h.shape[0], min_kmer_count,
                                             out.ctypes.data))
         return out
+
+    def qv_strings(self, yak_idx, seqs, min_count=1, hist=False, bits=False):
+        """np2_qv_strings: k-mers and absent k-mers of every sequence of `seqs` (bytes-like each) against table `yak_idx`
+        -> QvStats.  count(k-mer) is the stored count if >= min_count, else 0; absent means count == 0."""
+        seqs = [bytes(s) for s in seqs]
+        n = len(seqs)
+        off = np.zeros(n + 1, dtype=np.uint64)
+        if n:
+            off[1:] = np.cumsum([len(s) for s in seqs])
+        blob = np.frombuffer(b"".join(seqs) + b"\0", dtype=np.uint8)
+        stats = np.zeros((max(n, 1), 2), dtype=np.uint64)
+        h = np.zeros(1024, dtype=np.uint64) if hist else None
+        nb = [(len(s) + 7) // 8 for s in seqs]
+        raw = np.zeros(sum(nb) + 1, dtype=np.uint8) if bits else None
+        ms = C.c_float()
+        self._check(lib().np2_qv_strings(self._h, yak_idx, blob.ctypes.data, off.ctypes.data, n, min_count, stats.ctypes.data,
+                                         h.ctypes.data if hist else None, raw.ctypes.data if bits else None, C.byref(ms)))
+        per_seq = None
+        if bits:
+            cuts = np.concatenate([[0], np.cumsum(nb)]).astype(np.int64)
+            per_seq = [raw[cuts[i]:cuts[i + 1]] for i in range(n)]
+        return QvStats(stats[:n], h, per_seq, ms.value)
+
+    def qv_device(self, yak_idx, dev_ptr, n, min_count=1, hist=False, bits=False):
+        """np2_qv_device: the same measurement of ONE sequence of `n` bytes at device address `dev_ptr` on this context's
+        device (last_result_device()) -> QvStats with one row."""
+        stats = np.zeros((1, 2), dtype=np.uint64)
+        h = np.zeros(1024, dtype=np.uint64) if hist else None
+        raw = np.zeros((int(n) + 7) // 8 + 1, dtype=np.uint8) if bits else None
+        ms = C.c_float()
+        self._check(lib().np2_qv_device(self._h, yak_idx, C.c_void_p(dev_ptr) if dev_ptr else None, int(n), min_count,
+                                        stats.ctypes.data, h.ctypes.data if hist else None, raw.ctypes.data if bits else None,
+                                        C.byref(ms)))
+        return QvStats(stats, h, [raw[:(int(n) + 7) // 8]] if bits else None, ms.value)
 
 
 class BatchPolisher:

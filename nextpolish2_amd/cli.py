@@ -54,6 +54,12 @@ def build_parser():
     p.add_argument("--sr_min_count", type=int, default=None, metavar="N",
                    help="drop k-mers of --sr counted fewer than N times [2, or -k/--min_kmer_count where that is smaller]")
     p.add_argument("-o", "--out", default=None, metavar="FILE", help="output file [stdout]")
+    p.add_argument("--qv", default=None, metavar="FILE",
+                   help="k-mer QV of every contig as read and as written, per k-mer table, as a TSV (a k-mer the tables do not "
+                        "hold is an error; tables without singletons call singletons absent)")
+    p.add_argument("--qv_min_count", type=int, default=1, metavar="N", help="--qv reads a k-mer count below N as absent [1]")
+    p.add_argument("--qv_bed", default=None, metavar="PREFIX",
+                   help="with --qv: intervals covered by absent k-mers, PREFIX.k<K>.in.bed and PREFIX.k<K>.out.bed")
     p.add_argument("-u", "--uppercase", action="store_true", help="output in uppercase sequences")
     p.add_argument("--out_pos", action="store_true", help=argparse.SUPPRESS)
     p.add_argument("-k", "--min_kmer_count", type=int, default=5)
@@ -97,6 +103,16 @@ def _record(a, name, b, first, last, pos=None):
     if a.out_pos:
         return b"".join(b"%s\t%c\t%d\n" % (name.encode(), b[i:i + 1], int(pos[i])) for i in range(len(b)))
     return b">%s start:%d end:%d\n%s\n" % (name.encode(), first, last, b)
+
+
+def _record_sequence(rec):
+    """the sequence of a FASTA record as written: '>name start:a end:b\\nSEQ\\n'"""
+    return rec[rec.index(b"\n") + 1:-1]
+
+
+def _qv_report(a, ks):
+    from .qv import QvReport
+    return QvReport(ks, a.qv_min_count, want_bed=a.qv_bed is not None)
 
 
 def _init_distributed(a):
@@ -202,13 +218,22 @@ def _main_distributed(a, argv, t0, out, yaks, opts, fopts):
     got = all_gather_sequences(local, device=xdev)
     if rank == 0:
         records.update(got)
+        report, qpol = None, None
+        if a.qv is not None:  # rank 0 measures what it writes, on its own device and a context of its own
+            report, qpol = _qv_report(a, [y.k for y in yaks]), pol.clone()
         for i, (name, seq) in enumerate(contigs):
             if i in records:
-                out.write(records[i])
+                rec = records[i]
             else:  # pass-through (main.rs:1727-1730)
                 s_ = seq.upper() if a.uppercase else seq
-                out.write(_record(a, name, s_, 0, len(seq) - 1, range(len(seq))))
+                rec = _record(a, name, s_, 0, len(seq) - 1, range(len(seq)))
+            out.write(rec)
+            if report is not None:
+                report.add(qpol, name, seq, _record_sequence(rec))
         out.flush()
+        if report is not None:
+            qpol.close()
+            report.write_cli(a.qv, a.qv_bed)
         if out is not sys.stdout.buffer:
             out.close()
         print(resource_str(t0, ["nextPolish2"] + argv), file=sys.stderr)
@@ -236,6 +261,12 @@ def main(argv=None):
             parser.error("--sr_k: only 2 <= k < 32 is supported")
         if a.sr_min_count is None:  # no word the polish would look at is ever dropped
             a.sr_min_count = max(1, min(2, a.min_kmer_count))
+    if a.qv is not None and a.out_pos:
+        parser.error("--qv measures the sequences of a FASTA output: not with --out_pos")
+    if a.qv_bed is not None and a.qv is None:
+        parser.error("--qv_bed needs --qv")
+    if not 0 <= a.qv_min_count <= 1023:
+        parser.error("--qv_min_count: 0 .. 1023")
     if a.model.lower() not in ("ref", "len"):
         raise SystemExit("error: invalid value for --model (ref|len)")
     for y in a.yak:  # (before the output file exists: a broken dump must not leave a partial output behind)
@@ -428,6 +459,11 @@ def main(argv=None):
                 for c in contigs:
                     c.free()
 
+    report, qpol = None, []
+    if a.qv is not None:
+        report = _qv_report(a, a.sr_ks if a.sr else sorted(np2io.check_yak_header(y) for y in a.yak))
+        base_future.append(yak_pool.submit(build_base))  # the tables are needed even when every contig passes through
+
     workers = []
     try:
         with ThreadPoolExecutor(max_workers=n_front) as fpool:
@@ -435,17 +471,27 @@ def main(argv=None):
             for w in workers:
                 w.start()
             pending, pending_len = [], []  # records in input order: bytes or futures; the contigs' lengths
+            pending_in = []  # --qv: (name, sequence as read) of the same contigs
 
             def drain(keep):
                 while len(pending) > keep:
                     rec = pending.pop(0)
                     pending_len.pop(0)
-                    out.write(rec if isinstance(rec, bytes) else rec.result())
+                    rec = rec if isinstance(rec, bytes) else rec.result()
+                    out.write(rec)
+                    if report is not None:  # measured as written, on this thread's own context over the shared tables
+                        if not qpol:
+                            b0 = base_future[0].result()
+                            with base_lock:
+                                qpol.append(b0.clone())
+                        report.add(qpol[0], *pending_in.pop(0), _record_sequence(rec))
 
             try:
                 for name, seq in np2io.read_fasta(a.fa):
                     if len(seq) >= 0xFFFFFFFF:
                         raise SystemExit(f"{name} is too long!")
+                    if report is not None:
+                        pending_in.append((name, seq))
                     if len(seq) < a.min_ctg_len:  # pass-through (main.rs:1727-1730)
                         s = seq.upper() if a.uppercase else seq
                         if a.out_pos:
@@ -477,6 +523,8 @@ def main(argv=None):
                 for w in workers:
                     w.join()
             out.flush()
+            if report is not None:
+                report.write_cli(a.qv, a.qv_bed)
             if prof:
                 print(f"[np2 profile] last record written at +{time.time() - t0:.3f} s", file=sys.stderr)
         if not base_future and not a.sr:
@@ -484,6 +532,8 @@ def main(argv=None):
         if prof:
             print(f"[np2 profile] contexts released at +{time.time() - t0:.3f} s", file=sys.stderr)
     finally:
+        for q in qpol:  # (the QV context, on the error paths too)
+            q.close()
         yak_pool.shutdown(wait=False)
         if out is not None and out is not sys.stdout.buffer:
             out.close()

@@ -1352,7 +1352,7 @@ __device__ __forceinline__ void k_pair_count(const uint32_t np2_bid, const uint3
 // open-addressed with linear probing on (x >> 10); the slot holds the file word verbatim
 // ((x >> 10) << 10 | count, kmer.rs:52-58).  EMPTY = ~0 (a file word never has its top bits set).
 // ------------------------------------------------------------------------------------------
-static constexpr uint64_t YAK_EMPTY = ~0ULL;
+// (YAK_EMPTY and yak_get, the lookup every kernel shares: np2_kernels.hpp)
 
 __global__ void k_yak_insert(const uint64_t *__restrict__ words, const uint64_t *__restrict__ bucket_off,
                              uint32_t n_buckets, uint64_t *__restrict__ table, uint32_t cap_log2,
@@ -1399,34 +1399,6 @@ __global__ void k_yak_insert_dup(const uint64_t *__restrict__ words, const uint6
         while (atomicCAS((unsigned long long *)&tb[s], (unsigned long long)YAK_EMPTY, (unsigned long long)w) != YAK_EMPTY)
             s = (s + 1) & capm;
         ob[s] = (uint32_t)i; // (read by later launches only)
-    }
-}
-
-__device__ __forceinline__ uint16_t yak_get(const YakDev &y, uint64_t x, uint16_t min_count) {
-    // KmerInfo::get after retrieve_kmers(min_count) (kmer.rs:123-125,160-166), unwrap_or(0)
-    const uint64_t capm = (1ULL << y.cap_log2) - 1;
-    const uint64_t *tb = y.table + ((x & 1023) << y.cap_log2);
-    const uint64_t key = x >> 10;
-    uint64_t s = key & capm;
-    if (y.ord) { // repeated keys: the whole probe cluster, last passing word in file order
-        const uint32_t *ob = y.ord + ((x & 1023) << y.cap_log2);
-        uint16_t c = 0;
-        int64_t at = -1;
-        for (;;) {
-            const uint64_t w = tb[s];
-            if (w == YAK_EMPTY) return c;
-            if ((w >> 10) == key && (uint16_t)(w & 1023) >= min_count && (int64_t)ob[s] > at) at = ob[s], c = (uint16_t)(w & 1023);
-            s = (s + 1) & capm;
-        }
-    }
-    for (;;) {
-        const uint64_t w = tb[s];
-        if (w == YAK_EMPTY) return 0;
-        if ((w >> 10) == key) {
-            const uint16_t c = (uint16_t)(w & 1023);
-            return c >= min_count ? c : 0;
-        }
-        s = (s + 1) & capm;
     }
 }
 

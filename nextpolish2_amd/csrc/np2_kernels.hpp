@@ -87,6 +87,39 @@ struct YakDev {
     uint32_t k;
     const uint32_t *ord; // nullptr unless the dump repeated a key: a slot's index in its bucket's file order (k_yak_insert_dup)
 };
+static constexpr uint64_t YAK_EMPTY = ~0ULL; // an unused slot (a file word never has its top bits set)
+#if defined(__HIPCC__)
+// the lookup of the polish kernels (np2_kernels.hip).  The QV scan (np2_qv.hip) answers the same question with probe loops
+// of its own, bounded by the sub-table's capacity (several k-mers a lane in flight; qv_get_bounded for `ord` tables);
+// tests/test_gpu_qv.py holds the two to the same counts through np2_lookup_hashes.
+__device__ __forceinline__ uint16_t yak_get(const YakDev &y, uint64_t x, uint16_t min_count) {
+    // KmerInfo::get after retrieve_kmers(min_count) (kmer.rs:123-125,160-166), unwrap_or(0)
+    const uint64_t capm = (1ULL << y.cap_log2) - 1;
+    const uint64_t *tb = y.table + ((x & 1023) << y.cap_log2);
+    const uint64_t key = x >> 10;
+    uint64_t s = key & capm;
+    if (y.ord) { // repeated keys: the whole probe cluster, last passing word in file order
+        const uint32_t *ob = y.ord + ((x & 1023) << y.cap_log2);
+        uint16_t c = 0;
+        int64_t at = -1;
+        for (;;) {
+            const uint64_t w = tb[s];
+            if (w == YAK_EMPTY) return c;
+            if ((w >> 10) == key && (uint16_t)(w & 1023) >= min_count && (int64_t)ob[s] > at) at = ob[s], c = (uint16_t)(w & 1023);
+            s = (s + 1) & capm;
+        }
+    }
+    for (;;) {
+        const uint64_t w = tb[s];
+        if (w == YAK_EMPTY) return 0;
+        if ((w >> 10) == key) {
+            const uint16_t c = (uint16_t)(w & 1023);
+            return c >= min_count ? c : 0;
+        }
+        s = (s + 1) & capm;
+    }
+}
+#endif
 
 // refnib: [0, stride) the contig's codes, position p in nibble p & 1 of byte p >> 1; [stride, 2 stride) and [2 stride,
 // 3 stride) the same codes in the packed streams' own order (even column in the high nibble) for windows that start at an
