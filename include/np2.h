@@ -153,6 +153,26 @@ int np2_qv_strings(np2_ctx_t *ctx, int yak_idx, const uint8_t *strs, const uint6
 int np2_qv_device(np2_ctx_t *ctx, int yak_idx, const uint8_t *dev_seq, uint64_t len, uint16_t min_count, np2_qv_t *out,
                   uint64_t *hist, uint8_t *absent_bits, float *kernel_ms);
 
+/* Switch and Hamming error of sequences against a paternal and a maternal k-mer table of the same k (the `yak trioeval`
+ * measurement; the semantics are this project's, not yak's report byte for byte).  c_P, c_M: a k-mer's stored counts, 0
+ * when a table does not hold it (a table that repeats keys answers with its last word in file order).  With
+ * 1 <= min_count <= mid_count <= 1023 a valid k-mer (bases and validity as np2_qv_*) is a PATERNAL MARKER when
+ * c_P >= mid_count and c_M < min_count, a MATERNAL MARKER when c_M >= mid_count and c_P < min_count.  Per sequence, over
+ * its markers in ascending end position: n_pat, n_mat, and pairs[pp, pm, mp, mm] of consecutive markers as (earlier,
+ * later); a non-base byte breaks k-mers, not adjacency; no pair spans two sequences.  switch = pm + mp out of the sum of
+ * pairs; hamming = min(n_pat, n_mat) out of n_pat + n_mat.
+ * pat_bits / mat_bits (either may be NULL): the parents' marker bitmaps, laid out like np2_qv_*'s absent_bits: bit e is
+ * set when the k-mer ending at base e is that parent's marker.  kernel_ms (or NULL): HIP-event time of the two kernels.
+ * NP2_E_ARG before anything is launched: an index out of range, pat_idx == mat_idx, tables of different k, thresholds
+ * outside the rule above, out NULL, off NULL with n > 0, off descending, strs / dev_seq NULL with a non-zero length. */
+typedef struct np2_trio { uint64_t n_kmers, n_pat, n_mat, pairs[4]; } np2_trio_t;   /* pp, pm, mp, mm */
+int np2_trio_strings(np2_ctx_t *ctx, int pat_idx, int mat_idx, const uint8_t *strs, const uint64_t *off, uint64_t n,
+                     uint16_t min_count, uint16_t mid_count, np2_trio_t *out,
+                     uint8_t *pat_bits, uint8_t *mat_bits, float *kernel_ms);
+int np2_trio_device(np2_ctx_t *ctx, int pat_idx, int mat_idx, const uint8_t *dev_seq, uint64_t len,
+                    uint16_t min_count, uint16_t mid_count, np2_trio_t *out,
+                    uint8_t *pat_bits, uint8_t *mat_bits, float *kernel_ms);
+
 /* Stage-level exports for kernel parity tests and profiling.
  * After np2_polish_resident with tracing enabled, np2_trace_get returns a pointer to a
  * host copy of intermediate `name` of pass `pass` (valid until the next polish call). */

@@ -26,7 +26,7 @@ ABI_SYMBOLS = [
     "np2_shard_begin", "np2_shard_passes_left", "np2_shard_vote", "np2_vote_decide", "np2_shard_apply", "np2_shard_final",
     "np2_shard_final_device", "np2_shard_fetch", "np2_alloc_pinned", "np2_trim_device_cache",
     "np2_shard_end", "np2_swiss_order", "np2_batch_set_timing", "np2_batch_set_priority", "np2_batch_last_diff_ms", "np2_batch_stats", "np2_batch_last_call_ms",
-    "np2_qv_strings", "np2_qv_device",
+    "np2_qv_strings", "np2_qv_device", "np2_trio_strings", "np2_trio_device",
 ]
 
 # include/np2_io.h (input side; bound by nextpolish2_amd.io)
@@ -85,6 +85,8 @@ def _lib_locked():
         L.np2_lookup_hashes.argtypes = [vp, C.c_int, vp, u64, u16, vp]
         L.np2_qv_strings.argtypes = [vp, C.c_int, vp, vp, u64, u16, vp, vp, vp, C.POINTER(C.c_float)]
         L.np2_qv_device.argtypes = [vp, C.c_int, vp, u64, u16, vp, vp, vp, C.POINTER(C.c_float)]
+        L.np2_trio_strings.argtypes = [vp, C.c_int, C.c_int, vp, vp, u64, u16, u16, vp, vp, vp, C.POINTER(C.c_float)]
+        L.np2_trio_device.argtypes = [vp, C.c_int, C.c_int, vp, u64, u16, u16, vp, vp, vp, C.POINTER(C.c_float)]
         L.np2_ctx_set_trace.argtypes = [vp, C.c_int]
         L.np2_ctx_set_timing.argtypes = [vp, C.c_int]
         L.np2_ctx_set_timing.restype = None
@@ -185,6 +187,26 @@ class QvStats:
     @property
     def n_absent(self):
         return int(self.stats[:, 1].sum())
+
+
+class TrioStats:
+    """What np2_trio_strings / np2_trio_device return.  stats: uint64 array (n, 7) per sequence of (n_kmers, n_pat, n_mat,
+    pp, pm, mp, mm): k-mers, paternal and maternal markers, consecutive marker pairs as (earlier, later); pat_bits /
+    mat_bits: one uint8 array per sequence (ceil(len / 8) bytes, least significant bit first, bit e = the k-mer ending at
+    base e is that parent's marker) or None; kernel_ms: HIP-event time of the two kernels."""
+    __slots__ = ("stats", "pat_bits", "mat_bits", "kernel_ms")
+
+    def __init__(self, stats, pat_bits, mat_bits, kernel_ms):
+        self.stats, self.pat_bits, self.mat_bits, self.kernel_ms = stats, pat_bits, mat_bits, kernel_ms
+
+    @property
+    def total(self):
+        """the seven counters summed over the sequences"""
+        return tuple(int(x) for x in self.stats.sum(axis=0, dtype=np.uint64)) if len(self.stats) else (0,) * 7
+
+    @property
+    def n_switch(self):
+        return self.total[4] + self.total[5]
 
 
 class ResidentContig:
@@ -386,6 +408,42 @@ class Polisher:
                                         stats.ctypes.data, h.ctypes.data if hist else None, raw.ctypes.data if bits else None,
                                         C.byref(ms)))
         return QvStats(stats, h, [raw[:(int(n) + 7) // 8]] if bits else None, ms.value)
+
+
+    def trio_strings(self, pat_idx, mat_idx, seqs, min_count=2, mid_count=5, bits=False):
+        """np2_trio_strings: parental markers and consecutive marker pairs of every sequence of `seqs` (bytes-like each)
+        against the paternal table `pat_idx` and the maternal table `mat_idx` of the same k -> TrioStats.  A k-mer is a
+        parent's marker when that parent's count is >= mid_count and the other's is < min_count."""
+        seqs = [bytes(s) for s in seqs]
+        n = len(seqs)
+        off = np.zeros(n + 1, dtype=np.uint64)
+        if n:
+            off[1:] = np.cumsum([len(s) for s in seqs])
+        blob = np.frombuffer(b"".join(seqs) + b"\0", dtype=np.uint8)
+        stats = np.zeros((max(n, 1), 7), dtype=np.uint64)
+        nb = [(len(s) + 7) // 8 for s in seqs]
+        raw = [np.zeros(sum(nb) + 1, dtype=np.uint8) for _ in range(2)] if bits else None
+        ms = C.c_float()
+        self._check(lib().np2_trio_strings(self._h, pat_idx, mat_idx, blob.ctypes.data, off.ctypes.data, n, min_count, mid_count,
+                                           stats.ctypes.data, raw[0].ctypes.data if bits else None,
+                                           raw[1].ctypes.data if bits else None, C.byref(ms)))
+        per = [None, None]
+        if bits:
+            cuts = np.concatenate([[0], np.cumsum(nb)]).astype(np.int64)
+            per = [[r[cuts[i]:cuts[i + 1]] for i in range(n)] for r in raw]
+        return TrioStats(stats[:n], per[0], per[1], ms.value)
+
+    def trio_device(self, pat_idx, mat_idx, dev_ptr, n, min_count=2, mid_count=5, bits=False):
+        """np2_trio_device: the same measurement of ONE sequence of `n` bytes at device address `dev_ptr` on this
+        context's device (last_result_device()) -> TrioStats with one row."""
+        stats = np.zeros((1, 7), dtype=np.uint64)
+        nb = (int(n) + 7) // 8
+        raw = [np.zeros(nb + 1, dtype=np.uint8) for _ in range(2)] if bits else None
+        ms = C.c_float()
+        self._check(lib().np2_trio_device(self._h, pat_idx, mat_idx, C.c_void_p(dev_ptr) if dev_ptr else None, int(n), min_count,
+                                          mid_count, stats.ctypes.data, raw[0].ctypes.data if bits else None,
+                                          raw[1].ctypes.data if bits else None, C.byref(ms)))
+        return TrioStats(stats, [raw[0][:nb]] if bits else None, [raw[1][:nb]] if bits else None, ms.value)
 
 
 class BatchPolisher:

@@ -60,6 +60,14 @@ def build_parser():
     p.add_argument("--qv_min_count", type=int, default=1, metavar="N", help="--qv reads a k-mer count below N as absent [1]")
     p.add_argument("--qv_bed", default=None, metavar="PREFIX",
                    help="with --qv: intervals covered by absent k-mers, PREFIX.k<K>.in.bed and PREFIX.k<K>.out.bed")
+    p.add_argument("--trio", default=None, metavar="FILE",
+                   help="switch and Hamming error of every contig as read and as written against parental k-mer tables, as a TSV "
+                        "(needs --trio_pat and --trio_mat)")
+    p.add_argument("--trio_pat", type=_existing, default=None, metavar="pat.yak", help="--trio: the paternal k-mer dump")
+    p.add_argument("--trio_mat", type=_existing, default=None, metavar="mat.yak", help="--trio: the maternal k-mer dump (same k)")
+    p.add_argument("--trio_min_count", type=int, default=2, metavar="N", help="--trio: a parent counting a k-mer fewer than N times does not have it [2]")
+    p.add_argument("--trio_mid_count", type=int, default=5, metavar="N", help="--trio: a parent counting a k-mer at least N times has it [5]")
+    p.add_argument("--trio_bed", default=None, metavar="PREFIX", help="with --trio: switch sites, PREFIX.in.bed and PREFIX.out.bed")
     p.add_argument("-u", "--uppercase", action="store_true", help="output in uppercase sequences")
     p.add_argument("--out_pos", action="store_true", help=argparse.SUPPRESS)
     p.add_argument("-k", "--min_kmer_count", type=int, default=5)
@@ -113,6 +121,16 @@ def _record_sequence(rec):
 def _qv_report(a, ks):
     from .qv import QvReport
     return QvReport(ks, a.qv_min_count, want_bed=a.qv_bed is not None)
+
+
+def _trio_report(a):
+    from .trio import TrioReport
+    return TrioReport(a.trio_k, a.trio_min_count, a.trio_mid_count, want_bed=a.trio_bed is not None)
+
+
+def _trio_polisher(a):
+    """a context of its own that holds the two parental tables: paternal 0, maternal 1 (dumps of one k keep their order)"""
+    return np2io.polisher_from_yak_files([a.trio_pat, a.trio_mat], device=a.device)
 
 
 def _init_distributed(a):
@@ -221,6 +239,9 @@ def _main_distributed(a, argv, t0, out, yaks, opts, fopts):
         report, qpol = None, None
         if a.qv is not None:  # rank 0 measures what it writes, on its own device and a context of its own
             report, qpol = _qv_report(a, [y.k for y in yaks]), pol.clone()
+        treport, tpol = None, None
+        if a.trio is not None:
+            treport, tpol = _trio_report(a), _trio_polisher(a)
         for i, (name, seq) in enumerate(contigs):
             if i in records:
                 rec = records[i]
@@ -230,10 +251,15 @@ def _main_distributed(a, argv, t0, out, yaks, opts, fopts):
             out.write(rec)
             if report is not None:
                 report.add(qpol, name, seq, _record_sequence(rec))
+            if treport is not None:
+                treport.add(tpol, name, seq, _record_sequence(rec))
         out.flush()
         if report is not None:
             qpol.close()
             report.write_cli(a.qv, a.qv_bed)
+        if treport is not None:
+            tpol.close()
+            treport.write_cli(a.trio, a.trio_bed)
         if out is not sys.stdout.buffer:
             out.close()
         print(resource_str(t0, ["nextPolish2"] + argv), file=sys.stderr)
@@ -267,12 +293,26 @@ def main(argv=None):
         parser.error("--qv_bed needs --qv")
     if not 0 <= a.qv_min_count <= 1023:
         parser.error("--qv_min_count: 0 .. 1023")
+    if a.trio is not None and (a.trio_pat is None or a.trio_mat is None):
+        parser.error("--trio needs both --trio_pat and --trio_mat")
+    if a.trio_bed is not None and a.trio is None:
+        parser.error("--trio_bed needs --trio")
+    if a.trio is not None and a.out_pos:
+        parser.error("--trio measures the sequences of a FASTA output: not with --out_pos")
+    if not 1 <= a.trio_min_count <= a.trio_mid_count <= 1023:
+        parser.error("--trio thresholds: 1 <= --trio_min_count <= --trio_mid_count <= 1023")
     if a.model.lower() not in ("ref", "len"):
         raise SystemExit("error: invalid value for --model (ref|len)")
     for y in a.yak:  # (before the output file exists: a broken dump must not leave a partial output behind)
         try:
             np2io.check_yak_header(y)
         except (ValueError, OSError) as e:  # (a malformed dump, or one that cannot be read at all)
+            raise SystemExit(f"Error: {e}")
+    if a.trio is not None:
+        from .trio import parental_k
+        try:
+            a.trio_k = parental_k(a.trio_pat, a.trio_mat)
+        except (ValueError, OSError) as e:
             raise SystemExit(f"Error: {e}")
     out = sys.stdout.buffer
     distributed = int(os.environ.get("WORLD_SIZE", "1")) > 1 and "RANK" in os.environ
@@ -464,6 +504,11 @@ def main(argv=None):
         report = _qv_report(a, a.sr_ks if a.sr else sorted(np2io.check_yak_header(y) for y in a.yak))
         base_future.append(yak_pool.submit(build_base))  # the tables are needed even when every contig passes through
 
+    treport, tpol, trio_pool = None, [], None
+    if a.trio is not None:  # the parental tables go into HBM next to the polish, in a context of their own
+        treport, trio_pool = _trio_report(a), ThreadPoolExecutor(max_workers=1)
+        trio_future = trio_pool.submit(_trio_polisher, a)
+
     workers = []
     try:
         with ThreadPoolExecutor(max_workers=n_front) as fpool:
@@ -472,6 +517,7 @@ def main(argv=None):
                 w.start()
             pending, pending_len = [], []  # records in input order: bytes or futures; the contigs' lengths
             pending_in = []  # --qv: (name, sequence as read) of the same contigs
+            pending_trio = []  # --trio: the same
 
             def drain(keep):
                 while len(pending) > keep:
@@ -485,6 +531,10 @@ def main(argv=None):
                             with base_lock:
                                 qpol.append(b0.clone())
                         report.add(qpol[0], *pending_in.pop(0), _record_sequence(rec))
+                    if treport is not None:
+                        if not tpol:
+                            tpol.append(trio_future.result())
+                        treport.add(tpol[0], *pending_trio.pop(0), _record_sequence(rec))
 
             try:
                 for name, seq in np2io.read_fasta(a.fa):
@@ -492,6 +542,8 @@ def main(argv=None):
                         raise SystemExit(f"{name} is too long!")
                     if report is not None:
                         pending_in.append((name, seq))
+                    if treport is not None:
+                        pending_trio.append((name, seq))
                     if len(seq) < a.min_ctg_len:  # pass-through (main.rs:1727-1730)
                         s = seq.upper() if a.uppercase else seq
                         if a.out_pos:
@@ -525,6 +577,8 @@ def main(argv=None):
             out.flush()
             if report is not None:
                 report.write_cli(a.qv, a.qv_bed)
+            if treport is not None:
+                treport.write_cli(a.trio, a.trio_bed)
             if prof:
                 print(f"[np2 profile] last record written at +{time.time() - t0:.3f} s", file=sys.stderr)
         if not base_future and not a.sr:
@@ -534,6 +588,12 @@ def main(argv=None):
     finally:
         for q in qpol:  # (the QV context, on the error paths too)
             q.close()
+        if trio_pool is not None:
+            trio_pool.shutdown(wait=True)
+            if not tpol and trio_future.exception() is None:
+                tpol.append(trio_future.result())
+            for q in tpol:
+                q.close()
         yak_pool.shutdown(wait=False)
         if out is not None and out is not sys.stdout.buffer:
             out.close()

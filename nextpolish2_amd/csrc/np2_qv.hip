@@ -29,24 +29,6 @@ namespace {
 static constexpr uint32_t QV_CHUNKS = (HALO + QV_TILE) / 16 + 1; // 16-byte pieces of a tile's window (+ 1: a source that is not 16-byte aligned)
 static constexpr uint32_t PAD4 = 0x0A0A0A0Au;
 
-// yak_get (np2_kernels.hpp) with its probe loops bounded by the sub-table's capacity: the lookup of a table that repeats
-// keys (`ord`: the last passing word in file order wins), one k-mer at a time
-__device__ __forceinline__ uint32_t qv_get_bounded(const YakDev &y, uint64_t x, uint32_t min_count) {
-    const uint64_t capm = (1ULL << y.cap_log2) - 1;
-    const uint64_t *tb = y.table + ((uint64_t)bucket_of(x) << y.cap_log2);
-    const uint32_t *ob = y.ord + ((uint64_t)bucket_of(x) << y.cap_log2);
-    const uint64_t key = key_of(x);
-    uint64_t s = key & capm;
-    uint32_t c = 0;
-    int64_t at = -1;
-    for (uint64_t probe = 0; probe <= capm; ++probe, s = (s + 1) & capm) {
-        const uint64_t w = tb[s];
-        if (w == YAK_EMPTY) break;
-        if ((w >> COUNT_BITS) == key && (uint32_t)(w & COUNT_MAX) >= min_count && (int64_t)ob[s] > at) at = ob[s], c = (uint32_t)(w & COUNT_MAX);
-    }
-    return c;
-}
-
 // the block's k-mer counters of sequence `seq` -> global memory: wavefront sums, an LDS pair, one pair of atomics
 __device__ __forceinline__ void qv_flush(uint32_t &n_kmers, uint32_t &n_absent, uint32_t *s_cnt, unsigned long long *stats, uint32_t seq) {
     uint32_t a = n_kmers, b = n_absent;

@@ -1,6 +1,7 @@
 // Host driver of the k-mer QV scan (np2_qv.hip): np2_qv_strings streams host sequences through a staging buffer of fixed
 // size, np2_qv_device scans one sequence where a polish left it.  (np2_qv.cpp would share the kernel file's object name.)
 #include "np2_ctx.hpp"
+#include "np2_kernel_timer.hpp"
 #include "np2_qv.hpp"
 
 using namespace np2qv;
@@ -21,32 +22,6 @@ uint32_t qv_blocks(int device) {
     HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
     return (uint32_t)std::max(1, cus) * 4u;
 }
-
-struct KernelTimer { // HIP events around the scan kernel alone, summed over the pieces
-    hipEvent_t a = nullptr, b = nullptr;
-    float ms = 0.f;
-    explicit KernelTimer(bool on) {
-        if (!on) return;
-        HIPCHK(hipEventCreate(&a));
-        HIPCHK(hipEventCreate(&b));
-    }
-    ~KernelTimer() {
-        if (a) (void)hipEventDestroy(a);
-        if (b) (void)hipEventDestroy(b);
-    }
-    void start(hipStream_t s) {
-        if (a) HIPCHK(hipEventRecord(a, s));
-    }
-    void stop(hipStream_t s) {
-        if (b) HIPCHK(hipEventRecord(b, s));
-    }
-    void collect() { // (after the stream was drained)
-        if (!a) return;
-        float t = 0.f;
-        HIPCHK(hipEventElapsedTime(&t, a, b));
-        ms += t;
-    }
-};
 
 struct QvBufs { // released after the call's device work has completed: cached blocks (DevCache)
     DevBuf<uint8_t> stage;

@@ -1,0 +1,31 @@
+// Launchers of the trio scan (np2_trio.hip) for its host driver (np2_trio_host.cpp).
+#pragma once
+#include <cstdint>
+#include <hip/hip_runtime.h>
+
+#include "np2_kernels.hpp"
+#include "np2_trio_core.hpp"
+
+namespace np2 {
+
+// One scan: tiles [0, n_tiles) of a stream laid out and masked exactly as QvScan's (np2_qv.hpp): offset 0 is `src` (any
+// alignment), only offsets in [lo, hi) are read as bases, every sequence starts at a tile boundary.
+struct TrioScan {
+    const uint8_t *src;
+    int64_t lo, hi;
+    const uint32_t *desc;      // per tile: sequence index | QV_FIRST; nullptr: one sequence (index 0) starting at offset 0
+    uint32_t n_tiles;
+    uint32_t min_count, mid_count;
+    unsigned long long *stats; // per sequence TRIO_STATS counters (added to): n_kmers, n_pat, n_mat, pp, pm, mp, mm
+    uint32_t *tiles;           // n_tiles words: np2trio::tile_word of every tile (written)
+    uint32_t *pat_bits;        // n_tiles * QV_BLOCK words each: a lane's 32 bitmap bits, or nullptr
+    uint32_t *mat_bits;
+    uint32_t *carry;           // one word: class of the last marker of the sequence that goes on in the next piece; read
+                               // as what lies before tile 0 when that tile does not start a sequence, written at the end
+};
+// k_trio_scan: everything inside a tile.  `blocks`: the grid; blocks stride over the tiles
+void launch_trio_scan(hipStream_t s, const YakDev &pat, const YakDev &mat, const TrioScan &q, uint32_t blocks);
+// k_trio_join: the pairs across tile boundaries, one block over all tiles (a segmented scan of q.tiles); after the scan
+void launch_trio_join(hipStream_t s, const TrioScan &q);
+
+} // namespace np2
