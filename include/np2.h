@@ -173,6 +173,22 @@ int np2_trio_device(np2_ctx_t *ctx, int pat_idx, int mat_idx, const uint8_t *dev
                     uint16_t min_count, uint16_t mid_count, np2_trio_t *out,
                     uint8_t *pat_bits, uint8_t *mat_bits, float *kernel_ms);
 
+/* Bin long reads by parental k-mers (the `yak triobin` step of a trio recipe; the semantics are this project's, not yak's
+ * report byte for byte).  `stream` is a packed separator stream: the reads' bytes back to back, every read followed by
+ * one '\n' (np2_seqfile_stream's format), n_reads reads in n_bytes bytes.  Markers and thresholds are np2_trio_strings';
+ * stats[r] (or NULL) are read r's tallies: exactly what np2_trio_strings returns for the read as a sequence of its own.
+ * Scores: s_pat = pairs[0] (pp), s_mat = pairs[3] (mm).  cls[r] is one byte: '0' when both scores are below min_score;
+ * otherwise with L = max, S = min of the scores 'a' when s_pat == s_mat or S * 1000 > L * minor_permille; otherwise 'p'
+ * or 'm', the larger score.  Paternal bin = p, a, 0; maternal bin = m, a, 0.  opts NULL: {2, 5, 2, 330}.
+ * kernel_ms (or NULL): HIP-event time of the kernels.  NP2_E_ARG before anything is launched: the table and threshold
+ * errors of np2_trio_strings, minor_permille > 1000, cls NULL, stream NULL with n_bytes > 0, a non-empty stream that does
+ * not end in '\n', n_reads != the number of '\n', a read of 2^32 - 1 bytes or more.  n_reads == 0 is fine. */
+typedef struct np2_bin { uint32_t n_kmers, n_pat, n_mat, pairs[4]; } np2_bin_t;   /* pp, pm, mp, mm */
+typedef struct np2_bin_opts { uint16_t min_count, mid_count; uint32_t min_score, minor_permille; } np2_bin_opts_t;
+int np2_bin_stream(np2_ctx_t *ctx, int pat_idx, int mat_idx, const uint8_t *stream, uint64_t n_bytes, uint64_t n_reads,
+                   const np2_bin_opts_t *opts, uint8_t *cls /* [n_reads] */, np2_bin_t *stats /* [n_reads] or NULL */,
+                   float *kernel_ms);
+
 /* Stage-level exports for kernel parity tests and profiling.
  * After np2_polish_resident with tracing enabled, np2_trace_get returns a pointer to a
  * host copy of intermediate `name` of pass `pass` (valid until the next polish call). */

@@ -147,6 +147,20 @@ int np2_kcount_last_stats(uint64_t *kmers, uint64_t *distinct, uint64_t *spilled
  * release with np2_free */
 int np2_seqfile_stream(const char *path, uint8_t **out, uint64_t *n);
 
+/* Read files -> classes (np2_bin_stream's device path, fed by the counter's reader threads through pinned pieces, in
+ * file order; errors: np2_last_error(ctx)).  A read's name is its header up to the first whitespace, without '>' / '@';
+ * a record without one (one sequence per line) is named by its 1-based number in its file.  Every path of `out` may be
+ * NULL: tsv (a header line, then per read: read class s_pat s_mat n_pat n_mat pm mp kmers len), pat_list / mat_list (the
+ * names of the paternal bin p, a, 0 / the maternal bin m, a, 0), pat_fa / mat_fa (the two bins as FASTA, one line per
+ * sequence, qualities dropped, plain files).  counts (or NULL): reads of class p, m, a, 0. */
+typedef struct np2_bin_out { const char *tsv, *pat_list, *mat_list, *pat_fa, *mat_fa; } np2_bin_out_t;
+int np2_bin_files(np2_ctx_t *ctx, int pat_idx, int mat_idx, const char *const *paths, int n_paths,
+                  const np2_bin_opts_t *opts, const np2_bin_out_t *out, uint64_t *counts /* [4] */, float *kernel_ms);
+/* host only, no device: what that reader makes of one file.  names: the reads' names, each followed by '\n'
+ * (names_bytes bytes); ends: per read the offset of its separator in the file's separator stream; release both with
+ * np2_free.  Errors: np2_io_last_error(). */
+int np2_seqfile_reads(const char *path, char **names, uint64_t *names_bytes, uint64_t **ends, uint64_t *n_reads);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,7 +26,7 @@ ABI_SYMBOLS = [
     "np2_shard_begin", "np2_shard_passes_left", "np2_shard_vote", "np2_vote_decide", "np2_shard_apply", "np2_shard_final",
     "np2_shard_final_device", "np2_shard_fetch", "np2_alloc_pinned", "np2_trim_device_cache",
     "np2_shard_end", "np2_swiss_order", "np2_batch_set_timing", "np2_batch_set_priority", "np2_batch_last_diff_ms", "np2_batch_stats", "np2_batch_last_call_ms",
-    "np2_qv_strings", "np2_qv_device", "np2_trio_strings", "np2_trio_device",
+    "np2_qv_strings", "np2_qv_device", "np2_trio_strings", "np2_trio_device", "np2_bin_stream",
 ]
 
 # include/np2_io.h (input side; bound by nextpolish2_amd.io)
@@ -36,10 +36,18 @@ IO_ABI_SYMBOLS = [
     "np2_contig_export", "np2_shard_bam_begin", "np2_shard_bam_finish", "np2_shard_bam_abort", "np2_ctx_create_from_files",
     "np2_bgzf_inflate_device", "np2_crc32_device",
     "np2_kcount_files", "np2_kcount_bytes", "np2_kcount_files_to_dumps", "np2_ctx_create_from_reads", "np2_kcount_last_stats",
-    "np2_seqfile_stream",
+    "np2_seqfile_stream", "np2_bin_files", "np2_seqfile_reads",
 ]
 
 ERRORS = {-1: "NP2_E_ARG", -2: "NP2_E_DEVICE", -3: "NP2_E_NOMEM", -4: "NP2_E_UNSUPPORTED", -5: "NP2_E_REFPANIC"}
+
+
+class np2_bin_opts_t(C.Structure):
+    _fields_ = [("min_count", C.c_uint16), ("mid_count", C.c_uint16), ("min_score", C.c_uint32), ("minor_permille", C.c_uint32)]
+
+
+BIN_DTYPE = np.dtype([("n_kmers", "<u4"), ("n_pat", "<u4"), ("n_mat", "<u4"), ("pairs", "<u4", (4,))])  # np2_bin_t
+assert BIN_DTYPE.itemsize == 28
 
 
 class Np2Error(RuntimeError):
@@ -87,6 +95,7 @@ def _lib_locked():
         L.np2_qv_device.argtypes = [vp, C.c_int, vp, u64, u16, vp, vp, vp, C.POINTER(C.c_float)]
         L.np2_trio_strings.argtypes = [vp, C.c_int, C.c_int, vp, vp, u64, u16, u16, vp, vp, vp, C.POINTER(C.c_float)]
         L.np2_trio_device.argtypes = [vp, C.c_int, C.c_int, vp, u64, u16, u16, vp, vp, vp, C.POINTER(C.c_float)]
+        L.np2_bin_stream.argtypes = [vp, C.c_int, C.c_int, vp, u64, u64, C.POINTER(np2_bin_opts_t), vp, vp, C.POINTER(C.c_float)]
         L.np2_ctx_set_trace.argtypes = [vp, C.c_int]
         L.np2_ctx_set_timing.argtypes = [vp, C.c_int]
         L.np2_ctx_set_timing.restype = None
@@ -207,6 +216,15 @@ class TrioStats:
     @property
     def n_switch(self):
         return self.total[4] + self.total[5]
+
+
+class BinResult:
+    """What np2_bin_stream returns.  classes: bytes, one of b"pma0" per read; stats: uint32 array (n, 7) per read of
+    (n_kmers, n_pat, n_mat, pp, pm, mp, mm) or None; kernel_ms: HIP-event time of the kernels."""
+    __slots__ = ("classes", "stats", "kernel_ms")
+
+    def __init__(self, classes, stats, kernel_ms):
+        self.classes, self.stats, self.kernel_ms = classes, stats, kernel_ms
 
 
 class ResidentContig:
@@ -444,6 +462,30 @@ class Polisher:
                                           mid_count, stats.ctypes.data, raw[0].ctypes.data if bits else None,
                                           raw[1].ctypes.data if bits else None, C.byref(ms)))
         return TrioStats(stats, [raw[0][:nb]] if bits else None, [raw[1][:nb]] if bits else None, ms.value)
+
+    def bin_stream(self, pat_idx, mat_idx, reads_or_stream, min_count=2, mid_count=5, min_score=2, minor_permille=330, stats=False):
+        """np2_bin_stream: the class of every read (b"p", b"m", b"a", b"0") against the paternal table `pat_idx` and the
+        maternal table `mat_idx` of the same k -> BinResult.  `reads_or_stream`: a list of reads (bytes-like each, none
+        holding a newline) or ONE bytes object holding a packed separator stream (every read followed by a newline)."""
+        if isinstance(reads_or_stream, (bytes, bytearray, memoryview)):
+            stream = bytes(reads_or_stream)
+        else:
+            reads = [bytes(r) for r in reads_or_stream]
+            if any(b"\n" in r for r in reads):
+                raise ValueError("a read holds a newline")
+            stream = b"".join(r + b"\n" for r in reads)
+        n = stream.count(b"\n")
+        blob = np.frombuffer(stream + b"\0", dtype=np.uint8)
+        cls = np.zeros(n + 1, dtype=np.uint8)
+        st = np.zeros(n + 1, dtype=BIN_DTYPE) if stats else None
+        o = np2_bin_opts_t(min_count, mid_count, min_score, minor_permille)
+        ms = C.c_float()
+        self._check(lib().np2_bin_stream(self._h, pat_idx, mat_idx, blob.ctypes.data if len(stream) else None, len(stream), n, C.byref(o),
+                                         cls.ctypes.data, st.ctypes.data if stats else None, C.byref(ms)))
+        table = None
+        if stats:
+            table = np.concatenate([st["n_kmers"][:n, None], st["n_pat"][:n, None], st["n_mat"][:n, None], st["pairs"][:n]], axis=1)
+        return BinResult(cls[:n].tobytes(), table, ms.value)
 
 
 class BatchPolisher:

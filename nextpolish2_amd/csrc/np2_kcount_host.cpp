@@ -19,6 +19,7 @@
 #include "np2_ctx.hpp"
 #include "np2_kcount.hpp"
 #include "np2_kcount_core.hpp"
+#include "np2_seqreader.hpp"
 
 #include <sys/stat.h>
 #include <zlib.h>
@@ -31,95 +32,7 @@
 namespace {
 using np2h::Np2Error;
 using namespace np2kc;
-
-// ---------------------------------------------------------------------------------------------------------------
-// sequence text -> separator stream
-// ---------------------------------------------------------------------------------------------------------------
-struct SeqParser {
-    enum Fmt { UNKNOWN, FASTA, FASTQ, LINES } fmt = UNKNOWN;
-    uint32_t line = 0;   // FASTQ: line of the record, 0 .. 3 (the 4-line rule: a quality line may begin with '@' or '>')
-    bool bol = true;     // at the beginning of a line
-    bool skip = false;   // the current line holds no sequence
-    bool blank = false;  // FASTQ: a blank line between records (does not advance `line`)
-    bool open = false;   // FASTA: a record has begun and its separator is still owed
-    template <class Put> void feed(const uint8_t *p, size_t n, Put &&put) {
-        static const uint8_t NL = '\n';
-        size_t i = 0;
-        while (i < n) {
-            if (bol) {
-                const uint8_t c = p[i];
-                if (fmt == UNKNOWN) {
-                    if (c == '\n' || c == '\r') {
-                        ++i;
-                        continue;
-                    }
-                    fmt = c == '>' ? FASTA : c == '@' ? FASTQ : LINES;
-                }
-                if (fmt == FASTA) {
-                    skip = c == '>';
-                    if (skip) {
-                        if (open) put(&NL, 1);
-                        open = true;
-                    }
-                } else if (fmt == FASTQ) {
-                    blank = line == 0 && (c == '\n' || c == '\r');
-                    skip = blank || line != 1;
-                } else {
-                    skip = false;
-                }
-                bol = false;
-            }
-            const uint8_t *e = (const uint8_t *)memchr(p + i, '\n', n - i);
-            const size_t end = e ? (size_t)(e - p) : n;
-            if (!skip) { // the line's bytes without '\r'
-                size_t a = i;
-                while (a < end) {
-                    const uint8_t *cr = (const uint8_t *)memchr(p + a, '\r', end - a);
-                    const size_t b = cr ? (size_t)(cr - p) : end;
-                    if (b > a) put(p + a, b - a);
-                    a = b + 1;
-                }
-            }
-            i = end;
-            if (e) {
-                ++i;
-                bol = true;
-                if (fmt == FASTQ) {
-                    if (line == 1) put(&NL, 1);
-                    if (!blank) line = (line + 1) & 3u;
-                } else if (fmt == LINES) {
-                    put(&NL, 1);
-                }
-            }
-        }
-    }
-    template <class Put> void finish(Put &&put) { // a last line without newline
-        static const uint8_t NL = '\n';
-        if (fmt == FASTA ? open : fmt == FASTQ ? (!bol && line == 1) : (fmt == LINES && !bol)) put(&NL, 1);
-        open = false;
-    }
-};
-
-// a whole file through the parser; throws NP2_E_ARG for a file that cannot be opened or a damaged / truncated gzip
-template <class Put> void parse_file(const std::string &path, Put &&put, const std::function<bool()> &stop) {
-    gzFile f = gzopen(path.c_str(), "rb");
-    if (!f) throw Np2Error(NP2_E_ARG, "cannot open " + path);
-    std::unique_ptr<gzFile_s, int (*)(gzFile)> guard(f, gzclose);
-    gzbuffer(f, 1 << 20);
-    std::vector<uint8_t> buf((size_t)1 << 20);
-    SeqParser ps;
-    for (;;) {
-        if (stop && stop()) return;
-        const int got = gzread(f, buf.data(), (unsigned)buf.size());
-        int zerr = Z_OK;
-        const char *zmsg = gzerror(f, &zerr);
-        if (got < 0 || (zerr != Z_OK && zerr != Z_STREAM_END))
-            throw Np2Error(NP2_E_ARG, path + ": cannot read the sequence file (" + (zmsg && *zmsg ? zmsg : "damaged or truncated gzip") + ")");
-        if (got == 0) break;
-        ps.feed(buf.data(), (size_t)got, put);
-    }
-    ps.finish(put);
-}
+using np2seq::parse_file;
 
 // ---------------------------------------------------------------------------------------------------------------
 // pieces between the reader threads and the counting thread

@@ -2,6 +2,7 @@
 #pragma once
 #include <cstdint>
 #include <hip/hip_runtime.h>
+#include <string>
 
 #include "np2_kernels.hpp"
 #include "np2_trio_core.hpp"
@@ -28,4 +29,12 @@ void launch_trio_scan(hipStream_t s, const YakDev &pat, const YakDev &mat, const
 // k_trio_join: the pairs across tile boundaries, one block over all tiles (a segmented scan of q.tiles); after the scan
 void launch_trio_join(hipStream_t s, const TrioScan &q);
 
+
+} // namespace np2
+
+struct np2_ctx;
+namespace np2 {
+// np2_trio_host.cpp: everything about the two tables and the thresholds, before anything is launched (NP2_E_ARG, the
+// message begins with `who`)
+void trio_check_tables(np2_ctx *cx, int pat_idx, int mat_idx, uint16_t min_count, uint16_t mid_count, const std::string &who);
 } // namespace np2

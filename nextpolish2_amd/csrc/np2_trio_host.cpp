@@ -33,8 +33,19 @@ struct TrioBufs { // released after the call's device work has completed: cached
     TrioBufs() { stage.cached = desc.cached = tiles.cached = pat_bits.cached = mat_bits.cached = carry.cached = stats.cached = true; }
 };
 
+np2_trio_t trio_of(const uint64_t *st) { return np2_trio_t{st[0], st[1], st[2], {st[3], st[4], st[5], st[6]}}; }
+
+void add_to(np2_trio_t &o, const uint64_t *st) {
+    o.n_kmers += st[0];
+    o.n_pat += st[1];
+    o.n_mat += st[2];
+    for (int i = 0; i < 4; ++i) o.pairs[i] += st[3 + i];
+}
+
+} // namespace
+
 // everything about the tables and the thresholds, before anything is launched
-void check_tables(np2_ctx *cx, int pat_idx, int mat_idx, uint16_t min_count, uint16_t mid_count, const std::string &who) {
+void np2::trio_check_tables(np2_ctx *cx, int pat_idx, int mat_idx, uint16_t min_count, uint16_t mid_count, const std::string &who) {
     const int n = (int)cx->yaks.size();
     if (pat_idx < 0 || pat_idx >= n)
         throw Np2Error(NP2_E_ARG, who + ": pat_idx " + std::to_string(pat_idx) + " out of range (the context has " + std::to_string(n) + " tables)");
@@ -49,17 +60,6 @@ void check_tables(np2_ctx *cx, int pat_idx, int mat_idx, uint16_t min_count, uin
                                       std::to_string(mid_count) + ")");
 }
 
-np2_trio_t trio_of(const uint64_t *st) { return np2_trio_t{st[0], st[1], st[2], {st[3], st[4], st[5], st[6]}}; }
-
-void add_to(np2_trio_t &o, const uint64_t *st) {
-    o.n_kmers += st[0];
-    o.n_pat += st[1];
-    o.n_mat += st[2];
-    for (int i = 0; i < 4; ++i) o.pairs[i] += st[3 + i];
-}
-
-} // namespace
-
 extern "C" {
 
 int np2_trio_strings(np2_ctx_t *cx, int pat_idx, int mat_idx, const uint8_t *strs, const uint64_t *off, uint64_t n,
@@ -67,7 +67,7 @@ int np2_trio_strings(np2_ctx_t *cx, int pat_idx, int mat_idx, const uint8_t *str
     if (!cx) return NP2_E_ARG;
     return abi_guard([&] {
         // every argument is checked before anything is launched
-        check_tables(cx, pat_idx, mat_idx, min_count, mid_count, "np2_trio_strings");
+        np2::trio_check_tables(cx, pat_idx, mat_idx, min_count, mid_count, "np2_trio_strings");
         if (!out) throw Np2Error(NP2_E_ARG, "np2_trio_strings: out is NULL");
         if (n && !off) throw Np2Error(NP2_E_ARG, "np2_trio_strings: off is NULL with n > 0");
         for (uint64_t i = 0; i < n; ++i)
@@ -173,7 +173,7 @@ int np2_trio_device(np2_ctx_t *cx, int pat_idx, int mat_idx, const uint8_t *dev_
                     uint16_t mid_count, np2_trio_t *out, uint8_t *pat_bits, uint8_t *mat_bits, float *kernel_ms) {
     if (!cx) return NP2_E_ARG;
     return abi_guard([&] {
-        check_tables(cx, pat_idx, mat_idx, min_count, mid_count, "np2_trio_device");
+        np2::trio_check_tables(cx, pat_idx, mat_idx, min_count, mid_count, "np2_trio_device");
         if (!out) throw Np2Error(NP2_E_ARG, "np2_trio_device: out is NULL");
         if (len && !dev_seq) throw Np2Error(NP2_E_ARG, "np2_trio_device: dev_seq is NULL with a non-zero length");
         if (tiles_of(len) >= QV_FIRST) throw Np2Error(NP2_E_ARG, "np2_trio_device: the sequence is too long");

@@ -15,7 +15,7 @@ IO_SYMBOLS = ["np2_fasta_open", "np2_fasta_next", "np2_fasta_close", "np2_yak_lo
               "np2_bam_close", "np2_bam_n_refs", "np2_bam_ref_name", "np2_io_last_error", "np2_contig_from_records",
               "np2_contig_from_bam", "np2_contig_export", "np2_ctx_create_from_files", "np2_bgzf_inflate_device", "np2_crc32_device",
               "np2_kcount_files", "np2_kcount_bytes", "np2_kcount_files_to_dumps", "np2_ctx_create_from_reads", "np2_kcount_last_stats",
-              "np2_seqfile_stream"]
+              "np2_seqfile_stream", "np2_bin_files", "np2_seqfile_reads"]
 
 
 class np2_front_opts_t(C.Structure):
@@ -26,6 +26,10 @@ class np2_front_opts_t(C.Structure):
 
 class np2_kcount_opts_t(C.Structure):
     _fields_ = [("min_count", C.c_uint16), ("mem_bytes", C.c_uint64)]
+
+
+class np2_bin_out_t(C.Structure):
+    _fields_ = [("tsv", C.c_char_p), ("pat_list", C.c_char_p), ("mat_list", C.c_char_p), ("pat_fa", C.c_char_p), ("mat_fa", C.c_char_p)]
 
 
 class FrontOpts:
@@ -107,6 +111,9 @@ def _bind_kcount(L):
     L.np2_ctx_create_from_reads.argtypes = [C.POINTER(vp), C.c_int, cpp, C.c_int, vp, C.c_int, ko]
     L.np2_kcount_last_stats.argtypes = [C.POINTER(C.c_uint64)] * 3 + [C.POINTER(C.c_uint32)] * 2 + [C.POINTER(C.c_float)] * 2
     L.np2_seqfile_stream.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_uint64)]
+    from .api import np2_bin_opts_t
+    L.np2_bin_files.argtypes = [vp, C.c_int, C.c_int, cpp, C.c_int, C.POINTER(np2_bin_opts_t), C.POINTER(np2_bin_out_t), vp, C.POINTER(C.c_float)]
+    L.np2_seqfile_reads.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(vp), C.POINTER(C.c_uint64)]
 
 
 def _io_check(rc):
@@ -201,6 +208,38 @@ def seqfile_stream(path):
         return C.string_at(p.value, n.value) if n.value else b""
     finally:
         L.np2_free(p)
+
+
+def seqfile_reads(path):
+    """np2_seqfile_reads (host only): (names, ends) of one sequence file as the read binner's reader sees it: the reads'
+    names (header up to the first whitespace, without '>' / '@') and, per read, the offset of its separator in the
+    file's separator stream (seqfile_stream)."""
+    L = _bind()
+    names, nb, ends, n = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64()
+    _io_check(L.np2_seqfile_reads(os.fspath(path).encode(), C.byref(names), C.byref(nb), C.byref(ends), C.byref(n)))
+    try:
+        text = C.string_at(names.value, nb.value) if nb.value else b""
+        e = np.ctypeslib.as_array(C.cast(ends, C.POINTER(C.c_uint64)), shape=(max(1, n.value),))[:n.value].copy()
+        return [x.decode() for x in text.split(b"\n")[:-1]], e
+    finally:
+        L.np2_free(names)
+        L.np2_free(ends)
+
+
+def bin_files(pol, paths, pat_idx=0, mat_idx=1, min_count=2, mid_count=5, min_score=2, minor_permille=330, tsv=None, pat_list=None,
+              mat_list=None, pat_fa=None, mat_fa=None):
+    """np2_bin_files: read files -> classes on the device of Polisher `pol`, written natively (every output path may be
+    None) -> ({"p": n, "m": n, "a": n, "0": n}, kernel_ms)."""
+    from .api import np2_bin_opts_t
+    L = _bind()
+    arr, n = _paths(paths)
+    enc = lambda p: None if p is None else os.fspath(p).encode()
+    out = np2_bin_out_t(enc(tsv), enc(pat_list), enc(mat_list), enc(pat_fa), enc(mat_fa))
+    o = np2_bin_opts_t(min_count, mid_count, min_score, minor_permille)
+    counts = np.zeros(4, np.uint64)
+    ms = C.c_float()
+    pol._check(L.np2_bin_files(pol._h, pat_idx, mat_idx, arr, n, C.byref(o), C.byref(out), counts.ctypes.data, C.byref(ms)))
+    return dict(zip("pma0", (int(x) for x in counts))), ms.value
 
 
 def count_kmers(inputs, ks, min_count=1, device=0, mem_bytes=0):

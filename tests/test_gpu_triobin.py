@@ -1,0 +1,353 @@
+"""The read binner on the device (np2_bin_stream, np2_bin_files, python -m nextpolish2_amd.triobin) against the numpy
+brute force of tests/test_triobin_cpu.py (numpy_trio per read, the class rule written out again) AND against
+np2_trio_strings given the same reads as sequences of their own: an independent device path with its own staging layout.
+
+Every comparison is exact.  A case is a few hundred KB of reads at most."""
+import gzip
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from nextpolish2_amd import Polisher, api, triobin
+from nextpolish2_amd import io as np2io
+from nextpolish2_amd._types import Yak
+from nextpolish2_amd.synth import Synth
+from test_gpu_qv import TILE, noisy, random_bases, yak_table
+from test_gpu_trio import chimera, parent_yak
+from test_kcount_cpu import numpy_count
+from test_trio_cpu import numpy_trio
+from test_triobin_cpu import brute_force, expected_class
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ENV = dict(os.environ, PYTHONPATH=ROOT)
+E_ARG = -1
+KS = (21, 31)
+THRESHOLDS = ((1, 1), (2, 5), (5, 1023))
+
+
+def stream_of(reads):
+    return b"".join(r + b"\n" for r in reads)
+
+
+def check_reads(pol, k, tp, tm, reads, min_count, mid_count, pat_idx=0, mat_idx=1, min_score=2, minor_permille=330, exp=None):
+    """np2_bin_stream == the brute force == np2_trio_strings with every read a sequence of its own -> the BinResult"""
+    r = pol.bin_stream(pat_idx, mat_idx, reads, min_count, mid_count, min_score, minor_permille, stats=True)
+    assert len(r.classes) == len(reads) and r.stats.shape == (len(reads), 7) and r.stats.dtype == np.uint32
+    exp = exp if exp is not None else brute_force(reads, k, tp, tm, min_count, mid_count, min_score, minor_permille)
+    t = pol.trio_strings(pat_idx, mat_idx, reads, min_count, mid_count)
+    for i, (e_stats, e_cls) in enumerate(exp):
+        got = tuple(int(x) for x in r.stats[i])
+        assert got == e_stats, (k, min_count, mid_count, i, len(reads[i]))
+        assert got == tuple(int(x) for x in t.stats[i]), (k, min_count, mid_count, i, len(reads[i]))
+        assert chr(r.classes[i]) == e_cls, (k, min_count, mid_count, i, e_stats)
+    # the tallies nobody asked for change nothing
+    r2 = pol.bin_stream(pat_idx, mat_idx, reads, min_count, mid_count, min_score, minor_permille)
+    assert r2.classes == r.classes and r2.stats is None
+    return r
+
+
+# ---- 1. equality: every length, every phase ---------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def edge_setup():
+    """two parents a SNP in a hundred apart, a base sequence that changes parent every 700 bases, tables for k 21 and 31"""
+    rng = np.random.default_rng(23)
+    p = random_bases(rng, 60000)
+    m = noisy(rng, p, 0.01)
+    yaks = [y for k in KS for y in (parent_yak(p, k), parent_yak(m, k))]  # tables 2 i (paternal), 2 i + 1 (maternal) of KS[i]
+    pol = Polisher(yaks)
+    yield rng, chimera(p, m, 700), p, m, [yak_table(y) for y in yaks], pol
+    pol.close()
+
+
+def edge_reads(rng, base, p, m, k):
+    """The stream of case 1 as a list of reads; built with the running offset in hand, so that the reads named below lie
+    where they must."""
+    reads, at = [], [0]
+
+    def put(r):
+        reads.append(r)
+        at[0] += len(r) + 1
+
+    def cut(n, src=base):
+        a = int(rng.integers(0, len(src) - n))
+        return src[a:a + n]
+
+    put(cut(TILE - 1))          # its separator is tile 0's last byte
+    assert at[0] == TILE
+    # three tiles, tile-aligned: marker-bearing ends, a middle tile without a marker (bases no table holds)
+    middle = random_bases(rng, TILE)
+    three = cut(TILE) + middle + cut(TILE - 1)
+    put(three)
+    assert at[0] == 4 * TILE
+    put(cut(TILE))              # a whole tile: its separator is the next tile's first byte
+    put(cut(TILE + 1))
+    put(cut(2 * TILE + 5))
+    for n in (0, 1, k - 1, k, k + 1, 31, 32, 33, 150):
+        put(noisy(rng, cut(n), 0.02))
+    for _ in range(70):         # a run of empty reads across two lane boundaries
+        put(b"")
+    put(cut(400, p))
+    put(cut((-at[0] - 21) % TILE))  # ... and one across a tile boundary: 20 separators before it, 30 behind
+    assert at[0] % TILE == TILE - 20
+    for _ in range(50):
+        put(b"")
+    put(cut(400, m))
+    # the same short reads behind padding reads of length 0 .. 32: a boundary at every phase of a lane's stretch
+    body = [noisy(rng, cut(n), 0.02) for n in (0, 1, k - 1, k, k + 1, 31, 32, 33, 150)] + [cut(300, p), b"", cut(300, m), cut(700)]
+    for pad in range(33):
+        put(cut(pad))
+        for r in body:
+            put(r)
+    return reads, three, middle
+
+
+@pytest.mark.parametrize("ki", [0, 1])
+def test_equality_on_every_length_and_phase(edge_setup, ki):
+    rng, base, p, m, tables, pol = edge_setup
+    k = KS[ki]
+    tp, tm = tables[2 * ki], tables[2 * ki + 1]
+    reads, three, middle = edge_reads(np.random.default_rng(5), base, p, m, k)
+    assert len(stream_of(reads)) < 200_000
+    # the precondition of the three-tile read: markers in both ends, none in the middle tile
+    ends = [numpy_trio(x, k, tp, tm, 2, 5)[0] for x in (three[:TILE], three[TILE - k + 1:2 * TILE + k - 1], three[2 * TILE:])]
+    assert ends[0][1] + ends[0][2] > 0 and ends[1][1:] == (0,) * 6 and ends[2][1] + ends[2][2] > 0
+    seen, tallies = set(), {}
+    for min_count, mid_count in THRESHOLDS:
+        exp = brute_force(reads, k, tp, tm, min_count, mid_count)
+        tallies[(min_count, mid_count)] = [st for st, _ in exp]
+        r = check_reads(pol, k, tp, tm, reads, min_count, mid_count, 2 * ki, 2 * ki + 1, exp=exp)
+        seen.update(chr(c) for c in r.classes)
+        if mid_count <= 5:
+            tot = r.stats.sum(axis=0)
+            assert tot[1] > 0 and tot[2] > 0 and tot[4] > 0 and tot[5] > 0  # both kinds of marker, switches inside reads
+        else:
+            assert not r.stats[:, 1:].any() and set(r.classes) == {ord("0")}  # no count reaches 1023
+        assert r.kernel_ms > 0
+    assert seen == set("pma0")
+    # other score options on the same tallies
+    for min_score, permille in ((1, 0), (40, 1000)):
+        exp = [(st, expected_class(st[3], st[6], min_score, permille)) for st in tallies[(2, 5)]]
+        check_reads(pol, k, tp, tm, reads, 2, 5, 2 * ki, 2 * ki + 1, min_score, permille, exp=exp)
+    # a stream handed over as bytes is the same call; no read at all is fine
+    r = pol.bin_stream(2 * ki, 2 * ki + 1, stream_of(reads[:40]), stats=True)
+    assert r.classes == pol.bin_stream(2 * ki, 2 * ki + 1, reads[:40]).classes
+    e = pol.bin_stream(2 * ki, 2 * ki + 1, [], stats=True)
+    assert e.classes == b"" and e.stats.shape == (0, 7)
+    assert pol.bin_stream(2 * ki, 2 * ki + 1, [b"", b""]).classes == b"00"
+
+
+# ---- 2. layout independence -----------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def layout_reference(edge_setup):
+    rng, base, p, m, tables, pol = edge_setup
+    reads, _, _ = edge_reads(np.random.default_rng(5), base, p, m, 21)
+    ref = pol.bin_stream(0, 1, reads, 2, 5, stats=True)  # (compared with the brute force by the test above)
+    return reads, ref
+
+
+@pytest.mark.parametrize("stage_tiles", [1, 2, 5])
+@pytest.mark.parametrize("blocks", [1, 3, None])
+def test_layout_independence(edge_setup, layout_reference, monkeypatch, blocks, stage_tiles):
+    """NP2_BIN_TEST_STAGE_TILES: pieces of a few tiles, so that reads go on from piece to piece with their tallies and
+    their last marker; NP2_BIN_TEST_BLOCKS: one block scans every tile in turn, or three share them"""
+    rng, base, p, m, tables, pol = edge_setup
+    reads, ref = layout_reference
+    monkeypatch.setenv("NP2_BIN_TEST_STAGE_TILES", str(stage_tiles))
+    if blocks is not None:
+        monkeypatch.setenv("NP2_BIN_TEST_BLOCKS", str(blocks))
+    r = pol.bin_stream(0, 1, reads, 2, 5, stats=True)
+    assert r.classes == ref.classes and r.stats.tobytes() == ref.stats.tobytes()
+
+
+# ---- 3. the known answer ------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def diploid():
+    s = Synth(60000, depth=30, seed=11, diploid=True, read_len_mean=9000.0, read_len_sd=1500.0)
+    yaks = [parent_yak(s.hap1, 21), parent_yak(s.hap2, 21)]
+    pol = Polisher(yaks)
+    yield s, yaks, [yak_table(y) for y in yaks], pol
+    pol.close()
+
+
+def diploid_reads(s, rng, n_each=12):
+    n = min(len(s.hap1), len(s.hap2))
+    groups = {"h1": [], "h2": [], "chim": []}
+    for _ in range(n_each):
+        a, ln = int(rng.integers(0, n - 6000)), int(rng.integers(500, 6000))
+        groups["h1"].append(s.hap1[a:a + ln])
+        a, ln = int(rng.integers(0, n - 6000)), int(rng.integers(500, 6000))
+        groups["h2"].append(s.hap2[a:a + ln])
+        a, ln = int(rng.integers(0, n - 6000)), int(rng.integers(500, 6000))
+        groups["chim"].append(s.hap1[a:a + ln // 2] + s.hap2[a + ln // 2:a + ln])
+    groups["h1"] += [s.hap1[100:100 + 21], s.hap1[:40]]  # too short for two adjacent markers
+    return groups
+
+
+def test_known_answer_on_reads_of_a_diploid_contig(diploid):
+    s, yaks, (tp, tm), pol = diploid
+    groups = diploid_reads(s, np.random.default_rng(2))
+    order = [(g, r) for g in ("h1", "chim", "h2") for r in groups[g]]
+    reads = [r for _, r in order]
+    exp = brute_force(reads, 21, tp, tm, 2, 5)
+    classes = [c for _, c in exp]
+    assert "p" in classes and "m" in classes and "a" in classes  # the precondition, from the brute force
+    r = check_reads(pol, 21, tp, tm, reads, 2, 5, exp=exp)
+    for (g, _), c, st in zip(order, r.classes.decode(), r.stats):
+        assert not (g == "h1" and c == "m") and not (g == "h2" and c == "p")
+        if int(st[3]) < 2 and int(st[6]) < 2:  # no two adjacent markers of one parent: nothing to go by
+            assert c == "0"
+    assert any(int(st[3]) < 2 and int(st[6]) < 2 for st in r.stats)
+    # the parents swapped: the mirror
+    sw = pol.bin_stream(1, 0, reads, 2, 5, stats=True)
+    assert sw.classes == r.classes.translate(bytes.maketrans(b"pm", b"mp"))
+    assert np.array_equal(sw.stats[:, [0, 2, 1, 6, 5, 4, 3]], r.stats)
+
+
+# ---- 4. tables that repeat keys -----------------------------------------------------------------------------------------------
+def test_repeated_keys_answer_like_trio_strings():
+    """Hand-made dumps with repeated keys in their buckets (yak writes none): the last word in file order is the k-mer's
+    count, as np2_trio_strings has it."""
+    rng = np.random.default_rng(29)
+    p = random_bases(rng, 20000)
+    m = noisy(rng, p, 0.01)
+
+    def with_repeats(seq, first, last):
+        words, off = numpy_count((seq + b"\n") * 5, 21)
+        out_words, out_off = [], [0]
+        for b in range(1024):
+            w = words[int(off[b]):int(off[b + 1])]
+            keys = w[::3] & ~np.uint64(1023)  # every third word again, with other counts, before and after the original
+            w = np.concatenate([keys | np.uint64(first), w, keys | np.uint64(last)])
+            out_words.append(w)
+            out_off.append(out_off[-1] + len(w))
+        return Yak(21, np.concatenate(out_words), np.array(out_off, np.uint64))
+
+    reads = [chimera(p, m, 900)[:9000], b"", chimera(m, p, 1100)[9000:15000], p[100:130], noisy(rng, p[:TILE + 50]), m[5000:5600], p[7000:7400]]
+    seen = set()
+    for yaks in ([with_repeats(p, 9, 1), parent_yak(m, 21)], [parent_yak(p, 21), with_repeats(m, 1, 7)], [with_repeats(p, 7, 3), with_repeats(m, 2, 1)]):
+        pol = Polisher(yaks)
+        for min_count, mid_count in ((2, 5), (1, 1), (4, 7), (2, 3)):
+            r = pol.bin_stream(0, 1, reads, min_count, mid_count, stats=True)
+            t = pol.trio_strings(0, 1, reads, min_count, mid_count)
+            assert np.array_equal(r.stats.astype(np.uint64), t.stats)
+            assert r.classes.decode() == "".join(expected_class(int(st[3]), int(st[6])) for st in t.stats)
+            seen.add(r.stats.tobytes())
+        pol.close()
+    assert len(seen) >= 4  # (the repeats change the answers: a third of the keys read 1, 3 or 7 instead of 5)
+
+
+# ---- 5. files -----------------------------------------------------------------------------------------------------------------
+def expected_outputs(named, exp):
+    """(tsv, paternal list, maternal list, paternal FASTA, maternal FASTA) as bytes from [(name, read)] and the brute force"""
+    tsv = ["\t".join(triobin.TSV_HEADER) + "\n"]
+    lists, fas = {"pat": [], "mat": []}, {"pat": [], "mat": []}
+    for (name, seq), (st, cls) in zip(named, exp):
+        nk, n_pat, n_mat, pp, pm, mp, mm = st
+        tsv.append("\t".join([name, cls] + [str(x) for x in (pp, mm, n_pat, n_mat, pm, mp, nk, len(seq))]) + "\n")
+        for side in ("pat", "mat"):
+            if triobin.keep(cls, side):
+                lists[side].append(name + "\n")
+                fas[side].append(">" + name + "\n" + seq.decode("latin-1") + "\n")
+    return tuple("".join(x).encode("latin-1") for x in (tsv, lists["pat"], lists["mat"], fas["pat"], fas["mat"]))
+
+
+def test_files_through_the_module_on_dumps_and_on_parental_reads(diploid, tmp_path):
+    s, yaks, (tp, tm), pol = diploid
+    groups = diploid_reads(s, np.random.default_rng(9), n_each=8)
+    reads = [r for g in ("h1", "h2", "chim") for r in groups[g]] + [b"", b"ACGTNNNN" * 10]
+    named = [(f"read{i}/{i % 3}", r) for i, r in enumerate(reads)]
+    half = len(named) // 2
+    fa, fq = str(tmp_path / "a.fa.gz"), str(tmp_path / "b.fq")
+    with gzip.open(fa, "wb") as f:  # multi-line FASTA with descriptions
+        for name, seq in named[:half]:
+            f.write(b">" + name.encode() + b" some description\n" + b"".join(seq[i:i + 80] + b"\n" for i in range(0, len(seq), 80)))
+    with open(fq, "wb") as f:  # FASTQ, quality lines that begin with '@'
+        for name, seq in named[half:]:
+            f.write(b"@" + name.encode() + b"\n" + seq + b"\n+\n" + b"@" * len(seq) + b"\n")
+    exp = brute_force(reads, 21, tp, tm, 2, 5)
+    assert {"p", "m", "0"} <= {c for _, c in exp}
+    e_tsv, e_pl, e_ml, e_pf, e_mf = expected_outputs(named, exp)
+    dumps = []
+    for name, y in zip(("pat", "mat"), yaks):
+        dumps.append(str(tmp_path / f"{name}.yak"))
+        np2io.write_yak(dumps[-1], y)
+
+    def run(tag, front, extra=()):
+        out = {x: str(tmp_path / f"{tag}.{x}") for x in ("tsv", "pl", "ml", "pf", "mf")}
+        r = subprocess.run([sys.executable, "-m", "nextpolish2_amd.triobin"] + front + ["-o", out["tsv"], "--pat_list", out["pl"], "--mat_list", out["ml"],
+                           "--pat_fa", out["pf"], "--mat_fa", out["mf"]] + list(extra), capture_output=True, env=ENV, timeout=600)
+        assert r.returncode == 0, r.stderr.decode()
+        assert r.stdout == b""
+        return {x: open(p, "rb").read() for x, p in out.items()}, r.stderr.decode()
+
+    got, err = run("d", dumps + [fa, fq])
+    assert got["tsv"] == e_tsv and got["pl"] == e_pl and got["ml"] == e_ml and got["pf"] == e_pf and got["mf"] == e_mf
+    n_cls = {c: sum(1 for _, x in exp if x == c) for c in "pma0"}
+    for c in "pma0":
+        assert f"{c}\t{n_cls[c]}\t" in err
+    # small pieces: reads, names and sequences go on from piece to piece
+    env_small = dict(ENV, NP2_BIN_TEST_STAGE_TILES="1", NP2_BIN_TEST_BLOCKS="3")
+    out = str(tmp_path / "small.pf")
+    r = subprocess.run([sys.executable, "-m", "nextpolish2_amd.triobin"] + dumps + [fa, fq, "--pat_fa", out], capture_output=True, env=env_small, timeout=600)
+    assert r.returncode == 0, r.stderr.decode()
+    assert r.stdout == e_tsv and open(out, "rb").read() == e_pf  # (no -o: the report goes to standard output)
+    # other options
+    exp2 = brute_force(reads, 21, tp, tm, 1, 3, 1, 0)
+    got2, _ = run("o", dumps + [fa, fq], ["--min_count", "1", "--mid_count", "3", "--min_score", "1", "--max_minor", "0"])
+    assert (got2["tsv"], got2["pl"], got2["ml"], got2["pf"], got2["mf"]) == expected_outputs(named, exp2)
+    # the parents' reads counted on the device: every haplotype five times over, one read a line, in two files each
+    sr = {}
+    for name, hap in (("pat", s.hap1), ("mat", s.hap2)):
+        sr[name] = [str(tmp_path / f"{name}.{i}.txt") for i in range(2)]
+        open(sr[name][0], "wb").write((hap + b"\n") * 2)
+        open(sr[name][1], "wb").write((hap + b"\n") * 3)
+    got3, _ = run("r", ["--pat_sr"] + sr["pat"] + ["--mat_sr", sr["mat"][0], "--mat_sr", sr["mat"][1], "--sr_k", "21", "--sr_min_count", "2", fa, fq])
+    assert got3 == got
+
+
+# ---- 6. argument errors -----------------------------------------------------------------------------------------------------------
+def test_argument_errors_return_before_a_launch_and_leave_the_context_usable(edge_setup):
+    import ctypes as C
+    rng, base, p, m, tables, pol = edge_setup
+    L = api.lib()
+    n_tables = 2 * len(KS)
+    stream = np.frombuffer(base[:60] + b"\n" + base[100:140] + b"\n\0", dtype=np.uint8)
+    n_bytes = 102
+    cls = np.zeros(8, np.uint8)
+    good = pol.bin_stream(0, 1, [base[:3000], b""], stats=True)
+    assert int(good.stats[0, 0]) == 3000 - 21 + 1
+
+    def call(p_idx=0, m_idx=1, strm=stream.ctypes.data, nb=n_bytes, nr=2, opts=(2, 5, 2, 330), out=cls.ctypes.data):
+        o = api.np2_bin_opts_t(*opts) if opts is not None else None
+        return L.np2_bin_stream(pol._h, p_idx, m_idx, strm, nb, nr, C.byref(o) if o is not None else None, out, None, None)
+
+    assert call() == 0 and call(opts=None) == 0
+    cases = [
+        (lambda: call(p_idx=n_tables), "pat_idx"), (lambda: call(p_idx=-1), "pat_idx"), (lambda: call(m_idx=n_tables), "mat_idx"),
+        (lambda: call(m_idx=-1), "mat_idx"), (lambda: call(1, 1), "pat_idx == mat_idx"), (lambda: call(0, 3), "different k"),
+        (lambda: call(opts=(0, 5, 2, 330)), "thresholds"), (lambda: call(opts=(6, 5, 2, 330)), "thresholds"),
+        (lambda: call(opts=(2, 1024, 2, 330)), "thresholds"), (lambda: call(opts=(2, 5, 2, 1001)), "minor_permille"),
+        (lambda: call(nb=n_bytes - 1), "does not end in a newline"), (lambda: call(nr=1), "n_reads"), (lambda: call(nr=3), "n_reads"),
+        (lambda: call(nr=0), "n_reads"), (lambda: call(out=None), "cls is NULL"), (lambda: call(strm=None), "stream is NULL"),
+    ]
+    for fn, text in cases:
+        assert fn() == E_ARG
+        assert text in L.np2_last_error(pol._h).decode(), text
+        r = pol.bin_stream(0, 1, [base[:3000], b""], stats=True)  # the context still answers
+        assert r.classes == good.classes and np.array_equal(r.stats, good.stats)
+    for bad in ((9, 0, 2, 5, 2, 330), (0, 0, 2, 5, 2, 330), (0, 1, 0, 5, 2, 330), (0, 1, 3, 2, 2, 330), (0, 1, 2, 5, 2, 1001)):
+        with pytest.raises(api.Np2Error) as e:
+            pol.bin_stream(bad[0], bad[1], [b"ACGT"], *bad[2:])
+        assert e.value.code == E_ARG
+    with pytest.raises(ValueError):
+        pol.bin_stream(0, 1, [b"AC\nGT"])
+    assert L.np2_bin_stream(None, 0, 1, None, 0, 0, None, None, None, None) == E_ARG
+    assert call(strm=None, nb=0, nr=0) == 0  # no read at all is fine
+    with pytest.raises(api.Np2Error) as e:
+        np2io.bin_files(pol, [os.path.join(ROOT, "missing.fa")])
+    assert e.value.code == E_ARG and "cannot open" in str(e.value)
