@@ -189,6 +189,31 @@ int np2_bin_stream(np2_ctx_t *ctx, int pat_idx, int mat_idx, const uint8_t *stre
                    const np2_bin_opts_t *opts, uint8_t *cls /* [n_reads] */, np2_bin_t *stats /* [n_reads] or NULL */,
                    float *kernel_ms);
 
+/* K-mer completeness and copy-number spectrum of an assembly set against the reads' table `yak_idx` (Merqury's second
+ * headline number and the spectra-cn it is read from; the semantics are this project's, not Merqury's files byte for
+ * byte).  The set is the n sequences strs[off[i] .. off[i+1]); its k-mers are canonical, bases and validity are
+ * np2_qv_strings' (ACGTUacgtu are bases, any other byte breaks the run, no k-mer spans two sequences), and
+ * cn(x) = min(occurrences of x in the whole set, 1023): what np2_kcount_bytes with min_count 1 stores.  A k-mer of the
+ * reads' table is RELIABLE when its stored count c is >= max(min_count, 1).  Over DISTINCT k-mers:
+ *   n_read      reliable read k-mers;                  n_found     those of them with cn > 0;
+ *   n_asm       k-mers of the set;                     n_asm_only  those of them whose read count, read as 0 when it is
+ *                                                                  below min_count (np2_qv_*'s rule), is 0;
+ *   completeness = n_found / n_read (nan when n_read == 0);
+ *   spectra[cls * 1024 + c] (6 * 1024 counters, or NULL): reliable read k-mers with stored count c and
+ *     cls = min(cn, 5): 0 is read-only, 1 .. 4 are the copy numbers, 5 is "more than 4".  Everything sums to n_read, the
+ *     rows cls >= 1 to n_found, and the columns c < max(min_count, 1) are 0;
+ *   asm_only[cls] (6 counters, or NULL): the n_asm_only k-mers by min(cn, 5); entry 0 is always 0.
+ * The set is counted on the device for the table's k, in one pass within the counter's default memory budget
+ * (NP2_E_NOMEM otherwise); np2_kcount_last_stats describes that count.  kernel_ms (or NULL): HIP-event time of the two
+ * join kernels alone.  NP2_E_UNSUPPORTED, before anything is launched: a table that repeats keys (a k-mer would count
+ * twice).  NP2_E_ARG, before anything is launched and with a message in np2_last_error: yak_idx out of range,
+ * min_count > 1023, out NULL, off NULL with n > 0, descending off, strs NULL with a non-zero length.  n == 0, empty
+ * sequences and sequences shorter than k are fine: n_asm = 0, n_found = 0 and all of n_read lies in class 0. */
+typedef struct np2_cmp { uint64_t n_read, n_found, n_asm, n_asm_only; } np2_cmp_t;
+int np2_cmp_strings(np2_ctx_t *ctx, int yak_idx, const uint8_t *strs, const uint64_t *off, uint64_t n,
+                    uint16_t min_count, np2_cmp_t *out, uint64_t *spectra /* [6*1024] or NULL */,
+                    uint64_t *asm_only /* [6] or NULL */, float *kernel_ms /* or NULL */);
+
 /* Stage-level exports for kernel parity tests and profiling.
  * After np2_polish_resident with tracing enabled, np2_trace_get returns a pointer to a
  * host copy of intermediate `name` of pass `pass` (valid until the next polish call). */

@@ -27,6 +27,7 @@ ABI_SYMBOLS = [
     "np2_shard_final_device", "np2_shard_fetch", "np2_alloc_pinned", "np2_trim_device_cache",
     "np2_shard_end", "np2_swiss_order", "np2_batch_set_timing", "np2_batch_set_priority", "np2_batch_last_diff_ms", "np2_batch_stats", "np2_batch_last_call_ms",
     "np2_qv_strings", "np2_qv_device", "np2_trio_strings", "np2_trio_device", "np2_bin_stream",
+    "np2_cmp_strings",
 ]
 
 # include/np2_io.h (input side; bound by nextpolish2_amd.io)
@@ -96,6 +97,7 @@ def _lib_locked():
         L.np2_trio_strings.argtypes = [vp, C.c_int, C.c_int, vp, vp, u64, u16, u16, vp, vp, vp, C.POINTER(C.c_float)]
         L.np2_trio_device.argtypes = [vp, C.c_int, C.c_int, vp, u64, u16, u16, vp, vp, vp, C.POINTER(C.c_float)]
         L.np2_bin_stream.argtypes = [vp, C.c_int, C.c_int, vp, u64, u64, C.POINTER(np2_bin_opts_t), vp, vp, C.POINTER(C.c_float)]
+        L.np2_cmp_strings.argtypes = [vp, C.c_int, vp, vp, u64, u16, vp, vp, vp, C.POINTER(C.c_float)]
         L.np2_ctx_set_trace.argtypes = [vp, C.c_int]
         L.np2_ctx_set_timing.argtypes = [vp, C.c_int]
         L.np2_ctx_set_timing.restype = None
@@ -225,6 +227,26 @@ class BinResult:
 
     def __init__(self, classes, stats, kernel_ms):
         self.classes, self.stats, self.kernel_ms = classes, stats, kernel_ms
+
+
+class CmpStats:
+    """What np2_cmp_strings returns.  stats: (n_read, n_found, n_asm, n_asm_only), distinct k-mers: reliable read k-mers,
+    those of them the assembly set holds, the set's k-mers, those of them the reads do not have; spectra: uint64 array
+    (6, 1024), spectra[min(cn, 5), c] = reliable read k-mers with stored count c and copy number cn in the set, or None;
+    asm_only: uint64[6], the n_asm_only k-mers by min(cn, 5); kernel_ms: HIP-event time of the two join kernels."""
+    __slots__ = ("stats", "spectra", "asm_only", "kernel_ms")
+
+    def __init__(self, stats, spectra, asm_only, kernel_ms):
+        self.stats, self.spectra, self.asm_only, self.kernel_ms = stats, spectra, asm_only, kernel_ms
+
+    n_read = property(lambda self: self.stats[0])
+    n_found = property(lambda self: self.stats[1])
+    n_asm = property(lambda self: self.stats[2])
+    n_asm_only = property(lambda self: self.stats[3])
+
+    @property
+    def completeness(self):
+        return self.stats[1] / self.stats[0] if self.stats[0] else float("nan")
 
 
 class ResidentContig:
@@ -427,6 +449,22 @@ class Polisher:
                                         C.byref(ms)))
         return QvStats(stats, h, [raw[:(int(n) + 7) // 8]] if bits else None, ms.value)
 
+    def cmp_strings(self, yak_idx, seqs, min_count=2, spectra=False):
+        """np2_cmp_strings: k-mer completeness of the set `seqs` (bytes-like each, taken together) against the reads' table
+        `yak_idx` -> CmpStats.  A read k-mer is reliable when its stored count is >= max(min_count, 1)."""
+        seqs = [bytes(s) for s in seqs]
+        n = len(seqs)
+        off = np.zeros(n + 1, dtype=np.uint64)
+        if n:
+            off[1:] = np.cumsum([len(s) for s in seqs])
+        blob = np.frombuffer(b"".join(seqs) + b"\0", dtype=np.uint8)
+        st = np.zeros(4, dtype=np.uint64)
+        sp = np.zeros((6, 1024), dtype=np.uint64) if spectra else None
+        ao = np.zeros(6, dtype=np.uint64)
+        ms = C.c_float()
+        self._check(lib().np2_cmp_strings(self._h, yak_idx, blob.ctypes.data, off.ctypes.data, n, min_count, st.ctypes.data,
+                                          sp.ctypes.data if spectra else None, ao.ctypes.data, C.byref(ms)))
+        return CmpStats(tuple(int(x) for x in st), sp, ao, ms.value)
 
     def trio_strings(self, pat_idx, mat_idx, seqs, min_count=2, mid_count=5, bits=False):
         """np2_trio_strings: parental markers and consecutive marker pairs of every sequence of `seqs` (bytes-like each)

@@ -60,6 +60,12 @@ def build_parser():
     p.add_argument("--qv_min_count", type=int, default=1, metavar="N", help="--qv reads a k-mer count below N as absent [1]")
     p.add_argument("--qv_bed", default=None, metavar="PREFIX",
                    help="with --qv: intervals covered by absent k-mers, PREFIX.k<K>.in.bed and PREFIX.k<K>.out.bed")
+    p.add_argument("--cmp", default=None, metavar="FILE",
+                   help="k-mer completeness of the assembly as read and as written, per k-mer table, as a TSV (the share of "
+                        "the reliable read k-mers the assembly holds)")
+    p.add_argument("--cmp_min_count", type=int, default=2, metavar="N", help="--cmp: a read k-mer counted at least N times is reliable [2]")
+    p.add_argument("--cmp_spectra", default=None, metavar="PREFIX",
+                   help="with --cmp: copy-number spectra, PREFIX.k<K>.in.tsv and PREFIX.k<K>.out.tsv")
     p.add_argument("--trio", default=None, metavar="FILE",
                    help="switch and Hamming error of every contig as read and as written against parental k-mer tables, as a TSV "
                         "(needs --trio_pat and --trio_mat)")
@@ -121,6 +127,18 @@ def _record_sequence(rec):
 def _qv_report(a, ks):
     from .qv import QvReport
     return QvReport(ks, a.qv_min_count, want_bed=a.qv_bed is not None)
+
+
+def _cmp_report(a, ks):
+    from .completeness import CmpReport
+    return CmpReport(ks, a.cmp_min_count, want_spectra=a.cmp_spectra is not None)
+
+
+def _cmp_finish(a, creport, pol, seqs_in, seqs_out):
+    """--cmp: the whole assembly as read and as written, one call per side and table, after the last contig"""
+    creport.add(pol, "in", seqs_in)
+    creport.add(pol, "out", seqs_out)
+    creport.write_cli(a.cmp, a.cmp_spectra)
 
 
 def _trio_report(a):
@@ -242,6 +260,9 @@ def _main_distributed(a, argv, t0, out, yaks, opts, fopts):
         treport, tpol = None, None
         if a.trio is not None:
             treport, tpol = _trio_report(a), _trio_polisher(a)
+        creport, cmp_in, cmp_out = None, [], []
+        if a.cmp is not None:
+            creport = _cmp_report(a, [y.k for y in yaks])
         for i, (name, seq) in enumerate(contigs):
             if i in records:
                 rec = records[i]
@@ -253,10 +274,19 @@ def _main_distributed(a, argv, t0, out, yaks, opts, fopts):
                 report.add(qpol, name, seq, _record_sequence(rec))
             if treport is not None:
                 treport.add(tpol, name, seq, _record_sequence(rec))
+            if creport is not None:
+                cmp_in.append(seq)
+                cmp_out.append(_record_sequence(rec))
         out.flush()
         if report is not None:
             qpol.close()
             report.write_cli(a.qv, a.qv_bed)
+        if creport is not None:
+            cpol = pol.clone()
+            try:
+                _cmp_finish(a, creport, cpol, cmp_in, cmp_out)
+            finally:
+                cpol.close()
         if treport is not None:
             tpol.close()
             treport.write_cli(a.trio, a.trio_bed)
@@ -293,6 +323,12 @@ def main(argv=None):
         parser.error("--qv_bed needs --qv")
     if not 0 <= a.qv_min_count <= 1023:
         parser.error("--qv_min_count: 0 .. 1023")
+    if a.cmp is not None and a.out_pos:
+        parser.error("--cmp measures the sequences of a FASTA output: not with --out_pos")
+    if a.cmp_spectra is not None and a.cmp is None:
+        parser.error("--cmp_spectra needs --cmp")
+    if not 0 <= a.cmp_min_count <= 1023:
+        parser.error("--cmp_min_count: 0 .. 1023")
     if a.trio is not None and (a.trio_pat is None or a.trio_mat is None):
         parser.error("--trio needs both --trio_pat and --trio_mat")
     if a.trio_bed is not None and a.trio is None:
@@ -504,6 +540,12 @@ def main(argv=None):
         report = _qv_report(a, a.sr_ks if a.sr else sorted(np2io.check_yak_header(y) for y in a.yak))
         base_future.append(yak_pool.submit(build_base))  # the tables are needed even when every contig passes through
 
+    creport, cmp_in, cmp_out = None, [], []
+    if a.cmp is not None:
+        creport = _cmp_report(a, a.sr_ks if a.sr else sorted(np2io.check_yak_header(y) for y in a.yak))
+        if not base_future:
+            base_future.append(yak_pool.submit(build_base))  # (as for --qv)
+
     treport, tpol, trio_pool = None, [], None
     if a.trio is not None:  # the parental tables go into HBM next to the polish, in a context of their own
         treport, trio_pool = _trio_report(a), ThreadPoolExecutor(max_workers=1)
@@ -535,6 +577,8 @@ def main(argv=None):
                         if not tpol:
                             tpol.append(trio_future.result())
                         treport.add(tpol[0], *pending_trio.pop(0), _record_sequence(rec))
+                    if creport is not None:
+                        cmp_out.append(_record_sequence(rec))
 
             try:
                 for name, seq in np2io.read_fasta(a.fa):
@@ -544,6 +588,8 @@ def main(argv=None):
                         pending_in.append((name, seq))
                     if treport is not None:
                         pending_trio.append((name, seq))
+                    if creport is not None:
+                        cmp_in.append(seq)
                     if len(seq) < a.min_ctg_len:  # pass-through (main.rs:1727-1730)
                         s = seq.upper() if a.uppercase else seq
                         if a.out_pos:
@@ -579,6 +625,14 @@ def main(argv=None):
                 report.write_cli(a.qv, a.qv_bed)
             if treport is not None:
                 treport.write_cli(a.trio, a.trio_bed)
+            if creport is not None:  # the whole assembly, on this thread's own context over the shared tables
+                b0 = base_future[0].result()
+                with base_lock:
+                    cpol = b0.clone()
+                try:
+                    _cmp_finish(a, creport, cpol, cmp_in, cmp_out)
+                finally:
+                    cpol.close()
             if prof:
                 print(f"[np2 profile] last record written at +{time.time() - t0:.3f} s", file=sys.stderr)
         if not base_future and not a.sr:

@@ -2,6 +2,7 @@
 #pragma once
 #include <cstdint>
 #include <hip/hip_runtime.h>
+#include <memory>
 #include <string>
 
 namespace np2 {
@@ -36,4 +37,16 @@ void launch_kcount_words(hipStream_t s, const uint64_t *keys, const uint32_t *co
 namespace np2h {
 // the I/O entry points' message slot (np2_io_last_error); returns `code`
 int io_set_error(int code, const std::string &msg);
+
+// One separator stream in host memory counted for one k into a table that STAYS in HBM (np2_cmp_host.cpp's second table):
+// all 1024 sub-tables in YakDev's layout, every word's count at least 1 and capped at 1023, `distinct` words.  Counted on
+// `stream` of `device` within the counter's default memory budget, in one pass: NP2_E_NOMEM otherwise.  The stream has
+// been drained when the call returns; the run's figures are np2_kcount_last_stats'.
+template <class T> struct DevBuf;
+struct ResidentCount {
+    std::shared_ptr<DevBuf<uint64_t>> table;
+    uint32_t cap_log2;
+    uint64_t distinct;
+};
+ResidentCount kcount_resident(int device, hipStream_t stream, const uint8_t *sep_stream, uint64_t n, uint32_t k);
 } // namespace np2h

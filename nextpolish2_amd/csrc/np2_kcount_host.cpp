@@ -559,6 +559,19 @@ struct DumpFile {
 
 } // namespace
 
+np2h::ResidentCount np2h::kcount_resident(int device, hipStream_t stream, const uint8_t *sep_stream, uint64_t n, uint32_t k) {
+    check_ks(&k, 1);
+    static const uint8_t none = '\n';
+    Source src;
+    src.mem = n ? sep_stream : &none, src.mem_n = n;
+    Counter c;
+    setup(c, device, &k, 1, nullptr, stream);
+    run_count(c, src, true, [](const RangeOut &) {}, [] {});
+    HIPCHK(hipStreamSynchronize(c.st));
+    g_stats = c.stats;
+    return ResidentCount{c.tabs[0].tab, c.tabs[0].cap_log2, c.tabs[0].claimed};
+}
+
 extern "C" {
 
 int np2_seqfile_stream(const char *path, uint8_t **out, uint64_t *n) {
