@@ -79,6 +79,46 @@ int np2_contig_from_records(np2_ctx_t *ctx, const uint8_t *ref, uint32_t L, cons
 /* same, reading the records of contig `name` from an indexed BAM (must be coordinate sorted) */
 int np2_contig_from_bam(np2_ctx_t *ctx, np2_bam_t *bam, const char *name, const uint8_t *ref, uint32_t L,
                         const np2_front_opts_t *opts, np2_contig_t **out);
+/* ---- mapping depth of a contig and its stretches of sufficient depth -----------------------------------------------------
+ * Depth counts ALIGNMENT RECORDS, not polish-admitted reads: np2_front_opts_t plays no part.  For one record with CIGAR
+ * operations (op, len): span = sum of len over M D N = X (a record whose sum is 0 covers 1 position, as htslib's end
+ * position does), aligned = sum over M I = X, read_len = sum over M I S H = X.  The record is counted iff
+ * (flag & exclude_flags) == 0, mapq >= min_mapq, n_cigar > 0, read_len > 0 and not
+ * (double)aligned / (double)read_len < min_aligned_fra (IEEE double).  depth[i], 0 <= i < L, is the number of counted
+ * records with pos <= i < min(pos + span, L); records with pos < 0 or pos >= L are ignored.  A run is a maximal [s, e]
+ * (0-based, inclusive) with depth >= min_depth throughout; it is kept iff e - s + 1 >= min_len.  min_depth = 0 gives the
+ * one run [0, L - 1] even without a record; L = 0 gives nothing.
+ * Outputs: starts[i], ends[i] of the *n_runs kept runs in ascending order (release both with np2_free; NULL when there is
+ * none), depth (or NULL): the caller's array of L words — the per-base array leaves the device only then.
+ * NP2_E_ARG before anything is launched, the context stays usable: min_aligned_fra outside [0, 1] or NaN, a NULL argument,
+ * a contig name the BAM header lacks.  L above 4294901760 is NP2_E_UNSUPPORTED. */
+typedef struct np2_depth_opts {
+    uint32_t min_depth;     /* -d 3 */
+    uint32_t min_len;       /* -l 1000 */
+    double min_aligned_fra; /* --min_fra 0.8 */
+    uint16_t exclude_flags; /* 0x4: unmapped */
+    uint8_t min_mapq;       /* 0 */
+} np2_depth_opts_t;
+typedef struct np2_depth_stats {
+    uint64_t records_seen;    /* records handed in or fetched */
+    uint64_t records_counted; /* those of them that entered the depth */
+    uint64_t sum_depth;  /* over all L positions */
+    uint64_t bases_kept; /* positions inside kept runs */
+    uint32_t max_depth;
+    uint32_t bases_ok;   /* positions with depth >= min_depth */
+    uint32_t runs;       /* before the length filter */
+    uint32_t runs_kept;  /* = *n_runs */
+    float kernel_ms;     /* the depth kernels together (HIP events) */
+} np2_depth_stats_t;
+/* recs / cigar as np2_contig_from_records takes them (host memory); seq_off and l_seq are not read */
+int np2_depth_from_records(np2_ctx_t *ctx, uint32_t L, const np2_bamrec_t *recs, uint32_t n_recs, const uint32_t *cigar,
+                           const np2_depth_opts_t *opts, uint32_t **starts, uint32_t **ends, uint32_t *n_runs,
+                           uint32_t *depth /* [L] or NULL */, np2_depth_stats_t *stats /* or NULL */);
+/* the same over the records of contig `name` of an indexed BAM, fetched the way np2_contig_from_bam fetches them (on the
+ * device path the records and CIGAR words are in HBM already; no SEQ byte moves on either path) */
+int np2_depth_from_bam(np2_ctx_t *ctx, np2_bam_t *bam, const char *name, uint32_t L, const np2_depth_opts_t *opts,
+                       uint32_t **starts, uint32_t **ends, uint32_t *n_runs, uint32_t *depth /* [L] or NULL */,
+                       np2_depth_stats_t *stats /* or NULL */);
 /* ---- one reference interval of a contig straight from the BAM (multi-GPU: every rank parses only its part) -----------
  * begin: fetch the records overlapping [own_lo - halo, own_hi + halo) through the .bai linear index, admit + columnarise
  *        them; returns the BGZF virtual offsets of the pushed records that START in [own_lo, own_hi) (file order).

@@ -38,6 +38,7 @@ IO_ABI_SYMBOLS = [
     "np2_bgzf_inflate_device", "np2_crc32_device",
     "np2_kcount_files", "np2_kcount_bytes", "np2_kcount_files_to_dumps", "np2_ctx_create_from_reads", "np2_kcount_last_stats",
     "np2_seqfile_stream", "np2_bin_files", "np2_seqfile_reads",
+    "np2_depth_from_records", "np2_depth_from_bam",
 ]
 
 ERRORS = {-1: "NP2_E_ARG", -2: "NP2_E_DEVICE", -3: "NP2_E_NOMEM", -4: "NP2_E_UNSUPPORTED", -5: "NP2_E_REFPANIC"}
@@ -46,6 +47,19 @@ ERRORS = {-1: "NP2_E_ARG", -2: "NP2_E_DEVICE", -3: "NP2_E_NOMEM", -4: "NP2_E_UNS
 class np2_bin_opts_t(C.Structure):
     _fields_ = [("min_count", C.c_uint16), ("mid_count", C.c_uint16), ("min_score", C.c_uint32), ("minor_permille", C.c_uint32)]
 
+
+class np2_depth_opts_t(C.Structure):
+    _fields_ = [("min_depth", C.c_uint32), ("min_len", C.c_uint32), ("min_aligned_fra", C.c_double), ("exclude_flags", C.c_uint16),
+                ("min_mapq", C.c_uint8)]
+
+
+class np2_depth_stats_t(C.Structure):
+    _fields_ = [("records_seen", C.c_uint64), ("records_counted", C.c_uint64), ("sum_depth", C.c_uint64), ("bases_kept", C.c_uint64),
+                ("max_depth", C.c_uint32), ("bases_ok", C.c_uint32), ("runs", C.c_uint32), ("runs_kept", C.c_uint32),
+                ("kernel_ms", C.c_float)]
+
+
+assert C.sizeof(np2_depth_opts_t) == 24 and C.sizeof(np2_depth_stats_t) == 56
 
 BIN_DTYPE = np.dtype([("n_kmers", "<u4"), ("n_pat", "<u4"), ("n_mat", "<u4"), ("pairs", "<u4", (4,))])  # np2_bin_t
 assert BIN_DTYPE.itemsize == 28
@@ -98,6 +112,10 @@ def _lib_locked():
         L.np2_trio_device.argtypes = [vp, C.c_int, C.c_int, vp, u64, u16, u16, vp, vp, vp, C.POINTER(C.c_float)]
         L.np2_bin_stream.argtypes = [vp, C.c_int, C.c_int, vp, u64, u64, C.POINTER(np2_bin_opts_t), vp, vp, C.POINTER(C.c_float)]
         L.np2_cmp_strings.argtypes = [vp, C.c_int, vp, vp, u64, u16, vp, vp, vp, C.POINTER(C.c_float)]
+        L.np2_depth_from_records.argtypes = [vp, u32, vp, u32, vp, C.POINTER(np2_depth_opts_t), C.POINTER(vp), C.POINTER(vp),
+                                             C.POINTER(u32), vp, C.POINTER(np2_depth_stats_t)]
+        L.np2_depth_from_bam.argtypes = [vp, vp, C.c_char_p, u32, C.POINTER(np2_depth_opts_t), C.POINTER(vp), C.POINTER(vp),
+                                         C.POINTER(u32), vp, C.POINTER(np2_depth_stats_t)]
         L.np2_ctx_set_trace.argtypes = [vp, C.c_int]
         L.np2_ctx_set_timing.argtypes = [vp, C.c_int]
         L.np2_ctx_set_timing.restype = None
@@ -179,6 +197,41 @@ def _owned(ptr, n, ctype):
     base = np.asarray(_Raw(ptr.value, max(n, 1), _TYPESTR[ctype]))
     weakref.finalize(base, lib().np2_free, C.c_void_p(ptr.value))
     return base[:n]
+
+
+def depth_call(pol, L_, call, min_depth=3, min_len=1000, min_aligned_fra=0.8, exclude_flags=0x4, min_mapq=0, want_depth=False):
+    """One np2_depth_* call: `call(opts, starts, ends, n_runs, depth, stats)` is the entry point with its leading arguments
+    bound -> (kept runs as an (n, 2) uint32 array of inclusive (s, e), stats dict, per-base uint32 depth or None)."""
+    o = np2_depth_opts_t(min_depth, min_len, min_aligned_fra, exclude_flags, min_mapq)
+    ps, pe, n, st = C.c_void_p(), C.c_void_p(), C.c_uint32(), np2_depth_stats_t()
+    depth = np.zeros(max(int(L_), 1), dtype=np.uint32) if want_depth else None
+    try:
+        pol._check(call(C.byref(o), C.byref(ps), C.byref(pe), C.byref(n), depth.ctypes.data if want_depth else None, C.byref(st)))
+        runs = np.zeros((n.value, 2), dtype=np.uint32)
+        if n.value:
+            runs[:, 0] = np.asarray(_Raw(ps.value, n.value, "<u4"))
+            runs[:, 1] = np.asarray(_Raw(pe.value, n.value, "<u4"))
+    finally:
+        if ps.value:
+            lib().np2_free(ps)
+        if pe.value:
+            lib().np2_free(pe)
+    stats = {f: getattr(st, f) for f, _ in np2_depth_stats_t._fields_}
+    return runs, stats, (depth[:int(L_)] if want_depth else None)
+
+
+def depth_from_records(pol, L_, recs, cigar, **kw):
+    """np2_depth_from_records: mapping depth of a contig of `L_` positions from alignment records (`recs`: np2_bamrec_t as
+    io.BAMREC_DTYPE, `cigar`: the BAM CIGAR words their cigar_off index) and its runs of depth >= min_depth that are at
+    least min_len long.  Keywords: min_depth=3, min_len=1000, min_aligned_fra=0.8, exclude_flags=0x4, min_mapq=0,
+    want_depth=False.  See depth_call for what comes back."""
+    recs = np.ascontiguousarray(recs)
+    if recs.ndim != 1 or (len(recs) and recs.dtype.itemsize != 40):
+        raise ValueError("recs must be a one-dimensional array of np2_bamrec_t (io.BAMREC_DTYPE)")
+    cigar = np.ascontiguousarray(cigar, dtype=np.uint32)
+    L = lib()
+    return depth_call(pol, L_, lambda *a: L.np2_depth_from_records(pol._h, int(L_), recs.ctypes.data if len(recs) else None, len(recs),
+                                                                   cigar.ctypes.data if len(cigar) else None, *a), **kw)
 
 
 class QvStats:

@@ -24,6 +24,7 @@
 #include <unordered_map>
 #include <unordered_set>
 
+#include "np2_depth.hpp"
 #include "np2_inflate.hpp"
 #include "np2_inflate_core.hpp"
 #include "np2_kcount.hpp"
@@ -1162,7 +1163,8 @@ void contig_from_records(np2_ctx *cx, const uint8_t *ref, uint32_t L, const np2_
 // (SeqStream), *seq_bytes is their total, bam->seq4 stays empty.
 void fetch_records(np2_bam *bam, int tid, uint32_t L, uint32_t zone_lo, uint32_t zone_hi, const np2_front_opts_t *opts,
                    std::vector<np2_bamrec_t> &recs, std::vector<uint32_t> &cigar, std::vector<uint64_t> *voffs,
-                   hipStream_t up_stream = nullptr, uint64_t *seq_bytes = nullptr) {
+                   hipStream_t up_stream = nullptr, uint64_t *seq_bytes = nullptr, bool no_seq = false) {
+        // (no_seq: the caller reads positions, flags and CIGARs only — the depth report —: no SEQ byte is copied)
         PinnedBytes &seq4 = bam->seq4;
         seq4.clear();
         const bool streamed = up_stream != nullptr && !opts->use_secondary;
@@ -1251,7 +1253,7 @@ void fetch_records(np2_bam *bam, int tid, uint32_t L, uint32_t zone_lo, uint32_t
                         r.seq_off = so;
                         co += r.n_cigar;
                         const uint32_t flag = rec[14] | (rec[15] << 8);
-                        if (!(opts->use_secondary && (flag & 0x100))) so += ((uint64_t)r.l_seq + 1) / 2;
+                        if (!no_seq && !(opts->use_secondary && (flag & 0x100))) so += ((uint64_t)r.l_seq + 1) / 2;
                         rr.push_back(r);
                     }
                     p += 4 + (size_t)bs;
@@ -1289,7 +1291,7 @@ void fetch_records(np2_bam *bam, int tid, uint32_t L, uint32_t zone_lo, uint32_t
                         r.l_seq = q.l_seq;
                         r.seq_off = q.seq_off;
                         for (uint32_t k = 0; k < q.n_cigar; ++k) cigar[q.cigar_off + k] = le32(pc + 4 * k);
-                        memcpy(seq_dst + (q.seq_off - so0), pc + (size_t)q.n_cigar * 4, ((size_t)q.l_seq + 1) / 2);
+                        if (!no_seq) memcpy(seq_dst + (q.seq_off - so0), pc + (size_t)q.n_cigar * 4, ((size_t)q.l_seq + 1) / 2);
                         recs[r0 + i] = r;
                     });
                     if (streamed) {
@@ -2445,6 +2447,50 @@ int np2_contig_from_bam(np2_ctx_t *cx, np2_bam_t *bam, const char *name, const u
         np2h::flush_timings(cx);
         return NP2_OK;
     }, np2h::ctx_sink(cx, true));
+}
+
+// Mapping depth of contig `name` and its runs of sufficient depth (np2_depth.hip).  The records come from the fetcher
+// np2_contig_from_bam would take: on the device path they and their CIGAR words are in HBM already (GpuFetch::d_recs,
+// d_cigar) and the kernels read them there; on the host path positions, flags and CIGAR words are uploaded, SEQ is not read.
+int np2_depth_from_bam(np2_ctx_t *cx, np2_bam_t *bam, const char *name, uint32_t L, const np2_depth_opts_t *opts, uint32_t **starts,
+                       uint32_t **ends, uint32_t *n_runs, uint32_t *depth, np2_depth_stats_t *stats) {
+    if (!cx) return NP2_E_ARG;
+    if (starts) *starts = nullptr;
+    if (ends) *ends = nullptr;
+    if (n_runs) *n_runs = 0;
+    return np2h::abi_guard([&] {
+        // every argument is checked before anything is launched
+        const np2::DepthRule rule = np2h::depth_rule(opts);
+        if (!bam || !name || !starts || !ends || !n_runs) throw np2h::Np2Error(NP2_E_ARG, "np2_depth_from_bam: bam, name, starts, ends or n_runs is NULL");
+        const int tid = ref_id(bam, name);
+        HIPCHK(hipSetDevice(cx->device));
+        if (gpu_fetch_wanted(bam, tid)) {
+            GpuRecs gr;
+            if (fetch_records_gpu(bam, tid, L, 0, L, cx->stream, gr)) { // (false: not this BAM / index, or no room on the device)
+                np2h::depth_device(cx, L, gr.n_recs ? bam->gpu->d_recs.p : nullptr, gr.n_recs, gr.n_recs ? bam->gpu->d_cigar.p : nullptr, rule,
+                                   starts, ends, n_runs, depth, stats);
+                return NP2_OK;
+            }
+        }
+        std::vector<np2_bamrec_t> recs;
+        std::vector<uint32_t> cigar;
+        np2_front_opts_t fo;
+        memset(&fo, 0, sizeof fo); // (read admission plays no part; -S off: no pass over the file for SEQ nobody reads)
+        fetch_records(bam, tid, L, 0, L, &fo, recs, cigar, nullptr, nullptr, nullptr, true);
+        np2h::DevBuf<np2_bamrec_t> d_recs;
+        np2h::DevBuf<uint32_t> d_cigar;
+        d_recs.cached = d_cigar.cached = true; // (released after depth_device has drained the stream)
+        if (!recs.empty()) {
+            d_recs.ensure(recs.size());
+            HIPCHK(hipMemcpyAsync(d_recs.p, recs.data(), recs.size() * sizeof(np2_bamrec_t), hipMemcpyHostToDevice, cx->stream));
+        }
+        if (!cigar.empty()) {
+            d_cigar.ensure(cigar.size());
+            HIPCHK(hipMemcpyAsync(d_cigar.p, cigar.data(), cigar.size() * 4, hipMemcpyHostToDevice, cx->stream));
+        }
+        np2h::depth_device(cx, L, d_recs.p, (uint32_t)recs.size(), d_cigar.p, rule, starts, ends, n_runs, depth, stats);
+        return NP2_OK;
+    }, np2h::ctx_sink(cx));
 }
 
 // ---- a reference-interval shard straight from the BAM -----------------------------------------------------------------

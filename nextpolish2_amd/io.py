@@ -15,7 +15,7 @@ IO_SYMBOLS = ["np2_fasta_open", "np2_fasta_next", "np2_fasta_close", "np2_yak_lo
               "np2_bam_close", "np2_bam_n_refs", "np2_bam_ref_name", "np2_io_last_error", "np2_contig_from_records",
               "np2_contig_from_bam", "np2_contig_export", "np2_ctx_create_from_files", "np2_bgzf_inflate_device", "np2_crc32_device",
               "np2_kcount_files", "np2_kcount_bytes", "np2_kcount_files_to_dumps", "np2_ctx_create_from_reads", "np2_kcount_last_stats",
-              "np2_seqfile_stream", "np2_bin_files", "np2_seqfile_reads"]
+              "np2_seqfile_stream", "np2_bin_files", "np2_seqfile_reads", "np2_depth_from_records", "np2_depth_from_bam"]
 
 
 class np2_front_opts_t(C.Structure):
@@ -373,6 +373,15 @@ def contig_from_records(pol, ref, recs, cigar, seq4, opts=None, name="ctg"):
     pol._check(L.np2_contig_from_records(pol._h, ref.ctypes.data, ref.shape[0], recs.ctypes.data, recs.shape[0],
                                          cigar.ctypes.data, seq4.ctypes.data, C.byref(o), C.byref(h)))
     return _resident(pol, h, name, int(ref.shape[0]))
+
+
+def depth_from_bam(pol, bam, name, L_, **kw):
+    """np2_depth_from_bam: mapping depth of contig `name` (`L_` positions) of the indexed BAM `bam` on the device of Polisher
+    `pol`, and its runs of depth >= min_depth that are at least min_len long -> (runs as an (n, 2) uint32 array of inclusive
+    (s, e), stats dict, per-base depth or None).  Keywords as api.depth_from_records."""
+    from .api import depth_call
+    L = _bind()
+    return depth_call(pol, L_, lambda *a: L.np2_depth_from_bam(pol._h, bam._h, name.encode(), int(L_), *a), **kw)
 
 
 def shard_cuts(L_, n_shards):
