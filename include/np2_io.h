@@ -187,6 +187,70 @@ int np2_kcount_last_stats(uint64_t *kmers, uint64_t *distinct, uint64_t *spilled
  * release with np2_free */
 int np2_seqfile_stream(const char *path, uint8_t **out, uint64_t *n);
 
+/* ---- short-read quality trimming and filtering in front of the k-mer counter ---------------------------------------------
+ * The preparation step the reference's README calls essential (its recipe: fastp -5 -3 -n 0 -f 5 -F 5 -t 5 -T 5 -q 20),
+ * on the device.  THE RULE IS DEFINED HERE, on the options of that recipe; it is not pinned against the fastp binary.
+ * One read has n bases s[0..n) and n quality bytes, p[i] = max(0, byte - 33).
+ *   1. a = min(trim_front, n), b = max(a, n - trim_tail) (saturating at 0): the kept span is [a, b).
+ *   2. cut_front, if on and b > a: the smallest i with a <= i, i + W <= b and p[i] + .. + p[i+W-1] >= M * W.  No such i
+ *      (b - a < W included): a = b.  Otherwise a = i, then a += 1 while a < b and s[a] is N or n.
+ *   3. cut_tail, if on and b > a: the largest j with j <= b, j - W >= a and p[j-W] + .. + p[j-1] >= M * W.  No such j:
+ *      b = a.  Otherwise b = j, then b -= 1 while b > a and s[b-1] is N or n.
+ *   4. len = b - a, nN = N / n in [a, b), lowq = positions of [a, b) with p < Q.  Class, in this order: 1 too short
+ *      (len < min_len or len == 0), 2 too many N (nN > n_base_limit), 3 low quality (100 * lowq > U * len), else 0 pass.
+ *   5. The masked stream: every base of a failed read, and every base of a passing read outside [a, b), becomes 'N';
+ *      separators stay.  Counting it gives the tables of the kept substrings counted as reads of their own.
+ * Reads are judged one by one (paired files are not kept in step); no adapter, poly-G / poly-X, complexity or
+ * average-quality filter.  Options out of range are NP2_E_ARG before the first device call.  Inputs are FASTQ, plain or
+ * gzip: FASTA or one sequence per line is NP2_E_ARG naming the file, a record whose quality line is not as long as its
+ * sequence NP2_E_ARG naming the file and the 1-based record.  The streams are filtered in pieces that end at a read
+ * boundary (8 MiB; NP2_KCOUNT_TEST_PIECE): a read that does not fit an empty piece is NP2_E_UNSUPPORTED. */
+#define NP2_SRQC_CUT_FRONT 1u
+#define NP2_SRQC_CUT_TAIL 2u
+typedef struct np2_srqc_opts {
+    uint32_t trim_front;          /* -f / -F 5 */
+    uint32_t trim_tail;           /* -t / -T 5 */
+    uint32_t cut_window;          /* W: 4, 1 .. 1000 */
+    uint32_t cut_mean_q;          /* M: 20, 0 .. 93 */
+    uint32_t n_base_limit;        /* -n 0 */
+    uint32_t qualified_q;         /* Q: -q 20, 0 .. 93 */
+    uint32_t unqualified_percent; /* U: 40, 0 .. 100 */
+    uint32_t min_len;             /* 15 */
+    uint32_t flags;               /* NP2_SRQC_CUT_FRONT (-5) | NP2_SRQC_CUT_TAIL (-3) */
+} np2_srqc_opts_t;
+typedef struct np2_srqc_read {
+    uint32_t begin, end; /* a and b of the rule as step 4 sees them, from the read's first base */
+    uint32_t cls;        /* 0 pass, 1 too short, 2 too many N, 3 low quality */
+} np2_srqc_read_t;
+typedef struct np2_srqc_stats {
+    uint64_t reads, pass, too_short, too_many_n, low_quality, bases_in, bases_out;
+} np2_srqc_stats_t;
+/* One pair of streams in host memory (the reads' bases / quality bytes, every read followed by one '\n' in both; n bytes
+ * each), walked piece by piece.  masked_out (or NULL): n bytes, the masked stream.  reads_out (or NULL): one entry per
+ * read.  n_reads must be the number of separators (NP2_E_ARG otherwise); the last byte of a stream that is not empty must
+ * be one.  stats may be NULL.  Errors: np2_io_last_error(). */
+int np2_srqc_bytes(int device, const uint8_t *seq, const uint8_t *qual, uint64_t n, const np2_srqc_opts_t *opts,
+                   uint8_t *masked_out, np2_srqc_read_t *reads_out, uint64_t n_reads, np2_srqc_stats_t *stats);
+/* FASTQ files -> totals (stats: [n_paths + 1], per file and then the sum; or NULL) and, with out_paths (or NULL; single
+ * entries may be NULL), one cleaned plain-text FASTQ per input: the passing reads in file order, each the header line as
+ * read, the kept bases, "+", the kept qualities. */
+int np2_srqc_files(int device, const char *const *paths, int n_paths, const np2_srqc_opts_t *opts,
+                   const char *const *out_paths, np2_srqc_stats_t *stats);
+/* the totals of the last filtering call on this thread (of a multi-pass count: of one pass, not the sum over passes) */
+int np2_srqc_last_stats(np2_srqc_stats_t *stats);
+/* ms in the filter kernel during that call (HIP events) */
+int np2_srqc_last_kernel_ms(float *ms);
+/* The three counting entry points with the filter in front of the counter: qc == NULL is exactly the call without it.
+ * Every input must then be FASTQ. */
+int np2_kcount_files_qc(int device, const char *const *paths, int n_paths, const uint32_t *ks, int n_k,
+                        const np2_kcount_opts_t *opts, const np2_srqc_opts_t *qc, np2_yak_t *out /* [n_k] */);
+int np2_kcount_files_to_dumps_qc(int device, const char *const *paths, int n_paths, const uint32_t *ks, int n_k,
+                                 const np2_kcount_opts_t *opts, const np2_srqc_opts_t *qc, const char *const *out_paths);
+int np2_ctx_create_from_reads_qc(np2_ctx_t **out, int device, const char *const *paths, int n_paths, const uint32_t *ks,
+                                 int n_k, const np2_kcount_opts_t *opts, const np2_srqc_opts_t *qc);
+/* host only, no device: the two streams the reader makes of one FASTQ file (n bytes each; release both with np2_free) */
+int np2_seqfile_stream_qual(const char *path, uint8_t **seq, uint8_t **qual, uint64_t *n);
+
 /* Read files -> classes (np2_bin_stream's device path, fed by the counter's reader threads through pinned pieces, in
  * file order; errors: np2_last_error(ctx)).  A read's name is its header up to the first whitespace, without '>' / '@';
  * a record without one (one sequence per line) is named by its 1-based number in its file.  Every path of `out` may be

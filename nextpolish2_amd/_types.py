@@ -62,6 +62,24 @@ class np2_shard_piece_t(C.Structure):
                 ("hi_bases", C.c_void_p), ("lo_pos", C.c_void_p), ("hi_pos", C.c_void_p)]
 
 
+class np2_srqc_opts_t(C.Structure):
+    _fields_ = [("trim_front", C.c_uint32), ("trim_tail", C.c_uint32), ("cut_window", C.c_uint32), ("cut_mean_q", C.c_uint32),
+                ("n_base_limit", C.c_uint32), ("qualified_q", C.c_uint32), ("unqualified_percent", C.c_uint32), ("min_len", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+
+class np2_srqc_read_t(C.Structure):
+    _fields_ = [("begin", C.c_uint32), ("end", C.c_uint32), ("cls", C.c_uint32)]
+
+
+class np2_srqc_stats_t(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("reads", "pass_", "too_short", "too_many_n", "low_quality", "bases_in", "bases_out")]
+
+
+SRQC_READ_DTYPE = np.dtype([("begin", "<u4"), ("end", "<u4"), ("cls", "<u4")])
+SRQC_STATS = ("reads", "pass", "too_short", "too_many_n", "low_quality", "bases_in", "bases_out")
+
+
 class Opts:
     """Defaults of the reference CLI (src/utils/option.rs:267-292)."""
 

@@ -53,6 +53,8 @@ def build_parser():
     p.add_argument("--sr_k", default="21,31", metavar="K[,K...]", help="k-mer sizes counted from --sr [21,31]")
     p.add_argument("--sr_min_count", type=int, default=None, metavar="N",
                    help="drop k-mers of --sr counted fewer than N times [2, or -k/--min_kmer_count where that is smaller]")
+    p.add_argument("--sr_qc", nargs="?", const=np2io.SrQc(), default=None, type=np2io.sr_qc_arg, metavar="SPEC",
+                   help="with --sr: " + np2io.SR_QC_HELP)
     p.add_argument("-o", "--out", default=None, metavar="FILE", help="output file [stdout]")
     p.add_argument("--qv", default=None, metavar="FILE",
                    help="k-mer QV of every contig as read and as written, per k-mer table, as a TSV (a k-mer the tables do not "
@@ -98,6 +100,12 @@ def build_parser():
     p.add_argument("--dist_backend", default=None, help="torch.distributed backend under torchrun [nccl]")
     p.add_argument("-V", "--version", action="version", version=VERSION)
     return p
+
+
+def _report_sr_qc(a):
+    """the filter's totals as one [INFO] line (on the thread that counted: the totals are that thread's)"""
+    if a.sr_qc is not None:
+        print(f"[INFO] sr_qc: {np2io.srqc_stats_text(np2io.srqc_last_stats())}", file=sys.stderr)
 
 
 def _cpu_seconds():
@@ -308,6 +316,8 @@ def main(argv=None):
         parser.error("the following arguments are required: short.read.yak")
     if a.sr and a.yak:
         parser.error("give either short.read.yak files or --sr reads, not both")
+    if a.sr_qc is not None and not a.sr:
+        parser.error("--sr_qc filters the reads of --sr: give --sr")
     if a.sr:
         try:
             a.sr_ks = sorted(int(k) for k in a.sr_k.split(","))
@@ -381,7 +391,9 @@ def main(argv=None):
     def load_yaks():
         t_y = time.time()
         if a.sr:  # (under torch.distributed.run every rank counts for itself: the tables are replicated per GPU anyway)
-            return np2io.count_kmers(a.sr, a.sr_ks, min_count=a.sr_min_count, device=a.device)
+            ys = np2io.count_kmers(a.sr, a.sr_ks, min_count=a.sr_min_count, device=a.device, qc=a.sr_qc)
+            _report_sr_qc(a)
+            return ys
         with ThreadPoolExecutor(max_workers=max(1, len(a.yak))) as ex:  # (the loader runs outside the GIL: one thread per dump)
             ys = sorted(ex.map(np2io.load_yak, a.yak), key=lambda y: y.k)  # option.rs:238
         if prof:
@@ -421,7 +433,8 @@ def main(argv=None):
         if prof:
             print(f"[np2 profile] k-mer dumps: start at +{t_b - t0:.3f} s", file=sys.stderr)
         if a.sr:  # reads -> HBM tables that never visit the host (np2_ctx_create_from_reads)
-            pol = np2io.polisher_from_reads(a.sr, a.sr_ks, min_count=a.sr_min_count, device=a.device)
+            pol = np2io.polisher_from_reads(a.sr, a.sr_ks, min_count=a.sr_min_count, device=a.device, qc=a.sr_qc)
+            _report_sr_qc(a)
         else:
             pol = np2io.polisher_from_yak_files(a.yak, device=a.device)
         if prof:

@@ -15,11 +15,17 @@
 // Memory: mem_bytes bounds the tables of all k together, a growth's old and new table included (0: half of the device
 // memory that is free when the call starts).  A growth that would exceed it restarts the run with twice as many passes
 // over bucket ranges (inputs reopened / rescanned; every range is emitted before the next begins).
+//
+// Quality filter (the *_qc entry points with options): the reader threads fill pieces of BOTH streams that end at a read
+// boundary (np2_srqc_host.hpp), and count_piece runs the filter kernel on the uploaded bases before the count kernels read
+// them: failed reads and trimmed ends are 'N' by then, which ends a k-mer run as a separator does.  Without options
+// nothing of this runs.
 #include "../../include/np2_io.h"
 #include "np2_ctx.hpp"
 #include "np2_kcount.hpp"
 #include "np2_kcount_core.hpp"
 #include "np2_seqreader.hpp"
+#include "np2_srqc_host.hpp"
 
 #include <sys/stat.h>
 #include <zlib.h>
@@ -40,6 +46,7 @@ using np2seq::parse_file;
 struct Piece {
     uint8_t *buf = nullptr; // pinned: HALO bytes, then up to `cap` bytes, then room for the padding
     size_t n = 0;
+    np2h::QcPiece qc; // with the quality filter: qc.seq == buf, the quality bytes and the separators beside it
 };
 struct PieceQueue {
     std::mutex mu;
@@ -190,6 +197,9 @@ struct Counter {
     np2h::PinnedBuf pin_ctr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     Stats stats;
+    bool qc = false; // the quality filter runs in front of the count kernel
+    np2h::SrqcDev qcd;
+    uint64_t qc_totals[np2srqc::N_TOTALS] = {0, 0, 0, 0, 0, 0, 0};
 
     ~Counter() {
         if (ev0) (void)hipEventDestroy(ev0);
@@ -218,6 +228,7 @@ struct Counter {
         d_spill[0].ensure(hooks.piece);
         d_ctr.ensure((size_t)np2::KC_N_CTR * tabs.size());
         pin_ctr.ensure(np2::KC_N_CTR * 8);
+        if (qc) qcd.init(st, hooks.piece);
     }
     np2::KcTable kt(const KTable &t) const { return np2::KcTable{t.tab->p, t.cap_log2, lo, hi}; }
     uint64_t *ctr(size_t ki) { return d_ctr.p + ki * np2::KC_N_CTR; }
@@ -243,6 +254,7 @@ struct Counter {
             HIPCHK(hipMemsetAsync(t.tab->p, 0xFF, slots * 8, st));
         }
         HIPCHK(hipMemsetAsync(d_ctr.p, 0, np2::KC_N_CTR * 8 * tabs.size(), st));
+        if (qc) qcd.zero(st); // (every pass filters again: the totals are one pass's)
     }
     // the table of tabs[ki] with twice the capacity (or more, should a sub-table of the new one fill)
     void grow(size_t ki) {
@@ -263,10 +275,11 @@ struct Counter {
             return;
         }
     }
-    void count_piece(const Piece &pc) {
+    void count_piece(Piece &pc) {
         const size_t n = pc.n, padded = (HALO + n + 15) & ~(size_t)15;
         memset(pc.buf + HALO + n, '\n', padded - (HALO + n));
         HIPCHK(hipMemcpyAsync(d_in.p, pc.buf, padded, hipMemcpyHostToDevice, st));
+        if (qc) qcd.run(st, d_in.p, pc.qc, nullptr);
         for (size_t ki = 0; ki < tabs.size(); ++ki) {
             KTable &t = tabs[ki];
             while (t.claimed + n > ((uint64_t)(hi - lo) << t.cap_log2) / 2) grow(ki);
@@ -304,13 +317,20 @@ struct Counter {
         struct Release {
             std::vector<Piece> &v;
             ~Release() {
-                for (auto &p : v)
+                for (auto &p : v) {
                     if (p.buf) np2h::pinned_pool().put(p.buf);
+                    if (p.qc.qual) np2h::pinned_pool().put(p.qc.qual);
+                }
             }
         } release{pieces};
         for (auto &p : pieces) {
             p.buf = (uint8_t *)np2h::pinned_pool().get(HALO + hooks.piece + 64);
             if (!p.buf) throw Np2Error(NP2_E_NOMEM, "hipHostMalloc failed");
+            if (qc) {
+                p.qc.seq = p.buf, p.qc.owner = &p;
+                p.qc.qual = (uint8_t *)np2h::pinned_pool().get(HALO + hooks.piece + 64);
+                if (!p.qc.qual) throw Np2Error(NP2_E_NOMEM, "hipHostMalloc failed");
+            }
             q.idle.push_back(&p);
         }
         q.producers = (int)n_threads;
@@ -328,18 +348,34 @@ struct Counter {
                 int code = NP2_OK;
                 std::string msg;
                 try {
-                    PieceWriter w(q, hooks.piece);
-                    auto put = [&](const uint8_t *p, size_t n) { w.put(p, n); };
-                    if (src.mem) {
-                        put(src.mem, src.mem_n);
-                        static const uint8_t NL = '\n';
-                        put(&NL, 1);
+                    if (qc) { // both streams, in pieces that end at a read boundary
+                        np2h::QcAssembler as(hooks.piece, false);
+                        as.take = [&]() -> np2h::QcPiece * {
+                            Piece *p = q.take_idle();
+                            return p ? &p->qc : nullptr;
+                        };
+                        as.full = [&](np2h::QcPiece *c) {
+                            Piece *p = (Piece *)c->owner;
+                            p->n = c->n;
+                            q.give_full(p);
+                        };
+                        as.unused = [&](np2h::QcPiece *c) { q.give_idle((Piece *)c->owner); };
+                        for (size_t fi = ti; fi < src.paths.size() && !as.dead; fi += n_threads) as.file(src.paths[fi]);
+                        as.flush();
                     } else {
-                        for (size_t fi = ti; fi < src.paths.size() && !w.dead; fi += n_threads) {
-                            parse_file(src.paths[fi], put, [&] { return w.dead; }); // (its stream ends with a separator)
+                        PieceWriter w(q, hooks.piece);
+                        auto put = [&](const uint8_t *p, size_t n) { w.put(p, n); };
+                        if (src.mem) {
+                            put(src.mem, src.mem_n);
+                            static const uint8_t NL = '\n';
+                            put(&NL, 1);
+                        } else {
+                            for (size_t fi = ti; fi < src.paths.size() && !w.dead; fi += n_threads) {
+                                parse_file(src.paths[fi], put, [&] { return w.dead; }); // (its stream ends with a separator)
+                            }
                         }
+                        w.flush();
                     }
-                    w.flush();
                 } catch (const Np2Error &e) {
                     code = e.code, msg = e.what();
                 } catch (const std::exception &e) {
@@ -356,6 +392,7 @@ struct Counter {
             q.give_idle(p);
         }
         if (q.err_code != NP2_OK) throw Np2Error(q.err_code, q.err);
+        if (qc) qcd.totals(st, qc_totals);
     }
 
     // the current range of tabs[ki] as sorted file words on the device
@@ -460,8 +497,11 @@ uint32_t min_count_of(const np2_kcount_opts_t *o) {
     return std::max(1u, m);
 }
 
-void setup(Counter &c, int device, const uint32_t *ks, int n_k, const np2_kcount_opts_t *opts, hipStream_t st) {
+void setup(Counter &c, int device, const uint32_t *ks, int n_k, const np2_kcount_opts_t *opts, hipStream_t st,
+           const np2srqc::Opts *qc = nullptr) {
     c.device = device;
+    c.qc = qc != nullptr;
+    if (qc) c.qcd.o = *qc;
     c.min_count = min_count_of(opts);
     c.tabs.resize(n_k);
     for (int i = 0; i < n_k; ++i) c.tabs[i].k = ks[i];
@@ -492,9 +532,21 @@ struct HostYak {
     }
 };
 
-int count_to_host(int device, const Source &src, const uint32_t *ks, int n_k, const np2_kcount_opts_t *opts, np2_yak_t *out) {
+// the options of a *_qc call, checked; nullptr without them
+const np2srqc::Opts *qc_of(const np2_srqc_opts_t *qc, np2srqc::Opts &store) {
+    if (!qc) return nullptr;
+    store = np2h::srqc_checked(qc);
+    (void)np2h::srqc_piece_bytes();
+    return &store;
+}
+void publish_qc(const Counter &c) {
+    if (c.qc) np2h::srqc_publish(c.qc_totals, c.qcd.kernel_ms);
+}
+
+int count_to_host(int device, const Source &src, const uint32_t *ks, int n_k, const np2_kcount_opts_t *opts, np2_yak_t *out,
+                  const np2srqc::Opts *qc = nullptr) {
     Counter c;
-    setup(c, device, ks, n_k, opts, nullptr);
+    setup(c, device, ks, n_k, opts, nullptr, qc);
     std::vector<HostYak> hy(n_k);
     run_count(c, src, false, [&](const RangeOut &r) { hy[r.ki].take(r, c.st); }, [&] { for (auto &h : hy) h.reset(); });
     std::vector<uint64_t *> offs;
@@ -514,6 +566,7 @@ int count_to_host(int device, const Source &src, const uint32_t *ks, int n_k, co
         hy[i].words = nullptr;
     }
     g_stats = c.stats;
+    publish_qc(c);
     return NP2_OK;
 }
 
@@ -590,13 +643,20 @@ int np2_seqfile_stream(const char *path, uint8_t **out, uint64_t *n) {
 
 int np2_kcount_files(int device, const char *const *paths, int n_paths, const uint32_t *ks, int n_k,
                      const np2_kcount_opts_t *opts, np2_yak_t *out) {
+    return np2_kcount_files_qc(device, paths, n_paths, ks, n_k, opts, nullptr, out);
+}
+
+int np2_kcount_files_qc(int device, const char *const *paths, int n_paths, const uint32_t *ks, int n_k,
+                        const np2_kcount_opts_t *opts, const np2_srqc_opts_t *qc, np2_yak_t *out) {
     return np2h::abi_guard([&] {
         if (!out) throw Np2Error(NP2_E_ARG, "np2_kcount_files: out is NULL");
         check_ks(ks, n_k);
         (void)min_count_of(opts);
+        np2srqc::Opts qo;
+        const np2srqc::Opts *q = qc_of(qc, qo);
         Source src;
         check_paths(paths, n_paths, src);
-        return count_to_host(device, src, ks, n_k, opts, out);
+        return count_to_host(device, src, ks, n_k, opts, out, q);
     }, np2h::io_set_error);
 }
 
@@ -615,16 +675,23 @@ int np2_kcount_bytes(int device, const uint8_t *seq, uint64_t n, const uint32_t 
 
 int np2_kcount_files_to_dumps(int device, const char *const *paths, int n_paths, const uint32_t *ks, int n_k,
                               const np2_kcount_opts_t *opts, const char *const *out_paths) {
+    return np2_kcount_files_to_dumps_qc(device, paths, n_paths, ks, n_k, opts, nullptr, out_paths);
+}
+
+int np2_kcount_files_to_dumps_qc(int device, const char *const *paths, int n_paths, const uint32_t *ks, int n_k,
+                                 const np2_kcount_opts_t *opts, const np2_srqc_opts_t *qc, const char *const *out_paths) {
     return np2h::abi_guard([&] {
         check_ks(ks, n_k);
         (void)min_count_of(opts);
+        np2srqc::Opts qo;
+        const np2srqc::Opts *q = qc_of(qc, qo);
         if (!out_paths) throw Np2Error(NP2_E_ARG, "np2_kcount_files_to_dumps: out_paths is NULL");
         for (int i = 0; i < n_k; ++i)
             if (!out_paths[i]) throw Np2Error(NP2_E_ARG, "np2_kcount_files_to_dumps: an output path is NULL");
         Source src;
         check_paths(paths, n_paths, src);
         Counter c;
-        setup(c, device, ks, n_k, opts, nullptr);
+        setup(c, device, ks, n_k, opts, nullptr, q);
         std::vector<DumpFile> dumps(n_k);
         for (int i = 0; i < n_k; ++i) dumps[i].path = out_paths[i], dumps[i].start(ks[i]);
         std::vector<uint64_t> stage;
@@ -638,17 +705,25 @@ int np2_kcount_files_to_dumps(int device, const char *const *paths, int n_paths,
             d.f = nullptr;
         }
         g_stats = c.stats;
+        publish_qc(c);
         return NP2_OK;
     }, np2h::io_set_error);
 }
 
 int np2_ctx_create_from_reads(np2_ctx_t **out, int device, const char *const *paths, int n_paths, const uint32_t *ks, int n_k,
                               const np2_kcount_opts_t *opts) {
+    return np2_ctx_create_from_reads_qc(out, device, paths, n_paths, ks, n_k, opts, nullptr);
+}
+
+int np2_ctx_create_from_reads_qc(np2_ctx_t **out, int device, const char *const *paths, int n_paths, const uint32_t *ks, int n_k,
+                                 const np2_kcount_opts_t *opts, const np2_srqc_opts_t *qc) {
     if (!out) return np2h::io_set_error(NP2_E_ARG, "np2_ctx_create_from_reads: out is NULL");
     *out = nullptr;
     return np2h::abi_guard([&] {
         check_ks(ks, n_k);
         (void)min_count_of(opts);
+        np2srqc::Opts qo;
+        const np2srqc::Opts *q = qc_of(qc, qo);
         Source src;
         check_paths(paths, n_paths, src);
         std::vector<uint32_t> sk(ks, ks + n_k);
@@ -659,7 +734,7 @@ int np2_ctx_create_from_reads(np2_ctx_t **out, int device, const char *const *pa
         std::unique_ptr<np2_ctx, void (*)(np2_ctx_t *)> cx(made, np2_ctx_destroy);
         {
             Counter c;
-            setup(c, device, sk.data(), n_k, opts, cx->stream);
+            setup(c, device, sk.data(), n_k, opts, cx->stream, q);
             run_count(c, src, true, [](const RangeOut &) {}, [] {});
             for (size_t ki = 0; ki < c.tabs.size(); ++ki) {
                 KTable &t = c.tabs[ki];
@@ -705,6 +780,7 @@ int np2_ctx_create_from_reads(np2_ctx_t **out, int device, const char *const *pa
             }
             HIPCHK(hipStreamSynchronize(c.st));
             g_stats = c.stats;
+            publish_qc(c);
         }
         *out = cx.release();
         return NP2_OK;

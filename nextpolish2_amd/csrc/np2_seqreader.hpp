@@ -1,7 +1,8 @@
 // The sequence-file reader of the k-mer counter and of the read binner (np2_kcount_host.cpp, np2_bin_host.cpp): FASTA
 // (multi-line joined) / FASTQ (the 4-line rule) / one-sequence-per-line text, plain or gzip (zlib's gzread: multi-member
 // files work through it), into the separator stream: every read's bytes as they stand, '\r' dropped, one '\n' after each
-// read; empty reads are kept, a last line needs no newline.  A caller that wants the records' names passes `hdr`.
+// read; empty reads are kept, a last line needs no newline.  A caller that wants the records' names passes `hdr`; one that
+// wants the FASTQ quality lines passes `qual` and receives a second stream of the same shape (parse_file_qual).
 #pragma once
 #include <zlib.h>
 
@@ -34,6 +35,11 @@ struct SeqParser {
     // hdr(nullptr, 0, true): a record begins (FASTA / FASTQ: at its header line; one sequence per line: at every line);
     // hdr(bytes, n, false): the next bytes of its header line, '>' / '@' included, in as many calls as the input arrives in
     template <class Put, class Hdr> void feed(const uint8_t *p, size_t n, Put &&put, Hdr &&hdr) {
+        feed(p, n, put, hdr, [](const uint8_t *, size_t) {});
+    }
+    // qual(bytes, n): the bytes of FASTQ line 3 without '\r', and one '\n' where `put` got the record's separator: the
+    // quality stream has the length and the separator offsets of the sequence stream when every record's two lines agree
+    template <class Put, class Hdr, class Qual> void feed(const uint8_t *p, size_t n, Put &&put, Hdr &&hdr, Qual &&qual) {
         static const uint8_t NL = '\n';
         size_t i = 0;
         while (i < n) {
@@ -67,21 +73,24 @@ struct SeqParser {
             const uint8_t *e = (const uint8_t *)memchr(p + i, '\n', n - i);
             const size_t end = e ? (size_t)(e - p) : n;
             if (head && end > i) hdr(p + i, end - i, false);
-            if (!skip) { // the line's bytes without '\r'
+            auto without_cr = [&](auto &sink) { // the line's bytes without '\r'
                 size_t a = i;
                 while (a < end) {
                     const uint8_t *cr = (const uint8_t *)memchr(p + a, '\r', end - a);
                     const size_t b = cr ? (size_t)(cr - p) : end;
-                    if (b > a) put(p + a, b - a);
+                    if (b > a) sink(p + a, b - a);
                     a = b + 1;
                 }
-            }
+            };
+            if (!skip) without_cr(put);
+            else if (fmt == FASTQ && line == 3) without_cr(qual);
             i = end;
             if (e) {
                 ++i;
                 bol = true;
                 if (fmt == FASTQ) {
                     if (line == 1) put(&NL, 1);
+                    if (line == 3) qual(&NL, 1);
                     if (!blank) line = (line + 1) & 3u;
                 } else if (fmt == LINES) {
                     put(&NL, 1);
@@ -94,30 +103,86 @@ struct SeqParser {
         if (fmt == FASTA ? open : fmt == FASTQ ? (!bol && line == 1) : (fmt == LINES && !bol)) put(&NL, 1);
         open = false;
     }
+    template <class Put, class Qual> void finish(Put &&put, Qual &&qual) { // ... and a last quality line without one (or none)
+        static const uint8_t NL = '\n';
+        const bool owed = fmt == FASTQ && line == 3;
+        finish(put);
+        if (owed) qual(&NL, 1);
+    }
 };
 
-// a whole file through the parser; throws NP2_E_ARG for a file that cannot be opened or a damaged / truncated gzip
-template <class Put, class Hdr> void parse_file(const std::string &path, Put &&put, const std::function<bool()> &stop, Hdr &&hdr) {
+// a whole file, 1 MiB at a time: chunk(bytes, n) until the end (true) or until stop() says so (false); throws NP2_E_ARG
+// for a file that cannot be opened or a damaged / truncated gzip
+template <class Chunk> bool read_chunks(const std::string &path, const std::function<bool()> &stop, Chunk &&chunk) {
     gzFile f = gzopen(path.c_str(), "rb");
     if (!f) throw Np2Error(NP2_E_ARG, "cannot open " + path);
     std::unique_ptr<gzFile_s, int (*)(gzFile)> guard(f, gzclose);
     gzbuffer(f, 1 << 20);
     std::vector<uint8_t> buf((size_t)1 << 20);
-    SeqParser ps;
     for (;;) {
-        if (stop && stop()) return;
+        if (stop && stop()) return false;
         const int got = gzread(f, buf.data(), (unsigned)buf.size());
         int zerr = Z_OK;
         const char *zmsg = gzerror(f, &zerr);
         if (got < 0 || (zerr != Z_OK && zerr != Z_STREAM_END))
             throw Np2Error(NP2_E_ARG, path + ": cannot read the sequence file (" + (zmsg && *zmsg ? zmsg : "damaged or truncated gzip") + ")");
-        if (got == 0) break;
-        ps.feed(buf.data(), (size_t)got, put, hdr);
+        if (got == 0) return true;
+        chunk(buf.data(), (size_t)got);
     }
-    ps.finish(put);
+}
+// a whole file through the parser
+template <class Put, class Hdr> void parse_file(const std::string &path, Put &&put, const std::function<bool()> &stop, Hdr &&hdr) {
+    SeqParser ps;
+    if (read_chunks(path, stop, [&](const uint8_t *p, size_t n) { ps.feed(p, n, put, hdr); })) ps.finish(put);
 }
 template <class Put> void parse_file(const std::string &path, Put &&put, const std::function<bool()> &stop) {
     parse_file(path, put, stop, [](const uint8_t *, size_t, bool) {});
+}
+
+// What a quality-filtering call checks of every FASTQ record while its two lines go by: the quality line is as long as
+// the sequence.  The sinks call seq_bytes / seq_end / qual_bytes / qual_end; NP2_E_ARG names the file and the 1-based record.
+struct RecordCheck {
+    std::string path;
+    uint64_t record = 0; // complete records of this file
+    uint64_t sl = 0, ql = 0;
+    bool seq_done = false;
+    [[noreturn]] void mismatch() const {
+        throw Np2Error(NP2_E_ARG, path + ": record " + std::to_string(record + 1) + ": the quality line is not as long as the sequence");
+    }
+    void seq_bytes(size_t n) { sl += n; }
+    void seq_end() { seq_done = true; }
+    void qual_bytes(size_t n) {
+        if (!seq_done || ql + n > sl) mismatch();
+        ql += n;
+    }
+    void qual_end() {
+        if (!seq_done || ql != sl) mismatch();
+        ++record, sl = ql = 0, seq_done = false;
+    }
+    void file_end() const { // a sequence line the file has no quality line for
+        if (seq_done || sl) mismatch();
+    }
+    void file_begin(const std::string &p) { path = p, record = 0, sl = ql = 0, seq_done = false; }
+};
+
+// A whole FASTQ file through the parser with its quality lines: put(bytes, n) and qual(bytes, n) receive the two streams
+// (a separator arrives as one '\n' of its own).  NP2_E_ARG, naming the file: FASTA or one sequence per line.  The caller
+// checks the records (RecordCheck) in its sinks and at the end.
+template <class Put, class Qual, class Hdr>
+void parse_file_qual(const std::string &path, Put &&put, Qual &&qual, const std::function<bool()> &stop, Hdr &&hdr) {
+    SeqParser ps;
+    const bool whole = read_chunks(path, stop, [&](const uint8_t *p, size_t n) {
+        if (ps.fmt == SeqParser::UNKNOWN)
+            for (size_t i = 0; i < n; ++i)
+                if (p[i] != '\n' && p[i] != '\r') {
+                    if (p[i] != '@')
+                        throw Np2Error(NP2_E_ARG, path + ": quality filtering needs FASTQ input, and this is " +
+                                                      (p[i] == '>' ? "FASTA" : "one sequence per line"));
+                    break;
+                }
+        ps.feed(p, n, put, hdr, qual);
+    });
+    if (whole) ps.finish(put, qual);
 }
 
 // Keeps the name of the record the reader is in, from its `hdr` calls: the header up to the first whitespace, without

@@ -4,7 +4,8 @@ import os
 
 import numpy as np
 
-from ._types import READ_DTYPE, Pileup, Yak, np2_read_t, np2_yak_t
+from ._types import (READ_DTYPE, SRQC_READ_DTYPE, SRQC_STATS, Pileup, Yak, np2_read_t, np2_srqc_opts_t, np2_srqc_stats_t,
+                     np2_yak_t)
 from .api import Np2Error, ResidentContig, lib
 
 BAMREC_DTYPE = np.dtype([("pos", "<i4"), ("flag", "<u2"), ("mapq", "u1"), ("pad", "u1"), ("n_cigar", "<u4"),
@@ -15,7 +16,9 @@ IO_SYMBOLS = ["np2_fasta_open", "np2_fasta_next", "np2_fasta_close", "np2_yak_lo
               "np2_bam_close", "np2_bam_n_refs", "np2_bam_ref_name", "np2_io_last_error", "np2_contig_from_records",
               "np2_contig_from_bam", "np2_contig_export", "np2_ctx_create_from_files", "np2_bgzf_inflate_device", "np2_crc32_device",
               "np2_kcount_files", "np2_kcount_bytes", "np2_kcount_files_to_dumps", "np2_ctx_create_from_reads", "np2_kcount_last_stats",
-              "np2_seqfile_stream", "np2_bin_files", "np2_seqfile_reads", "np2_depth_from_records", "np2_depth_from_bam"]
+              "np2_seqfile_stream", "np2_bin_files", "np2_seqfile_reads", "np2_depth_from_records", "np2_depth_from_bam",
+              "np2_srqc_bytes", "np2_srqc_files", "np2_srqc_last_stats", "np2_srqc_last_kernel_ms", "np2_kcount_files_qc",
+              "np2_kcount_files_to_dumps_qc", "np2_ctx_create_from_reads_qc", "np2_seqfile_stream_qual"]
 
 
 class np2_front_opts_t(C.Structure):
@@ -45,6 +48,82 @@ class FrontOpts:
     def c(self):
         return np2_front_opts_t(self.min_read_len, self.min_map_len, self.min_map_fra, self.min_map_qual,
                                 self.max_clip_len, 1 if self.use_supplementary else 0, 1 if self.use_secondary else 0)
+
+
+class SrQc:
+    """Options of the short-read quality filter that runs in front of the k-mer counter (include/np2_io.h has the rule: fixed
+    trims, a sliding window from each end, N / unqualified-base / length filters).  The rule is this project's own, built on
+    the options of the reference README's fastp recipe; it is not pinned against the fastp binary.  Reads are judged one by
+    one (paired files are not kept in step); there is no adapter, poly-G / poly-X, complexity or average-quality filter.
+    SrQc() and SrQc.recipe() are the recipe: -5 -3 -n 0 -f 5 -F 5 -t 5 -T 5 -q 20."""
+
+    # key of the option text -> (attribute, lowest, highest)
+    KEYS = {"front": ("trim_front", 0, 2 ** 32 - 1), "tail": ("trim_tail", 0, 2 ** 32 - 1), "cut5": ("cut_front", 0, 1),
+            "cut3": ("cut_tail", 0, 1), "window": ("cut_window", 1, 1000), "mean": ("cut_mean_q", 0, 93),
+            "n": ("n_base_limit", 0, 2 ** 32 - 1), "q": ("qualified_q", 0, 93), "u": ("unqualified_percent", 0, 100),
+            "len": ("min_len", 0, 2 ** 32 - 1)}
+
+    def __init__(self, trim_front=5, trim_tail=5, cut_front=True, cut_tail=True, cut_window=4, cut_mean_q=20, n_base_limit=0,
+                 qualified_q=20, unqualified_percent=40, min_len=15):
+        given = dict(trim_front=trim_front, trim_tail=trim_tail, cut_front=cut_front, cut_tail=cut_tail, cut_window=cut_window,
+                     cut_mean_q=cut_mean_q, n_base_limit=n_base_limit, qualified_q=qualified_q,
+                     unqualified_percent=unqualified_percent, min_len=min_len)
+        for key, (attr, lo, hi) in self.KEYS.items():
+            v = int(given[attr])
+            if not lo <= v <= hi:
+                raise ValueError(f"{attr} ({key}) must be in [{lo}, {hi}], not {given[attr]}")
+            setattr(self, attr, bool(v) if attr in ("cut_front", "cut_tail") else v)
+
+    @classmethod
+    def recipe(cls):
+        return cls()
+
+    @classmethod
+    def parse(cls, text):
+        """The option text of the command lines: "" or None is the recipe, "key=value,..." overrides single keys of it
+        (front tail cut5 cut3 window mean n q u len).  ValueError names what is wrong."""
+        kw = {}
+        for item in (text or "").split(","):
+            if not item.strip():
+                continue
+            key, eq, val = item.partition("=")
+            key = key.strip()
+            if key not in cls.KEYS or not eq:
+                raise ValueError(f"{item.strip()!r}: expected key=value with a key of {' '.join(cls.KEYS)}")
+            if key in kw:
+                raise ValueError(f"{key} is given twice")
+            try:
+                kw[key] = int(val.strip())
+            except ValueError:
+                raise ValueError(f"{key}={val.strip()}: not an integer") from None
+        return cls(**{cls.KEYS[k][0]: v for k, v in kw.items()})
+
+    def c(self):
+        return np2_srqc_opts_t(self.trim_front, self.trim_tail, self.cut_window, self.cut_mean_q, self.n_base_limit, self.qualified_q,
+                               self.unqualified_percent, self.min_len, (1 if self.cut_front else 0) | (2 if self.cut_tail else 0))
+
+    def __repr__(self):
+        return "SrQc(" + ", ".join(f"{k}={int(getattr(self, a))}" for k, (a, _, _) in self.KEYS.items()) + ")"
+
+
+def sr_qc_arg(text):
+    """argparse type of --sr_qc [SPEC], shared by the command lines: a bad key or value ends the parser (exit 2) before the
+    library is loaded"""
+    import argparse
+    try:
+        return SrQc.parse(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
+SR_QC_HELP = ("quality-trim and filter the reads on the GPU before their k-mers are counted (FASTQ input). Alone: the recipe "
+              "front=5,tail=5,cut5=1,cut3=1,window=4,mean=20,n=0,q=20,u=40,len=15 (the options of fastp -5 -3 -n 0 -f 5 -F 5 -t 5 -T 5 "
+              "-q 20; the rule is this project's own, reads are judged one by one, no adapter / poly-G / complexity filter). "
+              "SPEC overrides single keys, e.g. front=0,tail=0,mean=25")
+
+
+def srqc_stats_text(st):
+    return ", ".join(f"{k} {st[k]}" for k in SRQC_STATS)
 
 
 _BOUND = False
@@ -114,6 +193,15 @@ def _bind_kcount(L):
     from .api import np2_bin_opts_t
     L.np2_bin_files.argtypes = [vp, C.c_int, C.c_int, cpp, C.c_int, C.POINTER(np2_bin_opts_t), C.POINTER(np2_bin_out_t), vp, C.POINTER(C.c_float)]
     L.np2_seqfile_reads.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(vp), C.POINTER(C.c_uint64)]
+    qo, qs = C.POINTER(np2_srqc_opts_t), C.POINTER(np2_srqc_stats_t)
+    L.np2_kcount_files_qc.argtypes = [C.c_int, cpp, C.c_int, vp, C.c_int, ko, qo, C.POINTER(np2_yak_t)]
+    L.np2_kcount_files_to_dumps_qc.argtypes = [C.c_int, cpp, C.c_int, vp, C.c_int, ko, qo, cpp]
+    L.np2_ctx_create_from_reads_qc.argtypes = [C.POINTER(vp), C.c_int, cpp, C.c_int, vp, C.c_int, ko, qo]
+    L.np2_srqc_bytes.argtypes = [C.c_int, vp, vp, C.c_uint64, qo, vp, vp, C.c_uint64, qs]
+    L.np2_srqc_files.argtypes = [C.c_int, cpp, C.c_int, qo, cpp, qs]
+    L.np2_srqc_last_stats.argtypes = [qs]
+    L.np2_srqc_last_kernel_ms.argtypes = [C.POINTER(C.c_float)]
+    L.np2_seqfile_stream_qual.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_uint64)]
 
 
 def _io_check(rc):
@@ -242,22 +330,29 @@ def bin_files(pol, paths, pat_idx=0, mat_idx=1, min_count=2, mid_count=5, min_sc
     return dict(zip("pma0", (int(x) for x in counts))), ms.value
 
 
-def count_kmers(inputs, ks, min_count=1, device=0, mem_bytes=0):
+def _qc(qc):
+    return None if qc is None else C.byref(qc.c())
+
+
+def count_kmers(inputs, ks, min_count=1, device=0, mem_bytes=0, qc=None):
     """Canonical k-mers of short reads counted on the device -> one Yak per k (np2_kcount_files / np2_kcount_bytes).
     `inputs`: sequence file paths (FASTA / FASTQ / one sequence per line, plain or gzip), or ONE bytes object holding a
     separator stream (the reads' bytes with a newline, or any non-base byte, between reads).  Words with a count below
-    `min_count` are left out (an exact threshold); counts saturate at 1023."""
+    `min_count` are left out (an exact threshold); counts saturate at 1023.  `qc` (an SrQc; files only, FASTQ): the reads
+    are quality-trimmed and filtered on the device before they are counted; srqc_last_stats() has the totals."""
     import weakref
     L = _bind()
     kk = _ks(ks)
     o = np2_kcount_opts_t(min_count, mem_bytes)
     out = (np2_yak_t * max(1, len(kk)))()
     if isinstance(inputs, (bytes, bytearray, memoryview)):
+        if qc is not None:
+            raise ValueError("qc needs FASTQ files: a separator stream has no qualities")
         buf = np.frombuffer(inputs, dtype=np.uint8)
         _io_check(L.np2_kcount_bytes(device, buf.ctypes.data if len(buf) else None, len(buf), kk.ctypes.data, len(kk), C.byref(o), out))
     else:
         arr, n = _paths(inputs)
-        _io_check(L.np2_kcount_files(device, arr, n, kk.ctypes.data, len(kk), C.byref(o), out))
+        _io_check(L.np2_kcount_files_qc(device, arr, n, kk.ctypes.data, len(kk), C.byref(o), _qc(qc), out))
     yaks = []
     for i in range(len(kk)):
         y = np2_yak_t.from_buffer_copy(out[i])
@@ -269,8 +364,8 @@ def count_kmers(inputs, ks, min_count=1, device=0, mem_bytes=0):
     return yaks
 
 
-def count_kmers_to_files(paths, ks, out_paths, min_count=1, device=0, mem_bytes=0):
-    """np2_kcount_files_to_dumps: sequence files -> one yak v2 dump per k, written bucket by bucket."""
+def count_kmers_to_files(paths, ks, out_paths, min_count=1, device=0, mem_bytes=0, qc=None):
+    """np2_kcount_files_to_dumps: sequence files -> one yak v2 dump per k, written bucket by bucket (qc: as count_kmers)."""
     L = _bind()
     kk = _ks(ks)
     if len(out_paths) != len(kk):
@@ -278,19 +373,19 @@ def count_kmers_to_files(paths, ks, out_paths, min_count=1, device=0, mem_bytes=
     arr, n = _paths(paths)
     outs, _ = _paths(out_paths)
     o = np2_kcount_opts_t(min_count, mem_bytes)
-    _io_check(L.np2_kcount_files_to_dumps(device, arr, n, kk.ctypes.data, len(kk), C.byref(o), outs))
+    _io_check(L.np2_kcount_files_to_dumps_qc(device, arr, n, kk.ctypes.data, len(kk), C.byref(o), _qc(qc), outs))
 
 
-def polisher_from_reads(paths, ks, min_count=1, device=0, mem_bytes=0):
+def polisher_from_reads(paths, ks, min_count=1, device=0, mem_bytes=0, qc=None):
     """np2_ctx_create_from_reads: a Polisher whose HBM k-mer tables are counted from the reads and never visit the host
-    (tables ordered by k, option.rs:238).  Single-pass runs only."""
+    (tables ordered by k, option.rs:238).  Single-pass runs only.  qc: as count_kmers."""
     from .api import Polisher
     L = _bind()
     kk = _ks(ks)
     arr, n = _paths(paths)
     o = np2_kcount_opts_t(min_count, mem_bytes)
     h = C.c_void_p()
-    _io_check(L.np2_ctx_create_from_reads(C.byref(h), device, arr, n, kk.ctypes.data, len(kk), C.byref(o)))
+    _io_check(L.np2_ctx_create_from_reads_qc(C.byref(h), device, arr, n, kk.ctypes.data, len(kk), C.byref(o), _qc(qc)))
     p = Polisher.__new__(Polisher)
     p._yaks = []
     p._h = h
@@ -307,6 +402,66 @@ def kcount_last_stats():
     L.np2_kcount_last_stats(C.byref(a), C.byref(b), C.byref(c), C.byref(g), C.byref(p), C.byref(km), C.byref(rm))
     return {"kmers": a.value, "distinct": b.value, "spilled": c.value, "growths": g.value, "passes": p.value,
             "kernel_ms": km.value, "read_ms": rm.value}
+
+
+def _stats_dict(st):
+    return dict(zip(SRQC_STATS, (int(getattr(st, f)) for f, _ in np2_srqc_stats_t._fields_)))
+
+
+def srqc_last_stats():
+    """np2_srqc_last_stats: the totals of the last quality-filtering call on this thread (of a multi-pass count: one pass's)
+    plus kernel_ms, the filter kernel's time in that call."""
+    L = _bind()
+    st, ms = np2_srqc_stats_t(), C.c_float()
+    L.np2_srqc_last_stats(C.byref(st))
+    L.np2_srqc_last_kernel_ms(C.byref(ms))
+    return dict(_stats_dict(st), kernel_ms=ms.value)
+
+
+def srqc_bytes(seq, qual, qc=None, device=0, want_masked=True, want_reads=True):
+    """np2_srqc_bytes: one pair of streams (the reads' bases / quality bytes, every read followed by a newline in both)
+    through the filter -> (masked stream or None, per-read array of (begin, end, cls) or None, totals dict)."""
+    L = _bind()
+    s, q = np.frombuffer(seq, dtype=np.uint8), np.frombuffer(qual, dtype=np.uint8)
+    if len(s) != len(q):
+        raise ValueError("the two streams differ in length")
+    n_reads = int((s == 10).sum())
+    masked = np.empty(max(1, len(s)), np.uint8) if want_masked else None
+    reads = np.zeros(max(1, n_reads), SRQC_READ_DTYPE) if want_reads else None
+    st = np2_srqc_stats_t()
+    o = (qc or SrQc()).c()
+    _io_check(L.np2_srqc_bytes(device, s.ctypes.data if len(s) else None, q.ctypes.data if len(s) else None, len(s), C.byref(o),
+                               masked.ctypes.data if want_masked else None, reads.ctypes.data if want_reads else None, n_reads, C.byref(st)))
+    return (masked[:len(s)].tobytes() if want_masked else None), (reads[:n_reads] if want_reads else None), _stats_dict(st)
+
+
+def srqc_files(paths, qc=None, out_paths=None, device=0):
+    """np2_srqc_files: FASTQ files through the filter -> [totals dict per file] + [their sum]; out_paths (one per input,
+    entries may be None): the cleaned plain-text FASTQ files."""
+    L = _bind()
+    arr, n = _paths(paths)
+    outs = None
+    if out_paths is not None:
+        if len(out_paths) != n:
+            raise ValueError("one output path per input")
+        outs = (C.c_char_p * n)(*[None if p is None else os.fspath(p).encode() for p in out_paths])
+    st = (np2_srqc_stats_t * (n + 1))()
+    o = (qc or SrQc()).c()
+    _io_check(L.np2_srqc_files(device, arr, n, C.byref(o), outs, st))
+    return [_stats_dict(x) for x in st]
+
+
+def seqfile_stream_qual(path):
+    """np2_seqfile_stream_qual (host only): (sequence stream, quality stream) the reader makes of one FASTQ file, plain or
+    gzip: equal lengths, a newline after every read in both."""
+    L = _bind()
+    ps, pq, n = C.c_void_p(), C.c_void_p(), C.c_uint64()
+    _io_check(L.np2_seqfile_stream_qual(os.fspath(path).encode(), C.byref(ps), C.byref(pq), C.byref(n)))
+    try:
+        return (C.string_at(ps.value, n.value), C.string_at(pq.value, n.value)) if n.value else (b"", b"")
+    finally:
+        L.np2_free(ps)
+        L.np2_free(pq)
 
 
 def write_yak(path, yak):
