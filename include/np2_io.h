@@ -265,6 +265,49 @@ int np2_bin_files(np2_ctx_t *ctx, int pat_idx, int mat_idx, const char *const *p
  * np2_free.  Errors: np2_io_last_error(). */
 int np2_seqfile_reads(const char *path, char **names, uint64_t *names_bytes, uint64_t **ends, uint64_t *n_reads);
 
+/* ---- the repetitive k-mers of an assembly (the list winnowmap -W takes; the reference's README, "General usage" step 1:
+ * meryl count k=15 output merylDB asm.fa.gz; meryl print greater-than distinct=0.9998 merylDB > repetitive_k15.txt) ----------
+ * THE RULE IS DEFINED HERE, on meryl's documented options; it is not pinned against the meryl binary.
+ *   Input: FASTA files, plain or gzip, through the counter's reader into a separator stream (np2_seqfile_stream).
+ *   Bases: ACGTU in either case are 0..3 (U is counted and printed as T); every other byte (N, separators, bytes >= 0x80)
+ *     ends the run of bases.
+ *   k: 2 <= k <= 16, 15 by default; anything else is NP2_E_UNSUPPORTED.  A k-mer's index is v = min(fw, rv): its forward and
+ *     reverse-complement 2-bit words, first base most significant, A=0 C=1 G=2 T=3: the lexicographically smaller of the two
+ *     strings.  A palindrome (even k) is counted once per occurrence.  count[v], a uint32, is the number of stream positions
+ *     whose k-mer has index v.  A stream that could hold more than 2^32 - 1 k-mers is NP2_E_UNSUPPORTED (for gzip input this
+ *     shows only as the file is read).  A table (4 * 4^k bytes: 4 GiB at k = 15, 16 GiB at k = 16) that does not fit the
+ *     device's free memory is NP2_E_NOMEM, and the message says so.
+ *   Threshold: D = indices with count > 0, cum(c) = those of them with count <= c.  With distinct = f, 0 <= f <= 1 (NaN or
+ *     out of range is NP2_E_ARG): target = (uint64_t)(f * (double)D) in IEEE double, and the threshold is the smallest count
+ *     value c that occurs in the table with cum(c) >= target; with f = 0 the smallest occurring count.  With use_min_count
+ *     (meryl's greater-than N) the threshold is min_count and distinct is not read.  D = 0: threshold 0, an empty list, NP2_OK.
+ *   Listed: every index with count > threshold, in ascending v (ascending ACGT text); in the file one line "KMER\tCOUNT\n"
+ *     each, upper-case letters.  both_strands writes a listed k-mer's reverse complement on the line after it with the same
+ *     count, unless the k-mer is its own reverse complement (which strand winnowmap's reader expects is not checked here).
+ * Every argument is checked before the first device call.  Errors: np2_io_last_error().  Test hook, read once per call:
+ * NP2_REP_TEST_PIECE (piece size in bytes; the stream is uploaded in pieces of 8 MiB with a 32-byte halo). */
+typedef struct np2_rep_opts {
+    uint32_t k;             /* 15 */
+    uint32_t use_min_count; /* 0: distinct decides; otherwise min_count does */
+    uint32_t min_count;     /* greater-than N */
+    double distinct;        /* 0.9998 */
+} np2_rep_opts_t;
+typedef struct np2_rep_stats {
+    uint64_t kmers;              /* k-mers counted: the sum of all counters */
+    uint64_t distinct;           /* D */
+    uint64_t listed;             /* indices with count > threshold */
+    uint64_t listed_occurrences; /* the sum of their counts */
+    uint32_t threshold, max_count;
+    float count_ms, select_ms, emit_ms; /* the three stages' kernels (HIP events) */
+} np2_rep_stats_t;
+/* a separator stream in host memory -> the list: index[i] ascending, count[i]; both released with np2_free, both NULL when
+ * nothing is listed.  stats may be NULL. */
+int np2_rep_bytes(int device, const uint8_t *seq, uint64_t n, const np2_rep_opts_t *opts, uint32_t **index, uint32_t **count,
+                  uint64_t *n_listed, np2_rep_stats_t *stats);
+/* FASTA files -> the text file out_path */
+int np2_rep_files(int device, const char *const *paths, int n_paths, const np2_rep_opts_t *opts, const char *out_path,
+                  int both_strands, np2_rep_stats_t *stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -41,6 +41,7 @@ IO_ABI_SYMBOLS = [
     "np2_depth_from_records", "np2_depth_from_bam",
     "np2_srqc_bytes", "np2_srqc_files", "np2_srqc_last_stats", "np2_srqc_last_kernel_ms", "np2_kcount_files_qc",
     "np2_kcount_files_to_dumps_qc", "np2_ctx_create_from_reads_qc", "np2_seqfile_stream_qual",
+    "np2_rep_bytes", "np2_rep_files",
 ]
 
 ERRORS = {-1: "NP2_E_ARG", -2: "NP2_E_DEVICE", -3: "NP2_E_NOMEM", -4: "NP2_E_UNSUPPORTED", -5: "NP2_E_REFPANIC"}
@@ -62,6 +63,19 @@ class np2_depth_stats_t(C.Structure):
 
 
 assert C.sizeof(np2_depth_opts_t) == 24 and C.sizeof(np2_depth_stats_t) == 56
+
+
+class np2_rep_opts_t(C.Structure):
+    _fields_ = [("k", C.c_uint32), ("use_min_count", C.c_uint32), ("min_count", C.c_uint32), ("distinct", C.c_double)]
+
+
+class np2_rep_stats_t(C.Structure):
+    _fields_ = [("kmers", C.c_uint64), ("distinct", C.c_uint64), ("listed", C.c_uint64), ("listed_occurrences", C.c_uint64),
+                ("threshold", C.c_uint32), ("max_count", C.c_uint32), ("count_ms", C.c_float), ("select_ms", C.c_float),
+                ("emit_ms", C.c_float)]
+
+
+assert C.sizeof(np2_rep_opts_t) == 24 and np2_rep_opts_t.distinct.offset == 16 and C.sizeof(np2_rep_stats_t) == 56
 
 BIN_DTYPE = np.dtype([("n_kmers", "<u4"), ("n_pat", "<u4"), ("n_mat", "<u4"), ("pairs", "<u4", (4,))])  # np2_bin_t
 assert BIN_DTYPE.itemsize == 28
@@ -164,6 +178,11 @@ def _lib_locked():
         L.np2_shard_end.restype = None
         L.np2_swiss_order.argtypes = [vp, vp, u32, vp, C.POINTER(u32)]
         L.np2_batch_stats.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+        L.np2_io_last_error.restype = C.c_char_p
+        L.np2_rep_bytes.argtypes = [C.c_int, vp, u64, C.POINTER(np2_rep_opts_t), C.POINTER(vp), C.POINTER(vp), C.POINTER(u64),
+                                    C.POINTER(np2_rep_stats_t)]
+        L.np2_rep_files.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.c_int, C.POINTER(np2_rep_opts_t), C.c_char_p, C.c_int,
+                                    C.POINTER(np2_rep_stats_t)]
         _LIB = L
     return _LIB
 
@@ -951,3 +970,48 @@ def phase_vote(keys, pairs, ref=None):
     if rc != 0:
         raise Np2Error(rc, "np2_phase_vote")
     return out[: n.value].tolist()
+
+
+def _rep_opts(k, distinct, min_count):
+    if min_count is not None and not 0 <= int(min_count) <= 0xFFFFFFFF:
+        raise ValueError("min_count: 0 .. 2^32 - 1")
+    if not 0 <= int(k) <= 0xFFFFFFFF:
+        raise ValueError("k must not be negative")
+    return np2_rep_opts_t(int(k), 0 if min_count is None else 1, 0 if min_count is None else int(min_count), float(distinct))
+
+
+def _rep_check(rc):
+    if rc != 0:
+        raise Np2Error(rc, (lib().np2_io_last_error() or b"").decode())
+
+
+def rep_bytes(seq, k=15, distinct=0.9998, min_count=None, device=0):
+    """np2_rep_bytes: the repetitive k-mers of a separator stream (sequences' bytes, any non-base byte between them) ->
+    (index, count, stats): the canonical indices with count > threshold in ascending order as uint32 arrays, and the
+    np2_rep_stats_t fields as a dict.  The threshold comes from `distinct` (meryl's greater-than distinct=f), or is
+    `min_count` when that is given (greater-than N).  The rule: include/np2_io.h."""
+    L = lib()
+    s = np.frombuffer(seq, dtype=np.uint8)
+    o, st = _rep_opts(k, distinct, min_count), np2_rep_stats_t()
+    pi, pc, n = C.c_void_p(), C.c_void_p(), C.c_uint64()
+    _rep_check(L.np2_rep_bytes(device, s.ctypes.data if len(s) else None, len(s), C.byref(o), C.byref(pi), C.byref(pc), C.byref(n),
+                               C.byref(st)))
+    try:
+        index = np.asarray(_Raw(pi.value, n.value, "<u4")).copy() if n.value else np.zeros(0, np.uint32)
+        count = np.asarray(_Raw(pc.value, n.value, "<u4")).copy() if n.value else np.zeros(0, np.uint32)
+    finally:
+        L.np2_free(pi)
+        L.np2_free(pc)
+    return index, count, {f: getattr(st, f) for f, _ in np2_rep_stats_t._fields_}
+
+
+def rep_files(paths, out_path, k=15, distinct=0.9998, min_count=None, both=False, device=0):
+    """np2_rep_files: FASTA files (plain or gzip) -> the text file `out_path`, one "KMER<tab>COUNT" line per listed k-mer
+    (with `both`, its reverse complement on the next line) -> the stats dict."""
+    L = lib()
+    paths = [paths] if isinstance(paths, (str, os.PathLike)) else list(paths)
+    arr = (C.c_char_p * max(1, len(paths)))(*[os.fspath(p).encode() for p in paths])
+    o, st = _rep_opts(k, distinct, min_count), np2_rep_stats_t()
+    _rep_check(L.np2_rep_files(device, arr, len(paths), C.byref(o), None if out_path is None else os.fspath(out_path).encode(),
+                               1 if both else 0, C.byref(st)))
+    return {f: getattr(st, f) for f, _ in np2_rep_stats_t._fields_}
