@@ -190,6 +190,8 @@ def _lib_locked():
 TRACE_DTYPES = {
     "graph.off": np.uint32, "graph.bases": np.uint16, "graph.delta": np.uint16, "graph.count": np.uint32,
     "lq.start": np.uint32, "lq.end": np.uint32, "invalid_ids": np.uint32,
+    # the graph a phasing pass's vote is decided on: CSR offsets per read, rows of (neighbour, weight)
+    "vote.row_off": np.uint32, "vote.rows": np.dtype([("nbr", "<u4"), ("w", "<f4")]),
 }
 for _t in ("cand", "seed", "hete", "rech0", "rech1", "rech2"):
     TRACE_DTYPES.update({

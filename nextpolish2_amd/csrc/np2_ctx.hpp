@@ -509,7 +509,7 @@ struct np2_ctx {
     DevBuf<uint32_t> mlen; // consensus length after each splice round of the final pass (device-side chain)
     // region logic
     DevBuf<uint8_t> reg_lable, grp, cns_base2, rech_groups, rech_groups_tmp;
-    DevBuf<uint8_t> votepack;  // the vote's device-to-host payload in one piece: per-read arrays, row offsets, compact pair words
+    DevBuf<uint8_t> votepack;  // the vote's device-to-host payload in one piece: per-read arrays, row offsets, adjacency rows
     DevBuf<uint8_t> votepack2; // ... of the wide form (shards, sort fallback), gathered by copy kernels (batch driver)
     DevBuf<uint32_t> rech_headjobs; // per RECH region: 0 or 1 + the job count of the group it heads
     DevBuf<uint32_t> ecount, eval, eval_s, eflag, eidx, seed_cand, keep_n, keep_list, cns_pos2, sp_idx_s,
@@ -527,7 +527,7 @@ struct np2_ctx {
     uint32_t bucket_cap = 0;      // layout of the sorted records of the current contig (0 = compact)
     DevBuf<uint2> nrec;
     DevBuf<uint8_t> votebuf;
-    DevBuf<uint32_t> band, band_n, band_off; // banded read-pair accumulator of the phasing vote
+    DevBuf<uint32_t> band, band_n, band_off, row_cnt; // banded read-pair accumulator of the phasing vote; edges per adjacency row
     DevBuf<int64_t> run_gain, tile_gain;
     DevBuf<uint8_t> out_snap;
     DevBuf<uint8_t> run_flag; // long runs handed from the eight-lane DP kernel to the per-thread one
@@ -583,7 +583,8 @@ enum Scal { S_ERR = 0, S_NNODES, S_NRUNS, S_BEST, S_PATHBEGIN, S_NRAW, S_NREG, S
             S_GAIN1, S_DEEP, S_NDPLIST, S_NRECH, S_NGROUPS, S_NLONG, S_NLQ, S_PF, S_M0, S_M1, S_M2, S_M3, S_NC, S_SB, S_GROW,
             // the fused pass front (np2_passfront.hip): S_PF = flag word of the pass under way (above), tiles listed for the big
             // variant, the flags as the host reads them, total of the path-score gains, best end node's relative score
-            S_NBAD, S_PFOUT, S_PFGAIN0, S_PFGAIN1, S_PFEND0, S_PFEND1, S_NBAD2, S_PFPAD, S_COUNT = 34 };
+            // S_NOKEY: pairs of a vote with an endpoint that never voted (k_vote_rows_emit)
+            S_NBAD, S_PFOUT, S_PFGAIN0, S_PFGAIN1, S_PFEND0, S_PFEND1, S_NBAD2, S_NOKEY, S_COUNT = 34 };
 static_assert(S_M1 % 2 == 0 && S_LAST0 % 2 == 0 && S_GAIN0 % 2 == 0 && S_PFGAIN0 % 2 == 0 && S_PFEND0 % 2 == 0,
               "64-bit device counters live in these slot pairs");
 

@@ -159,19 +159,23 @@ struct VoteData {
     const uint64_t *view_key = nullptr;
     const uint32_t *view_cnt = nullptr;
     uint64_t view_n = 0;
-    // ... or the compact rows of the plain pipeline (k_band_emit_compact: 4 bytes per pair; row a of the reads' band =
-    // words [c_off[a], c_off[a + 1]), word = (b - a - 1) | agree << 8 | disagree << 20), again a view of the staging
-    const uint32_t *c_off = nullptr, *c_pairs = nullptr;
-    std::vector<uint32_t> c_off_own, c_pairs_own;
-    bool compact() const { return c_off != nullptr; }
+    // ... or the finished adjacency rows of the plain pipeline (k_vote_rows_emit: row v of the vote's graph = edges
+    // [off[v], off[v + 1]), its partners below it, then those above it, flagged reads already left out unless every read
+    // is used), again a view of the staging; n_nokey: pairs with an endpoint that never voted (an internal error)
+    const uint32_t *off = nullptr;
+    const phase::Graph::Edge *edges = nullptr;
+    uint32_t n_nokey = 0;
+    std::vector<uint32_t> off_own;
+    std::vector<phase::Graph::Edge> edges_own;
+    bool rows() const { return off != nullptr; }
     const uint64_t *keys() const { return view_key ? view_key : pair_key.data(); }
     const uint32_t *cnts() const { return view_key ? view_cnt : pair_cnt.data(); }
-    uint64_t n_pairs() const { return compact() ? (uint64_t)c_off[R] : view_key ? view_n : (uint64_t)pair_key.size(); }
+    uint64_t n_pairs() const { return view_key ? view_n : (uint64_t)pair_key.size(); } // (not of the rows form)
     void own() { // copy a view into the vectors (the viewed memory is about to be reused)
-        if (compact() && c_off_own.empty()) {
-            c_off_own.assign(c_off, c_off + R + 1);
-            c_pairs_own.assign(c_pairs, c_pairs + c_off[R]);
-            c_off = c_off_own.data(), c_pairs = c_pairs_own.data();
+        if (rows() && off_own.empty()) {
+            off_own.assign(off, off + R + 1);
+            edges_own.assign(edges, edges + off[R]);
+            off = off_own.data(), edges = edges_own.data();
         }
         if (!view_key) return;
         pair_key.assign(view_key, view_key + view_n);
@@ -186,10 +190,54 @@ struct VoteData {
     bool key_added = false;           // (wide form) the pair keys already carry the shard's read-number shift
 };
 
+// The rows form of a vote from its sorted pair list, on the host: a plain serial restatement of what k_vote_rows_count /
+// the row-total scan / k_vote_rows_emit deliver (np2_regions.hip), and the model those kernels are tested against.
+// Row v = partners below v ascending, then partners above v ascending; weight = -neg if neg >= 3, else same - neg
+// (main.rs:996-1002); unless every read is used, a flagged read has an empty row and appears in none; pairs with an
+// endpoint that never voted are counted, not listed.  -> false: the list is not sorted by (a, b) with a < b, or a pair
+// lies outside the band (b - a - 1 >= EDGE_BAND) — the kernels' band does not hold such a vote.
+bool vote_rows_from_pairs(VoteData &vd, bool use_all) {
+    const uint32_t R = vd.R;
+    const uint64_t *k = vd.keys();
+    const uint32_t *cn = vd.cnts();
+    const uint64_t np = vd.n_pairs();
+    std::vector<uint32_t> n_lo(R, 0), n_up(R, 0);
+    uint32_t nokey = 0;
+    auto listed = [&](uint64_t i, uint32_t &a, uint32_t &b) { // is pair i an edge of the rows?
+        a = (uint32_t)(k[i] >> 32), b = (uint32_t)k[i];
+        if (a >= R || b >= R || vd.first_key[a] == 0xFFFFFFFFu || vd.first_key[b] == 0xFFFFFFFFu) return false;
+        return use_all || !(vd.bad[a] | vd.bad[b]);
+    };
+    for (uint64_t i = 0; i < np; ++i) {
+        uint32_t a = (uint32_t)(k[i] >> 32), b = (uint32_t)k[i];
+        if (b <= a || b - a - 1 >= EDGE_BAND || (i && k[i - 1] >= k[i])) return false;
+        if (a >= R || b >= R || vd.first_key[a] == 0xFFFFFFFFu || vd.first_key[b] == 0xFFFFFFFFu) ++nokey;
+        if (listed(i, a, b)) ++n_lo[b], ++n_up[a];
+    }
+    vd.off_own.assign((size_t)R + 1, 0);
+    std::vector<uint32_t> cur_lo(R), cur_up(R);
+    for (uint32_t v = 0; v < R; ++v) {
+        cur_lo[v] = vd.off_own[v], cur_up[v] = vd.off_own[v] + n_lo[v];
+        vd.off_own[v + 1] = cur_up[v] + n_up[v];
+    }
+    vd.edges_own.resize(vd.off_own[R]);
+    for (uint64_t i = 0; i < np; ++i) {
+        uint32_t a, b;
+        if (!listed(i, a, b)) continue;
+        const int32_t same = (int32_t)(cn[i] & 0xFFFFu), neg = (int32_t)(cn[i] >> 16);
+        const float w = (float)(neg >= 3 ? -neg : same - neg);
+        vd.edges_own[cur_lo[b]++] = phase::Graph::Edge(a, w);
+        vd.edges_own[cur_up[a]++] = phase::Graph::Edge(b, w);
+    }
+    vd.off = vd.off_own.data(), vd.edges = vd.edges_own.data(), vd.n_nokey = nokey;
+    return true;
+}
+
 // GPU part of the phasing pass: mark_hete (main.rs:916-946), pair votes (948-1002) over the regions whose start lies in
 // [own_lo, own_hi)
-// `wide`: pairs as (a << 32 | b, counts) — what the shards of a contig export and merge; otherwise the compact rows, read
-// back in the SAME wait as the counters that size them (one device round trip and 8 bytes per pair less)
+// `wide`: pairs as (a << 32 | b, counts) — what the shards of a contig export and merge; otherwise the finished adjacency
+// rows of the vote's graph, read back in the SAME wait as the counters that size them (one device round trip less, and
+// no row building on the host)
 void vote_collect(np2_ctx *cx, np2_contig *c, PassCounts &pc, bool asref, bool use_all, int pass, uint32_t own_lo,
                   uint32_t own_hi, VoteData &vd, bool wide = false, uint64_t key_add = 0) {
     hipStream_t s = cx->stream;
@@ -205,7 +253,7 @@ void vote_collect(np2_ctx *cx, np2_contig *c, PassCounts &pc, bool asref, bool u
         cx->ecount.ensure(n_reg + 2);
         cx->eoff.ensure(std::max<size_t>(n_reg + 2, (size_t)c->L + 2));
         // per-read vote outputs live in one buffer: [first_reg u32 x RP][ref_w i32 x RP][ref_seen u8 x RP][bad u8 x RP]
-        // (compact: followed by the row offsets and the pair words — one piece to read back)
+        // (plain: followed by the row offsets and the adjacency rows — one piece to read back)
         const size_t RP = ((size_t)R + 63) & ~(size_t)63;
         const size_t band_words = (size_t)R * EDGE_BAND;
         const size_t b_v = RP * 10, b_off = (((size_t)R + 2) * 4 + 15) & ~(size_t)15;
@@ -216,7 +264,7 @@ void vote_collect(np2_ctx *cx, np2_contig *c, PassCounts &pc, bool asref, bool u
             cx->band_off.ensure((size_t)R + 2);
             vbuf = cx->votebuf.p, row_off = cx->band_off.p;
         } else {
-            cx->votepack.ensure(b_v + b_off + band_words * 4 + 64);
+            cx->votepack.ensure(b_v + b_off + band_words * 2 * sizeof(phase::Graph::Edge) + 64); // (every pair is listed in two rows)
             vbuf = cx->votepack.p, row_off = (uint32_t *)(cx->votepack.p + b_v);
         }
         uint32_t *v_first = (uint32_t *)vbuf;
@@ -237,14 +285,18 @@ void vote_collect(np2_ctx *cx, np2_contig *c, PassCounts &pc, bool asref, bool u
         op_fill(cx, cx->scal.p + S_M3, 0, 4);
         launch_edges_row(s, rt, cx->grp.p, cx->ecount.p, cx->pj.p, cx->pcount.p, cx->alive.p, R, cx->band.p, cx->band_n.p,
                          cx->scal.p + S_M3);
-        exclusive_total_n(cx, cx->band_n.p, row_off, R);
         if (wide) {
+            exclusive_total_n(cx, cx->band_n.p, row_off, R);
             cx->ekey.ensure(band_words + 2);
             cx->eval.ensure(band_words + 2);
             launch_band_emit(s, cx->band.p, R, row_off, cx->ekey.p, cx->eval.p, cx->scal.p + S_NRAW, key_add);
         } else {
-            launch_band_emit_compact(s, cx->band.p, R, row_off, (uint32_t *)(cx->votepack.p + b_v + b_off), cx->scal.p + S_NRAW,
-                                     cx->scal.p + S_M3);
+            // the rows' edge counts (both directions of every pair, flagged reads left out), their offsets, the rows
+            cx->row_cnt.ensure((size_t)R + 2);
+            launch_vote_rows_count(s, cx->band.p, cx->band_n.p, v_bad, use_all, R, cx->row_cnt.p, cx->scal.p + S_NOKEY);
+            exclusive_total_n(cx, cx->row_cnt.p, row_off, R);
+            launch_vote_rows_emit(s, cx->band.p, cx->band_n.p, v_bad, use_all, v_first, R, row_off, cx->votepack.p + b_v + b_off,
+                                  cx->scal.p + S_NRAW, cx->scal.p + S_NOKEY);
         }
     }
     const size_t RP = ((size_t)R + 63) & ~(size_t)63;
@@ -259,20 +311,23 @@ void vote_collect(np2_ctx *cx, np2_contig *c, PassCounts &pc, bool asref, bool u
     {
         std::vector<uint32_t> sc;
         uint8_t *pin = nullptr;
-        // pairs the first copy has room for: 64 per read (a 30x diploid pileup has ~36); more follow in a second copy
-        const uint32_t likely = (uint32_t)std::min<size_t>((size_t)R * EDGE_BAND, std::max<size_t>((size_t)R * 64, 1u << 14));
+        // edges the first copy has room for: 128 per read (a 30x diploid pileup has ~36 partners above a read and as many
+        // below it); more follow in a second copy
+        const size_t EB = sizeof(phase::Graph::Edge);
+        static_assert(sizeof(phase::Graph::Edge) == 8 && alignof(phase::Graph::Edge) <= 8, "an edge is {u32 neighbour, f32 weight}");
+        const uint32_t likely = (uint32_t)std::min<size_t>((size_t)R * EDGE_BAND * 2, std::max<size_t>((size_t)R * 128, 1u << 15));
         if (wide) {
             sc = fetch_scal(cx, cx->scal.p + S_M0, cx->eoff.p + n_reg);
         } else {
-            // counters, per-read arrays, row offsets and the pair words in ONE wait: the mailbox post, two copies (the second
-            // one sized on the device by the number of pairs), one synchronisation
-            pin = (uint8_t *)cx->pin_d2h.ensure(b_v + b_off + (size_t)likely * 4 + 64);
+            // counters, per-read arrays, row offsets and the rows in ONE wait: the mailbox post, two copies (the second
+            // one sized on the device by the number of edges), one synchronisation
+            pin = (uint8_t *)cx->pin_d2h.ensure(b_v + b_off + (size_t)likely * EB + 64);
             const uint32_t seq = ++cx->mbox_seq;
             launch_post(cx->stream, cx->scal.p, S_COUNT, cx->mbox_dev, seq, cx->scal.p + S_M0, cx->eoff.p + n_reg, nullptr, nullptr,
                         nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
             op_d2h(cx, pin, cx->votepack.p, b_v + b_off);
             launch_copy_counted(cx->stream, (uint32_t *)(pin + b_v + b_off), (const uint32_t *)(cx->votepack.p + b_v + b_off),
-                                (const uint32_t *)(cx->votepack.p + b_v) + R, likely);
+                                (const uint32_t *)(cx->votepack.p + b_v) + R, likely * (uint32_t)(EB / 4), (uint32_t)(EB / 4));
             op_sync(cx);
             if (__atomic_load_n(&cx->mbox_host[0], __ATOMIC_ACQUIRE) != seq)
                 throw Np2Error(NP2_E_DEVICE, "mailbox not posted after a synchronisation");
@@ -287,23 +342,27 @@ void vote_collect(np2_ctx *cx, np2_contig *c, PassCounts &pc, bool asref, bool u
         }
         NU = sc[S_NRAW];
         far = sc[S_M3] != 0 || cx->hooks.edge_sort; // (test hook: force the sort-based path)
+        // (counts, read through np2_last_timings by the tests: which form the pass's vote arrived in)
+        if (!wide) cx->timing.host.push_back({far ? "vote_sort" : "vote_rows", 1.0f});
         if (!wide) {
             per_read(pin);
             have_per_read = true;
             vd.d_bad = cx->votepack.p + RP * 9;
             if (!far) {
-                if (NU > likely) { // more pairs than the first copy had room for: fetch the whole piece again
-                    pin = (uint8_t *)cx->pin_d2h.ensure(b_v + b_off + (size_t)NU * 4 + 64);
-                    op_d2h(cx, pin, cx->votepack.p, b_v + b_off + (size_t)NU * 4);
+                if (NU > likely) { // more edges than the first copy had room for: fetch the whole piece again
+                    pin = (uint8_t *)cx->pin_d2h.ensure(b_v + b_off + (size_t)NU * EB + 64);
+                    op_d2h(cx, pin, cx->votepack.p, b_v + b_off + (size_t)NU * EB);
                     op_sync(cx);
                 }
-                vd.c_off = (const uint32_t *)(pin + b_v), vd.c_pairs = (const uint32_t *)(pin + b_v + b_off);
-                if (vd.c_off[R] != NU) throw Np2Error(NP2_E_DEVICE, "internal: vote rows and pair count disagree");
+                // (the rows stay in the staging: Graph::adopt_rows borrows them from there)
+                vd.off = (const uint32_t *)(pin + b_v), vd.edges = (const phase::Graph::Edge *)(pin + b_v + b_off);
+                vd.n_nokey = sc[S_NOKEY];
+                if (vd.off[R] != NU) throw Np2Error(NP2_E_DEVICE, "internal: vote rows and edge count disagree");
             }
         }
     }
     vd.any = true;
-    if (NE && far) { // some pair lies outside the band (deep pileup) or a count outgrew 12 bits: sort the raw votes instead
+    if (NE && far) { // some pair lies outside the band (deep pileup): sort the raw votes instead
         {
             EventTimer t(cx, "vote_phase");
             cx->ekey.ensure(NE + 2);
@@ -371,11 +430,12 @@ void vote_collect(np2_ctx *cx, np2_contig *c, PassCounts &pc, bool asref, bool u
 // Host part of the vote: rebuild the weight maps in the reference's key-creation order, then Louvain
 // (louvain.rs:290-356).  Outer keys of `data` are created region by region (index order), valid non-ref candidates in
 // position (= read index) order, first occurrence wins.
-std::vector<uint32_t> vote_decide(np2_ctx *cx, const VoteData &vd, bool use_all) {
+// (pass: where a tracing context files the graph the decision is taken on)
+std::vector<uint32_t> vote_decide(np2_ctx *cx, const VoteData &vd, bool use_all, int pass = -1) {
     if (!vd.any) return {};
     const uint32_t R = vd.R;
-    const uint64_t NU = vd.n_pairs();
-    const uint32_t *const pair_cnt = vd.compact() ? nullptr : vd.cnts();
+    const uint64_t NU = vd.rows() ? 0 : vd.n_pairs();
+    const uint32_t *const pair_cnt = vd.rows() ? nullptr : vd.cnts();
     const double t_host0 = now_ms();
     // reads with a key, by (creation rank, read): the reads come in read order, so a STABLE sort by rank alone does it —
     // two 16-bit counting passes (a comparison sort of a chromosome's 3 x 10^5 keys was 12 ms)
@@ -417,11 +477,8 @@ std::vector<uint32_t> vote_decide(np2_ctx *cx, const VoteData &vd, bool use_all)
         return (float)(neg >= 3 ? -neg : same - neg);
     };
     // data.retain(..) + per-row retain (main.rs:1004-1010) drop the reads flagged bad and every edge pointing at one:
-    // those edges are left out while the rows are built (the rows' relative order is all that is kept of them)
-    auto weight_c = [](uint32_t w) {
-        const int32_t same = (int32_t)((w >> 8) & 0xFFFu), neg = (int32_t)(w >> 20);
-        return (float)(neg >= 3 ? -neg : same - neg);
-    };
+    // those edges are left out while the rows are built (the rows' relative order is all that is kept of them); rows
+    // that arrive finished (the plain pipeline's) have left them out already
     // data.retain(..) on the keys themselves (erase order = bucket order) BEFORE the rows: the rows leave the flagged reads'
     // edges out by themselves, and with the key table final the first level's community map — the keys inserted into a
     // fresh map in the table's iteration order, 10 ms of hash-order emulation for a chromosome — is built on a helper
@@ -436,8 +493,12 @@ std::vector<uint32_t> vote_decide(np2_ctx *cx, const VoteData &vd, bool use_all)
         communities = std::async(std::launch::async, [&data] { return phase::SignedLouvain::first_communities(data.keys); });
     bool ok = false;
     try {
-        ok = vd.compact() ? data.add_edges_rows(vd.c_off, vd.c_pairs, R, weight_c, use_all ? nullptr : vd.bad.data())
-                          : data.add_edges_sorted(vd.keys(), NU, weight, use_all ? nullptr : vd.bad.data());
+        if (vd.rows()) {
+            ok = vd.n_nokey == 0;
+            if (ok) data.adopt_rows(vd.off, vd.edges, R); // (borrowed: vd outlives the decision)
+        } else {
+            ok = data.add_edges_sorted(vd.keys(), NU, weight, use_all ? nullptr : vd.bad.data());
+        }
     } catch (...) {
         if (communities.valid()) communities.wait(); // (it reads data.keys)
         throw;
@@ -449,6 +510,11 @@ std::vector<uint32_t> vote_decide(np2_ctx *cx, const VoteData &vd, bool use_all)
     if (!use_all)
         for (uint32_t b : bad) data.is_key[b] = 0;
     mark("keys + edges");
+    if (cx && cx->trace && pass >= 0) { // the graph the decision is taken on, whichever path built it
+        trace_put(cx, pass, "vote.row_off", data.off);
+        const phase::Graph::Edge *e0 = data.n_ids() ? data.adj(0).b : nullptr;
+        trace_put(cx, pass, "vote.rows", std::vector<phase::Graph::Edge>(e0, e0 + (e0 ? data.n_edges() : 0)));
+    }
     std::vector<float> ref_row(R, 0.f);
     std::vector<uint8_t> ref_have(R, 0);
     bool have_ref = false;
@@ -1201,7 +1267,7 @@ struct PolishRun {
     bool reuse = false;
     bool front_issued = false; // graph, DP, consensus and LQ regions of pass `pass` are already on their way (polish_impl)
     uint32_t grow_prev = 0xFFFFFFFFu; // growth bound of the previous (phasing) pass, read back with its vote for free
-    bool wide_votes = false; // the shards of a contig export (a << 32 | b, counts) pairs; the plain pipeline reads compact rows
+    bool wide_votes = false; // the shards of a contig export (a << 32 | b, counts) pairs; the plain pipeline reads the graph's finished rows
     uint64_t key_add = 0;    // ... with the shard's read-number shift added on the device (s << 32 | s)
     PassCounts pc;
     bool final_pass() const { return pass + 1 == o.iter_count; }
@@ -1414,7 +1480,7 @@ void polish_impl(np2_ctx *cx, np2_contig *c, const np2_opts_t *o, ResultOut &res
         if (vd->any && vd->d_bad && !use_all && !cx->trace && !no_spec)
             for (uint8_t b : vd->bad) n_bad += b;
         if (n_bad == 0) {
-            run_apply_losers(r, vote_decide(cx, *vd, use_all));
+            run_apply_losers(r, vote_decide(cx, *vd, use_all, (int)r.pass));
             continue;
         }
         launch_kill_flagged(cx->stream, vd->d_bad, c->R, cx->alive.p);
@@ -1426,7 +1492,6 @@ void polish_impl(np2_ctx *cx, np2_contig *c, const np2_opts_t *o, ResultOut &res
         pass_front_issue(cx, c, r.T, (int)r.pass);
         r.front_issued = true;
         op_submit(cx);
-        vd->own(); // (the pairs sit in the context's read-back staging, which the pipeline goes on using)
         pend.vd = vd;
         pend.n_bad = n_bad;
         pend.active = true;
@@ -1439,12 +1504,15 @@ void polish_impl(np2_ctx *cx, np2_contig *c, const np2_opts_t *o, ResultOut &res
         };
         if (tl_recorder() == nullptr) {
             // one contig on its own context (a chromosome: ~100 ms of host vote next to ~50 ms of device work for the pass)
+            vd->own(); // (the rows sit in the context's read-back staging, which the pipeline goes on using meanwhile)
             pend.fut = std::async(std::launch::async, decide);
         } else {
             // Under the batch driver the decision is taken here and now, next to the part of the pass that is already on
             // its way: with four batch groups the device is the busy part of a step, and seventeen more host threads
             // deciding votes beside the pipelines' own cost more than the rest of the overlap gave (3.72 ms per
             // yeast-sized assembly this way, 3.9 - 4.1 with helper threads; 4.06 without any early start).
+            // The rows are read where the vote's read-back left them: nothing has been read back since, and nothing is
+            // before the decision stands.
             std::promise<Decision> p;
             pend.fut = p.get_future();
             try {
@@ -2350,22 +2418,9 @@ int np2_vote_decide(const np2_vote_t *votes, int n_votes, uint32_t n_reads_total
         for (uint32_t r = 0; r < n_reads_total; ++r)
             if (votes_any[r]) vd.first_key[r] = 0xFFFFFFFEu - first_pos[r]; // ascending = right to left
         if (getenv("NP2_VOTE_COMPACT")) {
-            // test hook (no device needed): the same vote in the compact row form the plain pipeline reads back from the
-            // vote kernels, so that the row builder over that form is checked against recorded votes on the CPU
-            const uint64_t *k = vd.keys();
-            const uint32_t *cn = vd.cnts();
-            const uint64_t np = vd.n_pairs();
-            vd.c_off_own.assign((size_t)n_reads_total + 1, 0);
-            vd.c_pairs_own.resize(np);
-            for (uint64_t i = 0; i < np; ++i) {
-                const uint32_t a = (uint32_t)(k[i] >> 32), b = (uint32_t)k[i], same = cn[i] & 0xFFFFu, neg = cn[i] >> 16;
-                if (b <= a || b - a - 1 > 255u || same > VOTE_CNT_MAX || neg > VOTE_CNT_MAX || (i && k[i - 1] >= k[i]))
-                    return NP2_E_UNSUPPORTED; // (such a vote takes the wide form)
-                ++vd.c_off_own[a + 1];
-                vd.c_pairs_own[i] = (b - a - 1) | (same << 8) | (neg << 20);
-            }
-            for (uint32_t r = 0; r < n_reads_total; ++r) vd.c_off_own[r + 1] += vd.c_off_own[r];
-            vd.c_off = vd.c_off_own.data(), vd.c_pairs = vd.c_pairs_own.data();
+            // test hook (no device needed): the same vote in the form the plain pipeline reads back from the vote kernels
+            // — finished adjacency rows —, so that the adopting path is checked against recorded votes on the CPU
+            if (!vote_rows_from_pairs(vd, opts->use_all_reads != 0)) return NP2_E_UNSUPPORTED; // (such a vote takes the wide form)
         }
         std::vector<uint32_t> ls = vote_decide(nullptr, vd, opts->use_all_reads != 0);
         *n_losers = (uint32_t)ls.size();

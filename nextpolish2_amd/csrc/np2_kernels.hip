@@ -100,12 +100,12 @@ __device__ __forceinline__ void k_copy_len(const uint32_t np2_bid, const uint32_
                                            const uint32_t *__restrict__ n_dev, uint32_t elem, uint64_t cap) {
     k_copy(np2_bid, np2_nb, dst, src, min((uint64_t)*n_dev * elem, cap));
 }
-// copy of n 32-bit words where n = min(*n_dev, cap) lives on the device: the grid is sized by the host's bound, the
+// copy of n 32-bit words where n = min(*n_dev * words_per, cap) lives on the device: the grid is sized by the host's bound, the
 // threads walk the real length (16 bytes per thread and step).  A read-back whose size is only known on the device
 // rides in the same wait as the counters that say how large it is.
 __device__ __forceinline__ void k_copy_counted(const uint32_t np2_bid, const uint32_t np2_nb, uint32_t *__restrict__ dst, const uint32_t *__restrict__ src,
-                                               const uint32_t *__restrict__ n_dev, uint32_t cap) {
-    const uint32_t n = min(*n_dev, cap);
+                                               const uint32_t *__restrict__ n_dev, uint32_t cap, uint32_t words_per) {
+    const uint32_t n = (uint32_t)min((uint64_t)*n_dev * words_per, (uint64_t)cap);
     const bool wide = ((((uintptr_t)dst) | ((uintptr_t)src)) & 15) == 0;
     for (uint64_t o = ((uint64_t)np2_bid * 256 + threadIdx.x) * 4; o < n; o += (uint64_t)np2_nb * 256 * 4) {
         if (wide && o + 4 <= n) {
@@ -1555,8 +1555,8 @@ void launch_copy(hipStream_t s, uint8_t *dst, const uint8_t *src, uint64_t bytes
 void launch_copy_len(hipStream_t s, uint8_t *dst, const uint8_t *src, const uint32_t *n_dev, uint32_t elem, uint64_t cap_bytes) {
     if (cap_bytes) NP2_LAUNCH(k_copy_len, grid1((cap_bytes + 15) / 16), 256, s, dst, src, n_dev, elem, cap_bytes);
 }
-void launch_copy_counted(hipStream_t s, uint32_t *dst, const uint32_t *src, const uint32_t *n_dev, uint32_t cap) {
-    if (cap) NP2_LAUNCH(k_copy_counted, dim3(std::max<uint32_t>(1, std::min<uint32_t>((cap + 1023) / 1024, 2048))), 256, s, dst, src, n_dev, cap);
+void launch_copy_counted(hipStream_t s, uint32_t *dst, const uint32_t *src, const uint32_t *n_dev, uint32_t cap, uint32_t words_per) {
+    if (cap) NP2_LAUNCH(k_copy_counted, dim3(std::max<uint32_t>(1, std::min<uint32_t>((cap + 1023) / 1024, 2048))), 256, s, dst, src, n_dev, cap, words_per);
 }
 void launch_init_alive(hipStream_t s, const np2_read_t *reads, uint32_t R, uint8_t *alive) {
     NP2_LAUNCH(k_init_alive, grid1(R), 256, s, reads, R, alive);

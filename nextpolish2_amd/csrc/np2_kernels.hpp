@@ -137,8 +137,8 @@ void launch_post(hipStream_t s, uint32_t *scal, uint32_t n_scal, uint32_t *mbox,
 void launch_fill(hipStream_t s, uint8_t *p, uint64_t bytes, uint8_t byte);
 void launch_copy(hipStream_t s, uint8_t *dst, const uint8_t *src, uint64_t bytes);
 void launch_copy_len(hipStream_t s, uint8_t *dst, const uint8_t *src, const uint32_t *n_dev, uint32_t elem, uint64_t cap_bytes);
-// min(*n_dev, cap) 32-bit words, the count read on the device
-void launch_copy_counted(hipStream_t s, uint32_t *dst, const uint32_t *src, const uint32_t *n_dev, uint32_t cap);
+// min(*n_dev * words_per, cap) 32-bit words, the count read on the device
+void launch_copy_counted(hipStream_t s, uint32_t *dst, const uint32_t *src, const uint32_t *n_dev, uint32_t cap, uint32_t words_per = 1);
 void launch_init_alive(hipStream_t s, const np2_read_t *reads, uint32_t R, uint8_t *alive);
 void launch_kill_reads(hipStream_t s, const uint32_t *ids, uint32_t n, uint8_t *alive);
 void launch_revive_reads(hipStream_t s, const uint32_t *ids, uint32_t n, uint8_t *alive); // alive[ids[i]] = 1 (np2_shard_apply)
@@ -332,11 +332,14 @@ void launch_edges_row(hipStream_t s, const RegionTables &rt, const uint8_t *grp,
                       const uint32_t *pcount, const uint8_t *alive, uint32_t R, uint32_t *band, uint32_t *row_n, uint32_t *ovf);
 void launch_band_emit(hipStream_t s, const uint32_t *band, uint32_t R, const uint32_t *row_off, uint64_t *ukey, uint32_t *uw,
                       uint32_t *n_out, uint64_t key_add = 0);
-// the same pairs in 4 bytes each, row by row: word = (b - a - 1) | agreeing regions << 8 | disagreeing regions << 20
-// (12 bits each; a larger count bumps *ovf and the host takes the sort path), row a = [row_off[a], row_off[a + 1])
-static constexpr uint32_t VOTE_CNT_MAX = 0xFFFu;
-void launch_band_emit_compact(hipStream_t s, const uint32_t *band, uint32_t R, const uint32_t *row_off, uint32_t *pairs,
-                              uint32_t *n_out, uint32_t *ovf);
+// the plain pipeline's form: the finished adjacency rows of the vote's graph (np2_regions.hip: k_vote_rows_*).  cnt[v] =
+// edges of row v; with off = its exclusive scan (off[R] = total), row v = edges[off[v] .. off[v + 1]), 8 bytes per
+// edge {u32 neighbour, f32 weight} (phase::Graph::Edge), partners below v ascending, then partners above v ascending;
+// *n_out = off[R], *nokey = pairs with an endpoint that never voted (cleared by the counting kernel)
+void launch_vote_rows_count(hipStream_t s, const uint32_t *band, const uint32_t *row_n, const uint8_t *bad, bool use_all, uint32_t R,
+                            uint32_t *cnt, uint32_t *nokey);
+void launch_vote_rows_emit(hipStream_t s, const uint32_t *band, const uint32_t *row_n, const uint8_t *bad, bool use_all,
+                           const uint32_t *first_reg, uint32_t R, const uint32_t *off, void *edges, uint32_t *n_out, uint32_t *nokey);
 void launch_edge_reduce(hipStream_t s, const uint64_t *ekey, const uint32_t *eval, uint32_t n, uint32_t *flag, uint32_t *wout);
 void launch_edge_compact(hipStream_t s, const uint64_t *ekey, const uint32_t *flag, const uint32_t *idx, const uint32_t *wout,
                          uint32_t n, uint64_t *ukey, uint32_t *uw, uint32_t *n_out);

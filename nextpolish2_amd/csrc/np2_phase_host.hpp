@@ -396,7 +396,10 @@ struct Graph {
         }
     }
     bool has_key(uint32_t k) const { return k < is_key.size() && is_key[k]; }
-    Row adj(uint32_t v) const { return Row{edges.data() + off[v], edges.data() + off[v + 1]}; }
+    Row adj(uint32_t v) const {
+        const Edge *base = ext_ ? ext_ : edges.data();
+        return Row{base + off[v], base + off[v + 1]};
+    }
     // (Re)build the rows from a list of undirected weighted edges: count, prefix, fill.  Returns false if an
     // endpoint is not a key.
     // `skip` (optional, per node): edges with a flagged endpoint are left out — what drop_nodes would remove afterwards.
@@ -508,67 +511,22 @@ struct Graph {
         if (prof) fprintf(stderr, "    rows: check %.2f ms, count %.2f ms, offsets + allocation %.2f ms, fill %.2f ms (%zu threads, largest b - a %u)\n", t1 - t0, t2 - t1, t3 - t2, now() - t3, T, maxgap);
         return true;
     }
-    // The same rows from the COMPACT pair rows of the vote kernels (k_band_emit_compact): row a of the band = words
-    // [row_off[a], row_off[a + 1]), word & 255 = b - a - 1, the rest decoded by gw(word).  The pairs come in the order of
-    // the sorted (a, b) list, so the result is the one add_edges_sorted / add_edges give for that list: every row holds
-    // its partners below it (ascending), then those above it (ascending).  Threads own row ranges; the partners below a
-    // row sit in the rows of the 256 reads before it.
-    template <class GetW>
-    bool add_edges_rows(const uint32_t *row_off, const uint32_t *cp, uint32_t R, GetW gw, const uint8_t *skip = nullptr) {
-        const uint32_t N = n_ids();
-        if (R > N) return false;
-        const uint64_t n = row_off[R];
-        const uint32_t BAND = 256;
-        const size_t T = (n < (1u << 18) || host_threads() < 2) ? 1 : std::min<size_t>(host_threads(), n >> 16);
-        // endpoints are keys
-        std::vector<uint8_t> bad_t(T, 0);
-        std::vector<uint32_t> row_lo(T + 1, 0);
-        for (size_t t = 1; t < T; ++t)
-            row_lo[t] = std::max<uint32_t>(row_lo[t - 1], (uint32_t)(std::upper_bound(row_off, row_off + R + 1, (uint32_t)(n * t / T)) - row_off - 1));
-        row_lo[T] = R;
-        off.assign((size_t)N + 1, 0);
-        std::vector<uint32_t> n_lo((size_t)N, 0); // partners below each row
-        std::vector<uint32_t> cur_lo_all, cur_up_all;
-        auto scan = [&](size_t t, bool fill) {
-            const uint32_t r0 = row_lo[t], r1 = row_lo[t + 1];
-            if (r0 >= r1) return;
-            const uint32_t rb = r0 > BAND ? r0 - BAND : 0;
-            std::vector<uint32_t> cur_lo, cur_up;
-            if (fill) {
-                cur_lo.assign(off.begin() + r0, off.begin() + r1);
-                cur_up.resize(r1 - r0);
-                for (uint32_t v = r0; v < r1; ++v) cur_up[v - r0] = off[v] + n_lo[v];
-            }
-            for (uint32_t a = rb; a < r1; ++a) {
-                const uint32_t i0 = row_off[a], i1 = row_off[a + 1];
-                if (i0 == i1) continue;
-                if (!fill && a >= r0 && !has_key(a)) bad_t[t] = 1;
-                const bool sa = skip && skip[a];
-                for (uint32_t i = i0; i < i1; ++i) {
-                    const uint32_t w = cp[i], b = a + 1 + (w & 255u);
-                    if (!fill && a >= r0 && !has_key(b)) bad_t[t] = 1;
-                    if (sa || b >= N || (skip && skip[b])) continue;
-                    if (b >= r0 && b < r1) { // a partner below row b
-                        if (fill) edges[cur_lo[b - r0]++] = Edge(a, gw(w));
-                        else ++n_lo[b];
-                    }
-                    if (a >= r0) { // a partner above row a
-                        if (fill) edges[cur_up[a - r0]++] = Edge(b, gw(w));
-                        else ++off[a + 1];
-                    }
-                }
-            }
-        };
-        auto run = [&](bool fill) { parallel_each(T, [&](size_t t) { scan(t, fill); }); };
-        run(false);
-        for (uint8_t b : bad_t)
-            if (b) return false;
-        for (uint32_t v = 0; v < N; ++v) off[v + 1] += off[v] + n_lo[v];
-        edges_resize(off[N]);
+    // The same rows delivered FINISHED by the vote kernels (k_vote_rows_emit) or by their serial restatement on the host
+    // (np2_vote_decide under NP2_VOTE_COMPACT): o[0 .. R] are the row offsets, e the directed edges, every row its partners
+    // below it (ascending), then those above it (ascending); the reads flagged bad and the edges pointing at one are
+    // already left out.  The offsets are copied; the edges are BORROWED: they stay where the caller keeps them (the
+    // read-back staging of the vote, or the vote's own copy), which has to outlive this graph.  A first-level graph is
+    // only read once it is built, and `edges` stays empty, so nothing of a borrowed array ever reaches retire().
+    void adopt_rows(const uint32_t *o, const Edge *e, uint32_t R) {
+        reserve_ids(R);
+        off.assign((size_t)n_ids() + 1, o[R]);
+        std::copy(o, o + (size_t)R + 1, off.begin());
+        edges.clear();
+        ext_ = e;
         rows_sorted = true;
-        run(true);
-        return true;
     }
+    bool borrowed() const { return ext_ != nullptr; }
+    size_t n_edges() const { return off.empty() ? 0 : off.back(); }
     // drop the rows of the flagged nodes and every edge pointing at one (row order is preserved)
     void drop_nodes(const uint8_t *bad) {
         const uint32_t N = n_ids();
@@ -590,6 +548,7 @@ struct Graph {
         is_key.assign(n, 0);
         off.assign((size_t)n + 1, 0);
         edges.clear();
+        ext_ = nullptr;
         rows_sorted = false;
         next_row_ = 0;
     }
@@ -602,6 +561,7 @@ struct Graph {
     }
 
   private:
+    const Edge *ext_ = nullptr; // adopt_rows: the rows live in the caller's array
     uint32_t next_row_ = 0;
 };
 
@@ -966,7 +926,7 @@ class SignedLouvain {
     std::vector<float> all_weights(const std::vector<uint32_t> &moff, const std::vector<uint32_t> &mlist) const {
         const size_t n = node_id_.size();
         std::vector<float> w(n, 0.f);
-        if (g_.edges.size() < (1u << 20) || host_threads() < 2) {
+        if (g_.n_edges() < (1u << 20) || host_threads() < 2) {
             for (uint32_t id = 0; id < n; ++id)
                 if (cnt_[id]) w[id] = weight_only(id, mlist.data() + moff[id], mlist.data() + moff[id + 1]);
             return w;
@@ -1017,7 +977,7 @@ class SignedLouvain {
     }
 
     void aggregate() { // second_stage, louvain.rs:119-195
-        const bool prof = getenv("NP2_PHASE_PROFILE") != nullptr && g_.edges.size() >= (1u << 20);
+        const bool prof = getenv("NP2_PHASE_PROFILE") != nullptr && g_.n_edges() >= (1u << 20);
         auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
         double t_m = now();
         auto mark = [&](const char *what) {
@@ -1104,7 +1064,7 @@ class SignedLouvain {
             std::vector<std::pair<uint32_t, uint32_t>> row; // (id, end offset in edges)
         };
         std::vector<Rows> part(host_threads());
-        parallel_ranges((size_t)max_id + 1, g_.edges.size() >= (1u << 20) ? 4096 : (size_t)max_id + 2,
+        parallel_ranges((size_t)max_id + 1, g_.n_edges() >= (1u << 20) ? 4096 : (size_t)max_id + 2,
                         [&](unsigned t, size_t lo, size_t hi) {
             Rows &out = part[t];
             std::vector<std::pair<uint32_t, float>> local;
@@ -1148,7 +1108,7 @@ class SignedLouvain {
         }
         ng.end_rows();
         mark("new graph");
-        if (g_.edges.size() >= (1u << 22)) Graph::retire(std::move(g_.edges)); // (kept for the next large vote: see Graph::Spare)
+        if (!g_.borrowed() && g_.edges.size() >= (1u << 22)) Graph::retire(std::move(g_.edges)); // (kept for the next large vote: see Graph::Spare)
         g_ = std::move(ng);
         comm_keys_ = std::move(ncomm);
         node_id_.assign(max_id + 1, 0);

@@ -404,35 +404,95 @@ __device__ __forceinline__ void k_band_emit(const uint32_t np2_bid, const uint32
         }
 }
 
-// the compact form the plain pipeline reads back (4 bytes per pair instead of 12: the pair list is the largest thing a
-// phasing pass sends over the bus): the rows keep their order, a row's read is implied by row_off
-__device__ __forceinline__ void k_band_emit_compact(const uint32_t np2_bid, const uint32_t np2_nb, const uint32_t *__restrict__ band, uint32_t R,
-                                                    const uint32_t *__restrict__ row_off, uint32_t *__restrict__ pairs,
-                                                    uint32_t *__restrict__ n_out, uint32_t *__restrict__ ovf) {
+// ---- the vote's adjacency rows, finished on the device ----------------------------------------------------------
+// What the plain pipeline reads back: the symmetric CSR rows the host's Louvain sweeps over (Graph::adopt_rows), so
+// that the host has nothing to build.  Row v = the partners of read v below it in ascending order, then those above
+// it in ascending order; an edge is {neighbour, f32 weight} with weight = -neg if neg >= 3, else same - neg
+// (main.rs:996-1002), from the unclipped 16-bit halves of the band word.  The partners above v are v's own band row,
+// those below it the column band[a * EDGE_BAND + (v - a - 1)] over the EDGE_BAND reads before v.  A band row is valid
+// only where row_n[a] != 0 (k_edges_row never writes the others: they hold whatever an earlier contig left).  Without
+// use_all a read flagged bad by k_vote_phase has an empty row and appears in none (data.retain, main.rs:1004-1010);
+// read 0, the contig itself, never enters a pair.
+// One wavefront per read, two kernels with the row-total scan between them; both decide with these two functions.
+__device__ __forceinline__ uint32_t vote_row_above(const uint32_t *__restrict__ band, const uint8_t *__restrict__ bad, uint32_t use_all,
+                                                   uint32_t R, uint32_t v, uint32_t d) { // (row_n[v] != 0) -> band word or 0
+    const uint32_t b = v + 1 + d;
+    if (b >= R) return 0;
+    const uint32_t w = band[(uint64_t)v * EDGE_BAND + d];
+    return (w != 0 && (use_all || !bad[b])) ? w : 0u;
+}
+__device__ __forceinline__ uint32_t vote_row_below(const uint32_t *__restrict__ band, const uint32_t *__restrict__ row_n,
+                                                   const uint8_t *__restrict__ bad, uint32_t use_all, uint32_t v, int64_t a) {
+    if (a < 1 || a >= (int64_t)v || v - (uint32_t)a > EDGE_BAND) return 0;
+    if (row_n[a] == 0 || (!use_all && bad[a])) return 0;
+    return band[(uint64_t)a * EDGE_BAND + (v - (uint32_t)a - 1)];
+}
+__device__ __forceinline__ float vote_weight(uint32_t w) {
+    const int32_t same = (int32_t)(w & 0xFFFFu), neg = (int32_t)(w >> 16);
+    return (float)(neg >= 3 ? -neg : same - neg);
+}
+// edges of every row (cnt[v]); the wave of read 0 clears the emitting kernel's key-check counter
+__device__ __forceinline__ void k_vote_rows_count(const uint32_t np2_bid, const uint32_t np2_nb, const uint32_t *__restrict__ band,
+                                                  const uint32_t *__restrict__ row_n, const uint8_t *__restrict__ bad, uint32_t use_all,
+                                                  uint32_t R, uint32_t *__restrict__ cnt, uint32_t *__restrict__ nokey) {
     const uint32_t lane = threadIdx.x & 63;
-    const uint32_t a = (uint32_t)__builtin_amdgcn_readfirstlane((int)((np2_bid * blockDim.x + threadIdx.x) >> 6)); // (uniform)
-    if (a >= R) return;
-    if (a == R - 1 && lane == 0) *n_out = row_off[R];
-    if (row_off[a + 1] == row_off[a]) return;
-    const uint4 w = *reinterpret_cast<const uint4 *>(band + (uint64_t)a * EDGE_BAND + lane * 4);
-    const uint32_t v[4] = {w.x, w.y, w.z, w.w};
-    const uint32_t c = (w.x != 0) + (w.y != 0) + (w.z != 0) + (w.w != 0);
-    uint32_t inc = c;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = __shfl_up(inc, o);
-        if (lane >= (uint32_t)o) inc += t;
-    }
-    uint32_t o = row_off[a] + inc - c;
-    bool big = false;
+    const uint32_t v = (uint32_t)__builtin_amdgcn_readfirstlane((int)((np2_bid * blockDim.x + threadIdx.x) >> 6)); // (uniform)
+    if (v >= R) return;
+    if (v == 0 && lane == 0) *nokey = 0;
+    uint32_t c = 0;
+    if (v != 0 && (use_all || !bad[v])) {
+        const bool own = row_n[v] != 0;
 #pragma unroll
-    for (uint32_t k = 0; k < 4; ++k)
-        if (v[k]) {
-            const uint32_t same = v[k] & 0xFFFFu, neg = v[k] >> 16;
-            big = big || same > VOTE_CNT_MAX || neg > VOTE_CNT_MAX;
-            pairs[o] = (lane * 4 + k) | ((same & VOTE_CNT_MAX) << 8) | ((neg & VOTE_CNT_MAX) << 20);
-            ++o;
+        for (uint32_t k = 0; k < EDGE_BAND / 64; ++k) {
+            const uint32_t d = k * 64 + lane;
+            if (own) c += vote_row_above(band, bad, use_all, R, v, d) != 0;
+            c += vote_row_below(band, row_n, bad, use_all, v, (int64_t)v - 1 - d) != 0;
         }
-    if (big) atomicAdd(ovf, 1u);
+    }
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+    if (lane == 0) cnt[v] = c;
+}
+// off = exclusive scan of cnt (off[R] = all edges, posted through *n_out); *nokey counts the pairs of the band with an
+// endpoint that never voted (first_reg == 0xFFFFFFFF: it has no key in the host's graph — an internal error there)
+__device__ __forceinline__ void k_vote_rows_emit(const uint32_t np2_bid, const uint32_t np2_nb, const uint32_t *__restrict__ band,
+                                                 const uint32_t *__restrict__ row_n, const uint8_t *__restrict__ bad, uint32_t use_all,
+                                                 const uint32_t *__restrict__ first_reg, uint32_t R, const uint32_t *__restrict__ off,
+                                                 uint2 *__restrict__ edges, uint32_t *__restrict__ n_out, uint32_t *__restrict__ nokey) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t v = (uint32_t)__builtin_amdgcn_readfirstlane((int)((np2_bid * blockDim.x + threadIdx.x) >> 6)); // (uniform)
+    if (v >= R) return;
+    if (v == R - 1 && lane == 0) *n_out = off[R];
+    if (v == 0) return;
+    const bool own = row_n[v] != 0, live = use_all || !bad[v];
+    const uint64_t lt = (1ull << lane) - 1;
+    uint32_t o = off[v];
+    const uint32_t end = off[v + 1]; // (count and emit decide alike: nothing is written past the row's end whatever happens)
+    if (live && end != o) {
+#pragma unroll
+        for (uint32_t k = 0; k < EDGE_BAND / 64; ++k) { // partners below, ascending
+            const int64_t a = (int64_t)v - EDGE_BAND + k * 64 + lane;
+            const uint32_t w = vote_row_below(band, row_n, bad, use_all, v, a);
+            const uint64_t m = __ballot(w != 0);
+            const uint32_t at = o + (uint32_t)__popcll(m & lt);
+            if (w != 0 && at < end) edges[at] = make_uint2((uint32_t)a, __float_as_uint(vote_weight(w)));
+            o += (uint32_t)__popcll(m);
+        }
+    }
+    if (!own) return;
+    const bool v_key = first_reg[v] != 0xFFFFFFFFu;
+    uint32_t nk = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < EDGE_BAND / 64; ++k) { // partners above, ascending
+        const uint32_t d = k * 64 + lane, b = v + 1 + d;
+        if (b < R && band[(uint64_t)v * EDGE_BAND + d] != 0 && !(v_key && first_reg[b] != 0xFFFFFFFFu)) ++nk;
+        const uint32_t w = live ? vote_row_above(band, bad, use_all, R, v, d) : 0u;
+        const uint64_t m = __ballot(w != 0);
+        const uint32_t at = o + (uint32_t)__popcll(m & lt);
+        if (w != 0 && at < end) edges[at] = make_uint2(b, __float_as_uint(vote_weight(w)));
+        o += (uint32_t)__popcll(m);
+    }
+    for (int x = 32; x > 0; x >>= 1) nk += __shfl_xor(nk, x);
+    if (nk && lane == 0) atomicAdd(nokey, nk);
 }
 
 // reduce sorted edges to per-pair counts: agreeing regions | disagreeing regions << 16
@@ -1149,9 +1209,13 @@ void launch_edges_row(hipStream_t s, const RegionTables &rt, const uint8_t *grp,
                       const uint32_t *pcount, const uint8_t *alive, uint32_t R, uint32_t *band, uint32_t *row_n, uint32_t *ovf) {
     if (R) NP2_LAUNCH(k_edges_row, g1((uint64_t)R * 64), 256, s, rt, grp, ecount, pj, pcount, alive, R, band, row_n, ovf);
 }
-void launch_band_emit_compact(hipStream_t s, const uint32_t *band, uint32_t R, const uint32_t *row_off, uint32_t *pairs,
-                              uint32_t *n_out, uint32_t *ovf) {
-    if (R) NP2_LAUNCH(k_band_emit_compact, g1((uint64_t)R * 64), 256, s, band, R, row_off, pairs, n_out, ovf);
+void launch_vote_rows_count(hipStream_t s, const uint32_t *band, const uint32_t *row_n, const uint8_t *bad, bool use_all, uint32_t R,
+                            uint32_t *cnt, uint32_t *nokey) {
+    if (R) NP2_LAUNCH(k_vote_rows_count, g1((uint64_t)R * 64), 256, s, band, row_n, bad, use_all ? 1u : 0u, R, cnt, nokey);
+}
+void launch_vote_rows_emit(hipStream_t s, const uint32_t *band, const uint32_t *row_n, const uint8_t *bad, bool use_all,
+                           const uint32_t *first_reg, uint32_t R, const uint32_t *off, void *edges, uint32_t *n_out, uint32_t *nokey) {
+    if (R) NP2_LAUNCH(k_vote_rows_emit, g1((uint64_t)R * 64), 256, s, band, row_n, bad, use_all ? 1u : 0u, first_reg, R, off, (uint2 *)edges, n_out, nokey);
 }
 void launch_band_emit(hipStream_t s, const uint32_t *band, uint32_t R, const uint32_t *row_off, uint64_t *ukey, uint32_t *uw,
                       uint32_t *n_out, uint64_t key_add) {
