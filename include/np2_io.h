@@ -308,6 +308,74 @@ int np2_rep_bytes(int device, const uint8_t *seq, uint64_t n, const np2_rep_opts
 int np2_rep_files(int device, const char *const *paths, int n_paths, const np2_rep_opts_t *opts, const char *out_path,
                   int both_strands, np2_rep_stats_t *stats);
 
+/* ---- the mapper's SAM, parsed and coordinate-sorted on the device (the reference's recipe: `| samtools sort -o ... ;
+ * samtools index ...`, which exist only so that an indexed reader can fetch one contig's records in coordinate order) -------
+ * THE RULE IS DEFINED HERE, on the SAM specification section 1.4 and on what samtools' coordinate comparison is understood to
+ * do; it is not pinned against the samtools binary.
+ *   Input: one or more files, plain or gzip, or a stream that cannot be read twice (path "-": standard input).  The bytes
+ *     are taken as they stand, in pieces that end at a line boundary (32 MiB; test hook NP2_SAM_TEST_PIECE, in bytes, read
+ *     once per call).  A line that does not fit an empty piece is NP2_E_UNSUPPORTED, naming the 1-based line.  A '\r' directly
+ *     before '\n' is dropped, a last line needs no newline, empty lines are skipped.
+ *   Header: the lines beginning with '@' before the first alignment line.  @SQ lines give the references in order (SN:, LN:);
+ *     other header lines are ignored.  NP2_E_ARG: an '@' line after the first alignment line, an @SQ line without SN or LN, a
+ *     duplicate SN, files that do not carry the same @SQ list.  The host reads the header.
+ *   Alignment line: at least 11 tab-separated fields (fewer: NP2_E_ARG naming the 1-based line).  Only FLAG, RNAME, POS, MAPQ,
+ *     CIGAR and SEQ are read.  FLAG decimal 0..65535; POS decimal 0..2^31-1, pos = POS - 1; MAPQ decimal 0..255; a non-digit
+ *     or an overflow in any of them is NP2_E_ARG.  RNAME "*" is tid -1, any other name must be an @SQ name (else NP2_E_ARG).
+ *     CIGAR "*" is n_cigar = 0, otherwise one or more of <decimal length below 2^28><one of MIDNSHP=X> (anything else:
+ *     NP2_E_ARG), the word len << 4 | op.  SEQ "*" is l_seq = 0, otherwise every byte maps through BAM's "=ACMGRSVTWYHKDBN"
+ *     in either case and any other byte to 15; packed 4 bits a base, high nibble first, every record starting at a byte
+ *     (np2_bamrec_t.seq_off).  QNAME, RNEXT, PNEXT, TLEN, QUAL and the optional fields are skipped and not validated.
+ *   Kept and dropped: a record with tid == -1 or flag & 0x4 is counted in stats.unmapped and not kept.
+ *   Order: the kept records ascending by (tid, pos + 1, s), s = (flag >> 4) & 1 with tie_by_strand (the samtools order) and 0
+ *     without.  Records equal in that key keep input order: file order, files in argument order.  The reference numbers reads
+ *     in file order (main.rs:1813), so this order is part of the result: with tie_by_strand = 0 a BAM whose ties are in input
+ *     order gives the same polish through either door.
+ *   Errors: the first offending line in input order speaks; the process stays usable.  Device memory that does not suffice
+ *     for the packed SEQ, the CIGAR words and the records (about half a byte per base and 40 bytes per record, twice the
+ *     records and words while they are sorted) is NP2_E_NOMEM, and the message says how much was needed.
+ * Messages: np2_io_last_error() on the calling thread (np2_contig_from_sam: also np2_last_error(ctx)). */
+typedef struct np2_sam_opts {
+    uint32_t tie_by_strand; /* 1 */
+} np2_sam_opts_t;
+typedef struct np2_sam_stats {
+    uint64_t lines;       /* lines read, header and empty ones included */
+    uint64_t records;     /* alignment lines */
+    uint64_t unmapped;    /* of them: tid == -1 or flag & 0x4 */
+    uint64_t kept;        /* records - unmapped */
+    uint64_t cigar_words; /* of the kept records */
+    uint64_t seq_bytes;   /* packed SEQ of the kept records */
+    float parse_ms;       /* k_sam_lines, k_sam_fields and the scans (HIP events, summed over the pieces) */
+    float pack_ms;        /* k_sam_pack */
+    float sort_ms;        /* the key sort and k_sam_gather */
+    float read_ms;        /* wall time the calling thread waited for its reader thread */
+} np2_sam_stats_t;
+typedef struct np2_sam np2_sam_t;
+/* Reads everything and leaves the sorted records, their CIGAR words and the packed SEQ resident on ctx's device (the work
+ * runs on ctx's stream).  opts == NULL: the defaults.  The arguments are checked and every file but "-" is opened once
+ * before the first device call: a NULL argument or a file that cannot be opened is NP2_E_ARG.  The handle is read-only
+ * afterwards: any number of threads may call np2_contig_from_sam on it, each with a context of its own on that device. */
+int np2_sam_open(np2_ctx_t *ctx, const char *const *paths, int n_paths, const np2_sam_opts_t *opts, np2_sam_t **out);
+void np2_sam_close(np2_sam_t *s);
+int np2_sam_n_refs(np2_sam_t *s);
+const char *np2_sam_ref_name(np2_sam_t *s, int tid, uint32_t *len);
+int np2_sam_stats(np2_sam_t *s, np2_sam_stats_t *stats);
+/* np2_contig_from_bam for a resident SAM: the host copies back the range of records and CIGAR words of reference `name`
+ * (binary search on the sorted keys) and the front end reads the SEQ bytes where they are.  use_secondary is
+ * NP2_E_UNSUPPORTED (a secondary record needs the SEQ of its read's primary record, found by name: use a BAM); a name the
+ * @SQ lines lack, a NULL argument or a context of another device is NP2_E_ARG.  These are checked before the first device call. */
+int np2_contig_from_sam(np2_ctx_t *ctx, np2_sam_t *sam, const char *name, const uint8_t *ref, uint32_t L,
+                        const np2_front_opts_t *opts, np2_contig_t **out);
+/* SAM text in host memory, header included -> the sorted records on the host, for parity tests and measurements: recs
+ * (cigar_off in sorted order, seq_off as the records were met in the text), tids, cigar (n_recs entries / stats.cigar_words
+ * words), seq4 (stats.seq_bytes bytes).  Release the four with np2_free; each is NULL when it would be empty.  stats may be
+ * NULL. */
+int np2_sam_parse_bytes(int device, const uint8_t *text, uint64_t n, const np2_sam_opts_t *opts, np2_bamrec_t **recs, int32_t **tids,
+                        uint32_t **cigar, uint8_t **seq4, uint64_t *n_recs, np2_sam_stats_t *stats);
+/* the same four arrays of a resident SAM copied back to the host (parity tests of np2_sam_open; np2_sam_stats has the sizes) */
+int np2_sam_export(np2_ctx_t *ctx, np2_sam_t *sam, np2_bamrec_t **recs, int32_t **tids, uint32_t **cigar, uint8_t **seq4,
+                   uint64_t *n_recs);
+
 #ifdef __cplusplus
 }
 #endif

@@ -135,6 +135,20 @@ def write_bam(path, refs, records):
         f.write(out)
 
 
+def write_sam(path, refs, records, gz=False):
+    """The text twin of write_bam: the same record dicts, in the order given (no order is asked of them), as SAM text with
+    an @SQ line per reference, RNEXT "*", PNEXT 0, TLEN 0 and QUAL "*"; gz=True writes gzip.  For tests and examples."""
+    import gzip
+    out = [b"@HD\tVN:1.6\tSO:unsorted\n"] + [b"@SQ\tSN:%s\tLN:%d\n" % (n.encode(), l) for n, l in refs]
+    for i, r in enumerate(records):
+        seq = r["seq"].encode("latin-1") if isinstance(r["seq"], str) else bytes(r["seq"])
+        out.append(b"%s\t%d\t%s\t%d\t%d\t%s\t*\t0\t0\t%s\t*\n" % (
+            r.get("name", b"r%d" % i), r.get("flag", 0), refs[r["tid"]][0].encode() if r["tid"] >= 0 else b"*", r["pos"] + 1,
+            r.get("mapq", 60), "".join("%d%s" % (l, op) for op, l in r["cigar"]).encode() or b"*", seq or b"*"))
+    with (gzip.open(path, "wb", compresslevel=1) if gz else open(path, "wb")) as f:
+        f.write(b"".join(out))
+
+
 def write_bam_raw(path, refs, contigs, level=1, threads=16):
     """Whole-assembly BAM + .bai from already encoded alignment records (Synth.bam_records): contigs = per reference
     sequence, in order, (blob, record offsets, positions, reference lengths).  Records are packed into BGZF blocks of

@@ -1,8 +1,9 @@
 """nextPolish2 command line mirror (src/utils/option.rs:45-292, src/main.rs:1689-1856).
 
-Usage: nextPolish2 [OPTIONS] <HiFi.map.bam> <genome.fa[.gz]> <short.read.yak>...
+Usage: nextPolish2 [OPTIONS] <HiFi.map.bam|HiFi.map.sam[.gz]|-> <genome.fa[.gz]> <short.read.yak>...
 Same positionals, flags, defaults and output format as the reference; contigs are polished on the GPU and written in
-input order.  `-t N` (N >= 2) keeps two front ends (BGZF inflate + record walk on the host pool or the device, GPU
+input order.  The first positional may also be the mapper's SAM text, unsorted (plain or gzip, any name; `-` is standard
+input): it is parsed and coordinate-sorted on the GPU (io.Sam), so no samtools sort / index step is needed.  `-t N` (N >= 2) keeps two front ends (BGZF inflate + record walk on the host pool or the device, GPU
 columnariser) and two polish workers going side by side; a worker polishes the contigs that are resident by its turn as
 ONE batch (np2_batch_polish: one launch per pipeline step for all of them), and the host-side phases of one batch (the
 phasing vote's Louvain) overlap the GPU phases of the other; the k-mer dumps are streamed into their HBM tables next to
@@ -31,6 +32,10 @@ def _existing(path):
     return p
 
 
+def _existing_or_stdin(path):
+    return path if path == "-" else _existing(path)
+
+
 def _map_len(v):
     """-a INT.FLOAT parsed as f32 like the reference (option.rs:232 remove_one::<f32>)."""
     return np.float32(v)
@@ -45,7 +50,10 @@ def split_map_len(v):
 
 def build_parser():
     p = argparse.ArgumentParser(prog="nextPolish2", description="Repeat-aware polishing genomes assembled using HiFi long reads")
-    p.add_argument("bam", type=_existing, metavar="HiFi.map.bam", help="HiFi-to-ref mapping file in sorted BAM format")
+    p.add_argument("bam", type=_existing_or_stdin, metavar="HiFi.map.bam",
+                   help="HiFi-to-ref mapping file in sorted BAM format, or the mapper's SAM text, unsorted ([GZIP]; - is standard input)")
+    p.add_argument("--sam_tie", choices=np2io.SAM_TIES, default="strand",
+                   help="SAM input: records at one position are ordered by strand, as samtools sort orders them, or stay in input order [strand]")
     p.add_argument("fa", type=_existing, metavar="genome.fa[.gz]", help="genome assembly file in [GZIP] FASTA format")
     p.add_argument("yak", type=_existing, nargs="*", metavar="short.read.yak", help="one or more k-mer dataset in yak format")
     p.add_argument("--sr", type=_existing, action="append", default=[], metavar="FILE",
@@ -349,6 +357,14 @@ def main(argv=None):
         parser.error("--trio thresholds: 1 <= --trio_min_count <= --trio_mid_count <= 1023")
     if a.model.lower() not in ("ref", "len"):
         raise SystemExit("error: invalid value for --model (ref|len)")
+    try:  # (a look at the file's first bytes; standard input cannot be looked at twice and is SAM text)
+        a.sam = a.bam == "-" or np2io.mapping_kind(a.bam) == "sam"
+    except (ValueError, OSError) as e:
+        raise SystemExit(f"Error: {e}")
+    if a.sam and a.use_secondary:
+        raise SystemExit("Error: -S needs the SEQ of a read's primary record, which is found by name: not with SAM input, use a sorted BAM")
+    if a.sam and int(os.environ.get("WORLD_SIZE", "1")) > 1 and "RANK" in os.environ:
+        raise SystemExit("Error: SAM input runs on one rank: interval sharding reads the .bai of a sorted BAM")
     for y in a.yak:  # (before the output file exists: a broken dump must not leave a partial output behind)
         try:
             np2io.check_yak_header(y)
@@ -441,8 +457,40 @@ def main(argv=None):
             print(f"[np2 profile] k-mer dumps read + tables in HBM {time.time() - t_b:.3f} s (at +{time.time() - t0:.3f} s)", file=sys.stderr)
         return pol
 
+    sam_pool, sam_future, sam_lock = ThreadPoolExecutor(max_workers=1), [], threading.Lock()
+
+    def open_sam():
+        """the SAM text parsed and sorted on the device, resident for every front-end thread (np2_sam_open), on a table-less
+        context of its own"""
+        t_s = time.time()
+        spol = Polisher([], device=a.device)
+        try:
+            sam = np2io.Sam(spol, [a.bam], tie=a.sam_tie)
+        except BaseException:
+            spol.close()
+            raise
+        if prof:
+            print(f"[np2 profile] SAM parsed and sorted {time.time() - t_s:.3f} s: {sam.stats()} (at +{time.time() - t0:.3f} s)", file=sys.stderr)
+        return spol, sam
+
+    def front_sam(name, seq):
+        """the contig's pileup from the resident SAM (np2_contig_from_sam), on this thread's table-less context"""
+        with sam_lock:
+            if not sam_future:
+                sam_future.append(sam_pool.submit(open_sam))
+        sam = sam_future[0].result()[1]
+        if getattr(tls, "fpol", None) is None:
+            tls.fpol = Polisher([], device=a.device)
+        t_f = time.time()
+        c = np2io.contig_from_sam(tls.fpol, sam, name, seq, fopts)
+        if prof:
+            print(f"[np2 profile] {name}: front end {1e3 * (time.time() - t_f):.1f} ms (done at +{time.time() - t0:.3f} s)", file=sys.stderr)
+        return c
+
     def front(name, seq):
         """the contig's pileup, resident in HBM (np2_contig_from_bam) — on this thread's table-less context"""
+        if a.sam:
+            return front_sam(name, seq)
         if getattr(tls, "fpol", None) is None:
             t_c = time.time()
             tls.fpol = Polisher([], device=a.device)
@@ -662,6 +710,11 @@ def main(argv=None):
             for q in tpol:
                 q.close()
         yak_pool.shutdown(wait=False)
+        sam_pool.shutdown(wait=True)
+        if sam_future and sam_future[0].exception() is None:  # (after the front ends: nothing reads the resident SAM any more)
+            spol, sam = sam_future[0].result()
+            sam.close()
+            spol.close()
         if out is not None and out is not sys.stdout.buffer:
             out.close()
     print(resource_str(t0, ["nextPolish2"] + argv, cpu0), file=sys.stderr)

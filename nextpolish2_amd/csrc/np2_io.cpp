@@ -28,6 +28,7 @@
 #include "np2_inflate.hpp"
 #include "np2_inflate_core.hpp"
 #include "np2_kcount.hpp"
+#include "np2_sam.hpp"
 namespace {
 
 // Raw-deflate decoder for BGZF blocks (each block is one complete deflate stream of known inflated size): libdeflate's
@@ -1352,6 +1353,16 @@ void fetch_records(np2_bam *bam, int tid, uint32_t L, uint32_t zone_lo, uint32_t
 }
 
 } // namespace
+
+// the front end for the SAM reader (np2_sam_host.cpp): its SEQ bytes are resident, its records and CIGAR words come from the host
+namespace np2h {
+void contig_from_device_seq(np2_ctx *cx, const uint8_t *ref, uint32_t L, const np2_bamrec_t *recs, uint32_t n_recs, const uint32_t *cigar,
+                            const uint8_t *d_seq4, uint64_t seq4_bytes, const np2_front_opts_t *opts, np2_contig **out) {
+    FrontWork fw;
+    front_begin(cx, ref, L, recs, n_recs, cigar, nullptr, n_recs ? seq4_bytes : 0, opts, nullptr, fw, n_recs ? d_seq4 : nullptr);
+    front_finish(cx, fw, out);
+}
+} // namespace np2h
 
 // NP2_SEGV_TRACE=1: print the native stack of a crashing thread (field debugging; off by default)
 #include <execinfo.h>

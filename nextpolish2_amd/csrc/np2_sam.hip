@@ -1,0 +1,236 @@
+// SAM text -> alignment records, CIGAR words and packed SEQ on the device (include/np2_io.h: np2_sam_*; the per-lane rule is
+// np2_sam_core.hpp).  A piece of the text ends at a line boundary and is gone after three kernels:
+//
+//   k_sam_lines   16 text bytes a lane: the '\n' bytes are counted, the block scan and the decoupled look-back
+//                 (np2_blockscan.hpp, np2_lookback.hpp) give the first one its ordinal, the offsets go out in order.
+//                 1 byte read per byte of text.
+//   k_sam_fields  a wavefront per line: 256 bytes a step, a ballot per 64 finds the first ten tabs; lanes 0 - 3 read FLAG,
+//                 RNAME (through the @SQ name table), POS and MAPQ; the lanes stride over the CIGAR field, judge every byte
+//                 and count the operation letters.  The optional fields and QUAL are not read: the walk ends at the tenth tab.
+//   k_sam_pack    after the scans placed the kept records: a wavefront per kept line writes the record (ten words, one a
+//                 lane), the CIGAR words (a lane that owns an operation letter reads the digits in front of it; its rank among
+//                 the letters comes from the ballot) and the SEQ nibbles (two bases a lane a step, byte stores next to each other).
+//
+// After the last piece the keys are sorted with the record ordinals as values (rocPRIM, np2_prims.hip: stable) and
+//   k_sam_gather  a wavefront per record moves the record and its CIGAR words into sorted order; SEQ bytes stay where they are.
+// Plain vector stores throughout; integer atomics only on the piece's three counters.
+#include "np2_sam.hpp"
+#include "np2_blockscan.hpp"
+
+namespace np2 {
+
+namespace {
+using np2sam::Line;
+using np2sam::NameTab;
+
+__device__ __forceinline__ uint64_t lanes_below() { return (1ull << (threadIdx.x & 63u)) - 1ull; }
+
+__global__ __launch_bounds__(SAM_BLOCK) void k_sam_lines(Lookback lb, const uint8_t *__restrict__ text, uint32_t n,
+                                                          uint32_t *__restrict__ line_end, SamCtr *__restrict__ ctr) {
+    __shared__ uint32_t sh[16];
+    const uint32_t bid = lb_block_id(lb, sh);
+    const uint32_t i0 = bid * SAM_TILE + threadIdx.x * SAM_STRETCH;
+    uint32_t nl = 0; // bit k: text[i0 + k] is a '\n' of the piece
+    if (i0 < n) {    // (the 16 bytes lie inside n + SAM_TEXT_PAD)
+        const uint4 q = *reinterpret_cast<const uint4 *>(text + i0);
+        const uint32_t w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+        for (uint32_t k = 0; k < SAM_STRETCH; ++k)
+            if (((w[k >> 2] >> (8u * (k & 3u))) & 255u) == (uint32_t)'\n' && i0 + k < n) nl |= 1u << k;
+    }
+    uint32_t total, pre, unused;
+    uint32_t rank = block_excl_scan<OpAdd, SAM_BLOCK / 64>((uint32_t)__builtin_popcount(nl), sh, total);
+    lb_exclusive2(lb, bid, total, 0u, sh, &ctr->err, pre, unused);
+    rank += pre; // lines that end before i0: at most n of them, and line_end has room for n
+    while (nl) {
+        line_end[rank++] = i0 + (uint32_t)__builtin_ctz(nl);
+        nl &= nl - 1u;
+    }
+    if (bid == lb.n_blocks - 1 && threadIdx.x == 0) ctr->n_lines = pre + total;
+}
+
+__global__ __launch_bounds__(SAM_BLOCK) void k_sam_fields(const uint8_t *__restrict__ text, const uint32_t *__restrict__ line_end,
+                                                           uint32_t n_lines, NameTab nt, Line *__restrict__ lines, uint32_t *__restrict__ kept,
+                                                           uint32_t *__restrict__ n_cig, uint32_t *__restrict__ n_seq, SamCtr *__restrict__ ctr) {
+    const uint32_t r = (blockIdx.x * SAM_BLOCK + threadIdx.x) >> 6, lane = threadIdx.x & 63u;
+    if (r == n_lines && lane == 0) kept[r] = n_cig[r] = n_seq[r] = 0u; // the scans' closing entries
+    if (r >= n_lines) return;                                          // (uniform across the wavefront)
+    const uint32_t s = r ? line_end[r - 1] + 1u : 0u;
+    uint32_t e = line_end[r];
+    if (e > s && text[e - 1] == (uint8_t)'\r') --e;
+    Line ln;
+    ln.cig_a = ln.cig_b = ln.seq_a = ln.l_seq = 0, ln.tid = np2sam::TID_NONE, ln.pos = -1, ln.n_cigar = 0, ln.flag = 0, ln.mapq = 0, ln.err = np2sam::OK;
+    if (e == s) {
+        ln.tid = np2sam::TID_EMPTY_LINE;
+    } else if (text[s] == (uint8_t)'@') {
+        ln.err = np2sam::E_HEADER_LATE;
+    } else {
+        // lane k keeps the offset of tab k
+        uint32_t n_tab = 0, my_tab = 0;
+        for (uint32_t c = s; c < e && n_tab < np2sam::N_TABS; c += 256u) {
+            uint8_t b[4];
+#pragma unroll
+            for (uint32_t u = 0; u < 4; ++u) b[u] = c + 64u * u + lane < e ? text[c + 64u * u + lane] : (uint8_t)0;
+#pragma unroll
+            for (uint32_t u = 0; u < 4; ++u) {
+                uint64_t m = __ballot(b[u] == (uint8_t)'\t');
+                while (m && n_tab < np2sam::N_TABS) {
+                    if (lane == n_tab) my_tab = c + 64u * u + (uint32_t)__builtin_ctzll(m);
+                    ++n_tab;
+                    m &= m - 1ull;
+                }
+            }
+        }
+        if (n_tab < np2sam::N_TABS) {
+            ln.err = np2sam::E_FIELDS;
+        } else {
+            const uint32_t t0 = __shfl(my_tab, 0), t1 = __shfl(my_tab, 1), t2 = __shfl(my_tab, 2), t3 = __shfl(my_tab, 3),
+                           t4 = __shfl(my_tab, 4), t5 = __shfl(my_tab, 5), t8 = __shfl(my_tab, 8), t9 = __shfl(my_tab, 9);
+            uint32_t val = 0, err = np2sam::OK; // lane 0: FLAG, 1: tid, 2: pos, 3: MAPQ
+            if (lane == 0) err = np2sam::parse_flag(text, t0 + 1u, t1, &val);
+            if (lane == 1) {
+                int32_t tid = 0;
+                err = np2sam::parse_rname(nt, text, t1 + 1u, t2, &tid);
+                val = (uint32_t)tid;
+            }
+            if (lane == 2) {
+                int32_t pos = 0;
+                err = np2sam::parse_pos(text, t2 + 1u, t3, &pos);
+                val = (uint32_t)pos;
+            }
+            if (lane == 3) err = np2sam::parse_mapq(text, t3 + 1u, t4, &val);
+            ln.flag = (uint16_t)__shfl(val, 0), ln.tid = (int32_t)__shfl(val, 1), ln.pos = (int32_t)__shfl(val, 2), ln.mapq = (uint8_t)__shfl(val, 3);
+            ln.cig_a = t4 + 1u, ln.cig_b = t5;
+            uint32_t cnt = 0;
+            if (ln.cig_b == ln.cig_a) {
+                if (lane == 4) err = np2sam::E_CIGAR;
+            } else if (!(ln.cig_b - ln.cig_a == 1u && text[ln.cig_a] == (uint8_t)'*')) {
+                for (uint32_t i = ln.cig_a + lane; i < ln.cig_b; i += 64u) {
+                    uint32_t w;
+                    const uint32_t k = np2sam::cigar_byte(text, ln.cig_a, ln.cig_b, i, &w);
+                    if (k == 2u) err = np2sam::first_err(err, np2sam::E_CIGAR);
+                    cnt += k == 1u ? 1u : 0u;
+                }
+            }
+            for (int o = 32; o > 0; o >>= 1) {
+                cnt += __shfl_xor(cnt, o);
+                err = np2sam::first_err(err, (uint32_t)__shfl_xor(err, o));
+            }
+            ln.n_cigar = cnt, ln.err = (uint8_t)err;
+            ln.seq_a = t8 + 1u;
+            ln.l_seq = t9 - ln.seq_a == 1u && text[ln.seq_a] == (uint8_t)'*' ? 0u : t9 - ln.seq_a;
+        }
+    }
+    if (lane == 0) {
+        const bool k = np2sam::line_kept(ln);
+        lines[r] = ln;
+        kept[r] = k ? 1u : 0u, n_cig[r] = k ? ln.n_cigar : 0u, n_seq[r] = k ? (ln.l_seq + 1u) / 2u : 0u;
+        if (ln.err != np2sam::OK) atomicMin(&ctr->first_err, r);
+        if (ln.tid == np2sam::TID_EMPTY_LINE) atomicAdd(&ctr->n_empty, 1u);
+    }
+}
+
+__global__ __launch_bounds__(SAM_BLOCK) void k_sam_pack(const uint8_t *__restrict__ text, const Line *__restrict__ lines, uint32_t n_lines,
+                                                         const uint32_t *__restrict__ kept_off, const uint32_t *__restrict__ cig_off,
+                                                         const uint32_t *__restrict__ seq_off, uint64_t rec_base, uint64_t cig_base, uint64_t seq_base,
+                                                         uint32_t tie_by_strand, uint32_t *__restrict__ recs, int32_t *__restrict__ tids,
+                                                         uint64_t *__restrict__ keys, uint32_t *__restrict__ cigar, uint8_t *__restrict__ seq4) {
+    const uint32_t r = (blockIdx.x * SAM_BLOCK + threadIdx.x) >> 6, lane = threadIdx.x & 63u;
+    if (r >= n_lines) return; // (uniform across the wavefront, as is the next one)
+    const Line ln = lines[r];
+    if (!np2sam::line_kept(ln)) return;
+    const uint64_t k = rec_base + kept_off[r], co = cig_base + cig_off[r], so = seq_base + seq_off[r];
+    if (lane < SAM_REC_WORDS) { // np2_bamrec_t, padding included
+        const uint32_t w[SAM_REC_WORDS] = {(uint32_t)ln.pos, (uint32_t)ln.flag | (uint32_t)ln.mapq << 16, ln.n_cigar, 0u,
+                                           (uint32_t)co, (uint32_t)(co >> 32), ln.l_seq, 0u, (uint32_t)so, (uint32_t)(so >> 32)};
+        uint32_t v = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < SAM_REC_WORDS; ++j) v = lane == j ? w[j] : v;
+        recs[k * SAM_REC_WORDS + lane] = v;
+    }
+    if (lane == 0) {
+        tids[k] = ln.tid;
+        keys[k] = np2sam::sort_key(ln.tid, ln.pos, ln.flag, tie_by_strand);
+    }
+    if (ln.n_cigar) { // letters before this chunk + letters of lower lanes: below n_cigar, what k_sam_fields counted
+        uint32_t done = 0;
+        for (uint32_t c = ln.cig_a; c < ln.cig_b; c += 64u) {
+            const uint32_t i = c + lane;
+            uint32_t w = 0;
+            const bool is_op = i < ln.cig_b && np2sam::cigar_byte(text, ln.cig_a, ln.cig_b, i, &w) == 1u;
+            const uint64_t m = __ballot(is_op);
+            if (is_op) cigar[co + done + (uint32_t)__popcll(m & lanes_below())] = w;
+            done += (uint32_t)__popcll(m);
+        }
+    }
+    const uint32_t n_bytes = (ln.l_seq + 1u) / 2u;
+    for (uint32_t j = lane; j < n_bytes; j += 64u) { // seq_a + 2 j + 1 < seq_a + l_seq: inside the line
+        const uint32_t hi = np2sam::base_code(text[ln.seq_a + 2u * j]);
+        const uint32_t lo = 2u * j + 1u < ln.l_seq ? np2sam::base_code(text[ln.seq_a + 2u * j + 1u]) : 0u;
+        seq4[so + j] = (uint8_t)(hi << 4 | lo);
+    }
+}
+
+__global__ __launch_bounds__(SAM_BLOCK) void k_sam_iota(uint32_t *__restrict__ vals, uint32_t n) {
+    const uint32_t i = blockIdx.x * SAM_BLOCK + threadIdx.x;
+    if (i < n) vals[i] = i;
+}
+
+__global__ __launch_bounds__(SAM_BLOCK) void k_sam_sorted_sizes(const uint32_t *__restrict__ recs_in, const uint32_t *__restrict__ order, uint32_t n,
+                                                                 uint32_t *__restrict__ n_cig) {
+    const uint32_t i = blockIdx.x * SAM_BLOCK + threadIdx.x;
+    if (i < n) n_cig[i] = recs_in[(uint64_t)order[i] * SAM_REC_WORDS + 2u]; // (order holds each of 0 .. n - 1 once)
+    if (i == n) n_cig[i] = 0u;
+}
+
+__global__ __launch_bounds__(SAM_BLOCK) void k_sam_gather(const uint32_t *__restrict__ recs_in, const int32_t *__restrict__ tids_in,
+                                                           const uint32_t *__restrict__ cigar_in, const uint32_t *__restrict__ order,
+                                                           const uint32_t *__restrict__ cig_off, uint32_t n, uint32_t *__restrict__ recs,
+                                                           int32_t *__restrict__ tids, uint32_t *__restrict__ cigar) {
+    const uint32_t r = (blockIdx.x * SAM_BLOCK + threadIdx.x) >> 6, lane = threadIdx.x & 63u;
+    if (r >= n) return; // (uniform across the wavefront)
+    const uint64_t src = order[r];
+    const uint32_t *in = recs_in + src * SAM_REC_WORDS;
+    const uint32_t n_cigar = in[2];
+    const uint64_t from = (uint64_t)in[4] | (uint64_t)in[5] << 32, to = cig_off[r];
+    if (lane < SAM_REC_WORDS) {
+        uint32_t v = in[lane];
+        if (lane == 4) v = (uint32_t)to;
+        if (lane == 5) v = 0u;
+        recs[(uint64_t)r * SAM_REC_WORDS + lane] = v;
+    }
+    if (lane == 0) tids[r] = tids_in[src];
+    for (uint32_t j = lane; j < n_cigar; j += 64u) cigar[to + j] = cigar_in[from + j];
+}
+
+inline dim3 wave_grid(uint64_t waves) { return dim3((uint32_t)((waves * 64u + SAM_BLOCK - 1) / SAM_BLOCK)); }
+
+} // namespace
+
+void launch_sam_lines(hipStream_t s, const Lookback &lb, const uint8_t *text, uint32_t n, uint32_t *line_end, SamCtr *ctr) {
+    if (n) hipLaunchKernelGGL(k_sam_lines, dim3(sam_line_blocks(n)), dim3(SAM_BLOCK), 0, s, lb, text, n, line_end, ctr);
+}
+void launch_sam_fields(hipStream_t s, const uint8_t *text, const uint32_t *line_end, uint32_t n_lines, np2sam::NameTab nt,
+                       np2sam::Line *lines, uint32_t *kept, uint32_t *n_cig, uint32_t *n_seq, SamCtr *ctr) {
+    hipLaunchKernelGGL(k_sam_fields, wave_grid((uint64_t)n_lines + 1), dim3(SAM_BLOCK), 0, s, text, line_end, n_lines, nt, lines, kept, n_cig,
+                       n_seq, ctr);
+}
+void launch_sam_pack(hipStream_t s, const uint8_t *text, const np2sam::Line *lines, uint32_t n_lines, const uint32_t *kept_off,
+                     const uint32_t *cig_off, const uint32_t *seq_off, uint64_t rec_base, uint64_t cig_base, uint64_t seq_base,
+                     uint32_t tie_by_strand, uint32_t *recs, int32_t *tids, uint64_t *keys, uint32_t *cigar, uint8_t *seq4) {
+    if (n_lines)
+        hipLaunchKernelGGL(k_sam_pack, wave_grid(n_lines), dim3(SAM_BLOCK), 0, s, text, lines, n_lines, kept_off, cig_off, seq_off, rec_base,
+                           cig_base, seq_base, tie_by_strand, recs, tids, keys, cigar, seq4);
+}
+void launch_sam_iota(hipStream_t s, uint32_t *vals, uint32_t n) {
+    if (n) hipLaunchKernelGGL(k_sam_iota, dim3((n + SAM_BLOCK - 1) / SAM_BLOCK), dim3(SAM_BLOCK), 0, s, vals, n);
+}
+void launch_sam_sorted_sizes(hipStream_t s, const uint32_t *recs_in, const uint32_t *order, uint32_t n, uint32_t *n_cig) {
+    hipLaunchKernelGGL(k_sam_sorted_sizes, dim3(n / SAM_BLOCK + 1), dim3(SAM_BLOCK), 0, s, recs_in, order, n, n_cig);
+}
+void launch_sam_gather(hipStream_t s, const uint32_t *recs_in, const int32_t *tids_in, const uint32_t *cigar_in, const uint32_t *order,
+                       const uint32_t *cig_off, uint32_t n, uint32_t *recs, int32_t *tids, uint32_t *cigar) {
+    if (n) hipLaunchKernelGGL(k_sam_gather, wave_grid(n), dim3(SAM_BLOCK), 0, s, recs_in, tids_in, cigar_in, order, cig_off, n, recs, tids, cigar);
+}
+
+} // namespace np2

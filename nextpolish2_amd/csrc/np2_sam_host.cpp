@@ -1,0 +1,665 @@
+// Host driver of the SAM reader (include/np2_io.h: np2_sam_*; kernels: np2_sam.hip).
+//
+// A reader thread takes the bytes of the files as they stand (zlib's gzread: plain and gzip alike, "-" is standard input)
+// into pinned pieces that end at a line boundary, reads the header lines of each file on the way and hands the rest over;
+// the calling thread copies a piece to the device, finds its lines, judges them, asks for the three totals, grows the resident
+// buffers where they are short (a larger block and a device-to-device copy, after a look at the free memory) and packs.
+// After the last piece: keys -> stable sort -> records and CIGAR words gathered into sorted order.  The sorted keys come
+// back to the host once; a contig's range is a binary search in them.
+#include "../../include/np2_io.h"
+#include "np2_ctx.hpp"
+#include "np2_kcount.hpp"
+#include "np2_sam.hpp"
+
+#include <zlib.h>
+#include <unistd.h>
+
+#include <condition_variable>
+#include <deque>
+#include <functional>
+#include <thread>
+
+struct np2_sam {
+    int device = 0;
+    np2sam::Refs refs;
+    // resident: records and tids in sorted order, their CIGAR words in that order, SEQ bytes as they were met
+    DevBuf<uint32_t> recs; // SAM_REC_WORDS words a record
+    DevBuf<int32_t> tids;
+    DevBuf<uint32_t> cigar;
+    DevBuf<uint8_t> seq4;
+    uint64_t n_recs = 0, n_cigar = 0, seq_bytes = 0;
+    std::vector<uint64_t> keys; // sorted
+    np2_sam_stats_t stats{};
+    np2_sam() { recs.cached = tids.cached = cigar.cached = seq4.cached = true; } // (released when nothing reads them any more)
+    ~np2_sam() { (void)hipSetDevice(device); }
+};
+
+namespace {
+using np2h::Np2Error;
+
+struct Hooks {
+    size_t piece = (size_t)32 << 20;
+    bool profile = false; // NP2_SAM_PROFILE: one line on stderr with the kernels' times apart (tools/sam_probe.py)
+    Hooks() { // read once per call, like the other NP2_* switches
+        if (const char *e = getenv("NP2_SAM_TEST_PIECE")) piece = (size_t)std::min<long long>(1ll << 30, std::max<long long>(64, atoll(e)));
+        profile = getenv("NP2_SAM_PROFILE") != nullptr;
+    }
+};
+
+// where the bytes come from: a file (plain or gzip), standard input, or host memory
+struct Source {
+    gzFile f = nullptr;
+    const uint8_t *mem = nullptr;
+    size_t mem_n = 0, mem_at = 0;
+    std::string name;
+    ~Source() {
+        if (f) gzclose(f);
+    }
+    void open(const std::string &path) {
+        name = path == "-" ? "standard input" : path;
+        f = path == "-" ? gzdopen(dup(0), "rb") : gzopen(path.c_str(), "rb");
+        if (!f) throw Np2Error(NP2_E_ARG, "cannot open " + name);
+        gzbuffer(f, 1 << 20);
+    }
+    size_t read(uint8_t *dst, size_t n) { // 0: the end
+        if (!f) {
+            const size_t take = std::min(n, mem_n - mem_at);
+            if (take) memcpy(dst, mem + mem_at, take);
+            mem_at += take;
+            return take;
+        }
+        const int got = gzread(f, dst, (unsigned)std::min<size_t>(n, (size_t)1 << 30));
+        int zerr = Z_OK;
+        const char *zmsg = gzerror(f, &zerr);
+        if (got < 0 || (zerr != Z_OK && zerr != Z_STREAM_END))
+            throw Np2Error(NP2_E_ARG, name + ": cannot read the SAM text (" + (zmsg && *zmsg ? zmsg : "damaged or truncated gzip") + ")");
+        return (size_t)got;
+    }
+};
+
+struct Piece {
+    int buf = -1;
+    size_t off = 0, n = 0;  // the alignment lines of the piece: bytes [off, off + n) of its buffer, ending with '\n'
+    int file = 0;
+    uint64_t first_line = 0; // 1-based number, in its file, of the line at `off`
+};
+
+// the reader thread: pieces in input order through a two-buffer queue
+struct Reader {
+    const Hooks &hooks;
+    std::vector<std::string> paths; // empty: `mem`
+    const uint8_t *mem = nullptr;
+    size_t mem_n = 0;
+    static constexpr int NBUF = 2;
+    np2h::PinnedBuf pinned[NBUF];
+    uint8_t *pin[NBUF] = {nullptr, nullptr};
+    size_t piece = 0;
+
+    std::mutex mu;
+    std::condition_variable cv;
+    std::deque<Piece> ready;
+    std::vector<int> idle;
+    bool done = false, stop = false;
+    int err_code = 0;
+    std::string err_msg;
+    np2sam::Refs refs; // of the first file, set before its first piece is handed over
+    bool have_refs = false;
+    uint64_t lines = 0; // of all files, when done
+    std::thread th;
+
+    explicit Reader(const Hooks &h) : hooks(h) {}
+    ~Reader() {
+        {
+            std::lock_guard<std::mutex> l(mu);
+            stop = true;
+        }
+        cv.notify_all();
+        if (th.joinable()) th.join();
+    }
+    void start(size_t bytes_bound) { // bytes_bound: what the input can hold at most, 0 when that is not known
+        piece = hooks.piece;
+        if (bytes_bound) piece = std::min(piece, std::max<size_t>(bytes_bound + 1, 64));
+        for (int b = 0; b < NBUF; ++b) {
+            pin[b] = (uint8_t *)pinned[b].ensure(piece + 64);
+            idle.push_back(b);
+        }
+        th = std::thread([this] { run(); });
+    }
+    int acquire() {
+        std::unique_lock<std::mutex> l(mu);
+        cv.wait(l, [&] { return stop || !idle.empty(); });
+        if (stop) return -1;
+        const int b = idle.back();
+        idle.pop_back();
+        return b;
+    }
+    void release(int b) {
+        {
+            std::lock_guard<std::mutex> l(mu);
+            idle.push_back(b);
+        }
+        cv.notify_all();
+    }
+    // the calling thread: the next piece (false: the input is through, or the reader failed: see err_code)
+    bool next(Piece &p) {
+        std::unique_lock<std::mutex> l(mu);
+        cv.wait(l, [&] { return done || !ready.empty(); });
+        if (ready.empty()) return false;
+        p = ready.front();
+        ready.pop_front();
+        return true;
+    }
+    void file_refs(const np2sam::Refs &r, const std::string &name) {
+        std::lock_guard<std::mutex> l(mu);
+        if (!have_refs) {
+            refs = r, have_refs = true;
+        } else if (!(refs == r)) {
+            throw Np2Error(NP2_E_ARG, name + ": its @SQ lines differ from those of the first file");
+        }
+    }
+    void one_file(Source &src, int file) {
+        np2sam::Refs r;
+        bool in_header = true, refs_done = false, eof = false;
+        uint64_t line_no = 0; // lines of this file handed over or read as header
+        std::vector<uint8_t> carry;
+        while (!eof) {
+            const int b = acquire();
+            if (b < 0) return;
+            uint8_t *buf = pin[b];
+            size_t fill = carry.size();
+            if (fill) memcpy(buf, carry.data(), fill);
+            carry.clear();
+            while (fill < piece && !eof) {
+                const size_t got = src.read(buf + fill, piece - fill);
+                eof = got == 0;
+                fill += got;
+            }
+            if (eof && fill && buf[fill - 1] != '\n') buf[fill++] = '\n'; // (the buffers hold piece + 64 bytes)
+            size_t cut = fill;
+            while (cut && buf[cut - 1] != '\n') --cut;
+            if (fill && !cut) {
+                release(b);
+                throw Np2Error(NP2_E_UNSUPPORTED, src.name + ": line " + std::to_string(line_no + 1) + " does not fit a piece of " +
+                                                      std::to_string(piece) + " bytes");
+            }
+            carry.assign(buf + cut, buf + fill);
+            size_t at = 0;
+            while (in_header && at < cut) {
+                const size_t nl = (const uint8_t *)memchr(buf + at, '\n', cut - at) - buf;
+                const size_t end = nl > at && buf[nl - 1] == '\r' ? nl - 1 : nl;
+                if (end > at && buf[at] != '@') {
+                    in_header = false;
+                    break;
+                }
+                if (end > at) {
+                    const std::string bad = np2sam::header_line(buf, at, end, r);
+                    if (!bad.empty()) {
+                        release(b);
+                        throw Np2Error(NP2_E_ARG, src.name + ": line " + std::to_string(line_no + 1) + ": " + bad);
+                    }
+                }
+                at = nl + 1, ++line_no;
+            }
+            if (!refs_done && (!in_header || eof)) { // the header is through
+                try {
+                    file_refs(r, src.name);
+                } catch (...) {
+                    release(b);
+                    throw;
+                }
+                refs_done = true;
+            }
+            if (at < cut) {
+                Piece p;
+                p.buf = b, p.off = at, p.n = cut - at, p.file = file, p.first_line = line_no + 1;
+                line_no += (uint64_t)std::count(buf + at, buf + cut, (uint8_t)'\n');
+                {
+                    std::lock_guard<std::mutex> l(mu);
+                    ready.push_back(p);
+                }
+                cv.notify_all();
+            } else {
+                release(b);
+            }
+        }
+        std::lock_guard<std::mutex> l(mu);
+        lines += line_no;
+    }
+    void run() {
+        try {
+            if (paths.empty()) {
+                Source src;
+                src.mem = mem, src.mem_n = mem_n, src.name = "the text";
+                one_file(src, 0);
+            }
+            for (size_t i = 0; i < paths.size(); ++i) {
+                Source src;
+                src.open(paths[i]);
+                one_file(src, (int)i);
+            }
+        } catch (...) {
+            std::lock_guard<std::mutex> l(mu);
+            np2h::current_error(err_code, err_msg);
+        }
+        {
+            std::lock_guard<std::mutex> l(mu);
+            done = true;
+        }
+        cv.notify_all();
+    }
+};
+
+struct Event {
+    hipEvent_t e = nullptr;
+    ~Event() {
+        if (e) (void)hipEventDestroy(e);
+    }
+    void make() { HIPCHK(hipEventCreate(&e)); }
+};
+float elapsed(const Event &a, const Event &b) {
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, a.e, b.e));
+    return ms;
+}
+
+// room for `bytes` more on the device, or NP2_E_NOMEM saying how much was needed
+void need_device(size_t bytes, const char *what) {
+    const size_t margin = (size_t)64 << 20;
+    size_t fr = 0, tot = 0;
+    HIPCHK(hipMemGetInfo(&fr, &tot));
+    if (bytes + margin > fr) {
+        np2h::dev_cache().trim(0); // (this process's idle blocks may be what is missing)
+        HIPCHK(hipMemGetInfo(&fr, &tot));
+    }
+    if (bytes + margin > fr)
+        throw Np2Error(NP2_E_NOMEM, std::string("the SAM's ") + what + " need a block of " + std::to_string(bytes) +
+                                        " bytes, and the device has " + std::to_string(fr) + " bytes free: the packed SEQ, the CIGAR words and "
+                                        "the records of a SAM input must fit one device's memory");
+}
+template <class T> void take_over(DevBuf<T> &a, DevBuf<T> &b) { // a <- b's block, b <- a's
+    std::swap(a.p, b.p), std::swap(a.cap, b.cap), std::swap(a.cached, b.cached), std::swap(a.cache_bytes, b.cache_bytes),
+        std::swap(a.slab_bytes, b.slab_bytes);
+}
+// `b` holds `used` elements and gets room for `need`: a larger block and a device-to-device copy, as SeqStream::push grows
+template <class T> void grow(DevBuf<T> &b, size_t used, size_t need, hipStream_t st, const char *what) {
+    if (need <= b.cap) return;
+    const size_t want = std::max(need, b.cap + b.cap / 2);
+    need_device((want + want / 8 + 64) * sizeof(T), what);
+    DevBuf<T> nb;
+    nb.cached = true;
+    nb.ensure(want);
+    if (used) HIPCHK(hipMemcpyAsync(nb.p, b.p, used * sizeof(T), hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipStreamSynchronize(st)); // (the old block goes back to the cache: nothing may still read it)
+    take_over(b, nb);
+}
+
+// text -> the handle's resident arrays
+struct Build {
+    np2_ctx *cx;
+    np2_sam &sam;
+    Hooks hooks;
+    uint32_t tie = 1;
+    hipStream_t st;
+    // input order, while the pieces come in
+    DevBuf<uint32_t> recs_in, cigar_in;
+    DevBuf<int32_t> tids_in;
+    DevBuf<uint64_t> keys_in;
+    uint64_t n_recs = 0, n_cigar = 0, seq_bytes = 0, n_records = 0;
+    // one piece
+    DevBuf<uint8_t> d_text, d_tmp;
+    DevBuf<uint32_t> d_end, d_kept, d_ncig, d_nseq, d_koff, d_coff, d_soff;
+    DevBuf<np2sam::Line> d_lines;
+    DevBuf<np2::SamCtr> d_ctr;
+    // the name table
+    DevBuf<uint32_t> d_slot, d_noff;
+    DevBuf<uint8_t> d_names;
+    np2sam::NameTab nt{};
+    bool have_nt = false;
+    np2h::PinnedBuf pin;
+    Event e0, e1, e_mid;
+    float lines_ms = 0;    // k_sam_lines alone, of parse_ms
+    uint64_t text_bytes = 0;
+
+    Build(np2_ctx *c, np2_sam &s) : cx(c), sam(s), st(c->stream) {
+        recs_in.cached = cigar_in.cached = tids_in.cached = keys_in.cached = true; // (every release below follows a drained stream)
+        d_text.cached = d_tmp.cached = d_end.cached = d_kept.cached = d_ncig.cached = d_nseq.cached = d_koff.cached = d_coff.cached = true;
+        d_soff.cached = d_lines.cached = d_ctr.cached = d_slot.cached = d_noff.cached = d_names.cached = true;
+        e0.make(), e1.make(), e_mid.make();
+    }
+    ~Build() { (void)hipStreamSynchronize(st); }
+
+    void name_table(const np2sam::Refs &refs) {
+        const np2sam::NameTabHost h(refs);
+        d_slot.ensure(h.slot.size()), d_noff.ensure(h.off.size()), d_names.ensure(h.names.size());
+        HIPCHK(hipMemcpyAsync(d_slot.p, h.slot.data(), h.slot.size() * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_noff.p, h.off.data(), h.off.size() * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_names.p, h.names.data(), h.names.size(), hipMemcpyHostToDevice, st));
+        HIPCHK(hipStreamSynchronize(st)); // (pageable sources: `h` goes away)
+        nt = np2sam::NameTab{d_slot.p, d_noff.p, d_names.p, h.mask};
+        have_nt = true;
+    }
+
+    // one piece: `text` (pinned) holds n bytes of whole lines; `where` names the file, first_line its first line
+    void piece(const uint8_t *text, size_t n, const std::string &where, uint64_t first_line, const std::function<void()> &text_copied) {
+        if (n >= (1ull << 31)) throw Np2Error(NP2_E_UNSUPPORTED, "a piece of SAM text of 2 GiB or more");
+        d_text.ensure(n + np2::SAM_TEXT_PAD);
+        d_end.ensure(n);
+        d_ctr.ensure(1);
+        np2::SamCtr *h = (np2::SamCtr *)pin.ensure(256); // the counters, the three totals, the offending line
+        uint32_t *h_tot = (uint32_t *)(h + 1);
+        h->n_lines = 0, h->first_err = 0xFFFFFFFFu, h->n_empty = 0, h->err = 0;
+        HIPCHK(hipMemcpyAsync(d_ctr.p, h, sizeof *h, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_text.p, text, n, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemsetAsync(d_text.p + n, 0, np2::SAM_TEXT_PAD, st));
+        Lookback lb = np2h::next_lookback(cx, np2::sam_line_blocks(n)); // (the first one of a context fills its status words on the stream)
+        lb.err = &d_ctr.p->err;
+        HIPCHK(hipEventRecord(e0.e, st));
+        try {
+            np2::launch_sam_lines(st, lb, d_text.p, (uint32_t)n, d_end.p, d_ctr.p);
+            HIPCHK(hipGetLastError());
+        } catch (...) { // (tickets were issued for a launch that may not have run: the next descriptor starts over)
+            cx->lb_dirty = true;
+            throw;
+        }
+        HIPCHK(hipEventRecord(e_mid.e, st));
+        HIPCHK(hipMemcpyAsync(h, d_ctr.p, sizeof *h, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        const float ms_lines = elapsed(e0, e_mid);
+        lines_ms += ms_lines, text_bytes += n;
+        text_copied(); // the pinned buffer goes back to the reader
+        if (h->err) throw Np2Error(NP2_E_DEVICE, "np2_sam: a look-back wait gave up");
+        const uint32_t n_lines = h->n_lines;
+        if (n_lines == 0 || n_lines > n) throw Np2Error(NP2_E_DEVICE, "np2_sam: line counter out of range");
+        const size_t m = (size_t)n_lines + 1;
+        d_lines.ensure(m), d_kept.ensure(m), d_ncig.ensure(m), d_nseq.ensure(m), d_koff.ensure(m), d_coff.ensure(m), d_soff.ensure(m);
+        const size_t tmp_bytes = np2::prim_temp_bytes(m);
+        d_tmp.ensure(tmp_bytes);
+        HIPCHK(hipEventRecord(e0.e, st)); // (the stream was idle while the host read the line count)
+        np2::launch_sam_fields(st, d_text.p, d_end.p, n_lines, nt, d_lines.p, d_kept.p, d_ncig.p, d_nseq.p, d_ctr.p);
+        if (np2::prim_exclusive_sum_u32(st, d_tmp.p, tmp_bytes, d_kept.p, d_koff.p, m) ||
+            np2::prim_exclusive_sum_u32(st, d_tmp.p, tmp_bytes, d_ncig.p, d_coff.p, m) ||
+            np2::prim_exclusive_sum_u32(st, d_tmp.p, tmp_bytes, d_nseq.p, d_soff.p, m))
+            throw Np2Error(NP2_E_DEVICE, "rocprim exclusive_scan failed");
+        HIPCHK(hipEventRecord(e1.e, st));
+        HIPCHK(hipMemcpyAsync(h, d_ctr.p, sizeof *h, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(h_tot + 0, d_koff.p + n_lines, 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(h_tot + 1, d_coff.p + n_lines, 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(h_tot + 2, d_soff.p + n_lines, 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipGetLastError());
+        sam.stats.parse_ms += ms_lines + elapsed(e0, e1);
+        if (h->first_err != 0xFFFFFFFFu) { // the first offending line of the first offending piece
+            if (h->first_err >= n_lines) throw Np2Error(NP2_E_DEVICE, "np2_sam: error line out of range");
+            np2sam::Line *bad = (np2sam::Line *)(h_tot + 4);
+            HIPCHK(hipMemcpyAsync(bad, d_lines.p + h->first_err, sizeof *bad, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            throw Np2Error(NP2_E_ARG, where + ": line " + std::to_string(first_line + h->first_err) + ": " + np2sam::err_text(bad->err));
+        }
+        const uint64_t kept = h_tot[0], n_cig = h_tot[1], n_seq = h_tot[2];
+        if (h->n_empty > n_lines || kept > n_lines - h->n_empty) throw Np2Error(NP2_E_DEVICE, "np2_sam: record counters out of range");
+        n_records += n_lines - h->n_empty;
+        if (n_recs + kept >= (1ull << 31)) throw Np2Error(NP2_E_UNSUPPORTED, "a SAM input of 2^31 alignment records or more");
+        if (n_cigar + n_cig >= 0xFFFF0000ull) throw Np2Error(NP2_E_UNSUPPORTED, "a SAM input of more than 4294901760 CIGAR operations");
+        if (kept) {
+            grow(recs_in, n_recs * np2::SAM_REC_WORDS, (n_recs + kept) * np2::SAM_REC_WORDS, st, "records");
+            grow(tids_in, n_recs, n_recs + kept, st, "records");
+            grow(keys_in, n_recs, n_recs + kept, st, "sort keys");
+            grow(cigar_in, n_cigar, n_cigar + n_cig + 1, st, "CIGAR words");
+            grow(sam.seq4, seq_bytes, seq_bytes + n_seq + 16, st, "packed SEQ");
+            HIPCHK(hipEventRecord(e0.e, st));
+            np2::launch_sam_pack(st, d_text.p, d_lines.p, n_lines, d_koff.p, d_coff.p, d_soff.p, n_recs, n_cigar, seq_bytes, tie, recs_in.p,
+                                 tids_in.p, keys_in.p, cigar_in.p, sam.seq4.p);
+            HIPCHK(hipEventRecord(e1.e, st));
+            HIPCHK(hipStreamSynchronize(st));
+            HIPCHK(hipGetLastError());
+            sam.stats.pack_ms += elapsed(e0, e1);
+        }
+        n_recs += kept, n_cigar += n_cig, seq_bytes += n_seq;
+    }
+
+    // after the last piece: input order -> sorted order
+    void finish() {
+        const uint32_t n = (uint32_t)n_recs;
+        sam.n_recs = n_recs, sam.n_cigar = n_cigar, sam.seq_bytes = seq_bytes;
+        sam.stats.records = n_records, sam.stats.kept = n_recs, sam.stats.unmapped = n_records - n_recs;
+        sam.stats.cigar_words = n_cigar, sam.stats.seq_bytes = seq_bytes;
+        if (seq_bytes) HIPCHK(hipMemsetAsync(sam.seq4.p + seq_bytes, 0, 16, st)); // (what records_to_arrays appends, for a reader of 16-byte words)
+        if (n == 0) {
+            HIPCHK(hipStreamSynchronize(st));
+            return;
+        }
+        const size_t tmp_bytes = np2::prim_temp_bytes((size_t)n + 1);
+        need_device((size_t)n * (8 + 4 + 4 + 4 + 4 + 4 + 40) + (n_cigar + 1) * 4 + tmp_bytes, "sorted records and CIGAR words");
+        DevBuf<uint64_t> keys_out;
+        DevBuf<uint32_t> vals_in, vals_out, sizes, offs;
+        keys_out.cached = vals_in.cached = vals_out.cached = sizes.cached = offs.cached = true; // (released after the last synchronisation below)
+        keys_out.ensure(n), vals_in.ensure(n), vals_out.ensure(n), sizes.ensure((size_t)n + 1), offs.ensure((size_t)n + 1);
+        d_tmp.ensure(tmp_bytes);
+        sam.recs.ensure((size_t)n * np2::SAM_REC_WORDS), sam.tids.ensure(n), sam.cigar.ensure(n_cigar + 1);
+        HIPCHK(hipEventRecord(e0.e, st));
+        np2::launch_sam_iota(st, vals_in.p, n);
+        if (np2::prim_sort_pairs_u64_u32(st, d_tmp.p, tmp_bytes, keys_in.p, keys_out.p, vals_in.p, vals_out.p, n, 64))
+            throw Np2Error(NP2_E_DEVICE, "rocprim radix_sort_pairs failed");
+        np2::launch_sam_sorted_sizes(st, recs_in.p, vals_out.p, n, sizes.p);
+        if (np2::prim_exclusive_sum_u32(st, d_tmp.p, tmp_bytes, sizes.p, offs.p, (size_t)n + 1))
+            throw Np2Error(NP2_E_DEVICE, "rocprim exclusive_scan failed");
+        np2::launch_sam_gather(st, recs_in.p, tids_in.p, cigar_in.p, vals_out.p, offs.p, n, sam.recs.p, sam.tids.p, sam.cigar.p);
+        HIPCHK(hipEventRecord(e1.e, st));
+        sam.keys.resize(n);
+        HIPCHK(hipMemcpyAsync(sam.keys.data(), keys_out.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipGetLastError());
+        sam.stats.sort_ms = elapsed(e0, e1);
+    }
+    void report() const {
+        if (!hooks.profile) return;
+        fprintf(stderr, "np2_sam: %llu bytes of alignment lines: k_sam_lines %.3f ms, k_sam_fields + scans %.3f ms, k_sam_pack %.3f ms, sort + k_sam_gather %.3f ms, waited for the reader %.3f ms\n",
+                (unsigned long long)text_bytes, lines_ms, sam.stats.parse_ms - lines_ms, sam.stats.pack_ms, sam.stats.sort_ms, sam.stats.read_ms);
+    }
+};
+
+// everything: `rd` has its source set and has not been started
+void build(np2_ctx *cx, np2_sam &sam, Reader &rd, const np2_sam_opts_t *opts, size_t bytes_bound) {
+    HIPCHK(hipSetDevice(cx->device));
+    sam.device = cx->device;
+    Build b(cx, sam);
+    b.tie = opts ? (opts->tie_by_strand ? 1u : 0u) : 1u;
+    rd.start(bytes_bound);
+    Piece p;
+    for (;;) {
+        const double t0 = np2h::now_ms();
+        const bool got = rd.next(p);
+        sam.stats.read_ms += (float)(np2h::now_ms() - t0);
+        if (!got) break;
+        if (!b.have_nt) {
+            std::lock_guard<std::mutex> l(rd.mu);
+            sam.refs = rd.refs;
+        }
+        if (!b.have_nt) b.name_table(sam.refs);
+        const std::string where = rd.paths.empty() ? "the text" : rd.paths[p.file] == "-" ? "standard input" : rd.paths[p.file];
+        bool back = false;
+        try {
+            b.piece(rd.pin[p.buf] + p.off, p.n, where, p.first_line, [&] { rd.release(p.buf), back = true; });
+        } catch (...) {
+            if (!back) {
+                (void)hipStreamSynchronize(cx->stream); // (the copy out of the pinned buffer may be in flight)
+                rd.release(p.buf);
+            }
+            throw;
+        }
+    }
+    {
+        std::lock_guard<std::mutex> l(rd.mu);
+        if (rd.err_code) throw Np2Error(rd.err_code, rd.err_msg);
+        sam.refs = rd.refs;
+        sam.stats.lines = rd.lines;
+    }
+    b.finish();
+    b.report();
+}
+
+// the resident arrays copied back into malloc'ed blocks (np2_free); an error returns none
+void export_arrays(hipStream_t st, const np2_sam &sam, np2_bamrec_t **recs, int32_t **tids, uint32_t **cigar, uint8_t **seq4, uint64_t *n_recs) {
+    void *h[4] = {nullptr, nullptr, nullptr, nullptr};
+    const void *d[4] = {sam.recs.p, sam.tids.p, sam.cigar.p, sam.seq4.p};
+    const size_t bytes[4] = {(size_t)sam.n_recs * sizeof(np2_bamrec_t), (size_t)sam.n_recs * 4, (size_t)sam.n_cigar * 4, (size_t)sam.seq_bytes};
+    try {
+        for (int i = 0; i < 4; ++i) {
+            if (!bytes[i]) continue;
+            h[i] = malloc(bytes[i]);
+            if (!h[i]) throw Np2Error(NP2_E_NOMEM, "out of memory for the parsed records");
+            HIPCHK(hipMemcpyAsync(h[i], d[i], bytes[i], hipMemcpyDeviceToHost, st));
+        }
+        HIPCHK(hipStreamSynchronize(st));
+    } catch (...) {
+        (void)hipStreamSynchronize(st);
+        for (void *p : h) free(p);
+        throw;
+    }
+    *recs = (np2_bamrec_t *)h[0], *tids = (int32_t *)h[1], *cigar = (uint32_t *)h[2], *seq4 = (uint8_t *)h[3];
+    *n_recs = sam.n_recs;
+}
+
+int ref_tid(const np2_sam *s, const char *name) {
+    for (size_t i = 0; i < s->refs.names.size(); ++i)
+        if (s->refs.names[i] == name) return (int)i;
+    return -1;
+}
+
+} // namespace
+
+extern "C" {
+
+int np2_sam_open(np2_ctx_t *cx, const char *const *paths, int n_paths, const np2_sam_opts_t *opts, np2_sam_t **out) {
+    if (out) *out = nullptr;
+    bool touched = false;
+    return np2h::abi_guard([&] {
+        // the arguments and the files, before the first device call
+        if (!cx || !out || !paths || n_paths < 1) throw Np2Error(NP2_E_ARG, "np2_sam_open: NULL argument or no path");
+        Hooks hooks;
+        Reader rd(hooks);
+        int n_stdin = 0;
+        for (int i = 0; i < n_paths; ++i) {
+            if (!paths[i]) throw Np2Error(NP2_E_ARG, "np2_sam_open: a path is NULL");
+            rd.paths.push_back(paths[i]);
+            if (rd.paths.back() == "-") {
+                if (++n_stdin > 1) throw Np2Error(NP2_E_ARG, "np2_sam_open: standard input is given twice");
+                continue;
+            }
+            FILE *f = fopen(paths[i], "rb");
+            if (!f) throw Np2Error(NP2_E_ARG, std::string("cannot open ") + paths[i]);
+            fclose(f);
+        }
+        touched = true;
+        std::unique_ptr<np2_sam> sam(new np2_sam());
+        build(cx, *sam, rd, opts, 0);
+        *out = sam.release();
+        return NP2_OK;
+    }, [&](int code, const std::string &msg) {
+        if (touched) {
+            (void)hipStreamSynchronize(cx->stream);
+            cx->err = msg;
+        }
+        np2h::io_set_error(code, msg);
+    });
+}
+
+void np2_sam_close(np2_sam_t *s) {
+    if (!s) return;
+    (void)hipSetDevice(s->device);
+    delete s;
+}
+int np2_sam_n_refs(np2_sam_t *s) { return s ? (int)s->refs.names.size() : 0; }
+const char *np2_sam_ref_name(np2_sam_t *s, int tid, uint32_t *len) {
+    if (!s || tid < 0 || (size_t)tid >= s->refs.names.size()) return nullptr;
+    if (len) *len = s->refs.lens[tid];
+    return s->refs.names[tid].c_str();
+}
+int np2_sam_stats(np2_sam_t *s, np2_sam_stats_t *stats) {
+    if (!s || !stats) return NP2_E_ARG;
+    *stats = s->stats;
+    return NP2_OK;
+}
+
+int np2_contig_from_sam(np2_ctx_t *cx, np2_sam_t *sam, const char *name, const uint8_t *ref, uint32_t L, const np2_front_opts_t *opts,
+                        np2_contig_t **out) {
+    if (out) *out = nullptr;
+    bool touched = false;
+    return np2h::abi_guard([&] {
+        // checked before anything of the context or the handle is looked at
+        if (!cx || !sam || !name || !ref || !opts || !out) throw Np2Error(NP2_E_ARG, "np2_contig_from_sam: NULL argument");
+        if (opts->use_secondary)
+            throw Np2Error(NP2_E_UNSUPPORTED, "np2_contig_from_sam: a secondary record takes the SEQ of its read's primary record, which is "
+                                              "found by name: use a BAM for -S");
+        const int tid = ref_tid(sam, name);
+        if (tid < 0) throw Np2Error(NP2_E_ARG, std::string("the SAM header has no @SQ line for ") + name);
+        if (cx->device != sam->device) throw Np2Error(NP2_E_ARG, "np2_contig_from_sam: the context is on another device than the SAM");
+        touched = true;
+        HIPCHK(hipSetDevice(cx->device));
+        const uint64_t lo = (uint64_t)tid << 33, hi = (uint64_t)(tid + 1) << 33;
+        const size_t a = std::lower_bound(sam->keys.begin(), sam->keys.end(), lo) - sam->keys.begin();
+        const size_t b = std::lower_bound(sam->keys.begin(), sam->keys.end(), hi) - sam->keys.begin();
+        std::vector<np2_bamrec_t> recs(b - a);
+        std::vector<uint32_t> cigar;
+        if (b > a) {
+            const std::vector<uint32_t> words = np2h::d2h(cx, sam->recs.p + a * np2::SAM_REC_WORDS, (b - a) * np2::SAM_REC_WORDS);
+            memcpy((void *)recs.data(), words.data(), words.size() * 4);
+            const uint64_t c0 = recs.front().cigar_off, c1 = recs.back().cigar_off + recs.back().n_cigar;
+            if (c1 < c0 || c1 > sam->n_cigar) throw Np2Error(NP2_E_DEVICE, "np2_sam: CIGAR offsets out of range");
+            cigar = np2h::d2h(cx, sam->cigar.p + c0, c1 - c0);
+            for (np2_bamrec_t &r : recs) r.cigar_off -= c0;
+        }
+        cigar.push_back(0); // (never a NULL array)
+        np2h::contig_from_device_seq(cx, ref, L, recs.data(), (uint32_t)recs.size(), cigar.data(), sam->seq4.p, sam->seq_bytes, opts, out);
+        np2h::flush_timings(cx);
+        return NP2_OK;
+    }, [&](int code, const std::string &msg) {
+        if (touched) {
+            (void)hipStreamSynchronize(cx->stream);
+            np2h::flush_timings(cx);
+            cx->err = msg;
+        }
+        np2h::io_set_error(code, msg);
+    });
+}
+
+int np2_sam_parse_bytes(int device, const uint8_t *text, uint64_t n, const np2_sam_opts_t *opts, np2_bamrec_t **recs, int32_t **tids,
+                        uint32_t **cigar, uint8_t **seq4, uint64_t *n_recs, np2_sam_stats_t *stats) {
+    np2_ctx_t *cx = nullptr;
+    const int rc = np2h::abi_guard([&] {
+        if (!recs || !tids || !cigar || !seq4 || !n_recs || (n && !text)) throw Np2Error(NP2_E_ARG, "np2_sam_parse_bytes: NULL argument");
+        *recs = nullptr, *tids = nullptr, *cigar = nullptr, *seq4 = nullptr, *n_recs = 0;
+        if (np2_ctx_create(&cx, device, nullptr, 0) != NP2_OK) throw Np2Error(NP2_E_DEVICE, "np2_sam_parse_bytes: no context on that device");
+        Hooks hooks;
+        Reader rd(hooks);
+        rd.mem = text, rd.mem_n = n;
+        np2_sam sam;
+        build(cx, sam, rd, opts, n);
+        export_arrays(cx->stream, sam, recs, tids, cigar, seq4, n_recs);
+        if (stats) *stats = sam.stats;
+        return NP2_OK;
+    }, [&](int code, const std::string &msg) {
+        if (cx) (void)hipStreamSynchronize(cx->stream);
+        np2h::io_set_error(code, msg);
+    });
+    if (cx) np2_ctx_destroy(cx);
+    return rc;
+}
+
+int np2_sam_export(np2_ctx_t *cx, np2_sam_t *sam, np2_bamrec_t **recs, int32_t **tids, uint32_t **cigar, uint8_t **seq4, uint64_t *n_recs) {
+    bool touched = false;
+    return np2h::abi_guard([&] {
+        if (!cx || !sam || !recs || !tids || !cigar || !seq4 || !n_recs) throw Np2Error(NP2_E_ARG, "np2_sam_export: NULL argument");
+        *recs = nullptr, *tids = nullptr, *cigar = nullptr, *seq4 = nullptr, *n_recs = 0;
+        if (cx->device != sam->device) throw Np2Error(NP2_E_ARG, "np2_sam_export: the context is on another device than the SAM");
+        touched = true;
+        HIPCHK(hipSetDevice(cx->device));
+        export_arrays(cx->stream, *sam, recs, tids, cigar, seq4, n_recs);
+        return NP2_OK;
+    }, [&](int code, const std::string &msg) {
+        if (touched) cx->err = msg;
+        np2h::io_set_error(code, msg);
+    });
+}
+
+} // extern "C"

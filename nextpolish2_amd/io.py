@@ -18,7 +18,8 @@ IO_SYMBOLS = ["np2_fasta_open", "np2_fasta_next", "np2_fasta_close", "np2_yak_lo
               "np2_kcount_files", "np2_kcount_bytes", "np2_kcount_files_to_dumps", "np2_ctx_create_from_reads", "np2_kcount_last_stats",
               "np2_seqfile_stream", "np2_bin_files", "np2_seqfile_reads", "np2_depth_from_records", "np2_depth_from_bam",
               "np2_srqc_bytes", "np2_srqc_files", "np2_srqc_last_stats", "np2_srqc_last_kernel_ms", "np2_kcount_files_qc",
-              "np2_kcount_files_to_dumps_qc", "np2_ctx_create_from_reads_qc", "np2_seqfile_stream_qual"]
+              "np2_kcount_files_to_dumps_qc", "np2_ctx_create_from_reads_qc", "np2_seqfile_stream_qual", "np2_sam_open", "np2_sam_close",
+              "np2_sam_n_refs", "np2_sam_ref_name", "np2_sam_stats", "np2_contig_from_sam", "np2_sam_parse_bytes", "np2_sam_export"]
 
 
 class np2_front_opts_t(C.Structure):
@@ -33,6 +34,15 @@ class np2_kcount_opts_t(C.Structure):
 
 class np2_bin_out_t(C.Structure):
     _fields_ = [("tsv", C.c_char_p), ("pat_list", C.c_char_p), ("mat_list", C.c_char_p), ("pat_fa", C.c_char_p), ("mat_fa", C.c_char_p)]
+
+
+class np2_sam_opts_t(C.Structure):
+    _fields_ = [("tie_by_strand", C.c_uint32)]
+
+
+class np2_sam_stats_t(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("lines", "records", "unmapped", "kept", "cigar_words", "seq_bytes")] + \
+               [(n, C.c_float) for n in ("parse_ms", "pack_ms", "sort_ms", "read_ms")]
 
 
 class FrontOpts:
@@ -171,6 +181,7 @@ def _bind_locked(L):
         L.np2_crc32_device.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, vp, C.POINTER(C.c_float)]
         _bind_shard(L)
         _bind_kcount(L)
+        _bind_sam(L)
 
 
 def _bind_shard(L):
@@ -180,6 +191,21 @@ def _bind_shard(L):
     L.np2_shard_bam_finish.argtypes = [vp, vp, C.c_uint64, C.POINTER(np2_shard_plan_t), C.POINTER(vp), C.POINTER(C.c_uint32)]
     L.np2_shard_bam_abort.argtypes = [vp]
     L.np2_shard_bam_abort.restype = None
+
+
+def _bind_sam(L):
+    vp, so, ss = C.c_void_p, C.POINTER(np2_sam_opts_t), C.POINTER(np2_sam_stats_t)
+    L.np2_sam_open.argtypes = [vp, C.POINTER(C.c_char_p), C.c_int, so, C.POINTER(vp)]
+    L.np2_sam_close.argtypes = [vp]
+    L.np2_sam_close.restype = None
+    L.np2_sam_n_refs.argtypes = [vp]
+    L.np2_sam_ref_name.restype = C.c_char_p
+    L.np2_sam_ref_name.argtypes = [vp, C.c_int, C.POINTER(C.c_uint32)]
+    L.np2_sam_stats.argtypes = [vp, ss]
+    L.np2_contig_from_sam.argtypes = [vp, vp, C.c_char_p, vp, C.c_uint32, C.POINTER(np2_front_opts_t), C.POINTER(vp)]
+    L.np2_sam_parse_bytes.argtypes = [C.c_int, vp, C.c_uint64, so, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
+                                      C.POINTER(C.c_uint64), ss]
+    L.np2_sam_export.argtypes = [vp, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_uint64)]
 
 
 def _bind_kcount(L):
@@ -499,6 +525,119 @@ class Bam:
             self.close()
         except Exception:
             pass
+
+
+SAM_TIES = ("strand", "input")
+
+
+def _sam_opts(tie):
+    if tie not in SAM_TIES:
+        raise ValueError(f"tie must be one of {' '.join(SAM_TIES)}, not {tie!r}")
+    return np2_sam_opts_t(1 if tie == "strand" else 0)
+
+
+def _sam_stats_dict(st):
+    return {n: (int if t is C.c_uint64 else float)(getattr(st, n)) for n, t in np2_sam_stats_t._fields_}
+
+
+class Sam:
+    """np2_sam_open: the mapper's SAM text (one or more files, plain or gzip; "-" is standard input) parsed and
+    coordinate-sorted on the device of Polisher `pol`, the sorted records, their CIGAR words and the packed SEQ left resident
+    there (include/np2_io.h has the rule).  tie: "strand" orders records at one position by strand, as samtools sort does;
+    "input" leaves them in input order.  Read-only once open: contig_from_sam may be called from several threads, each with
+    a Polisher of its own on that device."""
+
+    def __init__(self, pol, paths, tie="strand"):
+        L = _bind()
+        o = _sam_opts(tie)
+        arr, n = _paths(paths)
+        self._h = C.c_void_p()
+        _io_check(L.np2_sam_open(pol._h, arr, n, C.byref(o), C.byref(self._h)))
+
+    def refs(self):
+        L = _bind()
+        out = []
+        for i in range(L.np2_sam_n_refs(self._h)):
+            n = C.c_uint32()
+            out.append((L.np2_sam_ref_name(self._h, i, C.byref(n)).decode(), n.value))
+        return out
+
+    def stats(self):
+        st = np2_sam_stats_t()
+        _io_check(_bind().np2_sam_stats(self._h, C.byref(st)))
+        return _sam_stats_dict(st)
+
+    def export(self, pol):
+        """np2_sam_export: (recs, tids, cigar, seq4) as sam_parse_bytes returns them (parity tests)"""
+        L = _bind()
+        pr, pt, pc, ps, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64()
+        _io_check(L.np2_sam_export(pol._h, self._h, C.byref(pr), C.byref(pt), C.byref(pc), C.byref(ps), C.byref(n)))
+        return _sam_arrays(L, pr, pt, pc, ps, n.value, self.stats())
+
+    def close(self):
+        if self._h:
+            _bind().np2_sam_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _sam_arrays(L, pr, pt, pc, ps, n, stats):
+    """the four malloc'ed arrays of np2_sam_parse_bytes / np2_sam_export as numpy arrays of their own; releases them"""
+    try:
+        take = lambda p, nbytes, dt: np.frombuffer(C.string_at(p.value, nbytes), dtype=dt).copy() if nbytes else np.zeros(0, dt)
+        return (take(pr, n * BAMREC_DTYPE.itemsize, BAMREC_DTYPE), take(pt, n * 4, np.int32),
+                take(pc, stats["cigar_words"] * 4, np.uint32), take(ps, stats["seq_bytes"], np.uint8))
+    finally:
+        for p in (pr, pt, pc, ps):
+            L.np2_free(p)
+
+
+def contig_from_sam(pol, sam, name, ref, opts=None):
+    """The records of reference `name` of a resident Sam -> packed pileup resident in HBM (GPU columnariser).  -S
+    (use_secondary) is not supported from SAM: use a BAM."""
+    L = _bind()
+    ref = np.frombuffer(ref, dtype=np.uint8) if isinstance(ref, (bytes, bytearray)) else np.ascontiguousarray(ref, dtype=np.uint8)
+    o = (opts or FrontOpts()).c()
+    h = C.c_void_p()
+    _io_check(L.np2_contig_from_sam(pol._h, sam._h, name.encode(), ref.ctypes.data, ref.shape[0], C.byref(o), C.byref(h)))
+    return _resident(pol, h, name, int(ref.shape[0]))
+
+
+def sam_parse_bytes(text, tie="strand", device=0):
+    """np2_sam_parse_bytes: SAM text (bytes, header included) -> (recs as a BAMREC_DTYPE array in sorted order, tids int32,
+    cigar uint32 in sorted order, seq4 uint8 as the records were met, stats dict).  For parity tests and measurements."""
+    L = _bind()
+    o = _sam_opts(tie)
+    buf = np.frombuffer(text, dtype=np.uint8)
+    pr, pt, pc, ps, n, st = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64(), np2_sam_stats_t()
+    _io_check(L.np2_sam_parse_bytes(device, buf.ctypes.data if len(buf) else None, len(buf), C.byref(o), C.byref(pr), C.byref(pt),
+                                    C.byref(pc), C.byref(ps), C.byref(n), C.byref(st)))
+    stats = _sam_stats_dict(st)
+    return _sam_arrays(L, pr, pt, pc, ps, n.value, stats) + (stats,)
+
+
+def mapping_kind(path):
+    """"bam" or "sam" for an alignment file, from its first bytes (gunzipped when they are gzip): BAM\1 is a BAM; a line
+    that begins with @ or holds at least 10 tabs is SAM text.  Anything else is a ValueError naming the file."""
+    import zlib
+    with open(path, "rb") as f:
+        head = f.read(65536)
+    if head[:2] == b"\x1f\x8b":
+        try:
+            head = zlib.decompressobj(31).decompress(head, 65536)
+        except zlib.error:
+            raise ValueError(f"{path}: damaged gzip") from None
+    if head[:4] == b"BAM\x01":
+        return "bam"
+    first = head.split(b"\n", 1)[0]
+    if head[:1] == b"@" or first.count(b"\t") >= 10:
+        return "sam"
+    raise ValueError(f"{path}: neither a BAM nor SAM text")
 
 
 def _resident(pol, h, name, L_, n_reads=0, n_cols=0):
