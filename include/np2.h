@@ -214,6 +214,70 @@ int np2_cmp_strings(np2_ctx_t *ctx, int yak_idx, const uint8_t *strs, const uint
                     uint16_t min_count, np2_cmp_t *out, uint64_t *spectra /* [6*1024] or NULL */,
                     uint64_t *asm_only /* [6] or NULL */, float *kernel_ms /* or NULL */);
 
+/* ---- what a polish changed: edits of the contig, normalised, with the k-mer tables' verdict -----------------------------
+ * The reference's only trace of its changes is the hidden --out_pos (a position per output base), and it misleads: every
+ * base of a replaced low-quality region is stamped with the region's start (update_consensus_with_lqseqs,
+ * main.rs:1039-1049), whether or not the replacement differs from the contig.  np2_edits_* tell the real edits from the
+ * regions rewritten the same.  The rule is this project's; no outside tool pins it (`bcftools norm` is not claimed).
+ *
+ * Inputs: the contig ref[0 .. L); the output (bases[i], pos[i]), i < n, pos non-decreasing and < L.  Bytes compare without
+ * regard to ASCII case.  first = pos[0], last = pos[n-1]; positions outside [first, last] are OUTSIDE THE SPAN: never
+ * edits, only counted.  n == 0: no span, no edits, every position outside.
+ *  1. group(p) = the output bases with pos == p.  Position p in [first, last] is CLEAN when group(p) is one base equal
+ *     to ref[p].
+ *  2. A RAW RUN is a maximal [s, e] of non-clean positions; REF = ref[s .. e], ALT = its groups concatenated, o_s = the
+ *     index of the first output base with pos >= s.
+ *  3. Trimming: the common suffix of REF and ALT is dropped, then the common prefix (s and o_s advance).  Both empty: the
+ *     run was REWRITTEN THE SAME; it is no edit, only counted.
+ *  4. Kinds: SNV (lengths 1 and 1), MNV (equal lengths > 1), INS (REF empty), DEL (ALT empty), CPX (anything else).  A
+ *     replaced region has no inner alignment: two substitutions inside one region are ONE MNV or CPX, whatever lies
+ *     between them.
+ *  5. Left-alignment of INS and DEL only, X being the inserted / deleted string: while s > lo and ref[s-1] == X[last],
+ *     X is rotated right by one byte, s -= 1, o_s -= 1.  lo = max(first, one past the previous real edit's trimmed REF
+ *     before that edit's own shift): every edit shifts independently of the others.  Between two real edits output and
+ *     contig are the same string (regions rewritten the same included), so both coordinates move in lock step.
+ *  6. Support per edit and k-mer table of size k, in the shifted coordinates: the k-mers wholly inside
+ *     ref[max(0, s-(k-1)) .. min(L, s+|REF|+(k-1))) give n_in / absent_in, those wholly inside
+ *     out[max(0, o_s-(k-1)) .. min(n, o_s+|ALT|+(k-1))) give n_out / absent_out.  Validity and absence are np2_qv_*'s
+ *     (any non-ACGTU byte breaks the run; a stored count below min_count reads as 0).
+ * Records are unanchored (an INS has ref_len 0 at the position it precedes); a VCF writer adds the anchor base.
+ * Totals: bases_inserted = sum of max(alt_len - ref_len, 0), bases_deleted = sum of max(ref_len - alt_len, 0), so that
+ * n == (last - first + 1) + bases_inserted - bases_deleted.
+ *
+ * np2_edits_buffers works on host buffers (this project's or the reference binary's --out_pos alike).  Both conditions
+ * on pos are checked ON THE DEVICE: NP2_E_ARG with a message, never a fault.  np2_edits_last works on the consensus the
+ * last successful np2_polish_resident of this context left in HBM and on `contig` as uploaded (its bases as the device
+ * holds them: upper case, a non-ACGT byte as N); nothing is copied up.  Device memory while the call lasts: 8 bytes
+ * per contig position, 84 per possible run ((L + 1) / 2 of them) and 16 more per run and table.
+ * opts (NULL: {1, -1}): min_count of rule 6; tables = a bit mask of the context's tables to judge by, -1 all, 0 none (at
+ * most 8).  NP2_E_ARG before anything is launched: a NULL pointer with a non-zero length, out NULL, a table bit beyond
+ * the context's tables; NP2_E_UNSUPPORTED: n >= 2^32 - 65536, more than 8 tables.  Release with np2_edits_free. */
+#define NP2_EDIT_SNV 0
+#define NP2_EDIT_MNV 1
+#define NP2_EDIT_INS 2
+#define NP2_EDIT_DEL 3
+#define NP2_EDIT_CPX 4
+#define NP2_EDITS_MAX_TABLES 8
+#define NP2_EDITS_STAGES 6 /* kernel_ms: flags, runs, trim, shift, emit, support */
+typedef struct np2_edit { uint32_t ref_pos, ref_len, out_off, alt_len, kind; } np2_edit_t; /* after the shift */
+typedef struct np2_edit_support { uint32_t n_in, absent_in, n_out, absent_out; } np2_edit_support_t;
+typedef struct np2_edits_opts { uint16_t min_count; int32_t tables; } np2_edits_opts_t;
+typedef struct np2_edits {
+    uint32_t n_edits, n_tables;
+    np2_edit_t *edits;                 /* [n_edits], ascending ref_pos */
+    uint32_t *ref_off, *alt_off;       /* [n_edits + 1]: edit i's REF is ref_pool[ref_off[i] .. ref_off[i+1]), ALT likewise */
+    uint8_t *ref_pool, *alt_pool;
+    np2_edit_support_t *support;       /* [n_edits * n_tables], edit-major */
+    uint32_t table_idx[NP2_EDITS_MAX_TABLES], table_k[NP2_EDITS_MAX_TABLES];
+    uint32_t has_span, first_pos, last_pos, pad;
+    uint64_t raw_runs, same_runs, n_kind[5], bases_inserted, bases_deleted, outside_span;
+    float kernel_ms[NP2_EDITS_STAGES]; /* HIP-event times of the stages' kernels */
+} np2_edits_t;
+int np2_edits_buffers(np2_ctx_t *ctx, const uint8_t *ref, uint32_t L, const uint8_t *bases, const uint32_t *pos, uint64_t n,
+                      const np2_edits_opts_t *opts, np2_edits_t *out);
+int np2_edits_last(np2_ctx_t *ctx, np2_contig_t *contig, const np2_edits_opts_t *opts, np2_edits_t *out);
+void np2_edits_free(np2_edits_t *out);
+
 /* Stage-level exports for kernel parity tests and profiling.
  * After np2_polish_resident with tracing enabled, np2_trace_get returns a pointer to a
  * host copy of intermediate `name` of pass `pass` (valid until the next polish call). */

@@ -28,6 +28,7 @@ ABI_SYMBOLS = [
     "np2_shard_end", "np2_swiss_order", "np2_batch_set_timing", "np2_batch_set_priority", "np2_batch_last_diff_ms", "np2_batch_stats", "np2_batch_last_call_ms",
     "np2_qv_strings", "np2_qv_device", "np2_trio_strings", "np2_trio_device", "np2_bin_stream",
     "np2_cmp_strings",
+    "np2_edits_buffers", "np2_edits_last", "np2_edits_free",
 ]
 
 # include/np2_io.h (input side; bound by nextpolish2_amd.io)
@@ -79,6 +80,24 @@ class np2_rep_stats_t(C.Structure):
 
 assert C.sizeof(np2_rep_opts_t) == 24 and np2_rep_opts_t.distinct.offset == 16 and C.sizeof(np2_rep_stats_t) == 56
 
+class np2_edits_opts_t(C.Structure):
+    _fields_ = [("min_count", C.c_uint16), ("tables", C.c_int32)]
+
+
+class np2_edits_t(C.Structure):
+    _fields_ = [("n_edits", C.c_uint32), ("n_tables", C.c_uint32), ("edits", C.c_void_p), ("ref_off", C.c_void_p),
+                ("alt_off", C.c_void_p), ("ref_pool", C.c_void_p), ("alt_pool", C.c_void_p), ("support", C.c_void_p),
+                ("table_idx", C.c_uint32 * 8), ("table_k", C.c_uint32 * 8), ("has_span", C.c_uint32), ("first_pos", C.c_uint32),
+                ("last_pos", C.c_uint32), ("pad", C.c_uint32), ("raw_runs", C.c_uint64), ("same_runs", C.c_uint64),
+                ("n_kind", C.c_uint64 * 5), ("bases_inserted", C.c_uint64), ("bases_deleted", C.c_uint64),
+                ("outside_span", C.c_uint64), ("kernel_ms", C.c_float * 6)]
+
+
+assert C.sizeof(np2_edits_opts_t) == 8 and C.sizeof(np2_edits_t) == 240 and np2_edits_t.raw_runs.offset == 136
+
+EDIT_DTYPE = np.dtype([("ref_pos", "<u4"), ("ref_len", "<u4"), ("out_off", "<u4"), ("alt_len", "<u4"), ("kind", "<u4")])  # np2_edit_t
+EDIT_KINDS = ("SNV", "MNV", "INS", "DEL", "CPX")
+EDIT_STAGES = ("flags", "runs", "trim", "shift", "emit", "support")
 BIN_DTYPE = np.dtype([("n_kmers", "<u4"), ("n_pat", "<u4"), ("n_mat", "<u4"), ("pairs", "<u4", (4,))])  # np2_bin_t
 assert BIN_DTYPE.itemsize == 28
 
@@ -130,6 +149,10 @@ def _lib_locked():
         L.np2_trio_device.argtypes = [vp, C.c_int, C.c_int, vp, u64, u16, u16, vp, vp, vp, C.POINTER(C.c_float)]
         L.np2_bin_stream.argtypes = [vp, C.c_int, C.c_int, vp, u64, u64, C.POINTER(np2_bin_opts_t), vp, vp, C.POINTER(C.c_float)]
         L.np2_cmp_strings.argtypes = [vp, C.c_int, vp, vp, u64, u16, vp, vp, vp, C.POINTER(C.c_float)]
+        L.np2_edits_buffers.argtypes = [vp, vp, u32, vp, vp, u64, C.POINTER(np2_edits_opts_t), C.POINTER(np2_edits_t)]
+        L.np2_edits_last.argtypes = [vp, vp, C.POINTER(np2_edits_opts_t), C.POINTER(np2_edits_t)]
+        L.np2_edits_free.argtypes = [C.POINTER(np2_edits_t)]
+        L.np2_edits_free.restype = None
         L.np2_depth_from_records.argtypes = [vp, u32, vp, u32, vp, C.POINTER(np2_depth_opts_t), C.POINTER(vp), C.POINTER(vp),
                                              C.POINTER(u32), vp, C.POINTER(np2_depth_stats_t)]
         L.np2_depth_from_bam.argtypes = [vp, vp, C.c_char_p, u32, C.POINTER(np2_depth_opts_t), C.POINTER(vp), C.POINTER(vp),
@@ -325,6 +348,44 @@ class CmpStats:
     @property
     def completeness(self):
         return self.stats[1] / self.stats[0] if self.stats[0] else float("nan")
+
+
+class Edits:
+    """What np2_edits_buffers / np2_edits_last return, copied out of the library's blocks.  edits: EDIT_DTYPE records after
+    the shift, unanchored, ascending ref_pos; ref(i) / alt(i): edit i's strings (bytes); support: uint32 array
+    (n_edits, n_tables, 4) of (n_in, absent_in, n_out, absent_out); table_idx / table_k: the tables judged by; totals: dict
+    (has_span, first, last, raw_runs, same_runs, n_kind[5], bases_inserted, bases_deleted, outside); kernel_ms: HIP-event
+    time per stage (EDIT_STAGES)."""
+
+    def __init__(self, r: np2_edits_t):
+        n, nt = r.n_edits, r.n_tables
+
+        def take(addr, count, typestr):
+            return np.array(np.asarray(_Raw(addr, count, typestr)), copy=True) if count else np.zeros(0, dtype=np.dtype(typestr))
+        self.edits = take(r.edits, n * 5, "<u4").view(EDIT_DTYPE) if n else np.zeros(0, dtype=EDIT_DTYPE)
+        self.ref_off, self.alt_off = take(r.ref_off, n + 1, "<u4"), take(r.alt_off, n + 1, "<u4")
+        self.ref_pool = take(r.ref_pool, int(self.ref_off[-1]), "|u1").tobytes()
+        self.alt_pool = take(r.alt_pool, int(self.alt_off[-1]), "|u1").tobytes()
+        self.support = take(r.support, n * nt * 4, "<u4").reshape(n, nt, 4)
+        self.table_idx, self.table_k = [int(r.table_idx[i]) for i in range(nt)], [int(r.table_k[i]) for i in range(nt)]
+        self.totals = dict(has_span=int(r.has_span), first=int(r.first_pos), last=int(r.last_pos), raw_runs=int(r.raw_runs),
+                           same_runs=int(r.same_runs), n_kind=[int(x) for x in r.n_kind], bases_inserted=int(r.bases_inserted),
+                           bases_deleted=int(r.bases_deleted), outside=int(r.outside_span))
+        self.kernel_ms = {s: float(r.kernel_ms[i]) for i, s in enumerate(EDIT_STAGES)}
+
+    def __len__(self):
+        return len(self.edits)
+
+    def ref(self, i):
+        return self.ref_pool[int(self.ref_off[i]):int(self.ref_off[i + 1])]
+
+    def alt(self, i):
+        return self.alt_pool[int(self.alt_off[i]):int(self.alt_off[i + 1])]
+
+    def records(self):
+        """the edits as the dicts tests/edits_model.py writes: ref_pos, out_off, ref, alt, kind"""
+        return [dict(ref_pos=int(e["ref_pos"]), out_off=int(e["out_off"]), ref=self.ref(i), alt=self.alt(i), kind=EDIT_KINDS[int(e["kind"])])
+                for i, e in enumerate(self.edits)]
 
 
 class ResidentContig:
@@ -526,6 +587,34 @@ class Polisher:
                                         stats.ctypes.data, h.ctypes.data if hist else None, raw.ctypes.data if bits else None,
                                         C.byref(ms)))
         return QvStats(stats, h, [raw[:(int(n) + 7) // 8]] if bits else None, ms.value)
+
+    def _edits(self, call, min_count, tables):
+        o, r = np2_edits_opts_t(int(min_count), int(tables)), np2_edits_t()
+        self._check(call(C.byref(o), C.byref(r)))
+        try:
+            return Edits(r)
+        finally:
+            lib().np2_edits_free(C.byref(r))
+
+    def edits_buffers(self, ref, bases, pos, min_count=1, tables=-1):
+        """np2_edits_buffers: where the output (`bases` with their contig positions `pos`, this project's or the reference
+        binary's --out_pos alike) differs from the contig `ref` -> Edits.  tables: bit mask of this context's k-mer tables
+        to judge every edit by, -1 all, 0 none.  Np2Error(NP2_E_ARG) for positions that decrease or are not below len(ref)."""
+        ref = np.frombuffer(bytes(ref), dtype=np.uint8) if not isinstance(ref, np.ndarray) else np.ascontiguousarray(ref, dtype=np.uint8)
+        bases = np.frombuffer(bytes(bases), dtype=np.uint8) if not isinstance(bases, np.ndarray) else np.ascontiguousarray(bases, dtype=np.uint8)
+        pos = np.ascontiguousarray(pos, dtype=np.uint32)
+        if len(bases) != len(pos):
+            raise ValueError("bases and pos differ in length")
+        L = lib()
+        return self._edits(lambda o, r: L.np2_edits_buffers(self._h, ref.ctypes.data if len(ref) else None, len(ref),
+                                                            bases.ctypes.data if len(bases) else None,
+                                                            pos.ctypes.data if len(pos) else None, len(bases), o, r), min_count, tables)
+
+    def edits_last(self, contig, min_count=1, tables=-1):
+        """np2_edits_last: the same for the consensus the last polish_resident of this context left on the device, against
+        `contig` (the ResidentContig it polished) as uploaded; nothing is copied up."""
+        L = lib()
+        return self._edits(lambda o, r: L.np2_edits_last(self._h, contig._h, o, r), min_count, tables)
 
     def cmp_strings(self, yak_idx, seqs, min_count=2, spectra=False):
         """np2_cmp_strings: k-mer completeness of the set `seqs` (bytes-like each, taken together) against the reads' table

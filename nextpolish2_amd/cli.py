@@ -84,6 +84,11 @@ def build_parser():
     p.add_argument("--trio_min_count", type=int, default=2, metavar="N", help="--trio: a parent counting a k-mer fewer than N times does not have it [2]")
     p.add_argument("--trio_mid_count", type=int, default=5, metavar="N", help="--trio: a parent counting a k-mer at least N times has it [5]")
     p.add_argument("--trio_bed", default=None, metavar="PREFIX", help="with --trio: switch sites, PREFIX.in.bed and PREFIX.out.bed")
+    p.add_argument("--edits", default=None, metavar="FILE.vcf",
+                   help="what the polish changed: the edits of every polished contig as VCF 4.2, left-aligned, each with the k-mer "
+                        "tables' verdict (regions rewritten the same are no edits)")
+    p.add_argument("--edits_summary", default=None, metavar="FILE.tsv", help="edits per contig and kind, bases inserted and deleted, verdicts")
+    p.add_argument("--edits_min_count", type=int, default=1, metavar="N", help="--edits reads a k-mer count below N as absent [1]")
     p.add_argument("-u", "--uppercase", action="store_true", help="output in uppercase sequences")
     p.add_argument("--out_pos", action="store_true", help=argparse.SUPPRESS)
     p.add_argument("-k", "--min_kmer_count", type=int, default=5)
@@ -155,6 +160,11 @@ def _cmp_finish(a, creport, pol, seqs_in, seqs_out):
     creport.add(pol, "in", seqs_in)
     creport.add(pol, "out", seqs_out)
     creport.write_cli(a.cmp, a.cmp_spectra)
+
+
+def _edits_report(a, ks):
+    from .edits import EditsReport
+    return EditsReport(ks, a.edits_min_count)
 
 
 def _trio_report(a):
@@ -355,6 +365,13 @@ def main(argv=None):
         parser.error("--trio measures the sequences of a FASTA output: not with --out_pos")
     if not 1 <= a.trio_min_count <= a.trio_mid_count <= 1023:
         parser.error("--trio thresholds: 1 <= --trio_min_count <= --trio_mid_count <= 1023")
+    a.want_edits = a.edits is not None or a.edits_summary is not None
+    if a.want_edits and a.out_pos:
+        parser.error("--edits reports on a FASTA output: not with --out_pos (python -m nextpolish2_amd.edits reads an --out_pos text)")
+    if a.want_edits and int(os.environ.get("WORLD_SIZE", "1")) > 1 and "RANK" in os.environ:
+        parser.error("--edits runs on one rank: not under torchrun")
+    if not 0 <= a.edits_min_count <= 1023:
+        parser.error("--edits_min_count: 0 .. 1023")
     if a.model.lower() not in ("ref", "len"):
         raise SystemExit("error: invalid value for --model (ref|len)")
     try:  # (a look at the file's first bytes; standard input cannot be looked at twice and is SAM text)
@@ -511,6 +528,8 @@ def main(argv=None):
             b = b.upper()
         if a.out_pos:
             return b"".join(b"%s\t%c\t%d\n" % (name.encode(), b[i:i + 1], int(pos[i])) for i in range(len(b)))
+        if a.want_edits:  # (every position was fetched for the report: the span is its ends)
+            return b">%s start:%d end:%d\n%s\n" % (name.encode(), pos[0], pos[-1], b), bases, pos
         return b">%s start:%d end:%d\n%s\n" % (name.encode(), pos[0], pos[1], b)
 
     from collections import deque
@@ -569,7 +588,7 @@ def main(argv=None):
                 ensure_batch()
                 t_p = time.time()
                 try:
-                    res = tls.batch.polish(contigs, opts, want_pos=a.out_pos)
+                    res = tls.batch.polish(contigs, opts, want_pos=a.out_pos or a.want_edits)
                 except Exception:
                     if len(contigs) == 1:
                         raise
@@ -578,7 +597,7 @@ def main(argv=None):
                     res = []
                     for it, c in zip(live, contigs):
                         try:
-                            res.append(tls.batch.polish([c], opts, want_pos=a.out_pos)[0])
+                            res.append(tls.batch.polish([c], opts, want_pos=a.out_pos or a.want_edits)[0])
                         except Exception as e1:
                             it[3].set_exception(e1)
                             res.append(None)
@@ -607,6 +626,10 @@ def main(argv=None):
         if not base_future:
             base_future.append(yak_pool.submit(build_base))  # (as for --qv)
 
+    ereport, epol = None, []
+    if a.want_edits:  # (its context is made when the first polished contig is written: the tables are in HBM by then)
+        ereport = _edits_report(a, a.sr_ks if a.sr else sorted(np2io.check_yak_header(y) for y in a.yak))
+
     treport, tpol, trio_pool = None, [], None
     if a.trio is not None:  # the parental tables go into HBM next to the polish, in a context of their own
         treport, trio_pool = _trio_report(a), ThreadPoolExecutor(max_workers=1)
@@ -621,12 +644,24 @@ def main(argv=None):
             pending, pending_len = [], []  # records in input order: bytes or futures; the contigs' lengths
             pending_in = []  # --qv: (name, sequence as read) of the same contigs
             pending_trio = []  # --trio: the same
+            pending_ed = []  # --edits: the same
 
             def drain(keep):
                 while len(pending) > keep:
                     rec = pending.pop(0)
                     pending_len.pop(0)
                     rec = rec if isinstance(rec, bytes) else rec.result()
+                    if ereport is not None:  # found on this thread's own context over the shared tables, from the fetched positions
+                        e_name, e_seq = pending_ed.pop(0)
+                        if isinstance(rec, tuple):
+                            if not epol:
+                                b0 = base_future[0].result()
+                                with base_lock:
+                                    epol.append(b0.clone())
+                            ereport.add(epol[0], e_name, e_seq, rec[1], rec[2])
+                            rec = rec[0]
+                        else:
+                            ereport.add_unpolished(e_name, len(e_seq))
                     out.write(rec)
                     if report is not None:  # measured as written, on this thread's own context over the shared tables
                         if not qpol:
@@ -649,6 +684,8 @@ def main(argv=None):
                         pending_in.append((name, seq))
                     if treport is not None:
                         pending_trio.append((name, seq))
+                    if ereport is not None:
+                        pending_ed.append((name, seq))
                     if creport is not None:
                         cmp_in.append(seq)
                     if len(seq) < a.min_ctg_len:  # pass-through (main.rs:1727-1730)
@@ -686,6 +723,8 @@ def main(argv=None):
                 report.write_cli(a.qv, a.qv_bed)
             if treport is not None:
                 treport.write_cli(a.trio, a.trio_bed)
+            if ereport is not None:
+                ereport.write_cli(a.edits, a.edits_summary)
             if creport is not None:  # the whole assembly, on this thread's own context over the shared tables
                 b0 = base_future[0].result()
                 with base_lock:
@@ -701,7 +740,7 @@ def main(argv=None):
         if prof:
             print(f"[np2 profile] contexts released at +{time.time() - t0:.3f} s", file=sys.stderr)
     finally:
-        for q in qpol:  # (the QV context, on the error paths too)
+        for q in qpol + epol:  # (the QV and the edits context, on the error paths too)
             q.close()
         if trio_pool is not None:
             trio_pool.shutdown(wait=True)
