@@ -282,6 +282,23 @@ def depth_from_records(pol, L_, recs, cigar, **kw):
                                                                    cigar.ctypes.data if len(cigar) else None, *a), **kw)
 
 
+def _pack_seqs(seqs, to_bytes=True):
+    """what the *_strings entry points take: (the sequences, as bytes each unless told otherwise; their n + 1 offsets; the
+    bytes themselves, one after the other, with a byte of room behind)"""
+    if to_bytes:
+        seqs = [bytes(s) for s in seqs]
+    off = np.zeros(len(seqs) + 1, dtype=np.uint64)
+    if len(seqs):
+        off[1:] = np.cumsum([len(s) for s in seqs])
+    return seqs, off, np.frombuffer(b"".join(seqs) + b"\0", dtype=np.uint8)
+
+
+def _split_bits(raw, nb):
+    """the per-sequence bitmaps of `raw`, sequence i's being its next nb[i] bytes (views)"""
+    cuts = np.concatenate([[0], np.cumsum(nb)]).astype(np.int64)
+    return [raw[cuts[i]:cuts[i + 1]] for i in range(len(nb))]
+
+
 class QvStats:
     """What np2_qv_strings / np2_qv_device return.  stats: uint64 array (n, 2) of (n_kmers, n_absent) per sequence;
     hist: uint64[1024] (hist[c] = k-mers with count c) or None; bits: one uint8 array per sequence (ceil(len / 8) bytes,
@@ -538,10 +555,7 @@ class Polisher:
         return out
 
     def score_strings(self, yak_idx, strings, min_kmer_count=5):
-        off = np.zeros(len(strings) + 1, dtype=np.uint64)
-        if strings:
-            off[1:] = np.cumsum([len(s) for s in strings])
-        blob = np.frombuffer(b"".join(strings) + b"\0", dtype=np.uint8)
+        strings, off, blob = _pack_seqs(strings, to_bytes=False)
         out = np.zeros(len(strings), dtype=np.uint16)
         self._check(lib().np2_score_strings(self._h, yak_idx, blob.ctypes.data, off.ctypes.data, len(strings),
                                             min_kmer_count, out.ctypes.data))
@@ -557,12 +571,8 @@ class Polisher:
     def qv_strings(self, yak_idx, seqs, min_count=1, hist=False, bits=False):
         """np2_qv_strings: k-mers and absent k-mers of every sequence of `seqs` (bytes-like each) against table `yak_idx`
         -> QvStats.  count(k-mer) is the stored count if >= min_count, else 0; absent means count == 0."""
-        seqs = [bytes(s) for s in seqs]
+        seqs, off, blob = _pack_seqs(seqs)
         n = len(seqs)
-        off = np.zeros(n + 1, dtype=np.uint64)
-        if n:
-            off[1:] = np.cumsum([len(s) for s in seqs])
-        blob = np.frombuffer(b"".join(seqs) + b"\0", dtype=np.uint8)
         stats = np.zeros((max(n, 1), 2), dtype=np.uint64)
         h = np.zeros(1024, dtype=np.uint64) if hist else None
         nb = [(len(s) + 7) // 8 for s in seqs]
@@ -570,11 +580,7 @@ class Polisher:
         ms = C.c_float()
         self._check(lib().np2_qv_strings(self._h, yak_idx, blob.ctypes.data, off.ctypes.data, n, min_count, stats.ctypes.data,
                                          h.ctypes.data if hist else None, raw.ctypes.data if bits else None, C.byref(ms)))
-        per_seq = None
-        if bits:
-            cuts = np.concatenate([[0], np.cumsum(nb)]).astype(np.int64)
-            per_seq = [raw[cuts[i]:cuts[i + 1]] for i in range(n)]
-        return QvStats(stats[:n], h, per_seq, ms.value)
+        return QvStats(stats[:n], h, _split_bits(raw, nb) if bits else None, ms.value)
 
     def qv_device(self, yak_idx, dev_ptr, n, min_count=1, hist=False, bits=False):
         """np2_qv_device: the same measurement of ONE sequence of `n` bytes at device address `dev_ptr` on this context's
@@ -619,12 +625,8 @@ class Polisher:
     def cmp_strings(self, yak_idx, seqs, min_count=2, spectra=False):
         """np2_cmp_strings: k-mer completeness of the set `seqs` (bytes-like each, taken together) against the reads' table
         `yak_idx` -> CmpStats.  A read k-mer is reliable when its stored count is >= max(min_count, 1)."""
-        seqs = [bytes(s) for s in seqs]
+        seqs, off, blob = _pack_seqs(seqs)
         n = len(seqs)
-        off = np.zeros(n + 1, dtype=np.uint64)
-        if n:
-            off[1:] = np.cumsum([len(s) for s in seqs])
-        blob = np.frombuffer(b"".join(seqs) + b"\0", dtype=np.uint8)
         st = np.zeros(4, dtype=np.uint64)
         sp = np.zeros((6, 1024), dtype=np.uint64) if spectra else None
         ao = np.zeros(6, dtype=np.uint64)
@@ -637,12 +639,8 @@ class Polisher:
         """np2_trio_strings: parental markers and consecutive marker pairs of every sequence of `seqs` (bytes-like each)
         against the paternal table `pat_idx` and the maternal table `mat_idx` of the same k -> TrioStats.  A k-mer is a
         parent's marker when that parent's count is >= mid_count and the other's is < min_count."""
-        seqs = [bytes(s) for s in seqs]
+        seqs, off, blob = _pack_seqs(seqs)
         n = len(seqs)
-        off = np.zeros(n + 1, dtype=np.uint64)
-        if n:
-            off[1:] = np.cumsum([len(s) for s in seqs])
-        blob = np.frombuffer(b"".join(seqs) + b"\0", dtype=np.uint8)
         stats = np.zeros((max(n, 1), 7), dtype=np.uint64)
         nb = [(len(s) + 7) // 8 for s in seqs]
         raw = [np.zeros(sum(nb) + 1, dtype=np.uint8) for _ in range(2)] if bits else None
@@ -650,10 +648,7 @@ class Polisher:
         self._check(lib().np2_trio_strings(self._h, pat_idx, mat_idx, blob.ctypes.data, off.ctypes.data, n, min_count, mid_count,
                                            stats.ctypes.data, raw[0].ctypes.data if bits else None,
                                            raw[1].ctypes.data if bits else None, C.byref(ms)))
-        per = [None, None]
-        if bits:
-            cuts = np.concatenate([[0], np.cumsum(nb)]).astype(np.int64)
-            per = [[r[cuts[i]:cuts[i + 1]] for i in range(n)] for r in raw]
+        per = [_split_bits(r, nb) for r in raw] if bits else [None, None]
         return TrioStats(stats[:n], per[0], per[1], ms.value)
 
     def trio_device(self, pat_idx, mat_idx, dev_ptr, n, min_count=2, mid_count=5, bits=False):

@@ -145,6 +145,11 @@ def _record_sequence(rec):
     return rec[rec.index(b"\n") + 1:-1]
 
 
+def table_ks(a):
+    """the k of every table the reports measure against, in table order"""
+    return a.sr_ks if a.sr else sorted(np2io.check_yak_header(y) for y in a.yak)
+
+
 def _qv_report(a, ks):
     from .qv import QvReport
     return QvReport(ks, a.qv_min_count, want_bed=a.qv_bed is not None)
@@ -337,10 +342,7 @@ def main(argv=None):
     if a.sr_qc is not None and not a.sr:
         parser.error("--sr_qc filters the reads of --sr: give --sr")
     if a.sr:
-        try:
-            a.sr_ks = sorted(int(k) for k in a.sr_k.split(","))
-        except ValueError:
-            parser.error("--sr_k takes comma-separated integers")
+        a.sr_ks = np2io.sr_k_arg(parser, a.sr_k)
         if not a.sr_ks or any(k < 2 or k >= 32 for k in a.sr_ks):
             parser.error("--sr_k: only 2 <= k < 32 is supported")
         if a.sr_min_count is None:  # no word the polish would look at is ever dropped
@@ -617,18 +619,18 @@ def main(argv=None):
 
     report, qpol = None, []
     if a.qv is not None:
-        report = _qv_report(a, a.sr_ks if a.sr else sorted(np2io.check_yak_header(y) for y in a.yak))
+        report = _qv_report(a, table_ks(a))
         base_future.append(yak_pool.submit(build_base))  # the tables are needed even when every contig passes through
 
     creport, cmp_in, cmp_out = None, [], []
     if a.cmp is not None:
-        creport = _cmp_report(a, a.sr_ks if a.sr else sorted(np2io.check_yak_header(y) for y in a.yak))
+        creport = _cmp_report(a, table_ks(a))
         if not base_future:
             base_future.append(yak_pool.submit(build_base))  # (as for --qv)
 
     ereport, epol = None, []
     if a.want_edits:  # (its context is made when the first polished contig is written: the tables are in HBM by then)
-        ereport = _edits_report(a, a.sr_ks if a.sr else sorted(np2io.check_yak_header(y) for y in a.yak))
+        ereport = _edits_report(a, table_ks(a))
 
     treport, tpol, trio_pool = None, [], None
     if a.trio is not None:  # the parental tables go into HBM next to the polish, in a context of their own

@@ -16,7 +16,6 @@ The helpers at the top need no device (completeness_value, completeness_text, sp
 Polisher.cmp_strings."""
 import argparse
 import math
-import os
 import sys
 
 import numpy as np
@@ -87,14 +86,12 @@ class CmpReport:
 
 
 def build_parser():
+    from . import io as np2io
     p = argparse.ArgumentParser(prog="nextpolish2_amd.completeness",
                                 description="k-mer completeness and copy-number spectrum of an assembly against short-read k-mer tables")
     p.add_argument("fa", metavar="asm.fa[.gz]", help="assembly in [GZIP] FASTA format")
-    p.add_argument("yak", nargs="*", metavar="k.yak", help="k-mer dumps in yak format")
     p.add_argument("--hap2", default=None, metavar="FILE", help="the other haplotype's assembly: rows hap1, hap2 and both")
-    p.add_argument("--sr", action="append", default=[], metavar="FILE", help="short reads (may repeat): count their k-mers on the GPU instead")
-    p.add_argument("--sr_k", default="21,31", metavar="K[,K...]", help="k-mer sizes counted from --sr [21,31]")
-    p.add_argument("--sr_min_count", type=int, default=2, metavar="N", help="drop k-mers of --sr counted fewer than N times [2]")
+    np2io.add_table_args(p)
     p.add_argument("--min_count", type=int, default=2, metavar="N", help="a read k-mer counted at least N times is reliable [2]")
     p.add_argument("--spectra", default=None, metavar="PREFIX", help="copy-number spectra: PREFIX.k<K>.<set>.tsv (copies, count, kmers)")
     p.add_argument("--device", type=int, default=0)
@@ -112,18 +109,7 @@ def main(argv=None):
     if not 0 <= a.min_count <= 1023:
         parser.error("--min_count: 0 .. 1023")
     try:
-        if a.sr:
-            try:
-                ks = sorted(int(k) for k in a.sr_k.split(","))
-            except ValueError:
-                parser.error("--sr_k takes comma-separated integers")
-            pol = np2io.polisher_from_reads(a.sr, ks, min_count=a.sr_min_count, device=a.device)
-        else:
-            try:
-                ks = sorted(np2io.check_yak_header(y) for y in a.yak)
-            except (ValueError, OSError) as e:
-                raise SystemExit(f"Error: {e}")
-            pol = np2io.polisher_from_yak_files([os.path.abspath(y) for y in a.yak], device=a.device)
+        pol, ks = np2io.open_tables(parser, a)
         rep = CmpReport(ks, a.min_count, want_spectra=a.spectra is not None)
         hap1 = [seq for _, seq in np2io.read_fasta(a.fa)]
         if a.hap2 is None:

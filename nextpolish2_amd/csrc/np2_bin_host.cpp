@@ -8,12 +8,9 @@
 #include "np2_ctx.hpp"
 #include "np2_kcount.hpp"
 #include "np2_kernel_timer.hpp"
+#include "np2_pieces.hpp"
 #include "np2_seqreader.hpp"
 #include "np2_trio.hpp"
-
-#include <condition_variable>
-#include <deque>
-#include <thread>
 
 using namespace np2qv;
 using namespace np2bin;
@@ -22,18 +19,10 @@ using np2kc::HALO;
 namespace {
 
 // tiles of a piece (32 MiB of reads); NP2_BIN_TEST_STAGE_TILES: a test's smaller pieces
-uint32_t stage_tiles() {
-    if (const char *e = getenv("NP2_BIN_TEST_STAGE_TILES")) return (uint32_t)std::min<long>(1 << 16, std::max<long>(1, atol(e)));
-    return 4096;
-}
+uint32_t stage_tiles() { return (uint32_t)test_hook("NP2_BIN_TEST_STAGE_TILES", 1, 1 << 16, 4096); }
 
 // the scan's grid: what the device holds at once (4 blocks per CU, as the QV scan); NP2_BIN_TEST_BLOCKS: a test's grid
-uint32_t bin_blocks(int device) {
-    if (const char *e = getenv("NP2_BIN_TEST_BLOCKS")) return (uint32_t)std::min<long>(1 << 16, std::max<long>(1, atol(e)));
-    int cus = 0;
-    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-    return (uint32_t)std::max(1, cus) * 4u;
-}
+uint32_t bin_blocks(int device) { return grid_blocks(device, 4, "NP2_BIN_TEST_BLOCKS"); }
 
 np2_bin_opts_t opts_of(const np2_bin_opts_t *o) {
     return o ? *o : np2_bin_opts_t{2, 5, DEFAULT_MIN_SCORE, DEFAULT_MINOR_PERMILLE};
@@ -117,115 +106,36 @@ struct BinPiece {
     int file = 0;
     bool last = false; // the file ends with this piece
 };
-struct BinQueue { // one per reader thread: its pieces come out in the order of its files
-    std::mutex mu;
-    std::condition_variable cv;
-    std::deque<BinPiece *> full, idle;
-    bool abort = false, done = false;
-    int err_code = NP2_OK;
-    std::string err;
-    BinPiece *take_idle() {
-        std::unique_lock<std::mutex> l(mu);
-        cv.wait(l, [&] { return abort || !idle.empty(); });
-        if (abort) return nullptr;
-        BinPiece *p = idle.front();
-        idle.pop_front();
-        return p;
-    }
-    void give(std::deque<BinPiece *> &q, BinPiece *p) {
-        std::lock_guard<std::mutex> l(mu);
-        q.push_back(p);
-        cv.notify_all();
-    }
-    BinPiece *take_full() { // nullptr: the thread has stopped (an error, or nothing left)
-        std::unique_lock<std::mutex> l(mu);
-        cv.wait(l, [&] { return !full.empty() || done; });
-        if (full.empty()) return nullptr;
-        BinPiece *p = full.front();
-        full.pop_front();
-        return p;
-    }
-    void finish(int code, const std::string &m) {
-        std::lock_guard<std::mutex> l(mu);
-        if (code != NP2_OK) err_code = code, err = m;
-        done = true;
-        cv.notify_all();
-    }
-    void give_up() {
-        std::lock_guard<std::mutex> l(mu);
-        abort = true;
-        cv.notify_all();
-    }
-};
+using BinQueue = PieceQueue<BinPiece>; // one per reader thread: its pieces come out in the order of its files
 
 // one file's stream into pieces of `cap` bytes
 struct BinWriter {
-    BinQueue &q;
-    size_t cap;
+    HaloWriter<BinPiece> w;
     int file;
-    BinPiece *cur = nullptr;
-    uint8_t tail[HALO];
-    bool dead = false;
     np2seq::NameCollector names;
     uint64_t open_len = 0; // bytes of the read that is open
-    BinWriter(BinQueue &q_, size_t cap_, int file_) : q(q_), cap(cap_), file(file_) { memset(tail, SEP, HALO); }
-    bool fresh() {
-        cur = q.take_idle();
-        if (!cur) return !(dead = true);
-        memcpy(cur->buf, tail, HALO);
-        cur->n = 0, cur->file = file, cur->last = false;
-        cur->ends.clear(), cur->names.clear();
-        return true;
+    BinWriter(BinQueue &q, size_t cap, int file_) : w(q, cap), file(file_) {
+        w.on_fresh = [this](BinPiece &p) {
+            p.file = file, p.last = false;
+            p.ends.clear(), p.names.clear();
+        };
     }
-    void flush(bool last) {
-        if (!cur && last && !fresh()) return; // (a file without a byte still ends)
-        if (!cur) return;
-        cur->last = last;
-        memcpy(tail, cur->buf + cur->n, HALO); // the last HALO bytes of halo + data
-        q.give(q.full, cur);
-        cur = nullptr;
+    void finish() { // (a file without a byte still ends: with an empty piece)
+        if (!w.cur && !w.fresh()) return;
+        w.cur->last = true;
+        w.flush(true);
     }
     void put(const uint8_t *p, size_t n) {
         const bool sep = n == 1 && *p == SEP; // (a line's bytes hold no '\n')
         if (!sep && (open_len += n) > MAX_READ) throw Np2Error(NP2_E_ARG, "np2_bin_files: a read of 2^32 - 1 bytes or more");
-        while (n && !dead) {
-            if (!cur && !fresh()) return;
-            const size_t take = std::min(n, cap - cur->n);
-            memcpy(cur->buf + HALO + cur->n, p, take);
-            if (sep) {
-                cur->ends.push_back((uint32_t)cur->n);
-                cur->names += names.close();
-                cur->names.push_back('\n');
-                open_len = 0;
-            }
-            cur->n += take, p += take, n -= take;
-            if (cur->n == cap) flush(false);
+        if (sep) { // the read that is open ends in the piece that takes its separator
+            if (w.dead || (!w.cur && !w.fresh())) return;
+            w.cur->ends.push_back((uint32_t)w.cur->n);
+            w.cur->names += names.close();
+            w.cur->names.push_back('\n');
+            open_len = 0;
         }
-    }
-};
-
-struct OutFile {
-    std::string path;
-    FILE *f = nullptr;
-    ~OutFile() {
-        if (f) fclose(f);
-    }
-    void open(const char *p) {
-        if (!p) return;
-        path = p;
-        f = fopen(p, "wb");
-        if (!f) throw Np2Error(NP2_E_ARG, "cannot open " + path + " for writing");
-        setvbuf(f, nullptr, _IOFBF, 1 << 20);
-    }
-    void put(const void *p, size_t n) {
-        if (f && n && fwrite(p, 1, n, f) != n) throw Np2Error(NP2_E_ARG, "cannot write " + path);
-    }
-    void close() {
-        if (f && fclose(f) != 0) {
-            f = nullptr;
-            throw Np2Error(NP2_E_ARG, "cannot write " + path);
-        }
-        f = nullptr;
+        w.put(p, n);
     }
 };
 
@@ -307,46 +217,20 @@ int np2_bin_files(np2_ctx_t *cx, int pat_idx, int mat_idx, const char *const *pa
         const size_t n_threads = std::min<size_t>(files.size(), 16);
         std::vector<BinQueue> queues(n_threads);
         std::vector<BinPiece> pieces(2 * n_threads);
-        struct Release {
-            std::vector<BinPiece> &v;
-            ~Release() {
-                for (auto &p : v)
-                    if (p.buf) np2h::pinned_pool().put(p.buf);
-            }
-        } release{pieces};
+        PinnedBlocks pinned;
         for (size_t i = 0; i < pieces.size(); ++i) {
-            pieces[i].buf = (uint8_t *)np2h::pinned_pool().get(HALO + cap + 64);
-            if (!pieces[i].buf) throw Np2Error(NP2_E_NOMEM, "hipHostMalloc failed");
+            pieces[i].buf = pinned.get(HALO + cap + 64);
             queues[i / 2].idle.push_back(&pieces[i]);
         }
-        std::vector<std::thread> th;
-        struct Join {
-            std::vector<BinQueue> &q;
-            std::vector<std::thread> &th;
-            ~Join() {
-                for (auto &x : q) x.give_up();
-                for (auto &t : th) t.join();
+        auto readers = run_readers(n_threads, queues, [&](size_t ti) {
+            for (size_t fi = ti; fi < files.size(); fi += n_threads) {
+                BinWriter w(queues[ti], cap, (int)fi);
+                np2seq::parse_file(files[fi], [&](const uint8_t *p, size_t n) { w.put(p, n); }, [&] { return w.w.dead; },
+                                   [&](const uint8_t *p, size_t n, bool begin) { w.names(p, n, begin); });
+                w.finish();
+                if (w.w.dead) break;
             }
-        } join{queues, th};
-        for (size_t ti = 0; ti < n_threads; ++ti)
-            th.emplace_back([&, ti] {
-                int code = NP2_OK;
-                std::string msg;
-                try {
-                    for (size_t fi = ti; fi < files.size(); fi += n_threads) {
-                        BinWriter w(queues[ti], cap, (int)fi);
-                        np2seq::parse_file(files[fi], [&](const uint8_t *p, size_t n) { w.put(p, n); }, [&] { return w.dead; },
-                                           [&](const uint8_t *p, size_t n, bool begin) { w.names(p, n, begin); });
-                        w.flush(true);
-                        if (w.dead) break;
-                    }
-                } catch (const Np2Error &e) {
-                    code = e.code, msg = e.what();
-                } catch (const std::exception &e) {
-                    code = NP2_E_NOMEM, msg = e.what();
-                }
-                queues[ti].finish(code, msg);
-            });
+        });
 
         std::vector<uint8_t> cls;
         std::vector<np2_bin_t> st;
@@ -389,7 +273,7 @@ int np2_bin_files(np2_ctx_t *cx, int pat_idx, int mat_idx, const char *const *pa
                 }
                 open_len += p->n - from;
                 if (want_seq) open_seq.append((const char *)bytes + from, p->n - from);
-                q.give(q.idle, p);
+                q.give_idle(p);
             }
         }
         tsv.close(), pat_list.close(), mat_list.close(), pat_fa.close(), mat_fa.close();

@@ -5,17 +5,13 @@
 #include "np2_cmp.hpp"
 #include "np2_kcount.hpp"
 #include "np2_kernel_timer.hpp"
+#include "np2_pieces.hpp"
 
 namespace {
 
 // the grid: four blocks per CU (24 KiB of LDS each), striding over the table's turns; NP2_CMP_TEST_BLOCKS: a test's smaller
 // grid, so that a small table takes several strides with an uneven last one
-uint32_t cmp_blocks(int device) {
-    if (const char *e = getenv("NP2_CMP_TEST_BLOCKS")) return (uint32_t)std::min<long>(1 << 16, std::max<long>(1, atol(e)));
-    int cus = 0;
-    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-    return (uint32_t)std::max(1, cus) * 4u;
-}
+uint32_t cmp_blocks(int device) { return grid_blocks(device, 4, "NP2_CMP_TEST_BLOCKS"); }
 
 } // namespace
 
@@ -26,15 +22,10 @@ int np2_cmp_strings(np2_ctx_t *cx, int yak_idx, const uint8_t *strs, const uint6
     if (!cx) return NP2_E_ARG;
     return abi_guard([&] {
         // every argument is checked before anything is launched
-        if (yak_idx < 0 || (size_t)yak_idx >= cx->yaks.size())
-            throw Np2Error(NP2_E_ARG, "np2_cmp_strings: yak_idx " + std::to_string(yak_idx) + " out of range (the context has " +
-                                          std::to_string(cx->yaks.size()) + " tables)");
+        check_table(cx, yak_idx, "np2_cmp_strings", "yak_idx");
         if (min_count > np2kc::COUNT_MAX) throw Np2Error(NP2_E_ARG, "np2_cmp_strings: min_count must be at most 1023");
         if (!out) throw Np2Error(NP2_E_ARG, "np2_cmp_strings: out is NULL");
-        if (n && !off) throw Np2Error(NP2_E_ARG, "np2_cmp_strings: off is NULL with n > 0");
-        for (uint64_t i = 0; i < n; ++i)
-            if (off[i + 1] < off[i]) throw Np2Error(NP2_E_ARG, "np2_cmp_strings: off is descending at sequence " + std::to_string(i));
-        if (n && off[n] > off[0] && !strs) throw Np2Error(NP2_E_ARG, "np2_cmp_strings: strs is NULL with a non-zero length");
+        check_string_set("np2_cmp_strings", strs, off, n);
         const YakTable &yt = cx->yaks[yak_idx];
         if (yt.ord)
             throw Np2Error(NP2_E_UNSUPPORTED, "np2_cmp_strings: table " + std::to_string(yak_idx) + " repeats keys: a k-mer would be "

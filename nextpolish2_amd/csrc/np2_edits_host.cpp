@@ -45,18 +45,12 @@ void edits_release(np2_edits_t *o) {
     o->edits = nullptr, o->ref_off = o->alt_off = nullptr, o->ref_pool = o->alt_pool = nullptr, o->support = nullptr;
 }
 
-uint32_t wave_grid(int device) { // what the device holds at once, wavefronts striding over their jobs
-    int cus = 0;
-    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-    return (uint32_t)std::max(1, cus) * 4u;
-}
-
 // ref[L], bases[n], pos[n] on the device; `who` names the entry point in messages
 void edits_device(np2_ctx *cx, const uint8_t *d_ref, uint32_t L, const uint8_t *d_base, const uint32_t *d_pos, uint32_t n, const Tables &tb,
                   np2_edits_t *out, const char *who) {
     hipStream_t s = cx->stream;
     const uint32_t max_runs = (uint32_t)(((uint64_t)L + 1) / 2) + 1, n_words = (uint32_t)(((uint64_t)L + 31) / 32);
-    const uint32_t blocks = wave_grid(cx->device);
+    const uint32_t blocks = grid_blocks(cx->device, 4); // what the device holds at once, wavefronts striding over their jobs
     DevBuf<uint32_t> gse, bits, offs, runs, list, scans, sup;
     DevBuf<np2edits::Edit> rec;
     DevBuf<uint8_t> pools;

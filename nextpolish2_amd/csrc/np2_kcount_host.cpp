@@ -24,16 +24,15 @@
 #include "np2_ctx.hpp"
 #include "np2_kcount.hpp"
 #include "np2_kcount_core.hpp"
+#include "np2_kernel_timer.hpp"
+#include "np2_pieces.hpp"
 #include "np2_seqreader.hpp"
 #include "np2_srqc_host.hpp"
 
 #include <sys/stat.h>
 #include <zlib.h>
 
-#include <condition_variable>
-#include <deque>
 #include <functional>
-#include <thread>
 
 namespace {
 using np2h::Np2Error;
@@ -48,88 +47,8 @@ struct Piece {
     size_t n = 0;
     np2h::QcPiece qc; // with the quality filter: qc.seq == buf, the quality bytes and the separators beside it
 };
-struct PieceQueue {
-    std::mutex mu;
-    std::condition_variable cv;
-    std::deque<Piece *> full, idle;
-    int producers = 0;
-    bool abort = false;
-    int err_code = NP2_OK;
-    std::string err;
-    Piece *take_idle() { // reader side; nullptr: the run was given up
-        std::unique_lock<std::mutex> l(mu);
-        cv.wait(l, [&] { return abort || !idle.empty(); });
-        if (abort) return nullptr;
-        Piece *p = idle.front();
-        idle.pop_front();
-        return p;
-    }
-    void give_full(Piece *p) {
-        std::lock_guard<std::mutex> l(mu);
-        full.push_back(p);
-        cv.notify_all();
-    }
-    Piece *take_full() { // counting side; nullptr: every reader has finished and nothing is left
-        std::unique_lock<std::mutex> l(mu);
-        cv.wait(l, [&] { return !full.empty() || producers == 0; });
-        if (full.empty()) return nullptr;
-        Piece *p = full.front();
-        full.pop_front();
-        return p;
-    }
-    void give_idle(Piece *p) {
-        std::lock_guard<std::mutex> l(mu);
-        idle.push_back(p);
-        cv.notify_all();
-    }
-    void producer_done(int code, const std::string &m) {
-        std::lock_guard<std::mutex> l(mu);
-        if (code != NP2_OK && err_code == NP2_OK) err_code = code, err = m, abort = true;
-        --producers;
-        cv.notify_all();
-    }
-    void give_up() {
-        std::lock_guard<std::mutex> l(mu);
-        abort = true;
-        cv.notify_all();
-    }
-};
-
-// what a reader thread writes its stream into: pieces of `cap` bytes, each with the stream's last HALO bytes in front
-struct PieceWriter {
-    PieceQueue &q;
-    size_t cap;
-    Piece *cur = nullptr;
-    uint8_t tail[HALO];
-    bool dead = false;
-    PieceWriter(PieceQueue &q_, size_t cap_) : q(q_), cap(cap_) { memset(tail, '\n', HALO); }
-    bool fresh() {
-        cur = q.take_idle();
-        if (!cur) return !(dead = true);
-        memcpy(cur->buf, tail, HALO);
-        cur->n = 0;
-        return true;
-    }
-    void flush() {
-        if (!cur) return;
-        if (cur->n == 0) {
-            q.give_idle(cur);
-        } else {
-            memcpy(tail, cur->buf + cur->n, HALO); // the last HALO bytes of halo + data
-            q.give_full(cur);
-        }
-        cur = nullptr;
-    }
-    void put(const uint8_t *p, size_t n) {
-        while (n && !dead) {
-            if (!cur && !fresh()) return;
-            const size_t take = std::min(n, cap - cur->n);
-            memcpy(cur->buf + HALO + cur->n, p, take);
-            cur->n += take, p += take, n -= take;
-            if (cur->n == cap) flush();
-        }
-    }
-};
+using PieceQueue = np2h::PieceQueue<Piece>;
+using PieceWriter = np2h::HaloWriter<Piece>; // what a reader thread writes its stream into
 
 // ---------------------------------------------------------------------------------------------------------------
 // the run
@@ -148,9 +67,9 @@ struct Hooks {
     size_t piece = (size_t)8 << 20;
     uint32_t passes = 0;
     Hooks() { // read once per call, like the other NP2_* switches
-        if (const char *e = getenv("NP2_KCOUNT_TEST_CAP_LOG2")) cap_log2 = (uint32_t)std::min(30, std::max(4, atoi(e)));
-        if (const char *e = getenv("NP2_KCOUNT_TEST_PIECE")) piece = (size_t)std::max(64L, atol(e));
-        if (const char *e = getenv("NP2_KCOUNT_TEST_PASSES")) passes = (uint32_t)std::min(1024, std::max(1, atoi(e)));
+        cap_log2 = (uint32_t)np2h::test_hook("NP2_KCOUNT_TEST_CAP_LOG2", 4, 30, cap_log2);
+        piece = (size_t)np2h::test_hook("NP2_KCOUNT_TEST_PIECE", 64, LLONG_MAX, (long long)piece);
+        passes = (uint32_t)np2h::test_hook("NP2_KCOUNT_TEST_PASSES", 1, 1024, passes);
     }
 };
 
@@ -195,15 +114,13 @@ struct Counter {
     np2h::DevBuf<uint8_t> d_in;
     np2h::DevBuf<uint64_t> d_ctr, d_spill[2];
     np2h::PinnedBuf pin_ctr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    np2h::DevEvent ev0, ev1;
     Stats stats;
     bool qc = false; // the quality filter runs in front of the count kernel
     np2h::SrqcDev qcd;
     uint64_t qc_totals[np2srqc::N_TOTALS] = {0, 0, 0, 0, 0, 0, 0};
 
     ~Counter() {
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
         if (st && own_stream) {
             (void)hipStreamSynchronize(st);
             (void)hipStreamDestroy(st);
@@ -216,8 +133,7 @@ struct Counter {
             HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
             own_stream = true;
         }
-        HIPCHK(hipEventCreate(&ev0));
-        HIPCHK(hipEventCreate(&ev1));
+        ev0.make(), ev1.make();
         budget = mem_bytes;
         if (!budget) {
             size_t fr = 0, tot = 0;
@@ -276,21 +192,18 @@ struct Counter {
         }
     }
     void count_piece(Piece &pc) {
-        const size_t n = pc.n, padded = (HALO + n + 15) & ~(size_t)15;
-        memset(pc.buf + HALO + n, '\n', padded - (HALO + n));
-        HIPCHK(hipMemcpyAsync(d_in.p, pc.buf, padded, hipMemcpyHostToDevice, st));
+        const size_t n = pc.n;
+        HIPCHK(hipMemcpyAsync(d_in.p, pc.buf, np2h::pad_piece(pc.buf, n), hipMemcpyHostToDevice, st));
         if (qc) qcd.run(st, d_in.p, pc.qc, nullptr);
         for (size_t ki = 0; ki < tabs.size(); ++ki) {
             KTable &t = tabs[ki];
             while (t.claimed + n > ((uint64_t)(hi - lo) << t.cap_log2) / 2) grow(ki);
             HIPCHK(hipMemsetAsync(ctr(ki) + np2::KC_SPILLED, 0, 8, st));
-            HIPCHK(hipEventRecord(ev0, st));
+            HIPCHK(hipEventRecord(ev0.e, st));
             np2::launch_kcount(st, d_in.p, n, t.k, kt(t), ctr(ki), d_spill[0].p);
-            HIPCHK(hipEventRecord(ev1, st));
+            HIPCHK(hipEventRecord(ev1.e, st));
             const uint64_t *c = read_ctr(ki);
-            float ms = 0;
-            HIPCHK(hipEventElapsedTime(&ms, ev0, ev1));
-            stats.kernel_ms += ms;
+            stats.kernel_ms += np2h::elapsed(ev0, ev1);
             t.claimed = c[np2::KC_CLAIMED];
             t.kmers = c[np2::KC_KMERS];
             uint64_t n_spill = c[np2::KC_SPILLED];
@@ -314,75 +227,45 @@ struct Counter {
         PieceQueue q;
         const size_t n_threads = src.mem ? 1 : std::min<size_t>(src.paths.size(), 16);
         std::vector<Piece> pieces(2 * n_threads);
-        struct Release {
-            std::vector<Piece> &v;
-            ~Release() {
-                for (auto &p : v) {
-                    if (p.buf) np2h::pinned_pool().put(p.buf);
-                    if (p.qc.qual) np2h::pinned_pool().put(p.qc.qual);
-                }
-            }
-        } release{pieces};
+        np2h::PinnedBlocks pinned;
         for (auto &p : pieces) {
-            p.buf = (uint8_t *)np2h::pinned_pool().get(HALO + hooks.piece + 64);
-            if (!p.buf) throw Np2Error(NP2_E_NOMEM, "hipHostMalloc failed");
+            p.buf = pinned.get(HALO + hooks.piece + 64);
             if (qc) {
                 p.qc.seq = p.buf, p.qc.owner = &p;
-                p.qc.qual = (uint8_t *)np2h::pinned_pool().get(HALO + hooks.piece + 64);
-                if (!p.qc.qual) throw Np2Error(NP2_E_NOMEM, "hipHostMalloc failed");
+                p.qc.qual = pinned.get(HALO + hooks.piece + 64);
             }
             q.idle.push_back(&p);
         }
-        q.producers = (int)n_threads;
-        std::vector<std::thread> th;
-        struct Join {
-            PieceQueue &q;
-            std::vector<std::thread> &th;
-            ~Join() {
-                q.give_up();
-                for (auto &t : th) t.join();
-            }
-        } join{q, th};
-        for (size_t ti = 0; ti < n_threads; ++ti)
-            th.emplace_back([&, ti] {
-                int code = NP2_OK;
-                std::string msg;
-                try {
-                    if (qc) { // both streams, in pieces that end at a read boundary
-                        np2h::QcAssembler as(hooks.piece, false);
-                        as.take = [&]() -> np2h::QcPiece * {
-                            Piece *p = q.take_idle();
-                            return p ? &p->qc : nullptr;
-                        };
-                        as.full = [&](np2h::QcPiece *c) {
-                            Piece *p = (Piece *)c->owner;
-                            p->n = c->n;
-                            q.give_full(p);
-                        };
-                        as.unused = [&](np2h::QcPiece *c) { q.give_idle((Piece *)c->owner); };
-                        for (size_t fi = ti; fi < src.paths.size() && !as.dead; fi += n_threads) as.file(src.paths[fi]);
-                        as.flush();
-                    } else {
-                        PieceWriter w(q, hooks.piece);
-                        auto put = [&](const uint8_t *p, size_t n) { w.put(p, n); };
-                        if (src.mem) {
-                            put(src.mem, src.mem_n);
-                            static const uint8_t NL = '\n';
-                            put(&NL, 1);
-                        } else {
-                            for (size_t fi = ti; fi < src.paths.size() && !w.dead; fi += n_threads) {
-                                parse_file(src.paths[fi], put, [&] { return w.dead; }); // (its stream ends with a separator)
-                            }
-                        }
-                        w.flush();
+        auto readers = np2h::run_readers(n_threads, q, [&](size_t ti) {
+            if (qc) { // both streams, in pieces that end at a read boundary
+                np2h::QcAssembler as(hooks.piece, false);
+                as.take = [&]() -> np2h::QcPiece * {
+                    Piece *p = q.take_idle();
+                    return p ? &p->qc : nullptr;
+                };
+                as.full = [&](np2h::QcPiece *c) {
+                    Piece *p = (Piece *)c->owner;
+                    p->n = c->n;
+                    q.give_full(p);
+                };
+                as.unused = [&](np2h::QcPiece *c) { q.give_idle((Piece *)c->owner); };
+                for (size_t fi = ti; fi < src.paths.size() && !as.dead; fi += n_threads) as.file(src.paths[fi]);
+                as.flush();
+            } else {
+                PieceWriter w(q, hooks.piece);
+                auto put = [&](const uint8_t *p, size_t n) { w.put(p, n); };
+                if (src.mem) {
+                    put(src.mem, src.mem_n);
+                    static const uint8_t NL = '\n';
+                    put(&NL, 1);
+                } else {
+                    for (size_t fi = ti; fi < src.paths.size() && !w.dead; fi += n_threads) {
+                        parse_file(src.paths[fi], put, [&] { return w.dead; }); // (its stream ends with a separator)
                     }
-                } catch (const Np2Error &e) {
-                    code = e.code, msg = e.what();
-                } catch (const std::exception &e) {
-                    code = NP2_E_NOMEM, msg = e.what();
                 }
-                q.producer_done(code, msg);
-            });
+                w.flush();
+            }
+        });
         for (;;) { // read_ms: what the counting thread waits for its readers (the part of the pass the input bounds)
             const double t0 = np2h::now_ms();
             Piece *p = q.take_full();

@@ -2,6 +2,7 @@
 // size, np2_qv_device scans one sequence where a polish left it.  (np2_qv.cpp would share the kernel file's object name.)
 #include "np2_ctx.hpp"
 #include "np2_kernel_timer.hpp"
+#include "np2_pieces.hpp"
 #include "np2_qv.hpp"
 
 using namespace np2qv;
@@ -10,18 +11,11 @@ using np2kc::HALO;
 namespace {
 
 // tiles of the staging buffer (32 MiB of sequence per piece); NP2_QV_TEST_STAGE_TILES: a test's smaller pieces
-uint32_t stage_tiles() {
-    if (const char *e = getenv("NP2_QV_TEST_STAGE_TILES")) return (uint32_t)std::min<long>(1 << 16, std::max<long>(1, atol(e)));
-    return 4096;
-}
+uint32_t stage_tiles() { return (uint32_t)test_hook("NP2_QV_TEST_STAGE_TILES", 1, 1 << 16, 4096); }
 
 // the grid: what the device holds at once (the kernel's registers admit 4 wavefronts per SIMD: 4 blocks per CU), blocks
 // striding over the tiles
-uint32_t qv_blocks(int device) {
-    int cus = 0;
-    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-    return (uint32_t)std::max(1, cus) * 4u;
-}
+uint32_t qv_blocks(int device) { return grid_blocks(device, 4); }
 
 struct QvBufs { // released after the call's device work has completed: cached blocks (DevCache)
     DevBuf<uint8_t> stage;
@@ -29,12 +23,6 @@ struct QvBufs { // released after the call's device work has completed: cached b
     DevBuf<uint64_t> stats, hist;
     QvBufs() { stage.cached = desc.cached = bits.cached = stats.cached = hist.cached = true; }
 };
-
-void check_table(np2_ctx *cx, int yak_idx, const char *who) {
-    if (yak_idx < 0 || (size_t)yak_idx >= cx->yaks.size())
-        throw Np2Error(NP2_E_ARG, std::string(who) + ": yak_idx " + std::to_string(yak_idx) + " out of range (the context has " +
-                                      std::to_string(cx->yaks.size()) + " tables)");
-}
 
 } // namespace
 
@@ -45,12 +33,9 @@ int np2_qv_strings(np2_ctx_t *cx, int yak_idx, const uint8_t *strs, const uint64
     if (!cx) return NP2_E_ARG;
     return abi_guard([&] {
         // every argument is checked before anything is launched
-        check_table(cx, yak_idx, "np2_qv_strings");
+        check_table(cx, yak_idx, "np2_qv_strings", "yak_idx");
         if (!out) throw Np2Error(NP2_E_ARG, "np2_qv_strings: out is NULL");
-        if (n && !off) throw Np2Error(NP2_E_ARG, "np2_qv_strings: off is NULL with n > 0");
-        for (uint64_t i = 0; i < n; ++i)
-            if (off[i + 1] < off[i]) throw Np2Error(NP2_E_ARG, "np2_qv_strings: off is descending at sequence " + std::to_string(i));
-        if (n && off[n] > off[0] && !strs) throw Np2Error(NP2_E_ARG, "np2_qv_strings: strs is NULL with a non-zero length");
+        check_string_set("np2_qv_strings", strs, off, n);
         if (kernel_ms) *kernel_ms = 0.f;
         if (hist) memset(hist, 0, QV_HIST_BINS * sizeof(uint64_t));
         for (uint64_t i = 0; i < n; ++i) out[i] = np2_qv_t{0, 0};
@@ -71,48 +56,16 @@ int np2_qv_strings(np2_ctx_t *cx, int yak_idx, const uint8_t *strs, const uint64
             d.hist.ensure(QV_HIST_BINS);
             HIPCHK(hipMemsetAsync(d.hist.p, 0, QV_HIST_BINS * 8, cx->stream));
         }
-        std::vector<uint8_t> hs(HALO + (size_t)cap * QV_TILE), hb(absent_bits ? (size_t)cap * QV_TILE_BITS : 0);
-        std::vector<uint32_t> hd(cap);
+        std::vector<uint8_t> hb(absent_bits ? (size_t)cap * QV_TILE_BITS : 0);
         std::vector<uint64_t> hst(2 * (size_t)cap);
         KernelTimer timer(kernel_ms != nullptr);
-
-        struct Span { // a sequence's tiles in the piece, from tile0 on: the piece's counters `index in spans` are its own
-            uint64_t seq, bit_at, bit_bytes;
-            uint32_t tile0;
-        };
-        std::vector<Span> spans;
-        uint64_t i = 0, p = 0, bit_base = 0; // sequence, bytes of it already scanned, its first bitmap byte
-        while (i < n) {
-            // a piece: whole tiles of consecutive sequences, each starting at a tile boundary; a sequence longer than what
-            // is left of the piece goes on in the next one, whose halo then holds the 32 bytes before it
-            uint32_t nt = 0;
-            spans.clear();
-            if (p && p < off[i + 1] - off[i])
-                memcpy(hs.data(), strs + off[i] + p - HALO, HALO);
-            else
-                memset(hs.data(), QV_PAD, HALO);
-            while (i < n && nt < cap) {
-                const uint64_t len = off[i + 1] - off[i];
-                if (p >= len) {
-                    bit_base += bits_bytes(len);
-                    ++i;
-                    p = 0;
-                    continue;
-                }
-                const uint32_t take = (uint32_t)std::min<uint64_t>(tiles_of(len - p), cap - nt);
-                const uint64_t bytes = std::min<uint64_t>(len - p, (uint64_t)take * QV_TILE);
-                uint8_t *dst = hs.data() + HALO + (size_t)nt * QV_TILE;
-                memcpy(dst, strs + off[i] + p, bytes);
-                memset(dst + bytes, QV_PAD, (size_t)take * QV_TILE - bytes);
-                for (uint32_t x = 0; x < take; ++x) hd[nt + x] = (uint32_t)spans.size() | (p == 0 && x == 0 ? QV_FIRST : 0u);
-                spans.push_back({i, bit_base + p / 8, std::min<uint64_t>(bits_bytes(len) - p / 8, (uint64_t)take * QV_TILE_BITS), nt});
-                nt += take;
-                p += (uint64_t)take * QV_TILE;
-            }
-            if (nt == 0) break;
+        StringPieces sp(strs, off, n, cap, QV_TILE, HALO, QV_PAD, QV_FIRST, QV_TILE_BITS);
+        while (sp.next()) {
+            const uint32_t nt = sp.nt;
+            const auto &spans = sp.spans;
             const uint64_t n_rel = spans.size(); // (<= nt: every span has a tile)
-            HIPCHK(hipMemcpyAsync(d.stage.p, hs.data(), HALO + (size_t)nt * QV_TILE, hipMemcpyHostToDevice, cx->stream));
-            HIPCHK(hipMemcpyAsync(d.desc.p, hd.data(), (size_t)nt * 4, hipMemcpyHostToDevice, cx->stream));
+            HIPCHK(hipMemcpyAsync(d.stage.p, sp.hs.data(), HALO + (size_t)nt * QV_TILE, hipMemcpyHostToDevice, cx->stream));
+            HIPCHK(hipMemcpyAsync(d.desc.p, sp.hd.data(), (size_t)nt * 4, hipMemcpyHostToDevice, cx->stream));
             HIPCHK(hipMemsetAsync(d.stats.p, 0, n_rel * 16, cx->stream));
             QvScan q{};
             q.src = d.stage.p + HALO;
@@ -137,7 +90,7 @@ int np2_qv_strings(np2_ctx_t *cx, int yak_idx, const uint8_t *strs, const uint64
                 out[spans[r].seq].n_absent += hst[2 * r + 1];
             }
             if (absent_bits)
-                for (const Span &s : spans) memcpy(absent_bits + s.bit_at, hb.data() + (size_t)s.tile0 * QV_TILE_BITS, s.bit_bytes);
+                for (const auto &s : spans) memcpy(absent_bits + s.bit_at, hb.data() + (size_t)s.tile0 * QV_TILE_BITS, s.bit_bytes);
         }
         if (hist) {
             HIPCHK(hipMemcpyAsync(hist, d.hist.p, QV_HIST_BINS * 8, hipMemcpyDeviceToHost, cx->stream));
@@ -152,7 +105,7 @@ int np2_qv_device(np2_ctx_t *cx, int yak_idx, const uint8_t *dev_seq, uint64_t l
                   uint64_t *hist, uint8_t *absent_bits, float *kernel_ms) {
     if (!cx) return NP2_E_ARG;
     return abi_guard([&] {
-        check_table(cx, yak_idx, "np2_qv_device");
+        check_table(cx, yak_idx, "np2_qv_device", "yak_idx");
         if (!out) throw Np2Error(NP2_E_ARG, "np2_qv_device: out is NULL");
         if (len && !dev_seq) throw Np2Error(NP2_E_ARG, "np2_qv_device: dev_seq is NULL with a non-zero length");
         if (tiles_of(len) >= QV_FIRST) throw Np2Error(NP2_E_ARG, "np2_qv_device: the sequence is too long");

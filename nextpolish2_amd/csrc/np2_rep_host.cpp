@@ -12,6 +12,8 @@
 #include "../../include/np2_io.h"
 #include "np2_ctx.hpp"
 #include "np2_kcount.hpp"
+#include "np2_kernel_timer.hpp"
+#include "np2_pieces.hpp"
 #include "np2_rep.hpp"
 #include "np2_rep_core.hpp"
 #include "np2_seqreader.hpp"
@@ -49,23 +51,12 @@ struct Hooks {
     size_t piece = (size_t)8 << 20;
     bool collapse = true;
     Hooks() { // read once per call, like the other NP2_* switches
-        if (const char *e = getenv("NP2_REP_TEST_PIECE")) piece = (size_t)std::max(64L, atol(e));
+        piece = (size_t)np2h::test_hook("NP2_REP_TEST_PIECE", 64, LLONG_MAX, (long long)piece);
         collapse = getenv("NP2_REP_NO_COLLAPSE") == nullptr; // (tools/rep_probe.py's A/B)
     }
 };
 
-struct Event {
-    hipEvent_t e = nullptr;
-    ~Event() {
-        if (e) (void)hipEventDestroy(e);
-    }
-    void make() { HIPCHK(hipEventCreate(&e)); }
-};
-float elapsed(const Event &a, const Event &b) {
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, a.e, b.e));
-    return ms;
-}
+using np2h::elapsed;
 
 struct Run {
     int device = 0;
@@ -93,16 +84,10 @@ struct Run {
         HIPCHK(hipSetDevice(device));
         table_n = np2rep::table_size(o.k);
         const size_t chunks = (size_t)np2::rep_chunks(table_n) + 1;
-        const size_t need = table_n * 4 + chunks * 8 + np2::prim_temp_bytes(chunks) + hooks.piece + ((size_t)64 << 20);
-        size_t fr = 0, tot = 0;
-        HIPCHK(hipMemGetInfo(&fr, &tot));
-        if (need > fr) {
-            np2h::dev_cache().trim(0); // (this process's idle blocks may be what is missing)
-            HIPCHK(hipMemGetInfo(&fr, &tot));
-        }
-        if (need > fr)
-            throw Np2Error(NP2_E_NOMEM, "the counter table for k = " + std::to_string(o.k) + " takes " + std::to_string(table_n * 4) +
-                                            " bytes and does not fit the device's free memory (" + std::to_string(fr) + " bytes)");
+        np2h::need_device_bytes(table_n * 4 + chunks * 8 + np2::prim_temp_bytes(chunks) + hooks.piece, (size_t)64 << 20, [&](size_t fr) {
+            return "the counter table for k = " + std::to_string(o.k) + " takes " + std::to_string(table_n * 4) +
+                   " bytes and does not fit the device's free memory (" + std::to_string(fr) + " bytes)";
+        });
         HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
         if (hipMalloc((void **)&table, table_n * 4) != hipSuccess) {
             (void)hipGetLastError();
@@ -116,24 +101,31 @@ struct Run {
     }
 };
 
-// the stream, piece by piece, into the counters
+// the stream, piece by piece, into the counters: the writer's two pieces are this thread's own, filled and counted in turn
 struct Feeder {
+    struct Piece {
+        uint8_t *buf = nullptr;
+        size_t n = 0;
+    };
     Run &r;
     np2h::PinnedBuf pinned[2];
-    uint8_t *pin[2] = {nullptr, nullptr};
-    Event k0[2], k1[2];
+    Piece pc[2];
+    np2h::DevEvent k0[2], k1[2];
     bool in_flight[2] = {false, false};
     int cur = 0;
-    size_t n = 0;
     uint64_t stream_bytes = 0;
-    uint8_t tail[HALO];
-    explicit Feeder(Run &r_) : r(r_) {
-        memset(tail, '\n', HALO);
+    np2h::HaloWriter<Piece> w;
+    explicit Feeder(Run &r_) : r(r_), w(r_.hooks.piece) {
         for (int b = 0; b < 2; ++b) {
-            pin[b] = (uint8_t *)pinned[b].ensure(HALO + r.hooks.piece + 64);
+            pc[b].buf = (uint8_t *)pinned[b].ensure(HALO + r.hooks.piece + 64);
             k0[b].make(), k1[b].make();
         }
-        memcpy(pin[0], tail, HALO);
+        w.take = [this] {
+            retire(cur);
+            return &pc[cur];
+        };
+        w.full = [this](Piece *p) { count(*p); };
+        w.unused = [](Piece *) {};
     }
     ~Feeder() { (void)hipStreamSynchronize(r.st); } // (a copy out of a pinned buffer may be in flight when an exception unwinds)
     void retire(int b) { // the piece that last used buffer b has been copied and counted
@@ -142,34 +134,19 @@ struct Feeder {
         r.stats.count_ms += elapsed(k0[b], k1[b]);
         in_flight[b] = false;
     }
-    void flush() {
-        if (n == 0) return;
-        stream_bytes += n;
+    void count(Piece &p) { // (p is pc[cur])
+        stream_bytes += p.n;
         check_kmers(stream_bytes, r.o.k);
-        uint8_t *p = pin[cur];
-        const size_t padded = (HALO + n + 15) & ~(size_t)15;
-        memset(p + HALO + n, '\n', padded - (HALO + n));
-        memcpy(tail, p + n, HALO); // the last HALO bytes of halo + data
-        HIPCHK(hipMemcpyAsync(r.d_in.p, p, padded, hipMemcpyHostToDevice, r.st));
+        HIPCHK(hipMemcpyAsync(r.d_in.p, p.buf, np2h::pad_piece(p.buf, p.n), hipMemcpyHostToDevice, r.st));
         HIPCHK(hipEventRecord(k0[cur].e, r.st));
-        np2::launch_rep_count(r.st, r.d_in.p, n, r.o.k, r.table, r.hooks.collapse);
+        np2::launch_rep_count(r.st, r.d_in.p, p.n, r.o.k, r.table, r.hooks.collapse);
         HIPCHK(hipEventRecord(k1[cur].e, r.st));
         in_flight[cur] = true;
         cur ^= 1;
-        retire(cur);
-        memcpy(pin[cur], tail, HALO);
-        n = 0;
     }
-    void put(const uint8_t *p, size_t len) {
-        while (len) {
-            const size_t take = std::min(len, r.hooks.piece - n);
-            memcpy(pin[cur] + HALO + n, p, take);
-            n += take, p += take, len -= take;
-            if (n == r.hooks.piece) flush();
-        }
-    }
+    void put(const uint8_t *p, size_t len) { w.put(p, len); }
     void finish() {
-        flush();
+        w.flush();
         retire(0), retire(1);
         HIPCHK(hipGetLastError());
     }
@@ -178,9 +155,7 @@ struct Feeder {
 // counters -> threshold -> the list on the host
 void select_and_emit(Run &r) {
     hipStream_t st = r.st;
-    int cus = 0;
-    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, r.device));
-    const uint32_t blocks = (uint32_t)std::max(1, cus) * 8u; // 16 KiB of LDS a block
+    const uint32_t blocks = np2h::grid_blocks(r.device, 8); // 16 KiB of LDS a block
     np2h::DevBuf<uint32_t> d_hist; // high halves, then low halves
     np2h::DevBuf<unsigned long long> d_ctr;
     np2h::DevBuf<uint32_t> d_sizes, d_off, d_index, d_count;
@@ -191,7 +166,7 @@ void select_and_emit(Run &r) {
     np2h::PinnedBuf pin;
     uint32_t *h_hist = (uint32_t *)pin.ensure(2 * np2::REP_HALF * 4 + np2::REP_N_CTR * 8 + 8);
     unsigned long long *h_ctr = (unsigned long long *)(h_hist + 2 * np2::REP_HALF);
-    Event e0, e1;
+    np2h::DevEvent e0, e1;
     e0.make(), e1.make();
 
     HIPCHK(hipMemsetAsync(d_hist.p, 0, 2 * np2::REP_HALF * 4, st));

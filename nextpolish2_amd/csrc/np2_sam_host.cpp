@@ -9,6 +9,7 @@
 #include "../../include/np2_io.h"
 #include "np2_ctx.hpp"
 #include "np2_kcount.hpp"
+#include "np2_kernel_timer.hpp"
 #include "np2_sam.hpp"
 
 #include <zlib.h>
@@ -41,7 +42,7 @@ struct Hooks {
     size_t piece = (size_t)32 << 20;
     bool profile = false; // NP2_SAM_PROFILE: one line on stderr with the kernels' times apart (tools/sam_probe.py)
     Hooks() { // read once per call, like the other NP2_* switches
-        if (const char *e = getenv("NP2_SAM_TEST_PIECE")) piece = (size_t)std::min<long long>(1ll << 30, std::max<long long>(64, atoll(e)));
+        piece = (size_t)np2h::test_hook("NP2_SAM_TEST_PIECE", 64, 1ll << 30, (long long)piece);
         profile = getenv("NP2_SAM_PROFILE") != nullptr;
     }
 };
@@ -249,32 +250,14 @@ struct Reader {
     }
 };
 
-struct Event {
-    hipEvent_t e = nullptr;
-    ~Event() {
-        if (e) (void)hipEventDestroy(e);
-    }
-    void make() { HIPCHK(hipEventCreate(&e)); }
-};
-float elapsed(const Event &a, const Event &b) {
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, a.e, b.e));
-    return ms;
-}
+using np2h::elapsed;
 
 // room for `bytes` more on the device, or NP2_E_NOMEM saying how much was needed
 void need_device(size_t bytes, const char *what) {
-    const size_t margin = (size_t)64 << 20;
-    size_t fr = 0, tot = 0;
-    HIPCHK(hipMemGetInfo(&fr, &tot));
-    if (bytes + margin > fr) {
-        np2h::dev_cache().trim(0); // (this process's idle blocks may be what is missing)
-        HIPCHK(hipMemGetInfo(&fr, &tot));
-    }
-    if (bytes + margin > fr)
-        throw Np2Error(NP2_E_NOMEM, std::string("the SAM's ") + what + " need a block of " + std::to_string(bytes) +
-                                        " bytes, and the device has " + std::to_string(fr) + " bytes free: the packed SEQ, the CIGAR words and "
-                                        "the records of a SAM input must fit one device's memory");
+    np2h::need_device_bytes(bytes, (size_t)64 << 20, [&](size_t fr) {
+        return std::string("the SAM's ") + what + " need a block of " + std::to_string(bytes) + " bytes, and the device has " +
+               std::to_string(fr) + " bytes free: the packed SEQ, the CIGAR words and the records of a SAM input must fit one device's memory";
+    });
 }
 template <class T> void take_over(DevBuf<T> &a, DevBuf<T> &b) { // a <- b's block, b <- a's
     std::swap(a.p, b.p), std::swap(a.cap, b.cap), std::swap(a.cached, b.cached), std::swap(a.cache_bytes, b.cache_bytes),
@@ -316,7 +299,7 @@ struct Build {
     np2sam::NameTab nt{};
     bool have_nt = false;
     np2h::PinnedBuf pin;
-    Event e0, e1, e_mid;
+    np2h::DevEvent e0, e1, e_mid;
     float lines_ms = 0;    // k_sam_lines alone, of parse_ms
     uint64_t text_bytes = 0;
 

@@ -8,6 +8,7 @@
 #include "np2_srqc_host.hpp"
 
 #include "np2_kcount.hpp"
+#include "np2_kernel_timer.hpp"
 
 namespace {
 using np2h::Np2Error;
@@ -47,9 +48,7 @@ struct Runner {
     }
     // the filter over `pc`; `reads` holds the results, pc.seq the masked bytes (with `masked`) when it returns
     void run(bool masked) {
-        const size_t padded = (QC_FRONT + pc.n + 15) & ~(size_t)15;
-        memset(pc.seq + QC_FRONT + pc.n, '\n', padded - (QC_FRONT + pc.n));
-        HIPCHK(hipMemcpyAsync(d_seq.p, pc.seq, padded, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_seq.p, pc.seq, np2h::pad_piece(pc.seq, pc.n), hipMemcpyHostToDevice, st));
         reads.resize(pc.ends.size());
         dev.run(st, d_seq.p, pc, reads.data());
         if (masked) HIPCHK(hipMemcpyAsync(pc.seq + QC_FRONT, d_seq.p + QC_FRONT, pc.n, hipMemcpyDeviceToHost, st));
@@ -60,27 +59,6 @@ struct Runner {
 void add_totals(uint64_t *sum, const uint64_t *t) {
     for (uint32_t i = 0; i < np2srqc::N_TOTALS; ++i) sum[i] += t[i];
 }
-
-struct OutFile {
-    std::string path;
-    FILE *f = nullptr;
-    ~OutFile() {
-        if (f) fclose(f);
-    }
-    void open(const std::string &p) {
-        path = p;
-        f = fopen(p.c_str(), "wb");
-        if (!f) throw Np2Error(NP2_E_ARG, "cannot open " + p + " for writing");
-    }
-    void put(const void *p, size_t n) {
-        if (n && fwrite(p, 1, n, f) != n) throw Np2Error(NP2_E_ARG, "cannot write " + path);
-    }
-    void close() {
-        FILE *g = f;
-        f = nullptr;
-        if (g && fclose(g) != 0) throw Np2Error(NP2_E_ARG, "cannot write " + path);
-    }
-};
 
 } // namespace
 
@@ -95,8 +73,7 @@ void np2h::srqc_publish(const uint64_t *totals, float kernel_ms) {
     g_last.kernel_ms = kernel_ms;
 }
 size_t np2h::srqc_piece_bytes() {
-    size_t piece = (size_t)8 << 20;
-    if (const char *e = getenv("NP2_KCOUNT_TEST_PIECE")) piece = (size_t)std::max(64L, atol(e));
+    const size_t piece = (size_t)test_hook("NP2_KCOUNT_TEST_PIECE", 64, LLONG_MAX, 8 << 20);
     if (piece > ((size_t)1 << 31)) throw Np2Error(NP2_E_ARG, "NP2_KCOUNT_TEST_PIECE: at most 2147483648 with the quality filter");
     return piece;
 }
@@ -167,8 +144,8 @@ int np2_srqc_files(int device, const char *const *paths, int n_paths, const np2_
         uint64_t sum[np2srqc::N_TOTALS] = {0, 0, 0, 0, 0, 0, 0};
         float ms = 0;
         for (int fi = 0; fi < n_paths; ++fi) {
-            OutFile out;
-            if (out_paths && out_paths[fi]) out.open(out_paths[fi]);
+            np2h::OutFile out;
+            out.open(out_paths ? out_paths[fi] : nullptr);
             r.dev.zero(r.st);
             np2h::QcAssembler as(r.piece, out.f != nullptr);
             as.take = [&] { return &r.pc; };

@@ -3,6 +3,8 @@
 #pragma once
 #include "np2_ctx.hpp"
 #include "np2_kcount_core.hpp"
+#include "np2_kernel_timer.hpp"
+#include "np2_pieces.hpp"
 #include "np2_seqreader.hpp"
 #include "np2_srqc.hpp"
 
@@ -125,18 +127,13 @@ struct SrqcDev {
     DevBuf<uint32_t> d_ends;
     DevBuf<np2_srqc_read_t> d_reads;
     DevBuf<uint64_t> d_tot;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    DevEvent ev0, ev1;
     bool timed = false;
     float kernel_ms = 0;
-    ~SrqcDev() {
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-    }
     void init(hipStream_t st, size_t piece) {
         d_qual.ensure(QC_FRONT + piece + QC_BACK);
         d_tot.ensure(np2srqc::N_TOTALS);
-        HIPCHK(hipEventCreate(&ev0));
-        HIPCHK(hipEventCreate(&ev1));
+        ev0.make(), ev1.make();
         zero(st);
     }
     void zero(hipStream_t st) {
@@ -147,22 +144,21 @@ struct SrqcDev {
     // host room for pc.ends.size() results.  `pc` must stay as it is until `st` has been synchronised.
     void run(hipStream_t st, uint8_t *d_seq, QcPiece &pc, np2_srqc_read_t *reads) {
         collect();
-        const size_t padded = (QC_FRONT + pc.n + 15) & ~(size_t)15, n_reads = pc.ends.size();
-        memset(pc.qual + QC_FRONT + pc.n, '\n', padded - (QC_FRONT + pc.n));
-        HIPCHK(hipMemcpyAsync(d_qual.p, pc.qual, padded, hipMemcpyHostToDevice, st));
+        const size_t n_reads = pc.ends.size();
+        HIPCHK(hipMemcpyAsync(d_qual.p, pc.qual, pad_piece(pc.qual, pc.n), hipMemcpyHostToDevice, st));
         d_ends.ensure(n_reads + 1);
         HIPCHK(hipMemcpyAsync(d_ends.p, pc.ends.data(), n_reads * 4, hipMemcpyHostToDevice, st));
         if (reads) d_reads.ensure(n_reads + 1);
-        HIPCHK(hipEventRecord(ev0, st));
+        HIPCHK(hipEventRecord(ev0.e, st));
         np2::launch_srqc(st, d_seq + QC_FRONT, d_qual.p + QC_FRONT, d_ends.p, (uint32_t)n_reads, o, reads ? d_reads.p : nullptr, d_tot.p);
-        HIPCHK(hipEventRecord(ev1, st));
+        HIPCHK(hipEventRecord(ev1.e, st));
         timed = true;
         if (reads) HIPCHK(hipMemcpyAsync(reads, d_reads.p, n_reads * sizeof(np2_srqc_read_t), hipMemcpyDeviceToHost, st));
     }
     void collect() { // the last run's kernel time (its stream has been synchronised since)
         if (!timed) return;
         float ms = 0;
-        if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) kernel_ms += ms;
+        if (hipEventElapsedTime(&ms, ev0.e, ev1.e) == hipSuccess) kernel_ms += ms;
         timed = false;
     }
     void totals(hipStream_t st, uint64_t *out) { // (synchronises the stream)

@@ -3,6 +3,7 @@
 // the last marker of a sequence that goes on in the next piece stays on the device (TrioScan::carry).
 #include "np2_ctx.hpp"
 #include "np2_kernel_timer.hpp"
+#include "np2_pieces.hpp"
 #include "np2_trio.hpp"
 
 using namespace np2qv;
@@ -12,19 +13,11 @@ using np2kc::HALO;
 namespace {
 
 // tiles of the staging buffer (32 MiB of sequence per piece); NP2_TRIO_TEST_STAGE_TILES: a test's smaller pieces
-uint32_t stage_tiles() {
-    if (const char *e = getenv("NP2_TRIO_TEST_STAGE_TILES")) return (uint32_t)std::min<long>(1 << 16, std::max<long>(1, atol(e)));
-    return 4096;
-}
+uint32_t stage_tiles() { return (uint32_t)test_hook("NP2_TRIO_TEST_STAGE_TILES", 1, 1 << 16, 4096); }
 
 // the grid: what the device holds at once (4 blocks per CU, as the QV scan), blocks striding over the tiles;
 // NP2_TRIO_TEST_BLOCKS: a test's grid
-uint32_t trio_blocks(int device) {
-    if (const char *e = getenv("NP2_TRIO_TEST_BLOCKS")) return (uint32_t)std::min<long>(1 << 16, std::max<long>(1, atol(e)));
-    int cus = 0;
-    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-    return (uint32_t)std::max(1, cus) * 4u;
-}
+uint32_t trio_blocks(int device) { return grid_blocks(device, 4, "NP2_TRIO_TEST_BLOCKS"); }
 
 struct TrioBufs { // released after the call's device work has completed: cached blocks (DevCache)
     DevBuf<uint8_t> stage;
@@ -46,11 +39,8 @@ void add_to(np2_trio_t &o, const uint64_t *st) {
 
 // everything about the tables and the thresholds, before anything is launched
 void np2::trio_check_tables(np2_ctx *cx, int pat_idx, int mat_idx, uint16_t min_count, uint16_t mid_count, const std::string &who) {
-    const int n = (int)cx->yaks.size();
-    if (pat_idx < 0 || pat_idx >= n)
-        throw Np2Error(NP2_E_ARG, who + ": pat_idx " + std::to_string(pat_idx) + " out of range (the context has " + std::to_string(n) + " tables)");
-    if (mat_idx < 0 || mat_idx >= n)
-        throw Np2Error(NP2_E_ARG, who + ": mat_idx " + std::to_string(mat_idx) + " out of range (the context has " + std::to_string(n) + " tables)");
+    check_table(cx, pat_idx, who, "pat_idx");
+    check_table(cx, mat_idx, who, "mat_idx");
     if (pat_idx == mat_idx) throw Np2Error(NP2_E_ARG, who + ": pat_idx == mat_idx: the parents need a table each");
     if (cx->yaks[pat_idx].k != cx->yaks[mat_idx].k)
         throw Np2Error(NP2_E_ARG, who + ": the parental tables have different k (" + std::to_string(cx->yaks[pat_idx].k) + " and " +
@@ -69,10 +59,7 @@ int np2_trio_strings(np2_ctx_t *cx, int pat_idx, int mat_idx, const uint8_t *str
         // every argument is checked before anything is launched
         np2::trio_check_tables(cx, pat_idx, mat_idx, min_count, mid_count, "np2_trio_strings");
         if (!out) throw Np2Error(NP2_E_ARG, "np2_trio_strings: out is NULL");
-        if (n && !off) throw Np2Error(NP2_E_ARG, "np2_trio_strings: off is NULL with n > 0");
-        for (uint64_t i = 0; i < n; ++i)
-            if (off[i + 1] < off[i]) throw Np2Error(NP2_E_ARG, "np2_trio_strings: off is descending at sequence " + std::to_string(i));
-        if (n && off[n] > off[0] && !strs) throw Np2Error(NP2_E_ARG, "np2_trio_strings: strs is NULL with a non-zero length");
+        check_string_set("np2_trio_strings", strs, off, n);
         if (kernel_ms) *kernel_ms = 0.f;
         for (uint64_t i = 0; i < n; ++i) out[i] = np2_trio_t{};
         if (n == 0 || off[n] == off[0]) return NP2_OK;
@@ -91,49 +78,16 @@ int np2_trio_strings(np2_ctx_t *cx, int pat_idx, int mat_idx, const uint8_t *str
         if (pat_bits) d.pat_bits.ensure((size_t)cap * QV_BLOCK);
         if (mat_bits) d.mat_bits.ensure((size_t)cap * QV_BLOCK);
         HIPCHK(hipMemsetAsync(d.carry.p, 0, 4, cx->stream));
-        std::vector<uint8_t> hs(HALO + (size_t)cap * QV_TILE), hbp(pat_bits ? (size_t)cap * QV_TILE_BITS : 0),
-            hbm(mat_bits ? (size_t)cap * QV_TILE_BITS : 0);
-        std::vector<uint32_t> hd(cap);
+        std::vector<uint8_t> hbp(pat_bits ? (size_t)cap * QV_TILE_BITS : 0), hbm(mat_bits ? (size_t)cap * QV_TILE_BITS : 0);
         std::vector<uint64_t> hst(TRIO_STATS * (size_t)cap);
         KernelTimer timer(kernel_ms != nullptr);
-
-        struct Span { // a sequence's tiles in the piece, from tile0 on: the piece's counters `index in spans` are its own
-            uint64_t seq, bit_at, bit_bytes;
-            uint32_t tile0;
-        };
-        std::vector<Span> spans;
-        uint64_t i = 0, p = 0, bit_base = 0; // sequence, bytes of it already scanned, its first bitmap byte
-        while (i < n) {
-            // a piece: whole tiles of consecutive sequences, each starting at a tile boundary; a sequence longer than what
-            // is left of the piece goes on in the next one, whose halo then holds the 32 bytes before it
-            uint32_t nt = 0;
-            spans.clear();
-            if (p && p < off[i + 1] - off[i])
-                memcpy(hs.data(), strs + off[i] + p - HALO, HALO);
-            else
-                memset(hs.data(), QV_PAD, HALO);
-            while (i < n && nt < cap) {
-                const uint64_t len = off[i + 1] - off[i];
-                if (p >= len) {
-                    bit_base += bits_bytes(len);
-                    ++i;
-                    p = 0;
-                    continue;
-                }
-                const uint32_t take = (uint32_t)std::min<uint64_t>(tiles_of(len - p), cap - nt);
-                const uint64_t bytes = std::min<uint64_t>(len - p, (uint64_t)take * QV_TILE);
-                uint8_t *dst = hs.data() + HALO + (size_t)nt * QV_TILE;
-                memcpy(dst, strs + off[i] + p, bytes);
-                memset(dst + bytes, QV_PAD, (size_t)take * QV_TILE - bytes);
-                for (uint32_t x = 0; x < take; ++x) hd[nt + x] = (uint32_t)spans.size() | (p == 0 && x == 0 ? QV_FIRST : 0u);
-                spans.push_back({i, bit_base + p / 8, std::min<uint64_t>(bits_bytes(len) - p / 8, (uint64_t)take * QV_TILE_BITS), nt});
-                nt += take;
-                p += (uint64_t)take * QV_TILE;
-            }
-            if (nt == 0) break;
+        StringPieces sp(strs, off, n, cap, QV_TILE, HALO, QV_PAD, QV_FIRST, QV_TILE_BITS); // (the QV driver's pieces)
+        while (sp.next()) {
+            const uint32_t nt = sp.nt;
+            const auto &spans = sp.spans;
             const uint64_t n_rel = spans.size(); // (<= nt: every span has a tile)
-            HIPCHK(hipMemcpyAsync(d.stage.p, hs.data(), HALO + (size_t)nt * QV_TILE, hipMemcpyHostToDevice, cx->stream));
-            HIPCHK(hipMemcpyAsync(d.desc.p, hd.data(), (size_t)nt * 4, hipMemcpyHostToDevice, cx->stream));
+            HIPCHK(hipMemcpyAsync(d.stage.p, sp.hs.data(), HALO + (size_t)nt * QV_TILE, hipMemcpyHostToDevice, cx->stream));
+            HIPCHK(hipMemcpyAsync(d.desc.p, sp.hd.data(), (size_t)nt * 4, hipMemcpyHostToDevice, cx->stream));
             HIPCHK(hipMemsetAsync(d.stats.p, 0, n_rel * TRIO_STATS * 8, cx->stream));
             TrioScan q{};
             q.src = d.stage.p + HALO;
@@ -159,7 +113,7 @@ int np2_trio_strings(np2_ctx_t *cx, int pat_idx, int mat_idx, const uint8_t *str
             HIPCHK(hipStreamSynchronize(cx->stream)); // (the staging buffers are filled again for the next piece)
             timer.collect();
             for (uint64_t r = 0; r < n_rel; ++r) add_to(out[spans[r].seq], &hst[TRIO_STATS * r]);
-            for (const Span &s : spans) {
+            for (const auto &s : spans) {
                 if (pat_bits) memcpy(pat_bits + s.bit_at, hbp.data() + (size_t)s.tile0 * QV_TILE_BITS, s.bit_bytes);
                 if (mat_bits) memcpy(mat_bits + s.bit_at, hbm.data() + (size_t)s.tile0 * QV_TILE_BITS, s.bit_bytes);
             }

@@ -419,6 +419,34 @@ def polisher_from_reads(paths, ks, min_count=1, device=0, mem_bytes=0, qc=None):
     return p
 
 
+def sr_k_arg(parser, text):
+    """--sr_k's comma-separated k values, ascending (tables are ordered by k); anything else is the parser's error"""
+    try:
+        return sorted(int(k) for k in text.split(","))
+    except ValueError:
+        parser.error("--sr_k takes comma-separated integers")
+
+
+def add_table_args(p):
+    """where a report module's k-mer tables come from: yak dumps, or short reads counted on the device"""
+    p.add_argument("yak", nargs="*", metavar="k.yak", help="k-mer dumps in yak format")
+    p.add_argument("--sr", action="append", default=[], metavar="FILE", help="short reads (may repeat): count their k-mers on the GPU instead")
+    p.add_argument("--sr_k", default="21,31", metavar="K[,K...]", help="k-mer sizes counted from --sr [21,31]")
+    p.add_argument("--sr_min_count", type=int, default=2, metavar="N", help="drop k-mers of --sr counted fewer than N times [2]")
+
+
+def open_tables(parser, a):
+    """the arguments of add_table_args (and --device) -> (a Polisher with the tables in HBM, their k values in table order)"""
+    if a.sr:
+        ks = sr_k_arg(parser, a.sr_k)
+        return polisher_from_reads(a.sr, ks, min_count=a.sr_min_count, device=a.device), ks
+    try:
+        ks = sorted(check_yak_header(y) for y in a.yak)
+    except (ValueError, OSError) as e:
+        raise SystemExit(f"Error: {e}")
+    return polisher_from_yak_files([os.path.abspath(y) for y in a.yak], device=a.device), ks
+
+
 def kcount_last_stats():
     """np2_kcount_last_stats: figures of the last successful counting call on this thread."""
     L = _bind()

@@ -13,7 +13,6 @@ The helpers at the top need no device (qv_value, bed_intervals, format_rows); Qv
 Polisher.qv_strings."""
 import argparse
 import math
-import os
 import sys
 
 import numpy as np
@@ -111,12 +110,10 @@ class QvReport:
 
 
 def build_parser():
+    from . import io as np2io
     p = argparse.ArgumentParser(prog="nextpolish2_amd.qv", description="k-mer QV of an assembly against short-read k-mer tables")
     p.add_argument("fa", metavar="asm.fa[.gz]", help="assembly in [GZIP] FASTA format")
-    p.add_argument("yak", nargs="*", metavar="k.yak", help="k-mer dumps in yak format")
-    p.add_argument("--sr", action="append", default=[], metavar="FILE", help="short reads (may repeat): count their k-mers on the GPU instead")
-    p.add_argument("--sr_k", default="21,31", metavar="K[,K...]", help="k-mer sizes counted from --sr [21,31]")
-    p.add_argument("--sr_min_count", type=int, default=2, metavar="N", help="drop k-mers of --sr counted fewer than N times [2]")
+    np2io.add_table_args(p)
     p.add_argument("--qv_min_count", type=int, default=1, metavar="N", help="read a count below N as absent [1]")
     p.add_argument("--bed", default=None, metavar="FILE", help="intervals covered by absent k-mers (FILE.k<K> per table when there are several)")
     p.add_argument("--hist", default=None, metavar="FILE", help="count histogram: k, count, k-mers")
@@ -135,18 +132,7 @@ def main(argv=None):
     if not 0 <= a.qv_min_count <= 1023:
         parser.error("--qv_min_count: 0 .. 1023")
     try:
-        if a.sr:
-            try:
-                ks = sorted(int(k) for k in a.sr_k.split(","))
-            except ValueError:
-                parser.error("--sr_k takes comma-separated integers")
-            pol = np2io.polisher_from_reads(a.sr, ks, min_count=a.sr_min_count, device=a.device)
-        else:
-            try:
-                ks = sorted(np2io.check_yak_header(y) for y in a.yak)
-            except (ValueError, OSError) as e:
-                raise SystemExit(f"Error: {e}")
-            pol = np2io.polisher_from_yak_files([os.path.abspath(y) for y in a.yak], device=a.device)
+        pol, ks = np2io.open_tables(parser, a)
         rep = QvReport(ks, a.qv_min_count, want_bed=a.bed is not None, sides=("asm",), want_hist=a.hist is not None)
         for name, seq in np2io.read_fasta(a.fa):
             rep.add(pol, name, seq)

@@ -250,3 +250,25 @@ def test_two_runs_give_identical_bytes(tmp_path):
     words, off = numpy_count(stream, 21, 1)
     y = np2io.load_yak(outs[0][0])
     assert np.array_equal(y.words, words) and np.array_equal(y.bucket_off, off) and int((words & np.uint64(1023)).max()) == 1023
+
+
+# ---- 12. a reader fails in mid-run ---------------------------------------------------------------------------------------------
+def test_reader_failure_in_mid_run_is_returned_and_the_next_call_counts(tmp_path, monkeypatch):
+    """Three reader threads and pieces of 256 bytes; the second file is a gzip cut in the middle, so its reader stops with an
+    error while the other two fill pieces and the counting thread launches them.  The call returns that reader's status
+    and message; the same call on the whole files right afterwards counts what the numpy counter counts."""
+    stream = random_reads(seed=13, n_reads=300)
+    reads = stream.split(b"\n")[:-1]
+    third = len(reads) // 3
+    parts = [reads[:third], reads[third:2 * third], reads[2 * third:]]
+    fq = [b"".join(b"@r%d\n%s\n+\n%s\n" % (i, r, b"I" * len(r)) for i, r in enumerate(p)) for p in parts]
+    good = [tmp_path / "a.fq", tmp_path / "b.fq.gz", tmp_path / "c.fq"]
+    good[0].write_bytes(fq[0]), good[1].write_bytes(gzip.compress(fq[1])), good[2].write_bytes(fq[2])
+    whole = good[1].read_bytes()
+    cut = tmp_path / "cut.fq.gz"
+    cut.write_bytes(whole[: len(whole) // 2])
+    monkeypatch.setenv("NP2_KCOUNT_TEST_PIECE", "256")
+    with pytest.raises(api.Np2Error) as e:
+        np2io.count_kmers([str(good[0]), str(cut), str(good[2])], [16, 31], min_count=1)
+    assert e.value.code == -1 and "cut.fq.gz: cannot read the sequence file" in str(e.value)
+    same_tables(np2io.count_kmers([str(p) for p in good], [16, 31], min_count=1), stream, [16, 31], 1)

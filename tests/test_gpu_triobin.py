@@ -351,3 +351,34 @@ def test_argument_errors_return_before_a_launch_and_leave_the_context_usable(edg
     with pytest.raises(api.Np2Error) as e:
         np2io.bin_files(pol, [os.path.join(ROOT, "missing.fa")])
     assert e.value.code == E_ARG and "cannot open" in str(e.value)
+
+
+# ---- 7. a reader fails in mid-run ---------------------------------------------------------------------------------------------
+def test_reader_failure_in_mid_run_is_returned_and_the_polisher_goes_on(diploid, tmp_path, monkeypatch):
+    """Two reader threads and pieces of one tile; the second file is a gzip cut in the middle, so its reader stops with an
+    error after the device thread has classified pieces of the first.  The call returns that reader's status and message;
+    the same call on the whole files right afterwards writes the brute force's report, and the polisher answers
+    np2_bin_stream as it did before."""
+    s, yaks, (tp, tm), pol = diploid
+    rng = np.random.default_rng(31)
+    n = min(len(s.hap1), len(s.hap2))
+    reads = [(s.hap1 if i % 2 else s.hap2)[a:a + 150] for i, a in enumerate(rng.integers(0, n - 150, size=400).tolist())]
+    named = [(f"r{i}", r) for i, r in enumerate(reads)]
+    half = len(named) // 2
+    fq = [b"".join(b"@" + nm.encode() + b"\n" + r + b"\n+\n" + b"I" * len(r) + b"\n" for nm, r in part) for part in (named[:half], named[half:])]
+    a, b, cut = tmp_path / "a.fq", tmp_path / "b.fq.gz", tmp_path / "cut.fq.gz"
+    a.write_bytes(fq[0]), b.write_bytes(gzip.compress(fq[1]))
+    cut.write_bytes(b.read_bytes()[: len(b.read_bytes()) // 2])
+    few = reads[:5] + [s.hap1[1000:4000], b""]
+    before = pol.bin_stream(0, 1, few, 2, 5, stats=True)
+    monkeypatch.setenv("NP2_BIN_TEST_STAGE_TILES", "1")
+    with pytest.raises(api.Np2Error) as e:
+        np2io.bin_files(pol, [str(a), str(cut)], tsv=str(tmp_path / "bad.tsv"))
+    assert e.value.code == E_ARG and "cut.fq.gz: cannot read the sequence file" in str(e.value)
+    tsv = tmp_path / "good.tsv"
+    counts, _ = np2io.bin_files(pol, [str(a), str(b)], tsv=str(tsv))
+    exp = brute_force(reads, 21, tp, tm, 2, 5)
+    assert tsv.read_bytes() == expected_outputs(named, exp)[0]
+    assert counts == {c: sum(1 for _, x in exp if x == c) for c in "pma0"}
+    after = pol.bin_stream(0, 1, few, 2, 5, stats=True)
+    assert after.classes == before.classes and after.stats.tobytes() == before.stats.tobytes()
