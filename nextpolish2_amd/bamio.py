@@ -29,16 +29,20 @@ def reg2bin(beg, end):
 
 
 class _Bgzf:
-    def __init__(self, f):
+    def __init__(self, f, level=6):
         self.f = f
+        self.level = level
         self.buf = bytearray()
 
     def tell(self):
         return (self.f.tell() << 16) | len(self.buf)
 
     def _flush_block(self, data):
-        co = zlib.compressobj(6, zlib.DEFLATED, -15)
+        co = zlib.compressobj(self.level, zlib.DEFLATED, -15)
         comp = co.compress(bytes(data)) + co.flush()
+        if len(comp) + 26 > 65536:  # (does not deflate: stored)
+            co = zlib.compressobj(0, zlib.DEFLATED, -15)
+            comp = co.compress(bytes(data)) + co.flush()
         bsize = len(comp) + 25
         hdr = struct.pack("<BBBBIBBHBBHH", 31, 139, 8, 4, 0, 0, 255, 6, 66, 67, 2, bsize)
         self.f.write(hdr + comp + struct.pack("<II", zlib.crc32(bytes(data)) & 0xFFFFFFFF, len(data)))
@@ -61,6 +65,21 @@ class _Bgzf:
         self._flush_block(b"")  # EOF marker
 
 
+class _BgzfCut(_Bgzf):
+    """a block is cut wherever the buffer reaches `limit` bytes, whatever lies there (htslib's bgzf_write)"""
+
+    def __init__(self, f, limit, level):
+        assert 0 < limit <= 0xff00
+        _Bgzf.__init__(self, f, level)
+        self.limit = limit
+
+    def write(self, data, atomic=False):
+        self.buf += data
+        while len(self.buf) >= self.limit:
+            self._flush_block(self.buf[:self.limit])
+            del self.buf[:self.limit]
+
+
 def encode_record(tid, pos, mapq, flag, cigar, seq, name=b"r"):
     """cigar: list of (op_char, len); seq: str/bytes of read bases (may be empty)."""
     if isinstance(seq, str):
@@ -80,15 +99,17 @@ def encode_record(tid, pos, mapq, flag, cigar, seq, name=b"r"):
     return struct.pack("<I", len(body)) + body, ref_len
 
 
-def write_bam(path, refs, records):
+def write_bam(path, refs, records, block_limit=None, level=6):
     """refs: [(name, length)]; records: iterable of dicts(tid,pos,mapq,flag,cigar,seq[,name]) sorted by (tid,pos).
 
-    Writes <path> and <path>.bai."""
+    Writes <path> and <path>.bai.  By default a block is closed before a record that would not fit, so every block ends
+    on a record boundary.  block_limit=N cuts a block wherever the buffer reaches N bytes instead, as htslib's
+    bgzf_write does (samtools: 0xff00): records, their length words and their fixed fields straddle blocks."""
     n_ref = len(refs)
     bins = [dict() for _ in range(n_ref)]
     lin = [dict() for _ in range(n_ref)]
     with open(path, "wb") as f:
-        z = _Bgzf(f)
+        z = _Bgzf(f, level) if block_limit is None else _BgzfCut(f, block_limit, level)
         text = b"@HD\tVN:1.6\tSO:coordinate\n" + b"".join(b"@SQ\tSN:%s\tLN:%d\n" % (n.encode(), l) for n, l in refs)
         hdr = b"BAM\1" + struct.pack("<I", len(text)) + text + struct.pack("<I", n_ref)
         for n, l in refs:
@@ -102,7 +123,7 @@ def write_bam(path, refs, records):
             last = (r["tid"], r["pos"])
             data, ref_len = encode_record(r["tid"], r["pos"], r.get("mapq", 60), r.get("flag", 0), r["cigar"], r["seq"],
                                           r.get("name", b"r%d" % i))
-            if len(z.buf) + len(data) > 60000 and z.buf:
+            if block_limit is None and len(z.buf) + len(data) > 60000 and z.buf:
                 z.flush()
             beg = z.tell()
             z.write(data, atomic=False)
@@ -266,8 +287,8 @@ def read_bam(path):
 def pileup_to_records(pileup, tid=0, rng=None, decorate=False):
     """Turn the packed reads (index >= 1) of a Pileup back into BAM-style records (CIGAR + SEQ).
 
-    decorate=True adds soft clips, a few junk columns before/after the 8-match anchors and some records that
-    the admission filters must reject, to exercise fill_with_cigar / is_clip / trim / the filters."""
+    decorate=True adds soft clips, a few junk columns before the first 8-match anchor (never behind the last one) and
+    some records that the admission filters must reject, to exercise fill_with_cigar / is_clip / trim / the filters."""
     rng = rng or np.random.default_rng(0)
     code2 = "ACGT-NM"
     ref = pileup.ref.tobytes().decode()

@@ -4,14 +4,14 @@ random compression level; decorated records (clips, strands, supplementary, seco
 read through np2_contig_from_bam on the DEVICE (BGZF inflate kernel, record walk along the linear index, CIGARs, SEQ in
 place) and on the host pool, both compared with each other and with the oracle's front end over the same records.
    python tests/tools/fuzz_bam.py <seed> <files>"""
-import os, struct, sys, tempfile, time, zlib
+import os, sys, tempfile, time
 R = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, R); sys.path.insert(0, os.path.join(R, "tests"))
 import numpy as np
 from nextpolish2_amd import Polisher
 from nextpolish2_amd import io as np2io
 from nextpolish2_amd.api import Np2Error
-from nextpolish2_amd.bamio import encode_record, pileup_to_records, records_to_arrays, reg2bin
+from nextpolish2_amd.bamio import pileup_to_records, records_to_arrays, write_bam
 from nextpolish2_amd.synth import Synth
 from oracle import np2_oracle as orc
 from test_frontend_cpu import same_pileup
@@ -19,69 +19,7 @@ from test_frontend_cpu import same_pileup
 
 def write_bam_straddling(path, refs, records, limit, level):
     """like bamio.write_bam, but a block is cut wherever the buffer reaches `limit` bytes (htslib's bgzf_write)"""
-    n_ref = len(refs)
-    lin = [dict() for _ in range(n_ref)]
-    bins = [dict() for _ in range(n_ref)]
-    with open(path, "wb") as f:
-        buf = bytearray()
-
-        def flush_block(data):
-            co = zlib.compressobj(level, zlib.DEFLATED, -15)
-            comp = co.compress(bytes(data)) + co.flush()
-            if len(comp) + 26 > 65536:  # (does not deflate: stored)
-                co = zlib.compressobj(0, zlib.DEFLATED, -15)
-                comp = co.compress(bytes(data)) + co.flush()
-            f.write(struct.pack("<BBBBIBBHBBHH", 31, 139, 8, 4, 0, 0, 255, 6, 66, 67, 2, len(comp) + 25) + comp +
-                    struct.pack("<II", zlib.crc32(bytes(data)) & 0xFFFFFFFF, len(data)))
-
-        def put(data):
-            nonlocal buf
-            buf += data
-            while len(buf) >= limit:
-                flush_block(buf[:limit])
-                del buf[:limit]
-        text = b"@HD\tVN:1.6\tSO:coordinate\n" + b"".join(b"@SQ\tSN:%s\tLN:%d\n" % (n.encode(), l) for n, l in refs)
-        hdr = b"BAM\1" + struct.pack("<I", len(text)) + text + struct.pack("<I", n_ref)
-        for n, l in refs:
-            nb = n.encode() + b"\0"
-            hdr += struct.pack("<I", len(nb)) + nb + struct.pack("<I", l)
-        put(hdr)
-        if buf:  # (the header ends its block, as samtools writes it)
-            flush_block(buf)
-            buf = bytearray()
-        for i, r in enumerate(records):
-            data, ref_len = encode_record(r["tid"], r["pos"], r.get("mapq", 60), r.get("flag", 0), r["cigar"], r["seq"], r.get("name", b"r%d" % i))
-            beg = (f.tell() << 16) | len(buf)
-            put(data)
-            end = (f.tell() << 16) | len(buf)
-            tid = r["tid"]
-            if tid >= 0 and not (r.get("flag", 0) & 4):
-                b = reg2bin(r["pos"], r["pos"] + max(ref_len, 1))
-                ch = bins[tid].setdefault(b, [])
-                if ch and ch[-1][1] == beg:
-                    ch[-1][1] = end
-                else:
-                    ch.append([beg, end])
-                for w in range(r["pos"] >> 14, ((r["pos"] + max(ref_len, 1) - 1) >> 14) + 1):
-                    lin[tid].setdefault(w, beg)
-        if buf:
-            flush_block(buf)
-        flush_block(b"")
-    with open(path + ".bai", "wb") as f:
-        out = b"BAI\1" + struct.pack("<I", n_ref)
-        for tid in range(n_ref):
-            out += struct.pack("<I", len(bins[tid]))
-            for b, ch in sorted(bins[tid].items()):
-                out += struct.pack("<II", b, len(ch))
-                for beg, end in ch:
-                    out += struct.pack("<QQ", beg, end)
-            n_intv = (max(lin[tid]) + 1) if lin[tid] else 0
-            out += struct.pack("<I", n_intv)
-            prev = 0
-            for w in range(n_intv):
-                prev = lin[tid].get(w, prev)
-                out += struct.pack("<Q", prev)
-        f.write(out)
+    write_bam(path, refs, records, block_limit=limit, level=level)
 
 
 def main():
