@@ -29,9 +29,10 @@ def reg2bin(beg, end):
 
 
 class _Bgzf:
-    def __init__(self, f, level=6):
+    def __init__(self, f, level=6, extra_subfield=b""):
         self.f = f
         self.level = level
+        self.extra = bytes(extra_subfield)
         self.buf = bytearray()
 
     def tell(self):
@@ -40,11 +41,11 @@ class _Bgzf:
     def _flush_block(self, data):
         co = zlib.compressobj(self.level, zlib.DEFLATED, -15)
         comp = co.compress(bytes(data)) + co.flush()
-        if len(comp) + 26 > 65536:  # (does not deflate: stored)
+        if len(comp) + 26 + len(self.extra) > 65536:  # (does not deflate: stored)
             co = zlib.compressobj(0, zlib.DEFLATED, -15)
             comp = co.compress(bytes(data)) + co.flush()
-        bsize = len(comp) + 25
-        hdr = struct.pack("<BBBBIBBHBBHH", 31, 139, 8, 4, 0, 0, 255, 6, 66, 67, 2, bsize)
+        bsize = len(comp) + 25 + len(self.extra)
+        hdr = struct.pack("<BBBBIBBH", 31, 139, 8, 4, 0, 0, 255, 6 + len(self.extra)) + self.extra + struct.pack("<BBHH", 66, 67, 2, bsize)
         self.f.write(hdr + comp + struct.pack("<II", zlib.crc32(bytes(data)) & 0xFFFFFFFF, len(data)))
 
     def write(self, data, atomic=True):
@@ -68,9 +69,9 @@ class _Bgzf:
 class _BgzfCut(_Bgzf):
     """a block is cut wherever the buffer reaches `limit` bytes, whatever lies there (htslib's bgzf_write)"""
 
-    def __init__(self, f, limit, level):
+    def __init__(self, f, limit, level, extra_subfield=b""):
         assert 0 < limit <= 0xff00
-        _Bgzf.__init__(self, f, level)
+        _Bgzf.__init__(self, f, level, extra_subfield)
         self.limit = limit
 
     def write(self, data, atomic=False):
@@ -99,17 +100,18 @@ def encode_record(tid, pos, mapq, flag, cigar, seq, name=b"r"):
     return struct.pack("<I", len(body)) + body, ref_len
 
 
-def write_bam(path, refs, records, block_limit=None, level=6):
+def write_bam(path, refs, records, block_limit=None, level=6, extra_subfield=b""):
     """refs: [(name, length)]; records: iterable of dicts(tid,pos,mapq,flag,cigar,seq[,name]) sorted by (tid,pos).
 
     Writes <path> and <path>.bai.  By default a block is closed before a record that would not fit, so every block ends
     on a record boundary.  block_limit=N cuts a block wherever the buffer reaches N bytes instead, as htslib's
-    bgzf_write does (samtools: 0xff00): records, their length words and their fixed fields straddle blocks."""
+    bgzf_write does (samtools: 0xff00): records, their length words and their fixed fields straddle blocks.
+    extra_subfield: a complete subfield written before BC in the extra field of every block (none by default)."""
     n_ref = len(refs)
     bins = [dict() for _ in range(n_ref)]
     lin = [dict() for _ in range(n_ref)]
     with open(path, "wb") as f:
-        z = _Bgzf(f, level) if block_limit is None else _BgzfCut(f, block_limit, level)
+        z = _Bgzf(f, level, extra_subfield) if block_limit is None else _BgzfCut(f, block_limit, level, extra_subfield)
         text = b"@HD\tVN:1.6\tSO:coordinate\n" + b"".join(b"@SQ\tSN:%s\tLN:%d\n" % (n.encode(), l) for n, l in refs)
         hdr = b"BAM\1" + struct.pack("<I", len(text)) + text + struct.pack("<I", n_ref)
         for n, l in refs:

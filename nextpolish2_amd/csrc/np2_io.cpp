@@ -1,7 +1,10 @@
 // Input side of the hot path (include/np2_io.h): FASTA[.gz], yak v2 dumps, indexed BAM (BGZF + BAI on zlib),
 // record admission (src/main.rs:1758-1817) and the GPU columnariser orchestration.
 #include "../../include/np2_io.h"
+#include "np2_bgzf.hpp"
 #include "np2_ctx.hpp"
+#include "np2_iopool.hpp"
+#include "np2_kernel_timer.hpp"
 
 #include <algorithm>
 #include <zlib.h>
@@ -13,13 +16,10 @@
 #include <unistd.h>
 
 #include <atomic>
-#include <condition_variable>
-#include <exception>
 #include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
-#include <thread>
 #include <tuple>
 #include <unordered_map>
 #include <unordered_set>
@@ -102,7 +102,10 @@ bool bgzf_crc_on() {
     return on;
 }
 std::string crc_msg(uint64_t file_off) { return "BGZF CRC32 mismatch (block at file offset " + std::to_string(file_off) + ")"; }
-uint32_t le32(const uint8_t *p) { return p[0] | (p[1] << 8) | (p[2] << 16) | ((uint32_t)p[3] << 24); }
+using np2h::BgzfBlock;
+using np2h::IoPool;
+using np2h::le32;
+using np2h::RawBuf;
 
 thread_local std::string g_io_err;
 int io_fail(int code, const std::string &m) {
@@ -142,7 +145,7 @@ struct Bgzf {
     FILE *f = nullptr;
     std::vector<uint8_t> block, cdata;
     size_t bpos = 0;
-    uint64_t block_off = 0; // file offset of the current block
+    uint64_t block_off = 0, flen = 0; // file offset of the current block; length of the file
     // virtual offset of the next byte to be read
     uint64_t tell() {
         if (bpos >= block.size()) return (uint64_t)ftello(f) << 16;
@@ -152,42 +155,26 @@ struct Bgzf {
         block.clear();
         bpos = 0;
         block_off = (uint64_t)ftello(f);
-        uint8_t hd[18];
-        size_t n = fread(hd, 1, 18, f);
-        if (n == 0) return false;
-        if (n != 18 || hd[0] != 31 || hd[1] != 139 || hd[2] != 8 || !(hd[3] & 4))
-            throw np2h::Np2Error(NP2_E_ARG, "not a BGZF block");
-        const uint32_t xlen = hd[10] | (hd[11] << 8);
-        // the BC subfield is normally the first (and only) extra field
-        std::vector<uint8_t> extra(xlen);
-        memcpy(extra.data(), hd + 12, std::min<size_t>(6, xlen));
-        if (xlen > 6 && fread(extra.data() + 6, 1, xlen - 6, f) != xlen - 6)
-            throw np2h::Np2Error(NP2_E_ARG, "truncated BGZF header");
-        uint32_t bsize = 0;
-        for (size_t p = 0; p + 4 <= xlen;) {
-            const uint32_t slen = extra[p + 2] | (extra[p + 3] << 8);
-            if (extra[p] == 'B' && extra[p + 1] == 'C' && slen == 2) bsize = (extra[p + 4] | (extra[p + 5] << 8)) + 1;
-            p += 4 + slen;
+        if (block_off >= flen) return false;
+        const uint64_t left = flen - block_off;
+        size_t have = 0;
+        auto get = [&](size_t upto) { // bytes [have, upto) of the block
+            cdata.resize(upto);
+            if (fread(cdata.data() + have, 1, upto - have, f) != upto - have) throw np2h::Np2Error(NP2_E_ARG, "truncated BGZF block");
+            have = upto;
+        };
+        np2h::BgzfHeader h{(uint32_t)std::min<uint64_t>(18, left), 0, 0, 0};
+        while (h.need) {
+            get(h.need);
+            h = np2h::bgzf_header(cdata.data(), have, left);
         }
-        if (!bsize) throw np2h::Np2Error(NP2_E_ARG, "BGZF block without BC field");
-        const size_t clen = bsize - 12 - xlen - 8;
-        cdata.resize(clen + 8);
-        if (fread(cdata.data(), 1, clen + 8, f) != clen + 8) throw np2h::Np2Error(NP2_E_ARG, "truncated BGZF block");
-        const uint32_t isize = cdata[clen + 4] | (cdata[clen + 5] << 8) | (cdata[clen + 6] << 16) | ((uint32_t)cdata[clen + 7] << 24);
-        block.resize(isize);
-        if (isize && !Inflater::get().run(cdata.data(), clen, block.data(), isize))
-            throw np2h::Np2Error(NP2_E_ARG, "BGZF inflate failed");
-        if (bgzf_crc_on() && Inflater::get().crc(block.data(), isize) != le32(cdata.data() + clen)) throw np2h::Np2Error(NP2_E_ARG, crc_msg(block_off));
+        get(h.bsize);
+        const uint8_t *payload = cdata.data() + h.hdr_len;
+        const np2h::BgzfTrailer t = np2h::bgzf_trailer(payload + h.clen);
+        block.resize(t.isize);
+        if (t.isize && !Inflater::get().run(payload, h.clen, block.data(), t.isize)) throw np2h::Np2Error(NP2_E_ARG, "BGZF inflate failed");
+        if (bgzf_crc_on() && Inflater::get().crc(block.data(), t.isize) != t.crc) throw np2h::Np2Error(NP2_E_ARG, crc_msg(block_off));
         return true;
-    }
-    void seek(uint64_t voffset) {
-        fseeko(f, (off_t)(voffset >> 16), SEEK_SET);
-        if (!read_block()) {
-            block.clear();
-            bpos = 0;
-            return;
-        }
-        bpos = voffset & 0xFFFF;
     }
     // read exactly n bytes; returns false on clean EOF before the first byte
     bool read(void *dst, size_t n) {
@@ -210,215 +197,13 @@ struct Bgzf {
     }
 };
 
-// Small persistent pool for the input side: BGZF blocks are independent deflate streams and BAM records independent
-// byte ranges, so inflate and record copy are plain parallel loops.  Work items are handed out by an atomic counter;
-// the calling thread works too.  One pool per process, sized to the host (at most 64 workers).  Several loops may be
-// in flight at once (the command line keeps a few contigs' front ends going side by side): a worker takes items from
-// whichever open loop still has some, so a single caller gets the whole pool and concurrent callers share it.
-class IoPool {
-  public:
-    static IoPool &get() {
-        static IoPool *p = new IoPool(); // leaked on purpose: workers outlive static destruction
-        return *p;
-    }
-    unsigned size() const { return (unsigned)workers_.size() + 1; }
-    // run fn(i) for i in [0, n), at most `max_threads` threads including the caller
-    template <class F> void parallel_for(size_t n, unsigned max_threads, F fn) {
-        if (n == 0) return;
-        const unsigned want = (unsigned)std::min<size_t>(std::min<size_t>(max_threads, size()), n);
-        if (want <= 1) {
-            for (size_t i = 0; i < n; ++i) fn(i);
-            return;
-        }
-        Job job;
-        job.n = n;
-        job.slots = want - 1; // helpers wanted besides the caller
-        std::function<void(size_t)> body = fn;
-        job.fn = &body;
-        {
-            std::lock_guard<std::mutex> l(mu_);
-            jobs_.push_back(&job);
-        }
-        cv_.notify_all();
-        run(job);
-        std::unique_lock<std::mutex> l(mu_);
-        jobs_.erase(std::find(jobs_.begin(), jobs_.end(), &job)); // no new helper can pick it up from here on
-        done_cv_.wait(l, [&] { return job.helpers == 0; });
-    }
-
-    // the same loop with the CALLER doing `during()` first — work that consumes the items' results as they appear (it
-    // must only wait for items in index order: they are handed out in that order) — and joining the loop afterwards
-    template <class F, class G> void parallel_for_during(size_t n, unsigned max_threads, F fn, G during) {
-        const unsigned want = (unsigned)std::min<size_t>(std::min<size_t>(max_threads, size()), n);
-        if (want <= 1) { // nobody to wait for: items first
-            for (size_t i = 0; i < n; ++i) fn(i);
-            during();
-            return;
-        }
-        Job job;
-        job.n = n;
-        job.slots = want - 1;
-        std::function<void(size_t)> body = fn;
-        job.fn = &body;
-        {
-            std::lock_guard<std::mutex> l(mu_);
-            jobs_.push_back(&job);
-        }
-        cv_.notify_all();
-        std::exception_ptr ep;
-        try {
-            during();
-        } catch (...) {
-            ep = std::current_exception();
-        }
-        run(job);
-        {
-            std::unique_lock<std::mutex> l(mu_);
-            jobs_.erase(std::find(jobs_.begin(), jobs_.end(), &job));
-            done_cv_.wait(l, [&] { return job.helpers == 0; });
-        }
-        if (ep) std::rethrow_exception(ep);
-    }
-
-  private:
-    struct Job {
-        size_t n = 0;
-        std::atomic<size_t> next{0};
-        unsigned slots = 0;   // helpers that may still join (guarded by mu_)
-        unsigned helpers = 0; // helpers currently inside (guarded by mu_)
-        std::function<void(size_t)> *fn = nullptr;
-    };
-    static void run(Job &j) {
-        for (;;) {
-            const size_t i = j.next.fetch_add(1, std::memory_order_relaxed);
-            if (i >= j.n) break;
-            (*j.fn)(i);
-        }
-    }
-    IoPool() {
-        // sized by the hardware, not by the quota: the pool works in bursts of a few milliseconds (one contig's inflate),
-        // which a CFS quota does not throttle — measured on a box with 256 hardware threads and a quota of 16 CPUs: an
-        // E. coli-sized contig's records arrive in 8 ms with 64 workers and in 18 ms with 16
-        unsigned hw = std::thread::hardware_concurrency();
-        unsigned n = std::min<unsigned>(64, std::max<unsigned>(2, hw / 2));
-        if (const char *e = getenv("NP2_IO_THREADS")) n = (unsigned)std::max(1, atoi(e));
-        for (unsigned i = 1; i < n; ++i) workers_.emplace_back([this] { loop(); });
-        for (auto &t : workers_) t.detach();
-    }
-    Job *pick() { // mu_ held: an open loop with items left and a free helper slot
-        for (Job *j : jobs_)
-            if (j->slots && j->next.load(std::memory_order_relaxed) < j->n) return j;
-        return nullptr;
-    }
-    void loop() {
-        std::unique_lock<std::mutex> l(mu_);
-        for (;;) {
-            Job *j = nullptr;
-            cv_.wait(l, [&] { return (j = pick()) != nullptr; });
-            --j->slots;
-            ++j->helpers;
-            l.unlock();
-            run(*j);
-            l.lock();
-            if (--j->helpers == 0) done_cv_.notify_all();
-        }
-    }
-    std::vector<std::thread> workers_;
-    std::mutex mu_;
-    std::condition_variable cv_, done_cv_;
-    std::vector<Job *> jobs_;
-};
-
-// growable byte buffer without value-initialisation (a std::vector would zero 100+ MiB per refill just to have inflate
-// overwrite it); kept by the BAM handle, so its pages are faulted in once
-// Large host blocks kept across BAM handles (the command line opens one handle per front-end thread and run): a block
-// of this size goes back to the kernel when freed, and the next handle's inflate threads then fault 200 MB of fresh
-// pages in again (11-14 ms of an E. coli-sized contig's first front end).  At most 8 idle blocks / 1 GiB are kept.
-struct HostBlockPool {
-    std::mutex mu;
-    std::vector<std::pair<size_t, uint8_t *>> idle;
-    static HostBlockPool &get() {
-        static HostBlockPool *p = new HostBlockPool(); // leaked on purpose
-        return *p;
-    }
-    uint8_t *take(size_t want, size_t &cap) {
-        {
-            std::lock_guard<std::mutex> l(mu);
-            size_t best = idle.size();
-            for (size_t i = 0; i < idle.size(); ++i)
-                if (idle[i].first >= want && (best == idle.size() || idle[i].first < idle[best].first)) best = i;
-            if (best != idle.size()) {
-                uint8_t *p = idle[best].second;
-                cap = idle[best].first;
-                idle.erase(idle.begin() + (long)best);
-                return p;
-            }
-        }
-        cap = want;
-        return (uint8_t *)malloc(want);
-    }
-    void give(uint8_t *p, size_t cap) {
-        if (!p) return;
-        if (cap >= ((size_t)4 << 20)) {
-            std::lock_guard<std::mutex> l(mu);
-            size_t held = cap;
-            for (auto &b : idle) held += b.first;
-            if (idle.size() < 8 && held <= ((size_t)1 << 30)) {
-                idle.emplace_back(cap, p);
-                return;
-            }
-        }
-        free(p);
-    }
-};
-struct RawBuf {
-    uint8_t *p = nullptr;
-    size_t n = 0, cap = 0;
-    RawBuf() = default;
-    RawBuf(const RawBuf &) = delete;
-    RawBuf &operator=(const RawBuf &) = delete;
-    ~RawBuf() { HostBlockPool::get().give(p, cap); }
-    size_t size() const { return n; }
-    uint8_t *data() { return p; }
-    const uint8_t *data() const { return p; }
-    void clear() { n = 0; }
-    void resize(size_t m) {
-        if (m > cap) {
-            const size_t want = std::max(m, cap + cap / 2 + (1u << 20));
-            size_t got = 0;
-            uint8_t *q = HostBlockPool::get().take(want, got);
-            if (!q) throw std::bad_alloc();
-            if (n) memcpy(q, p, n);
-            HostBlockPool::get().give(p, cap);
-            p = q;
-            cap = got;
-        }
-        n = m;
-    }
-    void drop_front(size_t k) { // discard the first k bytes
-        if (k >= n) {
-            n = 0;
-            return;
-        }
-        memmove(p, p + k, n - k);
-        n -= k;
-    }
-};
-
 // Reads BGZF blocks in batches and inflates each batch with several host threads (blocks are independent).
 struct BgzfBatch {
-    FILE *f = nullptr;
     // the file mapped read-only: a block's deflate payload is inflated straight out of the page cache (reading 35 MB of
     // blocks with two freads each was 9 of the 19 ms the records of an E. coli-sized contig took to arrive); the pages
     // are first touched by the inflating threads, in parallel
     const uint8_t *map = nullptr;
     size_t map_len = 0, fpos = 0;
-    struct Blk {
-        const uint8_t *c = nullptr; // raw deflate payload (inside the mapping)
-        uint32_t clen = 0, isize = 0, crc = 0; // (crc: the block's CRC32 word)
-        size_t out_off = 0;
-        uint64_t file_off = 0; // offset of the block in the file
-    };
     // (buffer position of a block's first inflated byte, file offset of the block) for the blocks in `buf`: a record's
     // BGZF virtual offset = file offset << 16 | offset inside the block
     // (the front block may begin before the buffer once consumed bytes were dropped: signed positions)
@@ -438,37 +223,19 @@ struct BgzfBatch {
     // it only a few at a time (8, 16, ...: an index that understates the end costs time, never records).
     size_t hint_fpos = SIZE_MAX, past_hint = 8;
     // the batch being inflated: its blocks, a completion flag per block, the prefix of `buf` known to be inflated
-    std::vector<Blk> cur_blks;
+    std::vector<BgzfBlock> cur_blks; // (out_off: from cur_base on)
     std::unique_ptr<std::atomic<uint8_t>[]> blk_done;
     size_t blk_done_cap = 0, cur_base = 0, ready_bi = 0, ready_end = 0;
     bool eof = false;
     double ms_read = 0, ms_inflate = 0, ms_drop = 0; // where the refills' time goes (NP2_IO_PROFILE)
     double ms_walk = 0, ms_size = 0, ms_copy = 0;   // ... and the record pass over each refill
     size_t batch_blocks = 2048; // 64 KiB blocks per refill: 128 MiB of inflated BAM, all inflated in parallel
-    bool read_raw(Blk &b) {
+    bool read_raw(BgzfBlock &b) { // (its payload: map + file_off + hdr_len)
         if (fpos >= map_len) return false;
-        if (map_len - fpos < 18) throw np2h::Np2Error(NP2_E_ARG, "not a BGZF block");
-        const uint8_t *hd = map + fpos;
-        b.file_off = fpos;
-        if (hd[0] != 31 || hd[1] != 139 || hd[2] != 8 || !(hd[3] & 4)) throw np2h::Np2Error(NP2_E_ARG, "not a BGZF block");
-        const uint32_t xlen = hd[10] | (hd[11] << 8);
-        if (map_len - fpos < 12 + (size_t)xlen) throw np2h::Np2Error(NP2_E_ARG, "truncated BGZF header");
-        const uint8_t *extra = hd + 12;
-        uint32_t bsize = 0;
-        for (size_t p = 0; p + 4 <= xlen;) {
-            const uint32_t slen = extra[p + 2] | (extra[p + 3] << 8);
-            if (extra[p] == 'B' && extra[p + 1] == 'C' && slen == 2 && p + 6 <= xlen) bsize = (extra[p + 4] | (extra[p + 5] << 8)) + 1;
-            p += 4 + slen;
-        }
-        if (!bsize) throw np2h::Np2Error(NP2_E_ARG, "BGZF block without BC field");
-        if (bsize < 12 + xlen + 8 || map_len - fpos < bsize) throw np2h::Np2Error(NP2_E_ARG, "truncated BGZF block");
-        const size_t clen = bsize - 12 - xlen - 8;
-        b.c = hd + 12 + xlen;
-        b.clen = (uint32_t)clen;
-        const uint8_t *tail = b.c + clen;
-        b.crc = le32(tail);
-        b.isize = tail[4] | (tail[5] << 8) | (tail[6] << 16) | ((uint32_t)tail[7] << 24);
-        fpos += bsize;
+        const np2h::BgzfHeader h = np2h::bgzf_header(map + fpos, map_len - fpos, map_len - fpos);
+        const np2h::BgzfTrailer t = np2h::bgzf_trailer(map + fpos + h.hdr_len + h.clen);
+        b = BgzfBlock{fpos, 0, h.hdr_len, h.clen, t.isize, h.bsize, t.crc};
+        fpos += h.bsize;
         return true;
     }
     // start at a virtual offset
@@ -516,14 +283,14 @@ struct BgzfBatch {
             pos = 0;
         }
         const double t_f1 = np2h::now_ms();
-        std::vector<Blk> &blks = cur_blks;
+        std::vector<BgzfBlock> &blks = cur_blks;
         blks.clear();
         size_t total = 0;
         const bool past = fpos > hint_fpos;
         if (past) n_blocks = std::min(n_blocks, past_hint), past_hint *= 2;
         for (size_t i = 0; i < n_blocks; ++i) {
             if (!past && fpos > hint_fpos) break;
-            Blk b;
+            BgzfBlock b;
             if (!read_raw(b)) {
                 eof = true;
                 break;
@@ -550,7 +317,7 @@ struct BgzfBatch {
         auto one = [&](size_t i) {
             uint8_t *dst = buf.data() + base + blks[i].out_off;
             uint64_t why = 0;
-            if (blks[i].isize && !inf.run(blks[i].c, blks[i].clen, dst, blks[i].isize)) why = i + 1;
+            if (blks[i].isize && !inf.run(map + blks[i].file_off + blks[i].hdr_len, blks[i].clen, dst, blks[i].isize)) why = i + 1;
             else if (check_crc && inf.crc(dst, blks[i].isize) != blks[i].crc) why = (i + 1) | (1ull << 63);
             if (why) {
                 uint64_t seen = bad.load();
@@ -594,6 +361,41 @@ struct BgzfBatch {
 };
 
 uint64_t le64(const uint8_t *p) { return (uint64_t)le32(p) | ((uint64_t)le32(p + 4) << 32); }
+
+// File bytes [off, off + n) -> dst; false: the file ends before them.
+bool pread_full(int fd, uint8_t *dst, size_t n, uint64_t off) {
+    for (size_t got = 0; got < n;) {
+        const ssize_t r = pread(fd, dst + got, n - got, (off_t)(off + got));
+        if (r <= 0) return false;
+        got += (size_t)r;
+    }
+    return true;
+}
+// n bytes -> dst (device) through two alternating pinned pieces of piece_bytes each (ev: their events).  fill(stage, offset,
+// bytes) -> bool writes bytes [offset, offset + bytes) of the n to `stage`, 1 MiB a call on `threads` of the host pool (the page
+// cache is copied from at ~10 GB/s per thread, the bus takes 50); after_piece(stage, o0, o1) looks at a whole piece, bytes
+// [o0, o1), once its copy is under way.  false: a fill came up short.
+template <class Fill, class After>
+bool staged_upload(void *const *pin, const hipEvent_t *ev, size_t piece_bytes, unsigned threads, size_t n, uint8_t *dst, hipStream_t s, Fill fill, After after_piece) {
+    size_t piece = 0;
+    for (size_t o = 0; o < n; o += piece_bytes, ++piece) {
+        const int sl = (int)(piece & 1);
+        if (piece >= 2) HIPCHK(hipEventSynchronize(ev[sl])); // the copy that last used this staging piece
+        const size_t want = std::min(piece_bytes, n - o);
+        uint8_t *stage = (uint8_t *)pin[sl];
+        const size_t SUB = (size_t)1 << 20;
+        std::atomic<int> bad{0};
+        IoPool::get().parallel_for((want + SUB - 1) / SUB, threads, [&](size_t k) {
+            if (!fill(stage + k * SUB, o + k * SUB, std::min(SUB, want - k * SUB))) bad.store(1);
+        });
+        if (bad.load()) return false;
+        HIPCHK(hipMemcpyAsync(dst + o, stage, want, hipMemcpyHostToDevice, s));
+        HIPCHK(hipEventRecord(ev[sl], s));
+        after_piece(stage, o, o + want);
+    }
+    return true;
+}
+void no_look(const uint8_t *, size_t, size_t) {}
 
 // reference bases a CIGAR of n operations covers (M, D, N, =, X); given as words or as a record's little-endian bytes
 inline uint32_t cigar_word(const uint32_t *cigar, uint32_t k) { return cigar[k]; }
@@ -798,7 +600,6 @@ void load_secondary_seqs(np2_bam *bam) {
     std::unordered_set<std::string> ids;
     for (int pass = 0; pass < 2; ++pass) {
         BgzfBatch z;
-        z.f = bam->z.f;
         z.map = bam->map, z.map_len = bam->map_len;
         z.seek(bam->first_rec);
         for (;;) {
@@ -1162,6 +963,17 @@ void contig_from_records(np2_ctx *cx, const uint8_t *ref, uint32_t L, const np2_
 // np2_bamrec_t + CIGAR words + SEQ bytes (pinned staging of the handle); optionally their BGZF virtual offsets.
 // With `up_stream` (and without -S) the SEQ bytes do not stay on the host: they go to bam->seqs.dev batch by batch
 // (SeqStream), *seq_bytes is their total, bam->seq4 stays empty.
+// Where the records of a zone begin: at the reference's first record, or — zone_lo > 0 — at the smallest offset of a record
+// overlapping the 16 kb window of zone_lo in the linear index (an empty window takes the next one's, like htslib).  ~0: no record.
+uint64_t zone_start_offset(const np2_bam *bam, int tid, uint32_t zone_lo) {
+    const std::vector<uint64_t> &lin = bam->lin[tid];
+    const uint64_t first = bam->ref_start[tid];
+    if (first == ~0ull || zone_lo == 0 || lin.empty()) return first;
+    size_t w = std::min<size_t>(zone_lo >> 14, lin.size() - 1);
+    while (w + 1 < lin.size() && lin[w] == 0) ++w;
+    return lin[w] != 0 ? lin[w] : first;
+}
+
 void fetch_records(np2_bam *bam, int tid, uint32_t L, uint32_t zone_lo, uint32_t zone_hi, const np2_front_opts_t *opts,
                    std::vector<np2_bamrec_t> &recs, std::vector<uint32_t> &cigar, std::vector<uint64_t> *voffs,
                    hipStream_t up_stream = nullptr, uint64_t *seq_bytes = nullptr, bool no_seq = false) {
@@ -1171,17 +983,9 @@ void fetch_records(np2_bam *bam, int tid, uint32_t L, uint32_t zone_lo, uint32_t
         const bool streamed = up_stream != nullptr && !opts->use_secondary;
         uint64_t seq_total = 0; // (streamed: the running SEQ offset that seq4.size() is otherwise)
         if (opts->use_secondary) load_secondary_seqs(bam);
-        // where to start: the whole contig from its first record; a zone from the linear index (the smallest offset of a
-        // record overlapping the 16 kb window of zone_lo; an empty window takes the next one's, like htslib)
-        uint64_t start_off = bam->ref_start[tid];
-        if (start_off != ~0ull && zone_lo > 0 && !bam->lin[tid].empty()) {
-            size_t w = std::min<size_t>(zone_lo >> 14, bam->lin[tid].size() - 1);
-            while (w + 1 < bam->lin[tid].size() && bam->lin[tid][w] == 0) ++w;
-            if (bam->lin[tid][w] != 0) start_off = bam->lin[tid][w];
-        }
+        const uint64_t start_off = zone_start_offset(bam, tid, zone_lo);
         if (start_off != ~0ull) {
             BgzfBatch &z = bam->batch;
-            z.f = bam->z.f;
             z.map = bam->map, z.map_len = bam->map_len;
             z.seek(start_off, false);
             if (bam->ref_end[tid]) z.hint_fpos = (size_t)(bam->ref_end[tid] >> 16);
@@ -1502,7 +1306,7 @@ struct YakFile {
 void yak_file_to_table(YakFile &yf, int device, hipStream_t given) {
     hipStream_t st = given; // (one of the new context's idle streams, or our own)
     hipEvent_t ev[2] = {nullptr, nullptr};
-    uint8_t *pin[2] = {nullptr, nullptr};
+    void *pin[2] = {nullptr, nullptr};
     auto fail = [&](int code, const std::string &m) { yf.code = code, yf.msg = m; };
     const bool prof = getenv("NP2_IO_PROFILE") != nullptr;
     auto body = [&]() {
@@ -1548,7 +1352,7 @@ void yak_file_to_table(YakFile &yf, int device, hipStream_t given) {
         ta[4] = np2h::now_ms();
         const size_t PIECE = (size_t)8 << 20;
         for (int i = 0; i < 2; ++i) {
-            pin[i] = (uint8_t *)np2h::pinned_pool().get(PIECE);
+            pin[i] = np2h::pinned_pool().get(PIECE);
             if (!pin[i]) throw np2h::Np2Error(NP2_E_NOMEM, "hipHostMalloc failed");
             HIPCHK(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
         }
@@ -1557,32 +1361,8 @@ void yak_file_to_table(YakFile &yf, int device, hipStream_t given) {
             fprintf(stderr, "  yak k=%u allocations: stream %.1f ms, table (%.1f GB) %.1f ms, memset call %.1f ms, file image (%.1f GB) %.1f ms, "
                             "small buffers %.1f ms, pinned pieces + events %.1f ms\n", yf.k, ta[0] - t1, slots * 8 / 1e9, ta[1] - ta[0],
                     ta[2] - ta[1], body_words * 8 / 1e9, ta[3] - ta[2], ta[4] - ta[3], t2 - ta[4]);
-        const size_t body = body_words * 8;
-        size_t piece = 0;
-        for (size_t o = 0; o < body; o += PIECE, ++piece) {
-            const int sl = (int)(piece & 1);
-            if (piece >= 2) HIPCHK(hipEventSynchronize(ev[sl])); // the copy that last used this staging piece
-            const size_t want = std::min(PIECE, body - o);
-            // (the page cache is copied from at ~10 GB/s per thread, the bus takes 50: the piece is read by several of the pool's)
-            const size_t SUB = (size_t)1 << 20;
-            std::atomic<int> bad{0};
-            uint8_t *const stage = pin[sl];
-            IoPool::get().parallel_for((want + SUB - 1) / SUB, 8, [&](size_t k) {
-                size_t got = 0;
-                const size_t n = std::min(SUB, want - k * SUB);
-                while (got < n) {
-                    const ssize_t r = pread(yf.fd, stage + k * SUB + got, n - got, (off_t)(16 + o + k * SUB + got));
-                    if (r <= 0) {
-                        bad.store(1);
-                        return;
-                    }
-                    got += (size_t)r;
-                }
-            });
-            if (bad.load()) return fail(NP2_E_ARG, "Failed to parse the dump file");
-            HIPCHK(hipMemcpyAsync((uint8_t *)d_raw.p + o, pin[sl], want, hipMemcpyHostToDevice, st));
-            HIPCHK(hipEventRecord(ev[sl], st));
-        }
+        if (!staged_upload(pin, ev, PIECE, 8, body_words * 8, (uint8_t *)d_raw.p, st, [&](uint8_t *stage, size_t o, size_t n) { return pread_full(yf.fd, stage, n, 16 + o); }, no_look))
+            return fail(NP2_E_ARG, "Failed to parse the dump file");
         const double t3 = np2h::now_ms();
         // (the offsets are tiny: through the first staging piece once its last copy has drained)
         HIPCHK(hipStreamSynchronize(st));
@@ -1670,9 +1450,9 @@ int np2_bam_open(const char *path, np2_bam_t **out) {
         std::unique_ptr<np2_bam> b(new np2_bam());
         b->z.f = fopen(path, "rb");
         if (!b->z.f) throw np2h::Np2Error(NP2_E_ARG, std::string("cannot open ") + path);
-        fseeko(b->z.f, 0, SEEK_SET);
-        b->z.block.clear();
-        b->z.bpos = 0;
+        struct stat st;
+        if (fstat(fileno(b->z.f), &st) != 0) throw np2h::Np2Error(NP2_E_ARG, std::string("cannot stat ") + path);
+        b->z.flen = b->map_len = (size_t)st.st_size;
         uint8_t h8[8];
         if (!b->z.read(h8, 8) || memcmp(h8, "BAM\1", 4) != 0) throw np2h::Np2Error(NP2_E_ARG, "not a BAM file");
         const uint32_t l_text = le32(h8 + 4);
@@ -1694,14 +1474,9 @@ int np2_bam_open(const char *path, np2_bam_t **out) {
         b->ref_end.assign(n_ref, 0);
         b->lin.assign(n_ref, {});
         b->first_rec = b->z.tell();
-        {
-            struct stat st;
-            if (fstat(fileno(b->z.f), &st) != 0) throw np2h::Np2Error(NP2_E_ARG, std::string("cannot stat ") + path);
-            b->map_len = (size_t)st.st_size;
-            void *m = b->map_len ? mmap(nullptr, b->map_len, PROT_READ, MAP_SHARED, fileno(b->z.f), 0) : nullptr;
-            if (m == MAP_FAILED) throw np2h::Np2Error(NP2_E_NOMEM, std::string("cannot map ") + path);
-            b->map = (const uint8_t *)m;
-        }
+        void *m = b->map_len ? mmap(nullptr, b->map_len, PROT_READ, MAP_SHARED, fileno(b->z.f), 0) : nullptr;
+        if (m == MAP_FAILED) throw np2h::Np2Error(NP2_E_NOMEM, std::string("cannot map ") + path);
+        b->map = (const uint8_t *)m;
         // index: <path>.bai or <stem>.bai
         std::string p1 = std::string(path) + ".bai", p2 = path;
         if (p2.size() > 4 && p2.substr(p2.size() - 4) == ".bam") p2 = p2.substr(0, p2.size() - 4) + ".bai";
@@ -1768,23 +1543,19 @@ int np2_contig_from_records(np2_ctx_t *cx, const uint8_t *ref, uint32_t L, const
     }, np2h::ctx_sink(cx, true));
 }
 
-struct GBlk { // a BGZF block of the file
-    uint64_t file_off; // of the block
-    uint32_t hdr_len;  // 12 + XLEN: the raw DEFLATE payload starts there
-    uint32_t clen, isize;
-    uint32_t bsize;    // the whole block
-    uint32_t crc;      // its CRC32 word (of the inflated bytes)
-};
 // The whole file inflated on the device, once per process and device, for BAMs of many references and moderate size (an
 // assembly's: yeast 96 MB -> 600 MB): ONE inflate launch over every block — a block's decode latency, 2 - 3 ms, is paid once
 // instead of once per reference, and 10^4 blocks fill the device where a reference's few hundred leave it idle —, after which
 // a reference's front end is the record walk over its stretch of the resident stream.  Shared by the handles a process
 // opens on the file (the command line: one per front-end thread); released with the last of them.
+// The block table of an inflate launch as it goes to the device in one copy: n InfBlock, then the blocks' n CRC32 words
+// (k_bgzf_crc32 reads them there: d_blk.p + n).
+static size_t blk_table_bytes(size_t n) { return n * sizeof(np2::InfBlock) + n * 4; }
+static size_t blk_table_slots(size_t n) { return (blk_table_bytes(n) + sizeof(np2::InfBlock) - 1) / sizeof(np2::InfBlock) + 1; }
 struct ResidentBam {
     std::mutex mu;
     bool built = false, failed = false;
-    std::vector<GBlk> blks;        // every block from the first record's on, the end-of-file marker included
-    std::vector<uint64_t> out_off; // blks.size() + 1
+    std::vector<BgzfBlock> blks;   // every block from the first record's on, the end-of-file marker included
     np2h::DevBuf<uint8_t> d_inf;
     ResidentBam() { d_inf.cached = true; }
 };
@@ -1799,6 +1570,7 @@ struct ResidentBam {
 // E. coli-sized contig with sixteen: 8.4 - 9 ms either way; eight ranks of a node on a 16-CPU quota have two each, where
 // the pool's path takes 85 ms and this one 12), or when the reference's records are 128 MB of BAM and more.
 // -S (SEQ of secondary records from their primaries) and reference-interval shards stay on the host path.
+extern "C++" { // (a member template cannot stand inside a C linkage block)
 struct GpuFetch {
     np2h::DevBuf<uint8_t> d_comp, d_inf;
     np2h::DevBuf<np2::InfBlock> d_blk;
@@ -1832,8 +1604,10 @@ struct GpuFetch {
         }
         return p;
     }
-    // file bytes [src, src + n) -> dst (device), through two alternating pinned pieces filled by the host pool
-    void upload(const uint8_t *src, size_t n, uint8_t *dst, hipStream_t s) {
+    // pinned, for an inflate launch's block table (free until the records come back)
+    void *table_block(size_t n_blk) { return host_block(h_cigar, h_cigar_cap, std::max<size_t>(blk_table_bytes(n_blk), 64)); }
+    // n bytes -> dst (device): staged_upload through this fetcher's two pieces of 16 MiB
+    template <class Fill, class After> void upload(size_t n, uint8_t *dst, hipStream_t s, Fill fill, After after_piece) {
         for (int i = 0; i < 2; ++i) {
             if (!pin[i]) {
                 pin[i] = np2h::pinned_pool().get(PIECE);
@@ -1841,21 +1615,14 @@ struct GpuFetch {
             }
             if (!ev[i]) HIPCHK(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
         }
-        size_t piece = 0;
-        for (size_t o = 0; o < n; o += PIECE, ++piece) {
-            const int sl = (int)(piece & 1);
-            if (piece >= 2) HIPCHK(hipEventSynchronize(ev[sl]));
-            const size_t want = std::min(PIECE, n - o);
-            uint8_t *stage = (uint8_t *)pin[sl];
-            const size_t SUB = (size_t)1 << 20;
-            IoPool::get().parallel_for((want + SUB - 1) / SUB, 16, [&](size_t k) {
-                memcpy(stage + k * SUB, src + o + k * SUB, std::min(SUB, want - k * SUB));
-            });
-            HIPCHK(hipMemcpyAsync(dst + o, stage, want, hipMemcpyHostToDevice, s));
-            HIPCHK(hipEventRecord(ev[sl], s));
-        }
+        if (!staged_upload(pin, ev, PIECE, 16, n, dst, s, fill, after_piece)) throw np2h::Np2Error(NP2_E_ARG, "truncated BAM"); // (the file ends inside the range)
+    }
+    // memory [src, src + n) -> dst
+    void upload(const uint8_t *src, size_t n, uint8_t *dst, hipStream_t s) {
+        upload(n, dst, s, [&](uint8_t *stage, size_t o, size_t k) { return memcpy(stage, src + o, k) != nullptr; }, no_look);
     }
 };
+}
 np2_bam::~np2_bam() {
     delete gpu;
     if (map) munmap(const_cast<uint8_t *>(map), map_len);
@@ -1885,92 +1652,71 @@ struct GpuRecs {
     const uint8_t *d_stream = nullptr;
     uint64_t stream_bytes = 0;
 };
-// The block table of an inflate launch as it goes to the device in one copy: n InfBlock, then the blocks' n CRC32 words
-// (k_bgzf_crc32 reads them there: d_blk.p + n).
-size_t blk_table_bytes(size_t n) { return n * sizeof(np2::InfBlock) + n * 4; }
-size_t blk_table_slots(size_t n) { return (blk_table_bytes(n) + sizeof(np2::InfBlock) - 1) / sizeof(np2::InfBlock) + 1; }
-// File bytes [c_lo, read_end) -> pinned pieces (pread on the pool's threads: the page cache is copied from, no mapping of the
-// file is faulted in — through the mmap the same 2 GB of a chromosome's BAM took 0.08 to 2.7 s) -> g.d_comp; the 18-byte block
-// headers are parsed out of each piece while it is there.  blks: the blocks that lie wholly inside the range; eof: nothing
-// (but the end-of-file marker) follows them in the file.
-void read_blocks_to_device(GpuFetch &g, int fd, size_t file_len, size_t c_lo, size_t read_end, hipStream_t s, std::vector<GBlk> &blks, bool &eof) {
-    const size_t c_bytes = read_end - c_lo;
-    for (int i = 0; i < 2; ++i) {
-        if (!g.pin[i]) {
-            g.pin[i] = np2h::pinned_pool().get(GpuFetch::PIECE);
-            if (!g.pin[i]) throw np2h::Np2Error(NP2_E_NOMEM, "hipHostMalloc failed");
-        }
-        if (!g.ev[i]) HIPCHK(hipEventCreateWithFlags(&g.ev[i], hipEventDisableTiming));
+// status words of an inflate launch and the walk behind it: [0, n_blk) per block, then n_bad, walk flags, (pad), tail_at (64-bit, 8-byte aligned)
+struct StatusWords {
+    size_t bad, flags, tail;
+    explicit StatusWords(size_t n_blk) : bad((n_blk + 1) & ~(size_t)1), flags(bad + 1), tail(bad + 2) {}
+    size_t count() const { return tail + 2; }
+};
+uint64_t inflated_bytes(const std::vector<BgzfBlock> &blks) { return blks.empty() ? 0 : blks.back().out_off + blks.back().isize; }
+// One inflate launch over blocks whose payloads lie in d_comp (the file from c_lo on), into d_out: their table filled in the pinned
+// block and copied up, the status words and `pad` bytes behind the stream zeroed (the columnariser loads whole words behind the last
+// SEQ), the inflate kernel and, behind it, every block's CRC-32 over what the inflate left — reported through the same status words,
+// no wait of its own.  e0, e1 (optional): recorded around the inflate kernel alone, once all before it is done.  g.d_blk, g.d_status: roomy.
+void inflate_blocks(GpuFetch &g, const std::vector<BgzfBlock> &blks, size_t c_lo, const uint8_t *d_comp, uint8_t *d_out, size_t pad, hipStream_t s,
+                    unsigned long long *d_prof = nullptr, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr) {
+    const size_t n_blk = blks.size();
+    np2::InfBlock *h_tb = (np2::InfBlock *)g.table_block(n_blk);
+    uint32_t *h_crc = (uint32_t *)(h_tb + n_blk); // (the blocks' CRC32 words travel behind the table, in the same copy)
+    for (size_t i = 0; i < n_blk; ++i) {
+        h_tb[i] = np2::InfBlock{blks[i].file_off + blks[i].hdr_len - c_lo, blks[i].out_off, blks[i].clen, blks[i].isize};
+        h_crc[i] = blks[i].crc;
     }
-    auto small_read = [&](uint64_t off, uint8_t *dst, size_t n) { // a few bytes that straddle a piece
-        if (off + n > file_len || pread(fd, dst, n, (off_t)off) != (ssize_t)n) throw np2h::Np2Error(NP2_E_ARG, "truncated BGZF block");
+    HIPCHK(hipMemcpyAsync(g.d_blk.p, h_tb, blk_table_bytes(n_blk), hipMemcpyHostToDevice, s));
+    const StatusWords w(n_blk);
+    HIPCHK(hipMemsetAsync(g.d_status.p, 0, w.count() * 4, s));
+    if (pad) HIPCHK(hipMemsetAsync(d_out + inflated_bytes(blks), 0, pad, s));
+    if (e0) {
+        HIPCHK(hipStreamSynchronize(s));
+        HIPCHK(hipEventRecord(e0, s));
+    }
+    np2::launch_bgzf_inflate(s, g.d_blk.p, (uint32_t)n_blk, d_comp, d_out, g.d_status.p, g.d_status.p + w.bad, d_prof);
+    if (e1) HIPCHK(hipEventRecord(e1, s));
+    if (bgzf_crc_on()) np2::launch_bgzf_crc32(s, g.d_blk.p, (uint32_t)n_blk, (const uint32_t *)(g.d_blk.p + n_blk), d_out, g.d_status.p, g.d_status.p + w.bad);
+}
+// File bytes [c_lo, read_end) -> pinned pieces (pread on the pool's threads: the page cache is copied from, no mapping of the
+// file is faulted in — through the mmap the same 2 GB of a chromosome's BAM took 0.08 to 2.7 s) -> g.d_comp; the block headers
+// are parsed out of each piece while it is there.  blks: the blocks that lie wholly inside the range, their inflated bytes one
+// stream; eof: nothing (but the end-of-file marker) follows them in the file.
+void read_blocks_to_device(GpuFetch &g, int fd, size_t file_len, size_t c_lo, size_t read_end, hipStream_t s, std::vector<BgzfBlock> &blks, bool &eof) {
+    std::vector<uint8_t> sb;
+    auto small_read = [&](uint64_t off, size_t n) { // a few bytes that straddle a piece
+        sb.resize(n);
+        if (off + n > file_len || pread(fd, sb.data(), n, (off_t)off) != (ssize_t)n) throw np2h::Np2Error(NP2_E_ARG, "truncated BGZF block");
+        return (const uint8_t *)sb.data();
     };
     uint64_t hdr_at = c_lo; // file offset of the next block header
     bool range_done = false;
-    size_t piece = 0;
-    for (size_t o = 0; o < c_bytes; o += GpuFetch::PIECE, ++piece) {
-        const int sl = (int)(piece & 1);
-        if (piece >= 2) HIPCHK(hipEventSynchronize(g.ev[sl]));
-        const size_t want = std::min(GpuFetch::PIECE, c_bytes - o);
-        uint8_t *stage = (uint8_t *)g.pin[sl];
-        const size_t SUB = (size_t)1 << 20;
-        std::atomic<int> bad{0};
-        IoPool::get().parallel_for((want + SUB - 1) / SUB, 16, [&](size_t k) {
-            size_t got = 0;
-            const size_t n = std::min(SUB, want - k * SUB);
-            while (got < n) {
-                const ssize_t r = pread(fd, stage + k * SUB + got, n - got, (off_t)(c_lo + o + k * SUB + got));
-                if (r <= 0) {
-                    bad.store(1);
-                    return;
-                }
-                got += (size_t)r;
-            }
-        });
-        if (bad.load()) throw np2h::Np2Error(NP2_E_ARG, "truncated BAM");
-        HIPCHK(hipMemcpyAsync(g.d_comp.p + o, stage, want, hipMemcpyHostToDevice, s));
-        HIPCHK(hipEventRecord(g.ev[sl], s));
-        // the headers that begin inside this piece
-        const uint64_t p0 = c_lo + o, p1 = p0 + want;
+    g.upload(read_end - c_lo, g.d_comp.p, s, [&](uint8_t *stage, size_t o, size_t n) { return pread_full(fd, stage, n, c_lo + o); },
+             [&](const uint8_t *stage, size_t o0, size_t o1) { // the headers that begin inside this piece
+        const uint64_t p0 = c_lo + o0, p1 = c_lo + o1;
         while (!range_done && hdr_at < p1) {
-            if (hdr_at + 18 > file_len) throw np2h::Np2Error(NP2_E_ARG, "not a BGZF block");
-            uint8_t hb[18 + 256];
-            const uint8_t *hd = stage + (hdr_at - p0);
-            if (hdr_at + 18 > p1) small_read(hdr_at, hb, 18), hd = hb;
-            if (hd[0] != 31 || hd[1] != 139 || hd[2] != 8 || !(hd[3] & 4)) throw np2h::Np2Error(NP2_E_ARG, "not a BGZF block");
-            const uint32_t xlen = hd[10] | (hd[11] << 8);
-            if (xlen > 256) throw np2h::Np2Error(NP2_E_ARG, "BGZF block without BC field");
-            if (hd == hb || hdr_at + 12 + xlen > p1) small_read(hdr_at, hb, 12 + (size_t)xlen), hd = hb;
-            const uint8_t *ex = hd + 12;
-            uint32_t bsize = 0;
-            for (size_t q = 0; q + 4 <= xlen;) {
-                const uint32_t slen = ex[q + 2] | (ex[q + 3] << 8);
-                if (ex[q] == 'B' && ex[q + 1] == 'C' && slen == 2 && q + 6 <= xlen) bsize = (ex[q + 4] | (ex[q + 5] << 8)) + 1;
-                q += 4 + slen;
-            }
-            if (!bsize) throw np2h::Np2Error(NP2_E_ARG, "BGZF block without BC field");
-            if (bsize < 12 + xlen + 8 || hdr_at + bsize > file_len) throw np2h::Np2Error(NP2_E_ARG, "truncated BGZF block");
-            if (hdr_at + bsize > read_end) { // (the block continues beyond what this round reads: not part of it)
+            np2h::BgzfHeader h = np2h::bgzf_header(stage + (hdr_at - p0), (size_t)(p1 - hdr_at), file_len - hdr_at);
+            while (h.need) h = np2h::bgzf_header(small_read(hdr_at, h.need), h.need, file_len - hdr_at);
+            if (hdr_at + h.bsize > read_end) { // (the block continues beyond what this round reads: not part of it)
                 range_done = true;
                 break;
             }
-            uint8_t tb8[8];
-            const uint64_t tail = hdr_at + bsize - 8;
-            const uint8_t *tp = stage + (tail - p0);
-            if (tail + 8 > p1) small_read(tail, tb8, 8), tp = tb8;
-            GBlk b;
-            b.file_off = hdr_at, b.hdr_len = 12 + xlen, b.clen = bsize - 12 - xlen - 8, b.bsize = bsize;
-            b.crc = le32(tp);
-            b.isize = tp[4] | (tp[5] << 8) | (tp[6] << 16) | ((uint32_t)tp[7] << 24);
-            blks.push_back(b);
-            hdr_at += bsize;
+            const uint64_t tail = hdr_at + h.bsize - 8;
+            const np2h::BgzfTrailer t = np2h::bgzf_trailer(tail + 8 > p1 ? small_read(tail, 8) : stage + (tail - p0));
+            blks.push_back(BgzfBlock{hdr_at, inflated_bytes(blks), h.hdr_len, h.clen, t.isize, h.bsize, t.crc});
+            hdr_at += h.bsize;
         }
-    }
+    });
     eof = false;
     if (hdr_at >= file_len) eof = true;
     else if (hdr_at + 28 == file_len) { // nothing but the end-of-file marker behind the range: the range IS the rest of the file
-        uint8_t mk[28];
-        small_read(hdr_at, mk, 28);
+        const uint8_t *mk = small_read(hdr_at, 28);
         if (mk[0] == 31 && mk[1] == 139 && (mk[24] | mk[25] | mk[26] | mk[27]) == 0) eof = true;
     }
 }
@@ -2016,31 +1762,17 @@ ResidentBam *resident_for(np2_bam *bam, GpuFetch &g, hipStream_t s) {
         read_blocks_to_device(g, fd, file_len, c_lo, file_len, s, rb->blks, eof);
         const size_t n_blk = rb->blks.size();
         if (!n_blk || !eof) throw np2h::Np2Error(NP2_E_ARG, "BGZF blocks do not reach the end of the file");
-        rb->out_off.assign(n_blk + 1, 0);
-        for (size_t i = 0; i < n_blk; ++i) rb->out_off[i + 1] = rb->out_off[i] + rb->blks[i].isize;
-        const uint64_t total = rb->out_off[n_blk];
+        const uint64_t total = inflated_bytes(rb->blks);
         const double t1 = np2h::now_ms();
         rb->d_inf.ensure(total + 128);
         g.d_blk.ensure(blk_table_slots(n_blk));
         g.d_status.ensure(n_blk + 8);
-        np2::InfBlock *h_tb = (np2::InfBlock *)g.host_block(g.h_cigar, g.h_cigar_cap, blk_table_bytes(n_blk));
-        uint32_t *h_crc = (uint32_t *)(h_tb + n_blk); // (the blocks' CRC32 words travel behind the table, in the same copy)
-        for (size_t i = 0; i < n_blk; ++i) {
-            h_tb[i] = np2::InfBlock{rb->blks[i].file_off + rb->blks[i].hdr_len - c_lo, rb->out_off[i], rb->blks[i].clen, rb->blks[i].isize};
-            h_crc[i] = rb->blks[i].crc;
-        }
-        HIPCHK(hipMemcpyAsync(g.d_blk.p, h_tb, blk_table_bytes(n_blk), hipMemcpyHostToDevice, s));
-        const size_t w_bad = (n_blk + 1) & ~(size_t)1;
-        HIPCHK(hipMemsetAsync(g.d_status.p, 0, (w_bad + 4) * 4, s));
-        HIPCHK(hipMemsetAsync(rb->d_inf.p + total, 0, 128, s)); // (the columnariser loads whole words behind the last SEQ)
-        np2::launch_bgzf_inflate(s, g.d_blk.p, (uint32_t)n_blk, g.d_comp.p, rb->d_inf.p, g.d_status.p, g.d_status.p + w_bad);
         // (a CRC mismatch counts like a block that does not inflate: no resident stream, and the per-reference path names the block)
-        if (bgzf_crc_on()) np2::launch_bgzf_crc32(s, g.d_blk.p, (uint32_t)n_blk, (const uint32_t *)(g.d_blk.p + n_blk), rb->d_inf.p, g.d_status.p, g.d_status.p + w_bad);
-        uint32_t n_bad = 0;
-        HIPCHK(hipMemcpyAsync(h_tb, g.d_status.p + w_bad, 4, hipMemcpyDeviceToHost, s));
+        inflate_blocks(g, rb->blks, c_lo, g.d_comp.p, rb->d_inf.p, 128, s);
+        const uint32_t *n_bad = (const uint32_t *)g.table_block(n_blk);
+        HIPCHK(hipMemcpyAsync((void *)n_bad, g.d_status.p + StatusWords(n_blk).bad, 4, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
-        memcpy(&n_bad, h_tb, 4);
-        if (n_bad) throw np2h::Np2Error(NP2_E_ARG, "BGZF inflate failed"); // (or its CRC: caught below either way)
+        if (*n_bad) throw np2h::Np2Error(NP2_E_ARG, "BGZF inflate failed"); // (or its CRC: caught below either way)
         g.d_comp.release(); // (the file's bytes are not needed again)
         rb->built = true;
         rb->failed = false;
@@ -2051,11 +1783,224 @@ ResidentBam *resident_for(np2_bam *bam, GpuFetch &g, hipStream_t s) {
         (void)hipGetLastError();
         (void)hipStreamSynchronize(s);
         rb->blks.clear();
-        rb->out_off.clear();
         rb->d_inf.release();
         return nullptr;
     }
     return rb.get();
+}
+
+// One call of fetch_records_gpu, as its steps share it: what is asked for, the round's blocks, what a round hands to the next.
+struct FetchJob {
+    np2_bam *bam;
+    GpuFetch &g;
+    int tid;
+    uint32_t L, zone_lo, zone_hi;
+    hipStream_t s;
+    bool prof;
+    double t0;
+    uint64_t start_off;
+    size_t c_lo, file_len;
+    // the round's blocks and the stream their inflated bytes make
+    std::vector<BgzfBlock> blks;
+    const uint8_t *inf = nullptr;
+    uint64_t total = 0;
+    size_t c_bytes = 0;
+    bool eof = false;
+    double t1 = 0, t_up = 0, t_inf = 0, t2 = 0;
+    size_t extra = 0; // bytes read beyond the index's end of the reference (an index that understates it costs a second round)
+    // A block that does not inflate, or not to bytes of its CRC, may lie in what is read AHEAD of the reference's last record
+    // (64 KiB and more: another reference's blocks, which htslib would never open for this one).  The first such block ends
+    // the range instead: the round is repeated up to it, and the error is raised only if the walk then wants to go on.
+    size_t cap_end = 0;
+    std::string held_err;
+};
+enum FetchNext { FETCH_GO, FETCH_DONE, FETCH_HOST, FETCH_AGAIN }; // after a step: the next one | records out (or none) | the host's way | another round
+
+// Step 1, the blocks of [c_lo, read_end): the reference's stretch of the resident stream, or file bytes read, uploaded and inflated.
+FetchNext fetch_take_blocks(FetchJob &j, ResidentBam *res, size_t read_end) {
+    GpuFetch &g = j.g;
+    hipStream_t s = j.s;
+    j.blks.clear();
+    j.c_bytes = read_end - j.c_lo;
+    j.t1 = j.t0, j.t_up = 0, j.t_inf = 0;
+    if (res) {
+        // ---- the reference's stretch of the resident stream --------------------------------------------------------------
+        const auto &all = res->blks;
+        size_t first = (size_t)(std::lower_bound(all.begin(), all.end(), (uint64_t)j.c_lo, [](const BgzfBlock &x, uint64_t v) { return x.file_off < v; }) - all.begin());
+        if (first == all.size() || all[first].file_off != j.c_lo) return FETCH_HOST; // the index does not point at a block of this file
+        size_t last = first;
+        while (last < all.size() && all[last].file_off + all[last].bsize <= read_end) ++last;
+        j.blks.assign(all.begin() + (long)first, all.begin() + (long)last);
+        j.eof = last == all.size() || (last + 1 == all.size() && all[last].isize == 0);
+        const size_t n_blk = j.blks.size();
+        if (!n_blk) return FETCH_DONE;
+        const uint64_t base = all[first].out_off;
+        for (BgzfBlock &b : j.blks) b.out_off -= base;
+        j.total = inflated_bytes(j.blks);
+        j.inf = res->d_inf.p + base;
+        g.d_status.ensure(n_blk + 8);
+        HIPCHK(hipMemsetAsync(g.d_status.p, 0, StatusWords(n_blk).count() * 4, s));
+        j.t1 = j.t_up = j.t_inf = np2h::now_ms();
+        return FETCH_GO;
+    }
+    // ---- file bytes -> pinned pieces -> device; the block headers parsed on the way ---------------------------------------
+    // (file bytes + inflated stream: 13 GB for a human chromosome.  No room on the device next to what else lives there ->
+    // the host pool streams the same records through 128 MiB of host memory)
+    static const bool test_no_room = getenv("NP2_TEST_FETCH_NO_ROOM") != nullptr; // (tests/test_gpu_inflate.py)
+    auto room = [&](auto &buf, size_t n) {
+        if (test_no_room && (void *)&buf == (void *)&g.d_inf) return false;
+        try {
+            buf.ensure(n);
+        } catch (const np2h::Np2Error &) {
+            (void)hipGetLastError();
+            return false;
+        }
+        return true;
+    };
+    if (!room(g.d_comp, j.c_bytes + 64)) return FETCH_HOST;
+    read_blocks_to_device(g, fileno(j.bam->z.f), j.file_len, j.c_lo, read_end, s, j.blks, j.eof);
+    if (j.blks.empty()) {
+        HIPCHK(hipStreamSynchronize(s));
+        return FETCH_DONE;
+    }
+    const size_t n_blk = j.blks.size();
+    j.total = inflated_bytes(j.blks);
+    j.t1 = np2h::now_ms();
+    // ---- inflate --------------------------------------------------------------------------------------------------------
+    if (!room(g.d_inf, j.total + 128)) {
+        HIPCHK(hipStreamSynchronize(s)); // (the uploads into d_comp)
+        return FETCH_HOST;
+    }
+    j.inf = g.d_inf.p;
+    g.d_blk.ensure(blk_table_slots(n_blk));
+    g.d_status.ensure(n_blk + 8);
+    if (j.prof) {
+        HIPCHK(hipStreamSynchronize(s));
+        j.t_up = np2h::now_ms();
+    }
+    inflate_blocks(g, j.blks, j.c_lo, g.d_comp.p, g.d_inf.p, 64, s);
+    if (j.prof) {
+        HIPCHK(hipStreamSynchronize(s));
+        j.t_inf = np2h::now_ms();
+    }
+    return FETCH_GO;
+}
+
+// Step 2, chain starts: the linear index's record starts inside the range, as stream offsets.  false: the index is not this file's.
+bool fetch_chain_starts(const FetchJob &j, std::vector<uint64_t> &starts) {
+    const size_t n_blk = j.blks.size();
+    starts.push_back(j.blks[0].out_off + (j.start_off & 0xFFFF));
+    size_t bi = 0;
+    uint64_t prev = j.start_off;
+    for (uint64_t v : j.bam->lin[j.tid]) {
+        if (v <= prev) continue; // (0 = empty window; entries repeat while one record spans several windows)
+        const uint64_t fo = v >> 16;
+        while (bi < n_blk && j.blks[bi].file_off < fo) ++bi;
+        if (bi == n_blk) break;                      // beyond the range read so far
+        if (j.blks[bi].file_off != fo) return false; // not the start of a block
+        const uint64_t so = j.blks[bi].out_off + (v & 0xFFFF);
+        if ((v & 0xFFFF) >= j.blks[bi].isize) return false;
+        starts.push_back(so);
+        prev = v;
+    }
+    return true;
+}
+
+// Step 3: the chains' records counted, then ONE wait — block statuses' summary, the walk's flags, the chains' counts (info) — and
+// what they say: a damaged block, a walk that failed or wants a longer range, or on to the records.
+FetchNext fetch_count_and_judge(FetchJob &j, const std::vector<uint64_t> &starts, std::vector<uint2> &info) {
+    GpuFetch &g = j.g;
+    hipStream_t s = j.s;
+    const size_t n_blk = j.blks.size();
+    const uint32_t n_chains = (uint32_t)starts.size();
+    const StatusWords w(n_blk);
+    void *h_tb = g.table_block(n_blk);
+    HIPCHK(hipMemsetAsync(g.d_status.p + w.tail, 0xFF, 8, s));
+    g.d_starts.ensure(n_chains + 1);
+    g.d_info.ensure(n_chains + 1);
+    g.d_off.ensure(n_chains + 1);
+    uint64_t *h_st = (uint64_t *)g.host_block(g.h_recs, g.h_recs_cap, (size_t)n_chains * 8 + 64);
+    memcpy(h_st, starts.data(), (size_t)n_chains * 8);
+    HIPCHK(hipMemcpyAsync(g.d_starts.p, h_st, (size_t)n_chains * 8, hipMemcpyHostToDevice, s));
+    np2::launch_bam_chain_count(s, j.inf, g.d_starts.p, n_chains, j.total, j.tid, j.L, j.zone_lo, j.zone_hi, g.d_info.p, g.d_status.p + w.flags,
+                                (unsigned long long *)(g.d_status.p + w.tail));
+    info.resize(n_chains);
+    HIPCHK(hipMemcpyAsync(h_st, g.d_info.p, (size_t)n_chains * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(h_tb, g.d_status.p + w.bad, 16, hipMemcpyDeviceToHost, s)); // (stream order: after the table's upload has read it)
+    HIPCHK(hipStreamSynchronize(s));
+    memcpy(info.data(), h_st, (size_t)n_chains * 8);
+    const uint32_t *tailw = (const uint32_t *)h_tb; // n_bad, the walk's flags
+    j.t2 = np2h::now_ms();
+    if (tailw[0]) { // which block, and why
+        std::vector<uint32_t> stv(n_blk);
+        HIPCHK(hipMemcpy(stv.data(), g.d_status.p, n_blk * 4, hipMemcpyDeviceToHost));
+        size_t i = 0;
+        while (i < n_blk && !stv[i]) ++i;
+        if (i < n_blk) {
+            const std::string msg = stv[i] == np2inf::ST_CRC_MISMATCH ? crc_msg(j.blks[i].file_off)
+                                                                       : "BGZF inflate failed (block at file offset " + std::to_string(j.blks[i].file_off) + ", status " + std::to_string(stv[i]) + ")";
+            if (i == 0 || !j.held_err.empty()) throw np2h::Np2Error(NP2_E_ARG, msg);
+            j.held_err = msg, j.cap_end = (size_t)j.blks[i].file_off; // (the blocks before it once more, by themselves)
+            return FETCH_AGAIN;
+        }
+    }
+    const uint32_t flags = tailw[1];
+    if (flags & np2::WALK_BAD) throw np2h::Np2Error(NP2_E_ARG, "BAM/SAM parsing failed!");
+    if (flags & np2::WALK_MISALIGNED) return FETCH_HOST;
+    if ((flags & (np2::WALK_TAIL | np2::WALK_AT_END)) && !j.eof) { // the reference's records go on beyond the index's end: further
+        if (!j.held_err.empty()) throw np2h::Np2Error(NP2_E_ARG, j.held_err); // (into the damaged block)
+        j.extra = std::max<size_t>((size_t)1 << 20, j.extra * 2 + j.c_bytes / 4);
+        return FETCH_AGAIN;
+    }
+    if (flags & np2::WALK_TAIL) throw np2h::Np2Error(NP2_E_ARG, "truncated BAM");
+    return FETCH_GO;
+}
+
+// Step 4: offsets of the chains' records and CIGAR words, the records themselves written on the device and read back, with
+// their virtual offsets where the caller wants them.
+void fetch_write_back(FetchJob &j, const std::vector<uint2> &info, GpuRecs &out, std::vector<uint64_t> *voffs, uint64_t &n_rec, uint64_t &n_cig) {
+    GpuFetch &g = j.g;
+    hipStream_t s = j.s;
+    const uint32_t n_chains = (uint32_t)info.size();
+    std::vector<uint2> off(n_chains);
+    n_rec = n_cig = 0;
+    for (uint32_t c = 0; c < n_chains; ++c) {
+        off[c] = make_uint2((uint32_t)n_rec, (uint32_t)n_cig);
+        n_rec += info[c].x, n_cig += info[c].y;
+    }
+    if (n_rec > 0xFFFFFFF0ull || n_cig > 0xFFFFFFF0ull) throw np2h::Np2Error(NP2_E_NOMEM, "too many records for one contig");
+    out.n_recs = (uint32_t)n_rec;
+    out.d_stream = j.inf;
+    out.stream_bytes = j.total + 16;
+    if (!n_rec) return;
+    g.d_recs.ensure(n_rec + 1);
+    g.d_cig_src.ensure(n_rec + 1);
+    g.d_cigar.ensure(n_cig + 1);
+    uint64_t *h_st = (uint64_t *)g.h_recs; // (the chain starts' block: n_chains * 8 bytes and more)
+    memcpy(h_st, off.data(), (size_t)n_chains * 8);
+    HIPCHK(hipMemcpyAsync(g.d_off.p, h_st, (size_t)n_chains * 8, hipMemcpyHostToDevice, s));
+    np2::launch_bam_chain_write(s, j.inf, g.d_starts.p, n_chains, j.total, j.tid, j.L, j.zone_lo, j.zone_hi, g.d_off.p, g.d_recs.p, g.d_cig_src.p);
+    np2::launch_bam_cigars(s, j.inf, g.d_recs.p, g.d_cig_src.p, (uint32_t)n_rec, g.d_cigar.p);
+    HIPCHK(hipStreamSynchronize(s)); // (h_st is about to be given up for a larger block)
+    if (j.prof) fprintf(stderr, "  fetch_records_gpu: offsets + write + cigars %.2f ms\n", np2h::now_ms() - j.t2);
+    np2_bamrec_t *hr = (np2_bamrec_t *)g.host_block(g.h_recs, g.h_recs_cap, n_rec * sizeof(np2_bamrec_t) + 64);
+    uint32_t *hc = (uint32_t *)g.host_block(g.h_cigar, g.h_cigar_cap, n_cig * 4 + 64);
+    HIPCHK(hipMemcpyAsync(hr, g.d_recs.p, n_rec * sizeof(np2_bamrec_t), hipMemcpyDeviceToHost, s));
+    if (n_cig) HIPCHK(hipMemcpyAsync(hc, g.d_cigar.p, n_cig * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    out.recs = hr, out.cigar = hc;
+    if (voffs) { // stream offset of every record's start -> (file offset of its block << 16 | offset inside the block)
+        std::vector<uint64_t> src(n_rec);
+        HIPCHK(hipMemcpy(src.data(), g.d_cig_src.p, n_rec * 8, hipMemcpyDeviceToHost));
+        voffs->resize(n_rec);
+        IoPool::get().parallel_for((size_t)((n_rec + 4095) / 4096), 16, [&](size_t blk) {
+            for (uint64_t i = blk * 4096; i < std::min<uint64_t>(n_rec, (blk + 1) * 4096); ++i) {
+                const uint64_t at = src[i] - 36u - hr[i].pad; // (first byte of the record's block_size field)
+                const BgzfBlock &b = *(std::upper_bound(j.blks.begin(), j.blks.end(), at, [](uint64_t v, const BgzfBlock &x) { return v < x.out_off; }) - 1);
+                (*voffs)[i] = (b.file_off << 16) | (at - b.out_off);
+            }
+        });
+    }
 }
 
 // The records of reference `tid` (all of them: fetch(tid, 0, L)).  false: this BAM / index cannot take the device path
@@ -2066,231 +2011,40 @@ bool fetch_records_gpu(np2_bam *bam, int tid, uint32_t L, uint32_t zone_lo, uint
                        std::vector<uint64_t> *voffs = nullptr) {
     const bool prof = getenv("NP2_IO_PROFILE") != nullptr;
     const double t0 = np2h::now_ms();
-    uint64_t start_off = bam->ref_start[tid];
-    if (start_off == ~0ull) return true; // no record of this reference
+    if (bam->ref_start[tid] == ~0ull) return true; // no record of this reference
     if (bam->lin[tid].empty()) return false;
+    // where to stop: records that start at or beyond zone_hi lie behind the first record overlapping the window AFTER zone_hi's
+    const uint64_t start_off = zone_start_offset(bam, tid, zone_lo);
     uint64_t end_hint = bam->ref_end[tid];
-    {
-        // where to start / stop: the smallest offset of a record overlapping the 16 kb window of zone_lo (an empty window
-        // takes the next one's, like htslib); records that start at or beyond zone_hi lie behind the first record
-        // overlapping the window AFTER zone_hi's
+    if (zone_hi < L) {
         const std::vector<uint64_t> &lin = bam->lin[tid];
-        if (zone_lo > 0) {
-            size_t w = std::min<size_t>(zone_lo >> 14, lin.size() - 1);
-            while (w + 1 < lin.size() && lin[w] == 0) ++w;
-            if (lin[w] != 0) start_off = lin[w];
-        }
-        if (zone_hi < L) {
-            size_t w = (size_t)(zone_hi >> 14) + 1;
-            while (w < lin.size() && lin[w] == 0) ++w;
-            if (w < lin.size()) end_hint = lin[w];
-        }
+        size_t w = (size_t)(zone_hi >> 14) + 1;
+        while (w < lin.size() && lin[w] == 0) ++w;
+        if (w < lin.size()) end_hint = lin[w];
     }
     if (!bam->gpu) bam->gpu = new GpuFetch();
-    GpuFetch &g = *bam->gpu;
-    const int fd = fileno(bam->z.f);
-    const size_t file_len = bam->map_len;
-    const size_t c_lo = (size_t)(start_off >> 16);
-    size_t c_hi = end_hint ? (size_t)(end_hint >> 16) : file_len; // file offset of the last block wanted
-    if (getenv("NP2_TEST_FETCH_SHORT_HINT")) c_hi = c_lo; // test hook: an index that understates where the reference's records end
-    std::vector<GBlk> blks;
-    std::vector<uint64_t> out_off;
-    size_t extra = 0; // bytes read beyond the index's end of the reference (an index that understates it costs a second round)
-    ResidentBam *res = resident_for(bam, g, s); // the whole file on the device already (or now), or nullptr
-    // A block that does not inflate, or not to bytes of its CRC, may lie in what is read AHEAD of the reference's last record
-    // (64 KiB and more: another reference's blocks, which htslib would never open for this one).  The first such block ends
-    // the range instead: the round is repeated up to it, and the error is raised only if the walk then wants to go on.
-    size_t cap_end = file_len;
-    std::string held_err;
+    FetchJob j{bam, *bam->gpu, tid, L, zone_lo, zone_hi, s, prof, t0, start_off, (size_t)(start_off >> 16), bam->map_len};
+    j.cap_end = j.file_len;
+    size_t c_hi = end_hint ? (size_t)(end_hint >> 16) : j.file_len; // file offset of the last block wanted
+    if (getenv("NP2_TEST_FETCH_SHORT_HINT")) c_hi = j.c_lo; // test hook: an index that understates where the reference's records end
+    ResidentBam *res = resident_for(bam, j.g, s); // the whole file on the device already (or now), or nullptr
     for (int round = 0;; ++round) {
         if (round > 40) throw np2h::Np2Error(NP2_E_ARG, "BAM/SAM parsing failed!");
-        blks.clear();
-        const size_t read_end = std::min(std::min(file_len, c_hi + 65536 + extra), cap_end);
-        const size_t c_bytes = read_end - c_lo;
-        bool eof = false;
-        const uint8_t *inf = nullptr; // the inflated stream of the blocks taken
-        uint64_t total = 0;
-        double t1 = t0, t_up = 0, t_inf = 0;
-        size_t n_blk = 0;
-        if (res) {
-            // ---- the reference's stretch of the resident stream --------------------------------------------------------------
-            const auto &all = res->blks;
-            size_t first = (size_t)(std::lower_bound(all.begin(), all.end(), (uint64_t)c_lo, [](const GBlk &x, uint64_t v) { return x.file_off < v; }) - all.begin());
-            if (first == all.size() || all[first].file_off != c_lo) return false; // the index does not point at a block of this file
-            size_t last = first;
-            while (last < all.size() && all[last].file_off + all[last].bsize <= read_end) ++last;
-            blks.assign(all.begin() + (long)first, all.begin() + (long)last);
-            eof = last == all.size() || (last + 1 == all.size() && all[last].isize == 0);
-            n_blk = blks.size();
-            if (!n_blk) return true;
-            out_off.assign(n_blk + 1, 0);
-            for (size_t i = 0; i <= n_blk; ++i) out_off[i] = res->out_off[first + i] - res->out_off[first];
-            total = out_off[n_blk];
-            inf = res->d_inf.p + res->out_off[first];
-            g.d_status.ensure(n_blk + 8);
-            t1 = t_up = t_inf = np2h::now_ms();
-        } else {
-            // ---- file bytes -> pinned pieces -> device; the block headers parsed on the way ---------------------------------------
-            // (file bytes + inflated stream: 13 GB for a human chromosome.  No room on the device next to what else lives there ->
-            // false: the host pool streams the same records through 128 MiB of host memory)
-            static const bool test_no_room = getenv("NP2_TEST_FETCH_NO_ROOM") != nullptr; // (tests/test_gpu_inflate.py)
-            auto room = [&](auto &buf, size_t n) {
-                if (test_no_room && (void *)&buf == (void *)&g.d_inf) return false;
-                try {
-                    buf.ensure(n);
-                } catch (const np2h::Np2Error &) {
-                    (void)hipGetLastError();
-                    return false;
-                }
-                return true;
-            };
-            if (!room(g.d_comp, c_bytes + 64)) return false;
-            read_blocks_to_device(g, fd, file_len, c_lo, read_end, s, blks, eof);
-            if (blks.empty()) {
-                HIPCHK(hipStreamSynchronize(s));
-                return true;
-            }
-            n_blk = blks.size();
-            out_off.assign(n_blk + 1, 0);
-            for (size_t i = 0; i < n_blk; ++i) out_off[i + 1] = out_off[i] + blks[i].isize;
-            total = out_off[n_blk];
-            t1 = np2h::now_ms();
-            // ---- inflate --------------------------------------------------------------------------------------------------------
-            if (!room(g.d_inf, total + 128)) {
-                HIPCHK(hipStreamSynchronize(s)); // (the uploads into d_comp)
-                return false;
-            }
-            inf = g.d_inf.p;
-            g.d_blk.ensure(blk_table_slots(n_blk));
-            g.d_status.ensure(n_blk + 8);
-            if (prof) {
-                HIPCHK(hipStreamSynchronize(s));
-                t_up = np2h::now_ms();
-            }
-        }
-        np2::InfBlock *h_tb = (np2::InfBlock *)g.host_block(g.h_cigar, g.h_cigar_cap, std::max<size_t>(blk_table_bytes(n_blk), 64)); // (free until the records come back)
-        // status words: [0, n_blk) per block, then n_bad, walk flags, (pad), tail_at (64-bit, 8-byte aligned)
-        const size_t w_bad = (n_blk + 1) & ~(size_t)1, w_flags = w_bad + 1, w_tail = w_bad + 2;
-        HIPCHK(hipMemsetAsync(g.d_status.p, 0, (w_tail + 2) * 4, s));
-        HIPCHK(hipMemsetAsync(g.d_status.p + w_tail, 0xFF, 8, s));
-        if (!res) {
-            uint32_t *h_crc = (uint32_t *)(h_tb + n_blk); // (the blocks' CRC32 words travel behind the table, in the same copy)
-            for (size_t i = 0; i < n_blk; ++i) {
-                h_tb[i] = np2::InfBlock{blks[i].file_off + blks[i].hdr_len - c_lo, out_off[i], blks[i].clen, blks[i].isize};
-                h_crc[i] = blks[i].crc;
-            }
-            HIPCHK(hipMemcpyAsync(g.d_blk.p, h_tb, blk_table_bytes(n_blk), hipMemcpyHostToDevice, s));
-            HIPCHK(hipMemsetAsync(g.d_inf.p + total, 0, 64, s)); // (the columnariser loads whole words behind the last SEQ)
-            np2::launch_bgzf_inflate(s, g.d_blk.p, (uint32_t)n_blk, g.d_comp.p, g.d_inf.p, g.d_status.p, g.d_status.p + w_bad);
-            // every block's CRC-32 over what the inflate left, reported through the same status words (no wait of its own)
-            if (bgzf_crc_on()) np2::launch_bgzf_crc32(s, g.d_blk.p, (uint32_t)n_blk, (const uint32_t *)(g.d_blk.p + n_blk), g.d_inf.p, g.d_status.p, g.d_status.p + w_bad);
-            if (prof) {
-                HIPCHK(hipStreamSynchronize(s));
-                t_inf = np2h::now_ms();
-            }
-        }
-        // ---- chain starts: the linear index's record starts inside the range ----------------------------------------------------
+        FetchNext next = fetch_take_blocks(j, res, std::min(std::min(j.file_len, c_hi + 65536 + j.extra), j.cap_end));
+        if (next != FETCH_GO) return next == FETCH_DONE;
         std::vector<uint64_t> starts;
-        starts.push_back(out_off[0] + (start_off & 0xFFFF));
-        {
-            size_t bi = 0;
-            uint64_t prev = start_off;
-            for (uint64_t v : bam->lin[tid]) {
-                if (v <= prev) continue; // (0 = empty window; entries repeat while one record spans several windows)
-                const uint64_t fo = v >> 16;
-                while (bi < n_blk && blks[bi].file_off < fo) ++bi;
-                if (bi == n_blk) break;           // beyond the range read so far
-                if (blks[bi].file_off != fo) return false; // not the start of a block: the index is not this file's
-                const uint64_t so = out_off[bi] + (v & 0xFFFF);
-                if ((v & 0xFFFF) >= blks[bi].isize) return false;
-                starts.push_back(so);
-                prev = v;
-            }
-        }
-        const uint32_t n_chains = (uint32_t)starts.size();
-        g.d_starts.ensure(n_chains + 1);
-        g.d_info.ensure(n_chains + 1);
-        g.d_off.ensure(n_chains + 1);
-        uint64_t *h_st = (uint64_t *)g.host_block(g.h_recs, g.h_recs_cap, (size_t)n_chains * 8 + 64);
-        memcpy(h_st, starts.data(), (size_t)n_chains * 8);
-        HIPCHK(hipMemcpyAsync(g.d_starts.p, h_st, (size_t)n_chains * 8, hipMemcpyHostToDevice, s));
-        np2::launch_bam_chain_count(s, inf, g.d_starts.p, n_chains, total, tid, L, zone_lo, zone_hi, g.d_info.p, g.d_status.p + w_flags,
-                                    (unsigned long long *)(g.d_status.p + w_tail));
-        // one wait: block statuses' summary, the walk's flags, the chains' counts
-        std::vector<uint2> info(n_chains);
-        uint32_t tailw[4];
-        HIPCHK(hipMemcpyAsync(h_st, g.d_info.p, (size_t)n_chains * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(h_tb, g.d_status.p + w_bad, 16, hipMemcpyDeviceToHost, s)); // (stream order: after the table's upload has read it)
-        HIPCHK(hipStreamSynchronize(s));
-        memcpy(info.data(), h_st, (size_t)n_chains * 8);
-        memcpy(tailw, h_tb, 16);
-        const double t2 = np2h::now_ms();
-        if (tailw[0]) { // which block, and why
-            std::vector<uint32_t> stv(n_blk);
-            HIPCHK(hipMemcpy(stv.data(), g.d_status.p, n_blk * 4, hipMemcpyDeviceToHost));
-            size_t i = 0;
-            while (i < n_blk && !stv[i]) ++i;
-            if (i < n_blk) {
-                const std::string msg = stv[i] == np2inf::ST_CRC_MISMATCH ? crc_msg(blks[i].file_off)
-                                                                           : "BGZF inflate failed (block at file offset " + std::to_string(blks[i].file_off) + ", status " + std::to_string(stv[i]) + ")";
-                if (i == 0 || !held_err.empty()) throw np2h::Np2Error(NP2_E_ARG, msg);
-                held_err = msg, cap_end = (size_t)blks[i].file_off; // (the blocks before it once more, by themselves)
-                continue;
-            }
-        }
-        const uint32_t flags = tailw[1];
-        if (flags & np2::WALK_BAD) throw np2h::Np2Error(NP2_E_ARG, "BAM/SAM parsing failed!");
-        if (flags & np2::WALK_MISALIGNED) return false;
-        if ((flags & (np2::WALK_TAIL | np2::WALK_AT_END)) && !eof) { // the reference's records go on beyond the index's end: further
-            if (!held_err.empty()) throw np2h::Np2Error(NP2_E_ARG, held_err); // (into the damaged block)
-            extra = std::max<size_t>((size_t)1 << 20, extra * 2 + c_bytes / 4);
-            continue;
-        }
-        if (flags & np2::WALK_TAIL) throw np2h::Np2Error(NP2_E_ARG, "truncated BAM");
-        // ---- offsets of the chains' records and CIGAR words, the records themselves ---------------------------------------------------
-        std::vector<uint2> off(n_chains);
+        if (!fetch_chain_starts(j, starts)) return false;
+        std::vector<uint2> info;
+        next = fetch_count_and_judge(j, starts, info);
+        if (next == FETCH_AGAIN) continue;
+        if (next != FETCH_GO) return false;
         uint64_t n_rec = 0, n_cig = 0;
-        for (uint32_t c = 0; c < n_chains; ++c) {
-            off[c] = make_uint2((uint32_t)n_rec, (uint32_t)n_cig);
-            n_rec += info[c].x, n_cig += info[c].y;
-        }
-        if (n_rec > 0xFFFFFFF0ull || n_cig > 0xFFFFFFF0ull) throw np2h::Np2Error(NP2_E_NOMEM, "too many records for one contig");
-        out.n_recs = (uint32_t)n_rec;
-        out.d_stream = inf;
-        out.stream_bytes = total + 16;
-        if (n_rec) {
-            g.d_recs.ensure(n_rec + 1);
-            g.d_cig_src.ensure(n_rec + 1);
-            g.d_cigar.ensure(n_cig + 1);
-            memcpy(h_st, off.data(), (size_t)n_chains * 8);
-            HIPCHK(hipMemcpyAsync(g.d_off.p, h_st, (size_t)n_chains * 8, hipMemcpyHostToDevice, s));
-            np2::launch_bam_chain_write(s, inf, g.d_starts.p, n_chains, total, tid, L, zone_lo, zone_hi, g.d_off.p, g.d_recs.p, g.d_cig_src.p);
-            np2::launch_bam_cigars(s, inf, g.d_recs.p, g.d_cig_src.p, (uint32_t)n_rec, g.d_cigar.p);
-            HIPCHK(hipStreamSynchronize(s)); // (h_st is about to be given up for a larger block)
-            if (prof) fprintf(stderr, "  fetch_records_gpu: offsets + write + cigars %.2f ms\n", np2h::now_ms() - t2);
-            np2_bamrec_t *hr = (np2_bamrec_t *)g.host_block(g.h_recs, g.h_recs_cap, n_rec * sizeof(np2_bamrec_t) + 64);
-            uint32_t *hc = (uint32_t *)g.host_block(g.h_cigar, g.h_cigar_cap, n_cig * 4 + 64);
-            HIPCHK(hipMemcpyAsync(hr, g.d_recs.p, n_rec * sizeof(np2_bamrec_t), hipMemcpyDeviceToHost, s));
-            if (n_cig) HIPCHK(hipMemcpyAsync(hc, g.d_cigar.p, n_cig * 4, hipMemcpyDeviceToHost, s));
-            HIPCHK(hipStreamSynchronize(s));
-            out.recs = hr, out.cigar = hc;
-            if (voffs) { // stream offset of every record's start -> (file offset of its block << 16 | offset inside the block)
-                std::vector<uint64_t> src(n_rec);
-                HIPCHK(hipMemcpy(src.data(), g.d_cig_src.p, n_rec * 8, hipMemcpyDeviceToHost));
-                voffs->resize(n_rec);
-                IoPool::get().parallel_for((size_t)((n_rec + 4095) / 4096), 16, [&](size_t blk) {
-                    for (uint64_t i = blk * 4096; i < std::min<uint64_t>(n_rec, (blk + 1) * 4096); ++i) {
-                        const uint64_t at = src[i] - 36u - hr[i].pad; // (first byte of the record's block_size field)
-                        const size_t bi = (size_t)(std::upper_bound(out_off.begin(), out_off.end(), at) - out_off.begin()) - 1;
-                        (*voffs)[i] = (blks[bi].file_off << 16) | (at - out_off[bi]);
-                    }
-                });
-            }
-        }
+        fetch_write_back(j, info, out, voffs, n_rec, n_cig);
         if (prof)
             fprintf(stderr, "fetch_records_gpu: %zu blocks (%.1f MB -> %.1f MB), %u chains, %llu records, %llu CIGAR words: file -> pinned pieces (+ block headers) %.2f ms, "
-                            "rest of the upload %.2f ms, inflate %.2f ms, index + count + wait %.2f ms, records back %.2f ms%s\n", n_blk, c_bytes / 1e6, total / 1e6, n_chains,
-                    (unsigned long long)n_rec, (unsigned long long)n_cig, t1 - t0, t_up - t1, t_inf - t_up, t2 - t_inf, np2h::now_ms() - t2, res ? (round ? " (stretch of the resident stream, after extending the range)" : " (stretch of the resident stream)") : (round ? " (after extending the range)" : ""));
+                            "rest of the upload %.2f ms, inflate %.2f ms, index + count + wait %.2f ms, records back %.2f ms%s\n", j.blks.size(), j.c_bytes / 1e6, j.total / 1e6,
+                    (unsigned)starts.size(), (unsigned long long)n_rec, (unsigned long long)n_cig, j.t1 - t0, j.t_up - j.t1, j.t_inf - j.t_up, j.t2 - j.t_inf, np2h::now_ms() - j.t2,
+                    res ? (round ? " (stretch of the resident stream, after extending the range)" : " (stretch of the resident stream)") : (round ? " (after extending the range)" : ""));
         return true;
     }
 }
@@ -2299,74 +2053,56 @@ bool fetch_records_gpu(np2_bam *bam, int tid, uint32_t L, uint32_t zone_lo, uint
 int np2_bgzf_inflate_device(np2_ctx_t *cx, const uint8_t *bgzf, uint64_t n, uint8_t *out, uint64_t out_cap, uint64_t *out_len,
                             float *kernel_ms) {
     if (!cx || (!bgzf && n) || !out_len || (!out && out_cap)) return NP2_E_ARG;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    np2h::DevEvent e0, e1;
     return np2h::abi_guard([&] {
         HIPCHK(hipSetDevice(cx->device));
         hipStream_t s = cx->stream;
         BgzfBatch hdr;
         hdr.map = bgzf, hdr.map_len = (size_t)n, hdr.fpos = 0;
-        std::vector<np2::InfBlock> tb;
-        std::vector<uint32_t> crcs;
-        uint64_t total = 0;
-        for (;;) {
-            BgzfBatch::Blk b;
-            if (!hdr.read_raw(b)) break;
-            tb.push_back(np2::InfBlock{(uint64_t)(b.c - bgzf), total, b.clen, b.isize});
-            crcs.push_back(b.crc);
-            total += b.isize;
-        }
+        std::vector<BgzfBlock> blks;
+        for (BgzfBlock b; hdr.read_raw(b); blks.push_back(b)) b.out_off = inflated_bytes(blks);
+        const uint64_t total = inflated_bytes(blks);
+        const size_t n_blk = blks.size();
         *out_len = total;
         if (total > out_cap) throw np2h::Np2Error(NP2_E_ARG, "output buffer too small");
-        if (tb.empty()) return NP2_OK;
+        if (!n_blk) return NP2_OK;
         GpuFetch g;
         g.d_comp.ensure(n + 64);
         g.d_inf.ensure(total + 64);
-        g.d_blk.ensure(blk_table_slots(tb.size()));
-        g.d_status.ensure(tb.size() + 8);
+        g.d_blk.ensure(blk_table_slots(n_blk));
+        g.d_status.ensure(n_blk + 8);
         g.upload(bgzf, (size_t)n, g.d_comp.p, s);
-        HIPCHK(hipMemcpyAsync(g.d_blk.p, tb.data(), tb.size() * sizeof(np2::InfBlock), hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(g.d_blk.p + tb.size(), crcs.data(), crcs.size() * 4, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemsetAsync(g.d_status.p, 0, (tb.size() + 4) * 4, s));
-        HIPCHK(hipStreamSynchronize(s)); // (tb is pageable: the copy must have read it before it goes)
-        HIPCHK(hipEventCreate(&e0));
-        HIPCHK(hipEventCreate(&e1));
-        HIPCHK(hipEventRecord(e0, s));
         np2h::DevBuf<uint64_t> d_prof;
         const bool kprof = getenv("NP2_INF_PROF") != nullptr; // (phase clocks of the inflate kernel: a tool's switch)
         if (kprof) {
-            d_prof.ensure(tb.size() * 8 + 8);
-            HIPCHK(hipMemsetAsync(d_prof.p, 0, tb.size() * 64, s));
+            d_prof.ensure(n_blk * 8 + 8);
+            HIPCHK(hipMemsetAsync(d_prof.p, 0, n_blk * 64, s));
         }
-        np2::launch_bgzf_inflate(s, g.d_blk.p, (uint32_t)tb.size(), g.d_comp.p, g.d_inf.p, g.d_status.p, g.d_status.p + tb.size(),
-                                 kprof ? (unsigned long long *)d_prof.p : nullptr);
-        HIPCHK(hipEventRecord(e1, s)); // (kernel_ms is the inflate kernel alone: the CRC check goes behind it)
-        if (bgzf_crc_on()) np2::launch_bgzf_crc32(s, g.d_blk.p, (uint32_t)tb.size(), (const uint32_t *)(g.d_blk.p + tb.size()), g.d_inf.p, g.d_status.p, g.d_status.p + tb.size());
+        e0.make(), e1.make();
+        // (kernel_ms is the inflate kernel alone: the CRC check goes behind it)
+        inflate_blocks(g, blks, 0, g.d_comp.p, g.d_inf.p, 0, s, kprof ? (unsigned long long *)d_prof.p : nullptr, e0.e, e1.e);
         if (kprof) {
-            std::vector<uint64_t> pr(tb.size() * 8);
+            std::vector<uint64_t> pr(n_blk * 8);
             HIPCHK(hipMemcpyAsync(pr.data(), d_prof.p, pr.size() * 8, hipMemcpyDeviceToHost, s));
             HIPCHK(hipStreamSynchronize(s));
             double sum[8] = {0};
-            for (size_t i = 0; i < tb.size(); ++i)
+            for (size_t i = 0; i < n_blk; ++i)
                 for (int k = 0; k < 8; ++k) sum[k] += (double)pr[i * 8 + k];
-            const double nb = (double)tb.size();
+            const double nb = (double)n_blk;
             fprintf(stderr, "[inf_prof] %zu blocks; mean clocks per block: total %.0f, wide decode %.0f, chain %.0f (of which match copies %.0f); tokens %.0f, matches %.0f; "
                             "table builds %.0f clocks over %.1f deflate blocks\n",
-                    tb.size(), sum[0] / nb, sum[1] / nb, sum[2] / nb, sum[3] / nb, sum[4] / nb, sum[5] / nb, sum[6] / nb, sum[7] / nb);
+                    n_blk, sum[0] / nb, sum[1] / nb, sum[2] / nb, sum[3] / nb, sum[4] / nb, sum[5] / nb, sum[6] / nb, sum[7] / nb);
         }
-        std::vector<uint32_t> st(tb.size() + 1);
-        HIPCHK(hipMemcpyAsync(st.data(), g.d_status.p, st.size() * 4, hipMemcpyDeviceToHost, s));
+        std::vector<uint32_t> st(n_blk);
+        HIPCHK(hipMemcpyAsync(st.data(), g.d_status.p, n_blk * 4, hipMemcpyDeviceToHost, s));
         if (total) HIPCHK(hipMemcpyAsync(out, g.d_inf.p, total, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
-        if (kernel_ms) HIPCHK(hipEventElapsedTime(kernel_ms, e0, e1));
-        (void)hipEventDestroy(e0), (void)hipEventDestroy(e1);
-        e0 = e1 = nullptr;
-        for (size_t i = 0; i < tb.size(); ++i)
+        if (kernel_ms) *kernel_ms = np2h::elapsed(e0, e1);
+        for (size_t i = 0; i < n_blk; ++i)
             if (st[i] == np2inf::ST_CRC_MISMATCH) throw np2h::Np2Error(NP2_E_ARG, "BGZF CRC32 mismatch (block " + std::to_string(i) + ")");
             else if (st[i]) throw np2h::Np2Error(NP2_E_ARG, "BGZF inflate failed (block " + std::to_string(i) + ", status " + std::to_string(st[i]) + ")");
         return NP2_OK;
     }, [&](int code, const std::string &msg) {
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
         (void)hipStreamSynchronize(cx->stream);
         io_fail(code, msg);
     });
@@ -2374,7 +2110,7 @@ int np2_bgzf_inflate_device(np2_ctx_t *cx, const uint8_t *bgzf, uint64_t n, uint
 
 int np2_crc32_device(np2_ctx_t *cx, const uint8_t *data, uint64_t n, const uint64_t *off, uint32_t n_pieces, uint32_t *crc_out, float *kernel_ms) {
     if (!cx || (!data && n) || (n_pieces && (!off || !crc_out))) return NP2_E_ARG;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    np2h::DevEvent e0, e1;
     return np2h::abi_guard([&] {
         if (!n_pieces) {
             if (kernel_ms) *kernel_ms = 0.f;
@@ -2396,20 +2132,15 @@ int np2_crc32_device(np2_ctx_t *cx, const uint8_t *data, uint64_t n, const uint6
         if (n) g.upload(data, (size_t)n, g.d_inf.p, s);
         HIPCHK(hipMemcpyAsync(g.d_blk.p, tb.data(), tb.size() * sizeof(np2::InfBlock), hipMemcpyHostToDevice, s));
         HIPCHK(hipStreamSynchronize(s)); // (tb is pageable: the copy must have read it before it goes)
-        HIPCHK(hipEventCreate(&e0));
-        HIPCHK(hipEventCreate(&e1));
-        HIPCHK(hipEventRecord(e0, s));
+        e0.make(), e1.make();
+        HIPCHK(hipEventRecord(e0.e, s));
         np2::launch_bgzf_crc32(s, g.d_blk.p, n_pieces, nullptr, g.d_inf.p, nullptr, nullptr, g.d_status.p);
-        HIPCHK(hipEventRecord(e1, s));
+        HIPCHK(hipEventRecord(e1.e, s));
         HIPCHK(hipMemcpyAsync(crc_out, g.d_status.p, (size_t)n_pieces * 4, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
-        if (kernel_ms) HIPCHK(hipEventElapsedTime(kernel_ms, e0, e1));
-        (void)hipEventDestroy(e0), (void)hipEventDestroy(e1);
-        e0 = e1 = nullptr;
+        if (kernel_ms) *kernel_ms = np2h::elapsed(e0, e1);
         return NP2_OK;
     }, [&](int code, const std::string &msg) {
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
         (void)hipStreamSynchronize(cx->stream);
         io_fail(code, msg);
     });

@@ -185,3 +185,28 @@ def test_device_free_entry_points_report_bad_input_as_status(tmp_path):
     with pytest.raises(api.Np2Error) as e:
         api.phase_vote([1, 2, 3], [(1, 2, -1.0), (1, 3, -1.0), (2, 3, float("nan"))])
     assert e.value.code == E_REFPANIC
+
+
+def test_bam_open_reports_damaged_bgzf_headers(tmp_path):
+    """The stream that reads a BAM's header parses its blocks with the parser every reader shares (csrc/np2_bgzf.hpp): a BC
+    subfield whose value would lie beyond the extra field, a block size too small for header and trailer, and a file
+    shorter than a header are statuses with their messages (no device is needed to open a BAM)."""
+    import struct
+    from nextpolish2_amd import io
+    E_ARG = -1
+
+    def head(extra):
+        return struct.pack("<BBBBIBBH", 31, 139, 8, 4, 0, 0, 255, len(extra)) + extra
+    cases = {
+        # XLEN 4: the BC subfield's header ends the extra field; the payload's first bytes stand where BSIZE would be
+        "bc_cut.bam": (head(b"BC\2\0") + b"\x1b\0" + b"\3\0" + bytes(8), "BGZF block without BC field"),
+        # BSIZE = 12 + XLEN + 7
+        "small.bam": (head(b"BC\2\0" + struct.pack("<H", 12 + 6 + 7 - 1)) + b"\3\0" + bytes(8), "truncated BGZF block"),
+        "17.bam": ((head(b"BC\2\0" + struct.pack("<H", 27)) + b"\3\0" + bytes(8))[:17], "not a BGZF block"),
+    }
+    for name, (data, msg) in cases.items():
+        path = tmp_path / name
+        path.write_bytes(data)
+        with pytest.raises(api.Np2Error) as e:
+            io.Bam(str(path))
+        assert e.value.code == E_ARG and msg in str(e.value), (name, str(e.value))

@@ -196,3 +196,81 @@ def test_no_room_on_the_device_takes_the_host_pools_path(tmp_path):
         if mode == "no_room":
             assert "fetch_records_gpu:" not in r.stderr.decode()
     assert outs["no_room"] == outs["libdeflate"] and len(outs["no_room"]) > 100000
+
+
+def _strip_subfield(data, sub):
+    """a BGZF file written with extra_subfield=sub, the subfield taken out of every block again"""
+    out, at = [], 0
+    while at < len(data):
+        xlen, = struct.unpack_from("<H", data, at + 10)
+        assert data[at + 12:at + 12 + len(sub)] == sub and data[at + 12 + len(sub):at + 16 + len(sub)] == b"BC\2\0"
+        bsize = struct.unpack_from("<H", data, at + 16 + len(sub))[0] + 1
+        out.append(data[at:at + 10] + struct.pack("<H", xlen - len(sub)) + b"BC\2\0" + struct.pack("<H", bsize - len(sub) - 1) + data[at + 12 + xlen:at + bsize])
+        at += bsize
+    return b"".join(out)
+
+
+def test_blocks_with_a_long_extra_field_read_like_plain_ones(tmp_path):
+    """XLEN > 256: every block carries a 300-byte subfield in front of BC (the format allows any; the host pool always took
+    them, the device path refused them as "BGZF block without BC field").  The same records written plain and padded, as one
+    reference and as two (two: the whole file inflated on the device once), read with the device path and with the host pool:
+    pileup (records, CIGAR columns, SEQ), per-base depth (every record's position and CIGAR) and polished contig are the same."""
+    L = 3000
+    s = Synth(L, depth=8, seed=1000 + L % 97, read_len_mean=L / 3, read_len_sd=L / 20, read_len_min=L // 3)
+    recs = pileup_to_records(s.pileup, tid=0, rng=np.random.default_rng(3), decorate=True)
+    sub = b"ZZ" + struct.pack("<H", 296) + bytes(range(256)) + bytes(40)
+    assert len(sub) == 300
+    files = []
+    for n_ref, refs in ((1, [("ctgA", L)]), (2, [("ctgA", L), ("ctgB", 1000)])):
+        plain, padded = str(tmp_path / ("plain%d.bam" % n_ref)), str(tmp_path / ("padded%d.bam" % n_ref))
+        write_bam(plain, refs, recs)
+        write_bam(padded, refs, recs, extra_subfield=sub)
+        # the writer's default is what it was, byte for byte: the padded file without its padding IS the plain file, whose
+        # blocks begin with the one header there has always been; and the index does not depend on the padding's presence
+        raw = open(plain, "rb").read()
+        assert raw[:16] == struct.pack("<BBBBIBBHBBH", 31, 139, 8, 4, 0, 0, 255, 6, 66, 67, 2)
+        write_bam(str(tmp_path / "again.bam"), refs, recs, extra_subfield=b"")
+        assert open(str(tmp_path / "again.bam"), "rb").read() == raw
+        assert _strip_subfield(open(padded, "rb").read(), sub) == raw
+        assert struct.unpack_from("<H", open(padded, "rb").read(), 10)[0] == 306
+        files += [plain, padded]
+    (tmp_path / "ref.txt").write_bytes(s.pileup.ref.tobytes())
+    np2io.write_yak(str(tmp_path / "k21.yak"), s.yak(21))
+    # one process for every leg (NP2_INFLATE is read per contig): each file through the device path, then through the host pool
+    code = ("import os, sys, numpy as np; sys.path.insert(0, %r)\n"
+            "from nextpolish2_amd import Opts\nfrom nextpolish2_amd import io as np2io\n"
+            "pol = np2io.polisher_from_yak_files([sys.argv[2]])\n"
+            "ref = open(sys.argv[1], 'rb').read()\n"
+            "out = {}\n"
+            "for i, path in enumerate(sys.argv[4:]):\n"
+            "    for mode in ('gpu', 'libdeflate'):\n"
+            "        os.environ['NP2_INFLATE'] = mode\n"
+            "        sys.stderr.write('leg %%d %%s\\n' %% (i, mode)); sys.stderr.flush()\n"
+            "        bam = np2io.Bam(path)\n"
+            "        c = np2io.contig_from_bam(pol, bam, 'ctgA', ref, np2io.FrontOpts())\n"
+            "        ex = np2io.export_contig(pol, c, np.frombuffer(ref, dtype=np.uint8))\n"
+            "        b, p = pol.polish_resident(c, Opts())\n"
+            "        runs, st, depth = np2io.depth_from_bam(pol, bam, 'ctgA', len(ref), min_len=1, want_depth=True)\n"
+            "        for k, v in (('reads', ex.reads), ('nib', ex.nibbles), ('b', b), ('p', p), ('runs', runs), ('depth', depth)):\n"
+            "            out['%%d_%%s_%%s' %% (i, mode, k)] = v\n"
+            "        bam.close()\n"
+            "np.savez(sys.argv[3], **out)\n" % ROOT)
+    npz = str(tmp_path / "out.npz")
+    r = subprocess.run([sys.executable, "-c", code, str(tmp_path / "ref.txt"), str(tmp_path / "k21.yak"), npz] + files,
+                       capture_output=True, text=True, env=dict(os.environ, NP2_IO_PROFILE="1"), timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    got = np.load(npz)
+    legs = r.stderr.split("leg ")[1:]
+    assert len(legs) == 8
+    for leg in legs:  # (the device path really ran where it was asked for, the whole-file inflate for the two-reference files)
+        i, mode = leg.split()[:2]
+        assert ("fetch_records_gpu:" in leg) == (mode == "gpu"), leg[-2000:]
+        if mode == "gpu" and int(i) >= 2:
+            assert "stretch of the resident stream" in leg, leg[-2000:]
+    assert r.stderr.count("resident BAM:") == 2, r.stderr[-3000:]
+    assert len(got["0_libdeflate_reads"]) > 8 and got["0_libdeflate_depth"].max() >= 6
+    for k in ("reads", "nib", "b", "p", "runs", "depth"):
+        want = got["0_libdeflate_" + k]  # the plain single-reference file through the host pool
+        for i in range(4):
+            for mode in ("gpu", "libdeflate"):
+                assert np.array_equal(got["%d_%s_%s" % (i, mode, k)], want), (i, mode, k)
