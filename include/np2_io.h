@@ -251,6 +251,86 @@ int np2_ctx_create_from_reads_qc(np2_ctx_t **out, int device, const char *const 
 /* host only, no device: the two streams the reader makes of one FASTQ file (n bytes each; release both with np2_free) */
 int np2_seqfile_stream_qual(const char *path, uint8_t **seq, uint8_t **qual, uint64_t *n);
 
+/* ---- short-read adapter trimming in front of the k-mer counter: pair overlap and sequence ------------------------------------
+ * What fastp does by default for paired input beside the quality rule above: it finds where the two mates overlap, cuts the
+ * read-through adapter off both, and drops a pair as soon as one mate fails.  THE RULE IS DEFINED HERE, on fastp's documented
+ * options (overlap_len_require 30, overlap_diff_limit 5, overlap_diff_percent_limit 20, -a / --adapter_sequence,
+ * --adapter_sequence_r2); no fastp binary was at hand, and equality with fastp is not claimed.
+ * Notation: a base byte is case-folded; A/T and C/G are complements; any other byte is unknown and matches nothing.  Steps
+ * 1 - 3 of the quality rule run first, on each read alone, unchanged, and give the kept span [a, b).  With qc == NULL they run
+ * with every step off (trims 0, no cuts, n_base_limit 2^32 - 1, Q 0, U 100, min_len 0): the span is the whole read, and step 4
+ * below fails only a read that A or B left empty (class 1).
+ *   A. Pair overlap (pair mode only).  x = r1[a1, b1), n1 long; y = r2[a2, b2), n2 long; rcy the reverse complement of y.
+ *      For a shift s, x[i] faces rcy[i - s].  The overlap is i in [max(0, s), min(n1, n2 + s)), l(s) positions; d(s) is the
+ *      number of them where x[i] is unknown, rcy[i - s] is unknown, or the two differ.  s is accepted if l(s) >= O and
+ *      d(s) <= min(D, floor(P * l(s) / 100)).  Candidates are tried in the order s = 0, 1, 2, .., then s = -1, -2, ..; the
+ *      first accepted one wins (the smallest accepted s >= 0; if there is none, the accepted s < 0 nearest to 0).  On
+ *      acceptance T = n2 + s is the insert length as the kept spans see it, b1 = a1 + min(n1, T), b2 = a2 + min(n2, T).  An
+ *      accepted s > 0 with n1 <= T trims nothing (an overlap without read-through) and still ends the search.  A pair has no
+ *      overlap when either kept span is longer than 1024 bases (the cap bounds the per-wavefront LDS) or shorter than O.
+ *   B. Adapter by sequence, for a read step A did not decide: in single mode every read, in pair mode both mates of a pair
+ *      with no accepted s.  adapter1 is used for single reads and mate 1, adapter2 for mate 2 (NULL: adapter1); without a
+ *      string the step does nothing.  With A the adapter's length and n = b - a (4 <= n <= 1024; other spans are left as
+ *      they are): for p = 0 .. n - 4, c = min(n - p, A), m(p) = #{ j < c : fold(read[a + p + j]) != adapter[j] }.  The
+ *      smallest p with m(p) <= floor(c / 8) wins, and b = a + p.
+ *   C. Step 4 of the quality rule classifies the new [a, b) of every read (classes 0 - 3 unchanged).  In pair mode, if exactly
+ *      one mate has a class other than 0, the other mate gets class 4, mate failed.  Masking is step 5 of the quality rule
+ *      over the final span and class.
+ * Options: O in [1, 1024], D in [0, 1024], P in [0, 100]; an adapter string is 4 - 64 letters of ACGT (upper case); adapter2
+ * needs adapter1, and single mode needs adapter1; anything else is NP2_E_ARG before the first device call.
+ * Out of scope: interleaved FASTQ, read-name checks (names are not compared), fastp's base correction inside the overlap,
+ * merging mates, poly-G / poly-X, adapter auto-detection for single-end input, equality with the fastp binary. */
+#define NP2_SRADAPT_PAIRED 1u
+typedef struct np2_sradapt_opts {
+    uint32_t flags;                /* NP2_SRADAPT_PAIRED: reads 2r and 2r + 1 (files 2i and 2i + 1) are mates */
+    uint32_t overlap_min;          /* O: 30 */
+    uint32_t overlap_diff;         /* D: 5 */
+    uint32_t overlap_diff_percent; /* P: 20 */
+    const char *adapter1;          /* or NULL */
+    const char *adapter2;          /* or NULL: adapter1 */
+} np2_sradapt_opts_t;
+typedef struct np2_sradapt_read {
+    uint32_t begin, end; /* the final [a, b), from the read's first base */
+    uint32_t cls;        /* 0 pass, 1 too short, 2 too many N, 3 low quality, 4 mate failed */
+    uint32_t how;        /* 0 untouched by A and B, 1 end moved by A, 2 end moved by B */
+    uint32_t insert;     /* T for both mates of a pair with an accepted s, otherwise 0 */
+} np2_sradapt_read_t;
+typedef struct np2_sradapt_stats {
+    uint64_t reads, pass, too_short, too_many_n, low_quality, bases_in, bases_out; /* as np2_srqc_stats_t, of the final classes */
+    uint64_t mate_failed;      /* reads of class 4 */
+    uint64_t pairs;
+    uint64_t pairs_overlap;    /* pairs with an accepted s */
+    uint64_t pairs_unsearched; /* pairs past the 1024-base cap */
+    uint64_t trimmed_overlap;  /* reads with how 1 */
+    uint64_t trimmed_seq;      /* reads with how 2 */
+    uint64_t adapter_bases;    /* bases removed by A and B, over all reads */
+} np2_sradapt_stats_t;
+/* np2_srqc_bytes with the adapter rule.  qc == NULL: see above; ad == NULL: pair mode with the defaults and no sequences.
+ * In pair mode the mates are adjacent (read 2r is mate 1, read 2r + 1 mate 2), an odd n_reads is NP2_E_ARG, and a pair
+ * that does not fit a piece is NP2_E_UNSUPPORTED. */
+int np2_sradapt_bytes(int device, const uint8_t *seq, const uint8_t *qual, uint64_t n, const np2_srqc_opts_t *qc,
+                      const np2_sradapt_opts_t *ad, uint8_t *masked_out, np2_sradapt_read_t *reads_out, uint64_t n_reads,
+                      np2_sradapt_stats_t *stats);
+/* FASTQ files -> totals and, with out_paths (or NULL), one cleaned plain-text FASTQ per input.  In pair mode the paths are
+ * R1, R2, R1, R2, .. (an odd n_paths is NP2_E_ARG), the two files of a pair are read in step (files whose record counts
+ * differ are NP2_E_ARG; the message names both files and the first record, 1-based, that the shorter one lacks), and a
+ * pair is written only when both mates pass, so the outputs stay in step.  stats (or NULL): one entry per unit, a file in
+ * single mode and a pair of files in pair mode, then the sum. */
+int np2_sradapt_files(int device, const char *const *paths, int n_paths, const np2_srqc_opts_t *qc, const np2_sradapt_opts_t *ad,
+                      const char *const *out_paths, np2_sradapt_stats_t *stats);
+/* the totals of the last adapter-trimming call on this thread (of a multi-pass count: of one pass) and its kernel's ms */
+int np2_sradapt_last_stats(np2_sradapt_stats_t *stats);
+int np2_sradapt_last_kernel_ms(float *ms);
+/* The three *_qc counting entry points with the adapter rule in front of the counter: ad == NULL is exactly the *_qc call.
+ * Every input must be FASTQ; in pair mode the paths are R1, R2, R1, R2, .. */
+int np2_kcount_files_ad(int device, const char *const *paths, int n_paths, const uint32_t *ks, int n_k, const np2_kcount_opts_t *opts,
+                        const np2_srqc_opts_t *qc, const np2_sradapt_opts_t *ad, np2_yak_t *out /* [n_k] */);
+int np2_kcount_files_to_dumps_ad(int device, const char *const *paths, int n_paths, const uint32_t *ks, int n_k,
+                                 const np2_kcount_opts_t *opts, const np2_srqc_opts_t *qc, const np2_sradapt_opts_t *ad,
+                                 const char *const *out_paths);
+int np2_ctx_create_from_reads_ad(np2_ctx_t **out, int device, const char *const *paths, int n_paths, const uint32_t *ks, int n_k,
+                                 const np2_kcount_opts_t *opts, const np2_srqc_opts_t *qc, const np2_sradapt_opts_t *ad);
+
 /* Read files -> classes (np2_bin_stream's device path, fed by the counter's reader threads through pinned pieces, in
  * file order; errors: np2_last_error(ctx)).  A read's name is its header up to the first whitespace, without '>' / '@';
  * a record without one (one sequence per line) is named by its 1-based number in its file.  Every path of `out` may be

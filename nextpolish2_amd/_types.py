@@ -76,6 +76,24 @@ class np2_srqc_stats_t(C.Structure):
     _fields_ = [(f, C.c_uint64) for f in ("reads", "pass_", "too_short", "too_many_n", "low_quality", "bases_in", "bases_out")]
 
 
+class np2_sradapt_opts_t(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("overlap_min", C.c_uint32), ("overlap_diff", C.c_uint32), ("overlap_diff_percent", C.c_uint32),
+                ("adapter1", C.c_char_p), ("adapter2", C.c_char_p)]
+
+
+class np2_sradapt_read_t(C.Structure):
+    _fields_ = [("begin", C.c_uint32), ("end", C.c_uint32), ("cls", C.c_uint32), ("how", C.c_uint32), ("insert", C.c_uint32)]
+
+
+SRADAPT_STATS = ("reads", "pass", "too_short", "too_many_n", "low_quality", "bases_in", "bases_out", "mate_failed", "pairs", "pairs_overlap",
+                 "pairs_unsearched", "trimmed_overlap", "trimmed_seq", "adapter_bases")
+
+
+class np2_sradapt_stats_t(C.Structure):
+    _fields_ = [("pass_" if f == "pass" else f, C.c_uint64) for f in SRADAPT_STATS]
+
+
+SRADAPT_READ_DTYPE = np.dtype([("begin", "<u4"), ("end", "<u4"), ("cls", "<u4"), ("how", "<u4"), ("insert", "<u4")])
 SRQC_READ_DTYPE = np.dtype([("begin", "<u4"), ("end", "<u4"), ("cls", "<u4")])
 SRQC_STATS = ("reads", "pass", "too_short", "too_many_n", "low_quality", "bases_in", "bases_out")
 

@@ -42,6 +42,8 @@ IO_ABI_SYMBOLS = [
     "np2_depth_from_records", "np2_depth_from_bam",
     "np2_srqc_bytes", "np2_srqc_files", "np2_srqc_last_stats", "np2_srqc_last_kernel_ms", "np2_kcount_files_qc",
     "np2_kcount_files_to_dumps_qc", "np2_ctx_create_from_reads_qc", "np2_seqfile_stream_qual",
+    "np2_sradapt_bytes", "np2_sradapt_files", "np2_sradapt_last_stats", "np2_sradapt_last_kernel_ms", "np2_kcount_files_ad",
+    "np2_kcount_files_to_dumps_ad", "np2_ctx_create_from_reads_ad",
     "np2_rep_bytes", "np2_rep_files",
     "np2_sam_open", "np2_sam_close", "np2_sam_n_refs", "np2_sam_ref_name", "np2_sam_stats", "np2_contig_from_sam",
     "np2_sam_parse_bytes", "np2_sam_export",

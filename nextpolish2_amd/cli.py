@@ -63,6 +63,8 @@ def build_parser():
                    help="drop k-mers of --sr counted fewer than N times [2, or -k/--min_kmer_count where that is smaller]")
     p.add_argument("--sr_qc", nargs="?", const=np2io.SrQc(), default=None, type=np2io.sr_qc_arg, metavar="SPEC",
                    help="with --sr: " + np2io.SR_QC_HELP)
+    p.add_argument("--sr_adapter", nargs="?", const="", default=None, type=np2io.sr_adapter_arg, metavar="SPEC",
+                   help="with --sr: " + np2io.SR_ADAPTER_HELP)
     p.add_argument("-o", "--out", default=None, metavar="FILE", help="output file [stdout]")
     p.add_argument("--qv", default=None, metavar="FILE",
                    help="k-mer QV of every contig as read and as written, per k-mer table, as a TSV (a k-mer the tables do not "
@@ -117,7 +119,9 @@ def build_parser():
 
 def _report_sr_qc(a):
     """the filter's totals as one [INFO] line (on the thread that counted: the totals are that thread's)"""
-    if a.sr_qc is not None:
+    if a.sr_adapter is not None:
+        print(f"[INFO] sr_adapter: {np2io.sradapt_stats_text(np2io.sradapt_last_stats())}", file=sys.stderr)
+    elif a.sr_qc is not None:
         print(f"[INFO] sr_qc: {np2io.srqc_stats_text(np2io.srqc_last_stats())}", file=sys.stderr)
 
 
@@ -341,6 +345,9 @@ def main(argv=None):
         parser.error("give either short.read.yak files or --sr reads, not both")
     if a.sr_qc is not None and not a.sr:
         parser.error("--sr_qc filters the reads of --sr: give --sr")
+    if a.sr_adapter is not None and not a.sr:
+        parser.error("--sr_adapter trims the reads of --sr: give --sr")
+    np2io.check_sr_adapter(parser, a.sr_adapter, a.sr)
     if a.sr:
         a.sr_ks = np2io.sr_k_arg(parser, a.sr_k)
         if not a.sr_ks or any(k < 2 or k >= 32 for k in a.sr_ks):
@@ -426,7 +433,7 @@ def main(argv=None):
     def load_yaks():
         t_y = time.time()
         if a.sr:  # (under torch.distributed.run every rank counts for itself: the tables are replicated per GPU anyway)
-            ys = np2io.count_kmers(a.sr, a.sr_ks, min_count=a.sr_min_count, device=a.device, qc=a.sr_qc)
+            ys = np2io.count_kmers(a.sr, a.sr_ks, min_count=a.sr_min_count, device=a.device, qc=a.sr_qc, ad=a.sr_adapter)
             _report_sr_qc(a)
             return ys
         with ThreadPoolExecutor(max_workers=max(1, len(a.yak))) as ex:  # (the loader runs outside the GIL: one thread per dump)
@@ -468,7 +475,7 @@ def main(argv=None):
         if prof:
             print(f"[np2 profile] k-mer dumps: start at +{t_b - t0:.3f} s", file=sys.stderr)
         if a.sr:  # reads -> HBM tables that never visit the host (np2_ctx_create_from_reads)
-            pol = np2io.polisher_from_reads(a.sr, a.sr_ks, min_count=a.sr_min_count, device=a.device, qc=a.sr_qc)
+            pol = np2io.polisher_from_reads(a.sr, a.sr_ks, min_count=a.sr_min_count, device=a.device, qc=a.sr_qc, ad=a.sr_adapter)
             _report_sr_qc(a)
         else:
             pol = np2io.polisher_from_yak_files(a.yak, device=a.device)

@@ -20,6 +20,11 @@
 // boundary (np2_srqc_host.hpp), and count_piece runs the filter kernel on the uploaded bases before the count kernels read
 // them: failed reads and trimmed ends are 'N' by then, which ends a k-mer run as a separator does.  Without options
 // nothing of this runs.
+//
+// Adapter trimming (the *_ad entry points with options): the same pieces, the trimming kernel (np2_sradapt.hip) in the filter
+// kernel's place.  In pair mode the files are R1 R2 R1 R2 ..: a reader thread takes a pair of files, reads the two in step
+// (a thread and a bounded queue per file, np2_sradapt_host.hpp) and closes a piece only after an even number of reads; at
+// most 5 pairs are read at a time (15 threads beside the counting thread).
 #include "../../include/np2_io.h"
 #include "np2_ctx.hpp"
 #include "np2_kcount.hpp"
@@ -27,6 +32,7 @@
 #include "np2_kernel_timer.hpp"
 #include "np2_pieces.hpp"
 #include "np2_seqreader.hpp"
+#include "np2_sradapt_host.hpp"
 #include "np2_srqc_host.hpp"
 
 #include <sys/stat.h>
@@ -116,9 +122,12 @@ struct Counter {
     np2h::PinnedBuf pin_ctr;
     np2h::DevEvent ev0, ev1;
     Stats stats;
-    bool qc = false; // the quality filter runs in front of the count kernel
+    bool qc = false; // pieces of both streams: the quality filter, or the adapter trimmer, runs in front of the count kernel
     np2h::SrqcDev qcd;
     uint64_t qc_totals[np2srqc::N_TOTALS] = {0, 0, 0, 0, 0, 0, 0};
+    bool ad = false; // ... the adapter trimmer
+    np2h::AdDev add;
+    uint64_t ad_totals[np2sradapt::N_TOTALS] = {};
 
     ~Counter() {
         if (st && own_stream) {
@@ -144,7 +153,8 @@ struct Counter {
         d_spill[0].ensure(hooks.piece);
         d_ctr.ensure((size_t)np2::KC_N_CTR * tabs.size());
         pin_ctr.ensure(np2::KC_N_CTR * 8);
-        if (qc) qcd.init(st, hooks.piece);
+        if (ad) add.init(st, hooks.piece);
+        else if (qc) qcd.init(st, hooks.piece);
     }
     np2::KcTable kt(const KTable &t) const { return np2::KcTable{t.tab->p, t.cap_log2, lo, hi}; }
     uint64_t *ctr(size_t ki) { return d_ctr.p + ki * np2::KC_N_CTR; }
@@ -170,7 +180,8 @@ struct Counter {
             HIPCHK(hipMemsetAsync(t.tab->p, 0xFF, slots * 8, st));
         }
         HIPCHK(hipMemsetAsync(d_ctr.p, 0, np2::KC_N_CTR * 8 * tabs.size(), st));
-        if (qc) qcd.zero(st); // (every pass filters again: the totals are one pass's)
+        if (ad) add.zero(st); // (every pass filters again: the totals are one pass's)
+        else if (qc) qcd.zero(st);
     }
     // the table of tabs[ki] with twice the capacity (or more, should a sub-table of the new one fill)
     void grow(size_t ki) {
@@ -194,7 +205,8 @@ struct Counter {
     void count_piece(Piece &pc) {
         const size_t n = pc.n;
         HIPCHK(hipMemcpyAsync(d_in.p, pc.buf, np2h::pad_piece(pc.buf, n), hipMemcpyHostToDevice, st));
-        if (qc) qcd.run(st, d_in.p, pc.qc, nullptr);
+        if (ad) add.run(st, d_in.p, pc.qc, nullptr);
+        else if (qc) qcd.run(st, d_in.p, pc.qc, nullptr);
         for (size_t ki = 0; ki < tabs.size(); ++ki) {
             KTable &t = tabs[ki];
             while (t.claimed + n > ((uint64_t)(hi - lo) << t.cap_log2) / 2) grow(ki);
@@ -225,7 +237,8 @@ struct Counter {
     // one pass over the source for the current bucket range
     void stream_source(const Source &src) {
         PieceQueue q;
-        const size_t n_threads = src.mem ? 1 : std::min<size_t>(src.paths.size(), 16);
+        const bool paired = ad && (add.o.flags & np2sradapt::PAIRED);
+        const size_t n_threads = src.mem ? 1 : paired ? std::min<size_t>(src.paths.size() / 2, 5) : std::min<size_t>(src.paths.size(), 16);
         std::vector<Piece> pieces(2 * n_threads);
         np2h::PinnedBlocks pinned;
         for (auto &p : pieces) {
@@ -249,7 +262,10 @@ struct Counter {
                     q.give_full(p);
                 };
                 as.unused = [&](np2h::QcPiece *c) { q.give_idle((Piece *)c->owner); };
-                for (size_t fi = ti; fi < src.paths.size() && !as.dead; fi += n_threads) as.file(src.paths[fi]);
+                if (paired)
+                    for (size_t fi = ti; 2 * fi < src.paths.size() && !as.dead; fi += n_threads) np2h::pair_files(as, src.paths[2 * fi], src.paths[2 * fi + 1]);
+                else
+                    for (size_t fi = ti; fi < src.paths.size() && !as.dead; fi += n_threads) as.file(src.paths[fi]);
                 as.flush();
             } else {
                 PieceWriter w(q, hooks.piece);
@@ -275,7 +291,8 @@ struct Counter {
             q.give_idle(p);
         }
         if (q.err_code != NP2_OK) throw Np2Error(q.err_code, q.err);
-        if (qc) qcd.totals(st, qc_totals);
+        if (ad) add.totals(st, ad_totals);
+        else if (qc) qcd.totals(st, qc_totals);
     }
 
     // the current range of tabs[ki] as sorted file words on the device
@@ -381,10 +398,12 @@ uint32_t min_count_of(const np2_kcount_opts_t *o) {
 }
 
 void setup(Counter &c, int device, const uint32_t *ks, int n_k, const np2_kcount_opts_t *opts, hipStream_t st,
-           const np2srqc::Opts *qc = nullptr) {
+           const np2srqc::Opts *qc = nullptr, const np2sradapt::Opts *ad = nullptr) {
     c.device = device;
-    c.qc = qc != nullptr;
-    if (qc) c.qcd.o = *qc;
+    c.qc = qc != nullptr || ad != nullptr;
+    c.ad = ad != nullptr;
+    if (ad) c.add.o = *ad, c.add.qc = qc ? *qc : np2h::sradapt_qc(nullptr);
+    else if (qc) c.qcd.o = *qc;
     c.min_count = min_count_of(opts);
     c.tabs.resize(n_k);
     for (int i = 0; i < n_k; ++i) c.tabs[i].k = ks[i];
@@ -422,14 +441,23 @@ const np2srqc::Opts *qc_of(const np2_srqc_opts_t *qc, np2srqc::Opts &store) {
     (void)np2h::srqc_piece_bytes();
     return &store;
 }
+// the options of a *_ad call, checked; nullptr without them.  Pair mode takes the paths two by two.
+const np2sradapt::Opts *ad_of(const np2_sradapt_opts_t *ad, int n_paths, np2sradapt::Opts &store) {
+    if (!ad) return nullptr;
+    store = np2h::sradapt_checked(ad);
+    (void)np2h::srqc_piece_bytes();
+    if ((store.flags & np2sradapt::PAIRED) && n_paths % 2) throw Np2Error(NP2_E_ARG, "pair mode takes the files as R1 R2 R1 R2 ..: their number is odd");
+    return &store;
+}
 void publish_qc(const Counter &c) {
-    if (c.qc) np2h::srqc_publish(c.qc_totals, c.qcd.kernel_ms);
+    if (c.ad) np2h::sradapt_publish(c.ad_totals, c.add.kernel_ms);
+    else if (c.qc) np2h::srqc_publish(c.qc_totals, c.qcd.kernel_ms);
 }
 
 int count_to_host(int device, const Source &src, const uint32_t *ks, int n_k, const np2_kcount_opts_t *opts, np2_yak_t *out,
-                  const np2srqc::Opts *qc = nullptr) {
+                  const np2srqc::Opts *qc = nullptr, const np2sradapt::Opts *ad = nullptr) {
     Counter c;
-    setup(c, device, ks, n_k, opts, nullptr, qc);
+    setup(c, device, ks, n_k, opts, nullptr, qc, ad);
     std::vector<HostYak> hy(n_k);
     run_count(c, src, false, [&](const RangeOut &r) { hy[r.ki].take(r, c.st); }, [&] { for (auto &h : hy) h.reset(); });
     std::vector<uint64_t *> offs;
@@ -531,15 +559,22 @@ int np2_kcount_files(int device, const char *const *paths, int n_paths, const ui
 
 int np2_kcount_files_qc(int device, const char *const *paths, int n_paths, const uint32_t *ks, int n_k,
                         const np2_kcount_opts_t *opts, const np2_srqc_opts_t *qc, np2_yak_t *out) {
+    return np2_kcount_files_ad(device, paths, n_paths, ks, n_k, opts, qc, nullptr, out);
+}
+
+int np2_kcount_files_ad(int device, const char *const *paths, int n_paths, const uint32_t *ks, int n_k, const np2_kcount_opts_t *opts,
+                        const np2_srqc_opts_t *qc, const np2_sradapt_opts_t *ad, np2_yak_t *out) {
     return np2h::abi_guard([&] {
         if (!out) throw Np2Error(NP2_E_ARG, "np2_kcount_files: out is NULL");
         check_ks(ks, n_k);
         (void)min_count_of(opts);
         np2srqc::Opts qo;
         const np2srqc::Opts *q = qc_of(qc, qo);
+        np2sradapt::Opts ao;
+        const np2sradapt::Opts *a = ad_of(ad, n_paths, ao);
         Source src;
         check_paths(paths, n_paths, src);
-        return count_to_host(device, src, ks, n_k, opts, out, q);
+        return count_to_host(device, src, ks, n_k, opts, out, q, a);
     }, np2h::io_set_error);
 }
 
@@ -563,18 +598,26 @@ int np2_kcount_files_to_dumps(int device, const char *const *paths, int n_paths,
 
 int np2_kcount_files_to_dumps_qc(int device, const char *const *paths, int n_paths, const uint32_t *ks, int n_k,
                                  const np2_kcount_opts_t *opts, const np2_srqc_opts_t *qc, const char *const *out_paths) {
+    return np2_kcount_files_to_dumps_ad(device, paths, n_paths, ks, n_k, opts, qc, nullptr, out_paths);
+}
+
+int np2_kcount_files_to_dumps_ad(int device, const char *const *paths, int n_paths, const uint32_t *ks, int n_k,
+                                 const np2_kcount_opts_t *opts, const np2_srqc_opts_t *qc, const np2_sradapt_opts_t *ad,
+                                 const char *const *out_paths) {
     return np2h::abi_guard([&] {
         check_ks(ks, n_k);
         (void)min_count_of(opts);
         np2srqc::Opts qo;
         const np2srqc::Opts *q = qc_of(qc, qo);
+        np2sradapt::Opts ao;
+        const np2sradapt::Opts *a = ad_of(ad, n_paths, ao);
         if (!out_paths) throw Np2Error(NP2_E_ARG, "np2_kcount_files_to_dumps: out_paths is NULL");
         for (int i = 0; i < n_k; ++i)
             if (!out_paths[i]) throw Np2Error(NP2_E_ARG, "np2_kcount_files_to_dumps: an output path is NULL");
         Source src;
         check_paths(paths, n_paths, src);
         Counter c;
-        setup(c, device, ks, n_k, opts, nullptr, q);
+        setup(c, device, ks, n_k, opts, nullptr, q, a);
         std::vector<DumpFile> dumps(n_k);
         for (int i = 0; i < n_k; ++i) dumps[i].path = out_paths[i], dumps[i].start(ks[i]);
         std::vector<uint64_t> stage;
@@ -600,6 +643,11 @@ int np2_ctx_create_from_reads(np2_ctx_t **out, int device, const char *const *pa
 
 int np2_ctx_create_from_reads_qc(np2_ctx_t **out, int device, const char *const *paths, int n_paths, const uint32_t *ks, int n_k,
                                  const np2_kcount_opts_t *opts, const np2_srqc_opts_t *qc) {
+    return np2_ctx_create_from_reads_ad(out, device, paths, n_paths, ks, n_k, opts, qc, nullptr);
+}
+
+int np2_ctx_create_from_reads_ad(np2_ctx_t **out, int device, const char *const *paths, int n_paths, const uint32_t *ks, int n_k,
+                                 const np2_kcount_opts_t *opts, const np2_srqc_opts_t *qc, const np2_sradapt_opts_t *ad) {
     if (!out) return np2h::io_set_error(NP2_E_ARG, "np2_ctx_create_from_reads: out is NULL");
     *out = nullptr;
     return np2h::abi_guard([&] {
@@ -607,6 +655,8 @@ int np2_ctx_create_from_reads_qc(np2_ctx_t **out, int device, const char *const 
         (void)min_count_of(opts);
         np2srqc::Opts qo;
         const np2srqc::Opts *q = qc_of(qc, qo);
+        np2sradapt::Opts ao;
+        const np2sradapt::Opts *a = ad_of(ad, n_paths, ao);
         Source src;
         check_paths(paths, n_paths, src);
         std::vector<uint32_t> sk(ks, ks + n_k);
@@ -617,7 +667,7 @@ int np2_ctx_create_from_reads_qc(np2_ctx_t **out, int device, const char *const 
         std::unique_ptr<np2_ctx, void (*)(np2_ctx_t *)> cx(made, np2_ctx_destroy);
         {
             Counter c;
-            setup(c, device, sk.data(), n_k, opts, cx->stream, q);
+            setup(c, device, sk.data(), n_k, opts, cx->stream, q, a);
             run_count(c, src, true, [](const RangeOut &) {}, [] {});
             for (size_t ki = 0; ki < c.tabs.size(); ++ki) {
                 KTable &t = c.tabs[ki];

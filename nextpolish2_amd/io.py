@@ -4,8 +4,8 @@ import os
 
 import numpy as np
 
-from ._types import (READ_DTYPE, SRQC_READ_DTYPE, SRQC_STATS, Pileup, Yak, np2_read_t, np2_srqc_opts_t, np2_srqc_stats_t,
-                     np2_yak_t)
+from ._types import (READ_DTYPE, SRADAPT_READ_DTYPE, SRADAPT_STATS, SRQC_READ_DTYPE, SRQC_STATS, Pileup, Yak, np2_read_t,
+                     np2_sradapt_opts_t, np2_sradapt_stats_t, np2_srqc_opts_t, np2_srqc_stats_t, np2_yak_t)
 from .api import Np2Error, ResidentContig, lib
 
 BAMREC_DTYPE = np.dtype([("pos", "<i4"), ("flag", "<u2"), ("mapq", "u1"), ("pad", "u1"), ("n_cigar", "<u4"),
@@ -19,7 +19,9 @@ IO_SYMBOLS = ["np2_fasta_open", "np2_fasta_next", "np2_fasta_close", "np2_yak_lo
               "np2_seqfile_stream", "np2_bin_files", "np2_seqfile_reads", "np2_depth_from_records", "np2_depth_from_bam",
               "np2_srqc_bytes", "np2_srqc_files", "np2_srqc_last_stats", "np2_srqc_last_kernel_ms", "np2_kcount_files_qc",
               "np2_kcount_files_to_dumps_qc", "np2_ctx_create_from_reads_qc", "np2_seqfile_stream_qual", "np2_sam_open", "np2_sam_close",
-              "np2_sam_n_refs", "np2_sam_ref_name", "np2_sam_stats", "np2_contig_from_sam", "np2_sam_parse_bytes", "np2_sam_export"]
+              "np2_sam_n_refs", "np2_sam_ref_name", "np2_sam_stats", "np2_contig_from_sam", "np2_sam_parse_bytes", "np2_sam_export",
+              "np2_sradapt_bytes", "np2_sradapt_files", "np2_sradapt_last_stats", "np2_sradapt_last_kernel_ms", "np2_kcount_files_ad",
+              "np2_kcount_files_to_dumps_ad", "np2_ctx_create_from_reads_ad"]
 
 
 class np2_front_opts_t(C.Structure):
@@ -136,6 +138,97 @@ def srqc_stats_text(st):
     return ", ".join(f"{k} {st[k]}" for k in SRQC_STATS)
 
 
+class SrAdapt:
+    """Options of the short-read adapter trimmer that runs with the quality filter in front of the k-mer counter
+    (include/np2_io.h has the rule).  pair: the files are R1 R2 R1 R2 .., the mates' overlap is searched (at least `overlap`
+    bases with at most `diff` and at most `diffpct` percent of them different), a read-through adapter is cut off both
+    mates, and a pair is dropped as soon as one mate fails.  seq / seq2: adapter sequences (4 - 64 letters of ACGT) cut
+    off single reads and off the mates of pairs without an overlap; seq2 is mate 2's (default: seq).  The rule is this
+    project's own, built on fastp's documented options; equality with the fastp binary is not claimed.  Out of scope:
+    interleaved FASTQ, read-name checks, fastp's base correction inside the overlap, merging mates, poly-G / poly-X,
+    adapter auto-detection for single-end input."""
+
+    # key of the option text -> (attribute, lowest, highest)
+    KEYS = {"pair": ("pair", 0, 1), "overlap": ("overlap", 1, 1024), "diff": ("diff", 0, 1024), "diffpct": ("diffpct", 0, 100)}
+    SEQ_KEYS = ("seq", "seq2")
+
+    def __init__(self, pair=False, overlap=30, diff=5, diffpct=20, seq=None, seq2=None):
+        given = dict(pair=pair, overlap=overlap, diff=diff, diffpct=diffpct)
+        for key, (attr, lo, hi) in self.KEYS.items():
+            v = int(given[attr])
+            if not lo <= v <= hi:
+                raise ValueError(f"{key} must be in [{lo}, {hi}], not {given[attr]}")
+            setattr(self, attr, bool(v) if attr == "pair" else v)
+        for key, s in (("seq", seq), ("seq2", seq2)):
+            if s is not None and (not isinstance(s, str) or not 4 <= len(s) <= 64 or set(s) - set("ACGT")):
+                raise ValueError(f"{key}={s}: an adapter sequence is 4 to 64 letters of ACGT")
+        if seq2 is not None and seq is None:
+            raise ValueError("seq2 needs seq")
+        if not self.pair and seq is None:
+            raise ValueError("pair=0 trims by sequence: give seq=ADAPTER")
+        self.seq, self.seq2 = seq, seq2
+
+    @classmethod
+    def parse(cls, text):
+        """The option text of the command lines: "" or None is pair=1 with the defaults and no sequences, "key=value,..."
+        sets single keys (pair overlap diff diffpct seq seq2).  ValueError names what is wrong."""
+        kw = {"pair": 1}
+        seen = set()
+        for item in (text or "").split(","):
+            if not item.strip():
+                continue
+            key, eq, val = item.partition("=")
+            key, val = key.strip(), val.strip()
+            if (key not in cls.KEYS and key not in cls.SEQ_KEYS) or not eq:
+                raise ValueError(f"{item.strip()!r}: expected key=value with a key of {' '.join(list(cls.KEYS) + list(cls.SEQ_KEYS))}")
+            if key in seen:
+                raise ValueError(f"{key} is given twice")
+            seen.add(key)
+            if key in cls.SEQ_KEYS:
+                kw[key] = val
+            else:
+                try:
+                    kw[key] = int(val)
+                except ValueError:
+                    raise ValueError(f"{key}={val}: not an integer") from None
+        return cls(**kw)
+
+    def c(self):
+        return np2_sradapt_opts_t(1 if self.pair else 0, self.overlap, self.diff, self.diffpct, None if self.seq is None else self.seq.encode(),
+                                  None if self.seq2 is None else self.seq2.encode())
+
+    def __repr__(self):
+        return (f"SrAdapt(pair={int(self.pair)}, overlap={self.overlap}, diff={self.diff}, diffpct={self.diffpct}, seq={self.seq}, "
+                f"seq2={self.seq2})")
+
+
+def sr_adapter_arg(text):
+    """argparse type of --sr_adapter [SPEC], as sr_qc_arg"""
+    import argparse
+    try:
+        return SrAdapt.parse(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
+def check_sr_adapter(parser, ad, files):
+    """pair mode takes the read files two by two: an odd number is the parser's error, before the library loads"""
+    if ad is not None and ad.pair and len(files) % 2:
+        parser.error(f"--sr_adapter with pair=1 takes the read files as R1 R2 R1 R2 ..: {len(files)} file(s) given")
+
+
+SR_ADAPTER_HELP = ("trim adapters off the reads on the GPU before their k-mers are counted (FASTQ input). Alone: pair=1,overlap=30,"
+                   "diff=5,diffpct=20: the files are R1 R2 R1 R2 .., the mates' overlap is searched, a read-through adapter is cut "
+                   "off both, and a pair is dropped when one mate fails. seq=ACGT..[,seq2=ACGT..] also trims by sequence; "
+                   "pair=0,seq=AGATCGGAAGAGC trims single-end reads. The rule is this project's own, on fastp's documented options; "
+                   "equality with the fastp binary is not claimed. Not done: interleaved FASTQ, read-name checks, base correction "
+                   "in the overlap, merging, poly-G / poly-X, adapter auto-detection")
+
+
+def sradapt_stats_text(st):
+    return ", ".join(f"{k} {st[k]}" for k in SRADAPT_STATS)
+
+
 _BOUND = False
 
 
@@ -228,6 +321,14 @@ def _bind_kcount(L):
     L.np2_srqc_last_stats.argtypes = [qs]
     L.np2_srqc_last_kernel_ms.argtypes = [C.POINTER(C.c_float)]
     L.np2_seqfile_stream_qual.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_uint64)]
+    ao, as_ = C.POINTER(np2_sradapt_opts_t), C.POINTER(np2_sradapt_stats_t)
+    L.np2_kcount_files_ad.argtypes = [C.c_int, cpp, C.c_int, vp, C.c_int, ko, qo, ao, C.POINTER(np2_yak_t)]
+    L.np2_kcount_files_to_dumps_ad.argtypes = [C.c_int, cpp, C.c_int, vp, C.c_int, ko, qo, ao, cpp]
+    L.np2_ctx_create_from_reads_ad.argtypes = [C.POINTER(vp), C.c_int, cpp, C.c_int, vp, C.c_int, ko, qo, ao]
+    L.np2_sradapt_bytes.argtypes = [C.c_int, vp, vp, C.c_uint64, qo, ao, vp, vp, C.c_uint64, as_]
+    L.np2_sradapt_files.argtypes = [C.c_int, cpp, C.c_int, qo, ao, cpp, as_]
+    L.np2_sradapt_last_stats.argtypes = [as_]
+    L.np2_sradapt_last_kernel_ms.argtypes = [C.POINTER(C.c_float)]
 
 
 def _io_check(rc):
@@ -360,25 +461,31 @@ def _qc(qc):
     return None if qc is None else C.byref(qc.c())
 
 
-def count_kmers(inputs, ks, min_count=1, device=0, mem_bytes=0, qc=None):
+def _ad(ad):
+    return None if ad is None else C.byref(ad.c())
+
+
+def count_kmers(inputs, ks, min_count=1, device=0, mem_bytes=0, qc=None, ad=None):
     """Canonical k-mers of short reads counted on the device -> one Yak per k (np2_kcount_files / np2_kcount_bytes).
     `inputs`: sequence file paths (FASTA / FASTQ / one sequence per line, plain or gzip), or ONE bytes object holding a
     separator stream (the reads' bytes with a newline, or any non-base byte, between reads).  Words with a count below
     `min_count` are left out (an exact threshold); counts saturate at 1023.  `qc` (an SrQc; files only, FASTQ): the reads
-    are quality-trimmed and filtered on the device before they are counted; srqc_last_stats() has the totals."""
+    are quality-trimmed and filtered on the device before they are counted; srqc_last_stats() has the totals.  `ad` (an
+    SrAdapt; files only, FASTQ; with pair=True the files are R1 R2 R1 R2 ..): adapters are trimmed as well, and
+    sradapt_last_stats() has the totals instead."""
     import weakref
     L = _bind()
     kk = _ks(ks)
     o = np2_kcount_opts_t(min_count, mem_bytes)
     out = (np2_yak_t * max(1, len(kk)))()
     if isinstance(inputs, (bytes, bytearray, memoryview)):
-        if qc is not None:
-            raise ValueError("qc needs FASTQ files: a separator stream has no qualities")
+        if qc is not None or ad is not None:
+            raise ValueError("qc and ad need FASTQ files: a separator stream has no qualities")
         buf = np.frombuffer(inputs, dtype=np.uint8)
         _io_check(L.np2_kcount_bytes(device, buf.ctypes.data if len(buf) else None, len(buf), kk.ctypes.data, len(kk), C.byref(o), out))
     else:
         arr, n = _paths(inputs)
-        _io_check(L.np2_kcount_files_qc(device, arr, n, kk.ctypes.data, len(kk), C.byref(o), _qc(qc), out))
+        _io_check(L.np2_kcount_files_ad(device, arr, n, kk.ctypes.data, len(kk), C.byref(o), _qc(qc), _ad(ad), out))
     yaks = []
     for i in range(len(kk)):
         y = np2_yak_t.from_buffer_copy(out[i])
@@ -390,8 +497,8 @@ def count_kmers(inputs, ks, min_count=1, device=0, mem_bytes=0, qc=None):
     return yaks
 
 
-def count_kmers_to_files(paths, ks, out_paths, min_count=1, device=0, mem_bytes=0, qc=None):
-    """np2_kcount_files_to_dumps: sequence files -> one yak v2 dump per k, written bucket by bucket (qc: as count_kmers)."""
+def count_kmers_to_files(paths, ks, out_paths, min_count=1, device=0, mem_bytes=0, qc=None, ad=None):
+    """np2_kcount_files_to_dumps: sequence files -> one yak v2 dump per k, written bucket by bucket (qc, ad: as count_kmers)."""
     L = _bind()
     kk = _ks(ks)
     if len(out_paths) != len(kk):
@@ -399,19 +506,19 @@ def count_kmers_to_files(paths, ks, out_paths, min_count=1, device=0, mem_bytes=
     arr, n = _paths(paths)
     outs, _ = _paths(out_paths)
     o = np2_kcount_opts_t(min_count, mem_bytes)
-    _io_check(L.np2_kcount_files_to_dumps_qc(device, arr, n, kk.ctypes.data, len(kk), C.byref(o), _qc(qc), outs))
+    _io_check(L.np2_kcount_files_to_dumps_ad(device, arr, n, kk.ctypes.data, len(kk), C.byref(o), _qc(qc), _ad(ad), outs))
 
 
-def polisher_from_reads(paths, ks, min_count=1, device=0, mem_bytes=0, qc=None):
+def polisher_from_reads(paths, ks, min_count=1, device=0, mem_bytes=0, qc=None, ad=None):
     """np2_ctx_create_from_reads: a Polisher whose HBM k-mer tables are counted from the reads and never visit the host
-    (tables ordered by k, option.rs:238).  Single-pass runs only.  qc: as count_kmers."""
+    (tables ordered by k, option.rs:238).  Single-pass runs only.  qc, ad: as count_kmers."""
     from .api import Polisher
     L = _bind()
     kk = _ks(ks)
     arr, n = _paths(paths)
     o = np2_kcount_opts_t(min_count, mem_bytes)
     h = C.c_void_p()
-    _io_check(L.np2_ctx_create_from_reads_qc(C.byref(h), device, arr, n, kk.ctypes.data, len(kk), C.byref(o), _qc(qc)))
+    _io_check(L.np2_ctx_create_from_reads_ad(C.byref(h), device, arr, n, kk.ctypes.data, len(kk), C.byref(o), _qc(qc), _ad(ad)))
     p = Polisher.__new__(Polisher)
     p._yaks = []
     p._h = h
@@ -503,6 +610,53 @@ def srqc_files(paths, qc=None, out_paths=None, device=0):
     o = (qc or SrQc()).c()
     _io_check(L.np2_srqc_files(device, arr, n, C.byref(o), outs, st))
     return [_stats_dict(x) for x in st]
+
+
+def _ad_stats_dict(st):
+    return dict(zip(SRADAPT_STATS, (int(getattr(st, f)) for f, _ in np2_sradapt_stats_t._fields_)))
+
+
+def sradapt_last_stats():
+    """np2_sradapt_last_stats: the totals of the last adapter-trimming call on this thread plus kernel_ms"""
+    L = _bind()
+    st, ms = np2_sradapt_stats_t(), C.c_float()
+    L.np2_sradapt_last_stats(C.byref(st))
+    L.np2_sradapt_last_kernel_ms(C.byref(ms))
+    return dict(_ad_stats_dict(st), kernel_ms=ms.value)
+
+
+def sradapt_bytes(seq, qual, qc=None, ad=None, device=0, want_masked=True, want_reads=True):
+    """np2_sradapt_bytes: srqc_bytes with the adapter rule (ad: an SrAdapt, None: pair mode with the defaults; qc None: every
+    quality step off).  In pair mode reads 2r and 2r + 1 are mates.  -> (masked stream or None, per-read array of (begin,
+    end, cls, how, insert) or None, totals dict)."""
+    L = _bind()
+    s, q = np.frombuffer(seq, dtype=np.uint8), np.frombuffer(qual, dtype=np.uint8)
+    if len(s) != len(q):
+        raise ValueError("the two streams differ in length")
+    n_reads = int((s == 10).sum())
+    masked = np.empty(max(1, len(s)), np.uint8) if want_masked else None
+    reads = np.zeros(max(1, n_reads), SRADAPT_READ_DTYPE) if want_reads else None
+    st = np2_sradapt_stats_t()
+    _io_check(L.np2_sradapt_bytes(device, s.ctypes.data if len(s) else None, q.ctypes.data if len(s) else None, len(s), _qc(qc), _ad(ad),
+                                  masked.ctypes.data if want_masked else None, reads.ctypes.data if want_reads else None, n_reads, C.byref(st)))
+    return (masked[:len(s)].tobytes() if want_masked else None), (reads[:n_reads] if want_reads else None), _ad_stats_dict(st)
+
+
+def sradapt_files(paths, qc=None, ad=None, out_paths=None, device=0):
+    """np2_sradapt_files: FASTQ files through quality filter and adapter trimmer -> [totals dict per unit] + [their sum]; a
+    unit is a file, or in pair mode (the files R1 R2 R1 R2 ..) a pair of files.  out_paths (one per input): the cleaned
+    plain-text FASTQ files; of a pair only what passes in both mates is written."""
+    L = _bind()
+    arr, n = _paths(paths)
+    outs = None
+    if out_paths is not None:
+        if len(out_paths) != n:
+            raise ValueError("one output path per input")
+        outs = (C.c_char_p * n)(*[None if p is None else os.fspath(p).encode() for p in out_paths])
+    st = (np2_sradapt_stats_t * (n + 1))()
+    _io_check(L.np2_sradapt_files(device, arr, n, _qc(qc), _ad(ad), outs, st))
+    units = n // 2 if (ad is None or ad.pair) else n
+    return [_ad_stats_dict(x) for x in st[:units + 1]]
 
 
 def seqfile_stream_qual(path):

@@ -1,7 +1,7 @@
 """python -m nextpolish2_amd.srqc: quality-trim and filter short reads on the GPU (the preparation step the reference's
 README asks for before `yak count`; its recipe is fastp -5 -3 -n 0 -f 5 -F 5 -t 5 -T 5 -q 20).
 
-    python -m nextpolish2_amd.srqc reads.fq.gz ... [--sr_qc SPEC] [--report qc.tsv] [--out_fq PREFIX]
+    python -m nextpolish2_amd.srqc reads.fq.gz ... [--sr_qc SPEC] [--sr_adapter [SPEC]] [--report qc.tsv] [--out_fq PREFIX]
 
 The rule is this project's own, built on the options of that recipe; it is not pinned against the fastp binary.  One read
 has n bases and n quality bytes, p[i] = max(0, byte - 33):
@@ -17,13 +17,23 @@ complexity and no average-quality filter.  Inputs are FASTQ, plain or gzip.
 --report writes a TSV, one line per file and a total: reads, pass, too_short, too_many_n, low_quality, bases_in, bases_out
 (standard output without it).  --out_fq PREFIX writes the passing reads of input i, trimmed, to PREFIX.<i>.fq.  Existing
 files are not overwritten.  The k-mer counter takes the same option (nextpolish2_amd.count --sr_qc, nextPolish2 --sr ..
---sr_qc) and filters on the way, without the files."""
+--sr_qc) and filters on the way, without the files.
+
+--sr_adapter [SPEC] adds adapter trimming (include/np2_io.h has the rule; it is this project's own, on fastp's documented
+options, and equality with the fastp binary is not claimed).  Alone it is pair=1,overlap=30,diff=5,diffpct=20: the files are
+R1 R2 R1 R2 .. and are read in step, the mates' overlap is searched and a read-through adapter cut off both, a pair is
+dropped as soon as one mate fails (class mate_failed), and --out_fq writes only pairs that pass in both mates, so the
+outputs stay in step.  seq=ACGT..[,seq2=ACGT..] trims by sequence where no overlap was found; pair=0,seq=.. trims
+single-end reads.  The report then has one line per pair of files (named R1,R2) and the columns mate_failed, pairs,
+pairs_overlap, pairs_unsearched, trimmed_overlap, trimmed_seq, adapter_bases as well.  Not done: interleaved FASTQ,
+read-name checks, fastp's base correction inside the overlap, merging mates, poly-G / poly-X, adapter auto-detection for
+single-end input."""
 import argparse
 import os
 import sys
 
 from . import io as np2io
-from ._types import SRQC_STATS
+from ._types import SRADAPT_STATS, SRQC_STATS
 from .api import Np2Error
 
 
@@ -32,22 +42,24 @@ def build_parser():
                                 epilog=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument("reads", nargs="+", metavar="reads.fq[.gz]", help="FASTQ files, plain or gzip")
     p.add_argument("--sr_qc", nargs="?", const=np2io.SrQc(), default=np2io.SrQc(), type=np2io.sr_qc_arg, metavar="SPEC", help=np2io.SR_QC_HELP)
+    p.add_argument("--sr_adapter", nargs="?", const="", default=None, type=np2io.sr_adapter_arg, metavar="SPEC", help=np2io.SR_ADAPTER_HELP)
     p.add_argument("--report", default=None, metavar="FILE", help="the totals as a TSV [stdout]")
     p.add_argument("--out_fq", default=None, metavar="PREFIX", help="write the cleaned reads of input i to PREFIX.<i>.fq")
     p.add_argument("--device", type=int, default=0)
     return p
 
 
-def report_text(paths, stats):
-    rows = ["\t".join(("file",) + SRQC_STATS)]
+def report_text(paths, stats, names=SRQC_STATS):
+    rows = ["\t".join(("file",) + names)]
     for name, st in zip(list(paths) + ["total"], stats):
-        rows.append("\t".join([name] + [str(st[k]) for k in SRQC_STATS]))
+        rows.append("\t".join([name] + [str(st[k]) for k in names]))
     return "\n".join(rows) + "\n"
 
 
 def parse_args(argv=None):
     p = build_parser()
     a = p.parse_args(argv)
+    np2io.check_sr_adapter(p, a.sr_adapter, a.reads)
     for r in a.reads:
         if not os.path.exists(r):
             p.error(f"cannot open {r}")
@@ -61,16 +73,23 @@ def parse_args(argv=None):
 def main(argv=None):
     a = parse_args(argv)
     try:
-        stats = np2io.srqc_files(a.reads, a.sr_qc, a.out_paths, device=a.device)
+        if a.sr_adapter is not None:
+            stats = np2io.sradapt_files(a.reads, a.sr_qc, a.sr_adapter, a.out_paths, device=a.device)
+        else:
+            stats = np2io.srqc_files(a.reads, a.sr_qc, a.out_paths, device=a.device)
     except Np2Error as e:
         raise SystemExit(f"Error: {e}")
-    text = report_text(a.reads, stats)
+    if a.sr_adapter is not None:
+        units = [",".join(a.reads[i:i + 2]) for i in range(0, len(a.reads), 2)] if a.sr_adapter.pair else a.reads
+        text = report_text(units, stats, SRADAPT_STATS)
+    else:
+        text = report_text(a.reads, stats)
     if a.report:
         with open(a.report, "w") as f:
             f.write(text)
     else:
         sys.stdout.write(text)
-    print(f"[np2 srqc] {np2io.srqc_stats_text(stats[-1])}", file=sys.stderr)
+    print(f"[np2 srqc] {(np2io.sradapt_stats_text if a.sr_adapter is not None else np2io.srqc_stats_text)(stats[-1])}", file=sys.stderr)
     return 0
 
 
