@@ -415,6 +415,12 @@ void np2_trim_device_cache(void);
  * operations (0 insert, 1 remove, 2 entry().or_insert) — pinned by hand-traced vectors in tests/test_swiss_vectors.py. */
 int np2_swiss_order(const uint32_t *ops, const uint32_t *keys, uint32_t n, uint32_t *out, uint32_t *n_out);
 
+/* Test hook, process-wide.  byte in 0..255: every block the device pools and the pinned pool hand out from now on is
+ * filled with that byte first (the whole block, slack included).  byte < 0: off (the default).  Returns the old setting. */
+int np2_debug_poison(int byte);
+/* bytes filled since the process started: device blocks, pinned blocks (either may be NULL) */
+void np2_debug_poison_stats(uint64_t *device_bytes, uint64_t *pinned_bytes);
+
 /* Per-stage device timings of the last np2_polish_resident (HIP events on the ctx stream).
  * names: NUL-separated list terminated by an empty string; ms[i] matches names[i].
  * By default only the dense pass ("diff_reads") is timed; np2_ctx_set_timing(ctx, 1) arms every stage timer

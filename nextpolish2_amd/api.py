@@ -3,6 +3,7 @@
 There is no CPU fallback: importing is fine without a GPU (symbols can be inspected), but
 creating a Polisher requires the in-tree HIP library and a visible MI355X device.
 """
+import contextlib
 import ctypes as C
 import os
 import weakref
@@ -25,7 +26,7 @@ ABI_SYMBOLS = [
     "np2_batch_last_error", "np2_batch_polish", "np2_batch_flush_log", "np2_shard_plan", "np2_shard_upload",
     "np2_shard_begin", "np2_shard_passes_left", "np2_shard_vote", "np2_vote_decide", "np2_shard_apply", "np2_shard_final",
     "np2_shard_final_device", "np2_shard_fetch", "np2_alloc_pinned", "np2_trim_device_cache",
-    "np2_shard_end", "np2_swiss_order", "np2_batch_set_timing", "np2_batch_set_priority", "np2_batch_last_diff_ms", "np2_batch_stats", "np2_batch_last_call_ms",
+    "np2_shard_end", "np2_swiss_order", "np2_debug_poison", "np2_debug_poison_stats", "np2_batch_set_timing", "np2_batch_set_priority", "np2_batch_last_diff_ms", "np2_batch_stats", "np2_batch_last_call_ms",
     "np2_qv_strings", "np2_qv_device", "np2_trio_strings", "np2_trio_device", "np2_bin_stream",
     "np2_cmp_strings",
     "np2_edits_buffers", "np2_edits_last", "np2_edits_free",
@@ -204,6 +205,10 @@ def _lib_locked():
         L.np2_shard_end.argtypes = [vp]
         L.np2_shard_end.restype = None
         L.np2_swiss_order.argtypes = [vp, vp, u32, vp, C.POINTER(u32)]
+        L.np2_debug_poison.argtypes = [C.c_int]
+        L.np2_debug_poison.restype = C.c_int
+        L.np2_debug_poison_stats.argtypes = [C.POINTER(u64), C.POINTER(u64)]
+        L.np2_debug_poison_stats.restype = None
         L.np2_batch_stats.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
         L.np2_io_last_error.restype = C.c_char_p
         L.np2_rep_bytes.argtypes = [C.c_int, vp, u64, C.POINTER(np2_rep_opts_t), C.POINTER(vp), C.POINTER(vp), C.POINTER(u64),
@@ -1041,6 +1046,25 @@ def swiss_order(script):
     if lib().np2_swiss_order(ops.ctypes.data, keys.ctypes.data, len(script), out.ctypes.data, C.byref(n)) != 0:
         raise Np2Error(-1, "np2_swiss_order")
     return out[: n.value].tolist()
+
+
+@contextlib.contextmanager
+def alloc_poison(byte):
+    """np2_debug_poison for the length of a with block (a test hook): every block the device pools and the pinned pool
+    hand out inside it is filled with `byte` (0..255) first; None switches the fill off.  The old setting comes back on
+    exit.  A context keeps its buffers, so make it inside the block."""
+    old = lib().np2_debug_poison(-1 if byte is None else int(byte) & 255)
+    try:
+        yield
+    finally:
+        lib().np2_debug_poison(old)
+
+
+def alloc_poison_stats():
+    """(device bytes, pinned bytes) the poison hook has filled since the process started."""
+    d, p = C.c_uint64(), C.c_uint64()
+    lib().np2_debug_poison_stats(C.byref(d), C.byref(p))
+    return d.value, p.value
 
 
 def phase_vote(keys, pairs, ref=None):

@@ -7,6 +7,7 @@
 #include "np2_hostcpu.hpp"
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -55,6 +56,32 @@ struct SlowCall {
     }
 };
 
+// np2_debug_poison (a test hook): the byte every block the pools below hand out is filled with first, or < 0 for none.
+// No pool clears a block, so a kernel may assume nothing about memory it did not write in this call; the fill makes a
+// reader of unwritten memory show on every run instead of on the run that happens to get a recycled block.
+struct Poison {
+    std::atomic<int> byte{-1};
+    std::atomic<uint64_t> device_bytes{0}, pinned_bytes{0};
+};
+inline Poison &poison() {
+    static Poison *p = new Poison();
+    return *p;
+}
+// the block is idle (the pools' contract) and no pool lock is held
+inline void poison_device(void *p, size_t bytes) {
+    const int b = poison().byte.load(std::memory_order_relaxed);
+    if (b < 0 || !p) return;
+    HIPCHK(hipMemset(p, b, bytes));
+    HIPCHK(hipDeviceSynchronize());
+    poison().device_bytes.fetch_add(bytes, std::memory_order_relaxed);
+}
+inline void poison_pinned(void *p, size_t bytes) {
+    const int b = poison().byte.load(std::memory_order_relaxed);
+    if (b < 0 || !p) return;
+    memset(p, b, bytes);
+    poison().pinned_bytes.fetch_add(bytes, std::memory_order_relaxed);
+}
+
 // Device blocks of short-lived objects — the resident pileup of a contig, the front end's staging buffers — are cached
 // per device by size class instead of going back to the driver: hipMalloc / hipFree cost 0.1 - 1 ms each, hipFree
 // synchronises the device, and a contig of a many-contig assembly brings a dozen of each.  Only for memory whose owner
@@ -84,22 +111,24 @@ struct DevCache {
         int dev = 0;
         (void)hipGetDevice(&dev);
         bytes = size_class(bytes);
+        void *p = nullptr;
         {
             std::lock_guard<std::mutex> l(mu);
             auto it = free_.find({dev, bytes});
             if (it != free_.end() && !it->second.empty()) {
-                void *p = it->second.back();
+                p = it->second.back();
                 it->second.pop_back();
                 cached -= bytes;
-                return p;
             }
         }
-        void *p = nullptr;
-        SlowCall sc("hipMalloc (block)", bytes);
-        if (hipMalloc(&p, bytes) != hipSuccess) {
-            trim(0); // (the idle blocks may be what is missing)
-            HIPCHK(hipMalloc(&p, bytes));
+        if (!p) {
+            SlowCall sc("hipMalloc (block)", bytes);
+            if (hipMalloc(&p, bytes) != hipSuccess) {
+                trim(0); // (the idle blocks may be what is missing)
+                HIPCHK(hipMalloc(&p, bytes));
+            }
         }
+        poison_device(p, bytes);
         return p;
     }
     void put(void *p, size_t bytes) {
@@ -161,6 +190,11 @@ struct DevSlabs {
         int dev = 0;
         (void)hipGetDevice(&dev);
         bytes = (std::max<size_t>(bytes, 256) <= 4096) ? ((bytes + 255) & ~(size_t)255) : round(bytes);
+        void *p = carve(dev, bytes);
+        poison_device(p, bytes);
+        return p;
+    }
+    void *carve(int dev, size_t bytes) { // (bytes rounded by get)
         std::lock_guard<std::mutex> l(mu);
         auto it = free_.find({dev, bytes});
         if (it != free_.end() && !it->second.empty()) {
@@ -289,6 +323,12 @@ struct PinnedPool {
     std::map<void *, size_t> live;                 // handed out
     std::vector<std::pair<size_t, void *>> free_;  // (capacity, ptr)
     void *get(size_t bytes) {
+        size_t cap = 0;
+        void *p = take(bytes, cap);
+        poison_pinned(p, cap);
+        return p;
+    }
+    void *take(size_t bytes, size_t &cap) {
         std::lock_guard<std::mutex> l(mu);
         size_t best = free_.size();
         for (size_t i = 0; i < free_.size(); ++i)
@@ -296,7 +336,7 @@ struct PinnedPool {
                 (best == free_.size() || free_[i].first < free_[best].first))
                 best = i;
         void *p = nullptr;
-        size_t cap = 0;
+        cap = 0;
         if (best != free_.size()) {
             p = free_[best].second;
             cap = free_[best].first;

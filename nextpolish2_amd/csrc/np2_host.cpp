@@ -2520,6 +2520,13 @@ int np2_shard_final(np2_shard_run_t *h, uint8_t **out_bases, uint32_t **out_pos,
 void *np2_alloc_pinned(uint64_t bytes) { return pinned_pool().get((size_t)bytes + 1); }
 void np2_trim_device_cache(void) { dev_cache().trim(0); }
 
+// test hook: the pools fill every block they hand out with this byte (np2_ctx.hpp: poison_device, poison_pinned)
+int np2_debug_poison(int byte) { return poison().byte.exchange(byte < 0 ? -1 : (byte & 255), std::memory_order_relaxed); }
+void np2_debug_poison_stats(uint64_t *device_bytes, uint64_t *pinned_bytes) {
+    if (device_bytes) *device_bytes = poison().device_bytes.load(std::memory_order_relaxed);
+    if (pinned_bytes) *pinned_bytes = poison().pinned_bytes.load(std::memory_order_relaxed);
+}
+
 int np2_shard_final_device(np2_shard_run_t *h, np2_shard_piece_t *out) {
     ShardRun *sr = (ShardRun *)h;
     if (!sr || !out || !sr->run.final_pass()) return NP2_E_ARG;

@@ -95,6 +95,7 @@ struct Run {
             throw Np2Error(NP2_E_NOMEM, "the counter table for k = " + std::to_string(o.k) + " (" + std::to_string(table_n * 4) +
                                             " bytes) could not be allocated on the device");
         }
+        np2h::poison_device(table, table_n * 4); // (a block of its own, not a pool's: the test hook sees it all the same)
         HIPCHK(hipMemsetAsync(table, 0, table_n * 4, st));
         d_in.cached = true; // (released after ~Run has drained the stream)
         d_in.ensure(HALO + hooks.piece + 64);

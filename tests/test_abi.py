@@ -210,3 +210,27 @@ def test_bam_open_reports_damaged_bgzf_headers(tmp_path):
         with pytest.raises(api.Np2Error) as e:
             io.Bam(str(path))
         assert e.value.code == E_ARG and msg in str(e.value), (name, str(e.value))
+
+
+def test_poison_hook_round_trips_its_setting_without_a_device():
+    """np2_debug_poison returns the old setting (off by default, any byte 0..255, off again) and touches no device; in a
+    process that has allocated nothing np2_debug_poison_stats reads 0, with either pointer NULL too.  (A child process:
+    the counters are process-wide and this one may have polished under poison already.)"""
+    import subprocess
+    import sys
+    code = ("import ctypes as C, sys; sys.path.insert(0, %r)\n"
+            "from nextpolish2_amd import api\n"
+            "L = api.lib()\n"
+            "assert api.alloc_poison_stats() == (0, 0)\n"
+            "assert L.np2_debug_poison(0xA5) == -1 and L.np2_debug_poison(0) == 0xA5 and L.np2_debug_poison(255) == 0\n"
+            "assert L.np2_debug_poison(-7) == 255 and L.np2_debug_poison(-1) == -1\n"
+            "with api.alloc_poison(0xFF):\n"
+            "    with api.alloc_poison(None):\n"
+            "        assert L.np2_debug_poison(-1) == -1\n"
+            "    assert L.np2_debug_poison(0xFF) == 0xFF\n"  # (the inner block put back what it found)
+            "assert L.np2_debug_poison(-1) == -1\n"
+            "d = C.c_uint64(7); L.np2_debug_poison_stats(C.byref(d), None); assert d.value == 0\n"
+            "p = C.c_uint64(7); L.np2_debug_poison_stats(None, C.byref(p)); assert p.value == 0\n"
+            "print('ok')\n" % ROOT)
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.strip() == "ok", r.stderr[-3000:]

@@ -27,10 +27,11 @@ def oracle_traced(pu, yaks, opts):
     return o, ob, op
 
 
-def check_all_stages(pu, yaks, opts, ref=None):
+def check_all_stages(pu, yaks, opts, ref=None, g=None):
     # ref: oracle_traced(pu, yaks, opts) of an earlier call, to compare several device runs with one oracle run
+    # g: an existing polisher (made with these yaks) to run on instead of a new one
     o, ob, op = ref or oracle_traced(pu, yaks, opts)
-    g = Polisher(yaks)
+    g = g or Polisher(yaks)
     g.set_trace(True)
     gb, gp = g.polish(pu, opts)
     for ps in range(opts.iter_count):
