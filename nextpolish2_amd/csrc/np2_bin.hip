@@ -3,13 +3,13 @@
 // ('p', 'm', 'a', '0': np2_bin_core.hpp).  Read-only on the tables (YakDev).  What np2_trio.hip measures per contig, for a
 // read set: no read is aligned to a tile, a tile or a lane's stretch may hold any number of reads.
 //
-// Input: the counter's separator stream, HALO + QV_TILE bytes per turn through LDS with aligned 16-byte loads; a lane owns
+// Input: the counter's separator stream through stage_aligned (the staging contract of np2_kmerscan.hpp); a lane owns
 // the k-mers that END in its 32 bytes.  A '\n' resets the k-mer run (np2kc::push), so no k-mer spans two reads; the
 // separators below n_bytes are the read boundaries (their offsets, `ends`, give every tile the read that owns its first
 // byte: k_bin_owner).
 //
-// Probes: k_trio_scan's (np2_trio_probe.hpp): sixteen first-slot loads of both tables before a word is looked at, the
-// collision rounds together, the whole-cluster lookup for tables that repeat keys, every loop bounded by the capacity.
+// Probes: k_trio_scan's (the probe contract of np2_kmerscan.hpp): sixteen first-slot loads of both tables before a word is
+// looked at, the collision rounds together, the whole-cluster lookup for tables that repeat keys.
 //
 // Order and counters, level by level (np2_bin_core.hpp):
 //   lane   walks its 32 bytes; at a boundary it closes the open tally and starts a fresh Run.  What is left: `head` (the
@@ -29,16 +29,19 @@
 
 #include "np2_bin.hpp"
 #include "np2_blockscan.hpp"
-#include "np2_trio_probe.hpp"
+#include "np2_kmerscan.hpp"
+#include "np2_trio.hpp"
 
 namespace np2 {
+using namespace np2kc;
+using namespace np2qv;
+using namespace np2trio;
 using namespace np2bin;
 
 namespace {
 
 static constexpr uint32_t BIN_CHUNKS = (HALO + QV_TILE) / 16; // 16-byte pieces of a tile's window (the source is aligned)
 static constexpr uint32_t BIN_WAVES = QV_BLOCK / 64;
-static constexpr uint32_t PAD4 = 0x0A0A0A0Au;
 
 // one read's counters, lane by lane: zeros cost nothing
 __device__ __forceinline__ void bin_add(uint32_t *tallies, uint32_t read, const Tally &t) {
@@ -52,23 +55,10 @@ __device__ __forceinline__ void bin_add(uint32_t *tallies, uint32_t read, const 
     if (t.mm) atomicAdd(c + 6, t.mm);
 }
 
-// the block's counters of one read (lanes with `mine` contribute): wavefront sums, LDS, one atomic per non-zero counter
+// the block's counters of one read (lanes with `mine` contribute)
 __device__ __forceinline__ void bin_flush(bool mine, const Tally &t, uint32_t *s_cnt, uint32_t *tallies, uint32_t read) {
-    uint32_t v[BIN_STATS] = {t.n_kmers, t.n_pat, t.n_mat, t.pp, t.pm, t.mp, t.mm};
-#pragma unroll
-    for (uint32_t i = 0; i < BIN_STATS; ++i) v[i] = mine ? v[i] : 0u;
-#pragma unroll
-    for (uint32_t i = 0; i < BIN_STATS; ++i) {
-        for (int o = 32; o > 0; o >>= 1) v[i] += (uint32_t)__shfl_down((int)v[i], o);
-        if ((threadIdx.x & 63u) == 0 && v[i]) atomicAdd(&s_cnt[i], v[i]);
-    }
-    __syncthreads();
-    if (threadIdx.x < BIN_STATS) {
-        const uint32_t c = s_cnt[threadIdx.x];
-        if (c) atomicAdd(&tallies[BIN_STATS * (uint64_t)read + threadIdx.x], c);
-        s_cnt[threadIdx.x] = 0;
-    }
-    __syncthreads();
+    const uint32_t v[BIN_STATS] = {t.n_kmers, t.n_pat, t.n_mat, t.pp, t.pm, t.mp, t.mm};
+    block_flush<BIN_STATS>(mine, v, s_cnt, tallies + BIN_STATS * (uint64_t)read);
 }
 
 } // namespace
@@ -99,7 +89,6 @@ __global__ __launch_bounds__(QV_BLOCK) void k_bin_scan(YakDev yp, YakDev ym, Bin
 
     const uint32_t k = yp.k; // (== ym.k: the host driver refuses anything else)
     const uint64_t mask = kmer_mask(k);
-    const uint64_t capm_p = (1ULL << yp.cap_log2) - 1, capm_m = (1ULL << ym.cap_log2) - 1;
     const uint32_t *lds = reinterpret_cast<const uint32_t *>(tile) + tid * (QV_STRETCH / 4);
     const bool whole_cluster = yp.ord || ym.ord; // a table that repeats keys (yak writes none)
     const int64_t hi = (int64_t)q.n_bytes;
@@ -107,21 +96,7 @@ __global__ __launch_bounds__(QV_BLOCK) void k_bin_scan(YakDev yp, YakDev ym, Bin
     for (uint32_t t = blockIdx.x; t < q.n_tiles; t += gridDim.x) {
         const uint32_t r0 = q.owner[t];
         const int64_t t0 = (int64_t)t * QV_TILE;
-        const int64_t w0 = t0 - (int64_t)HALO;
-        for (uint32_t i = tid; i < BIN_CHUNKS; i += QV_BLOCK) {
-            const int64_t c0 = w0 + 16 * (int64_t)i;
-            uint32_t w[4] = {PAD4, PAD4, PAD4, PAD4};
-            if (c0 < hi) { // (c0 >= -HALO: the halo is always there)
-                const uint4 v = *reinterpret_cast<const uint4 *>(q.src + c0);
-                w[0] = v.x, w[1] = v.y, w[2] = v.z, w[3] = v.w;
-                if (c0 + 16 > hi) { // the piece's last load: what lies behind it is a separator
-#pragma unroll
-                    for (uint32_t b = 0; b < 16; ++b)
-                        if (c0 + (int64_t)b >= hi) w[b >> 2] = (w[b >> 2] & ~(0xFFu << (8 * (b & 3)))) | ((uint32_t)QV_PAD << (8 * (b & 3)));
-                }
-            }
-            tile[i] = make_uint4(w[0], w[1], w[2], w[3]);
-        }
+        stage_aligned<QV_BLOCK, BIN_CHUNKS>(tile, q.src, t0 - (int64_t)HALO, hi); // (the halo is always there)
         __syncthreads();
 
         // the boundaries of this lane's stretch: separators below n_bytes (the padding behind the piece is none)
@@ -140,13 +115,7 @@ __global__ __launch_bounds__(QV_BLOCK) void k_bin_scan(YakDev yp, YakDev ym, Bin
         const uint32_t head_read = min(r0 + bounds_before, q.n_ends); // (never clamped when `ends` are the stream's separators)
 
         Roll r;
-        uint64_t hh = 0;
-#pragma unroll 1
-        for (uint32_t i = 0; i < HALO / 4; ++i) {
-            const uint32_t w = lds[i];
-#pragma unroll
-            for (uint32_t j = 0; j < 4; ++j) (void)push(r, (uint8_t)(w >> (8 * j)), k, mask, &hh);
-        }
+        warm_halo(r, [&](uint32_t i) { return lds[i]; }, k, mask);
         Stretch st;
         Tally tally;
         Run run;
@@ -156,30 +125,21 @@ __global__ __launch_bounds__(QV_BLOCK) void k_bin_scan(YakDev yp, YakDev ym, Bin
             const uint32_t wa = lds[HALO / 4 + 2 * g], wb = lds[HALO / 4 + 2 * g + 1];
             uint64_t h[QV_GROUP];
             uint32_t cp[QV_GROUP], cm[QV_GROUP];
-            uint32_t valid = 0;
-#pragma unroll
-            for (uint32_t j = 0; j < QV_GROUP; ++j) {
-                h[j] = 0; // (a base no k-mer ends at probes slot 0 of sub-table 0: a valid address, its word is ignored)
-                const bool ok = push(r, (uint8_t)((j < 4 ? wa : wb) >> (8 * (j & 3))), k, mask, &h[j]);
-                if (!ok) h[j] = 0;
-                valid |= (ok ? 1u : 0u) << j;
-            }
+            const uint32_t valid = hash_group(r, wa, wb, k, mask, h);
             if (whole_cluster) {
 #pragma unroll
                 for (uint32_t j = 0; j < QV_GROUP; ++j) {
                     cp[j] = cm[j] = 0;
-                    if ((valid >> j) & 1u) cp[j] = trio_get_bounded(yp, h[j]), cm[j] = trio_get_bounded(ym, h[j]);
+                    if ((valid >> j) & 1u) cp[j] = get_bounded(yp, h[j], 1u), cm[j] = get_bounded(ym, h[j], 1u);
                 }
             } else {
                 // round 0 of both tables: sixteen first-slot loads are issued before any word is looked at
                 uint64_t wp[QV_GROUP], wm[QV_GROUP];
-#pragma unroll
-                for (uint32_t j = 0; j < QV_GROUP; ++j) wp[j] = yp.table[((uint64_t)bucket_of(h[j]) << yp.cap_log2) + (key_of(h[j]) & capm_p)];
-#pragma unroll
-                for (uint32_t j = 0; j < QV_GROUP; ++j) wm[j] = ym.table[((uint64_t)bucket_of(h[j]) << ym.cap_log2) + (key_of(h[j]) & capm_m)];
+                probe_issue(yp.table, yp.cap_log2, h, wp);
+                probe_issue(ym.table, ym.cap_log2, h, wm);
                 __builtin_amdgcn_sched_barrier(0);
-                trio_settle(yp, h, valid, wp, cp);
-                trio_settle(ym, h, valid, wm, cm);
+                probe_settle(yp.table, yp.cap_log2, h, valid, wp, cp);
+                probe_settle(ym.table, ym.cap_log2, h, valid, wm, cm);
             }
             const uint32_t sep8 = (seps >> (8 * g)) & 0xFFu;
 #pragma unroll

@@ -13,12 +13,12 @@
 // key << 10 | count with key = hash >> 10, so the hash is (w >> 10) << 10 | bucket and no base is ever looked at.  EMPTY
 // words and words below the threshold are dropped (a table is at most half full: about every other slot and more).
 //
-// Probes: yak_get's rule on the other table (sub-table `bucket`, start at key & capm, linear, wrapping inside the
-// sub-table, stop at the key or at EMPTY), as k_qv_scan issues it: the lane's CMP_GROUP first-slot loads back to back
-// before any word is looked at, then the words that met another key one more slot each per round, again together.  A
-// dropped slot probes slot 0 of sub-table 0 (a valid address, its word ignored).  Random 8-byte reads of a table beyond
-// the caches are bounded by latency, that is by the number of independent loads in flight.  Every probe loop is bounded by
-// the sub-table's capacity: a counting table's sub-table may be full.
+// Probes: the probe contract of np2_kmerscan.hpp on the other table: the lane's CMP_GROUP first-slot loads back to back
+// before any word is looked at, then the words that met another key one more slot each per round, again together.  The
+// loop is this kernel's own, on (key, bucket) pairs with a slot index per word: next to a stream of slots, with no hashing
+// to hide it behind, probe_settle's 64-bit slot arithmetic per round made the two kernels 8 % slower (0.403 -> 0.434 ms on
+// the 12 Mb assembly's tables, k = 21), and probe_settle with this loop's slot indices costs k_trio_scan a wavefront per
+// SIMD in registers.
 //
 // Cost: the scanned table's bytes once, in order, plus one random sector of the probed table per live word (and a few
 // more where a probe chain is longer than one slot).
@@ -33,7 +33,7 @@
 #include <algorithm>
 
 #include "np2_cmp.hpp"
-#include "np2_kernels.hpp"
+#include "np2_kmerscan.hpp"
 
 namespace np2 {
 using namespace np2kc;
@@ -140,8 +140,7 @@ template <bool JOIN> __device__ __forceinline__ void cmp_scan(const CmpJoin &q) 
         only[0] = n_live; // (asm_only[0] is always 0: a live word's own count is at least 1)
 #pragma unroll
         for (uint32_t k = 0; k < CMP_CLASSES; ++k) {
-            uint32_t a = only[k];
-            for (int o = 32; o > 0; o >>= 1) a += (uint32_t)__shfl_down((int)a, o);
+            const uint32_t a = wave_sum(only[k]);
             if ((tid & 63u) == 0 && a) atomicAdd(&s_hist[k == 0 ? 0 : 1 + k], a);
         }
         __syncthreads();

@@ -23,7 +23,7 @@
 #include <hip/hip_runtime.h>
 
 #include "np2_edits.hpp"
-#include "np2_qv.hpp"
+#include "np2_kmerscan.hpp"
 
 namespace np2 {
 using namespace np2edits;
@@ -31,11 +31,6 @@ using namespace np2edits;
 namespace {
 
 static constexpr uint32_t EB = 256; // lanes of a block
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_down((int)v, o);
-    return v; // (lane 0)
-}
 
 // common suffix (SUFFIX) or prefix of ref[s .. s + lr) and out[o .. o + la) by one wavefront: 64 bytes per step
 template <bool SUFFIX>
@@ -69,21 +64,6 @@ __device__ __forceinline__ bool run_bounds(const EditsSeq &q, const EditsDev *ct
     return true;
 }
 
-// the lookup of one k-mer, probes bounded by the sub-table's capacity
-__device__ __forceinline__ uint32_t edits_get(const YakDev &y, uint64_t h, uint32_t min_count) {
-    if (y.ord) return qv_get_bounded(y, h, min_count);
-    const uint64_t capm = (1ULL << y.cap_log2) - 1;
-    const uint64_t *tb = y.table + ((uint64_t)np2kc::bucket_of(h) << y.cap_log2);
-    const uint64_t key = np2kc::key_of(h);
-    uint64_t s = key & capm;
-    for (uint64_t probe = 0; probe <= capm; ++probe, s = (s + 1) & capm) {
-        const uint64_t w = tb[s];
-        if (w == YAK_EMPTY) return 0;
-        if ((w >> np2kc::COUNT_BITS) == key) return np2qv::passing((uint32_t)(w & np2kc::COUNT_MAX), min_count);
-    }
-    return 0;
-}
-
 // one window of rule 6 by a wavefront: a lane per k-mer end
 __device__ __forceinline__ void wave_window(const YakDev &y, uint32_t min_count, const uint8_t *seq, uint64_t n, uint64_t at, uint64_t len,
                                             uint32_t lane, uint32_t &n_kmers, uint32_t &n_absent) {
@@ -95,7 +75,7 @@ __device__ __forceinline__ void wave_window(const YakDev &y, uint32_t min_count,
         uint64_t h = 0;
         if (!kmer_at(seq, e, y.k, mask, &h)) continue;
         ++a;
-        if (edits_get(y, h, min_count) == 0) ++b;
+        if (get_bounded(y, h, min_count) == 0) ++b;
     }
     n_kmers = wave_sum(a);
     n_absent = wave_sum(b);

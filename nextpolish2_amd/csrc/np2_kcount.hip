@@ -19,6 +19,7 @@
 
 #include "np2_kcount.hpp"
 #include "np2_kcount_core.hpp"
+#include "np2_kmerscan.hpp"
 
 namespace np2 {
 using namespace np2kc;
@@ -65,35 +66,25 @@ __device__ __forceinline__ void kc_spill(bool full, uint64_t h, uint64_t *ctr, u
 }
 
 __device__ __forceinline__ void kc_wave_add(uint32_t v, uint64_t *dst) {
-    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_down((int)v, o);
+    v = wave_sum(v);
     if (__lane_id() == 0 && v) atomicAdd((unsigned long long *)dst, (unsigned long long)v);
 }
 
 } // namespace
 
-// One block owns KC_TILE bytes of the piece and brings them, with the HALO bytes before them, into LDS with contiguous
-// 16-byte loads; a lane then owns KC_STRETCH bytes: it rolls its words over the 32 bytes before its stretch (the window is
-// the last k bytes, so rolling more of them changes nothing) and counts the k-mers that END inside its stretch.
+// One block owns KC_TILE bytes of the piece (the staging contract of np2_kmerscan.hpp, stage_aligned) and counts the
+// k-mers that END inside it.
 __global__ __launch_bounds__(KC_BLOCK) void k_kcount(const uint8_t *__restrict__ in, uint64_t n, uint32_t k, KcTable t,
                                                      uint64_t *__restrict__ ctr, uint64_t *__restrict__ spill) {
     __shared__ uint4 tile[(HALO + KC_TILE) / 16];
-    const uint64_t tile0 = (uint64_t)blockIdx.x * KC_TILE; // `in` offset of the tile's halo = piece offset of its first byte
-    const uint64_t total = HALO + n;                       // (the host pads the buffer with '\n' to a multiple of 16)
-    for (uint32_t i = threadIdx.x; i < (HALO + KC_TILE) / 16; i += KC_BLOCK) {
-        const uint64_t off = tile0 + (uint64_t)i * 16;
-        tile[i] = off < total ? *reinterpret_cast<const uint4 *>(in + off) : make_uint4(0x0A0A0A0Au, 0x0A0A0A0Au, 0x0A0A0A0Au, 0x0A0A0A0Au);
-    }
+    // `in` offset of the tile's halo = piece offset of its first byte (the host pads the buffer with '\n' to a multiple of 16)
+    stage_aligned<KC_BLOCK, (HALO + KC_TILE) / 16>(tile, in, (int64_t)blockIdx.x * KC_TILE, (int64_t)(HALO + n));
     __syncthreads();
     const uint32_t *lw = reinterpret_cast<const uint32_t *>(tile) + threadIdx.x * (KC_STRETCH / 4);
     const uint64_t mask = kmer_mask(k);
     Roll r;
     uint64_t h = 0;
-#pragma unroll 1
-    for (uint32_t d = 0; d < HALO / 4; ++d) {
-        const uint32_t w = lw[d];
-#pragma unroll
-        for (uint32_t j = 0; j < 4; ++j) (void)push(r, (uint8_t)(w >> (8 * j)), k, mask, &h);
-    }
+    warm_halo(r, [&](uint32_t d) { return lw[d]; }, k, mask);
     uint32_t claimed = 0, kmers = 0;
 #pragma unroll 1
     for (uint32_t d = 0; d < KC_STRETCH / 4; ++d) {
@@ -151,7 +142,7 @@ __global__ __launch_bounds__(KC_BLOCK) void k_kcount_bucket_sizes(KcTable t, uin
         const uint64_t w = tb[i];
         c += (w != EMPTY && (uint32_t)(w & COUNT_MAX) >= min_count) ? 1u : 0u;
     }
-    for (int o = 32; o > 0; o >>= 1) c += (uint32_t)__shfl_down((int)c, o);
+    c = wave_sum(c);
     if ((threadIdx.x & 63u) == 0 && c) atomicAdd(&total, c);
     __syncthreads();
     if (threadIdx.x == 0) sizes[blockIdx.x] = total;

@@ -8,13 +8,17 @@
 
 namespace np2 {
 
-// One scan: tiles [0, n_tiles) of a stream whose offset 0 is `src` (any alignment).  Only offsets in [lo, hi) are read as
-// bases, everything else as separators; the 16-byte loads are aligned and those that straddle lo or hi are masked.
-struct QvScan {
+// The stream of one scan (QvScan, TrioScan): tiles [0, n_tiles) of a stream whose offset 0 is `src` (any alignment).  Only
+// offsets in [lo, hi) are read as bases, everything else as separators; the 16-byte loads are aligned and those that
+// straddle lo or hi are masked (stage_any, np2_kmerscan.hpp).  Every sequence starts at a tile boundary.
+struct ScanStream {
     const uint8_t *src;
     int64_t lo, hi;
-    const uint32_t *desc;      // per tile: sequence index | QV_FIRST; nullptr: one sequence (index 0) starting at offset 0
+    const uint32_t *desc; // per tile: sequence index | QV_FIRST; nullptr: one sequence (index 0) starting at offset 0
     uint32_t n_tiles;
+};
+struct QvScan {
+    ScanStream in;
     uint32_t min_count;
     unsigned long long *stats; // per sequence: n_kmers, n_absent (added to)
     unsigned long long *hist;  // QV_HIST_BINS counters (added to), or nullptr

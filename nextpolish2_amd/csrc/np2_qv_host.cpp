@@ -24,6 +24,21 @@ struct QvBufs { // released after the call's device work has completed: cached b
     QvBufs() { stage.cached = desc.cached = bits.cached = stats.cached = hist.cached = true; }
 };
 
+// one scan on the context's stream: `in` is the staged piece or the resident sequence
+void run_scan(np2_ctx_t *cx, int yak_idx, const np2::ScanStream &in, uint16_t min_count, const QvBufs &d, bool hist, bool bits,
+              KernelTimer &timer) {
+    QvScan q{};
+    q.in = in;
+    q.min_count = min_count;
+    q.stats = reinterpret_cast<unsigned long long *>(d.stats.p);
+    q.hist = hist ? reinterpret_cast<unsigned long long *>(d.hist.p) : nullptr;
+    q.bits = bits ? d.bits.p : nullptr;
+    timer.start(cx->stream);
+    launch_qv_scan(cx->stream, cx->yaks[yak_idx].dev(), q, qv_blocks(cx->device));
+    timer.stop(cx->stream);
+    HIPCHK(hipGetLastError());
+}
+
 } // namespace
 
 extern "C" {
@@ -42,11 +57,10 @@ int np2_qv_strings(np2_ctx_t *cx, int yak_idx, const uint8_t *strs, const uint64
         if (n == 0 || off[n] == off[0]) return NP2_OK;
 
         HIPCHK(hipSetDevice(cx->device));
-        const YakDev y = cx->yaks[yak_idx].dev();
         // the staging buffers, host and device: what the call needs, up to the fixed piece size
         uint64_t all_tiles = 0;
         for (uint64_t i = 0; i < n; ++i) all_tiles += tiles_of(off[i + 1] - off[i]);
-        const uint32_t cap = (uint32_t)std::min<uint64_t>(stage_tiles(), all_tiles), blocks = qv_blocks(cx->device);
+        const uint32_t cap = (uint32_t)std::min<uint64_t>(stage_tiles(), all_tiles);
         QvBufs d;
         d.stage.ensure(HALO + (size_t)cap * QV_TILE);
         d.desc.ensure(cap);
@@ -67,20 +81,8 @@ int np2_qv_strings(np2_ctx_t *cx, int yak_idx, const uint8_t *strs, const uint64
             HIPCHK(hipMemcpyAsync(d.stage.p, sp.hs.data(), HALO + (size_t)nt * QV_TILE, hipMemcpyHostToDevice, cx->stream));
             HIPCHK(hipMemcpyAsync(d.desc.p, sp.hd.data(), (size_t)nt * 4, hipMemcpyHostToDevice, cx->stream));
             HIPCHK(hipMemsetAsync(d.stats.p, 0, n_rel * 16, cx->stream));
-            QvScan q{};
-            q.src = d.stage.p + HALO;
-            q.lo = -(int64_t)HALO;
-            q.hi = (int64_t)nt * QV_TILE;
-            q.desc = d.desc.p;
-            q.n_tiles = nt;
-            q.min_count = min_count;
-            q.stats = reinterpret_cast<unsigned long long *>(d.stats.p);
-            q.hist = hist ? reinterpret_cast<unsigned long long *>(d.hist.p) : nullptr;
-            q.bits = absent_bits ? d.bits.p : nullptr;
-            timer.start(cx->stream);
-            launch_qv_scan(cx->stream, y, q, blocks);
-            timer.stop(cx->stream);
-            HIPCHK(hipGetLastError());
+            run_scan(cx, yak_idx, {d.stage.p + HALO, -(int64_t)HALO, (int64_t)nt * QV_TILE, d.desc.p, nt}, min_count, d, hist != nullptr,
+                     absent_bits != nullptr, timer);
             HIPCHK(hipMemcpyAsync(hst.data(), d.stats.p, n_rel * 16, hipMemcpyDeviceToHost, cx->stream));
             if (absent_bits) HIPCHK(hipMemcpyAsync(hb.data(), d.bits.p, (size_t)nt * QV_TILE_BITS, hipMemcpyDeviceToHost, cx->stream));
             HIPCHK(hipStreamSynchronize(cx->stream)); // (the staging buffers are filled again for the next piece)
@@ -125,20 +127,8 @@ int np2_qv_device(np2_ctx_t *cx, int yak_idx, const uint8_t *dev_seq, uint64_t l
         }
         if (absent_bits) d.bits.ensure((size_t)nt * QV_BLOCK);
         KernelTimer timer(kernel_ms != nullptr);
-        QvScan q{};
-        q.src = dev_seq; // any alignment, nothing readable promised around it: the kernel masks its first and last loads
-        q.lo = 0;
-        q.hi = (int64_t)len;
-        q.desc = nullptr;
-        q.n_tiles = nt;
-        q.min_count = min_count;
-        q.stats = reinterpret_cast<unsigned long long *>(d.stats.p);
-        q.hist = hist ? reinterpret_cast<unsigned long long *>(d.hist.p) : nullptr;
-        q.bits = absent_bits ? d.bits.p : nullptr;
-        timer.start(cx->stream);
-        launch_qv_scan(cx->stream, cx->yaks[yak_idx].dev(), q, qv_blocks(cx->device));
-        timer.stop(cx->stream);
-        HIPCHK(hipGetLastError());
+        // any alignment, nothing readable promised around it: the kernel masks its first and last loads
+        run_scan(cx, yak_idx, {dev_seq, 0, (int64_t)len, nullptr, nt}, min_count, d, hist != nullptr, absent_bits != nullptr, timer);
         uint64_t st[2] = {0, 0};
         HIPCHK(hipMemcpyAsync(st, d.stats.p, 16, hipMemcpyDeviceToHost, cx->stream));
         if (hist) HIPCHK(hipMemcpyAsync(hist, d.hist.p, QV_HIST_BINS * 8, hipMemcpyDeviceToHost, cx->stream));

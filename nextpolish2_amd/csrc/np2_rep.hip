@@ -15,37 +15,28 @@
 
 #include "np2_blockscan.hpp"
 #include "np2_kcount.hpp"
+#include "np2_kmerscan.hpp"
 #include "np2_rep.hpp"
 #include "np2_rep_core.hpp"
 
 namespace np2 {
 using np2kc::HALO;
 
-// The tiling of k_kcount: a block owns KC_TILE bytes of the piece and brings them, with the HALO bytes before them, into
-// LDS with 16-byte loads; a lane rolls its words over the 32 bytes before its stretch and counts the k-mers that END inside
+// The tiling of k_kcount (the staging contract of np2_kmerscan.hpp, stage_aligned): a lane counts the k-mers that END inside
 // its 32 bytes.  The update is one atomicAdd (no return value) on the k-mer's counter.  A homopolymer or a satellite sends
 // every k-mer of a stretch to one or two addresses, so with COLLAPSE a lane keeps (index, run length) and adds once when
 // the index changes: a 300 000-base homopolymer costs 9 400 adds on its counter instead of 300 000.
 template <bool COLLAPSE>
 __global__ __launch_bounds__(KC_BLOCK) void k_rep_count(const uint8_t *__restrict__ in, uint64_t n, uint32_t k, uint32_t *__restrict__ count) {
     __shared__ uint4 tile[(HALO + KC_TILE) / 16];
-    const uint64_t tile0 = (uint64_t)blockIdx.x * KC_TILE; // `in` offset of the tile's halo = piece offset of its first byte
-    const uint64_t total = HALO + n;                       // (the host pads the buffer with '\n' to a multiple of 16)
-    for (uint32_t i = threadIdx.x; i < (HALO + KC_TILE) / 16; i += KC_BLOCK) {
-        const uint64_t off = tile0 + (uint64_t)i * 16;
-        tile[i] = off < total ? *reinterpret_cast<const uint4 *>(in + off) : make_uint4(0x0A0A0A0Au, 0x0A0A0A0Au, 0x0A0A0A0Au, 0x0A0A0A0Au);
-    }
+    // `in` offset of the tile's halo = piece offset of its first byte (the host pads the buffer with '\n' to a multiple of 16)
+    stage_aligned<KC_BLOCK, (HALO + KC_TILE) / 16>(tile, in, (int64_t)blockIdx.x * KC_TILE, (int64_t)(HALO + n));
     __syncthreads();
     const uint32_t *lw = reinterpret_cast<const uint32_t *>(tile) + threadIdx.x * (KC_STRETCH / 4);
     const uint64_t mask = np2kc::kmer_mask(k);
     np2kc::Roll r;
     uint32_t v = 0;
-#pragma unroll 1
-    for (uint32_t d = 0; d < HALO / 4; ++d) {
-        const uint32_t w = lw[d];
-#pragma unroll
-        for (uint32_t j = 0; j < 4; ++j) (void)np2rep::push(r, (uint8_t)(w >> (8 * j)), k, mask, &v);
-    }
+    warm_halo(r, [&](uint32_t d) { return lw[d]; }, k, mask);
     uint32_t run_v = 0, run_n = 0;
 #pragma unroll 1
     for (uint32_t d = 0; d < KC_STRETCH / 4; ++d) {
@@ -65,13 +56,6 @@ __global__ __launch_bounds__(KC_BLOCK) void k_rep_count(const uint8_t *__restric
     }
     if (COLLAPSE && run_n) atomicAdd(&count[run_v], run_n);
 }
-
-namespace {
-__device__ __forceinline__ uint32_t rep_wave_sum(uint32_t v) {
-    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_down((int)v, o);
-    return v;
-}
-} // namespace
 
 // The selection's pass over the table, a grid-stride loop of uint4 loads.  Almost every counter is 0 or small, so what is
 // common never reaches a global atomic: the high-half bin 0, the counters above 0, their sum and maximum are per-lane
@@ -105,14 +89,14 @@ __global__ __launch_bounds__(REP_BLOCK) void k_rep_hist(const uint32_t *__restri
             else atomicAdd(&hist_lo[l], 1u);
         }
     }
-    n1 = rep_wave_sum(n1), n2 = rep_wave_sum(n2), n3 = rep_wave_sum(n3);
+    n1 = wave_sum(n1), n2 = wave_sum(n2), n3 = wave_sum(n3);
     if (__lane_id() == 0) {
         if (n1) atomicAdd(&lo[1], n1);
         if (n2) atomicAdd(&lo[2], n2);
         if (n3) atomicAdd(&lo[3], n3);
     }
     if (first) { // (uniform)
-        distinct = rep_wave_sum(distinct), hi0 = rep_wave_sum(hi0);
+        distinct = wave_sum(distinct), hi0 = wave_sum(hi0);
         for (int o = 32; o > 0; o >>= 1) {
             sum += __shfl_down(sum, o);
             mx = max(mx, (uint32_t)__shfl_down((int)mx, o));
@@ -149,7 +133,7 @@ __global__ __launch_bounds__(REP_BLOCK) void k_rep_sizes(const uint32_t *__restr
         const uint4 q = rep_slab(count, n4, blockIdx.x, s, &at);
         c += (q.x > threshold) + (q.y > threshold) + (q.z > threshold) + (q.w > threshold);
     }
-    c = rep_wave_sum(c);
+    c = wave_sum(c);
     if (__lane_id() == 0 && c) atomicAdd(&total, c);
     __syncthreads();
     if (threadIdx.x == 0) sizes[blockIdx.x] = total;

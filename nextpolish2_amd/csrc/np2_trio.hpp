@@ -4,18 +4,14 @@
 #include <hip/hip_runtime.h>
 #include <string>
 
-#include "np2_kernels.hpp"
+#include "np2_qv.hpp"
 #include "np2_trio_core.hpp"
 
 namespace np2 {
 
-// One scan: tiles [0, n_tiles) of a stream laid out and masked exactly as QvScan's (np2_qv.hpp): offset 0 is `src` (any
-// alignment), only offsets in [lo, hi) are read as bases, every sequence starts at a tile boundary.
+// One scan of a stream laid out and masked as the QV scan's (ScanStream, np2_qv.hpp).
 struct TrioScan {
-    const uint8_t *src;
-    int64_t lo, hi;
-    const uint32_t *desc;      // per tile: sequence index | QV_FIRST; nullptr: one sequence (index 0) starting at offset 0
-    uint32_t n_tiles;
+    ScanStream in;
     uint32_t min_count, mid_count;
     unsigned long long *stats; // per sequence TRIO_STATS counters (added to): n_kmers, n_pat, n_mat, pp, pm, mp, mm
     uint32_t *tiles;           // n_tiles words: np2trio::tile_word of every tile (written)
@@ -29,6 +25,17 @@ void launch_trio_scan(hipStream_t s, const YakDev &pat, const YakDev &mat, const
 // k_trio_join: the pairs across tile boundaries, one block over all tiles (a segmented scan of q.tiles); after the scan
 void launch_trio_join(hipStream_t s, const TrioScan &q);
 
+#if defined(__HIPCC__)
+// the scan operators of np2_trio_core.hpp's carry algebra (np2_blockscan.hpp), for np2_trio.hip and np2_bin.hip
+struct OpRight {
+    static __device__ __forceinline__ uint32_t ident() { return 0u; }
+    static __device__ __forceinline__ uint32_t apply(uint32_t a, uint32_t b) { return np2trio::right(a, b); }
+};
+struct OpSegRight {
+    static __device__ __forceinline__ uint32_t ident() { return 0u; }
+    static __device__ __forceinline__ uint32_t apply(uint32_t a, uint32_t b) { return np2trio::seg_right(a, b); }
+};
+#endif
 
 } // namespace np2
 

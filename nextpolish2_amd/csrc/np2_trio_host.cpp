@@ -35,6 +35,25 @@ void add_to(np2_trio_t &o, const uint64_t *st) {
     for (int i = 0; i < 4; ++i) o.pairs[i] += st[3 + i];
 }
 
+// one scan and its join on the context's stream: `in` is the staged piece or the resident sequence
+void run_scan(np2_ctx_t *cx, int pat_idx, int mat_idx, const np2::ScanStream &in, uint16_t min_count, uint16_t mid_count, const TrioBufs &d,
+              bool pat_bits, bool mat_bits, KernelTimer &timer) {
+    TrioScan q{};
+    q.in = in;
+    q.min_count = min_count;
+    q.mid_count = mid_count;
+    q.stats = reinterpret_cast<unsigned long long *>(d.stats.p);
+    q.tiles = d.tiles.p;
+    q.pat_bits = pat_bits ? d.pat_bits.p : nullptr;
+    q.mat_bits = mat_bits ? d.mat_bits.p : nullptr;
+    q.carry = d.carry.p;
+    timer.start(cx->stream);
+    launch_trio_scan(cx->stream, cx->yaks[pat_idx].dev(), cx->yaks[mat_idx].dev(), q, trio_blocks(cx->device));
+    launch_trio_join(cx->stream, q);
+    timer.stop(cx->stream);
+    HIPCHK(hipGetLastError());
+}
+
 } // namespace
 
 // everything about the tables and the thresholds, before anything is launched
@@ -65,10 +84,9 @@ int np2_trio_strings(np2_ctx_t *cx, int pat_idx, int mat_idx, const uint8_t *str
         if (n == 0 || off[n] == off[0]) return NP2_OK;
 
         HIPCHK(hipSetDevice(cx->device));
-        const YakDev yp = cx->yaks[pat_idx].dev(), ym = cx->yaks[mat_idx].dev();
         uint64_t all_tiles = 0;
         for (uint64_t i = 0; i < n; ++i) all_tiles += tiles_of(off[i + 1] - off[i]);
-        const uint32_t cap = (uint32_t)std::min<uint64_t>(stage_tiles(), all_tiles), blocks = trio_blocks(cx->device);
+        const uint32_t cap = (uint32_t)std::min<uint64_t>(stage_tiles(), all_tiles);
         TrioBufs d;
         d.stage.ensure(HALO + (size_t)cap * QV_TILE);
         d.desc.ensure(cap);
@@ -89,24 +107,8 @@ int np2_trio_strings(np2_ctx_t *cx, int pat_idx, int mat_idx, const uint8_t *str
             HIPCHK(hipMemcpyAsync(d.stage.p, sp.hs.data(), HALO + (size_t)nt * QV_TILE, hipMemcpyHostToDevice, cx->stream));
             HIPCHK(hipMemcpyAsync(d.desc.p, sp.hd.data(), (size_t)nt * 4, hipMemcpyHostToDevice, cx->stream));
             HIPCHK(hipMemsetAsync(d.stats.p, 0, n_rel * TRIO_STATS * 8, cx->stream));
-            TrioScan q{};
-            q.src = d.stage.p + HALO;
-            q.lo = -(int64_t)HALO;
-            q.hi = (int64_t)nt * QV_TILE;
-            q.desc = d.desc.p;
-            q.n_tiles = nt;
-            q.min_count = min_count;
-            q.mid_count = mid_count;
-            q.stats = reinterpret_cast<unsigned long long *>(d.stats.p);
-            q.tiles = d.tiles.p;
-            q.pat_bits = pat_bits ? d.pat_bits.p : nullptr;
-            q.mat_bits = mat_bits ? d.mat_bits.p : nullptr;
-            q.carry = d.carry.p;
-            timer.start(cx->stream);
-            launch_trio_scan(cx->stream, yp, ym, q, blocks);
-            launch_trio_join(cx->stream, q);
-            timer.stop(cx->stream);
-            HIPCHK(hipGetLastError());
+            run_scan(cx, pat_idx, mat_idx, {d.stage.p + HALO, -(int64_t)HALO, (int64_t)nt * QV_TILE, d.desc.p, nt}, min_count, mid_count, d,
+                     pat_bits != nullptr, mat_bits != nullptr, timer);
             HIPCHK(hipMemcpyAsync(hst.data(), d.stats.p, n_rel * TRIO_STATS * 8, hipMemcpyDeviceToHost, cx->stream));
             if (pat_bits) HIPCHK(hipMemcpyAsync(hbp.data(), d.pat_bits.p, (size_t)nt * QV_TILE_BITS, hipMemcpyDeviceToHost, cx->stream));
             if (mat_bits) HIPCHK(hipMemcpyAsync(hbm.data(), d.mat_bits.p, (size_t)nt * QV_TILE_BITS, hipMemcpyDeviceToHost, cx->stream));
@@ -146,24 +148,9 @@ int np2_trio_device(np2_ctx_t *cx, int pat_idx, int mat_idx, const uint8_t *dev_
         if (pat_bits) d.pat_bits.ensure((size_t)nt * QV_BLOCK);
         if (mat_bits) d.mat_bits.ensure((size_t)nt * QV_BLOCK);
         KernelTimer timer(kernel_ms != nullptr);
-        TrioScan q{};
-        q.src = dev_seq; // any alignment, nothing readable promised around it: the kernel masks its first and last loads
-        q.lo = 0;
-        q.hi = (int64_t)len;
-        q.desc = nullptr;
-        q.n_tiles = nt;
-        q.min_count = min_count;
-        q.mid_count = mid_count;
-        q.stats = reinterpret_cast<unsigned long long *>(d.stats.p);
-        q.tiles = d.tiles.p;
-        q.pat_bits = pat_bits ? d.pat_bits.p : nullptr;
-        q.mat_bits = mat_bits ? d.mat_bits.p : nullptr;
-        q.carry = d.carry.p;
-        timer.start(cx->stream);
-        launch_trio_scan(cx->stream, cx->yaks[pat_idx].dev(), cx->yaks[mat_idx].dev(), q, trio_blocks(cx->device));
-        launch_trio_join(cx->stream, q);
-        timer.stop(cx->stream);
-        HIPCHK(hipGetLastError());
+        // any alignment, nothing readable promised around it: the kernel masks its first and last loads
+        run_scan(cx, pat_idx, mat_idx, {dev_seq, 0, (int64_t)len, nullptr, nt}, min_count, mid_count, d, pat_bits != nullptr,
+                 mat_bits != nullptr, timer);
         uint64_t st[TRIO_STATS] = {};
         HIPCHK(hipMemcpyAsync(st, d.stats.p, TRIO_STATS * 8, hipMemcpyDeviceToHost, cx->stream));
         if (pat_bits) HIPCHK(hipMemcpyAsync(pat_bits, d.pat_bits.p, bits_bytes(len), hipMemcpyDeviceToHost, cx->stream));

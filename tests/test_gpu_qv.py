@@ -4,6 +4,7 @@ Polisher.lookup_hashes (the polish kernels' own lookup) as an independent device
 
 Every case is one bounded subprocess or a handful of in-process calls."""
 import ctypes as C
+import functools
 import gzip
 import os
 import subprocess
@@ -15,7 +16,7 @@ import pytest
 from nextpolish2_amd import Opts, Polisher, api, qv
 from nextpolish2_amd import io as np2io
 from nextpolish2_amd._types import Yak
-from test_kcount_cpu import FIXTURE, numpy_count
+from test_kcount_cpu import FIXTURE, numpy_count, stream_hashes
 from test_qv_cpu import (ASM_IN, ASM_OUT, BAM, BUNDLE, FASTA, KNOWN, aggregate, fasta_records, kmer_hashes_at, numpy_qv,
                          read_dump)
 
@@ -287,6 +288,57 @@ def test_repeated_keys_answer_like_lookup_hashes():
         assert np.array_equal(r.hist, e_hist)
         seen.add(tuple(int(x) for x in np.flatnonzero(r.hist)))
     assert len(seen) >= 3  # (the threshold chooses among a key's words: 2 / 9 / the original come and go)
+    pol.close()
+
+
+# ---- 6b. probe chains that wrap inside a crowded sub-table ------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def crowded(k):
+    """(sequence, hashes[1024, 7], counts[1024, 7]): a seeded 200 kb sequence and, for every bucket, seven of its k-mers
+    (the count model's distinct hashes) whose probe chain starts in slot 14 or 15 of a 16-slot sub-table, with distinct
+    counts.  A table of at most seven words per bucket is uploaded into 16-slot sub-tables (2 * 7 + 2), so every chain
+    of three and more of them runs 14, 15, 0, 1, ... and wraps; the bucket's other late-start k-mers (at least one, by the
+    precondition) are not in the table and walk the whole chain to an EMPTY slot.  Shared with the trio and triobin tests."""
+    seq = random_bases(np.random.default_rng(7), 200_000)
+    h = np.unique(stream_hashes(seq + b"\n", k))
+    late = h[((h >> np.uint64(10)) & np.uint64(15)) >= 14]
+    per = [late[(late & np.uint64(1023)) == b] for b in range(1024)]
+    assert min(len(x) for x in per) >= 8, (k, min(len(x) for x in per))  # the seed's precondition
+    hashes = np.stack([x[:7] for x in per])
+    counts = np.tile(np.arange(2, 9, dtype=np.uint64), (1024, 1))
+    return seq, hashes, counts
+
+
+def dump_of(hashes, counts):
+    """(words, bucket_off) of a dump holding `hashes` (distinct) with `counts`: bucket-major, ascending inside a bucket"""
+    order = np.lexsort((hashes, hashes & np.uint64(1023)))
+    h, c = hashes[order], counts[order]
+    off = np.zeros(1025, np.uint64)
+    off[1:] = np.cumsum(np.bincount((h & np.uint64(1023)).astype(np.int64), minlength=1024))
+    return ((h >> np.uint64(10)) << np.uint64(10)) | c, off
+
+
+@pytest.mark.parametrize("k", [21, 31])
+def test_probe_chains_wrap_inside_crowded_subtables(monkeypatch, k):
+    seq, hashes, counts = crowded(k)
+    yak = Yak(k, *dump_of(hashes.ravel(), counts.ravel()))
+    assert int(np.diff(yak.bucket_off.astype(np.int64)).max()) == 7  # 16-slot sub-tables
+    pol = Polisher([yak])
+    valid, hh = kmer_hashes_at(seq, k)
+    for min_count in (1, 5):
+        found = np.zeros(len(valid), np.uint32)
+        found[valid] = pol.lookup_hashes(0, hh[valid], min_count)
+        nk, na, e_hist, e_bits = aggregate(valid, found)
+        m_nk, m_na, m_hist, m_bits = numpy_qv(seq, k, yak_table(yak), min_count)
+        assert (nk, na) == (m_nk, m_na) and np.array_equal(e_hist, m_hist) and np.array_equal(e_bits, m_bits)
+        assert nk - na >= 1024 * (4 if min_count == 5 else 7) and na > 1024
+        for stage_tiles in (None, 1):
+            if stage_tiles is not None:
+                monkeypatch.setenv("NP2_QV_TEST_STAGE_TILES", str(stage_tiles))
+            r = pol.qv_strings(0, [seq], min_count, hist=True, bits=True)
+            assert (r.n_kmers, r.n_absent) == (nk, na), (k, min_count, stage_tiles)
+            assert np.array_equal(r.hist, e_hist) and np.array_equal(r.bits[0], e_bits), (k, min_count, stage_tiles)
+        monkeypatch.delenv("NP2_QV_TEST_STAGE_TILES")
     pol.close()
 
 

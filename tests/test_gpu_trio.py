@@ -14,7 +14,7 @@ from nextpolish2_amd import Opts, Polisher, api, trio
 from nextpolish2_amd import io as np2io
 from nextpolish2_amd._types import Yak
 from nextpolish2_amd.synth import Synth
-from test_gpu_qv import HALO, TILE, edge_sequences, noisy, random_bases, yak_table
+from test_gpu_qv import HALO, TILE, crowded, dump_of, edge_sequences, noisy, random_bases, yak_table
 from test_kcount_cpu import numpy_count
 from test_qv_cpu import kmer_hashes_at
 from test_trio_cpu import aggregate, classes, numpy_trio, table_of
@@ -200,6 +200,33 @@ def test_repeated_keys_answer_like_lookup_hashes():
         seen.update(same_as_lookup(pol, K, seqs, [(2, 5), (1, 1), (4, 7), (2, 3)]))
         pol.close()
     assert len(seen) >= 4  # (the repeats change the answers: a third of the keys read 1, 3 or 7 instead of 5)
+
+
+def crowded_parents(k):
+    """test_gpu_qv.crowded's seven k-mers per bucket split between a paternal table (3: counts 3, 5, 7) and a maternal one
+    (4: counts 2, 4, 6, 8), the other way round in bucket 0: both tables get 16-slot sub-tables, and every chain starts in
+    slot 14 or 15 and wraps"""
+    seq, hashes, counts = crowded(k)
+    pat = np.zeros(hashes.shape, bool)
+    pat[:, 1::2] = True
+    pat[0] = ~pat[0]
+    yaks = [Yak(k, *dump_of(hashes[sel], counts[sel])) for sel in (pat, ~pat)]
+    assert [int(np.diff(y.bucket_off.astype(np.int64)).max()) for y in yaks] == [4, 4]
+    return seq, yaks
+
+
+@pytest.mark.parametrize("k", [21, 31])
+def test_probe_chains_wrap_inside_crowded_subtables(monkeypatch, k):
+    seq, yaks = crowded_parents(k)
+    pol = Polisher(yaks)
+    tp, tm = yak_table(yaks[0]), yak_table(yaks[1])
+    for stage_tiles in (None, 1):
+        if stage_tiles is not None:
+            monkeypatch.setenv("NP2_TRIO_TEST_STAGE_TILES", str(stage_tiles))
+        r = same_as_numpy(pol, k, tp, tm, [seq], 2, 5)
+        assert r.total[1] > 1024 and r.total[2] > 1024 and r.total[4] > 100 and r.total[5] > 100
+        same_as_lookup(pol, k, [seq], [(2, 5), (1, 1), (3, 8)])
+    pol.close()
 
 
 def test_12mb_diploid_assembly_in_contigs():

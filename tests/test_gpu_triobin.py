@@ -16,9 +16,9 @@ from nextpolish2_amd import io as np2io
 from nextpolish2_amd._types import Yak
 from nextpolish2_amd.synth import Synth
 from test_gpu_qv import TILE, noisy, random_bases, yak_table
-from test_gpu_trio import chimera, parent_yak
+from test_gpu_trio import chimera, crowded_parents, lookup_counts, parent_yak
 from test_kcount_cpu import numpy_count
-from test_trio_cpu import numpy_trio
+from test_trio_cpu import aggregate, classes, numpy_trio
 from test_triobin_cpu import brute_force, expected_class
 
 pytestmark = pytest.mark.gpu
@@ -162,6 +162,32 @@ def test_layout_independence(edge_setup, layout_reference, monkeypatch, blocks, 
         monkeypatch.setenv("NP2_BIN_TEST_BLOCKS", str(blocks))
     r = pol.bin_stream(0, 1, reads, 2, 5, stats=True)
     assert r.classes == ref.classes and r.stats.tobytes() == ref.stats.tobytes()
+
+
+# ---- 2b. probe chains that wrap inside a crowded sub-table ------------------------------------------------------------------------
+@pytest.mark.parametrize("k", [21, 31])
+def test_probe_chains_wrap_inside_crowded_subtables(monkeypatch, k):
+    """test_gpu_trio.crowded_parents' sequence cut into reads of assorted lengths: the brute force, np2_trio_strings and the
+    polish kernels' lookup of both tables all give the binner's tallies, in one piece and in pieces of one tile"""
+    seq, yaks = crowded_parents(k)
+    rng = np.random.default_rng(3)
+    lens = [0, 1, k - 1, k, 33, TILE - 1, TILE, TILE + 1, 3 * TILE + 7]
+    reads, at = [], 0
+    while at < len(seq):
+        n = lens[len(reads)] if len(reads) < len(lens) else int(rng.integers(0, 6000))
+        reads.append(seq[at:at + n])
+        at += n
+    pol = Polisher(yaks)
+    tp, tm = yak_table(yaks[0]), yak_table(yaks[1])
+    e_lookup = [aggregate(v, classes(v, cp, cm, 2, 5))[0] for v, cp, cm in (lookup_counts(pol, k, x) for x in reads)]
+    for stage_tiles in (None, 1):
+        if stage_tiles is not None:
+            monkeypatch.setenv("NP2_BIN_TEST_STAGE_TILES", str(stage_tiles))
+        r = check_reads(pol, k, tp, tm, reads, 2, 5)
+        assert [tuple(int(x) for x in row) for row in r.stats] == e_lookup
+        tot = r.stats.sum(axis=0)
+        assert tot[1] > 1024 and tot[2] > 1024 and tot[4] > 50 and tot[5] > 50
+    pol.close()
 
 
 # ---- 3. the known answer ------------------------------------------------------------------------------------------------------
