@@ -551,6 +551,8 @@ struct np2_ctx {
     DevBuf<uint8_t> reg_lable, grp, cns_base2, rech_groups, rech_groups_tmp;
     DevBuf<uint8_t> votepack;  // the vote's device-to-host payload in one piece: per-read arrays, row offsets, adjacency rows
     DevBuf<uint8_t> votepack2; // ... of the wide form (shards, sort fallback), gathered by copy kernels (batch driver)
+    DevBuf<uint32_t> rl_list, rl_blob_off, rl_glen; // recheck from a region list: both rounds' lists; per group: first byte, slot length
+    DevBuf<uint2> rl_job_ol;                        // ... per job: offset and length of its string
     DevBuf<uint32_t> rech_headjobs; // per RECH region: 0 or 1 + the job count of the group it heads
     DevBuf<uint32_t> ecount, eval, eval_s, eflag, eidx, seed_cand, keep_n, keep_list, cns_pos2, sp_idx_s,
         sp_idx_e, ap_g, ap_s, ap_e, rech, rech_joboff, job_len,
@@ -589,8 +591,9 @@ struct np2_ctx {
     struct Hooks {
         bool front_unfused = false, pf_prof = false, edge_sort = false;
         bool test_misspeculate = false, shard_spec_log = false, phase_profile = false, exact_grow = false, no_speculate = false;
-        bool has_grow_guess = false;
+        bool has_grow_guess = false, rech_general = false, rech_log = false;
         uint32_t grow_guess = 0;
+        uint32_t rech_cap_list = 0xFFFFFFFFu, rech_cap_jobs = 0xFFFFFFFFu, rech_cap_blob = 0xFFFFFFFFu;
         bool has_pf_cap = false, has_pf_cap_big = false, has_pf_halo = false, has_pf_cov_max = false;
         uint32_t pf_cap = 0, pf_cap_big = 0, pf_halo = 0, pf_cov_max = 0;
         void read() {
@@ -602,6 +605,16 @@ struct np2_ctx {
             test_misspeculate = on("NP2_TEST_MISSPECULATE");
             shard_spec_log = on("NP2_SHARD_SPEC_LOG"), phase_profile = on("NP2_PHASE_PROFILE"), exact_grow = on("NP2_EXACT_GROW");
             no_speculate = on("NP2_NO_SPECULATE");
+            // the recheck of the final pass: NP2_RECH_GENERAL = always the general kernels (A/B runs, tests);
+            // NP2_TEST_RECH_CAP=<regions>[,<jobs>[,<bytes>]] lowers the list path's capacities (tests: the overflow and its redo)
+            rech_general = on("NP2_RECH_GENERAL");
+            rech_log = on("NP2_RECH_LOG"); // the general kernels print a round's counts (what the list path's capacities are set by)
+            if (const char *e = getenv("NP2_TEST_RECH_CAP")) {
+                char *end = nullptr;
+                rech_cap_list = (uint32_t)strtoul(e, &end, 10);
+                if (end && *end == ',') rech_cap_jobs = (uint32_t)strtoul(end + 1, &end, 10);
+                if (end && *end == ',') rech_cap_blob = (uint32_t)strtoul(end + 1, &end, 10);
+            }
             u32("NP2_TEST_GROW_GUESS", has_grow_guess, grow_guess);
             u32("NP2_PF_CAP", has_pf_cap, pf_cap), u32("NP2_PF_CAP_BIG", has_pf_cap_big, pf_cap_big);
             u32("NP2_PF_HALO", has_pf_halo, pf_halo), u32("NP2_PF_COV_MAX", has_pf_cov_max, pf_cov_max);
@@ -631,6 +644,9 @@ static_assert(S_M1 % 2 == 0 && S_LAST0 % 2 == 0 && S_GAIN0 % 2 == 0 && S_PFGAIN0
 static constexpr int NP2_MAX_YAK = 15; // splice rounds 0 .. n_yak index mlen[16] and the counters behind S_COUNT
 static constexpr uint32_t SCAL_TOTAL = 96; // posted block (S_COUNT) + per-splice-round counters behind it
 static_assert(S_COUNT + 2 * (NP2_MAX_YAK + 2) <= SCAL_TOTAL && S_COUNT < 64, "round counters behind the posted block; the mailbox holds 64 words");
+// ... and behind those the recheck's region lists (np2_regions.hip: k_rech_prepare): the two lists' counts, then the RL_* words
+static constexpr uint32_t S_RL = S_COUNT + 2 * (NP2_MAX_YAK + 2);
+static_assert(S_RL + 2 + np2::RL_STATE_WORDS <= SCAL_TOTAL, "the region lists' counters fit behind the round counters");
 
 inline double thread_cpu_ms() { // CPU time of the calling thread
     timespec ts;

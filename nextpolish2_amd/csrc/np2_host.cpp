@@ -130,8 +130,11 @@ void trace_region_tables(np2_ctx *cx, int pass, const std::string &tag, const Pa
 
 // the final pass ran its splice rounds with a guessed growth allowance that turned out too small (nothing was written
 // out of bounds: k_splice_plan): run_final_pass repeats the pass with the exact one
+// ... or its recheck rounds went by the region list and a list, job count or string size outgrew its capacity (again
+// nothing out of bounds, the round spliced nothing: k_rech_prepare): repeated with the general recheck kernels
 struct GrowRetry : Np2Error {
-    GrowRetry() : Np2Error(NP2_E_DEVICE, "internal: guessed growth allowance too small") {}
+    bool grow, rech_cap;
+    GrowRetry(bool g, bool r) : Np2Error(NP2_E_DEVICE, g ? "internal: guessed growth allowance too small" : "internal: recheck region list too small"), grow(g), rech_cap(r) {}
 };
 void check_region_err(np2_ctx *cx, uint32_t e) {
     (void)cx;
@@ -142,7 +145,7 @@ void check_region_err(np2_ctx *cx, uint32_t e) {
     if (e & 64u) throw Np2Error(NP2_E_REFPANIC, "reference would panic: consensus index out of bounds in reupdate");
     if (e & 128u) throw Np2Error(NP2_E_NOMEM, "cartesian product of chained LQ regions is too large");
     if (e & LB_ERR) throw Np2Error(NP2_E_DEVICE, "device-wide scan timed out waiting for a predecessor block");
-    if (e & GROW_ERR) throw GrowRetry();
+    if (e & (GROW_ERR | RECH_CAP_ERR)) throw GrowRetry((e & GROW_ERR) != 0, (e & RECH_CAP_ERR) != 0);
     if (e & LQ_LIST_ERR) throw Np2Error(NP2_E_DEVICE, "internal: more low-quality bases than their list was sized for");
 }
 
@@ -553,22 +556,30 @@ struct CnsDev {
 
 // update_consensus_with_lqseqs on the device; returns the new consensus (in the other buffer).  No read-back: the
 // new length is chained on the device into cx->mlen[version].
-CnsDev splice_gpu(np2_ctx *cx, const CnsDev &in, uint32_t n_reg, uint8_t lable, uint32_t grow_bound, bool to_b,
-                  uint32_t version) {
-    hipStream_t s = cx->stream;
-    EventTimer t(cx, "splice");
-    cx->sp_idx_s.ensure(n_reg + 2);
-    cx->sp_idx_e.ensure(n_reg + 2);
-    cx->ap_g.ensure(n_reg + 2);
-    cx->ap_s.ensure(n_reg + 2);
-    cx->ap_e.ensure(n_reg + 2);
-    cx->ap_delta.ensure(n_reg + 2);
-    cx->ap_shift.ensure(n_reg + 2);
+// the buffers of a splice round: the plan of up to n_slots applied regions, the other half of the consensus double buffer
+CnsDev splice_buffers(np2_ctx *cx, const CnsDev &in, uint32_t n_slots, uint32_t grow_bound, bool to_b, uint32_t version) {
+    cx->sp_idx_s.ensure(n_slots + 2);
+    cx->sp_idx_e.ensure(n_slots + 2);
+    cx->ap_g.ensure(n_slots + 2);
+    cx->ap_s.ensure(n_slots + 2);
+    cx->ap_e.ensure(n_slots + 2);
+    cx->ap_delta.ensure(n_slots + 2);
+    cx->ap_shift.ensure(n_slots + 2);
     cx->mlen.ensure(16);
     const uint32_t out_cap = in.M_cap + grow_bound;
     const size_t cap = (size_t)out_cap + 64;
     uint32_t *opos = to_b ? cx->cns_pos2.ensure(cap) : cx->cns_pos.ensure(cap);
     uint8_t *obase = to_b ? cx->cns_base2.ensure(cap) : cx->cns_base.ensure(cap);
+    return CnsDev{opos, obase, cx->mlen.p + version, out_cap};
+}
+CnsDev splice_gpu(np2_ctx *cx, const CnsDev &in, uint32_t n_reg, uint8_t lable, uint32_t grow_bound, bool to_b,
+                  uint32_t version) {
+    hipStream_t s = cx->stream;
+    EventTimer t(cx, "splice");
+    const CnsDev out = splice_buffers(cx, in, n_reg, grow_bound, to_b, version);
+    uint32_t *const opos = out.pos;
+    uint8_t *const obase = out.base;
+    const uint32_t out_cap = out.M_cap;
     // per-round counters (stuck, n_ap) live behind the posted scalar block; run_diff zeroes them once per contig
     uint32_t *const stuck_p = cx->scal.p + S_COUNT + 2 * version, *const nap_p = stuck_p + 1;
     launch_splice_find(s, in.pos, in.M_p, cx->lq_start.p, cx->lq_end.p, cx->reg_lable.p, lable, n_reg, cx->sp_idx_s.p,
@@ -580,7 +591,7 @@ CnsDev splice_gpu(np2_ctx *cx, const CnsDev &in, uint32_t n_reg, uint8_t lable, 
     launch_splice_write(s, in.pos, in.base, in.M_p, in.M_cap, cx->ap_g.p, cx->ap_s.p, cx->ap_e.p, cx->ap_delta.p,
                         cx->ap_shift.p, nap_p, n_reg, cx->lq_start.p, cx->seed_cand.p, cx->cand_seq_off.p,
                         cx->cand_seq.p, opos, obase);
-    return CnsDev{opos, obase, cx->mlen.p + version, out_cap};
+    return out;
 }
 
 Cns fetch_cns_dev(np2_ctx *cx, const CnsDev &c) { // trace only
@@ -591,7 +602,54 @@ Cns fetch_cns_dev(np2_ctx *cx, const CnsDev &c) { // trace only
     return r;
 }
 
-// reupdate_consensus_with_lqseqs for one yak table, on the device
+// The recheck rounds of a final pass from the list of its RECH regions (np2_regions.hip: k_rech_prepare): may this
+// contig take it?  Decided from what the host knows without a read-back; every contig that takes it issues the same
+// five kernels per table, so the batch driver merges them.
+bool rech_by_list(const np2_ctx *cx, uint32_t n_reg) {
+    return !cx->trace && !cx->hooks.rech_general && n_reg <= RL_NREG_MAX;
+}
+uint32_t rech_list_cap(const np2_ctx *cx) { return std::min(cx->hooks.rech_cap_list, RL_CAP_LIST); }
+// the list round y reads / the one it leaves for round y + 1, and their counts
+uint32_t *rech_list_of(np2_ctx *cx, size_t y) { return cx->rl_list.p + (y & 1) * RL_CAP_LIST; }
+uint32_t *rech_list_cnt(np2_ctx *cx, size_t y) { return cx->scal.p + S_RL + (y & 1); }
+
+CnsDev recheck_list_gpu(np2_ctx *cx, const CnsDev &in, const PassCounts &pc, int yak_idx, uint16_t min_kmer_count,
+                        bool first_yak, bool last_yak, bool to_b, uint32_t version) {
+    hipStream_t s = cx->stream;
+    EventTimer t(cx, "recheck");
+    const uint32_t ksize = cx->yaks[yak_idx].k;
+    const uint32_t cap_jobs = std::min(cx->hooks.rech_cap_jobs, RL_CAP_JOBS), cap_blob = std::min(cx->hooks.rech_cap_blob, RL_CAP_BLOB);
+    cx->rech.ensure(RL_CAP_LIST + 2);
+    cx->rech_groups.ensure((size_t)(RL_CAP_LIST + 2) * rech_group_bytes());
+    cx->rech_groups_tmp.ensure((size_t)(RL_CAP_LIST + 2) * rech_group_bytes());
+    cx->rech_joboff.ensure(RL_CAP_LIST + 2);
+    cx->rl_blob_off.ensure(RL_CAP_LIST + 2);
+    cx->rl_glen.ensure(RL_CAP_LIST + 2);
+    cx->rl_job_ol.ensure(RL_CAP_JOBS + 2);
+    cx->sstr.ensure((size_t)RL_CAP_BLOB + 64);
+    cx->sscore.ensure(RL_CAP_JOBS + 2);
+    const CnsDev out = splice_buffers(cx, in, std::max(pc.n_reg, RL_CAP_LIST), pc.grow, to_b, version);
+    uint32_t *const st = cx->scal.p + S_RL + 2, *const nap_p = cx->scal.p + S_COUNT + 2 * version + 1;
+    const RechList rl{rech_list_of(cx, (size_t)yak_idx), rech_list_cnt(cx, (size_t)yak_idx), rech_list_of(cx, (size_t)yak_idx + 1),
+                      rech_list_cnt(cx, (size_t)yak_idx + 1), st, cx->rech.p, cx->sp_idx_s.p, cx->sp_idx_e.p, cx->rech_groups.p, cx->rech_groups_tmp.p,
+                      cx->rech_joboff.p, cx->rl_blob_off.p, cx->rl_glen.p, cx->rl_job_ol.p, cx->sstr.p,
+                      rech_list_cap(cx), cap_jobs, cap_blob};
+    launch_rech_prepare(s, rl, in.pos, in.base, in.M_p, cx->lq_start.p, cx->lq_end.p, cx->keep_n.p, ksize, cx->reg_maxlen.p,
+                        cx->cand_off.p, cx->keep_list.p, cx->cand_seq_off.p, cx->cand_seq.p, cx->scal.p + S_ERR);
+    launch_score_jobs(s, cx->yaks[yak_idx].dev(), cx->sstr.p, cx->rl_job_ol.p, st + RL_NJOBS, min_kmer_count,
+                      cx->sscore.p);
+    launch_rech_finish(s, rl, cx->sscore.p, cx->keep_ks.p, cx->cand_off.p, cx->keep_n.p, cx->keep_list.p, cx->cand_order.p,
+                       first_yak, last_yak, cx->reg_lable.p, cx->seed_cand.p, in.pos, in.M_p, cx->lq_start.p,
+                       cx->cand_seq_off.p, cx->ap_g.p, cx->ap_s.p, cx->ap_e.p, cx->ap_delta.p, cx->ap_shift.p, nap_p, cx->mlen.p + version,
+                       out.M_cap, cx->scal.p + S_ERR);
+    launch_splice_write(s, in.pos, in.base, in.M_p, in.M_cap, cx->ap_g.p, cx->ap_s.p, cx->ap_e.p, cx->ap_delta.p,
+                        cx->ap_shift.p, nap_p, RL_CAP_LIST, cx->lq_start.p, cx->seed_cand.p, cx->cand_seq_off.p,
+                        cx->cand_seq.p, out.pos, out.base);
+    cx->timing.host.push_back({"rech_list", 1.0f}); // (a count, read through np2_last_timings by the tests)
+    return out;
+}
+
+// reupdate_consensus_with_lqseqs for one yak table, on the device: the general kernels, over all regions
 CnsDev recheck_gpu(np2_ctx *cx, const CnsDev &in, const PassCounts &pc, int yak_idx, uint16_t min_kmer_count,
                    bool first_yak, bool to_b, uint32_t version) {
     hipStream_t s = cx->stream;
@@ -619,6 +677,9 @@ CnsDev recheck_gpu(np2_ctx *cx, const CnsDev &in, const PassCounts &pc, int yak_
         n_rech = sc[S_NRECH];
         n_groups = sc[S_NGROUPS];
         n_jobs = sc[S_M0];
+        if (cx->hooks.rech_log)
+            fprintf(stderr, "np2 recheck, table %d: %u regions, %u RECH, %u groups, %u jobs, %llu string bytes at most\n", yak_idx, n_reg,
+                    n_rech, n_groups, n_jobs, (unsigned long long)blob_bound);
     }
     if (n_rech) {
         RechPtrs rp{cx->rech_groups.p, cx->rech_joboff.p, cx->rech.p, cx->cand_off.p, cx->keep_list.p,
@@ -1357,7 +1418,7 @@ void run_apply_losers(PolishRun &r, const std::vector<uint32_t> &losers) {
     ++r.pass;
 }
 
-void run_final_pass(PolishRun &r, ResultOut &result, bool exact_grow = false) {
+void run_final_pass(PolishRun &r, ResultOut &result, bool exact_grow = false, bool rech_general = false) {
     np2_ctx *cx = r.cx;
     np2_contig *c = r.c;
     hipStream_t s = cx->stream;
@@ -1390,13 +1451,20 @@ void run_final_pass(PolishRun &r, ResultOut &result, bool exact_grow = false) {
             pc.resolve(fetch_scal(cx));
         }
     }
+    // the recheck rounds go by the list of the RECH regions, which k_seed writes, unless the contig is too large for it, the
+    // stage traces want the per-stage tables, or the list overflowed in this pass's first attempt
+    const bool by_list = !rech_general && !cx->yaks.empty() && rech_by_list(cx, n_reg);
     try {
         cx->keep_list.ensure((size_t)pc.NC_cap + 2);
         cx->keep_ks.ensure((size_t)pc.NC_cap + 2);
+        if (by_list) cx->rl_list.ensure(2 * (size_t)RL_CAP_LIST);
         {
             EventTimer t(cx, "seed");
+            // (the first list's count is zero here: run_diff cleared it with the scalar block, k_rech_finish and the retry below
+            // leave it cleared)
             launch_seed(s, rt, r.o.max_indel_len, cx->reg_lable.p, cx->seed_cand.p, cx->keep_n.p, cx->keep_list.p,
-                        cx->keep_ks.p, cx->scal.p + S_ERR);
+                        cx->keep_ks.p, cx->scal.p + S_ERR, by_list ? rech_list_of(cx, 0) : nullptr,
+                        by_list ? rech_list_cnt(cx, 0) : nullptr, rech_list_cap(cx));
         }
         if (cx->trace) check_region_err(cx, d2h(cx, cx->scal.p + S_ERR, 1)[0]);
         trace_region_tables(cx, (int)r.pass, "seed", pc, true);
@@ -1407,18 +1475,22 @@ void run_final_pass(PolishRun &r, ResultOut &result, bool exact_grow = false) {
         to_b = !to_b;
         if (cx->trace) trace_cns(cx, (int)r.pass, "cns_succ", fetch_cns_dev(cx, cur));
         for (size_t y = 0; y < cx->yaks.size(); ++y) {
-            cur = recheck_gpu(cx, cur, pc, (int)y, r.o.min_kmer_count, y == 0, to_b, version++);
+            cur = by_list ? recheck_list_gpu(cx, cur, pc, (int)y, r.o.min_kmer_count, y == 0, y + 1 == cx->yaks.size(), to_b, version++)
+                          : recheck_gpu(cx, cur, pc, (int)y, r.o.min_kmer_count, y == 0, to_b, version++);
             to_b = !to_b;
             trace_region_tables(cx, (int)r.pass, "rech" + std::to_string(y), pc, true);
             if (cx->trace) trace_cns(cx, (int)r.pass, "cns_rech" + std::to_string(y), fetch_cns_dev(cx, cur));
         }
         fetch_result(cx, cur.pos, cur.base, cur.M_p, cur.M_cap, result, guessed ? r.M + r.grow_prev : r.M + pc.grow);
-    } catch (const GrowRetry &) {
-        if (!guessed) throw;
+    } catch (const GrowRetry &g) {
+        if ((g.grow && !guessed) || (g.rech_cap && !by_list)) throw;
         result.release();
         op_fill(cx, cx->scal.p + S_ERR, 0, 4); // (every other bit of the word would have been reported first)
+        // (the rounds' counters and the region lists' start over with the pass)
+        op_fill(cx, cx->scal.p + S_COUNT, 0, (size_t)(SCAL_TOTAL - S_COUNT) * 4);
+        if (g.rech_cap) cx->timing.host.push_back({"rech_redo", 1.0f}); // (a count, read through np2_last_timings by the tests)
         r.reuse = false;
-        run_final_pass(r, result, true);
+        run_final_pass(r, result, exact_grow || g.grow, rech_general || g.rech_cap);
     }
 }
 

@@ -1489,6 +1489,17 @@ __device__ __forceinline__ void k_score_strings(const uint32_t np2_bid, const ui
     if ((threadIdx.x & 63) == 0) out[w] = sc;
 }
 
+__device__ __forceinline__ void k_score_jobs(const uint32_t np2_bid, const uint32_t np2_nb, YakDev y, const uint8_t *__restrict__ strs, const uint2 *__restrict__ job_ol,
+                                             const uint32_t *__restrict__ n_jobs_p, uint16_t min_count, uint16_t *__restrict__ out) {
+    // the job count lives on the device (a few dozen for a megabase contig): the grid's wavefronts take the jobs in turn
+    const uint32_t n = *n_jobs_p, n_waves = np2_nb * (blockDim.x >> 6);
+    for (uint32_t w = np2_bid * (blockDim.x >> 6) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); w < n; w += n_waves) {
+        const uint2 ol = job_ol[w];
+        const uint16_t sc = wave_score_string(y, strs + ol.x, ol.y, min_count);
+        if ((threadIdx.x & 63) == 0) out[w] = sc;
+    }
+}
+
 // retrieve_kmer_count (main.rs:740-778): len > k -> min over the candidate's own k-mers (rare: one wave
 // each, second kernel), else the pre-hashed first k-mer (one lookup, thread per candidate), else 0
 __device__ __forceinline__ void k_cand_score(const uint32_t np2_bid, const uint32_t np2_nb, YakDev y, const uint32_t *__restrict__ cand_seq_off, const uint64_t *__restrict__ cand_kmer,
@@ -1668,6 +1679,10 @@ void launch_yak_insert_dup(hipStream_t s, const uint64_t *words, const uint64_t 
 void launch_lookup(hipStream_t s, const YakDev &y, const uint64_t *hashes, uint64_t n, uint16_t min_count,
                    uint16_t *out) {
     if (n) NP2_LAUNCH(k_lookup, grid1(n), 256, s, y, hashes, n, min_count, out);
+}
+void launch_score_jobs(hipStream_t s, const YakDev &y, const uint8_t *strs, const uint2 *job_ol, const uint32_t *n_jobs_p,
+                       uint16_t min_count, uint16_t *out) {
+    NP2_LAUNCH(k_score_jobs, dim3(16), 256, s, y, strs, job_ol, n_jobs_p, min_count, out);
 }
 void launch_score_strings(hipStream_t s, const YakDev &y, const uint8_t *strs, const uint64_t *off, uint64_t n,
                           uint16_t min_count, uint16_t *out, bool own_strings) {

@@ -202,6 +202,10 @@ void launch_yak_insert_dup(hipStream_t s, const uint64_t *words, const uint64_t 
 void launch_lookup(hipStream_t s, const YakDev &y, const uint64_t *hashes, uint64_t n, uint16_t min_count, uint16_t *out);
 void launch_score_strings(hipStream_t s, const YakDev &y, const uint8_t *strs, const uint64_t *off, uint64_t n,
                           uint16_t min_count, uint16_t *out, bool own_strings);
+// the same over the library's own strings given as (offset, length) per job, their count on the device (a fixed grid
+// whose wavefronts take the jobs in turn; np2_regions.hip: k_rech_prepare)
+void launch_score_jobs(hipStream_t s, const YakDev &y, const uint8_t *strs, const uint2 *job_ol, const uint32_t *n_jobs_p,
+                       uint16_t min_count, uint16_t *out);
 void launch_cand_score(hipStream_t s, const YakDev &y, const uint32_t *cand_seq_off, const uint8_t *cand_seq,
                        const uint64_t *cand_kmer, const uint32_t *n_cand_p, uint32_t cand_cap, uint16_t min_count,
                        uint16_t *kscore, uint32_t *long_list, uint32_t *n_long);
@@ -343,8 +347,10 @@ void launch_vote_rows_emit(hipStream_t s, const uint32_t *band, const uint32_t *
 void launch_edge_reduce(hipStream_t s, const uint64_t *ekey, const uint32_t *eval, uint32_t n, uint32_t *flag, uint32_t *wout);
 void launch_edge_compact(hipStream_t s, const uint64_t *ekey, const uint32_t *flag, const uint32_t *idx, const uint32_t *wout,
                          uint32_t n, uint64_t *ukey, uint32_t *uw, uint32_t *n_out);
+// rl_cnt != nullptr: every region labelled RECH is appended to rl_list (unordered; entries beyond rl_cap are only counted)
 void launch_seed(hipStream_t s, const RegionTables &rt, int32_t max_indel_len, uint8_t *reg_lable, uint32_t *seed_cand,
-                 uint32_t *keep_n, uint32_t *keep_list, uint16_t *keep_ks, uint32_t *err);
+                 uint32_t *keep_n, uint32_t *keep_list, uint16_t *keep_ks, uint32_t *err, uint32_t *rl_list = nullptr,
+                 uint32_t *rl_cnt = nullptr, uint32_t rl_cap = 0);
 // blocks of the look-back compaction kernels over regions (k_splice_plan, k_rech_list)
 uint32_t region_lb_blocks(uint32_t n_reg);
 void launch_splice_find(hipStream_t s, const uint32_t *cns_pos, const uint32_t *M_p, const uint32_t *lq_start,
@@ -381,6 +387,37 @@ void launch_rech_select(hipStream_t s, const uint32_t *rech, const uint32_t *n_r
                         const uint32_t *cand_off, const uint32_t *keep_n, const uint32_t *keep_list, const uint16_t *keep_ks,
                         const uint32_t *order, bool first_yak, uint8_t *reg_lable, uint32_t *seed_cand);
 void launch_rech_relabel(hipStream_t s, uint8_t *reg_lable, uint32_t n_reg);
+// recheck from a region list (k_rech_prepare / k_rech_finish): what a contig holds per round.  Capacities per contig; the
+// yeast- and E. coli-sized diploid workloads stay below a tenth of them.
+static constexpr uint32_t RL_CAP_LIST = 1024;     // listed regions (and groups)
+static constexpr uint32_t RL_CAP_JOBS = 2048;     // recheck strings
+static constexpr uint32_t RL_CAP_BLOB = 1u << 20; // their bytes, every string in a slot of its group's length bound
+static constexpr uint32_t RL_NREG_MAX = 400000;   // LQ regions from which a contig is left to the general kernels
+enum : uint32_t { RL_N = 0, RL_NGROUPS, RL_NJOBS, RL_OFF, RL_STATE_WORDS }; // st[]: entries, groups, jobs of the round; round switched off
+struct RechList {
+    const uint32_t *list_in; // this round's regions, in no particular order
+    uint32_t *cnt_in;        // their count (may exceed the capacity: the list is incomplete then); cleared by k_rech_finish
+    uint32_t *list_out, *cnt_out; // the next round's
+    uint32_t *st;            // RL_STATE_WORDS words
+    uint32_t *rech;          // the list in left -> right order
+    uint32_t *pos_lo, *pos_ub; // per entry: first consensus index at / behind the region's start, first one past its end
+    void *groups, *tmp_groups;
+    uint32_t *job_off, *blob_off, *glen; // per group: first job, first byte, slot length of its strings
+    uint2 *job_ol;           // per job: offset and length of its string
+    uint8_t *blob;
+    uint32_t cap_list, cap_jobs, cap_blob; // at most the RL_CAP_* (tests lower them)
+};
+void launch_rech_prepare(hipStream_t s, const RechList &a, const uint32_t *cns_pos, const uint8_t *cns_base, const uint32_t *M_p,
+                         const uint32_t *lq_start, const uint32_t *lq_end, const uint32_t *keep_n, uint32_t ksize,
+                         const uint32_t *reg_maxlen, const uint32_t *cand_off, const uint32_t *keep_list,
+                         const uint32_t *seq_off, const uint8_t *seq, uint32_t *err);
+// apply + select + splice plan (as launch_splice_find / launch_splice_plan leave it) + relabel + the next round's list
+void launch_rech_finish(hipStream_t s, const RechList &a, const uint16_t *score, uint16_t *keep_ks, const uint32_t *cand_off,
+                        const uint32_t *keep_n, const uint32_t *keep_list, const uint32_t *order, bool first_yak,
+                        bool last_round, uint8_t *reg_lable, uint32_t *seed_cand, const uint32_t *cns_pos,
+                        const uint32_t *M_in, const uint32_t *lq_start, const uint32_t *seq_off,
+                        uint32_t *ap_g, uint32_t *ap_s, uint32_t *ap_e, int32_t *ap_delta, int32_t *ap_shift_incl,
+                        uint32_t *n_ap, uint32_t *M_out, uint32_t out_cap, uint32_t *err);
 
 // ---- np2_front.hip: BAM record -> packed pileup columnariser ---------------------------------------
 struct FrontOp { // one column-producing CIGAR op (M = X I D), prefix sums precomputed by the host

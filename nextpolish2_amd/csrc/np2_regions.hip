@@ -530,7 +530,8 @@ __device__ __forceinline__ void k_edge_compact(const uint32_t np2_bid, const uin
 __device__ __forceinline__ void k_seed(const uint32_t np2_bid0, const uint32_t np2_nb, RegionTables rt, int32_t max_indel_len,
                                               uint8_t *__restrict__ reg_lable, uint32_t *__restrict__ seed_cand,
                                               uint32_t *__restrict__ keep_n, uint32_t *__restrict__ keep_list,
-                                              uint16_t *__restrict__ keep_ks, uint32_t *__restrict__ err) {
+                                              uint16_t *__restrict__ keep_ks, uint32_t *__restrict__ err,
+                                              uint32_t *__restrict__ rl_list, uint32_t *__restrict__ rl_cnt, uint32_t rl_cap) {
     const uint32_t np2_bid = xcd_order(np2_bid0, np2_nb); // (neighbouring items on one XCD: np2_common.hpp)
     // a wavefront owns two consecutive regions: side by side in its two halves when both have at most 32 candidates
     // (the usual case at 30x), otherwise one after the other over all 64 lanes
@@ -624,6 +625,12 @@ __device__ __forceinline__ void k_seed(const uint32_t np2_bid0, const uint32_t n
             reg_lable[g] = lable;
             seed_cand[g] = c0 + seed;
             keep_n[g] = kn;
+            // the recheck's region list (k_rech_prepare), in no particular order; past its capacity the regions are only
+            // counted: the count tells the list's user that it is incomplete
+            if (rl_cnt && (lable & LB_RECH)) {
+                const uint32_t i = atomicAdd(rl_cnt, 1u);
+                if (i < rl_cap) rl_list[i] = g;
+            }
         }
     }
 }
@@ -656,6 +663,46 @@ __device__ __forceinline__ uint32_t upper_bound_u32(const uint32_t *a, uint32_t 
     return bound16_u32<true>(a, n, v);
 }
 
+// where the positions [st, en] (st <= en) sit in the consensus: lo = first index with pos >= st, ub = first index with pos > en
+__device__ __forceinline__ void cns_span(const uint32_t *__restrict__ cns_pos, uint32_t M, uint32_t st, uint32_t en,
+                                         uint32_t &lo, uint32_t &ub) {
+    lo = lower_bound_u32(cns_pos, M, st);
+    // (the end lies a region's length behind the start: one or two rounds over that stretch instead of six over the
+    // whole consensus, whenever the element that closes the stretch is already past the end)
+    const uint32_t near = (uint32_t)min((uint64_t)M, (uint64_t)lo + (en - st) + 65u);
+    ub = (near == M || cns_pos[near - 1] > en) ? bound16_u32<true>(cns_pos, near, en, lo) : upper_bound_u32(cns_pos, M, en);
+}
+// [s, e): the consensus indices a region that starts at st deletes, from its span; false: its start position no longer
+// exists in the consensus
+__device__ __forceinline__ bool splice_range(const uint32_t *__restrict__ cns_pos, uint32_t M, uint32_t st, uint32_t lo,
+                                             uint32_t ub, uint32_t &s, uint32_t &e) {
+    const bool found = lo < M && cns_pos[lo] == st;
+    s = lo;
+    e = found ? max(lo, ub) : lo;
+    return found;
+}
+__device__ __forceinline__ bool splice_find_region(const uint32_t *__restrict__ cns_pos, uint32_t M, uint32_t st, uint32_t en,
+                                                   uint32_t &s, uint32_t &e) {
+    uint32_t lo, ub;
+    cns_span(cns_pos, M, st, en, lo, ub);
+    return splice_range(cns_pos, M, st, lo, ub, s, e);
+}
+// the end of a splice plan: the new length, unless the round would outgrow the output buffers.  They were sized with a
+// guessed growth allowance then: nothing is spliced (the consensus is copied as it is — that fits), the host sees GROW_ERR
+// and repeats the pass with the exact allowance
+__device__ __forceinline__ void splice_plan_total(uint32_t m_in, uint32_t dsum, uint32_t cnt, uint32_t out_cap,
+                                                  uint32_t *__restrict__ n_ap, uint32_t *__restrict__ M_out,
+                                                  uint32_t *__restrict__ err) {
+    const uint32_t m_out = m_in + dsum;
+    if (m_out > out_cap) {
+        atomicOr(err, GROW_ERR);
+        *n_ap = 0;
+        *M_out = m_in;
+    } else {
+        *n_ap = cnt;
+        *M_out = m_out;
+    }
+}
 // per labelled region: [idx_s, idx_e) to delete; the cursor gets stuck at the leftmost (highest index)
 // labelled region whose start position no longer exists in the consensus
 __device__ __forceinline__ void k_splice_find(const uint32_t np2_bid, const uint32_t np2_nb, const uint32_t *__restrict__ cns_pos, const uint32_t *__restrict__ M_p,
@@ -665,19 +712,9 @@ __device__ __forceinline__ void k_splice_find(const uint32_t np2_bid, const uint
                               uint32_t *__restrict__ stuck) {
     uint32_t g = np2_bid * blockDim.x + threadIdx.x;
     if (g >= n_reg || !(reg_lable[g] & lable)) return;
-    const uint32_t M = *M_p;
-    const uint32_t s = lower_bound_u32(cns_pos, M, lq_start[g]);
-    const bool found = s < M && cns_pos[s] == lq_start[g];
+    uint32_t s, e;
+    const bool found = splice_find_region(cns_pos, *M_p, lq_start[g], lq_end[g], s, e);
     idx_s[g] = s;
-    // (the region's end lies a region's length behind its start: one or two rounds over that stretch instead of six over the
-    // whole consensus, whenever the element that closes the stretch is already past the end)
-    uint32_t e = s;
-    if (found) {
-        const uint32_t en = lq_end[g];
-        const uint32_t near = (uint32_t)min((uint64_t)M, (uint64_t)s + (en - lq_start[g]) + 65u);
-        e = (near == M || cns_pos[near - 1] > en) ? bound16_u32<true>(cns_pos, near, en, s) : upper_bound_u32(cns_pos, M, en);
-        e = max(s, e);
-    }
     idx_e[g] = e;
     if (!found) atomicMax(stuck, g + 1);
 }
@@ -736,20 +773,7 @@ __device__ __forceinline__ void k_splice_plan(const uint32_t np2_bid, const uint
         lo += flag[k];
         ld += (uint32_t)delta[k];
     }
-    if (bid == n_blocks - 1 && threadIdx.x == 0) {
-        const uint32_t m_out = *M_in + pre_d + dsum;
-        if (m_out > out_cap) {
-            // the output buffers were sized with a guessed growth allowance and this round would outgrow them: nothing is
-            // spliced (the consensus is copied as it is — that fits), the host sees GROW_ERR and repeats the pass with the
-            // exact allowance
-            atomicOr(err, GROW_ERR);
-            *n_ap = 0;
-            *M_out = *M_in;
-        } else {
-            *n_ap = pre_c + cnt;
-            *M_out = m_out;
-        }
-    }
+    if (bid == n_blocks - 1 && threadIdx.x == 0) splice_plan_total(*M_in, pre_d + dsum, pre_c + cnt, out_cap, n_ap, M_out, err);
 }
 // copy the bases outside the applied regions to their shifted places.  A block covers SPLICE_SPAN consecutive consensus
 // indices (coalesced, several per thread): the slot search — a latency chain over the applied-region starts — is done once
@@ -903,6 +927,93 @@ struct RechGroup { // one recheck group = 1..6 chained RECH regions
 // the region's own index; k_rech_compact then moves the groups to their slots and leaves the job offsets (exclusive
 // sums of the group / job counts) with a look-back over a few blocks of four regions per thread.  As one kernel the
 // look-back chain ran over every block of the heavy threads (120 us per call on the yeast-sized assembly).
+// (the rules themselves — chain, head, group — are the helpers below: k_rech_prepare builds its groups with them too)
+__device__ __forceinline__ bool rech_chained(const uint32_t *rech, const uint32_t *__restrict__ lq_start,
+                                             const uint32_t *__restrict__ lq_end, uint32_t ksize, uint32_t x) {
+    return lq_start[rech[x]] < lq_end[rech[x - 1]] + ksize;
+}
+// does entry e of the (left -> right) list head a group?
+__device__ __forceinline__ bool rech_is_head(const uint32_t *rech, const uint32_t *__restrict__ lq_start,
+                                             const uint32_t *__restrict__ lq_end, uint32_t ksize, uint32_t e) {
+    uint32_t back = 0, x = e;
+    while (x > 0 && rech_chained(rech, lq_start, lq_end, ksize, x)) {
+        --x;
+        ++back;
+    }
+    return back % 6 == 0;
+}
+// where the listed regions sit in the consensus, for rech_group_build: lo(x) = first index with pos >= the start of entry
+// x, ub(x) = first index with pos > its end.  The general kernels search when asked; k_rech_prepare has searched every
+// entry once (cns_span) and looks the answers up.
+struct RechSearch {
+    const uint32_t *rech, *cns_pos, *lq_start, *lq_end;
+    uint32_t M;
+    __device__ __forceinline__ uint32_t lo(uint32_t x) const { return lower_bound_u32(cns_pos, M, lq_start[rech[x]]); }
+    __device__ __forceinline__ uint32_t ub(uint32_t x) const { return upper_bound_u32(cns_pos, M, lq_end[rech[x]]); }
+};
+struct RechFound {
+    const uint32_t *s_lo, *s_ub;
+    __device__ __forceinline__ uint32_t lo(uint32_t x) const { return s_lo[x]; }
+    __device__ __forceinline__ uint32_t ub(uint32_t x) const { return s_ub[x]; }
+};
+// the group headed by entry e; len_bound: upper bound of the length of each of its recheck strings
+template <class Where>
+__device__ __forceinline__ RechGroup rech_group_build(uint32_t e, uint32_t n_rech, const uint32_t *rech, const Where &where,
+                                                      uint32_t M, const uint32_t *__restrict__ lq_start,
+                                                      const uint32_t *__restrict__ lq_end,
+                                                      const uint32_t *__restrict__ keep_n, uint32_t ksize,
+                                                      const uint32_t *__restrict__ reg_maxlen, uint32_t *__restrict__ err,
+                                                      uint64_t &len_bound) {
+    RechGroup G = {};
+    G.first = e;
+    uint32_t n = 1;
+    while (n < 6 && e + n < n_rech && rech_chained(rech, lq_start, lq_end, ksize, e + n)) ++n;
+    G.n = n;
+    const uint32_t l = ksize - 1;
+    // iter_consensus_extend(toleft): first index with pos >= start; the reference indexes [i-1]
+    const uint32_t i0 = where.lo(e);
+    if (i0 == 0 || i0 >= M) atomicOr(err, 64u);
+    G.el = i0;
+    G.sl = i0 > l ? i0 - l : 0;
+    // iter_consensus_extend(right): last index with pos <= end; the reference indexes [i+1]
+    const uint32_t i1u = where.ub(e + n - 1);
+    if (i1u == 0 || i1u >= M) atomicOr(err, 64u);
+    const uint32_t i1 = i1u ? i1u - 1 : 0;
+    G.sr = i1 + 1;
+    G.er = (i1 + l < M) ? i1 + l + 1 : M;
+    uint64_t jobs = 1;
+#pragma unroll // (static indices keep G in registers; a dynamically indexed G lives in scratch memory)
+    for (uint32_t x = 0; x < 6; ++x) {
+        if (x >= n) break;
+        G.lens[x] = keep_n[rech[e + x]];
+        jobs *= G.lens[x];
+        if (jobs > 0x7FFFFFFFull) {
+            atomicOr(err, 128u);
+            jobs = 0;
+        }
+        if (x + 1 < n) { // iter_consensus_region(s, e): indices with s < pos < e
+            const uint32_t s = lq_end[rech[e + x]], en = lq_start[rech[e + x + 1]];
+            if (s + 1 == en) {
+                G.bs[x] = G.be[x] = 0;
+            } else {
+                G.bs[x] = where.ub(e + x);
+                G.be[x] = where.lo(e + x + 1);
+                if (G.be[x] < G.bs[x]) G.be[x] = G.bs[x];
+            }
+        }
+    }
+    G.njobs = (uint32_t)jobs;
+    // every string of the group: both flanks + per region its longest kept candidate + the stretches in between
+    uint64_t len = (uint64_t)(G.el - G.sl) + (G.er - G.sr);
+#pragma unroll
+    for (uint32_t x = 0; x < 6; ++x) {
+        if (x >= n) break;
+        len += reg_maxlen[rech[e + x]]; // longest candidate of the region (the kept ones are a subset)
+        if (x + 1 < n) len += G.be[x] - G.bs[x];
+    }
+    len_bound = len;
+    return G;
+}
 __device__ __forceinline__ void k_rech_groups(const uint32_t np2_bid, const uint32_t np2_nb, const uint32_t *__restrict__ rech,
                                                      const uint32_t *__restrict__ n_rech_p,
                                                      const uint32_t *__restrict__ cns_pos, const uint32_t *__restrict__ M_p,
@@ -917,68 +1028,13 @@ __device__ __forceinline__ void k_rech_groups(const uint32_t np2_bid, const uint
     unsigned long long bound = 0; // upper bound of the bytes of this group's recheck strings
     const uint32_t e = np2_bid * 256 + threadIdx.x;
     const uint32_t n_rech = *n_rech_p, M = *M_p;
-    auto chained = [&](uint32_t x) { return lq_start[rech[x]] < lq_end[rech[x - 1]] + ksize; };
-    bool head = false;
-    RechGroup G = {};
+    const bool head = e < n_rech && rech_is_head(rech, lq_start, lq_end, ksize, e);
     uint32_t jobs32 = 0;
-    if (e < n_rech) {
-        uint32_t back = 0, x = e;
-        while (x > 0 && chained(x)) {
-            --x;
-            ++back;
-        }
-        head = back % 6 == 0;
-    }
     if (head) {
-        G.first = e;
-        uint32_t n = 1;
-        while (n < 6 && e + n < n_rech && chained(e + n)) ++n;
-        G.n = n;
-        const uint32_t l = ksize - 1;
-        // iter_consensus_extend(toleft): first index with pos >= start; the reference indexes [i-1]
-        const uint32_t p0 = lq_start[rech[e]];
-        const uint32_t i0 = lower_bound_u32(cns_pos, M, p0);
-        if (i0 == 0 || i0 >= M) atomicOr(err, 64u);
-        G.el = i0;
-        G.sl = i0 > l ? i0 - l : 0;
-        // iter_consensus_extend(right): last index with pos <= end; the reference indexes [i+1]
-        const uint32_t p1 = lq_end[rech[e + n - 1]];
-        const uint32_t i1u = upper_bound_u32(cns_pos, M, p1);
-        if (i1u == 0 || i1u >= M) atomicOr(err, 64u);
-        const uint32_t i1 = i1u ? i1u - 1 : 0;
-        G.sr = i1 + 1;
-        G.er = (i1 + l < M) ? i1 + l + 1 : M;
-        uint64_t jobs = 1;
-#pragma unroll // (static indices keep G in registers; a dynamically indexed G lives in scratch memory)
-        for (uint32_t x = 0; x < 6; ++x) {
-            if (x >= n) break;
-            G.lens[x] = keep_n[rech[e + x]];
-            jobs *= G.lens[x];
-            if (jobs > 0x7FFFFFFFull) {
-                atomicOr(err, 128u);
-                jobs = 0;
-            }
-            if (x + 1 < n) { // iter_consensus_region(s, e): indices with s < pos < e
-                const uint32_t s = lq_end[rech[e + x]], en = lq_start[rech[e + x + 1]];
-                if (s + 1 == en) {
-                    G.bs[x] = G.be[x] = 0;
-                } else {
-                    G.bs[x] = upper_bound_u32(cns_pos, M, s);
-                    G.be[x] = lower_bound_u32(cns_pos, M, en);
-                    if (G.be[x] < G.bs[x]) G.be[x] = G.bs[x];
-                }
-            }
-        }
-        jobs32 = (uint32_t)jobs;
-        G.njobs = jobs32;
-        // every string of the group: both flanks + per region its longest kept candidate + the stretches in between
-        uint64_t len = (uint64_t)(G.el - G.sl) + (G.er - G.sr);
-#pragma unroll
-        for (uint32_t x = 0; x < 6; ++x) {
-            if (x >= n) break;
-            len += reg_maxlen[rech[e + x]]; // longest candidate of the region (the kept ones are a subset)
-            if (x + 1 < n) len += G.be[x] - G.bs[x];
-        }
+        uint64_t len;
+        const RechGroup G = rech_group_build(e, n_rech, rech, RechSearch{rech, cns_pos, lq_start, lq_end, M}, M, lq_start, lq_end,
+                                             keep_n, ksize, reg_maxlen, err, len);
+        jobs32 = G.njobs;
         bound = (unsigned long long)jobs32 * len;
         tmp_groups[e] = G;
     }
@@ -1050,33 +1106,38 @@ __device__ __forceinline__ uint32_t job_group(const RechCtx &cx, uint32_t job) {
     }
     return lo - 1;
 }
-// length (WRITE = false) or bytes (WRITE = true) of one recheck string:
+// length (WRITE = false) or bytes (WRITE = true) of one recheck string, job `rem` of group gi:
 // left flank + seq_0 [+ between_0 + seq_1 ...] + right flank  (main.rs:1141-1176, 1224-1230)
-template <bool WRITE> __device__ uint32_t rech_string(const RechCtx &cx, uint32_t job, uint8_t *__restrict__ out) {
-    const uint32_t gi = job_group(cx, job);
+// (nl lanes may share a string: lane `lane` writes every nl-th byte of each piece; all of them get the length)
+template <bool WRITE>
+__device__ uint32_t rech_group_string(const RechCtx &cx, uint32_t gi, uint32_t rem, uint8_t *__restrict__ out, uint32_t lane = 0,
+                                      uint32_t nl = 1) {
     const RechGroup &G = cx.groups[gi];
-    uint32_t rem = job - cx.job_off[gi];
     uint32_t pick[6];
     for (uint32_t x = G.n; x-- > 0;) { // last iterator fastest
         pick[x] = rem % G.lens[x];
         rem /= G.lens[x];
     }
     uint32_t o = 0;
-    for (uint32_t i = G.sl; i < G.el; ++i, ++o)
-        if (WRITE) out[o] = cx.cns_base[i];
+    auto piece = [&](const uint8_t *__restrict__ src, uint32_t n) {
+        if (WRITE)
+            for (uint32_t t = lane; t < n; t += nl) out[o + t] = src[t];
+        o += n;
+    };
+    piece(cx.cns_base + G.sl, G.el - G.sl);
     for (uint32_t x = 0; x < G.n; ++x) {
         const uint32_t g = cx.rech[G.first + x];
         const uint32_t c = cx.keep_list[cx.cand_off[g] + pick[x]];
-        const uint32_t so = cx.seq_off[c], len = cx.seq_off[c + 1] - so;
-        for (uint32_t t = 0; t < len; ++t, ++o)
-            if (WRITE) out[o] = cx.seq[so + t];
-        if (x + 1 < G.n)
-            for (uint32_t i = G.bs[x]; i < G.be[x]; ++i, ++o)
-                if (WRITE) out[o] = cx.cns_base[i];
+        const uint32_t so = cx.seq_off[c];
+        piece(cx.seq + so, cx.seq_off[c + 1] - so);
+        if (x + 1 < G.n) piece(cx.cns_base + G.bs[x], G.be[x] - G.bs[x]);
     }
-    for (uint32_t i = G.sr; i < G.er; ++i, ++o)
-        if (WRITE) out[o] = cx.cns_base[i];
+    piece(cx.cns_base + G.sr, G.er - G.sr);
     return o;
+}
+template <bool WRITE> __device__ uint32_t rech_string(const RechCtx &cx, uint32_t job, uint8_t *__restrict__ out) {
+    const uint32_t gi = job_group(cx, job);
+    return rech_group_string<WRITE>(cx, gi, job - cx.job_off[gi], out);
 }
 __device__ __forceinline__ void k_rech_job_len(const uint32_t np2_bid, const uint32_t np2_nb, RechCtx cx, uint32_t n_jobs, uint32_t *__restrict__ len) {
     uint32_t j = np2_bid * blockDim.x + threadIdx.x;
@@ -1094,9 +1155,8 @@ __device__ __forceinline__ void k_u32_to_u64_off(const uint32_t np2_bid, const u
 
 // apply the scores: single regions take their job's score; chains zero everything, then every product with
 // score > 0 stamps its members, later products overwriting earlier ones (main.rs:1358-1366)
-__device__ __forceinline__ void k_rech_apply(const uint32_t np2_bid, const uint32_t np2_nb, RechCtx cx, const uint16_t *__restrict__ score, uint16_t *__restrict__ keep_ks) {
-    uint32_t gi = np2_bid * blockDim.x + threadIdx.x;
-    if (gi >= cx.n_groups) return;
+__device__ __forceinline__ void rech_apply_group(const RechCtx &cx, uint32_t gi, const uint16_t *__restrict__ score,
+                                                 uint16_t *__restrict__ keep_ks) {
     const RechGroup &G = cx.groups[gi];
     const uint32_t j0 = cx.job_off[gi];
     if (G.n == 1) {
@@ -1119,16 +1179,18 @@ __device__ __forceinline__ void k_rech_apply(const uint32_t np2_bid, const uint3
         }
     }
 }
+__device__ __forceinline__ void k_rech_apply(const uint32_t np2_bid, const uint32_t np2_nb, RechCtx cx, const uint16_t *__restrict__ score, uint16_t *__restrict__ keep_ks) {
+    uint32_t gi = np2_bid * blockDim.x + threadIdx.x;
+    if (gi < cx.n_groups) rech_apply_group(cx, gi, score, keep_ks);
+}
 
 // selection per RECH region (main.rs:1371-1406)
-__device__ __forceinline__ void k_rech_select(const uint32_t np2_bid, const uint32_t np2_nb, const uint32_t *__restrict__ rech, const uint32_t *__restrict__ n_rech_p,
-                              const uint32_t *__restrict__ cand_off, const uint32_t *__restrict__ keep_n,
-                              const uint32_t *__restrict__ keep_list, const uint16_t *__restrict__ keep_ks,
-                              const uint32_t *__restrict__ order, uint32_t first_yak, uint8_t *__restrict__ reg_lable,
-                              uint32_t *__restrict__ seed_cand) {
-    uint32_t e = np2_bid * blockDim.x + threadIdx.x;
-    if (e >= *n_rech_p) return;
-    const uint32_t g = rech[e], c0 = cand_off[g], n = keep_n[g];
+__device__ __forceinline__ void rech_select_region(uint32_t g, const uint32_t *__restrict__ cand_off,
+                                                   const uint32_t *__restrict__ keep_n, const uint32_t *__restrict__ keep_list,
+                                                   const uint16_t *__restrict__ keep_ks, const uint32_t *__restrict__ order,
+                                                   uint32_t first_yak, uint8_t *__restrict__ reg_lable,
+                                                   uint32_t *__restrict__ seed_cand) {
+    const uint32_t c0 = cand_off[g], n = keep_n[g];
     uint32_t c = 0, valid = 0;
     for (uint32_t p = 0; p < n; ++p)
         if (keep_ks[c0 + p] != 0) {
@@ -1148,12 +1210,239 @@ __device__ __forceinline__ void k_rech_select(const uint32_t np2_bid, const uint
         seed_cand[g] = keep_list[c0 + i];
     }
 }
-__device__ __forceinline__ void k_rech_relabel(const uint32_t np2_bid, const uint32_t np2_nb, uint8_t *__restrict__ reg_lable, uint32_t n_reg) { // main.rs:1411-1417
+__device__ __forceinline__ void k_rech_select(const uint32_t np2_bid, const uint32_t np2_nb, const uint32_t *__restrict__ rech, const uint32_t *__restrict__ n_rech_p,
+                              const uint32_t *__restrict__ cand_off, const uint32_t *__restrict__ keep_n,
+                              const uint32_t *__restrict__ keep_list, const uint16_t *__restrict__ keep_ks,
+                              const uint32_t *__restrict__ order, uint32_t first_yak, uint8_t *__restrict__ reg_lable,
+                              uint32_t *__restrict__ seed_cand) {
+    uint32_t e = np2_bid * blockDim.x + threadIdx.x;
+    if (e >= *n_rech_p) return;
+    rech_select_region(rech[e], cand_off, keep_n, keep_list, keep_ks, order, first_yak, reg_lable, seed_cand);
+}
+// the label a RECH region leaves its round with (main.rs:1411-1417): still RECH when more than one candidate stayed valid
+__device__ __forceinline__ uint8_t rech_relabel(uint8_t l) {
+    return (l & LB_TEMP) ? (uint8_t)(l ^ LB_TEMP) : (uint8_t)(l ^ LB_RECH);
+}
+__device__ __forceinline__ void k_rech_relabel(const uint32_t np2_bid, const uint32_t np2_nb, uint8_t *__restrict__ reg_lable, uint32_t n_reg) {
     uint32_t g = np2_bid * blockDim.x + threadIdx.x;
     if (g >= n_reg) return;
     const uint8_t l = reg_lable[g];
-    if (!(l & LB_RECH)) return;
-    reg_lable[g] = (l & LB_TEMP) ? (uint8_t)(l ^ LB_TEMP) : (uint8_t)(l ^ LB_RECH);
+    if (l & LB_RECH) reg_lable[g] = rech_relabel(l);
+}
+
+// ---- recheck from a region list ----------------------------------------------------------------------------------------
+// A HiFi contig has a few dozen RECH regions per megabase among its tens of thousands of LQ regions, so the final pass
+// keeps them as a list: k_seed appends a region when it labels it, one workgroup per contig prepares a round from the
+// list (k_rech_prepare: groups, job offsets, strings), the jobs are scored (k_score_jobs), and one workgroup finishes the
+// round (k_rech_finish: apply, select, splice plan, relabel, the next table's list).  Nothing is read back: launches and
+// buffers are sized by the capacities in RechList, a list, job count or string size beyond them raises RECH_CAP_ERR,
+// the round splices nothing and the host repeats the final pass with the kernels above.  Both kernels leave everything
+// alone when the error word is already set (the first error is the one reported), except that the round's splice becomes
+// a plain copy.
+static constexpr uint32_t RL_ITEMS = 4; // list entries per thread: 256 threads hold RL_CAP_LIST entries
+static_assert(RL_CAP_LIST == 256 * RL_ITEMS, "a thread of the list kernels owns RL_ITEMS consecutive entries");
+static_assert((uint64_t)RL_CAP_LIST * (RL_CAP_JOBS + 1) < (1ull << 32) && (uint64_t)RL_CAP_LIST * (RL_CAP_BLOB + 1) < (1ull << 32),
+              "clamped per-group sums stay inside 32 bits");
+
+__device__ __forceinline__ RechCtx rl_ctx(const RechList &a, const uint32_t *rech, const uint32_t *__restrict__ cand_off,
+                                          const uint32_t *__restrict__ keep_list, const uint32_t *__restrict__ seq_off,
+                                          const uint8_t *__restrict__ seq, const uint8_t *__restrict__ cns_base, uint32_t n_groups) {
+    return RechCtx{(const RechGroup *)a.groups, a.job_off, rech, cand_off, keep_list, seq_off, seq, cns_base, n_groups};
+}
+// this round does nothing: no job, and k_rech_finish makes its splice a plain copy
+__device__ __forceinline__ void rl_round_off(const RechList &a, uint32_t cap_err, uint32_t *__restrict__ err) {
+    a.st[RL_N] = 0, a.st[RL_NGROUPS] = 0, a.st[RL_NJOBS] = 0, a.st[RL_OFF] = 1;
+    if (cap_err) atomicOr(err, RECH_CAP_ERR);
+}
+
+__device__ __forceinline__ void k_rech_prepare(const uint32_t np2_bid, const uint32_t np2_nb, RechList a,
+                                               const uint32_t *__restrict__ cns_pos, const uint8_t *__restrict__ cns_base,
+                                               const uint32_t *__restrict__ M_p, const uint32_t *__restrict__ lq_start,
+                                               const uint32_t *__restrict__ lq_end, const uint32_t *__restrict__ keep_n,
+                                               uint32_t ksize, const uint32_t *__restrict__ reg_maxlen,
+                                               const uint32_t *__restrict__ cand_off, const uint32_t *__restrict__ keep_list,
+                                               const uint32_t *__restrict__ seq_off, const uint8_t *__restrict__ seq,
+                                               uint32_t *__restrict__ err) {
+    __shared__ uint32_t s_raw[RL_CAP_LIST], s_rech[RL_CAP_LIST], s_lo[RL_CAP_LIST], s_ub[RL_CAP_LIST], sh[8], s_hdr[2];
+    const uint32_t tid = threadIdx.x;
+    if (tid == 0) s_hdr[0] = *err, s_hdr[1] = *a.cnt_in;
+    __syncthreads();
+    const uint32_t n = s_hdr[1], cap_list = min(a.cap_list, RL_CAP_LIST);
+    if (s_hdr[0] != 0 || n > cap_list) { // (uniform)
+        if (tid == 0) rl_round_off(a, s_hdr[0] == 0, err);
+        return;
+    }
+    // the list in left -> right order (descending region index; every region is listed once): rank by counting
+    for (uint32_t i = tid; i < n; i += 256) s_raw[i] = a.list_in[i];
+    __syncthreads();
+    for (uint32_t i = tid; i < n; i += 256) {
+        const uint32_t v = s_raw[i];
+        uint32_t rank = 0;
+        for (uint32_t j = 0; j < n; ++j) rank += s_raw[j] > v ? 1u : 0u;
+        s_rech[rank] = v;
+        a.rech[rank] = v;
+    }
+    __syncthreads();
+    const uint32_t M = *M_p;
+    // where every listed region sits in the consensus: the one search per region of the round — the groups' flanks and
+    // in-between stretches and k_rech_finish's splice ranges are all read off these (searches in the multi-megabyte
+    // consensus are chains of dependent loads; one after the other they were most of this kernel's time)
+    for (uint32_t i = tid; i < n; i += 256) {
+        const uint32_t g = s_rech[i];
+        uint32_t lo, ub;
+        cns_span(cns_pos, M, lq_start[g], lq_end[g], lo, ub);
+        s_lo[i] = lo, s_ub[i] = ub;
+        a.pos_lo[i] = lo, a.pos_ub[i] = ub;
+    }
+    __syncthreads();
+    // group heads among this thread's entries; a head's group goes to the scratch slot under its own index first
+    RechGroup *const groups = (RechGroup *)a.groups, *const tmp_groups = (RechGroup *)a.tmp_groups;
+    uint32_t head[RL_ITEMS], jobs[RL_ITEMS], bytes[RL_ITEMS], glen[RL_ITEMS], hs = 0, js = 0, bsum = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < RL_ITEMS; ++k) {
+        const uint32_t e = tid * RL_ITEMS + k;
+        head[k] = (e < n && rech_is_head(s_rech, lq_start, lq_end, ksize, e)) ? 1u : 0u;
+        jobs[k] = 0, bytes[k] = 0, glen[k] = 0;
+        if (head[k]) {
+            uint64_t len;
+            const RechGroup G = rech_group_build(e, n, s_rech, RechFound{s_lo, s_ub}, M, lq_start, lq_end, keep_n, ksize, reg_maxlen, err, len);
+            tmp_groups[e] = G;
+            // (clamped: a sum of clamped terms still exceeds its capacity when one of them does)
+            jobs[k] = min(G.njobs, a.cap_jobs + 1u);
+            glen[k] = (uint32_t)min(len, (uint64_t)a.cap_blob + 1u);
+            bytes[k] = (uint32_t)min((uint64_t)G.njobs * len, (uint64_t)a.cap_blob + 1u);
+        }
+        hs += head[k], js += jobs[k], bsum += bytes[k];
+    }
+    uint32_t nh, nj, nb;
+    uint32_t lh = block_excl_scan<OpAdd, 4>(hs, sh, nh);
+    uint32_t lj = block_excl_scan<OpAdd, 4>(js, sh, nj);
+    uint32_t lbt = block_excl_scan<OpAdd, 4>(bsum, sh, nb);
+    if (nj > min(a.cap_jobs, RL_CAP_JOBS) || nb > min(a.cap_blob, RL_CAP_BLOB)) { // (uniform)
+        if (tid == 0) rl_round_off(a, 1u, err);
+        return;
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < RL_ITEMS; ++k) {
+        if (!head[k]) continue;
+        groups[lh] = tmp_groups[tid * RL_ITEMS + k];
+        a.job_off[lh] = lj;
+        a.blob_off[lh] = lbt;
+        a.glen[lh] = glen[k];
+        ++lh, lj += jobs[k], lbt += bytes[k];
+    }
+    if (tid == 0) {
+        a.job_off[nh] = nj;
+        a.st[RL_N] = n, a.st[RL_NGROUPS] = nh, a.st[RL_NJOBS] = nj, a.st[RL_OFF] = 0;
+    }
+    __threadfence_block();
+    __syncthreads();
+    // the strings, each in a slot of its group's bound: job j of group gi at blob_off[gi] + j_local * glen[gi]
+    const RechCtx cx = rl_ctx(a, s_rech, cand_off, keep_list, seq_off, seq, cns_base, nh);
+    // (sixteen lanes share a string)
+    for (uint32_t j = tid >> 4; j < nj; j += 16) {
+        const uint32_t gi = job_group(cx, j), rem = j - a.job_off[gi];
+        const uint32_t off = a.blob_off[gi] + rem * a.glen[gi];
+        uint32_t len = rech_group_string<false>(cx, gi, rem, nullptr);
+        if (len <= a.glen[gi]) {
+            rech_group_string<true>(cx, gi, rem, a.blob + off, tid & 15u, 16u);
+        } else { // (a string longer than its group's bound: never by construction; its neighbours stay whole)
+            if ((tid & 15u) == 0) atomicOr(err, RECH_CAP_ERR);
+            len = 0;
+        }
+        if ((tid & 15u) == 0) a.job_ol[j] = make_uint2(off, len);
+    }
+}
+
+__device__ __forceinline__ void k_rech_finish(const uint32_t np2_bid, const uint32_t np2_nb, RechList a,
+                                              const uint16_t *__restrict__ score, uint16_t *__restrict__ keep_ks,
+                                              const uint32_t *__restrict__ cand_off, const uint32_t *__restrict__ keep_n,
+                                              const uint32_t *__restrict__ keep_list, const uint32_t *__restrict__ order,
+                                              uint32_t first_yak, uint32_t last_round, uint8_t *__restrict__ reg_lable,
+                                              uint32_t *__restrict__ seed_cand, const uint32_t *__restrict__ cns_pos,
+                                              const uint32_t *__restrict__ M_in, const uint32_t *__restrict__ lq_start,
+                                              const uint32_t *__restrict__ seq_off,
+                                              uint32_t *__restrict__ ap_g, uint32_t *__restrict__ ap_s,
+                                              uint32_t *__restrict__ ap_e, int32_t *__restrict__ ap_delta,
+                                              int32_t *__restrict__ ap_shift_incl, uint32_t *__restrict__ n_ap,
+                                              uint32_t *__restrict__ M_out, uint32_t out_cap, uint32_t *__restrict__ err) {
+    __shared__ uint32_t sh[8], s_hdr[4], s_stuck;
+    const uint32_t tid = threadIdx.x;
+    if (tid == 0) s_hdr[0] = *err, s_hdr[1] = a.st[RL_N], s_hdr[2] = a.st[RL_NGROUPS], s_hdr[3] = a.st[RL_OFF], s_stuck = 0;
+    __syncthreads();
+    if (s_hdr[0] != 0 || s_hdr[3] != 0) { // (uniform) an error, here or earlier: the round's splice is a plain copy
+        if (tid == 0) *n_ap = 0, *M_out = *M_in, *a.cnt_in = 0, *a.cnt_out = 0;
+        return;
+    }
+    const uint32_t n = s_hdr[1], n_groups = s_hdr[2], M = *M_in;
+    const RechCtx cx = rl_ctx(a, a.rech, cand_off, keep_list, seq_off, nullptr, nullptr, n_groups);
+    for (uint32_t gi = tid; gi < n_groups; gi += 256) rech_apply_group(cx, gi, score, keep_ks);
+    __threadfence_block();
+    __syncthreads();
+    // per listed region: the selection, then its range in the consensus from the span k_rech_prepare found (k_splice_find:
+    // the cursor gets stuck at the leftmost region whose start no longer exists)
+    uint32_t g[RL_ITEMS], s[RL_ITEMS], e[RL_ITEMS];
+#pragma unroll
+    for (uint32_t k = 0; k < RL_ITEMS; ++k) {
+        const uint32_t x = tid * RL_ITEMS + k;
+        g[k] = 0, s[k] = 0, e[k] = 0;
+        if (x >= n) continue;
+        g[k] = a.rech[x];
+        rech_select_region(g[k], cand_off, keep_n, keep_list, keep_ks, order, first_yak, reg_lable, seed_cand);
+        if (!splice_range(cns_pos, M, lq_start[g[k]], a.pos_lo[x], a.pos_ub[x], s[k], e[k])) atomicMax(&s_stuck, g[k] + 1);
+    }
+    __syncthreads();
+    // the splice plan over the list (k_splice_plan: applied slots in left -> right order)
+    const uint32_t stuck = s_stuck;
+    uint32_t flag[RL_ITEMS], fsum = 0;
+    int32_t delta[RL_ITEMS], dsum_t = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < RL_ITEMS; ++k) {
+        flag[k] = (tid * RL_ITEMS + k < n && g[k] + 1 > stuck) ? 1u : 0u;
+        delta[k] = 0;
+        if (flag[k]) {
+            const uint32_t c = seed_cand[g[k]];
+            delta[k] = (int32_t)(seq_off[c + 1] - seq_off[c]) - (int32_t)(e[k] - s[k]);
+        }
+        fsum += flag[k], dsum_t += delta[k];
+    }
+    uint32_t cnt, dsum;
+    uint32_t lo = block_excl_scan<OpAdd, 4>(fsum, sh, cnt);
+    uint32_t ld = block_excl_scan<OpAdd, 4>((uint32_t)dsum_t, sh, dsum);
+#pragma unroll
+    for (uint32_t k = 0; k < RL_ITEMS; ++k) {
+        if (flag[k]) {
+            ap_g[lo] = g[k];
+            ap_s[lo] = s[k];
+            ap_e[lo] = e[k];
+            ap_delta[lo] = delta[k];
+            ap_shift_incl[lo] = (int32_t)ld + delta[k];
+        }
+        lo += flag[k];
+        ld += (uint32_t)delta[k];
+    }
+    if (tid == 0) splice_plan_total(M, dsum, cnt, out_cap, n_ap, M_out, err);
+    // relabel; the regions that stay RECH are the next table's list (an ordered subset of this one)
+    uint32_t keep[RL_ITEMS], ksum = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < RL_ITEMS; ++k) {
+        keep[k] = 0;
+        if (tid * RL_ITEMS + k < n) {
+            const uint8_t l = rech_relabel(reg_lable[g[k]]);
+            reg_lable[g[k]] = l;
+            keep[k] = (l & LB_RECH) ? 1u : 0u;
+        }
+        ksum += keep[k];
+    }
+    uint32_t n_keep;
+    uint32_t lk = block_excl_scan<OpAdd, 4>(ksum, sh, n_keep);
+#pragma unroll
+    for (uint32_t k = 0; k < RL_ITEMS; ++k) {
+        if (keep[k]) a.list_out[lk] = g[k];
+        lk += keep[k];
+    }
+    // (the counts are left at zero behind the last table: k_seed of the next final pass adds to the first one)
+    if (tid == 0) *a.cnt_in = 0, *a.cnt_out = last_round ? 0u : n_keep;
 }
 
 // reads that vote in some HETE region (graph keys) / reads flagged invalid: when both are zero the phasing pass has
@@ -1230,9 +1519,10 @@ void launch_edge_compact(hipStream_t s, const uint64_t *ekey, const uint32_t *fl
     if (n) NP2_LAUNCH(k_edge_compact, g1(n), 256, s, ekey, flag, idx, wout, n, ukey, uw, n_out);
 }
 void launch_seed(hipStream_t s, const RegionTables &rt, int32_t max_indel_len, uint8_t *reg_lable, uint32_t *seed_cand,
-                 uint32_t *keep_n, uint32_t *keep_list, uint16_t *keep_ks, uint32_t *err) {
+                 uint32_t *keep_n, uint32_t *keep_list, uint16_t *keep_ks, uint32_t *err, uint32_t *rl_list, uint32_t *rl_cnt,
+                 uint32_t rl_cap) {
     if (rt.n_reg)
-        NP2_LAUNCH(k_seed, g1((uint64_t)((rt.n_reg + 1) / 2) * 64), 256, s, rt, max_indel_len, reg_lable, seed_cand, keep_n, keep_list, keep_ks, err);
+        NP2_LAUNCH(k_seed, g1((uint64_t)((rt.n_reg + 1) / 2) * 64), 256, s, rt, max_indel_len, reg_lable, seed_cand, keep_n, keep_list, keep_ks, err, rl_list, rl_cnt, rl_cap);
 }
 uint32_t region_lb_blocks(uint32_t n_reg) { return (n_reg + 256 * LB_REG_ITEMS - 1) / (256 * LB_REG_ITEMS); }
 void launch_splice_find(hipStream_t s, const uint32_t *cns_pos, const uint32_t *M_p, const uint32_t *lq_start,
@@ -1299,6 +1589,20 @@ void launch_rech_select(hipStream_t s, const uint32_t *rech, const uint32_t *n_r
 }
 void launch_rech_relabel(hipStream_t s, uint8_t *reg_lable, uint32_t n_reg) {
     NP2_LAUNCH(k_rech_relabel, g1(n_reg), 256, s, reg_lable, n_reg);
+}
+void launch_rech_prepare(hipStream_t s, const RechList &a, const uint32_t *cns_pos, const uint8_t *cns_base, const uint32_t *M_p,
+                         const uint32_t *lq_start, const uint32_t *lq_end, const uint32_t *keep_n, uint32_t ksize,
+                         const uint32_t *reg_maxlen, const uint32_t *cand_off, const uint32_t *keep_list,
+                         const uint32_t *seq_off, const uint8_t *seq, uint32_t *err) {
+    NP2_LAUNCH(k_rech_prepare, dim3(1), 256, s, a, cns_pos, cns_base, M_p, lq_start, lq_end, keep_n, ksize, reg_maxlen, cand_off, keep_list, seq_off, seq, err);
+}
+void launch_rech_finish(hipStream_t s, const RechList &a, const uint16_t *score, uint16_t *keep_ks, const uint32_t *cand_off,
+                        const uint32_t *keep_n, const uint32_t *keep_list, const uint32_t *order, bool first_yak,
+                        bool last_round, uint8_t *reg_lable, uint32_t *seed_cand, const uint32_t *cns_pos,
+                        const uint32_t *M_in, const uint32_t *lq_start, const uint32_t *seq_off,
+                        uint32_t *ap_g, uint32_t *ap_s, uint32_t *ap_e, int32_t *ap_delta, int32_t *ap_shift_incl,
+                        uint32_t *n_ap, uint32_t *M_out, uint32_t out_cap, uint32_t *err) {
+    NP2_LAUNCH(k_rech_finish, dim3(1), 256, s, a, score, keep_ks, cand_off, keep_n, keep_list, order, first_yak ? 1u : 0u, last_round ? 1u : 0u, reg_lable, seed_cand, cns_pos, M_in, lq_start, seq_off, ap_g, ap_s, ap_e, ap_delta, ap_shift_incl, n_ap, M_out, out_cap, err);
 }
 
 } // namespace np2
