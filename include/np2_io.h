@@ -147,6 +147,32 @@ int np2_bgzf_inflate_device(np2_ctx_t *ctx, const uint8_t *bgzf, uint64_t n, uin
  * offsets or off[n_pieces] > n: NP2_E_ARG.  The reference's counterpart: htslib's bgzf reader checks each block's CRC. */
 int np2_crc32_device(np2_ctx_t *ctx, const uint8_t *data, uint64_t n, const uint64_t *off, uint32_t n_pieces,
                      uint32_t *crc_out, float *kernel_ms);
+/* ---- BGZF output: DEFLATE on the device, the counterpart of np2_bgzf_inflate_device ----------------------------------------
+ * Host bytes become a whole BGZF stream: blocks of block_bytes input bytes (0: 65280, htslib's; else 1 .. 65280; more is
+ * NP2_E_ARG), each an 18-byte header with the BC subfield, one raw DEFLATE stream, CRC32 and ISIZE, then the canonical
+ * 28-byte EOF block; n = 0 gives the EOF block alone.  A block is tokenised with LZ77 (matches of 8 .. 258 bytes, at most
+ * 32768 back, every candidate verified on the input bytes) and coded as one dynamic Huffman block (codes of at most 15 bits,
+ * HLIT / HDIST / HCLEN trimmed), or stored when that would be no smaller than its bytes + 5: no block is larger than 65536
+ * bytes.  THE BYTES ARE A FUNCTION OF THE INPUT BYTES AND block_bytes ALONE: not of timing, of what the buffers held before,
+ * or of where they are computed — np2_bgzf_deflate_host, which uses no device, runs the same code on the CPU (64 lanes in
+ * turn) and returns the same bytes; it exists for tests and as the statement of what the kernel must produce.
+ * *out_len = the stream's bytes; out_cap too small is NP2_E_ARG, the message says how many are needed (never more than
+ * n + 31 per block + 28).  kernel_ms (optional): the deflate kernel alone (HIP events).  Errors: np2_io_last_error().
+ * The reference's counterpart: gzip on the host behind its recipe's sr.R1.clean.fastq.gz. */
+int np2_bgzf_deflate_device(np2_ctx_t *ctx, const uint8_t *data, uint64_t n, uint32_t block_bytes, uint8_t *out, uint64_t out_cap,
+                            uint64_t *out_len, float *kernel_ms);
+int np2_bgzf_deflate_host(const uint8_t *data, uint64_t n, uint32_t block_bytes, uint8_t *out, uint64_t out_cap, uint64_t *out_len);
+/* A BGZF file written through `device`.  The writer owns a stream and two batches of pinned and device buffers: one batch
+ * (256 blocks; NP2_BGZF_TEST_BATCH, in blocks, a test hook read once per writer) is compressed while the caller fills the
+ * next.  Blocks are cut every 65280 bytes whatever the sizes of the write calls, so the file is np2_bgzf_deflate_host of
+ * the bytes written.  close flushes the partial block, appends the EOF block, reports a write error as NP2_E_ARG "cannot
+ * write <path>" and releases the handle whatever it returns; bytes_in / bytes_out / kernel_ms (any may be NULL): what was
+ * written to the handle, to the file, and the ms in the deflate kernel.  After a failed write, close adds no EOF block: a
+ * writer abandoned on an error leaves a file that readers see as truncated.  Errors: np2_io_last_error(). */
+typedef struct np2_bgzf_writer np2_bgzf_writer_t;
+int np2_bgzf_writer_open(int device, const char *path, np2_bgzf_writer_t **out);
+int np2_bgzf_writer_write(np2_bgzf_writer_t *w, const void *p, uint64_t n);
+int np2_bgzf_writer_close(np2_bgzf_writer_t *w, uint64_t *bytes_in, uint64_t *bytes_out, float *kernel_ms);
 /* copy a resident packed pileup back to the host (parity tests / debugging); free both with np2_free */
 int np2_contig_export(np2_ctx_t *ctx, np2_contig_t *c, np2_read_t **reads, uint32_t *n_reads,
                       uint8_t **nibbles, uint64_t *nib_bytes);
@@ -233,7 +259,8 @@ int np2_srqc_bytes(int device, const uint8_t *seq, const uint8_t *qual, uint64_t
                    uint8_t *masked_out, np2_srqc_read_t *reads_out, uint64_t n_reads, np2_srqc_stats_t *stats);
 /* FASTQ files -> totals (stats: [n_paths + 1], per file and then the sum; or NULL) and, with out_paths (or NULL; single
  * entries may be NULL), one cleaned plain-text FASTQ per input: the passing reads in file order, each the header line as
- * read, the kept bases, "+", the kept qualities. */
+ * read, the kept bases, "+", the kept qualities.  An output path ending in .gz or .bgz is written as BGZF, compressed on
+ * `device` (np2_bgzf_writer_* below); every other path is the plain text. */
 int np2_srqc_files(int device, const char *const *paths, int n_paths, const np2_srqc_opts_t *opts,
                    const char *const *out_paths, np2_srqc_stats_t *stats);
 /* the totals of the last filtering call on this thread (of a multi-pass count: of one pass, not the sum over passes) */
@@ -315,7 +342,8 @@ int np2_sradapt_bytes(int device, const uint8_t *seq, const uint8_t *qual, uint6
  * R1, R2, R1, R2, .. (an odd n_paths is NP2_E_ARG), the two files of a pair are read in step (files whose record counts
  * differ are NP2_E_ARG; the message names both files and the first record, 1-based, that the shorter one lacks), and a
  * pair is written only when both mates pass, so the outputs stay in step.  stats (or NULL): one entry per unit, a file in
- * single mode and a pair of files in pair mode, then the sum. */
+ * single mode and a pair of files in pair mode, then the sum.  An output path ending in .gz or .bgz is written as BGZF,
+ * compressed on `device` (np2_bgzf_writer_* below); every other path is the plain text. */
 int np2_sradapt_files(int device, const char *const *paths, int n_paths, const np2_srqc_opts_t *qc, const np2_sradapt_opts_t *ad,
                       const char *const *out_paths, np2_sradapt_stats_t *stats);
 /* the totals of the last adapter-trimming call on this thread (of a multi-pass count: of one pass) and its kernel's ms */
@@ -336,7 +364,8 @@ int np2_ctx_create_from_reads_ad(np2_ctx_t **out, int device, const char *const 
  * a record without one (one sequence per line) is named by its 1-based number in its file.  Every path of `out` may be
  * NULL: tsv (a header line, then per read: read class s_pat s_mat n_pat n_mat pm mp kmers len), pat_list / mat_list (the
  * names of the paternal bin p, a, 0 / the maternal bin m, a, 0), pat_fa / mat_fa (the two bins as FASTA, one line per
- * sequence, qualities dropped, plain files).  counts (or NULL): reads of class p, m, a, 0. */
+ * sequence, qualities dropped).  A path of `out` ending in .gz or .bgz is written as BGZF, compressed on ctx's device
+ * (np2_bgzf_writer_* below); every other path is a plain file.  counts (or NULL): reads of class p, m, a, 0. */
 typedef struct np2_bin_out { const char *tsv, *pat_list, *mat_list, *pat_fa, *mat_fa; } np2_bin_out_t;
 int np2_bin_files(np2_ctx_t *ctx, int pat_idx, int mat_idx, const char *const *paths, int n_paths,
                   const np2_bin_opts_t *opts, const np2_bin_out_t *out, uint64_t *counts /* [4] */, float *kernel_ms);

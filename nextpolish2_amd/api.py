@@ -38,6 +38,7 @@ IO_ABI_SYMBOLS = [
     "np2_bam_n_refs", "np2_bam_ref_name", "np2_io_last_error", "np2_contig_from_records", "np2_contig_from_bam",
     "np2_contig_export", "np2_shard_bam_begin", "np2_shard_bam_finish", "np2_shard_bam_abort", "np2_ctx_create_from_files",
     "np2_bgzf_inflate_device", "np2_crc32_device",
+    "np2_bgzf_deflate_device", "np2_bgzf_deflate_host", "np2_bgzf_writer_open", "np2_bgzf_writer_write", "np2_bgzf_writer_close",
     "np2_kcount_files", "np2_kcount_bytes", "np2_kcount_files_to_dumps", "np2_ctx_create_from_reads", "np2_kcount_last_stats",
     "np2_seqfile_stream", "np2_bin_files", "np2_seqfile_reads",
     "np2_depth_from_records", "np2_depth_from_bam",

@@ -20,7 +20,7 @@ import numpy as np
 
 from . import io as np2io
 from ._types import Opts
-from .api import Polisher, fasta_record
+from .api import Np2Error, Polisher, fasta_record
 
 VERSION = "np2-mi355x 0.1 (reference semantics: NextPolish2 v0.2.2)"
 
@@ -212,12 +212,25 @@ def _init_distributed(a):
             if os.path.exists(path):
                 verdict = f"Error: {path!r} already exists!".encode()
             else:
-                out = open(path, "wb")
+                try:
+                    out = _open_out(path, a.device % max(1, torch.cuda.device_count()))
+                except SystemExit as e:  # (the other ranks must learn of it)
+                    verdict = str(e).encode()
     got = all_gather_arrays(np.frombuffer(verdict, dtype=np.uint8), device=xdev)
     if len(got[0]):
         dist.destroy_process_group()
         raise SystemExit(got[0].tobytes().decode())
     return out
+
+
+def _open_out(path, device):
+    """the output FASTA: a path ending in .gz or .bgz is written as BGZF, compressed on `device`; any other as plain bytes"""
+    if np2io.is_bgzf_path(path):
+        try:
+            return np2io.BgzfWriter(path, device=device)
+        except Np2Error as e:
+            raise SystemExit(f"Error: {e}")
+    return open(path, "wb")
 
 
 def _main_distributed(a, argv, t0, out, yaks, opts, fopts):
@@ -412,7 +425,7 @@ def main(argv=None):
         path = os.path.abspath(a.out)
         if os.path.exists(path):  # option.rs:312-316: refuse to overwrite
             raise SystemExit(f"Error: {path!r} already exists!")
-        out = open(path, "wb")
+        out = _open_out(path, a.device or 0)
     prof = os.environ.get("NP2_CLI_PROFILE")
     if a.device is None:
         a.device = int(os.environ.get("LOCAL_RANK", "0")) if distributed else 0

@@ -204,8 +204,8 @@ int np2_bin_files(np2_ctx_t *cx, int pat_idx, int mat_idx, const char *const *pa
             files.push_back(paths[i]);
         }
         OutFile tsv, pat_list, mat_list, pat_fa, mat_fa;
-        if (out) tsv.open(out->tsv), pat_list.open(out->pat_list), mat_list.open(out->mat_list), pat_fa.open(out->pat_fa), mat_fa.open(out->mat_fa);
-        const bool want_seq = pat_fa.f || mat_fa.f;
+        if (out) tsv.open(out->tsv, cx->device), pat_list.open(out->pat_list, cx->device), mat_list.open(out->mat_list, cx->device), pat_fa.open(out->pat_fa, cx->device), mat_fa.open(out->mat_fa, cx->device);
+        const bool want_seq = pat_fa.is_open() || mat_fa.is_open();
         if (kernel_ms) *kernel_ms = 0.f;
         uint64_t n_class[4] = {0, 0, 0, 0};
         static const char HEAD[] = "read\tclass\ts_pat\ts_mat\tn_pat\tn_mat\tpm\tmp\tkmers\tlen\n";
@@ -254,7 +254,7 @@ int np2_bin_files(np2_ctx_t *cx, int pat_idx, int mat_idx, const char *const *pa
                     const np2_bin_t &s = st[r];
                     const uint8_t c = cls[r];
                     ++n_class[class_slot(c)];
-                    if (tsv.f) {
+                    if (tsv.is_open()) {
                         row.assign(name, name_n);
                         char num[160];
                         snprintf(num, sizeof num, "\t%c\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%llu\n", (char)c, s.pairs[0], s.pairs[3], s.n_pat, s.n_mat, s.pairs[1],
@@ -266,7 +266,7 @@ int np2_bin_files(np2_ctx_t *cx, int pat_idx, int mat_idx, const char *const *pa
                         if (!(side == 0 ? keep_pat(c) : keep_mat(c))) continue;
                         OutFile &lst = side == 0 ? pat_list : mat_list, &fa = side == 0 ? pat_fa : mat_fa;
                         lst.put(name, name_n), lst.put("\n", 1);
-                        if (fa.f) fa.put(">", 1), fa.put(name, name_n), fa.put("\n", 1), fa.put(open_seq.data(), open_seq.size()), fa.put(bytes + from, end - from), fa.put("\n", 1);
+                        if (fa.is_open()) fa.put(">", 1), fa.put(name, name_n), fa.put("\n", 1), fa.put(open_seq.data(), open_seq.size()), fa.put(bytes + from, end - from), fa.put("\n", 1);
                     }
                     open_seq.clear(), open_len = 0;
                     from = end + 1, name_at = name_end + 1;

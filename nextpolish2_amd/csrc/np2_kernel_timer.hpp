@@ -4,6 +4,7 @@
 // that needs no HIP is np2_pieces.hpp.)
 #pragma once
 #include "np2_ctx.hpp"
+#include "np2_deflate.hpp"
 
 #include <climits>
 
@@ -66,23 +67,37 @@ struct PinnedBlocks {
     }
 };
 
-struct OutFile { // an output a caller may not have asked for: open(nullptr) leaves it closed, put() then writes nothing
+// An output a caller may not have asked for: open(nullptr, ...) leaves it closed, put() then writes nothing.  A path ending
+// in .gz or .bgz is written as BGZF through the device (BgzfWriter, np2_deflate.hpp), every other path as the plain bytes.
+// An OutFile that goes without close() — its driver failed — leaves a compressed file without the EOF block.
+struct OutFile {
     std::string path;
     FILE *f = nullptr;
+    std::unique_ptr<BgzfWriter> z;
     ~OutFile() {
         if (f) fclose(f);
     }
-    void open(const char *p) {
+    bool is_open() const { return f != nullptr || z != nullptr; }
+    void open(const char *p, int device) {
         if (!p) return;
         path = p;
+        if (bgzf_path(p)) {
+            z.reset(new BgzfWriter(device, p));
+            return;
+        }
         f = fopen(p, "wb");
         if (!f) throw Np2Error(NP2_E_ARG, "cannot open " + path + " for writing");
         setvbuf(f, nullptr, _IOFBF, 1 << 20);
     }
     void put(const void *p, size_t n) {
-        if (f && n && fwrite(p, 1, n, f) != n) throw Np2Error(NP2_E_ARG, "cannot write " + path);
+        if (z) z->write(p, n);
+        else if (f && n && fwrite(p, 1, n, f) != n) throw Np2Error(NP2_E_ARG, "cannot write " + path);
     }
     void close() {
+        if (z) {
+            std::unique_ptr<BgzfWriter> w(std::move(z));
+            w->close();
+        }
         FILE *g = f;
         f = nullptr;
         if (g && fclose(g) != 0) throw Np2Error(NP2_E_ARG, "cannot write " + path);

@@ -163,8 +163,8 @@ int np2_sradapt_files(int device, const char *const *paths, int n_paths, const n
         float ms = 0;
         for (int fi = 0; fi < n_paths; fi += step) {
             np2h::OutFile out[2];
-            for (int m = 0; m < step; ++m) out[m].open(out_paths ? out_paths[fi + m] : nullptr);
-            const bool writes = out[0].f || out[1].f;
+            for (int m = 0; m < step; ++m) out[m].open(out_paths ? out_paths[fi + m] : nullptr, device);
+            const bool writes = out[0].is_open() || out[1].is_open();
             r.dev.zero(r.st);
             np2h::QcAssembler as(r.piece, writes);
             as.take = [&] { return &r.pc; };

@@ -145,14 +145,14 @@ int np2_srqc_files(int device, const char *const *paths, int n_paths, const np2_
         float ms = 0;
         for (int fi = 0; fi < n_paths; ++fi) {
             np2h::OutFile out;
-            out.open(out_paths ? out_paths[fi] : nullptr);
+            out.open(out_paths ? out_paths[fi] : nullptr, device);
             r.dev.zero(r.st);
-            np2h::QcAssembler as(r.piece, out.f != nullptr);
+            np2h::QcAssembler as(r.piece, out.is_open());
             as.take = [&] { return &r.pc; };
             as.unused = [](QcPiece *) {};
             as.full = [&](QcPiece *pc) {
                 r.run(false);
-                if (!out.f) return;
+                if (!out.is_open()) return;
                 const char *h = pc->hdrs.data();
                 for (size_t i = 0; i < pc->ends.size(); ++i) {
                     const char *he = (const char *)memchr(h, '\n', pc->hdrs.data() + pc->hdrs.size() - h);

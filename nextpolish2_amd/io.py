@@ -21,7 +21,8 @@ IO_SYMBOLS = ["np2_fasta_open", "np2_fasta_next", "np2_fasta_close", "np2_yak_lo
               "np2_kcount_files_to_dumps_qc", "np2_ctx_create_from_reads_qc", "np2_seqfile_stream_qual", "np2_sam_open", "np2_sam_close",
               "np2_sam_n_refs", "np2_sam_ref_name", "np2_sam_stats", "np2_contig_from_sam", "np2_sam_parse_bytes", "np2_sam_export",
               "np2_sradapt_bytes", "np2_sradapt_files", "np2_sradapt_last_stats", "np2_sradapt_last_kernel_ms", "np2_kcount_files_ad",
-              "np2_kcount_files_to_dumps_ad", "np2_ctx_create_from_reads_ad"]
+              "np2_kcount_files_to_dumps_ad", "np2_ctx_create_from_reads_ad", "np2_bgzf_deflate_device", "np2_bgzf_deflate_host",
+              "np2_bgzf_writer_open", "np2_bgzf_writer_write", "np2_bgzf_writer_close"]
 
 
 class np2_front_opts_t(C.Structure):
@@ -272,6 +273,11 @@ def _bind_locked(L):
         L.np2_contig_export.argtypes = [vp, vp, C.POINTER(vp), C.POINTER(C.c_uint32), C.POINTER(vp), C.POINTER(C.c_uint64)]
         L.np2_bgzf_inflate_device.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_float)]
         L.np2_crc32_device.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, vp, C.POINTER(C.c_float)]
+        L.np2_bgzf_deflate_device.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_float)]
+        L.np2_bgzf_deflate_host.argtypes = [vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.np2_bgzf_writer_open.argtypes = [C.c_int, C.c_char_p, C.POINTER(vp)]
+        L.np2_bgzf_writer_write.argtypes = [vp, vp, C.c_uint64]
+        L.np2_bgzf_writer_close.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_float)]
         _bind_shard(L)
         _bind_kcount(L)
         _bind_sam(L)
@@ -935,6 +941,94 @@ def bgzf_inflate_device(pol, data):
     if rc != 0:
         raise Np2Error(rc, "np2_bgzf_inflate_device: " + (L.np2_io_last_error() or b"").decode())
     return out[: n.value].copy(), float(ms.value)
+
+
+def _u8(data):
+    return np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else data, dtype=np.uint8)
+
+
+def _bgzf_bound(n, block_bytes):
+    """the most a BGZF stream of n bytes takes: every block stored (5 + 26 bytes around it), and the EOF block"""
+    bb = block_bytes or 65280
+    return n + (n + bb - 1) // bb * 31 + 28
+
+
+def bgzf_deflate_device(pol, data, block_bytes=0):
+    """np2_bgzf_deflate_device: bytes -> a whole BGZF stream (blocks of block_bytes input bytes, 0: 65280; then the EOF
+    block), compressed on the polisher's device -> (the stream as bytes, milliseconds in the deflate kernel)."""
+    L = _bind()
+    src = _u8(data)
+    cap = _bgzf_bound(len(src), block_bytes)
+    out = np.empty(cap, dtype=np.uint8)
+    n, ms = C.c_uint64(), C.c_float()
+    rc = L.np2_bgzf_deflate_device(pol._h, src.ctypes.data if len(src) else None, len(src), block_bytes, out.ctypes.data, cap, C.byref(n), C.byref(ms))
+    if rc != 0:
+        raise Np2Error(rc, "np2_bgzf_deflate_device: " + (L.np2_io_last_error() or b"").decode())
+    return out[: n.value].tobytes(), float(ms.value)
+
+
+def bgzf_deflate_host(data, block_bytes=0):
+    """np2_bgzf_deflate_host: the same stream computed on the CPU by the code the kernel's lanes run (no device)."""
+    L = _bind()
+    src = _u8(data)
+    cap = _bgzf_bound(len(src), block_bytes)
+    out = np.empty(cap, dtype=np.uint8)
+    n = C.c_uint64()
+    rc = L.np2_bgzf_deflate_host(src.ctypes.data if len(src) else None, len(src), block_bytes, out.ctypes.data, cap, C.byref(n))
+    if rc != 0:
+        raise Np2Error(rc, "np2_bgzf_deflate_host: " + (L.np2_io_last_error() or b"").decode())
+    return out[: n.value].tobytes()
+
+
+def is_bgzf_path(path):
+    """the rule of every writer here: a path ending in .gz or .bgz is written as BGZF, any other as plain bytes"""
+    return str(path).endswith((".gz", ".bgz"))
+
+
+class BgzfWriter:
+    """np2_bgzf_writer_*: a BGZF file compressed on `device`, blocks cut every 65280 bytes whatever the sizes of the
+    writes.  close() appends the EOF block; a writer that failed leaves the file without it.  After close(): bytes_in,
+    bytes_out, kernel_ms."""
+
+    def __init__(self, path, device=0):
+        self._L = _bind()
+        self._h = C.c_void_p()
+        self.bytes_in = self.bytes_out = 0
+        self.kernel_ms = 0.0
+        rc = self._L.np2_bgzf_writer_open(device, os.fsencode(path), C.byref(self._h))
+        if rc != 0:
+            self._h = C.c_void_p()
+            raise Np2Error(rc, "np2_bgzf_writer_open: " + (self._L.np2_io_last_error() or b"").decode())
+
+    def write(self, data):
+        if not self._h:
+            raise ValueError("write to a closed BgzfWriter")
+        src = _u8(data.encode() if isinstance(data, str) else data)
+        if len(src):
+            rc = self._L.np2_bgzf_writer_write(self._h, src.ctypes.data, len(src))
+            if rc != 0:
+                raise Np2Error(rc, "np2_bgzf_writer_write: " + (self._L.np2_io_last_error() or b"").decode())
+        return len(src)
+
+    def close(self):
+        if not self._h:
+            return
+        h, self._h = self._h, C.c_void_p()
+        a, b, ms = C.c_uint64(), C.c_uint64(), C.c_float()
+        rc = self._L.np2_bgzf_writer_close(h, C.byref(a), C.byref(b), C.byref(ms))
+        if rc != 0:
+            raise Np2Error(rc, "np2_bgzf_writer_close: " + (self._L.np2_io_last_error() or b"").decode())
+        self.bytes_in, self.bytes_out, self.kernel_ms = a.value, b.value, float(ms.value)
+
+    def flush(self):
+        """(a file object's: the blocks leave with their batch and at close())"""
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
 
 
 def crc32_device(pol, data, offsets):

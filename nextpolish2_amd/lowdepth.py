@@ -5,6 +5,8 @@ mapped by HiFi reads, and this tells a user which regions those are).
     python -m nextpolish2_amd.lowdepth reads.map.sort.bam genome.fa[.gz] > genome.filter.fa
           [-d 3] [-l 1000] [--min_fra 0.8] [--min_mapq 0] [--exclude_flags 4] [--bed F] [--low_bed F] [--bedgraph F] [-o F]
 
+-o F writes the FASTA to F instead of standard output; an F ending in .gz or .bgz is written as BGZF, compressed on the device.
+
 Depth counts alignment records (include/np2_io.h, np2_depth_*): a record is counted unless one of its flag bits is in
 --exclude_flags, its mapping quality is below --min_mapq, it has no CIGAR, or its aligned query bases (M I = X) are less
 than --min_fra of its read length (M I S H = X); it covers its reference span (M D N = X), clamped to the contig.  A run is a
@@ -47,7 +49,7 @@ def build_parser():
     p.add_argument("--bed", default=None, metavar="FILE", help="the kept runs as BED")
     p.add_argument("--low_bed", default=None, metavar="FILE", help="the complement of the kept runs inside each contig as BED")
     p.add_argument("--bedgraph", default=None, metavar="FILE", help="the depth as bedGraph (brings the per-base array back to the host)")
-    p.add_argument("-o", "--out", default=None, metavar="FILE", help="FASTA [stdout]; an existing file is not overwritten")
+    p.add_argument("-o", "--out", default=None, metavar="FILE", help="FASTA [stdout]; a name ending in .gz or .bgz is written as BGZF; an existing file is not overwritten")
     return p
 
 
@@ -112,7 +114,15 @@ def main(argv=None):
     a = parse_args(argv)
     from . import io as np2io
     from .api import Np2Error, Polisher
-    out = sys.stdout.buffer if a.out is None else open(os.path.abspath(a.out), "xb")
+    try:
+        if a.out is None:
+            out = sys.stdout.buffer
+        elif np2io.is_bgzf_path(a.out):  # the writers' rule: .gz / .bgz is BGZF, compressed on the device
+            out = np2io.BgzfWriter(os.path.abspath(a.out), device=a.device)
+        else:
+            out = open(os.path.abspath(a.out), "xb")
+    except Np2Error as e:
+        raise SystemExit(f"Error: {e}")
     side = {k: open(p, "w") for k, p in (("bed", a.bed), ("low_bed", a.low_bed), ("bedgraph", a.bedgraph)) if p is not None}
     try:
         pol = Polisher([], device=a.device)  # (no k-mer table: the depth needs the device and the BAM only)

@@ -1,7 +1,7 @@
 """python -m nextpolish2_amd.srqc: quality-trim and filter short reads on the GPU (the preparation step the reference's
 README asks for before `yak count`; its recipe is fastp -5 -3 -n 0 -f 5 -F 5 -t 5 -T 5 -q 20).
 
-    python -m nextpolish2_amd.srqc reads.fq.gz ... [--sr_qc SPEC] [--sr_adapter [SPEC]] [--report qc.tsv] [--out_fq PREFIX]
+    python -m nextpolish2_amd.srqc reads.fq.gz ... [--sr_qc SPEC] [--sr_adapter [SPEC]] [--report qc.tsv] [--out_fq PREFIX [--out_gz]]
 
 The rule is this project's own, built on the options of that recipe; it is not pinned against the fastp binary.  One read
 has n bases and n quality bytes, p[i] = max(0, byte - 33):
@@ -15,7 +15,8 @@ Reads are judged one by one: paired files are not kept in step.  No adapter trim
 complexity and no average-quality filter.  Inputs are FASTQ, plain or gzip.
 
 --report writes a TSV, one line per file and a total: reads, pass, too_short, too_many_n, low_quality, bases_in, bases_out
-(standard output without it).  --out_fq PREFIX writes the passing reads of input i, trimmed, to PREFIX.<i>.fq.  Existing
+(standard output without it).  --out_fq PREFIX writes the passing reads of input i, trimmed, to PREFIX.<i>.fq; with --out_gz
+to PREFIX.<i>.fq.gz, BGZF compressed on the device (what the reference's recipe names sr.R1.clean.fastq.gz).  Existing
 files are not overwritten.  The k-mer counter takes the same option (nextpolish2_amd.count --sr_qc, nextPolish2 --sr ..
 --sr_qc) and filters on the way, without the files.
 
@@ -45,6 +46,7 @@ def build_parser():
     p.add_argument("--sr_adapter", nargs="?", const="", default=None, type=np2io.sr_adapter_arg, metavar="SPEC", help=np2io.SR_ADAPTER_HELP)
     p.add_argument("--report", default=None, metavar="FILE", help="the totals as a TSV [stdout]")
     p.add_argument("--out_fq", default=None, metavar="PREFIX", help="write the cleaned reads of input i to PREFIX.<i>.fq")
+    p.add_argument("--out_gz", action="store_true", help="with --out_fq: write PREFIX.<i>.fq.gz, BGZF compressed on the device")
     p.add_argument("--device", type=int, default=0)
     return p
 
@@ -60,10 +62,12 @@ def parse_args(argv=None):
     p = build_parser()
     a = p.parse_args(argv)
     np2io.check_sr_adapter(p, a.sr_adapter, a.reads)
+    if a.out_gz and a.out_fq is None:
+        p.error("--out_gz needs --out_fq")
     for r in a.reads:
         if not os.path.exists(r):
             p.error(f"cannot open {r}")
-    a.out_paths = None if a.out_fq is None else [f"{a.out_fq}.{i}.fq" for i in range(len(a.reads))]
+    a.out_paths = None if a.out_fq is None else [f"{a.out_fq}.{i}.fq" + (".gz" if a.out_gz else "") for i in range(len(a.reads))]
     for out in ([a.report] if a.report else []) + (a.out_paths or []):
         if os.path.exists(out):  # like the other modules: nothing is overwritten
             raise SystemExit(f"Error: {os.path.abspath(out)!r} already exists!")

@@ -13,6 +13,9 @@ the scores are equal or the smaller one is more than --max_minor of the larger; 
 The paternal bin keeps p, a and 0, the maternal bin m, a and 0.  The semantics are this project's own: yak's report is
 not reproduced byte for byte.
 
+An output named *.gz or *.bgz (the bins, the lists, the TSV) is written as BGZF, compressed on the device; any other name
+as plain text.
+
 TSV columns: read, class, s_pat, s_mat, n_pat, n_mat, pm, mp, kmers, len.  A summary per class goes to stderr.
 
 The helpers at the top need no device (classify, keep, permille_of, parse_args); main() drives np2_bin_files."""
@@ -64,8 +67,8 @@ def build_parser():
     p.add_argument("-o", "--out", default=None, metavar="FILE", help="TSV [stdout]")
     p.add_argument("--pat_list", default=None, metavar="FILE", help="names of the paternal bin (p, a, 0)")
     p.add_argument("--mat_list", default=None, metavar="FILE", help="names of the maternal bin (m, a, 0)")
-    p.add_argument("--pat_fa", default=None, metavar="FILE", help="the paternal bin as FASTA")
-    p.add_argument("--mat_fa", default=None, metavar="FILE", help="the maternal bin as FASTA")
+    p.add_argument("--pat_fa", default=None, metavar="FILE", help="the paternal bin as FASTA; a name ending in .gz or .bgz is written as BGZF, compressed on the device")
+    p.add_argument("--mat_fa", default=None, metavar="FILE", help="the maternal bin as FASTA (the same rule)")
     p.add_argument("--device", type=int, default=0)
     return p
 
