@@ -471,7 +471,8 @@ const char *np2_sam_ref_name(np2_sam_t *s, int tid, uint32_t *len);
 int np2_sam_stats(np2_sam_t *s, np2_sam_stats_t *stats);
 /* np2_contig_from_bam for a resident SAM: the host copies back the range of records and CIGAR words of reference `name`
  * (binary search on the sorted keys) and the front end reads the SEQ bytes where they are.  use_secondary is
- * NP2_E_UNSUPPORTED (a secondary record needs the SEQ of its read's primary record, found by name: use a BAM); a name the
+ * NP2_E_UNSUPPORTED (a secondary record needs the SEQ of its read's primary record, found by name: use a BAM, which
+ * np2_sam_write_bam below writes from this handle); a name the
  * @SQ lines lack, a NULL argument or a context of another device is NP2_E_ARG.  These are checked before the first device call. */
 int np2_contig_from_sam(np2_ctx_t *ctx, np2_sam_t *sam, const char *name, const uint8_t *ref, uint32_t L,
                         const np2_front_opts_t *opts, np2_contig_t **out);
@@ -484,6 +485,70 @@ int np2_sam_parse_bytes(int device, const uint8_t *text, uint64_t n, const np2_s
 /* the same four arrays of a resident SAM copied back to the host (parity tests of np2_sam_open; np2_sam_stats has the sizes) */
 int np2_sam_export(np2_ctx_t *ctx, np2_sam_t *sam, np2_bamrec_t **recs, int32_t **tids, uint32_t **cigar, uint8_t **seq4,
                    uint64_t *n_recs);
+
+/* ---- the sorted BAM and its .bai, written from a resident SAM (the reference's recipe: `samtools sort -o hifi.map.sort.bam -`
+ * and `samtools index`) ---------------------------------------------------------------------------------------------------
+ * THE RULE IS DEFINED HERE, on the SAM specification sections 4.2 (BAM) and 5.2 (BAI).  No samtools binary was at hand:
+ * equality with the files of `samtools sort` / `samtools index` is not claimed.
+ *   Names: np2_sam_open_ex with NP2_SAM_KEEP_NAMES keeps each kept record's QNAME, the bytes before the first tab as they
+ *     stand.  An empty QNAME or one longer than 254 bytes is NP2_E_ARG naming the 1-based line (after every other error of
+ *     its piece of text).  np2_bamrec_t stays as it is: per record, beside it and through the sort like the tids, travels
+ *     name_ref = offset << 8 | length into the name bytes, which stay where they were met.  Without the flag np2_sam_open_ex
+ *     is np2_sam_open and launches what that launches.
+ *   Stream S: "BAM\1", l_text, text, n_ref, then per reference l_name, name with NUL, l_ref.  text is
+ *     "@HD\tVN:1.6\tSO:coordinate\n" and one "@SQ\tSN:<name>\tLN:<len>\n" per reference in order; other header lines of the
+ *     input are not carried.  Then the kept records in the resident order ((tid, pos + 1, strand-or-0), ties in input order),
+ *     each: block_size, refID = tid, pos, l_read_name = length + 1, mapq, bin = reg2bin(pos, pos + max(span, 1)) with span the
+ *     summed lengths of the M, D, N, = and X operations, n_cigar_op, flag, l_seq, next_refID = -1, next_pos = -1, tlen = 0,
+ *     the name with NUL, the CIGAR words, the (l_seq + 1) / 2 packed SEQ bytes as they lie at seq_off with the low nibble of
+ *     an odd last byte 0, and l_seq bytes 0xFF.  QUAL, RNEXT, PNEXT, TLEN and the optional fields are not carried.
+ *   Refusals, each naming the record (0-based in the resident order) or the reference, all raised before the output file is
+ *     created: a record with pos < 0 (SAM POS 0) is NP2_E_ARG; n_cigar > 65535 is NP2_E_UNSUPPORTED (no CG tag is written);
+ *     a reference with LN > 2^29, or a record with pos + max(span, 1) > 2^29, is NP2_E_UNSUPPORTED (BAI's limit; there is no
+ *     CSI); a handle opened without NP2_SAM_KEEP_NAMES is NP2_E_ARG.
+ *   File: the .bam is np2_bgzf_deflate_host(S, 0) byte for byte: blocks cut every 65280 bytes of S wherever records fall,
+ *     and the EOF block.  Records, their length words and their fixed fields straddle blocks.
+ *   Index: C[b] is the file offset of BGZF block b (C[n_blk]: the EOF block's), V(u) = C[u / 65280] << 16 | u % 65280.
+ *     Record i lies at [off_i, off_i + 4 + block_size_i) of S; beg_i = V(off_i), end_i = V(off_i + 4 + block_size_i).  Per
+ *     reference a maximal run of consecutive records of one bin is one chunk [beg of the first, end of the last]; bins
+ *     ascending, a bin's chunks in file order.  n_intv = 1 + the largest (pos + max(span, 1) - 1) >> 14 of the reference;
+ *     ioffset[w] = beg of the first record in file order that overlaps window w, an empty window takes the previous one's
+ *     value, leading empty windows are 0.  A reference without records has n_bin = 0 and n_intv = 0.  No pseudo-bin 37450
+ *     and no n_no_coor.
+ *   Out of scope: QUAL, RNEXT, PNEXT, TLEN and optional fields; header lines other than @HD and @SQ; unmapped records; CSI;
+ *     the 37450 pseudo-bin; compression levels; several ranks; inputs larger than one device's memory; BAM to BAM.
+ * The stream is assembled (k_bam_emit), compressed (k_bgzf_deflate) and indexed on the device; it never passes through host
+ * memory.  Test hook, read once per call: NP2_BGZF_TEST_BATCH (blocks per batch). */
+#define NP2_SAM_KEEP_NAMES 1u
+/* np2_sam_open with a flags word (np2_sam_opts_t keeps its size) */
+int np2_sam_open_ex(np2_ctx_t *ctx, const char *const *paths, int n_paths, const np2_sam_opts_t *opts, uint32_t flags,
+                    np2_sam_t **out);
+typedef struct np2_bamout_stats {
+    uint64_t records;      /* written */
+    uint64_t stream_bytes; /* of S */
+    uint64_t file_bytes;   /* of the .bam */
+    uint64_t blocks;       /* BGZF blocks, the EOF block not counted */
+    uint64_t bins, chunks; /* of the .bai, all references */
+    float sizes_ms;        /* k_bam_sizes and its scan (HIP events; 0 from the host twin, as are the next three) */
+    float emit_ms;         /* k_bam_emit, summed over the batches */
+    float deflate_ms;      /* k_bgzf_deflate, summed over the batches */
+    float index_ms;        /* the index kernels, scans and sort */
+} np2_bamout_stats_t;
+/* Writes bam_path and bai_path (NULL: bam_path + ".bai").  stats may be NULL.  A refused call leaves no file. */
+int np2_sam_write_bam(np2_ctx_t *ctx, np2_sam_t *sam, const char *bam_path, const char *bai_path, np2_bamout_stats_t *stats);
+/* the uncompressed stream S on the host, for tests: *S is released with np2_free */
+int np2_sam_bam_stream(np2_ctx_t *ctx, np2_sam_t *sam, uint8_t **S, uint64_t *n);
+/* The host twin: uses no device.  From the arrays np2_sam_export returns (n_cigar_words and seq_bytes are their sizes), the
+ * name bytes and name_ref[i] = offset << 8 | length per record, and the reference list, it writes the same two files by
+ * running the kernels' per-record code on the CPU.  bam_path may be NULL (no file is written); S / n_S may be NULL, otherwise
+ * *S is the stream, released with np2_free.  Every array is checked against its size first (NP2_E_ARG). */
+int np2_bamout_host(const np2_bamrec_t *recs, const int32_t *tids, const uint32_t *cigar, const uint8_t *seq4, uint64_t n_recs,
+                    uint64_t n_cigar_words, uint64_t seq_bytes, const uint8_t *names, uint64_t name_bytes, const uint64_t *name_ref,
+                    const char *const *ref_names, const uint32_t *ref_lens, int n_refs, const char *bam_path, const char *bai_path,
+                    uint8_t **S, uint64_t *n_S, np2_bamout_stats_t *stats);
+/* the name bytes and name_ref array of a resident SAM opened with NP2_SAM_KEEP_NAMES, for the host twin and parity tests:
+ * both released with np2_free, NULL when empty */
+int np2_sam_export_names(np2_ctx_t *ctx, np2_sam_t *sam, uint8_t **names, uint64_t *name_bytes, uint64_t **name_ref, uint64_t *n_recs);
 
 #ifdef __cplusplus
 }

@@ -82,6 +82,9 @@ def build_parser():
                    help="switch and Hamming error of every contig as read and as written against parental k-mer tables, as a TSV "
                         "(needs --trio_pat and --trio_mat)")
     p.add_argument("--trio_pat", type=_existing, default=None, metavar="pat.yak", help="--trio: the paternal k-mer dump")
+    p.add_argument("--sorted_bam", default=None, metavar="hifi.map.sort.bam",
+                   help="SAM input: also write the coordinate-sorted BAM and its .bai (what samtools sort and index would make of "
+                        "the mapping), assembled, compressed and indexed on the GPU; single rank")
     p.add_argument("--trio_mat", type=_existing, default=None, metavar="mat.yak", help="--trio: the maternal k-mer dump (same k)")
     p.add_argument("--trio_min_count", type=int, default=2, metavar="N", help="--trio: a parent counting a k-mer fewer than N times does not have it [2]")
     p.add_argument("--trio_mid_count", type=int, default=5, metavar="N", help="--trio: a parent counting a k-mer at least N times has it [5]")
@@ -401,7 +404,10 @@ def main(argv=None):
     except (ValueError, OSError) as e:
         raise SystemExit(f"Error: {e}")
     if a.sam and a.use_secondary:
-        raise SystemExit("Error: -S needs the SEQ of a read's primary record, which is found by name: not with SAM input, use a sorted BAM")
+        raise SystemExit("Error: -S needs the SEQ of a read's primary record, which is found by name: not with SAM input, use a sorted BAM "
+                         "(python -m nextpolish2_amd.samsort writes one from the SAM text)")
+    if a.sorted_bam is not None and not a.sam:
+        raise SystemExit("Error: --sorted_bam writes the sorted BAM of SAM input; the mapping given is a BAM already")
     if a.sam and int(os.environ.get("WORLD_SIZE", "1")) > 1 and "RANK" in os.environ:
         raise SystemExit("Error: SAM input runs on one rank: interval sharding reads the .bai of a sorted BAM")
     for y in a.yak:  # (before the output file exists: a broken dump must not leave a partial output behind)
@@ -504,7 +510,11 @@ def main(argv=None):
         t_s = time.time()
         spol = Polisher([], device=a.device)
         try:
-            sam = np2io.Sam(spol, [a.bam], tie=a.sam_tie)
+            sam = np2io.Sam(spol, [a.bam], tie=a.sam_tie, keep_names=a.sorted_bam is not None)
+            if a.sorted_bam is not None:  # the mapping is kept from this one pass over a stream that cannot be read twice
+                st = sam.write_bam(spol, a.sorted_bam)
+                if prof:
+                    print(f"[np2 profile] sorted BAM written {time.time() - t_s:.3f} s after the start of the SAM: {st}", file=sys.stderr)
         except BaseException:
             spol.close()
             raise
@@ -771,6 +781,8 @@ def main(argv=None):
             for q in tpol:
                 q.close()
         yak_pool.shutdown(wait=False)
+        if a.sorted_bam is not None and not sam_future and sys.exc_info()[0] is None:  # (an assembly without a contig)
+            sam_future.append(sam_pool.submit(open_sam))
         sam_pool.shutdown(wait=True)
         if sam_future and sam_future[0].exception() is None:  # (after the front ends: nothing reads the resident SAM any more)
             spol, sam = sam_future[0].result()

@@ -44,6 +44,15 @@ public:
     uint64_t bytes_in() const;
     uint64_t bytes_out() const;
     float kernel_ms() const; // the deflate kernel alone (HIP events), summed over the batches
+    // The device-input door, for bytes that are made on the device: the caller fills the first n bytes of device_in()
+    // (batch_bytes() bytes, 16-byte aligned) with work on stream(), then commit_device(n) compresses them as one batch while
+    // the next is filled; every batch but the last holds batch_bytes().  sizes_dst (device, may be NULL) receives the size of
+    // each of the batch's blocks.  Not to be mixed with write().
+    hipStream_t stream() const;
+    size_t batch_bytes() const;
+    uint8_t *device_in();
+    void commit_device(size_t n, uint32_t *sizes_dst);
+    float fill_ms() const;   // what ran on stream() between device_in() and commit_device(), summed over the drained batches
 private:
     struct Impl;
     std::unique_ptr<Impl> im;

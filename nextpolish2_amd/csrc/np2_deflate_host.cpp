@@ -27,9 +27,9 @@ struct DeflateBatch {
     np2h::DevBuf<uint8_t> d_in, d_slots, d_packed;
     np2h::DevBuf<uint32_t> d_tok, d_sizes, d_offs, d_crc;
     np2h::DevBuf<np2::InfBlock> d_tb;
-    np2h::DevEvent e0, e1, done;
+    np2h::DevEvent e0, e1, f0, f1, done;
     uint32_t n_blk = 0;
-    bool pending = false;
+    bool pending = false, device_filled = false;
     void size(uint32_t blocks) {
         cap_blocks = blocks;
         pin_in.ensure((size_t)blocks * np2def::MAX_BLOCK);
@@ -40,20 +40,23 @@ struct DeflateBatch {
         d_packed.ensure((size_t)blocks * np2def::SLOT_BYTES);
         d_tok.ensure((size_t)blocks * np2def::TOK_WORDS);
         d_sizes.ensure(blocks + 1), d_offs.ensure(blocks + 2), d_crc.ensure(blocks + 1), d_tb.ensure(blocks + 1);
-        e0.make(), e1.make(), done.make();
+        e0.make(), e1.make(), f0.make(), f1.make(), done.make();
     }
     uint8_t *in() { return (uint8_t *)pin_in.p; }
     const uint8_t *out() const { return (const uint8_t *)pin_out.p; }
-    // the first n bytes of in(), in blocks of bb: upload, CRCs, deflate, pack; nothing is waited for
-    void submit(hipStream_t s, size_t n, uint32_t bb) {
+    // the first n bytes of in(), in blocks of bb: upload, CRCs, deflate, pack; nothing is waited for.  from_device: the
+    // bytes are in d_in already, written on s between f0 and f1.  sizes_dst: the blocks' sizes are copied there, on the device.
+    void submit(hipStream_t s, size_t n, uint32_t bb, bool from_device = false, uint32_t *sizes_dst = nullptr) {
         n_blk = (uint32_t)((n + bb - 1) / bb);
         if (!n_blk || n_blk > cap_blocks) throw Np2Error(NP2_E_ARG, "BGZF batch out of range");
-        HIPCHK(hipMemcpyAsync(d_in.p, pin_in.p, n, hipMemcpyHostToDevice, s));
+        device_filled = from_device;
+        if (!from_device) HIPCHK(hipMemcpyAsync(d_in.p, pin_in.p, n, hipMemcpyHostToDevice, s));
         np2::launch_deflate_pieces(s, d_tb.p, n_blk, bb, n);
         np2::launch_bgzf_crc32(s, d_tb.p, n_blk, nullptr, d_in.p, nullptr, nullptr, d_crc.p);
         HIPCHK(hipEventRecord(e0.e, s));
         np2::launch_bgzf_deflate(s, d_in.p, n, bb, n_blk, d_crc.p, d_slots.p, d_tok.p, d_sizes.p);
         HIPCHK(hipEventRecord(e1.e, s));
+        if (sizes_dst) HIPCHK(hipMemcpyAsync(sizes_dst, d_sizes.p, (size_t)n_blk * 4, hipMemcpyDeviceToDevice, s));
         np2::launch_deflate_pack(s, d_slots.p, d_sizes.p, n_blk, d_offs.p, d_packed.p, nullptr);
         HIPCHK(hipMemcpyAsync(pin_total.p, d_offs.p + n_blk, 4, hipMemcpyDeviceToHost, s));
         HIPCHK(hipGetLastError());
@@ -61,7 +64,7 @@ struct DeflateBatch {
         pending = true;
     }
     // the batch's packed bytes in out(): waits for its kernels, then for the one copy; returns their number
-    size_t finish(hipStream_t s, float &kernel_ms) {
+    size_t finish(hipStream_t s, float &kernel_ms, float *fill_ms = nullptr) {
         HIPCHK(hipEventSynchronize(done.e));
         pending = false;
         const size_t total = *(const uint32_t *)pin_total.p;
@@ -70,6 +73,7 @@ struct DeflateBatch {
         HIPCHK(hipMemcpyAsync(pin_out.p, d_packed.p, total, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         kernel_ms += np2h::elapsed(e0, e1);
+        if (device_filled && fill_ms) *fill_ms += np2h::elapsed(f0, f1);
         return total;
     }
 };
@@ -89,7 +93,7 @@ struct BgzfWriter::Impl {
     int cur = 0;
     size_t fill = 0, cap = 0;
     uint64_t n_in = 0, n_out = 0;
-    float ms = 0.f;
+    float ms = 0.f, fill_ms = 0.f;
     bool failed = false; // a write or a batch failed: the file never gets its EOF block
     ~Impl() {
         (void)hipSetDevice(device);
@@ -103,7 +107,7 @@ struct BgzfWriter::Impl {
     }
     void drain(int k) { // batch k's bytes to the file
         if (!b[k].pending) return;
-        const size_t n = b[k].finish(s, ms);
+        const size_t n = b[k].finish(s, ms, &fill_ms);
         put(b[k].out(), n);
     }
     void flush() { // the bytes gathered so far become a batch; the other one, compressed meanwhile, goes to the file first
@@ -162,6 +166,29 @@ void BgzfWriter::close() {
     im->f = nullptr;
     if (fclose(g) != 0) throw Np2Error(NP2_E_ARG, "cannot write " + im->path);
 }
+hipStream_t BgzfWriter::stream() const { return im->s; }
+size_t BgzfWriter::batch_bytes() const { return im->cap; }
+uint8_t *BgzfWriter::device_in() {
+    if (!im->f || im->failed) throw Np2Error(NP2_E_ARG, "cannot write " + im->path);
+    if (im->fill) throw Np2Error(NP2_E_ARG, "BGZF writer: device input after a partial host batch");
+    HIPCHK(hipSetDevice(im->device));
+    HIPCHK(hipEventRecord(im->b[im->cur].f0.e, im->s));
+    return im->b[im->cur].d_in.p;
+}
+void BgzfWriter::commit_device(size_t n, uint32_t *sizes_dst) {
+    if (!n || n > im->cap) throw Np2Error(NP2_E_ARG, "BGZF batch out of range");
+    try {
+        HIPCHK(hipEventRecord(im->b[im->cur].f1.e, im->s));
+        im->n_in += n;
+        im->drain(im->cur ^ 1);
+        im->b[im->cur].submit(im->s, n, np2def::MAX_BLOCK, true, sizes_dst);
+        im->cur ^= 1;
+    } catch (...) {
+        im->failed = true;
+        throw;
+    }
+}
+float BgzfWriter::fill_ms() const { return im->fill_ms; }
 uint64_t BgzfWriter::bytes_in() const { return im->n_in; }
 uint64_t BgzfWriter::bytes_out() const { return im->n_out; }
 float BgzfWriter::kernel_ms() const { return im->ms; }

@@ -445,6 +445,8 @@ size_t prim_temp_bytes(size_t n);
 int prim_sort_pairs_u64_u32(hipStream_t s, void *tmp, size_t tmp_bytes, const uint64_t *kin, uint64_t *kout,
                             const uint32_t *vin, uint32_t *vout, size_t n, unsigned end_bit);
 int prim_exclusive_sum_u32(hipStream_t s, void *tmp, size_t tmp_bytes, const uint32_t *in, uint32_t *out, size_t n);
+// ... of 32-bit values summed in 64 bits
+int prim_exclusive_sum_u32_u64(hipStream_t s, void *tmp, size_t tmp_bytes, const uint32_t *in, uint64_t *out, size_t n);
 int prim_inclusive_sum_i32(hipStream_t s, void *tmp, size_t tmp_bytes, const int32_t *in, int32_t *out, size_t n);
 int prim_inclusive_min_i32(hipStream_t s, void *tmp, size_t tmp_bytes, const int32_t *in, int32_t *out, size_t n);
 

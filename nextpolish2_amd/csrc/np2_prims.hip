@@ -18,6 +18,9 @@ size_t prim_temp_bytes(size_t n) {
     (void)rocprim::inclusive_scan(nullptr, b, (const int32_t *)nullptr, (int32_t *)nullptr, n, rocprim::minimum<int32_t>(),
                             (hipStream_t)0);
     best = b > best ? b : best;
+    (void)rocprim::exclusive_scan(nullptr, b, (const uint32_t *)nullptr, (uint64_t *)nullptr, (uint64_t)0, n,
+                            rocprim::plus<uint64_t>(), (hipStream_t)0);
+    best = b > best ? b : best;
     return best + 256;
 }
 int prim_sort_pairs_u64_u32(hipStream_t s, void *tmp, size_t tmp_bytes, const uint64_t *kin, uint64_t *kout,
@@ -28,6 +31,10 @@ int prim_sort_pairs_u64_u32(hipStream_t s, void *tmp, size_t tmp_bytes, const ui
 int prim_exclusive_sum_u32(hipStream_t s, void *tmp, size_t tmp_bytes, const uint32_t *in, uint32_t *out, size_t n) {
     if (n == 0) return 0;
     return (int)rocprim::exclusive_scan(tmp, tmp_bytes, in, out, 0u, n, rocprim::plus<uint32_t>(), s);
+}
+int prim_exclusive_sum_u32_u64(hipStream_t s, void *tmp, size_t tmp_bytes, const uint32_t *in, uint64_t *out, size_t n) {
+    if (n == 0) return 0;
+    return (int)rocprim::exclusive_scan(tmp, tmp_bytes, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), s);
 }
 int prim_inclusive_sum_i32(hipStream_t s, void *tmp, size_t tmp_bytes, const int32_t *in, int32_t *out, size_t n) {
     if (n == 0) return 0;

@@ -11,6 +11,12 @@
 //                 lane), the CIGAR words (a lane that owns an operation letter reads the digits in front of it; its rank among
 //                 the letters comes from the ballot) and the SEQ nibbles (two bases a lane a step, byte stores next to each other).
 //
+// With NP2_SAM_KEEP_NAMES (np2_sam_open_ex; the BAM writer, np2_bamout.hip, needs the QNAMEs) two more per piece:
+//   k_sam_name_len   a wavefront per line: a kept line's first tab among its first 256 bytes, by ballot; an empty name or one
+//                    above 254 bytes is the piece's first bad line by atomicMin
+//   k_sam_name_copy  after the scan placed the names: the bytes, and offset << 8 | length per record
+// and k_sam_gather_u64 moves those words into sorted order; the name bytes stay where they are, as SEQ does.
+//
 // After the last piece the keys are sorted with the record ordinals as values (rocPRIM, np2_prims.hip: stable) and
 //   k_sam_gather  a wavefront per record moves the record and its CIGAR words into sorted order; SEQ bytes stay where they are.
 // Plain vector stores throughout; integer atomics only on the piece's three counters.
@@ -203,6 +209,50 @@ __global__ __launch_bounds__(SAM_BLOCK) void k_sam_gather(const uint32_t *__rest
     for (uint32_t j = lane; j < n_cigar; j += 64u) cigar[to + j] = cigar_in[from + j];
 }
 
+// The QNAME of a kept line: the bytes before its first tab, which is among the first 255 bytes or the name is too long.
+__global__ __launch_bounds__(SAM_BLOCK) void k_sam_name_len(const uint8_t *__restrict__ text, const uint32_t *__restrict__ line_end,
+                                                             const Line *__restrict__ lines, uint32_t n_lines, uint32_t *__restrict__ n_name,
+                                                             uint32_t *__restrict__ first_bad) {
+    const uint32_t r = (blockIdx.x * SAM_BLOCK + threadIdx.x) >> 6, lane = threadIdx.x & 63u;
+    if (r == n_lines && lane == 0) n_name[r] = 0u; // the scan's closing entry
+    if (r >= n_lines) return;                      // (uniform across the wavefront, as is all below)
+    uint32_t len = 0;
+    if (np2sam::line_kept(lines[r])) {
+        const uint32_t s = r ? line_end[r - 1] + 1u : 0u, e = line_end[r];
+        uint32_t first = 256u;
+        for (uint32_t u = 0; u < 4u && first == 256u; ++u) {
+            const uint32_t i = s + 64u * u + lane;
+            const uint64_t m = __ballot(i < e && text[i] == (uint8_t)'\t');
+            if (m) first = 64u * u + (uint32_t)__builtin_ctzll(m);
+        }
+        if (first == 0u || first > 254u) {
+            if (lane == 0) atomicMin(first_bad, r);
+        } else {
+            len = first;
+        }
+    }
+    if (lane == 0) n_name[r] = len;
+}
+
+__global__ __launch_bounds__(SAM_BLOCK) void k_sam_name_copy(const uint8_t *__restrict__ text, const uint32_t *__restrict__ line_end,
+                                                              const Line *__restrict__ lines, uint32_t n_lines, const uint32_t *__restrict__ kept_off,
+                                                              const uint32_t *__restrict__ name_off, uint64_t rec_base, uint64_t name_base,
+                                                              uint8_t *__restrict__ names, uint64_t *__restrict__ name_ref) {
+    const uint32_t r = (blockIdx.x * SAM_BLOCK + threadIdx.x) >> 6, lane = threadIdx.x & 63u;
+    if (r >= n_lines) return; // (uniform across the wavefront, as is the next one)
+    if (!np2sam::line_kept(lines[r])) return;
+    const uint32_t s = r ? line_end[r - 1] + 1u : 0u, len = name_off[r + 1] - name_off[r]; // (at most 254, inside the line)
+    const uint64_t to = name_base + name_off[r];
+    for (uint32_t j = lane; j < len; j += 64u) names[to + j] = text[s + j];
+    if (lane == 0) name_ref[rec_base + kept_off[r]] = to << 8 | len;
+}
+
+__global__ __launch_bounds__(SAM_BLOCK) void k_sam_gather_u64(const uint64_t *__restrict__ in, const uint32_t *__restrict__ order, uint32_t n,
+                                                               uint64_t *__restrict__ out) {
+    const uint32_t i = blockIdx.x * SAM_BLOCK + threadIdx.x;
+    if (i < n) out[i] = in[order[i]]; // (order holds each of 0 .. n - 1 once)
+}
+
 inline dim3 wave_grid(uint64_t waves) { return dim3((uint32_t)((waves * 64u + SAM_BLOCK - 1) / SAM_BLOCK)); }
 
 } // namespace
@@ -221,6 +271,20 @@ void launch_sam_pack(hipStream_t s, const uint8_t *text, const np2sam::Line *lin
     if (n_lines)
         hipLaunchKernelGGL(k_sam_pack, wave_grid(n_lines), dim3(SAM_BLOCK), 0, s, text, lines, n_lines, kept_off, cig_off, seq_off, rec_base,
                            cig_base, seq_base, tie_by_strand, recs, tids, keys, cigar, seq4);
+}
+void launch_sam_name_len(hipStream_t s, const uint8_t *text, const uint32_t *line_end, const np2sam::Line *lines, uint32_t n_lines,
+                         uint32_t *n_name, uint32_t *first_bad) {
+    hipLaunchKernelGGL(k_sam_name_len, wave_grid((uint64_t)n_lines + 1), dim3(SAM_BLOCK), 0, s, text, line_end, lines, n_lines, n_name, first_bad);
+}
+void launch_sam_name_copy(hipStream_t s, const uint8_t *text, const uint32_t *line_end, const np2sam::Line *lines, uint32_t n_lines,
+                          const uint32_t *kept_off, const uint32_t *name_off, uint64_t rec_base, uint64_t name_base, uint8_t *names,
+                          uint64_t *name_ref) {
+    if (n_lines)
+        hipLaunchKernelGGL(k_sam_name_copy, wave_grid(n_lines), dim3(SAM_BLOCK), 0, s, text, line_end, lines, n_lines, kept_off, name_off, rec_base,
+                           name_base, names, name_ref);
+}
+void launch_sam_gather_u64(hipStream_t s, const uint64_t *in, const uint32_t *order, uint32_t n, uint64_t *out) {
+    if (n) hipLaunchKernelGGL(k_sam_gather_u64, dim3((n + SAM_BLOCK - 1) / SAM_BLOCK), dim3(SAM_BLOCK), 0, s, in, order, n, out);
 }
 void launch_sam_iota(hipStream_t s, uint32_t *vals, uint32_t n) {
     if (n) hipLaunchKernelGGL(k_sam_iota, dim3((n + SAM_BLOCK - 1) / SAM_BLOCK), dim3(SAM_BLOCK), 0, s, vals, n);

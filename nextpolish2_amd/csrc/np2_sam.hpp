@@ -46,6 +46,19 @@ void launch_sam_sorted_sizes(hipStream_t s, const uint32_t *recs_in, const uint3
 void launch_sam_gather(hipStream_t s, const uint32_t *recs_in, const int32_t *tids_in, const uint32_t *cigar_in, const uint32_t *order,
                        const uint32_t *cig_off, uint32_t n, uint32_t *recs, int32_t *tids, uint32_t *cigar);
 
+// NP2_SAM_KEEP_NAMES, after launch_sam_fields.  One wavefront per line: n_name[i] = the bytes of a kept line's QNAME (those
+// before its first tab), 0 for a line that is not kept; entry n_lines is set to 0.  A kept line whose QNAME is empty or longer
+// than 254 bytes: *first_bad = min(*first_bad, i).
+void launch_sam_name_len(hipStream_t s, const uint8_t *text, const uint32_t *line_end, const np2sam::Line *lines, uint32_t n_lines,
+                         uint32_t *n_name, uint32_t *first_bad);
+// ... and after the scan: a kept line's QNAME to names + name_base + name_off[i], and for its record (input order)
+// name_ref[rec_base + kept_off[i]] = offset << 8 | length
+void launch_sam_name_copy(hipStream_t s, const uint8_t *text, const uint32_t *line_end, const np2sam::Line *lines, uint32_t n_lines,
+                          const uint32_t *kept_off, const uint32_t *name_off, uint64_t rec_base, uint64_t name_base, uint8_t *names,
+                          uint64_t *name_ref);
+// out[i] = in[order[i]]
+void launch_sam_gather_u64(hipStream_t s, const uint64_t *in, const uint32_t *order, uint32_t n, uint64_t *out);
+
 } // namespace np2
 
 struct np2_ctx;

@@ -11,6 +11,7 @@
 #include "np2_kcount.hpp"
 #include "np2_kernel_timer.hpp"
 #include "np2_sam.hpp"
+#include "np2_sam_handle.hpp"
 
 #include <zlib.h>
 #include <unistd.h>
@@ -19,21 +20,6 @@
 #include <deque>
 #include <functional>
 #include <thread>
-
-struct np2_sam {
-    int device = 0;
-    np2sam::Refs refs;
-    // resident: records and tids in sorted order, their CIGAR words in that order, SEQ bytes as they were met
-    DevBuf<uint32_t> recs; // SAM_REC_WORDS words a record
-    DevBuf<int32_t> tids;
-    DevBuf<uint32_t> cigar;
-    DevBuf<uint8_t> seq4;
-    uint64_t n_recs = 0, n_cigar = 0, seq_bytes = 0;
-    std::vector<uint64_t> keys; // sorted
-    np2_sam_stats_t stats{};
-    np2_sam() { recs.cached = tids.cached = cigar.cached = seq4.cached = true; } // (released when nothing reads them any more)
-    ~np2_sam() { (void)hipSetDevice(device); }
-};
 
 namespace {
 using np2h::Np2Error;
@@ -288,6 +274,11 @@ struct Build {
     DevBuf<int32_t> tids_in;
     DevBuf<uint64_t> keys_in;
     uint64_t n_recs = 0, n_cigar = 0, seq_bytes = 0, n_records = 0;
+    // NP2_SAM_KEEP_NAMES: offset << 8 | length of each record's name, input order; the lengths of a piece, their scan, the first bad line
+    bool keep_names = false;
+    DevBuf<uint64_t> nref_in;
+    DevBuf<uint32_t> d_nname, d_nmoff, d_nbad;
+    uint64_t name_bytes = 0;
     // one piece
     DevBuf<uint8_t> d_text, d_tmp;
     DevBuf<uint32_t> d_end, d_kept, d_ncig, d_nseq, d_koff, d_coff, d_soff;
@@ -307,6 +298,7 @@ struct Build {
         recs_in.cached = cigar_in.cached = tids_in.cached = keys_in.cached = true; // (every release below follows a drained stream)
         d_text.cached = d_tmp.cached = d_end.cached = d_kept.cached = d_ncig.cached = d_nseq.cached = d_koff.cached = d_coff.cached = true;
         d_soff.cached = d_lines.cached = d_ctr.cached = d_slot.cached = d_noff.cached = d_names.cached = true;
+        nref_in.cached = d_nname.cached = d_nmoff.cached = d_nbad.cached = true;
         e0.make(), e1.make(), e_mid.make();
     }
     ~Build() { (void)hipStreamSynchronize(st); }
@@ -383,7 +375,30 @@ struct Build {
         n_records += n_lines - h->n_empty;
         if (n_recs + kept >= (1ull << 31)) throw Np2Error(NP2_E_UNSUPPORTED, "a SAM input of 2^31 alignment records or more");
         if (n_cigar + n_cig >= 0xFFFF0000ull) throw Np2Error(NP2_E_UNSUPPORTED, "a SAM input of more than 4294901760 CIGAR operations");
+        uint64_t n_name = 0;
+        if (keep_names && kept) { // the names' lengths and where they go; a bad one speaks after every other error of the piece
+            uint32_t *h_name = h_tot + 16; // [0]: the first bad line, [1]: the bytes of all names
+            d_nname.ensure(m), d_nmoff.ensure(m), d_nbad.ensure(1);
+            h_name[0] = 0xFFFFFFFFu;
+            HIPCHK(hipMemcpyAsync(d_nbad.p, h_name, 4, hipMemcpyHostToDevice, st));
+            np2::launch_sam_name_len(st, d_text.p, d_end.p, d_lines.p, n_lines, d_nname.p, d_nbad.p);
+            if (np2::prim_exclusive_sum_u32(st, d_tmp.p, tmp_bytes, d_nname.p, d_nmoff.p, m)) throw Np2Error(NP2_E_DEVICE, "rocprim exclusive_scan failed");
+            HIPCHK(hipMemcpyAsync(h_name, d_nbad.p, 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(h_name + 1, d_nmoff.p + n_lines, 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            HIPCHK(hipGetLastError());
+            if (h_name[0] != 0xFFFFFFFFu) {
+                if (h_name[0] >= n_lines) throw Np2Error(NP2_E_DEVICE, "np2_sam: error line out of range");
+                throw Np2Error(NP2_E_ARG, where + ": line " + std::to_string(first_line + h_name[0]) + ": QNAME is empty or longer than 254 bytes");
+            }
+            n_name = h_name[1];
+            if (n_name > kept * 254u) throw Np2Error(NP2_E_DEVICE, "np2_sam: name bytes out of range");
+        }
         if (kept) {
+            if (keep_names) {
+                grow(nref_in, n_recs, n_recs + kept, st, "names");
+                grow(sam.names, name_bytes, name_bytes + n_name + 1, st, "names");
+            }
             grow(recs_in, n_recs * np2::SAM_REC_WORDS, (n_recs + kept) * np2::SAM_REC_WORDS, st, "records");
             grow(tids_in, n_recs, n_recs + kept, st, "records");
             grow(keys_in, n_recs, n_recs + kept, st, "sort keys");
@@ -392,18 +407,21 @@ struct Build {
             HIPCHK(hipEventRecord(e0.e, st));
             np2::launch_sam_pack(st, d_text.p, d_lines.p, n_lines, d_koff.p, d_coff.p, d_soff.p, n_recs, n_cigar, seq_bytes, tie, recs_in.p,
                                  tids_in.p, keys_in.p, cigar_in.p, sam.seq4.p);
+            if (keep_names)
+                np2::launch_sam_name_copy(st, d_text.p, d_end.p, d_lines.p, n_lines, d_koff.p, d_nmoff.p, n_recs, name_bytes, sam.names.p, nref_in.p);
             HIPCHK(hipEventRecord(e1.e, st));
             HIPCHK(hipStreamSynchronize(st));
             HIPCHK(hipGetLastError());
             sam.stats.pack_ms += elapsed(e0, e1);
         }
-        n_recs += kept, n_cigar += n_cig, seq_bytes += n_seq;
+        n_recs += kept, n_cigar += n_cig, seq_bytes += n_seq, name_bytes += n_name;
     }
 
     // after the last piece: input order -> sorted order
     void finish() {
         const uint32_t n = (uint32_t)n_recs;
         sam.n_recs = n_recs, sam.n_cigar = n_cigar, sam.seq_bytes = seq_bytes;
+        sam.has_names = keep_names, sam.name_bytes = name_bytes;
         sam.stats.records = n_records, sam.stats.kept = n_recs, sam.stats.unmapped = n_records - n_recs;
         sam.stats.cigar_words = n_cigar, sam.stats.seq_bytes = seq_bytes;
         if (seq_bytes) HIPCHK(hipMemsetAsync(sam.seq4.p + seq_bytes, 0, 16, st)); // (what records_to_arrays appends, for a reader of 16-byte words)
@@ -412,7 +430,7 @@ struct Build {
             return;
         }
         const size_t tmp_bytes = np2::prim_temp_bytes((size_t)n + 1);
-        need_device((size_t)n * (8 + 4 + 4 + 4 + 4 + 4 + 40) + (n_cigar + 1) * 4 + tmp_bytes, "sorted records and CIGAR words");
+        need_device((size_t)n * (8 + 4 + 4 + 4 + 4 + 4 + 40 + (keep_names ? 8 : 0)) + (n_cigar + 1) * 4 + tmp_bytes, "sorted records and CIGAR words");
         DevBuf<uint64_t> keys_out;
         DevBuf<uint32_t> vals_in, vals_out, sizes, offs;
         keys_out.cached = vals_in.cached = vals_out.cached = sizes.cached = offs.cached = true; // (released after the last synchronisation below)
@@ -427,6 +445,10 @@ struct Build {
         if (np2::prim_exclusive_sum_u32(st, d_tmp.p, tmp_bytes, sizes.p, offs.p, (size_t)n + 1))
             throw Np2Error(NP2_E_DEVICE, "rocprim exclusive_scan failed");
         np2::launch_sam_gather(st, recs_in.p, tids_in.p, cigar_in.p, vals_out.p, offs.p, n, sam.recs.p, sam.tids.p, sam.cigar.p);
+        if (keep_names) {
+            sam.name_ref.ensure(n);
+            np2::launch_sam_gather_u64(st, nref_in.p, vals_out.p, n, sam.name_ref.p);
+        }
         HIPCHK(hipEventRecord(e1.e, st));
         sam.keys.resize(n);
         HIPCHK(hipMemcpyAsync(sam.keys.data(), keys_out.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
@@ -442,11 +464,12 @@ struct Build {
 };
 
 // everything: `rd` has its source set and has not been started
-void build(np2_ctx *cx, np2_sam &sam, Reader &rd, const np2_sam_opts_t *opts, size_t bytes_bound) {
+void build(np2_ctx *cx, np2_sam &sam, Reader &rd, const np2_sam_opts_t *opts, size_t bytes_bound, uint32_t flags = 0) {
     HIPCHK(hipSetDevice(cx->device));
     sam.device = cx->device;
     Build b(cx, sam);
     b.tie = opts ? (opts->tie_by_strand ? 1u : 0u) : 1u;
+    b.keep_names = (flags & NP2_SAM_KEEP_NAMES) != 0;
     rd.start(bytes_bound);
     Piece p;
     for (;;) {
@@ -514,11 +537,16 @@ int ref_tid(const np2_sam *s, const char *name) {
 extern "C" {
 
 int np2_sam_open(np2_ctx_t *cx, const char *const *paths, int n_paths, const np2_sam_opts_t *opts, np2_sam_t **out) {
+    return np2_sam_open_ex(cx, paths, n_paths, opts, 0u, out);
+}
+
+int np2_sam_open_ex(np2_ctx_t *cx, const char *const *paths, int n_paths, const np2_sam_opts_t *opts, uint32_t flags, np2_sam_t **out) {
     if (out) *out = nullptr;
     bool touched = false;
     return np2h::abi_guard([&] {
         // the arguments and the files, before the first device call
         if (!cx || !out || !paths || n_paths < 1) throw Np2Error(NP2_E_ARG, "np2_sam_open: NULL argument or no path");
+        if (flags & ~(uint32_t)NP2_SAM_KEEP_NAMES) throw Np2Error(NP2_E_ARG, "np2_sam_open_ex: unknown flag bits");
         Hooks hooks;
         Reader rd(hooks);
         int n_stdin = 0;
@@ -535,7 +563,7 @@ int np2_sam_open(np2_ctx_t *cx, const char *const *paths, int n_paths, const np2
         }
         touched = true;
         std::unique_ptr<np2_sam> sam(new np2_sam());
-        build(cx, *sam, rd, opts, 0);
+        build(cx, *sam, rd, opts, 0, flags);
         *out = sam.release();
         return NP2_OK;
     }, [&](int code, const std::string &msg) {

@@ -22,7 +22,8 @@ IO_SYMBOLS = ["np2_fasta_open", "np2_fasta_next", "np2_fasta_close", "np2_yak_lo
               "np2_sam_n_refs", "np2_sam_ref_name", "np2_sam_stats", "np2_contig_from_sam", "np2_sam_parse_bytes", "np2_sam_export",
               "np2_sradapt_bytes", "np2_sradapt_files", "np2_sradapt_last_stats", "np2_sradapt_last_kernel_ms", "np2_kcount_files_ad",
               "np2_kcount_files_to_dumps_ad", "np2_ctx_create_from_reads_ad", "np2_bgzf_deflate_device", "np2_bgzf_deflate_host",
-              "np2_bgzf_writer_open", "np2_bgzf_writer_write", "np2_bgzf_writer_close"]
+              "np2_bgzf_writer_open", "np2_bgzf_writer_write", "np2_bgzf_writer_close", "np2_sam_open_ex", "np2_sam_write_bam",
+              "np2_sam_bam_stream", "np2_bamout_host", "np2_sam_export_names"]
 
 
 class np2_front_opts_t(C.Structure):
@@ -46,6 +47,14 @@ class np2_sam_opts_t(C.Structure):
 class np2_sam_stats_t(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("lines", "records", "unmapped", "kept", "cigar_words", "seq_bytes")] + \
                [(n, C.c_float) for n in ("parse_ms", "pack_ms", "sort_ms", "read_ms")]
+
+
+class np2_bamout_stats_t(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("records", "stream_bytes", "file_bytes", "blocks", "bins", "chunks")] + \
+               [(n, C.c_float) for n in ("sizes_ms", "emit_ms", "deflate_ms", "index_ms")]
+
+
+NP2_SAM_KEEP_NAMES = 1
 
 
 class FrontOpts:
@@ -305,6 +314,13 @@ def _bind_sam(L):
     L.np2_sam_parse_bytes.argtypes = [C.c_int, vp, C.c_uint64, so, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
                                       C.POINTER(C.c_uint64), ss]
     L.np2_sam_export.argtypes = [vp, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_uint64)]
+    u64p, bs = C.POINTER(C.c_uint64), C.POINTER(np2_bamout_stats_t)
+    L.np2_sam_open_ex.argtypes = [vp, C.POINTER(C.c_char_p), C.c_int, so, C.c_uint32, C.POINTER(vp)]
+    L.np2_sam_write_bam.argtypes = [vp, vp, C.c_char_p, C.c_char_p, bs]
+    L.np2_sam_bam_stream.argtypes = [vp, vp, C.POINTER(vp), u64p]
+    L.np2_sam_export_names.argtypes = [vp, vp, C.POINTER(vp), u64p, C.POINTER(vp), u64p]
+    L.np2_bamout_host.argtypes = [vp, vp, vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, vp, C.c_uint64, vp, C.POINTER(C.c_char_p), vp,
+                                  C.c_int, C.c_char_p, C.c_char_p, C.POINTER(vp), u64p, bs]
 
 
 def _bind_kcount(L):
@@ -733,14 +749,18 @@ class Sam:
     coordinate-sorted on the device of Polisher `pol`, the sorted records, their CIGAR words and the packed SEQ left resident
     there (include/np2_io.h has the rule).  tie: "strand" orders records at one position by strand, as samtools sort does;
     "input" leaves them in input order.  Read-only once open: contig_from_sam may be called from several threads, each with
-    a Polisher of its own on that device."""
+    a Polisher of its own on that device.  keep_names=True (np2_sam_open_ex, NP2_SAM_KEEP_NAMES) keeps the QNAMEs resident too:
+    write_bam needs them."""
 
-    def __init__(self, pol, paths, tie="strand"):
+    def __init__(self, pol, paths, tie="strand", keep_names=False):
         L = _bind()
         o = _sam_opts(tie)
         arr, n = _paths(paths)
         self._h = C.c_void_p()
-        _io_check(L.np2_sam_open(pol._h, arr, n, C.byref(o), C.byref(self._h)))
+        if keep_names:  # np2_sam_open_ex: the QNAMEs stay resident too, for write_bam
+            _io_check(L.np2_sam_open_ex(pol._h, arr, n, C.byref(o), NP2_SAM_KEEP_NAMES, C.byref(self._h)))
+        else:
+            _io_check(L.np2_sam_open(pol._h, arr, n, C.byref(o), C.byref(self._h)))
 
     def refs(self):
         L = _bind()
@@ -762,6 +782,35 @@ class Sam:
         _io_check(L.np2_sam_export(pol._h, self._h, C.byref(pr), C.byref(pt), C.byref(pc), C.byref(ps), C.byref(n)))
         return _sam_arrays(L, pr, pt, pc, ps, n.value, self.stats())
 
+    def write_bam(self, pol, path, bai=None):
+        """np2_sam_write_bam: the coordinate-sorted BAM `path` and its index (`bai`, default path + ".bai"), assembled,
+        compressed and indexed on the device; needs keep_names=True.  -> the np2_bamout_stats_t fields as a dict."""
+        st = np2_bamout_stats_t()
+        _io_check(_bind().np2_sam_write_bam(pol._h, self._h, os.fspath(path).encode(), os.fspath(bai).encode() if bai is not None else None,
+                                            C.byref(st)))
+        return _bamout_stats_dict(st)
+
+    def bam_stream(self, pol):
+        """np2_sam_bam_stream: the uncompressed BAM stream as bytes (tests)"""
+        L = _bind()
+        p, n = C.c_void_p(), C.c_uint64()
+        _io_check(L.np2_sam_bam_stream(pol._h, self._h, C.byref(p), C.byref(n)))
+        try:
+            return C.string_at(p.value, n.value)
+        finally:
+            L.np2_free(p)
+
+    def export_names(self, pol):
+        """np2_sam_export_names: (names uint8, name_ref uint64: offset << 8 | length per record in sorted order)"""
+        L = _bind()
+        pn, pr, nb, n = C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
+        _io_check(L.np2_sam_export_names(pol._h, self._h, C.byref(pn), C.byref(nb), C.byref(pr), C.byref(n)))
+        try:
+            return (np.frombuffer(C.string_at(pn.value, nb.value), dtype=np.uint8).copy(),
+                    np.frombuffer(C.string_at(pr.value, n.value * 8), dtype=np.uint64).copy())
+        finally:
+            L.np2_free(pn), L.np2_free(pr)
+
     def close(self):
         if self._h:
             _bind().np2_sam_close(self._h)
@@ -772,6 +821,35 @@ class Sam:
             self.close()
         except Exception:
             pass
+
+
+def _bamout_stats_dict(st):
+    return {n: (int if t is C.c_uint64 else float)(getattr(st, n)) for n, t in np2_bamout_stats_t._fields_}
+
+
+def bamout_host(recs, tids, cigar, seq4, names, name_ref, refs, path=None, bai=None, want_stream=True):
+    """np2_bamout_host, the host twin of Sam.write_bam (no device): recs (BAMREC_DTYPE), tids, cigar and seq4 as Sam.export
+    returns them, names / name_ref as Sam.export_names does, refs [(name, length)].  Writes `path` and its index when path is
+    given.  -> (stream bytes or None, stats dict)."""
+    L = _bind()
+    recs = np.ascontiguousarray(recs, dtype=BAMREC_DTYPE)
+    tids, cigar = np.ascontiguousarray(tids, dtype=np.int32), np.ascontiguousarray(cigar, dtype=np.uint32)
+    seq4, names = np.ascontiguousarray(seq4, dtype=np.uint8), np.ascontiguousarray(names, dtype=np.uint8)
+    name_ref = np.ascontiguousarray(name_ref, dtype=np.uint64)
+    if not (len(recs) == len(tids) == len(name_ref)):
+        raise ValueError("recs, tids and name_ref must have one entry per record")
+    rn = (C.c_char_p * max(len(refs), 1))(*[n.encode() for n, _ in refs])
+    rl = np.ascontiguousarray([l for _, l in refs], dtype=np.uint32)
+    ptr = lambda a: a.ctypes.data if len(a) else None
+    p, n, st = C.c_void_p(), C.c_uint64(), np2_bamout_stats_t()
+    _io_check(L.np2_bamout_host(ptr(recs), ptr(tids), ptr(cigar), ptr(seq4), len(recs), len(cigar), len(seq4), ptr(names), len(names),
+                                ptr(name_ref), rn, ptr(rl), len(refs), os.fspath(path).encode() if path is not None else None,
+                                os.fspath(bai).encode() if bai is not None else None, C.byref(p) if want_stream else None,
+                                C.byref(n) if want_stream else None, C.byref(st)))
+    try:
+        return (C.string_at(p.value, n.value) if want_stream else None), _bamout_stats_dict(st)
+    finally:
+        L.np2_free(p)
 
 
 def _sam_arrays(L, pr, pt, pc, ps, n, stats):
@@ -787,7 +865,7 @@ def _sam_arrays(L, pr, pt, pc, ps, n, stats):
 
 def contig_from_sam(pol, sam, name, ref, opts=None):
     """The records of reference `name` of a resident Sam -> packed pileup resident in HBM (GPU columnariser).  -S
-    (use_secondary) is not supported from SAM: use a BAM."""
+    (use_secondary) is not supported from SAM: use a BAM (Sam.write_bam or python -m nextpolish2_amd.samsort writes one)."""
     L = _bind()
     ref = np.frombuffer(ref, dtype=np.uint8) if isinstance(ref, (bytes, bytearray)) else np.ascontiguousarray(ref, dtype=np.uint8)
     o = (opts or FrontOpts()).c()

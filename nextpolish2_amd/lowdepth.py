@@ -5,6 +5,8 @@ mapped by HiFi reads, and this tells a user which regions those are).
     python -m nextpolish2_amd.lowdepth reads.map.sort.bam genome.fa[.gz] > genome.filter.fa
           [-d 3] [-l 1000] [--min_fra 0.8] [--min_mapq 0] [--exclude_flags 4] [--bed F] [--low_bed F] [--bedgraph F] [-o F]
 
+The mapping is a coordinate-sorted, indexed BAM; from the mapper's SAM text `python -m nextpolish2_amd.samsort` writes one.
+
 -o F writes the FASTA to F instead of standard output; an F ending in .gz or .bgz is written as BGZF, compressed on the device.
 
 Depth counts alignment records (include/np2_io.h, np2_depth_*): a record is counted unless one of its flag bits is in

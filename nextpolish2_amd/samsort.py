@@ -1,0 +1,65 @@
+"""The mapper's SAM text -> the coordinate-sorted BAM and its .bai: the `samtools sort -o hifi.map.sort.bam -` and
+`samtools index` steps of the reference's recipe, on the GPU.
+
+Usage: python -m nextpolish2_amd.samsort map.sam[.gz]|- [more.sam ...] -o hifi.map.sort.bam [--sam_tie strand|input]
+
+The text (plain or gzip; "-" is standard input) is parsed and sorted on the device (io.Sam with its names kept), the BAM
+records are assembled there, compressed as BGZF there, and the index is derived there from the records' offsets and the
+blocks' compressed sizes (include/np2_io.h has the rule: SAM specification 4.2 and 5.2; not compared with samtools' files).
+QNAME, FLAG, RNAME, POS, MAPQ, CIGAR and SEQ are carried; QUAL, RNEXT, PNEXT, TLEN, the optional fields, unmapped records and
+header lines other than @HD / @SQ are not.  The file is what -S (use_secondary), lowdepth and interval sharding need."""
+import argparse
+import os
+import sys
+import time
+
+
+def build_parser():
+    from . import io as np2io
+    p = argparse.ArgumentParser(prog="nextpolish2_amd.samsort", description="sort the mapper's SAM text into an indexed BAM on the GPU")
+    p.add_argument("sam", nargs="+", metavar="map.sam[.gz]|-", help="SAM text, plain or gzip; - is standard input (once)")
+    p.add_argument("-o", "--out", required=True, metavar="hifi.map.sort.bam", help="the BAM; its index is written next to it as <out>.bai")
+    p.add_argument("--sam_tie", choices=np2io.SAM_TIES, default="strand",
+                   help="records at one position are ordered by strand, as samtools sort orders them, or stay in input order [strand]")
+    p.add_argument("--device", type=int, default=0)
+    return p
+
+
+def parse_args(argv=None):
+    """every argument error stops here, before a device is touched"""
+    parser = build_parser()
+    a = parser.parse_args(argv)
+    if a.sam.count("-") > 1:
+        parser.error("standard input is given twice")
+    for f in a.sam:
+        if f != "-" and not os.path.isfile(f):
+            parser.error(f"cannot open {f}")
+    return a
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    from . import Polisher
+    from . import io as np2io
+    from .api import Np2Error
+    t0 = time.time()
+    pol = Polisher([], device=a.device)
+    try:
+        sam = np2io.Sam(pol, a.sam, tie=a.sam_tie, keep_names=True)
+        try:
+            st = sam.write_bam(pol, a.out)
+            parsed = sam.stats()
+        finally:
+            sam.close()
+    except Np2Error as e:
+        raise SystemExit(f"Error: {e}")
+    finally:
+        pol.close()
+    print(f"[samsort] {parsed['kept']} of {parsed['records']} records -> {a.out} ({st['file_bytes']} bytes, {st['blocks']} blocks) and "
+          f"{a.out}.bai ({st['bins']} bins, {st['chunks']} chunks) in {time.time() - t0:.3f} s; kernels: emit {st['emit_ms']:.3f} ms, "
+          f"deflate {st['deflate_ms']:.3f} ms, index {st['index_ms']:.3f} ms", file=sys.stderr)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
