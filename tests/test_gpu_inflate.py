@@ -3,6 +3,7 @@ blocks uploaded as they lie in the file, inflated one wavefront per block, recor
 read by the columnariser out of the inflated stream — against the host path (libdeflate / zlib pool + record walk) and the
 oracle's front end."""
 import os
+import re
 import struct
 import subprocess
 import sys
@@ -13,6 +14,7 @@ import pytest
 
 from nextpolish2_amd import Opts, Polisher
 from nextpolish2_amd import io as np2io
+from nextpolish2_amd.api import Np2Error
 from nextpolish2_amd.bamio import pileup_to_records, records_to_arrays, write_bam
 from nextpolish2_amd.synth import Synth
 from oracle import np2_oracle as orc
@@ -63,13 +65,18 @@ def test_inflate_kernel_equals_zlib():
     exp = b"".join(want)
     assert len(got) == len(exp)
     assert got.tobytes() == exp
-    # a damaged block is reported, not decoded into something else silently — and never written past its ISIZE
+    # a damaged block is reported, not decoded into something else silently: a flipped payload bit ends in a status of the
+    # inflater or, where the stream still inflates to ISIZE bytes, in the CRC's mismatch; either names block 0
     bad = bytearray(blocks[3])
     bad[30] ^= 0x10
-    with pytest.raises(Exception):
-        g2, _ = np2io.bgzf_inflate_device(pol, bytes(bad))
-        assert g2.tobytes() != want[3]
-        raise RuntimeError("decoded to different bytes (acceptable: deflate carries no checksum of its own)")
+    with pytest.raises(Np2Error) as e:
+        np2io.bgzf_inflate_device(pol, bytes(bad))
+    msg = str(e.value)
+    assert e.value.code == -1, msg
+    assert re.search(r"BGZF inflate failed \(block 0, status \d+\)", msg) or "BGZF CRC32 mismatch (block 0)" in msg, msg
+    # ... and the context inflates the undamaged block as before
+    g3, _ = np2io.bgzf_inflate_device(pol, blocks[3])
+    assert g3.tobytes() == want[3]
 
 
 def _contig(tmp_path, s, env):
