@@ -1,6 +1,6 @@
 """Minimal BAM + BAI writer (BGZF on zlib) for synthetic test inputs, and pileup <-> record helpers.
 
-The product reads BAM through csrc/np2_io.cpp; this writer exists so that tests and examples can create
+The product reads BAM through csrc/np2_bamfile.cpp (host) and csrc/np2_fetch_gpu.cpp (device); this writer exists so that tests and examples can create
 coordinate-sorted, indexed BAM files without samtools/minimap2 (absent here; reference test/hh.sh:8-10)."""
 import struct
 import zlib
@@ -250,7 +250,7 @@ def write_bam_raw(path, refs, contigs, level=1, threads=16):
 
 def read_bam(path):
     """-> (refs [(name, length)], records) of a BAM file, records as the dicts write_bam takes.  A plain sequential
-    reader for tests (BGZF blocks are concatenated gzip members); the product reads BAM through csrc/np2_io.cpp."""
+    reader for tests (BGZF blocks are concatenated gzip members); the product reads BAM through csrc/np2_bamfile.cpp and csrc/np2_fetch_gpu.cpp."""
     import gzip
     with gzip.open(path, "rb") as f:
         data = f.read()

@@ -1,4 +1,4 @@
-// The BGZF block header, parsed in one place for every reader of np2_io.cpp: the FILE* stream that reads a BAM's header,
+// The BGZF block header, parsed in one place for every reader of a BAM (np2_bamfile.hpp, np2_fetch_gpu.cpp): the FILE* stream that reads a BAM's header,
 // the mmap reader of the host pool and the pinned pieces of the device path.  Host-only: no HIP here, so that a plain C++
 // compiler builds it (tests/tools/bgzf_test.cpp, under the address and undefined-behaviour sanitizers).
 #pragma once

@@ -1,6 +1,6 @@
 // Host driver of the mapping-depth kernels (np2_depth.hip): depth_device runs events -> scan -> runs -> keep over records
 // that are on the device already and brings back the kept runs and the counters (the per-base array only on request);
-// np2_depth_from_records uploads host records first.  np2_depth_from_bam (np2_io.cpp, next to the fetchers) ends here too.
+// np2_depth_from_records uploads host records first.  np2_depth_from_bam (np2_bamread.cpp, over the record source of the readers) ends here too.
 #include "np2_ctx.hpp"
 #include "np2_depth.hpp"
 #include "np2_kernel_timer.hpp"

@@ -1,5 +1,5 @@
 // GPU read extraction (np2_inflate.hip, np2_crc32.hip): BGZF inflate and CRC check, one wavefront per block, and the record walk over the inflated BAM
-// stream along the .bai linear index.  Host side: np2_io.cpp (GpuFetch).
+// stream along the .bai linear index.  Host side: np2_fetch_gpu.cpp (GpuFetch).
 #pragma once
 #include <cstdint>
 #include <hip/hip_runtime.h>

@@ -1,4 +1,4 @@
-// The persistent thread pool behind every parallel loop of np2_io.cpp, the cache of large host blocks and the byte buffer on it.
+// The persistent thread pool behind every parallel loop of the input side (np2_bamfile.cpp, np2_frontend.cpp, np2_fetch_gpu.cpp), the cache of large host blocks and the byte buffer on it.
 // Host-only: no HIP here, so that a plain C++ compiler builds it (tests/tools/iopool_test.cpp, under the thread and address sanitizers).
 #pragma once
 #include <algorithm>

@@ -1,4 +1,4 @@
-// Launchers of the SAM kernels (np2_sam.hip) for the host driver (np2_sam_host.cpp), and the door np2_io.cpp opens for it.
+// Launchers of the SAM kernels (np2_sam.hip) for the host driver (np2_sam_host.cpp), and the door np2_frontend.cpp opens for it.
 #pragma once
 #include <cstdint>
 #include <hip/hip_runtime.h>
@@ -65,7 +65,7 @@ struct np2_ctx;
 struct np2_contig;
 namespace np2h {
 // np2_contig_from_records over records and CIGAR words on the host and SEQ bytes that are on cx's device already (d_seq4:
-// seq4_bytes bytes, complete; seq_off indexes it).  np2_io.cpp, next to the front end.
+// seq4_bytes bytes, complete; seq_off indexes it).  np2_frontend.cpp, next to the front end.
 void contig_from_device_seq(np2_ctx *cx, const uint8_t *ref, uint32_t L, const np2_bamrec_t *recs, uint32_t n_recs, const uint32_t *cigar,
                             const uint8_t *d_seq4, uint64_t seq4_bytes, const np2_front_opts_t *opts, np2_contig **out);
 } // namespace np2h

@@ -321,3 +321,46 @@ def test_shards_read_straight_from_the_bam_number_their_reads_contig_wide(tmp_pa
     err = capfd.readouterr().err
     # (the whole contig once; then 2 and 3 shards, each read once by ShardFromBam and once by polish_sharded_bam_local)
     assert (err.count("fetch_records_gpu:") >= 11) == (inflate == "gpu"), err[-1500:]
+
+
+def test_shard_outlives_the_next_fetch_on_its_bam_handle(tmp_path, monkeypatch, capfd):
+    """np2_shard_bam_begin reads the device reader's records where they lie, in the handle's pinned blocks, and keeps no
+    pointer to them: a fetch of another reference through the same handle between begin and finish (it takes those blocks
+    over) changes nothing.  The stitched result of three shards is byte-identical under the device reader and the host pool."""
+    from nextpolish2_amd import io as np2io
+    from nextpolish2_amd.bamio import pileup_to_records, write_bam
+    from nextpolish2_amd.dist import _run_local
+    s = Synth(200000, seed=851, diploid=True, name="long1")
+    other = Synth(90000, seed=852, name="other")  # (about as many records as shard 0's zone holds: they overwrite its block)
+    recs = pileup_to_records(other.pileup, tid=0, rng=np.random.default_rng(7), decorate=True) + \
+        pileup_to_records(s.pileup, tid=1, rng=np.random.default_rng(8), decorate=True)
+    recs.sort(key=lambda r: (r["tid"], r["pos"]))
+    bam_path = str(tmp_path / "m.bam")
+    write_bam(bam_path, [("other", other.pileup.L), ("long1", s.pileup.L)], recs)
+    pol = Polisher([s.yak(21)])
+    ref, other_ref = s.pileup.ref.tobytes(), other.pileup.ref.tobytes()
+    cuts = np2io.shard_cuts(len(ref), 3)
+    monkeypatch.setenv("NP2_IO_PROFILE", "1")
+
+    def stitched(inflate):
+        monkeypatch.setenv("NP2_INFLATE", inflate)
+        ctxs = [pol.clone() for _ in cuts]
+        bams = [np2io.Bam(bam_path) for _ in cuts]
+        sb0 = np2io.ShardFromBam(ctxs[0], bams[0], "long1", ref, cuts[0][0], cuts[0][1], 20000)
+        np2io.contig_from_bam(ctxs[0], bams[0], "other", other_ref).free()  # the handle's next fetch, before shard 0 is finished
+        sbs = [sb0] + [np2io.ShardFromBam(ctxs[k], bams[k], "long1", ref, cuts[k][0], cuts[k][1], 20000) for k in (1, 2)]
+        all_off = np.concatenate([sb.own_offsets for sb in sbs])
+        fin = [sb.finish(all_off) for sb in sbs]
+        plans = [f[1] for f in fin]
+        runs = [ShardRun(ctxs[k], None, plans[k], Opts(), 1024, resident=fin[k][0]) for k in range(3)]
+        try:
+            b, p = _run_local(runs, plans, fin[0][2], Opts(), True)
+            return np.array(b).tobytes(), np.array(p).tobytes(), capfd.readouterr().err
+        finally:
+            for r in runs:
+                r.close()
+
+    b_gpu, p_gpu, err_gpu = stitched("gpu")
+    b_host, p_host, err_host = stitched("libdeflate")
+    assert err_gpu.count("fetch_records_gpu:") >= 4 and "fetch_records_gpu:" not in err_host, err_gpu[-1500:]
+    assert len(b_gpu) > 190000 and b_gpu == b_host and p_gpu == p_host
