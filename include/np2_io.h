@@ -501,7 +501,8 @@ int np2_sam_export(np2_ctx_t *ctx, np2_sam_t *sam, np2_bamrec_t **recs, int32_t 
  *     each: block_size, refID = tid, pos, l_read_name = length + 1, mapq, bin = reg2bin(pos, pos + max(span, 1)) with span the
  *     summed lengths of the M, D, N, = and X operations, n_cigar_op, flag, l_seq, next_refID = -1, next_pos = -1, tlen = 0,
  *     the name with NUL, the CIGAR words, the (l_seq + 1) / 2 packed SEQ bytes as they lie at seq_off with the low nibble of
- *     an odd last byte 0, and l_seq bytes 0xFF.  QUAL, RNEXT, PNEXT, TLEN and the optional fields are not carried.
+ *     an odd last byte 0, and l_seq bytes 0xFF.  QUAL, RNEXT, PNEXT, TLEN and the optional fields are not carried (a handle
+ *     opened with NP2_SAM_KEEP_ALL carries them: the full stream, below).
  *   Refusals, each naming the record (0-based in the resident order) or the reference, all raised before the output file is
  *     created: a record with pos < 0 (SAM POS 0) is NP2_E_ARG; n_cigar > 65535 is NP2_E_UNSUPPORTED (no CG tag is written);
  *     a reference with LN > 2^29, or a record with pos + max(span, 1) > 2^29, is NP2_E_UNSUPPORTED (BAI's limit; there is no
@@ -515,7 +516,8 @@ int np2_sam_export(np2_ctx_t *ctx, np2_sam_t *sam, np2_bamrec_t **recs, int32_t 
  *     ioffset[w] = beg of the first record in file order that overlaps window w, an empty window takes the previous one's
  *     value, leading empty windows are 0.  A reference without records has n_bin = 0 and n_intv = 0.  No pseudo-bin 37450
  *     and no n_no_coor.
- *   Out of scope: QUAL, RNEXT, PNEXT, TLEN and optional fields; header lines other than @HD and @SQ; unmapped records; CSI;
+ *   Out of scope: QUAL, RNEXT, PNEXT, TLEN, optional fields and header lines other than @HD and @SQ (all of them carried by
+ *     the full stream, NP2_SAM_KEEP_ALL, below); unmapped records; CSI;
  *     the 37450 pseudo-bin; compression levels; several ranks; inputs larger than one device's memory; BAM to BAM.
  * The stream is assembled (k_bam_emit), compressed (k_bgzf_deflate) and indexed on the device; it never passes through host
  * memory.  Test hook, read once per call: NP2_BGZF_TEST_BATCH (blocks per batch). */
@@ -549,6 +551,78 @@ int np2_bamout_host(const np2_bamrec_t *recs, const int32_t *tids, const uint32_
 /* the name bytes and name_ref array of a resident SAM opened with NP2_SAM_KEEP_NAMES, for the host twin and parity tests:
  * both released with np2_free, NULL when empty */
 int np2_sam_export_names(np2_ctx_t *ctx, np2_sam_t *sam, uint8_t **names, uint64_t *name_bytes, uint64_t **name_ref, uint64_t *n_recs);
+
+/* ---- the full BAM: QUAL, the mate fields, the optional fields and the header lines carried too ---------------------------------
+ * THE RULE IS DEFINED HERE, on the SAM specification sections 1.4, 1.5 and 4.2.4; it is not pinned against samtools.
+ * Everything here is opt-in: without NP2_SAM_KEEP_ALL np2_sam_open_ex, np2_sam_write_bam and np2_sam_bam_stream launch what
+ * they launch without it and write the same bytes (the lean stream above).
+ *   Flag: np2_sam_open_ex with NP2_SAM_KEEP_ALL, which implies NP2_SAM_KEEP_NAMES.
+ *   What the handle keeps: per kept record a TAIL in a device buffer of its own, written where the record was met, as the names
+ *     are: next_refID i32, next_pos i32, tlen i32, aux_len u32, then l_seq quality bytes if QUAL is present, then aux_len bytes
+ *     of binary optional fields, then zero bytes up to a multiple of 4 (every tail begins at a word).  Per record
+ *     tail_ref = offset << 1 | has_qual (u64) travels through the sort as name_ref does.  np2_bamrec_t and np2_sam_stats_t keep
+ *     their layouts.
+ *   RNEXT: "*" is -1, "=" the record's own tid, any other name must be an @SQ name (else NP2_E_ARG).  PNEXT: decimal
+ *     0..2^31-1, stored minus 1.  TLEN: an optional sign and a magnitude of at most 2^31-1.  A non-digit or an overflow is
+ *     NP2_E_ARG.
+ *   QUAL: "*" means no quality bytes; the writer then puts l_seq bytes 0xFF, as the lean stream does.  Otherwise QUAL is exactly
+ *     l_seq bytes, each in '!'..'~', stored minus 33.  NP2_E_ARG: a length that differs from SEQ's (an empty QUAL included), a
+ *     byte outside that range, QUAL given while SEQ is "*".
+ *   Optional fields: every further tab-separated field is TAG:TYPE:VALUE, kept in input order.  TAG is [A-Za-z][A-Za-z0-9].
+ *     A: one byte '!'..'~'.
+ *     i: an optional sign and decimal digits, value v, stored in the smallest type that holds it: v >= 0: C up to 255, S up to
+ *        65535, I up to 2^32-1; v < 0: c down to -128, s down to -32768, i down to -2^31; anything outside is NP2_E_ARG.
+ *     f: [-+]?digits[.digits]?([eE][-+]?digits)?.  The value is the double M x 10^e or M / 10^-e from ONE IEEE multiplication
+ *        or division, cast to float; M is all the digits read as an integer, e the exponent minus the number of fraction
+ *        digits.  Accepted only when M < 2^53 and |e| <= 22: both operands are then exact and the double is correctly rounded,
+ *        which is what (float)strtod() gives.  inf, nan and anything outside that window are NP2_E_UNSUPPORTED.  (The library
+ *        is built without fast-math; this needs that.)
+ *     Z: bytes ' '..'~', possibly none, stored with a NUL.  H: an even number of hex digits, stored as the text with a NUL.
+ *     B: [cCsSiIf](,number)*, zero elements allowed, every element range-checked against the subtype (an f element by the f
+ *        rule); stored as B, subtype, u32 count, the values.
+ *     NP2_E_ARG: a field shorter than 5 bytes, a malformed TAG or colon, an unknown TYPE.  Duplicate tags are not checked, CG
+ *     is not special, n_cigar > 65535 stays refused by the writer.
+ *   Which line speaks: within one line the first bad field in field order.  Within a piece of text tail errors rank with name
+ *     errors: the errors of the lean parse speak first, then the first line in input order with a bad name or tail, giving the
+ *     1-based line and the field, or the TAG where there is one.
+ *   Header text of the full stream: "@HD\tVN:1.6\tSO:coordinate\n", the @SQ lines as in the lean stream, then every other header
+ *     line of the input except @HD, in input order, files in argument order, each without its '\r'; a line byte-identical to an
+ *     earlier one is dropped.  The host reads the header.
+ *   Stream and index: a record is the lean stream's bytes up to SEQ with next_refID, next_pos and tlen taken from the tail,
+ *     then the quality bytes or the run of 0xFF, then the optional fields' bytes; block_size grows by aux_len.  File and index
+ *     rules are unchanged: blocks are cut every 65280 bytes, the .bai comes from the records' offsets, the refusals are the same.
+ *   Memory: the tails take about 1.5 bytes per base (with the packed SEQ: one for the quality, half for SEQ) plus the optional
+ *     fields and 16 bytes a record; device memory that does not suffice is NP2_E_NOMEM, and the message says how much was needed.
+ *     The lean handle needs about a third of that.
+ *   Out of scope: unmapped records (counted and dropped, as before); a CG tag for long CIGARs, CSI and the 37450 pseudo-bin; BAM
+ *     to BAM; several ranks; validating what a tag means; the sub-fields of the input's @HD line. */
+#define NP2_SAM_KEEP_ALL 2u
+/* the tail bytes and the tail_ref array (sorted order) of a resident SAM opened with NP2_SAM_KEEP_ALL: both released with
+ * np2_free, NULL when empty */
+int np2_sam_export_tails(np2_ctx_t *ctx, np2_sam_t *sam, uint8_t **tails, uint64_t *tail_bytes, uint64_t **tail_ref, uint64_t *n_recs);
+/* the header text of the full stream; borrowed until np2_sam_close.  A handle opened without NP2_SAM_KEEP_ALL: NP2_E_ARG */
+int np2_sam_header_text(np2_sam_t *sam, const char **text, uint64_t *n);
+/* k_sam_tail_len with its scan and k_sam_tail_emit (HIP events, summed over the pieces), and the bytes of all tails; any pointer
+ * may be NULL; zeros for a handle opened without NP2_SAM_KEEP_ALL */
+int np2_sam_tail_stats(np2_sam_t *sam, float *tail_len_ms, float *tail_emit_ms, uint64_t *tail_bytes);
+/* np2_bamout_host with the tails (tail_bytes of them; every offset a multiple of 4), tail_ref[i] per record and the header text
+ * as np2_sam_header_text returns it.  tail_ref == NULL: the lean records; header_text == NULL: the lean header.  No device. */
+int np2_bamout_host_full(const np2_bamrec_t *recs, const int32_t *tids, const uint32_t *cigar, const uint8_t *seq4, uint64_t n_recs,
+                         uint64_t n_cigar_words, uint64_t seq_bytes, const uint8_t *names, uint64_t name_bytes, const uint64_t *name_ref,
+                         const uint8_t *tails, uint64_t tail_bytes, const uint64_t *tail_ref, const char *header_text, uint64_t header_bytes,
+                         const char *const *ref_names, const uint32_t *ref_lens, int n_refs, const char *bam_path, const char *bai_path,
+                         uint8_t **S, uint64_t *n_S, np2_bamout_stats_t *stats);
+/* Host only, no device: SAM text in memory, header included, walked as ONE piece by the one-lane text of the rule
+ * (csrc/np2_samtail_core.hpp), which is what the kernels' lanes run.  Per alignment line that is not empty, in input order
+ * (*n_lines of them): status[i] = 0 for a kept record, whose tail lies at tail_ref[i] >> 1 of *tails (tail_ref[i] & 1:
+ * has_qual); 1 for a record that is not kept (unmapped: its tail is not looked at); NP2_E_ARG or NP2_E_UNSUPPORTED for a
+ * refused line, where[i] then (field + 1) << 8 | kind for a bad tail (field 0 - 3: RNEXT, PNEXT, TLEN, QUAL; 4 + k: optional
+ * field k), a small number for a bad QNAME and 0 for a line the lean parse refuses; tail_ref[i] is all ones unless status[i] is
+ * 0.  header_text (or NULL): the full stream's header text.  Release the five with np2_free.  Returns NP2_OK when no line is
+ * refused; otherwise the status of the line that speaks, with its message in np2_io_last_error(), the arrays filled all the
+ * same.  A bad header line is NP2_E_ARG and returns nothing. */
+int np2_sam_tails_host(const uint8_t *text, uint64_t n, uint8_t **tails, uint64_t *tail_bytes, uint64_t **tail_ref, int32_t **status,
+                       uint32_t **where, uint64_t *n_lines, char **header_text, uint64_t *header_bytes);
 
 #ifdef __cplusplus
 }

@@ -85,6 +85,9 @@ def build_parser():
     p.add_argument("--sorted_bam", default=None, metavar="hifi.map.sort.bam",
                    help="SAM input: also write the coordinate-sorted BAM and its .bai (what samtools sort and index would make of "
                         "the mapping), assembled, compressed and indexed on the GPU; single rank")
+    p.add_argument("--sorted_bam_full", action="store_true",
+                   help="--sorted_bam: carry QUAL, RNEXT, PNEXT, TLEN, the optional fields and the header lines (@RG, @PG, @CO) too; "
+                        "about three times the device memory for the resident mapping")
     p.add_argument("--trio_mat", type=_existing, default=None, metavar="mat.yak", help="--trio: the maternal k-mer dump (same k)")
     p.add_argument("--trio_min_count", type=int, default=2, metavar="N", help="--trio: a parent counting a k-mer fewer than N times does not have it [2]")
     p.add_argument("--trio_mid_count", type=int, default=5, metavar="N", help="--trio: a parent counting a k-mer at least N times has it [5]")
@@ -406,6 +409,8 @@ def main(argv=None):
     if a.sam and a.use_secondary:
         raise SystemExit("Error: -S needs the SEQ of a read's primary record, which is found by name: not with SAM input, use a sorted BAM "
                          "(python -m nextpolish2_amd.samsort writes one from the SAM text)")
+    if a.sorted_bam_full and a.sorted_bam is None:
+        raise SystemExit("Error: --sorted_bam_full says what --sorted_bam PATH carries: give --sorted_bam too")
     if a.sorted_bam is not None and not a.sam:
         raise SystemExit("Error: --sorted_bam writes the sorted BAM of SAM input; the mapping given is a BAM already")
     if a.sam and int(os.environ.get("WORLD_SIZE", "1")) > 1 and "RANK" in os.environ:
@@ -510,7 +515,7 @@ def main(argv=None):
         t_s = time.time()
         spol = Polisher([], device=a.device)
         try:
-            sam = np2io.Sam(spol, [a.bam], tie=a.sam_tie, keep_names=a.sorted_bam is not None)
+            sam = np2io.Sam(spol, [a.bam], tie=a.sam_tie, keep_names=a.sorted_bam is not None, keep_all=a.sorted_bam_full)
             if a.sorted_bam is not None:  # the mapping is kept from this one pass over a stream that cannot be read twice
                 st = sam.write_bam(spol, a.sorted_bam)
                 if prof:

@@ -7,7 +7,9 @@
 //                 (np2bam::rec_byte), so a record cut by a block's or a batch's edge needs no path of its own: a wavefront
 //                 takes a record that intersects the range (the first one by binary search on off[]) and its lanes write the
 //                 4-byte words of the destination that lie inside both, one word a lane a step; the words cut by the record's
-//                 or the range's edge go out byte by byte.  The run of 0xFF bytes, two thirds of a record, costs no load.
+//                 or the range's edge go out byte by byte.  The run of 0xFF bytes of a lean record, two thirds of it, costs no
+//                 load; packed SEQ, the quality bytes and the optional fields of a full record (NP2_SAM_KEEP_ALL: they lie in
+//                 the record's tail) are loaded as aligned words and shifted into place.
 //   k_bai_voff    after the blocks' compressed sizes were scanned into file offsets: the two virtual offsets of a record, and
 //                 whether it opens a run of records of one (tid, bin)
 //   k_bai_chunks  a run's key, first beg and last end; rocPRIM's stable sort orders the runs by key afterwards
@@ -16,6 +18,7 @@
 // Plain vector stores throughout; integer atomics on the refusals, the per-reference window counts and the windows.
 #include "np2_bamout.hpp"
 #include "np2_sam.hpp"
+#include "np2_samtail_core.hpp"
 
 namespace np2 {
 
@@ -33,7 +36,22 @@ __device__ __forceinline__ Rec load_rec(const BamSrc &src, const uint32_t *__res
     r.name = src.names + np2bam::name_off(nr);
     r.cigar = src.cigar + ((uint64_t)w[4] | (uint64_t)w[5] << 32);
     r.seq = src.seq4 + ((uint64_t)w[8] | (uint64_t)w[9] << 32);
+    r.tail = nullptr, r.has_qual = 0u, r.aux_len = 0u;
+    if (src.tails) { // the full stream (uniform across the launch)
+        const uint64_t tr = src.tail_ref[i];
+        r.tail = src.tails + np2tail::tail_off(tr), r.has_qual = np2tail::tail_has_qual(tr) ? 1u : 0u;
+        r.aux_len = *reinterpret_cast<const uint32_t *>(r.tail + 12); // (a tail begins at a word)
+    }
     return r;
+}
+
+// The four bytes at p, from the two aligned words that hold them, combined by a byte shift: adjacent lanes then share every
+// word they load, where four byte loads would each be a request of their own.  The word behind p's is read whole even when
+// p is aligned: the SEQ bytes and the tails have 16 bytes of room behind their last byte.
+__device__ __forceinline__ uint32_t load_bytes4(const uint8_t *p) {
+    const uint32_t *a = reinterpret_cast<const uint32_t *>((uintptr_t)p & ~(uintptr_t)3);
+    const uint32_t sh = 8u * (uint32_t)((uintptr_t)p & 3u);
+    return (uint32_t)(((uint64_t)a[1] << 32 | a[0]) >> sh);
 }
 
 __global__ __launch_bounds__(BLOCK) void k_bam_sizes(BamSrc src, uint32_t *__restrict__ sz, uint32_t *__restrict__ be,
@@ -53,7 +71,7 @@ __global__ __launch_bounds__(BLOCK) void k_bam_sizes(BamSrc src, uint32_t *__res
             atomicMin(&ref->far_end, i);
         } else {
             const uint32_t last = (uint32_t)(end - 1u) >> np2bam::WIN_SHIFT; // below 2^15
-            bytes = (uint32_t)np2bam::rec_bytes(r.name_len, r.n_cigar, r.l_seq); // (l_seq is below 2^31: below 2^32)
+            bytes = (uint32_t)np2bam::rec_bytes(r.name_len, r.n_cigar, r.l_seq, r.aux_len); // (l_seq and aux_len are below 2^31 each)
             packed = np2bam::reg2bin((uint32_t)r.pos, (uint32_t)end) | last << 16;
             atomicMax(&n_intv[r.tid], last + 1u);
         }
@@ -78,13 +96,20 @@ __global__ __launch_bounds__(BLOCK) void k_bam_emit(BamSrc src, const uint64_t *
         const uint64_t a = o > b0 ? o : b0, e = off[i + 1], b = e < b1 ? e : b1;
         uint8_t *p = dst + (a - b0), *q = dst + (b - b0); // the record's bytes [a - o, b - o) go to [p, q), inside dst[0, b1 - b0)
         const int64_t idx_p = (int64_t)(a - o);
-        const int64_t qual = (int64_t)np2bam::qual_begin(r);
+        // the regions with a word path: packed SEQ without the masked last byte of an odd read, the quality bytes (or the run of
+        // 0xFF), the optional fields.  With qualities the last two lie next to each other in the tail, as they do in the record.
+        const int64_t seq = (int64_t)np2bam::seq_begin(r), qual = (int64_t)np2bam::qual_begin(r), seq_end = qual - (int64_t)(r.l_seq & 1u);
+        const int64_t aux = qual + (int64_t)r.l_seq;
         uint8_t *w0 = p - ((uintptr_t)p & 3u);
         for (uint8_t *w = w0 + 4u * lane; w < q; w += 256u) {
             const int64_t idx = idx_p + (w - p); // the record's byte at w; negative only for bytes in front of p
-            if (w >= p && w + 4 <= q) {
-                uint32_t x = 0xFFFFFFFFu;
-                if (idx < qual)
+            if (w >= p && w + 4 <= q) { // (the four bytes are inside the record: idx + 4 <= its size)
+                uint32_t x;
+                if (idx >= seq && idx + 4 <= seq_end) x = load_bytes4(r.seq + (idx - seq));
+                else if (idx >= qual && r.has_qual) x = load_bytes4(r.tail + np2bam::TAIL_HEAD + (idx - qual));
+                else if (idx >= qual && idx + 4 <= aux) x = 0xFFFFFFFFu;
+                else if (idx >= aux) x = load_bytes4(r.tail + np2bam::TAIL_HEAD + (idx - aux));
+                else
                     x = (uint32_t)np2bam::rec_byte(r, (uint64_t)idx) | (uint32_t)np2bam::rec_byte(r, (uint64_t)idx + 1u) << 8 |
                         (uint32_t)np2bam::rec_byte(r, (uint64_t)idx + 2u) << 16 | (uint32_t)np2bam::rec_byte(r, (uint64_t)idx + 3u) << 24;
                 *reinterpret_cast<uint32_t *>(w) = x;

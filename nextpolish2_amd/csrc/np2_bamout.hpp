@@ -15,6 +15,8 @@ struct BamSrc {
     const uint8_t *seq4;
     const uint8_t *names;
     const uint64_t *name_ref;
+    const uint8_t *tails;     // NP2_SAM_KEEP_ALL: the tails and, per record, offset << 1 | has_qual; both nullptr for the lean stream
+    const uint64_t *tail_ref;
     uint32_t n;
 };
 

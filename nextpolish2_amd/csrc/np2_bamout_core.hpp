@@ -48,23 +48,33 @@ NP2_BAM_HD uint64_t cigar_span(const uint32_t *cigar, uint32_t n) {
     return span;
 }
 
-// one record as the encoder sees it; the three pointers are at the record's own first name byte, CIGAR word and SEQ byte
+// one record as the encoder sees it; the pointers are at the record's own first name byte, CIGAR word, SEQ byte and tail byte.
+// tail == nullptr is the lean record: no mate, no quality, no optional field.  Otherwise the tail (np2_samtail_core.hpp) begins
+// at a 4-byte boundary: next_refID, next_pos, tlen, aux_len, then l_seq quality bytes if has_qual, then aux_len bytes.
+static constexpr uint32_t TAIL_HEAD = 16;
 struct Rec {
     int32_t tid, pos;
     uint32_t flag, mapq, n_cigar, l_seq, name_len, bin;
     const uint8_t *name;
     const uint32_t *cigar;
     const uint8_t *seq;
+    const uint8_t *tail;
+    uint32_t has_qual, aux_len;
 };
+NP2_BAM_HD uint32_t tail_word(const uint8_t *tail, uint32_t w) {
+    const uint8_t *p = tail + 4u * w;
+    return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
+}
 
 // bytes of the record in the stream, its block_size word included
-NP2_BAM_HD uint64_t rec_bytes(uint32_t name_len, uint32_t n_cigar, uint32_t l_seq) {
-    return (uint64_t)FIXED_BYTES + name_len + 1u + 4ull * n_cigar + (l_seq + 1u) / 2u + l_seq;
+NP2_BAM_HD uint64_t rec_bytes(uint32_t name_len, uint32_t n_cigar, uint32_t l_seq, uint32_t aux_len = 0u) {
+    return (uint64_t)FIXED_BYTES + name_len + 1u + 4ull * n_cigar + (l_seq + 1u) / 2u + l_seq + aux_len;
 }
 
 NP2_BAM_HD uint32_t fixed_word(const Rec &r, uint32_t w) {
+    if (r.tail && w >= 6u) return tail_word(r.tail, w - 6u);
     switch (w) {
-    case 0: return (uint32_t)(rec_bytes(r.name_len, r.n_cigar, r.l_seq) - 4u);
+    case 0: return (uint32_t)(rec_bytes(r.name_len, r.n_cigar, r.l_seq, r.aux_len) - 4u);
     case 1: return (uint32_t)r.tid;
     case 2: return (uint32_t)r.pos;
     case 3: return (r.name_len + 1u) | r.mapq << 8 | r.bin << 16;
@@ -86,10 +96,14 @@ NP2_BAM_HD uint8_t rec_byte(const Rec &r, uint64_t idx) {
     idx -= 4ull * r.n_cigar;
     const uint32_t n_seq = (r.l_seq + 1u) / 2u;
     if (idx < n_seq) return (r.l_seq & 1u) && idx + 1u == n_seq ? (uint8_t)(r.seq[idx] & 0xF0u) : r.seq[idx];
-    return (uint8_t)0xFF;
+    idx -= n_seq;
+    if (idx < r.l_seq) return r.has_qual ? r.tail[TAIL_HEAD + idx] : (uint8_t)0xFF;
+    return r.tail[TAIL_HEAD + (r.has_qual ? idx : idx - r.l_seq)]; // an optional field's byte: idx - l_seq below aux_len
 }
-// where the run of 0xFF bytes begins
-NP2_BAM_HD uint64_t qual_begin(const Rec &r) { return rec_bytes(r.name_len, r.n_cigar, r.l_seq) - r.l_seq; }
+// where the quality bytes, or the run of 0xFF bytes, begin; the optional fields follow l_seq bytes later
+NP2_BAM_HD uint64_t qual_begin(const Rec &r) { return rec_bytes(r.name_len, r.n_cigar, r.l_seq, 0u) - r.l_seq; }
+// where the packed SEQ bytes begin
+NP2_BAM_HD uint64_t seq_begin(const Rec &r) { return (uint64_t)FIXED_BYTES + r.name_len + 1u + 4ull * r.n_cigar; }
 
 // the virtual offset of stream offset u: C[b] is the file offset of BGZF block b
 NP2_BAM_HD uint64_t voff(const uint64_t *C, uint64_t u) { return C[u / BLOCK_BYTES] << 16 | u % BLOCK_BYTES; }

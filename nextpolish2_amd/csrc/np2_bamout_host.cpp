@@ -14,6 +14,7 @@
 #include "np2_bamout.hpp"
 #include "np2_sam.hpp"
 #include "np2_sam_handle.hpp"
+#include "np2_samtail_core.hpp"
 
 #include <algorithm>
 #include <functional>
@@ -33,10 +34,8 @@ void put64(std::vector<uint8_t> &v, uint64_t x) {
     for (int i = 0; i < 8; ++i) v.push_back((uint8_t)(x >> (8 * i)));
 }
 
-// the stream in front of the first record
-std::vector<uint8_t> bam_header(const np2sam::Refs &refs) {
-    std::string text = "@HD\tVN:1.6\tSO:coordinate\n";
-    for (size_t i = 0; i < refs.names.size(); ++i) text += "@SQ\tSN:" + refs.names[i] + "\tLN:" + std::to_string(refs.lens[i]) + "\n";
+// the stream in front of the first record; text: the header text (the lean stream's: np2h::bam_header_text(refs, ""))
+std::vector<uint8_t> bam_header(const np2sam::Refs &refs, const std::string &text) {
     std::vector<uint8_t> h = {'B', 'A', 'M', 1};
     put32(h, (uint32_t)text.size());
     h.insert(h.end(), text.begin(), text.end());
@@ -48,6 +47,10 @@ std::vector<uint8_t> bam_header(const np2sam::Refs &refs) {
         put32(h, refs.lens[i]);
     }
     return h;
+}
+
+std::vector<uint8_t> bam_header(const np2_sam &sam) {
+    return bam_header(sam.refs, sam.has_tails ? sam.header_text : np2h::bam_header_text(sam.refs, ""));
 }
 
 void check_refs(const np2sam::Refs &refs) {
@@ -139,7 +142,8 @@ struct Sized {
 };
 
 np2::BamSrc source(const np2_sam &sam) {
-    return np2::BamSrc{sam.recs.p, sam.tids.p, sam.cigar.p, sam.seq4.p, sam.names.p, sam.name_ref.p, (uint32_t)sam.n_recs};
+    return np2::BamSrc{sam.recs.p, sam.tids.p, sam.cigar.p, sam.seq4.p, sam.names.p, sam.name_ref.p, sam.has_tails ? sam.tails.p : nullptr,
+                       sam.has_tails ? sam.tail_ref.p : nullptr, (uint32_t)sam.n_recs};
 }
 
 void sizes(np2_ctx *cx, const np2_sam &sam, size_t scan_items, Sized &z) {
@@ -188,7 +192,7 @@ void write_bam(np2_ctx *cx, np2_sam &sam, const std::string &bam_path, const std
     hipStream_t cs = cx->stream;
     const uint32_t n = (uint32_t)sam.n_recs;
     const size_t n_refs = sam.refs.names.size();
-    const std::vector<uint8_t> hdr = bam_header(sam.refs);
+    const std::vector<uint8_t> hdr = bam_header(sam);
     const uint64_t H = hdr.size();
     Sized z;
     sizes(cx, sam, 0, z); // (throws the refusals: nothing has been created)
@@ -282,6 +286,11 @@ struct HostIn {
     const uint8_t *names;
     uint64_t name_bytes;
     const uint64_t *name_ref;
+    const uint8_t *tails = nullptr; // np2_bamout_host_full: the tails, tail_ref[i] = offset << 1 | has_qual, the header text
+    uint64_t tail_bytes = 0;
+    const uint64_t *tail_ref = nullptr;
+    const char *header_text = nullptr;
+    uint64_t header_bytes = 0;
 };
 
 Rec host_rec(const HostIn &in, uint64_t i, size_t n_refs) {
@@ -297,6 +306,15 @@ Rec host_rec(const HostIn &in, uint64_t i, size_t n_refs) {
     Rec r;
     r.tid = in.tids[i], r.pos = b.pos, r.flag = b.flag, r.mapq = b.mapq, r.n_cigar = b.n_cigar, r.l_seq = b.l_seq, r.name_len = nl, r.bin = 0;
     r.name = in.names + no, r.cigar = in.cigar + b.cigar_off, r.seq = in.seq4 + b.seq_off;
+    r.tail = nullptr, r.has_qual = 0u, r.aux_len = 0u;
+    if (in.tail_ref) {
+        const uint64_t to = np2tail::tail_off(in.tail_ref[i]);
+        if (to % 4u || to > in.tail_bytes || in.tail_bytes - to < np2bam::TAIL_HEAD) throw Np2Error(NP2_E_ARG, who + ": tail outside the tail bytes or not at a word");
+        r.tail = in.tails + to, r.has_qual = np2tail::tail_has_qual(in.tail_ref[i]) ? 1u : 0u, r.aux_len = np2bam::tail_word(r.tail, 3);
+        if ((uint64_t)r.aux_len + (r.has_qual ? b.l_seq : 0u) > in.tail_bytes - to - np2bam::TAIL_HEAD)
+            throw Np2Error(NP2_E_ARG, who + ": quality bytes or optional fields outside the tail bytes");
+        if (r.aux_len >= (1u << 31)) throw Np2Error(NP2_E_ARG, who + ": aux_len of 2^31 or more");
+    }
     return r;
 }
 
@@ -325,7 +343,7 @@ void bamout_host(const HostIn &in, const np2sam::Refs &refs, const char *bam_pat
                 ref.far_end = std::min(ref.far_end, ord);
             } else {
                 last_win[i] = (uint32_t)(end - 1u) >> np2bam::WIN_SHIFT;
-                bytes = np2bam::rec_bytes(r.name_len, r.n_cigar, r.l_seq);
+                bytes = np2bam::rec_bytes(r.name_len, r.n_cigar, r.l_seq, r.aux_len);
                 r.bin = np2bam::reg2bin((uint32_t)r.pos, (uint32_t)end);
                 n_intv[(size_t)r.tid] = std::max(n_intv[(size_t)r.tid], last_win[i] + 1u);
             }
@@ -337,7 +355,7 @@ void bamout_host(const HostIn &in, const np2sam::Refs &refs, const char *bam_pat
                std::to_string((int64_t)in.recs[i].pos + 1) + ")";
     });
     // k_bam_emit, byte by byte
-    const std::vector<uint8_t> hdr = bam_header(refs);
+    const std::vector<uint8_t> hdr = bam_header(refs, in.header_text ? std::string(in.header_text, in.header_bytes) : np2h::bam_header_text(refs, ""));
     const uint64_t H = hdr.size(), total = H + off[in.n], n_blk = (total + np2bam::BLOCK_BYTES - 1) / np2bam::BLOCK_BYTES;
     std::unique_ptr<uint8_t, void (*)(void *)> S((uint8_t *)malloc(total), free);
     if (!S) throw Np2Error(NP2_E_NOMEM, "out of memory for the BAM stream");
@@ -389,6 +407,14 @@ void bamout_host(const HostIn &in, const np2sam::Refs &refs, const char *bam_pat
 
 } // namespace
 
+namespace np2h {
+std::string bam_header_text(const np2sam::Refs &refs, const std::string &extra) {
+    std::string text = "@HD\tVN:1.6\tSO:coordinate\n";
+    for (size_t i = 0; i < refs.names.size(); ++i) text += "@SQ\tSN:" + refs.names[i] + "\tLN:" + std::to_string(refs.lens[i]) + "\n";
+    return text + extra;
+}
+} // namespace np2h
+
 extern "C" {
 
 int np2_sam_write_bam(np2_ctx_t *cx, np2_sam_t *sam, const char *bam_path, const char *bai_path, np2_bamout_stats_t *stats) {
@@ -423,7 +449,7 @@ int np2_sam_bam_stream(np2_ctx_t *cx, np2_sam_t *sam, uint8_t **S, uint64_t *n_o
         touched = true;
         HIPCHK(hipSetDevice(cx->device));
         hipStream_t st = cx->stream;
-        const std::vector<uint8_t> hdr = bam_header(sam->refs);
+        const std::vector<uint8_t> hdr = bam_header(*sam);
         Sized z;
         sizes(cx, *sam, 0, z);
         const uint64_t H = hdr.size(), total = H + z.rec_total;
@@ -479,7 +505,19 @@ int np2_bamout_host(const np2_bamrec_t *recs, const int32_t *tids, const uint32_
                     uint64_t n_cigar_words, uint64_t seq_bytes, const uint8_t *names, uint64_t name_bytes, const uint64_t *name_ref,
                     const char *const *ref_names, const uint32_t *ref_lens, int n_refs, const char *bam_path, const char *bai_path,
                     uint8_t **S, uint64_t *n_S, np2_bamout_stats_t *stats) {
+    return np2_bamout_host_full(recs, tids, cigar, seq4, n_recs, n_cigar_words, seq_bytes, names, name_bytes, name_ref, nullptr, 0, nullptr, nullptr,
+                                0, ref_names, ref_lens, n_refs, bam_path, bai_path, S, n_S, stats);
+}
+
+int np2_bamout_host_full(const np2_bamrec_t *recs, const int32_t *tids, const uint32_t *cigar, const uint8_t *seq4, uint64_t n_recs,
+                         uint64_t n_cigar_words, uint64_t seq_bytes, const uint8_t *names, uint64_t name_bytes, const uint64_t *name_ref,
+                         const uint8_t *tails, uint64_t tail_bytes, const uint64_t *tail_ref, const char *header_text, uint64_t header_bytes,
+                         const char *const *ref_names, const uint32_t *ref_lens, int n_refs, const char *bam_path, const char *bai_path,
+                         uint8_t **S, uint64_t *n_S, np2_bamout_stats_t *stats) {
     return np2h::abi_guard([&] {
+        if ((tail_ref && tail_bytes && !tails) || (!tail_ref && tails) || (header_bytes && !header_text))
+            throw Np2Error(NP2_E_ARG, "np2_bamout_host: NULL argument");
+        if (header_bytes >= (1ull << 31)) throw Np2Error(NP2_E_UNSUPPORTED, "np2_bamout_host: a header text of 2 GiB or more");
         if (S) *S = nullptr;
         if (n_S) *n_S = 0;
         if (n_refs < 0 || (n_refs && (!ref_names || !ref_lens)) || (S && !n_S) || (n_recs && (!recs || !tids || !name_ref || !names)) ||
@@ -492,7 +530,9 @@ int np2_bamout_host(const np2_bamrec_t *recs, const int32_t *tids, const uint32_
             refs.names.push_back(ref_names[i]), refs.lens.push_back(ref_lens[i]);
         }
         np2_bamout_stats_t st{};
-        bamout_host(HostIn{recs, tids, cigar, seq4, n_recs, n_cigar_words, seq_bytes, names, name_bytes, name_ref}, refs, bam_path, bai_path, S, n_S, st);
+        HostIn in{recs, tids, cigar, seq4, n_recs, n_cigar_words, seq_bytes, names, name_bytes, name_ref};
+        in.tails = tails, in.tail_bytes = tail_bytes, in.tail_ref = n_recs ? tail_ref : nullptr, in.header_text = header_text, in.header_bytes = header_bytes;
+        bamout_host(in, refs, bam_path, bai_path, S, n_S, st);
         if (stats) *stats = st;
         return NP2_OK;
     }, np2h::io_set_error);

@@ -17,6 +17,15 @@
 //   k_sam_name_copy  after the scan placed the names: the bytes, and offset << 8 | length per record
 // and k_sam_gather_u64 moves those words into sorted order; the name bytes stay where they are, as SEQ does.
 //
+// With NP2_SAM_KEEP_ALL (the full BAM: QUAL, the mate fields and the optional fields) two more per piece, a wavefront per line:
+//   k_sam_tail_len   lanes 0 - 2 read RNEXT, PNEXT and TLEN; the lanes stride over QUAL, find its end and judge its bytes; the
+//                    tabs behind it are found by ballot, 64 a pass, and every lane takes one optional field TAG:TYPE:VALUE: its
+//                    binary size and whether it is well formed (np2_samtail_core.hpp).  The size of a Z or H value comes from
+//                    the tab positions; one of more than 64 bytes is judged by the whole wavefront.  The sizes are summed.
+//   k_sam_tail_emit  after the scan placed the tails: the three mate words and aux_len, the quality bytes minus 33 (all lanes),
+//                    the optional fields at the offsets of a wave prefix sum of their sizes, one field a lane, a long Z or H
+//                    value by all lanes; and offset << 1 | has_qual per record, which k_sam_gather_u64 moves as it moves name_ref.
+//
 // After the last piece the keys are sorted with the record ordinals as values (rocPRIM, np2_prims.hip: stable) and
 //   k_sam_gather  a wavefront per record moves the record and its CIGAR words into sorted order; SEQ bytes stay where they are.
 // Plain vector stores throughout; integer atomics only on the piece's three counters.
@@ -253,9 +262,206 @@ __global__ __launch_bounds__(SAM_BLOCK) void k_sam_gather_u64(const uint64_t *__
     if (i < n) out[i] = in[order[i]]; // (order holds each of 0 .. n - 1 once)
 }
 
+// ---- NP2_SAM_KEEP_ALL: the tail of a kept line (np2_samtail_core.hpp has the rule and the one-lane walk) ----------------------
+__device__ __forceinline__ uint32_t wave_first_word(uint32_t w) { // the smallest error word that is not 0
+    w = w ? w : 0xFFFFFFFFu;
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t x = (uint32_t)__shfl_xor(w, o);
+        w = x < w ? x : w;
+    }
+    return w == 0xFFFFFFFFu ? 0u : w;
+}
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
+    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor(v, o);
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_excl_sum(uint32_t v, uint32_t lane) {
+    uint32_t x = v;
+    for (uint32_t o = 1; o < 64u; o <<= 1) {
+        const uint32_t y = (uint32_t)__shfl_up(x, o);
+        if (lane >= o) x += y;
+    }
+    return x - v;
+}
+
+// One wavefront walks the line text[.., e) behind its CIGAR.  EMIT = false: *size, *aux_len, *has_qual and the error word are
+// found (every byte of the tail's text is judged here).  EMIT = true: the line was found good, has_qual is given, and the tail
+// goes to out (4-byte aligned, room for pad4(size) bytes).  All arguments and results are uniform across the wavefront.
+template <bool EMIT>
+__device__ __forceinline__ uint32_t tail_wave(const uint8_t *__restrict__ text, uint32_t e, const Line &ln, const NameTab &nt, uint32_t lane,
+                                              uint8_t *__restrict__ out, uint32_t &size, uint32_t &aux_len, bool &has_qual) {
+    namespace tl = np2tail;
+    size = aux_len = 0;
+    // tabs 6 and 7; tab 5 is cig_b, tab 8 is in front of SEQ
+    const uint32_t t8 = ln.seq_a - 1u;
+    uint32_t t6 = 0, t7 = 0, n_t = 0;
+    for (uint32_t c = ln.cig_b + 1u; c < t8 && n_t < 2u; c += 64u) {
+        const uint32_t i = c + lane;
+        uint64_t m = __ballot(i < t8 && text[i] == (uint8_t)'\t');
+        while (m && n_t < 2u) {
+            const uint32_t p = c + (uint32_t)__builtin_ctzll(m);
+            if (n_t == 0u) t6 = p;
+            else t7 = p;
+            ++n_t, m &= m - 1ull;
+        }
+    }
+    if (n_t < 2u) return tl::err_word(tl::F_QUAL, tl::T_QUAL_LEN); // (k_sam_fields found ten tabs: not reached)
+    uint32_t val = 0xFFFFFFFFu, err = 0; // lane 0: next_refID, 1: next_pos, 2: tlen
+    if (lane == 0) {
+        int32_t v = -1;
+        err = tl::err_word(tl::F_RNEXT, tl::parse_rnext(nt, text, ln.cig_b + 1u, t6, ln.tid, &v));
+        val = (uint32_t)v;
+    }
+    if (lane == 1) {
+        int32_t v = -1;
+        err = tl::err_word(tl::F_PNEXT, tl::parse_pnext(text, t6 + 1u, t7, &v));
+        val = (uint32_t)v;
+    }
+    if (lane == 2) {
+        int32_t v = 0;
+        err = tl::err_word(tl::F_TLEN, tl::parse_tlen(text, t7 + 1u, t8, &v));
+        val = (uint32_t)v;
+    }
+    // QUAL: from behind tab 9 to the next tab or the line's end
+    const uint32_t tab9 = ln.l_seq ? ln.seq_a + ln.l_seq : text[ln.seq_a] == (uint8_t)'\t' ? ln.seq_a : ln.seq_a + 1u;
+    const uint32_t qa = tab9 + 1u;
+    uint32_t qb = qa;
+    if (!EMIT) {
+        bool bad = false;
+        for (uint32_t c = qa;; c += 64u) {
+            const uint32_t i = c + lane;
+            const uint8_t b = i < e ? text[i] : (uint8_t)'\t';
+            const uint64_t m = __ballot(b == (uint8_t)'\t');
+            const uint32_t first = m ? (uint32_t)__builtin_ctzll(m) : 64u;
+            bad = bad || (lane < first && !tl::qual_byte_ok(b));
+            if (m) {
+                qb = c + first;
+                break;
+            }
+        }
+        uint32_t qk = tl::qual_shape(text, qa, qb, ln.l_seq, ln.l_seq == 0u, &has_qual);
+        if (has_qual && __ballot(bad)) qk = tl::T_QUAL_BYTE;
+        if (lane == 3) err = tl::err_word(tl::F_QUAL, qk);
+        if (qk != tl::T_OK) has_qual = false;
+    } else {
+        qb = has_qual ? qa + ln.l_seq : qa + 1u;
+        if (has_qual)
+            for (uint32_t j = lane; j < ln.l_seq; j += 64u) out[tl::HEAD_BYTES + j] = (uint8_t)(text[qa + j] - 33u);
+    }
+    const uint32_t n_qual = has_qual ? ln.l_seq : 0u;
+    // the optional fields, 64 a pass: lane k of a pass keeps the tab in front of its field; the 65th tab opens the next pass
+    uint32_t aux = 0, base = 0;
+    for (uint32_t cur = qb; cur < e;) { // text[cur] is a tab
+        uint32_t my_tab = 0, last = 0, n = 0;
+        for (uint32_t c = cur; c < e && n < 65u; c += 64u) {
+            const uint32_t i = c + lane;
+            uint64_t m = __ballot(i < e && text[i] == (uint8_t)'\t');
+            while (m && n < 65u) {
+                const uint32_t p = c + (uint32_t)__builtin_ctzll(m);
+                if (lane == n) my_tab = p;
+                if (n == 64u) last = p;
+                ++n, m &= m - 1ull;
+            }
+        }
+        const uint32_t nf = n < 64u ? n : 64u;
+        const uint32_t nxt = (uint32_t)__shfl(my_tab, (int)((lane + 1u) & 63u));
+        const uint32_t a = my_tab + 1u, b = lane + 1u < n ? (lane == 63u ? last : nxt) : e;
+        uint32_t sz = 0, fk = tl::T_OK;
+        bool wide = false;
+        if (lane < nf) fk = tl::field(text, a, b, &sz, &wide, nullptr);
+        uint32_t off = 0;
+        if (EMIT) {
+            off = tl::HEAD_BYTES + n_qual + aux + wave_excl_sum(sz, lane);
+            if (lane < nf) (void)tl::field(text, a, b, &sz, &wide, out + off);
+        }
+        // a long Z or H value: every lane takes part
+        for (uint64_t wm = __ballot(lane < nf && fk == tl::T_OK && wide); wm; wm &= wm - 1ull) {
+            const int src = __builtin_ctzll(wm);
+            const uint32_t wa = (uint32_t)__shfl(a, src) + 5u, wb = (uint32_t)__shfl(b, src);
+            if (!EMIT) {
+                const bool z = text[wa - 2u] == (uint8_t)'Z';
+                bool bad = false;
+                for (uint32_t i = wa + lane; i < wb; i += 64u) bad = bad || !(z ? tl::z_byte_ok(text[i]) : tl::h_byte_ok(text[i]));
+                if (__ballot(bad) && lane == (uint32_t)src) fk = z ? tl::T_Z : tl::T_H;
+            } else {
+                const uint32_t wo = (uint32_t)__shfl(off, src) + 3u;
+                for (uint32_t i = wa + lane; i < wb; i += 64u) out[wo + (i - wa)] = text[i];
+                if (lane == 0) out[wo + (wb - wa)] = 0;
+            }
+        }
+        if (lane < nf) err = tl::first_word(err, tl::err_word(tl::F_OPT + base + lane, fk));
+        aux += wave_sum(sz), base += nf;
+        cur = n == 65u ? last : e;
+    }
+    aux_len = aux, size = tl::HEAD_BYTES + n_qual + aux;
+    if (EMIT) {
+        if (lane < 3u) reinterpret_cast<uint32_t *>(out)[lane] = val;
+        if (lane == 3u) reinterpret_cast<uint32_t *>(out)[3] = aux;
+        if (lane < tl::pad4(size) - size) out[size + lane] = 0;
+        return 0u;
+    }
+    return wave_first_word(err);
+}
+
+// t_size[i]: the padded bytes of a kept line's tail (0 for a line that is not kept, and for entry n_lines); t_aux[i]: its
+// aux_len | has_qual << 31.  A kept line with a bad field: *first_bad = min(*first_bad, i) (the host reads the line again).
+__global__ __launch_bounds__(SAM_BLOCK) void k_sam_tail_len(const uint8_t *__restrict__ text, const uint32_t *__restrict__ line_end,
+                                                             const Line *__restrict__ lines, uint32_t n_lines, NameTab nt,
+                                                             uint32_t *__restrict__ t_size, uint32_t *__restrict__ t_aux, uint32_t *__restrict__ first_bad) {
+    const uint32_t r = (blockIdx.x * SAM_BLOCK + threadIdx.x) >> 6, lane = threadIdx.x & 63u;
+    if (r == n_lines && lane == 0) t_size[r] = t_aux[r] = 0u; // the scan's closing entry
+    if (r >= n_lines) return;                                 // (uniform across the wavefront, as is all below)
+    const Line ln = lines[r];
+    uint32_t size = 0, aux = 0;
+    bool has_qual = false;
+    if (np2sam::line_kept(ln)) {
+        const uint32_t s = r ? line_end[r - 1] + 1u : 0u;
+        uint32_t e = line_end[r];
+        if (e > s && text[e - 1] == (uint8_t)'\r') --e;
+        const uint32_t err = tail_wave<false>(text, e, ln, nt, lane, nullptr, size, aux, has_qual);
+        if (err) {
+            size = aux = 0, has_qual = false;
+            if (lane == 0) atomicMin(first_bad, r);
+        }
+    }
+    if (lane == 0) t_size[r] = np2tail::pad4(size), t_aux[r] = aux | (has_qual ? 0x80000000u : 0u);
+}
+
+__global__ __launch_bounds__(SAM_BLOCK) void k_sam_tail_emit(const uint8_t *__restrict__ text, const uint32_t *__restrict__ line_end,
+                                                              const Line *__restrict__ lines, uint32_t n_lines, NameTab nt,
+                                                              const uint32_t *__restrict__ kept_off, const uint32_t *__restrict__ tail_off,
+                                                              const uint32_t *__restrict__ t_aux, uint64_t rec_base, uint64_t tail_base,
+                                                              uint8_t *__restrict__ tails, uint64_t *__restrict__ tail_ref) {
+    const uint32_t r = (blockIdx.x * SAM_BLOCK + threadIdx.x) >> 6, lane = threadIdx.x & 63u;
+    if (r >= n_lines) return; // (uniform across the wavefront, as is the next one)
+    const Line ln = lines[r];
+    if (!np2sam::line_kept(ln)) return;
+    const uint32_t s = r ? line_end[r - 1] + 1u : 0u;
+    uint32_t e = line_end[r];
+    if (e > s && text[e - 1] == (uint8_t)'\r') --e;
+    const uint64_t to = tail_base + tail_off[r]; // a multiple of 4; tail_off[r + 1] - tail_off[r] bytes are this line's
+    bool has_qual = (t_aux[r] & 0x80000000u) != 0u;
+    uint32_t size = 0, aux = 0;
+    (void)tail_wave<true>(text, e, ln, nt, lane, tails + to, size, aux, has_qual);
+    if (lane == 0) tail_ref[rec_base + kept_off[r]] = np2tail::tail_ref(to, has_qual);
+}
+
 inline dim3 wave_grid(uint64_t waves) { return dim3((uint32_t)((waves * 64u + SAM_BLOCK - 1) / SAM_BLOCK)); }
 
 } // namespace
+
+void launch_sam_tail_len(hipStream_t s, const uint8_t *text, const uint32_t *line_end, const np2sam::Line *lines, uint32_t n_lines,
+                         np2sam::NameTab nt, uint32_t *t_size, uint32_t *t_aux, uint32_t *first_bad) {
+    hipLaunchKernelGGL(k_sam_tail_len, wave_grid((uint64_t)n_lines + 1), dim3(SAM_BLOCK), 0, s, text, line_end, lines, n_lines, nt, t_size, t_aux,
+                       first_bad);
+}
+void launch_sam_tail_emit(hipStream_t s, const uint8_t *text, const uint32_t *line_end, const np2sam::Line *lines, uint32_t n_lines,
+                          np2sam::NameTab nt, const uint32_t *kept_off, const uint32_t *tail_off, const uint32_t *t_aux, uint64_t rec_base,
+                          uint64_t tail_base, uint8_t *tails, uint64_t *tail_ref) {
+    if (n_lines)
+        hipLaunchKernelGGL(k_sam_tail_emit, wave_grid(n_lines), dim3(SAM_BLOCK), 0, s, text, line_end, lines, n_lines, nt, kept_off, tail_off, t_aux,
+                           rec_base, tail_base, tails, tail_ref);
+}
 
 void launch_sam_lines(hipStream_t s, const Lookback &lb, const uint8_t *text, uint32_t n, uint32_t *line_end, SamCtr *ctr) {
     if (n) hipLaunchKernelGGL(k_sam_lines, dim3(sam_line_blocks(n)), dim3(SAM_BLOCK), 0, s, lb, text, n, line_end, ctr);

@@ -6,6 +6,7 @@
 #include "../../include/np2_io.h"
 #include "np2_lookback.hpp"
 #include "np2_sam_core.hpp"
+#include "np2_samtail_core.hpp"
 
 namespace np2 {
 
@@ -56,6 +57,16 @@ void launch_sam_name_len(hipStream_t s, const uint8_t *text, const uint32_t *lin
 void launch_sam_name_copy(hipStream_t s, const uint8_t *text, const uint32_t *line_end, const np2sam::Line *lines, uint32_t n_lines,
                           const uint32_t *kept_off, const uint32_t *name_off, uint64_t rec_base, uint64_t name_base, uint8_t *names,
                           uint64_t *name_ref);
+// NP2_SAM_KEEP_ALL, after launch_sam_fields.  One wavefront per line: t_size[i] = the bytes of a kept line's tail (np2_samtail_core.hpp),
+// padded to a multiple of 4, 0 for a line that is not kept; t_aux[i] = its aux_len | has_qual << 31; entry n_lines of both is set
+// to 0.  A kept line with a bad mate field, QUAL or optional field: *first_bad = min(*first_bad, i).
+void launch_sam_tail_len(hipStream_t s, const uint8_t *text, const uint32_t *line_end, const np2sam::Line *lines, uint32_t n_lines,
+                         np2sam::NameTab nt, uint32_t *t_size, uint32_t *t_aux, uint32_t *first_bad);
+// ... and after the scan: a kept line's tail to tails + tail_base + tail_off[i] (tail_base a multiple of 4), and for its record
+// (input order) tail_ref[rec_base + kept_off[i]] = offset << 1 | has_qual
+void launch_sam_tail_emit(hipStream_t s, const uint8_t *text, const uint32_t *line_end, const np2sam::Line *lines, uint32_t n_lines,
+                          np2sam::NameTab nt, const uint32_t *kept_off, const uint32_t *tail_off, const uint32_t *t_aux, uint64_t rec_base,
+                          uint64_t tail_base, uint8_t *tails, uint64_t *tail_ref);
 // out[i] = in[order[i]]
 void launch_sam_gather_u64(hipStream_t s, const uint64_t *in, const uint32_t *order, uint32_t n, uint64_t *out);
 

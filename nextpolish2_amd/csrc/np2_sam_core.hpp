@@ -245,6 +245,14 @@ inline std::string header_line(const uint8_t *t, size_t a, size_t b, Refs &refs)
     return "";
 }
 
+// NP2_SAM_KEEP_ALL: is the header line text[a, b) carried into the BAM's header text as it stands?  Every line but @HD and @SQ
+// (the writer makes those itself).
+inline bool header_line_is_carried(const uint8_t *t, size_t a, size_t b) {
+    if (b - a < 3) return true;
+    const bool hd = t[a + 1] == 'H' && t[a + 2] == 'D', sq = t[a + 1] == 'S' && t[a + 2] == 'Q';
+    return !((hd || sq) && (b - a == 3 || t[a + 3] == '\t'));
+}
+
 // the table of NameTab over `refs`, as host arrays (names concatenated; slots: a power of two, at least twice the names)
 struct NameTabHost {
     std::vector<uint32_t> slot, off;

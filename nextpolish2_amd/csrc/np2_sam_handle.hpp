@@ -3,6 +3,7 @@
 #include "../../include/np2_io.h"
 #include "np2_ctx.hpp"
 #include "np2_sam_core.hpp"
+#include "np2_samtail_core.hpp"
 
 struct np2_sam {
     int device = 0;
@@ -16,9 +17,25 @@ struct np2_sam {
     bool has_names = false;
     DevBuf<uint8_t> names;
     DevBuf<uint64_t> name_ref;
+    // NP2_SAM_KEEP_ALL: the tails as they were met (np2_samtail_core.hpp: mate fields, aux_len, quality bytes, optional fields), per
+    // record, in sorted order, offset << 1 | has_qual, and the header lines of the input other than @HD and @SQ ('\n' after each)
+    bool has_tails = false;
+    DevBuf<uint8_t> tails;
+    DevBuf<uint64_t> tail_ref;
+    uint64_t tail_bytes = 0;
+    std::string extra_header, header_text; // header_text: what the full stream carries
+    float tail_len_ms = 0.f, tail_emit_ms = 0.f; // k_sam_tail_len and its scan; k_sam_tail_emit (HIP events, summed over the pieces)
     uint64_t n_recs = 0, n_cigar = 0, seq_bytes = 0, name_bytes = 0;
     std::vector<uint64_t> keys; // sorted
     np2_sam_stats_t stats{};
-    np2_sam() { recs.cached = tids.cached = cigar.cached = seq4.cached = names.cached = name_ref.cached = true; } // (released when nothing reads them any more)
+    np2_sam() { recs.cached = tids.cached = cigar.cached = seq4.cached = names.cached = name_ref.cached = tails.cached = tail_ref.cached = true; } // (released when nothing reads them any more)
     ~np2_sam() { (void)hipSetDevice(device); }
 };
+
+namespace np2h {
+// the text of the BAM header: @HD, one @SQ line per reference, then `extra` (whole lines, '\n' after each)
+std::string bam_header_text(const np2sam::Refs &refs, const std::string &extra);
+// The alignment line text[0, e) (no '\r', no '\n') has a bad mate field, QUAL or optional field: throws what tail_line says of
+// it, `at` in front, with the field's name or TAG.  Returns when the tail is good or the lean parse refuses the line.
+void throw_tail_error(const uint8_t *line, uint32_t e, const np2sam::NameTab &nt, const std::string &at);
+} // namespace np2h

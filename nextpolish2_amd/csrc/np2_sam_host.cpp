@@ -92,6 +92,7 @@ struct Reader {
     np2sam::Refs refs; // of the first file, set before its first piece is handed over
     bool have_refs = false;
     uint64_t lines = 0; // of all files, when done
+    std::vector<std::string> extra; // the header lines other than @HD and @SQ, in input order, each once, without '\r' and '\n'
     std::thread th;
 
     explicit Reader(const Hooks &h) : hooks(h) {}
@@ -183,6 +184,11 @@ struct Reader {
                     if (!bad.empty()) {
                         release(b);
                         throw Np2Error(NP2_E_ARG, src.name + ": line " + std::to_string(line_no + 1) + ": " + bad);
+                    }
+                    if (np2sam::header_line_is_carried(buf, at, end)) {
+                        std::string line((const char *)buf + at, end - at);
+                        std::lock_guard<std::mutex> l(mu);
+                        if (std::find(extra.begin(), extra.end(), line) == extra.end()) extra.push_back(std::move(line));
                     }
                 }
                 at = nl + 1, ++line_no;
@@ -279,6 +285,12 @@ struct Build {
     DevBuf<uint64_t> nref_in;
     DevBuf<uint32_t> d_nname, d_nmoff, d_nbad;
     uint64_t name_bytes = 0;
+    // NP2_SAM_KEEP_ALL: offset << 1 | has_qual of each record's tail, input order; the sizes of a piece's tails and their scan
+    bool keep_all = false;
+    DevBuf<uint64_t> tref_in;
+    DevBuf<uint32_t> d_tsize, d_taux, d_toff;
+    uint64_t tail_bytes = 0;
+    np2h::DevEvent e_t0, e_t1;
     // one piece
     DevBuf<uint8_t> d_text, d_tmp;
     DevBuf<uint32_t> d_end, d_kept, d_ncig, d_nseq, d_koff, d_coff, d_soff;
@@ -299,7 +311,8 @@ struct Build {
         d_text.cached = d_tmp.cached = d_end.cached = d_kept.cached = d_ncig.cached = d_nseq.cached = d_koff.cached = d_coff.cached = true;
         d_soff.cached = d_lines.cached = d_ctr.cached = d_slot.cached = d_noff.cached = d_names.cached = true;
         nref_in.cached = d_nname.cached = d_nmoff.cached = d_nbad.cached = true;
-        e0.make(), e1.make(), e_mid.make();
+        tref_in.cached = d_tsize.cached = d_taux.cached = d_toff.cached = true;
+        e0.make(), e1.make(), e_mid.make(), e_t0.make(), e_t1.make();
     }
     ~Build() { (void)hipStreamSynchronize(st); }
 
@@ -375,7 +388,7 @@ struct Build {
         n_records += n_lines - h->n_empty;
         if (n_recs + kept >= (1ull << 31)) throw Np2Error(NP2_E_UNSUPPORTED, "a SAM input of 2^31 alignment records or more");
         if (n_cigar + n_cig >= 0xFFFF0000ull) throw Np2Error(NP2_E_UNSUPPORTED, "a SAM input of more than 4294901760 CIGAR operations");
-        uint64_t n_name = 0;
+        uint64_t n_name = 0, n_tail = 0;
         if (keep_names && kept) { // the names' lengths and where they go; a bad one speaks after every other error of the piece
             uint32_t *h_name = h_tot + 16; // [0]: the first bad line, [1]: the bytes of all names
             d_nname.ensure(m), d_nmoff.ensure(m), d_nbad.ensure(1);
@@ -383,21 +396,41 @@ struct Build {
             HIPCHK(hipMemcpyAsync(d_nbad.p, h_name, 4, hipMemcpyHostToDevice, st));
             np2::launch_sam_name_len(st, d_text.p, d_end.p, d_lines.p, n_lines, d_nname.p, d_nbad.p);
             if (np2::prim_exclusive_sum_u32(st, d_tmp.p, tmp_bytes, d_nname.p, d_nmoff.p, m)) throw Np2Error(NP2_E_DEVICE, "rocprim exclusive_scan failed");
+            if (keep_all) { // the tails' sizes; a bad field ranks with a bad name: the first such line of the piece speaks
+                d_tsize.ensure(m), d_taux.ensure(m), d_toff.ensure(m);
+                HIPCHK(hipEventRecord(e_t0.e, st));
+                np2::launch_sam_tail_len(st, d_text.p, d_end.p, d_lines.p, n_lines, nt, d_tsize.p, d_taux.p, d_nbad.p);
+                if (np2::prim_exclusive_sum_u32(st, d_tmp.p, tmp_bytes, d_tsize.p, d_toff.p, m)) throw Np2Error(NP2_E_DEVICE, "rocprim exclusive_scan failed");
+                HIPCHK(hipEventRecord(e_t1.e, st));
+                HIPCHK(hipMemcpyAsync(h_name + 2, d_toff.p + n_lines, 4, hipMemcpyDeviceToHost, st));
+            }
             HIPCHK(hipMemcpyAsync(h_name, d_nbad.p, 4, hipMemcpyDeviceToHost, st));
             HIPCHK(hipMemcpyAsync(h_name + 1, d_nmoff.p + n_lines, 4, hipMemcpyDeviceToHost, st));
             HIPCHK(hipStreamSynchronize(st));
             HIPCHK(hipGetLastError());
+            if (keep_all) sam.tail_len_ms += elapsed(e_t0, e_t1);
             if (h_name[0] != 0xFFFFFFFFu) {
                 if (h_name[0] >= n_lines) throw Np2Error(NP2_E_DEVICE, "np2_sam: error line out of range");
-                throw Np2Error(NP2_E_ARG, where + ": line " + std::to_string(first_line + h_name[0]) + ": QNAME is empty or longer than 254 bytes");
+                const std::string at = where + ": line " + std::to_string(first_line + h_name[0]) + ": ";
+                if (keep_all) bad_tail(h_name[0], n, at); // (throws, unless the name is what is wrong)
+                throw Np2Error(NP2_E_ARG, at + "QNAME is empty or longer than 254 bytes");
             }
             n_name = h_name[1];
             if (n_name > kept * 254u) throw Np2Error(NP2_E_DEVICE, "np2_sam: name bytes out of range");
+            if (keep_all) {
+                n_tail = h_name[2];
+                if (n_tail % 4u || n_tail < kept * np2tail::HEAD_BYTES || n_tail > 4ull * n + kept * (np2tail::HEAD_BYTES + 4ull))
+                    throw Np2Error(NP2_E_DEVICE, "np2_sam: tail bytes out of range");
+            }
         }
         if (kept) {
             if (keep_names) {
                 grow(nref_in, n_recs, n_recs + kept, st, "names");
                 grow(sam.names, name_bytes, name_bytes + n_name + 1, st, "names");
+            }
+            if (keep_all) {
+                grow(tref_in, n_recs, n_recs + kept, st, "tails");
+                grow(sam.tails, tail_bytes, tail_bytes + n_tail + 16, st, "quality bytes and optional fields");
             }
             grow(recs_in, n_recs * np2::SAM_REC_WORDS, (n_recs + kept) * np2::SAM_REC_WORDS, st, "records");
             grow(tids_in, n_recs, n_recs + kept, st, "records");
@@ -413,8 +446,35 @@ struct Build {
             HIPCHK(hipStreamSynchronize(st));
             HIPCHK(hipGetLastError());
             sam.stats.pack_ms += elapsed(e0, e1);
+            if (keep_all) {
+                HIPCHK(hipEventRecord(e_t0.e, st));
+                np2::launch_sam_tail_emit(st, d_text.p, d_end.p, d_lines.p, n_lines, nt, d_koff.p, d_toff.p, d_taux.p, n_recs, tail_bytes, sam.tails.p,
+                                          tref_in.p);
+                HIPCHK(hipEventRecord(e_t1.e, st));
+                HIPCHK(hipStreamSynchronize(st));
+                HIPCHK(hipGetLastError());
+                sam.tail_emit_ms += elapsed(e_t0, e_t1);
+            }
         }
-        n_recs += kept, n_cigar += n_cig, seq_bytes += n_seq, name_bytes += n_name;
+        n_recs += kept, n_cigar += n_cig, seq_bytes += n_seq, name_bytes += n_name, tail_bytes += n_tail;
+    }
+
+    // Line `r` of the piece (n bytes, still in d_text) has a bad name or a bad tail: the host reads the line and walks it with the
+    // one-lane text of the rule to say which field.  Returns when the tail is good (the name is what is wrong).
+    void bad_tail(uint32_t r, size_t n, const std::string &at) {
+        uint32_t ends[2] = {0, 0};
+        if (r) HIPCHK(hipMemcpyAsync(ends, d_end.p + r - 1, 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(ends + 1, d_end.p + r, 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        const uint32_t s = r ? ends[0] + 1u : 0u;
+        if (s > ends[1] || ends[1] > n) throw Np2Error(NP2_E_DEVICE, "np2_sam: error line out of range");
+        std::vector<uint8_t> line(ends[1] - s + 1u);
+        if (ends[1] > s) HIPCHK(hipMemcpyAsync(line.data(), d_text.p + s, ends[1] - s, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        uint32_t e = ends[1] - s;
+        if (e && line[e - 1] == '\r') --e;
+        const np2sam::NameTabHost nth(sam.refs);
+        np2h::throw_tail_error(line.data(), e, nth.view(), at);
     }
 
     // after the last piece: input order -> sorted order
@@ -422,6 +482,8 @@ struct Build {
         const uint32_t n = (uint32_t)n_recs;
         sam.n_recs = n_recs, sam.n_cigar = n_cigar, sam.seq_bytes = seq_bytes;
         sam.has_names = keep_names, sam.name_bytes = name_bytes;
+        sam.has_tails = keep_all, sam.tail_bytes = tail_bytes;
+        if (tail_bytes) HIPCHK(hipMemsetAsync(sam.tails.p + tail_bytes, 0, 16, st)); // (the encoder reads whole words)
         sam.stats.records = n_records, sam.stats.kept = n_recs, sam.stats.unmapped = n_records - n_recs;
         sam.stats.cigar_words = n_cigar, sam.stats.seq_bytes = seq_bytes;
         if (seq_bytes) HIPCHK(hipMemsetAsync(sam.seq4.p + seq_bytes, 0, 16, st)); // (what records_to_arrays appends, for a reader of 16-byte words)
@@ -430,7 +492,7 @@ struct Build {
             return;
         }
         const size_t tmp_bytes = np2::prim_temp_bytes((size_t)n + 1);
-        need_device((size_t)n * (8 + 4 + 4 + 4 + 4 + 4 + 40 + (keep_names ? 8 : 0)) + (n_cigar + 1) * 4 + tmp_bytes, "sorted records and CIGAR words");
+        need_device((size_t)n * (8 + 4 + 4 + 4 + 4 + 4 + 40 + (keep_names ? 8 : 0) + (keep_all ? 8 : 0)) + (n_cigar + 1) * 4 + tmp_bytes, "sorted records and CIGAR words");
         DevBuf<uint64_t> keys_out;
         DevBuf<uint32_t> vals_in, vals_out, sizes, offs;
         keys_out.cached = vals_in.cached = vals_out.cached = sizes.cached = offs.cached = true; // (released after the last synchronisation below)
@@ -448,6 +510,10 @@ struct Build {
         if (keep_names) {
             sam.name_ref.ensure(n);
             np2::launch_sam_gather_u64(st, nref_in.p, vals_out.p, n, sam.name_ref.p);
+        }
+        if (keep_all) {
+            sam.tail_ref.ensure(n);
+            np2::launch_sam_gather_u64(st, tref_in.p, vals_out.p, n, sam.tail_ref.p);
         }
         HIPCHK(hipEventRecord(e1.e, st));
         sam.keys.resize(n);
@@ -469,7 +535,8 @@ void build(np2_ctx *cx, np2_sam &sam, Reader &rd, const np2_sam_opts_t *opts, si
     sam.device = cx->device;
     Build b(cx, sam);
     b.tie = opts ? (opts->tie_by_strand ? 1u : 0u) : 1u;
-    b.keep_names = (flags & NP2_SAM_KEEP_NAMES) != 0;
+    b.keep_all = (flags & NP2_SAM_KEEP_ALL) != 0;
+    b.keep_names = b.keep_all || (flags & NP2_SAM_KEEP_NAMES) != 0;
     rd.start(bytes_bound);
     Piece p;
     for (;;) {
@@ -499,7 +566,10 @@ void build(np2_ctx *cx, np2_sam &sam, Reader &rd, const np2_sam_opts_t *opts, si
         if (rd.err_code) throw Np2Error(rd.err_code, rd.err_msg);
         sam.refs = rd.refs;
         sam.stats.lines = rd.lines;
+        if (b.keep_all)
+            for (const std::string &l : rd.extra) sam.extra_header += l + "\n";
     }
+    if (b.keep_all) sam.header_text = np2h::bam_header_text(sam.refs, sam.extra_header);
     b.finish();
     b.report();
 }
@@ -546,7 +616,7 @@ int np2_sam_open_ex(np2_ctx_t *cx, const char *const *paths, int n_paths, const 
     return np2h::abi_guard([&] {
         // the arguments and the files, before the first device call
         if (!cx || !out || !paths || n_paths < 1) throw Np2Error(NP2_E_ARG, "np2_sam_open: NULL argument or no path");
-        if (flags & ~(uint32_t)NP2_SAM_KEEP_NAMES) throw Np2Error(NP2_E_ARG, "np2_sam_open_ex: unknown flag bits");
+        if (flags & ~(uint32_t)(NP2_SAM_KEEP_NAMES | NP2_SAM_KEEP_ALL)) throw Np2Error(NP2_E_ARG, "np2_sam_open_ex: unknown flag bits");
         Hooks hooks;
         Reader rd(hooks);
         int n_stdin = 0;
@@ -558,7 +628,7 @@ int np2_sam_open_ex(np2_ctx_t *cx, const char *const *paths, int n_paths, const 
                 continue;
             }
             FILE *f = fopen(paths[i], "rb");
-            if (!f) throw Np2Error(NP2_E_ARG, std::string("cannot open ") + paths[i]);
+            if (!f) throw Np2Error(NP2_E_ARG, std::string("cannot open ") + paths[i] + (flags & NP2_SAM_KEEP_ALL ? " (np2_sam_open_ex, flag NP2_SAM_KEEP_ALL)" : ""));
             fclose(f);
         }
         touched = true;

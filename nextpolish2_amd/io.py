@@ -23,7 +23,8 @@ IO_SYMBOLS = ["np2_fasta_open", "np2_fasta_next", "np2_fasta_close", "np2_yak_lo
               "np2_sradapt_bytes", "np2_sradapt_files", "np2_sradapt_last_stats", "np2_sradapt_last_kernel_ms", "np2_kcount_files_ad",
               "np2_kcount_files_to_dumps_ad", "np2_ctx_create_from_reads_ad", "np2_bgzf_deflate_device", "np2_bgzf_deflate_host",
               "np2_bgzf_writer_open", "np2_bgzf_writer_write", "np2_bgzf_writer_close", "np2_sam_open_ex", "np2_sam_write_bam",
-              "np2_sam_bam_stream", "np2_bamout_host", "np2_sam_export_names"]
+              "np2_sam_bam_stream", "np2_bamout_host", "np2_sam_export_names", "np2_sam_export_tails", "np2_sam_header_text",
+              "np2_sam_tail_stats", "np2_bamout_host_full", "np2_sam_tails_host"]
 
 
 class np2_front_opts_t(C.Structure):
@@ -55,6 +56,7 @@ class np2_bamout_stats_t(C.Structure):
 
 
 NP2_SAM_KEEP_NAMES = 1
+NP2_SAM_KEEP_ALL = 2
 
 
 class FrontOpts:
@@ -321,6 +323,12 @@ def _bind_sam(L):
     L.np2_sam_export_names.argtypes = [vp, vp, C.POINTER(vp), u64p, C.POINTER(vp), u64p]
     L.np2_bamout_host.argtypes = [vp, vp, vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, vp, C.c_uint64, vp, C.POINTER(C.c_char_p), vp,
                                   C.c_int, C.c_char_p, C.c_char_p, C.POINTER(vp), u64p, bs]
+    L.np2_sam_export_tails.argtypes = [vp, vp, C.POINTER(vp), u64p, C.POINTER(vp), u64p]
+    L.np2_sam_header_text.argtypes = [vp, C.POINTER(vp), u64p]
+    L.np2_sam_tail_stats.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), u64p]
+    L.np2_bamout_host_full.argtypes = [vp, vp, vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, vp, C.c_uint64, vp, vp, C.c_uint64, vp, vp, C.c_uint64,
+                                       C.POINTER(C.c_char_p), vp, C.c_int, C.c_char_p, C.c_char_p, C.POINTER(vp), u64p, bs]
+    L.np2_sam_tails_host.argtypes = [vp, C.c_uint64, C.POINTER(vp), u64p, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), u64p, C.POINTER(vp), u64p]
 
 
 def _bind_kcount(L):
@@ -750,14 +758,17 @@ class Sam:
     there (include/np2_io.h has the rule).  tie: "strand" orders records at one position by strand, as samtools sort does;
     "input" leaves them in input order.  Read-only once open: contig_from_sam may be called from several threads, each with
     a Polisher of its own on that device.  keep_names=True (np2_sam_open_ex, NP2_SAM_KEEP_NAMES) keeps the QNAMEs resident too:
-    write_bam needs them."""
+    write_bam needs them.  keep_all=True (NP2_SAM_KEEP_ALL, which implies the names) keeps QUAL, RNEXT, PNEXT, TLEN, the optional
+    fields and the header lines as well: write_bam and bam_stream then write the full BAM (about three times the device memory)."""
 
-    def __init__(self, pol, paths, tie="strand", keep_names=False):
+    def __init__(self, pol, paths, tie="strand", keep_names=False, keep_all=False):
         L = _bind()
         o = _sam_opts(tie)
         arr, n = _paths(paths)
         self._h = C.c_void_p()
-        if keep_names:  # np2_sam_open_ex: the QNAMEs stay resident too, for write_bam
+        if keep_all:
+            _io_check(L.np2_sam_open_ex(pol._h, arr, n, C.byref(o), NP2_SAM_KEEP_ALL, C.byref(self._h)))
+        elif keep_names:  # np2_sam_open_ex: the QNAMEs stay resident too, for write_bam
             _io_check(L.np2_sam_open_ex(pol._h, arr, n, C.byref(o), NP2_SAM_KEEP_NAMES, C.byref(self._h)))
         else:
             _io_check(L.np2_sam_open(pol._h, arr, n, C.byref(o), C.byref(self._h)))
@@ -811,6 +822,30 @@ class Sam:
         finally:
             L.np2_free(pn), L.np2_free(pr)
 
+    def export_tails(self, pol):
+        """np2_sam_export_tails (needs keep_all=True): (tails uint8, tail_ref uint64: offset << 1 | has_qual per record in sorted
+        order).  A tail: next_refID, next_pos, tlen, aux_len (four words), the quality bytes if has_qual, the optional fields."""
+        L = _bind()
+        pt, pr, nb, n = C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
+        _io_check(L.np2_sam_export_tails(pol._h, self._h, C.byref(pt), C.byref(nb), C.byref(pr), C.byref(n)))
+        try:
+            return (np.frombuffer(C.string_at(pt.value, nb.value), dtype=np.uint8).copy(),
+                    np.frombuffer(C.string_at(pr.value, n.value * 8), dtype=np.uint64).copy())
+        finally:
+            L.np2_free(pt), L.np2_free(pr)
+
+    def header_text(self):
+        """np2_sam_header_text (needs keep_all=True): the header text of the full BAM as bytes"""
+        p, n = C.c_void_p(), C.c_uint64()
+        _io_check(_bind().np2_sam_header_text(self._h, C.byref(p), C.byref(n)))
+        return C.string_at(p.value, n.value)
+
+    def tail_stats(self):
+        """np2_sam_tail_stats: {tail_len_ms, tail_emit_ms, tail_bytes} of the two kernels keep_all=True adds"""
+        a, b, n = C.c_float(), C.c_float(), C.c_uint64()
+        _io_check(_bind().np2_sam_tail_stats(self._h, C.byref(a), C.byref(b), C.byref(n)))
+        return {"tail_len_ms": a.value, "tail_emit_ms": b.value, "tail_bytes": n.value}
+
     def close(self):
         if self._h:
             _bind().np2_sam_close(self._h)
@@ -827,11 +862,14 @@ def _bamout_stats_dict(st):
     return {n: (int if t is C.c_uint64 else float)(getattr(st, n)) for n, t in np2_bamout_stats_t._fields_}
 
 
-def bamout_host(recs, tids, cigar, seq4, names, name_ref, refs, path=None, bai=None, want_stream=True):
+def bamout_host(recs, tids, cigar, seq4, names, name_ref, refs, path=None, bai=None, want_stream=True, tails=None, tail_ref=None,
+                header_text=None):
     """np2_bamout_host, the host twin of Sam.write_bam (no device): recs (BAMREC_DTYPE), tids, cigar and seq4 as Sam.export
     returns them, names / name_ref as Sam.export_names does, refs [(name, length)].  Writes `path` and its index when path is
-    given.  -> (stream bytes or None, stats dict)."""
+    given.  tails / tail_ref (as Sam.export_tails returns them) and header_text (bytes, as Sam.header_text does), any of which
+    is given: np2_bamout_host_full, the full stream.  -> (stream bytes or None, stats dict)."""
     L = _bind()
+    full = tails is not None or tail_ref is not None or header_text is not None
     recs = np.ascontiguousarray(recs, dtype=BAMREC_DTYPE)
     tids, cigar = np.ascontiguousarray(tids, dtype=np.int32), np.ascontiguousarray(cigar, dtype=np.uint32)
     seq4, names = np.ascontiguousarray(seq4, dtype=np.uint8), np.ascontiguousarray(names, dtype=np.uint8)
@@ -842,14 +880,47 @@ def bamout_host(recs, tids, cigar, seq4, names, name_ref, refs, path=None, bai=N
     rl = np.ascontiguousarray([l for _, l in refs], dtype=np.uint32)
     ptr = lambda a: a.ctypes.data if len(a) else None
     p, n, st = C.c_void_p(), C.c_uint64(), np2_bamout_stats_t()
-    _io_check(L.np2_bamout_host(ptr(recs), ptr(tids), ptr(cigar), ptr(seq4), len(recs), len(cigar), len(seq4), ptr(names), len(names),
-                                ptr(name_ref), rn, ptr(rl), len(refs), os.fspath(path).encode() if path is not None else None,
-                                os.fspath(bai).encode() if bai is not None else None, C.byref(p) if want_stream else None,
-                                C.byref(n) if want_stream else None, C.byref(st)))
+    rest = (rn, ptr(rl), len(refs), os.fspath(path).encode() if path is not None else None,
+            os.fspath(bai).encode() if bai is not None else None, C.byref(p) if want_stream else None,
+            C.byref(n) if want_stream else None, C.byref(st))
+    head = (ptr(recs), ptr(tids), ptr(cigar), ptr(seq4), len(recs), len(cigar), len(seq4), ptr(names), len(names), ptr(name_ref))
+    if full:
+        tails = np.ascontiguousarray(tails if tails is not None else [], dtype=np.uint8)
+        tail_ref = np.ascontiguousarray(tail_ref, dtype=np.uint64) if tail_ref is not None else None
+        if tail_ref is not None and len(tail_ref) != len(recs):
+            raise ValueError("tail_ref must have one entry per record")
+        ht = C.create_string_buffer(header_text, len(header_text)) if header_text is not None else None
+        _io_check(L.np2_bamout_host_full(*head, ptr(tails), len(tails), tail_ref.ctypes.data if tail_ref is not None else None,
+                                         C.addressof(ht) if ht is not None else None, len(header_text or b""), *rest))
+    else:
+        _io_check(L.np2_bamout_host(*head, *rest))
     try:
         return (C.string_at(p.value, n.value) if want_stream else None), _bamout_stats_dict(st)
     finally:
         L.np2_free(p)
+
+
+def sam_tails_host(text):
+    """np2_sam_tails_host (no device): SAM text (bytes, header included) walked by the one-lane text of the rule.  -> dict:
+    tails (uint8), tail_ref (uint64), status (int32) and where (uint32), one entry per alignment line that is not empty;
+    header_text (bytes); code and message: 0 and "" when no line is refused, else the status and message of the line that
+    speaks.  A bad header raises Np2Error."""
+    L = _bind()
+    buf = np.frombuffer(bytes(text), dtype=np.uint8)
+    pt, pr, ps, pw, ph = (C.c_void_p() for _ in range(5))
+    nb, n, hb = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    rc = L.np2_sam_tails_host(buf.ctypes.data if len(buf) else None, len(buf), C.byref(pt), C.byref(nb), C.byref(pr), C.byref(ps), C.byref(pw),
+                              C.byref(n), C.byref(ph), C.byref(hb))
+    if not pr.value:
+        _io_check(rc)
+    try:
+        take = lambda p, nbytes, dt: np.frombuffer(C.string_at(p.value, nbytes), dtype=dt).copy() if nbytes else np.zeros(0, dt)
+        return dict(tails=take(pt, nb.value, np.uint8), tail_ref=take(pr, n.value * 8, np.uint64), status=take(ps, n.value * 4, np.int32),
+                    where=take(pw, n.value * 4, np.uint32), header_text=C.string_at(ph.value, hb.value), code=rc,
+                    message=L.np2_io_last_error().decode(errors="replace") if rc else "")
+    finally:
+        for p in (pt, pr, ps, pw, ph):
+            L.np2_free(p)
 
 
 def _sam_arrays(L, pr, pt, pc, ps, n, stats):

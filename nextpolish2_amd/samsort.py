@@ -1,13 +1,17 @@
 """The mapper's SAM text -> the coordinate-sorted BAM and its .bai: the `samtools sort -o hifi.map.sort.bam -` and
 `samtools index` steps of the reference's recipe, on the GPU.
 
-Usage: python -m nextpolish2_amd.samsort map.sam[.gz]|- [more.sam ...] -o hifi.map.sort.bam [--sam_tie strand|input]
+Usage: python -m nextpolish2_amd.samsort map.sam[.gz]|- [more.sam ...] -o hifi.map.sort.bam [--sam_tie strand|input] [--full]
 
 The text (plain or gzip; "-" is standard input) is parsed and sorted on the device (io.Sam with its names kept), the BAM
 records are assembled there, compressed as BGZF there, and the index is derived there from the records' offsets and the
 blocks' compressed sizes (include/np2_io.h has the rule: SAM specification 4.2 and 5.2; not compared with samtools' files).
-QNAME, FLAG, RNAME, POS, MAPQ, CIGAR and SEQ are carried; QUAL, RNEXT, PNEXT, TLEN, the optional fields, unmapped records and
-header lines other than @HD / @SQ are not.  The file is what -S (use_secondary), lowdepth and interval sharding need."""
+Two kinds of file.  The lean BAM (the default) carries QNAME, FLAG, RNAME, POS, MAPQ, CIGAR and SEQ; QUAL is 0xFF, the mate
+fields are unset, and the optional fields and the header lines other than @HD / @SQ are not carried.  It is what this
+project's own readers need: -S (use_secondary), lowdepth and interval sharding.  The full BAM (--full) carries QUAL, RNEXT,
+PNEXT, TLEN, every optional field (TAG:TYPE:VALUE to BAM's binary form, on the device) and the @RG / @PG / @CO lines too, for
+tools that read base qualities or tags; the resident mapping then takes about three times the device memory.  Unmapped
+records are dropped from both.  The [samsort] line says which kind was written."""
 import argparse
 import os
 import sys
@@ -21,6 +25,9 @@ def build_parser():
     p.add_argument("-o", "--out", required=True, metavar="hifi.map.sort.bam", help="the BAM; its index is written next to it as <out>.bai")
     p.add_argument("--sam_tie", choices=np2io.SAM_TIES, default="strand",
                    help="records at one position are ordered by strand, as samtools sort orders them, or stay in input order [strand]")
+    p.add_argument("--full", action="store_true",
+                   help="the full BAM: QUAL, RNEXT, PNEXT, TLEN, the optional fields and the @RG / @PG / @CO header lines are carried too "
+                        "(about three times the device memory) [the lean BAM]")
     p.add_argument("--device", type=int, default=0)
     return p
 
@@ -45,17 +52,19 @@ def main(argv=None):
     t0 = time.time()
     pol = Polisher([], device=a.device)
     try:
-        sam = np2io.Sam(pol, a.sam, tie=a.sam_tie, keep_names=True)
+        sam = np2io.Sam(pol, a.sam, tie=a.sam_tie, keep_names=True, keep_all=a.full)
         try:
             st = sam.write_bam(pol, a.out)
             parsed = sam.stats()
+            ts = sam.tail_stats()
         finally:
             sam.close()
     except Np2Error as e:
         raise SystemExit(f"Error: {e}")
     finally:
         pol.close()
-    print(f"[samsort] {parsed['kept']} of {parsed['records']} records -> {a.out} ({st['file_bytes']} bytes, {st['blocks']} blocks) and "
+    kind = f"full BAM ({ts['tail_bytes']} bytes of qualities, mate and optional fields)" if a.full else "lean BAM"
+    print(f"[samsort] {kind}: {parsed['kept']} of {parsed['records']} records -> {a.out} ({st['file_bytes']} bytes, {st['blocks']} blocks) and "
           f"{a.out}.bai ({st['bins']} bins, {st['chunks']} chunks) in {time.time() - t0:.3f} s; kernels: emit {st['emit_ms']:.3f} ms, "
           f"deflate {st['deflate_ms']:.3f} ms, index {st['index_ms']:.3f} ms", file=sys.stderr)
     return 0
