@@ -421,7 +421,8 @@ int np2_rep_files(int device, const char *const *paths, int n_paths, const np2_r
  * samtools index ...`, which exist only so that an indexed reader can fetch one contig's records in coordinate order) -------
  * THE RULE IS DEFINED HERE, on the SAM specification section 1.4 and on what samtools' coordinate comparison is understood to
  * do; it is not pinned against the samtools binary.
- *   Input: one or more files, plain or gzip, or a stream that cannot be read twice (path "-": standard input).  The bytes
+ *   Input: one or more files, plain or gzip (or BAM: "BAM input", below), or a stream that cannot be read twice (path "-":
+ *     standard input).  The bytes
  *     are taken as they stand, in pieces that end at a line boundary (32 MiB; test hook NP2_SAM_TEST_PIECE, in bytes, read
  *     once per call).  A line that does not fit an empty piece is NP2_E_UNSUPPORTED, naming the 1-based line.  A '\r' directly
  *     before '\n' is dropped, a last line needs no newline, empty lines are skipped.
@@ -518,7 +519,8 @@ int np2_sam_export(np2_ctx_t *ctx, np2_sam_t *sam, np2_bamrec_t **recs, int32_t 
  *     and no n_no_coor.
  *   Out of scope: QUAL, RNEXT, PNEXT, TLEN, optional fields and header lines other than @HD and @SQ (all of them carried by
  *     the full stream, NP2_SAM_KEEP_ALL, below); unmapped records; CSI;
- *     the 37450 pseudo-bin; compression levels; several ranks; inputs larger than one device's memory; BAM to BAM.
+ *     the 37450 pseudo-bin; compression levels; several ranks; inputs larger than one device's memory; a BAM on standard
+ *     input (BAM files are taken: "BAM input", below).
  * The stream is assembled (k_bam_emit), compressed (k_bgzf_deflate) and indexed on the device; it never passes through host
  * memory.  Test hook, read once per call: NP2_BGZF_TEST_BATCH (blocks per batch). */
 #define NP2_SAM_KEEP_NAMES 1u
@@ -594,8 +596,9 @@ int np2_sam_export_names(np2_ctx_t *ctx, np2_sam_t *sam, uint8_t **names, uint64
  *   Memory: the tails take about 1.5 bytes per base (with the packed SEQ: one for the quality, half for SEQ) plus the optional
  *     fields and 16 bytes a record; device memory that does not suffice is NP2_E_NOMEM, and the message says how much was needed.
  *     The lean handle needs about a third of that.
- *   Out of scope: unmapped records (counted and dropped, as before); a CG tag for long CIGARs, CSI and the 37450 pseudo-bin; BAM
- *     to BAM; several ranks; validating what a tag means; the sub-fields of the input's @HD line. */
+ *   Out of scope: unmapped records (counted and dropped, as before); a CG tag for long CIGARs, CSI and the 37450 pseudo-bin; a
+ *     BAM on standard input; several ranks; inputs larger than one device's memory; validating what a tag means; the sub-fields
+ *     of the input's @HD line. */
 #define NP2_SAM_KEEP_ALL 2u
 /* the tail bytes and the tail_ref array (sorted order) of a resident SAM opened with NP2_SAM_KEEP_ALL: both released with
  * np2_free, NULL when empty */
@@ -623,6 +626,69 @@ int np2_bamout_host_full(const np2_bamrec_t *recs, const int32_t *tids, const ui
  * same.  A bad header line is NP2_E_ARG and returns nothing. */
 int np2_sam_tails_host(const uint8_t *text, uint64_t n, uint8_t **tails, uint64_t *tail_bytes, uint64_t **tail_ref, int32_t **status,
                        uint32_t **where, uint64_t *n_lines, char **header_text, uint64_t *header_bytes);
+
+/* ---- BAM input: np2_sam_open / np2_sam_open_ex take BAM files, inflated and unpacked on the device --------------------------
+ * THE RULE IS DEFINED HERE, on the SAM specification section 4.2; it is not pinned against samtools.
+ *   Inputs: each path is sniffed on its own: a file whose first bytes are a BGZF block that inflates to "BAM\1" is a BAM,
+ *     anything else is SAM text, as before.  SAM and BAM inputs may be mixed in one call.  A BAM on standard input is
+ *     NP2_E_UNSUPPORTED and the message says so.  No index is read, and the input's own order does not matter.
+ *   Header: the binary reference list (n_ref, names, l_ref) is the file's @SQ list, held to the several-files rule: it must
+ *     equal the first file's (else NP2_E_ARG with that rule's message).  The lines of the header text other than @HD and @SQ are
+ *     carried by a NP2_SAM_KEEP_ALL handle exactly as a SAM file's are.  The host reads the header (zlib on its first blocks).
+ *   A record is kept iff refID >= 0 and !(flag & 4); otherwise it counts in stats.unmapped and is looked at no further.  A
+ *     refID below -1 or >= n_ref is NP2_E_ARG.
+ *   A kept record becomes exactly what its SAM line would: np2_bamrec_t (pos, flag, mapq, n_cigar, l_seq), tid, the sort key of
+ *     the SAM path, the CIGAR words as they stand (an operation above 8 is NP2_E_ARG), the (l_seq + 1) / 2 SEQ bytes with the
+ *     low nibble of an odd last byte forced to 0; pos below -1 is NP2_E_ARG.  With NP2_SAM_KEEP_NAMES the l_read_name - 1 name
+ *     bytes: the name must be 1..254 bytes with a NUL behind them, else NP2_E_ARG.  With NP2_SAM_KEEP_ALL the tail of the full
+ *     BAM: next_refID must be -1 or < n_ref, next_pos >= -1 (else NP2_E_ARG), tlen is taken as it stands, aux_len is what
+ *     remains of block_size, then the quality bytes, then the optional fields copied verbatim.
+ *   Qualities: has_qual = 0 when l_seq == 0 or all l_seq bytes are 0xFF; otherwise every byte must be <= 93 (what the text
+ *     rule admits), else NP2_E_ARG.
+ *   Optional fields: one lane walks the types: A c C take 1 byte, s S 2, i I f 4, Z H run to a NUL inside the record, B is
+ *     subtype, u32 count, values.  The walk must end exactly at the record's end, else NP2_E_ARG.  Values are not re-encoded:
+ *     an integer keeps the type the file gave it, a float keeps its bits, inf and nan included.
+ *   Refusals: block_size < 32, or fields that overrun the record: NP2_E_ARG.  A last record the stream does not finish:
+ *     NP2_E_ARG "truncated BAM".  Fewer than 4 bytes behind the last record (or a block_size below 32 there): NP2_E_ARG.  The
+ *     long-CIGAR placeholder (n_cigar == 2, l_seq S, then an N operation): NP2_E_UNSUPPORTED, there is no CG support.  A record
+ *     of more than the piece size (4 + block_size bytes; 32 MiB, NP2_SAM_TEST_PIECE): NP2_E_UNSUPPORTED, as for a line.  A
+ *     block whose CRC32 fails: the readers' message with the block's file offset.  Every message names the file and the
+ *     record's 0-based number in that file; within a record the first check in the order of the W_* list of
+ *     csrc/np2_bamin_core.hpp speaks, within a file the first refused record.
+ *   Pieces: the reader thread takes the file's bytes into pinned pieces that end at a BGZF block boundary, so that the blocks'
+ *     summed ISIZE fits the piece size; a piece always holds at least one whole block.  A record that straddles pieces is
+ *     copied, device to device, to the front of the next piece's inflated bytes.  A missing EOF block is accepted, an empty
+ *     block anywhere too.
+ *   Order of ties is unchanged: input order, files in argument order.  np2_sam_stats_t keeps its layout: `lines` grows by a
+ *     BAM file's record count.
+ *   Out of scope: BAM on standard input, CG, CSI, unmapped records, several ranks, inputs larger than one device's memory. */
+typedef struct np2_bamin_stats {
+    uint64_t files;          /* inputs that were BAM */
+    uint64_t blocks;         /* their BGZF blocks behind the header, empty ones included */
+    uint64_t comp_bytes;     /* file bytes of those blocks */
+    uint64_t inflated_bytes; /* what they inflate to */
+    uint64_t records;        /* records walked, unmapped ones included */
+    float inflate_ms;        /* k_bgzf_inflate (HIP events, summed over the pieces, as the next four) */
+    float crc_ms;            /* k_bgzf_crc32 */
+    float walk_ms;           /* k_bamin_walk */
+    float fields_ms;         /* k_bamin_fields and the scans */
+    float pack_ms;           /* k_bamin_pack */
+} np2_bamin_stats_t;
+/* zeros for a handle none of whose inputs was a BAM */
+int np2_sam_bamin_stats(np2_sam_t *sam, np2_bamin_stats_t *stats);
+/* The host twin: uses no device.  An inflated BAM stream in host memory, header included, walked by the one-lane text of the
+ * rule (csrc/np2_bamin_core.hpp).  flags: 0, NP2_SAM_KEEP_NAMES or NP2_SAM_KEEP_ALL; opts may be NULL.  Per record in input order
+ * (*n_records of them): status[i] = 0 for a kept record, 1 for one that is not kept, NP2_E_ARG or NP2_E_UNSUPPORTED for a refused
+ * one, where[i] then says which check (np2bamin::W_*; 0 otherwise).  A stream that ends inside a record, or in bytes that are
+ * no record, has a last entry for that.  Of the *n_kept kept records, in input order: recs (cigar_off and seq_off index the
+ * arrays here), tids, cigar, seq4, names and name_ref (offset << 8 | length; with either flag), tails and tail_ref
+ * (offset << 1 | has_qual; with NP2_SAM_KEEP_ALL).  Release the ten with np2_free; each is NULL when empty.  Returns NP2_OK when
+ * no record is refused, otherwise the status of the first refused record with its message in np2_io_last_error(), the arrays
+ * filled all the same.  A bad header is NP2_E_ARG and returns nothing. */
+int np2_bamin_host(const uint8_t *stream, uint64_t n, uint32_t flags, const np2_sam_opts_t *opts, int32_t **status, uint32_t **where,
+                   uint64_t *n_records, np2_bamrec_t **recs, int32_t **tids, uint32_t **cigar, uint64_t *n_cigar_words, uint8_t **seq4,
+                   uint64_t *seq_bytes, uint8_t **names, uint64_t *name_bytes, uint64_t **name_ref, uint8_t **tails, uint64_t *tail_bytes,
+                   uint64_t **tail_ref, uint64_t *n_kept);
 
 #ifdef __cplusplus
 }

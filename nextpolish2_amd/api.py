@@ -50,7 +50,7 @@ IO_ABI_SYMBOLS = [
     "np2_sam_open", "np2_sam_close", "np2_sam_n_refs", "np2_sam_ref_name", "np2_sam_stats", "np2_contig_from_sam",
     "np2_sam_parse_bytes", "np2_sam_export",
     "np2_sam_open_ex", "np2_sam_write_bam", "np2_sam_bam_stream", "np2_bamout_host", "np2_sam_export_names",
-    "np2_sam_export_tails", "np2_sam_header_text", "np2_sam_tail_stats", "np2_bamout_host_full", "np2_sam_tails_host",
+    "np2_sam_export_tails", "np2_sam_header_text", "np2_sam_tail_stats", "np2_bamout_host_full", "np2_sam_tails_host", "np2_sam_bamin_stats", "np2_bamin_host",
 ]
 
 ERRORS = {-1: "NP2_E_ARG", -2: "NP2_E_DEVICE", -3: "NP2_E_NOMEM", -4: "NP2_E_UNSUPPORTED", -5: "NP2_E_REFPANIC"}

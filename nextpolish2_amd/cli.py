@@ -85,6 +85,9 @@ def build_parser():
     p.add_argument("--sorted_bam", default=None, metavar="hifi.map.sort.bam",
                    help="SAM input: also write the coordinate-sorted BAM and its .bai (what samtools sort and index would make of "
                         "the mapping), assembled, compressed and indexed on the GPU; single rank")
+    p.add_argument("--bam_unsorted", action="store_true",
+                   help="the BAM given is read whole, inflated, unpacked and coordinate-sorted on the GPU, as SAM text is: it need "
+                        "not be sorted and no .bai is read; what holds for SAM input holds (--sorted_bam allowed, no -S, single rank)")
     p.add_argument("--sorted_bam_full", action="store_true",
                    help="--sorted_bam: carry QUAL, RNEXT, PNEXT, TLEN, the optional fields and the header lines (@RG, @PG, @CO) too; "
                         "about three times the device memory for the resident mapping")
@@ -406,6 +409,10 @@ def main(argv=None):
         a.sam = a.bam == "-" or np2io.mapping_kind(a.bam) == "sam"
     except (ValueError, OSError) as e:
         raise SystemExit(f"Error: {e}")
+    if a.bam_unsorted:
+        if a.sam:
+            raise SystemExit("Error: --bam_unsorted says how a BAM is read; the mapping given is SAM text")
+        a.sam = True  # through the same door (io.Sam sniffs the file): every rule of SAM input below holds
     if a.sam and a.use_secondary:
         raise SystemExit("Error: -S needs the SEQ of a read's primary record, which is found by name: not with SAM input, use a sorted BAM "
                          "(python -m nextpolish2_amd.samsort writes one from the SAM text)")

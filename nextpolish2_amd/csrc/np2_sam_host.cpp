@@ -4,15 +4,26 @@
 // into pinned pieces that end at a line boundary, reads the header lines of each file on the way and hands the rest over;
 // the calling thread copies a piece to the device, finds its lines, judges them, asks for the three totals, grows the resident
 // buffers where they are short (a larger block and a device-to-device copy, after a look at the free memory) and packs.
+// An input that is a BAM (include/np2_io.h: "BAM input") goes the same way with other pieces: whole BGZF blocks as they lie in
+// the file, which the calling thread uploads, inflates and checks (k_bgzf_inflate, k_bgzf_crc32) behind the bytes of a record
+// the piece before left unfinished, walks (k_bamin_walk), judges (k_bamin_fields), scans and packs (k_bamin_pack) into the same
+// resident buffers.
 // After the last piece: keys -> stable sort -> records and CIGAR words gathered into sorted order.  The sorted keys come
 // back to the host once; a contig's range is a binary search in them.
 #include "../../include/np2_io.h"
+#include "np2_bamfile.hpp"
+#include "np2_bamin.hpp"
+#include "np2_bgzf.hpp"
 #include "np2_ctx.hpp"
+#include "np2_inflate.hpp"
+#include "np2_inflate_core.hpp"
 #include "np2_kcount.hpp"
 #include "np2_kernel_timer.hpp"
 #include "np2_sam.hpp"
 #include "np2_sam_handle.hpp"
 
+#include <fcntl.h>
+#include <sys/stat.h>
 #include <zlib.h>
 #include <unistd.h>
 
@@ -69,12 +80,20 @@ struct Piece {
     size_t off = 0, n = 0;  // the alignment lines of the piece: bytes [off, off + n) of its buffer, ending with '\n'
     int file = 0;
     uint64_t first_line = 0; // 1-based number, in its file, of the line at `off`
+    // a piece of a BAM: bytes [0, n) of the buffer are whole BGZF blocks, the file's bytes from file_off on
+    bool bam = false, last = false; // last: the file ends with this piece
+    uint64_t file_off = 0;
+    uint32_t skip = 0;                   // inflated bytes in front of the first record (the end of the header: the file's first piece)
+    std::vector<np2h::BgzfBlock> blks;   // the blocks that hold bytes; out_off counts from the piece's first block
+    uint32_t n_blocks = 0;               // ... and all of them
 };
 
 // the reader thread: pieces in input order through a two-buffer queue
 struct Reader {
     const Hooks &hooks;
     std::vector<std::string> paths; // empty: `mem`
+    std::vector<char> is_bam;       // per path (np2_sam_open_ex sniffs the files before the reader starts)
+    uint64_t bam_files = 0;
     const uint8_t *mem = nullptr;
     size_t mem_n = 0;
     static constexpr int NBUF = 2;
@@ -107,8 +126,9 @@ struct Reader {
     void start(size_t bytes_bound) { // bytes_bound: what the input can hold at most, 0 when that is not known
         piece = hooks.piece;
         if (bytes_bound) piece = std::min(piece, std::max<size_t>(bytes_bound + 1, 64));
-        for (int b = 0; b < NBUF; ++b) {
-            pin[b] = (uint8_t *)pinned[b].ensure(piece + 64);
+        const bool any_bam = std::find(is_bam.begin(), is_bam.end(), (char)1) != is_bam.end();
+        for (int b = 0; b < NBUF; ++b) { // (a piece of a BAM holds at least one whole block, of up to 64 KiB)
+            pin[b] = (uint8_t *)pinned[b].ensure(piece + 64 + (any_bam ? 65536 : 0));
             idle.push_back(b);
         }
         th = std::thread([this] { run(); });
@@ -161,6 +181,10 @@ struct Reader {
                 const size_t got = src.read(buf + fill, piece - fill);
                 eof = got == 0;
                 fill += got;
+            }
+            if (in_header && line_no == 0 && fill >= 4 && !memcmp(buf, "BAM\1", 4)) { // (gzread inflated it: a file was sniffed before)
+                release(b);
+                throw Np2Error(NP2_E_UNSUPPORTED, src.name + " is a BAM: a BAM is read from a file, not from a stream (SAM text may come from one)");
             }
             if (eof && fill && buf[fill - 1] != '\n') buf[fill++] = '\n'; // (the buffers hold piece + 64 bytes)
             size_t cut = fill;
@@ -218,6 +242,72 @@ struct Reader {
         std::lock_guard<std::mutex> l(mu);
         lines += line_no;
     }
+    // A BAM: the header on the host, then whole blocks into the pieces.  A piece ends before the block with which the summed
+    // ISIZE would pass the piece size (or the file bytes the buffer's size); it always holds one block.
+    void one_bam(const std::string &path, int file) {
+        struct Fd {
+            int fd = -1;
+            ~Fd() {
+                if (fd >= 0) close(fd);
+            }
+        } f;
+        f.fd = open(path.c_str(), O_RDONLY);
+        struct stat st;
+        if (f.fd < 0 || fstat(f.fd, &st) != 0) throw Np2Error(NP2_E_ARG, "cannot open " + path);
+        const uint64_t file_len = (uint64_t)st.st_size;
+        np2sam::Refs r;
+        std::vector<std::string> lines;
+        uint64_t pos = 0;
+        uint32_t skip = 0;
+        np2h::bam_read_header(f.fd, file_len, path, r, lines, &pos, &skip);
+        file_refs(r, path);
+        {
+            std::lock_guard<std::mutex> l(mu);
+            ++bam_files;
+            for (std::string &line : lines)
+                if (std::find(extra.begin(), extra.end(), line) == extra.end()) extra.push_back(std::move(line));
+        }
+        const size_t room = piece + 65536;
+        bool first = true;
+        while (first || pos < file_len) {
+            const int b = acquire();
+            if (b < 0) return;
+            uint8_t *buf = pin[b];
+            Piece p;
+            p.buf = b, p.file = file, p.bam = true, p.file_off = pos, p.skip = first ? skip : 0u;
+            first = false;
+            size_t fill = 0;
+            uint64_t inflated = 0;
+            try {
+                while (pos < file_len) {
+                    uint8_t head[18 + 65536], tail[8];
+                    const size_t avail = (size_t)std::min<uint64_t>(file_len - pos, 18);
+                    if (!np2h::pread_full(f.fd, head, avail, pos)) throw Np2Error(NP2_E_ARG, "cannot read the file");
+                    np2h::BgzfHeader h = np2h::bgzf_header(head, avail, file_len - pos);
+                    if (h.need) {
+                        if (!np2h::pread_full(f.fd, head, h.need, pos)) throw Np2Error(NP2_E_ARG, "cannot read the file");
+                        h = np2h::bgzf_header(head, h.need, file_len - pos);
+                    }
+                    if (!np2h::pread_full(f.fd, tail, 8, pos + h.bsize - 8)) throw Np2Error(NP2_E_ARG, "cannot read the file");
+                    const np2h::BgzfTrailer t = np2h::bgzf_trailer(tail);
+                    if (t.isize > 65536) throw Np2Error(NP2_E_ARG, "a BGZF block of more than 65536 bytes (block at file offset " + std::to_string(pos) + ")");
+                    if (p.n_blocks && (fill + h.bsize > room || inflated + t.isize > piece)) break;
+                    if (!np2h::pread_full(f.fd, buf + fill, h.bsize, pos)) throw Np2Error(NP2_E_ARG, "cannot read the file");
+                    if (t.isize) p.blks.push_back(np2h::BgzfBlock{pos, inflated, h.hdr_len, h.clen, t.isize, h.bsize, t.crc});
+                    ++p.n_blocks, fill += h.bsize, inflated += t.isize, pos += h.bsize;
+                }
+            } catch (const Np2Error &e) {
+                release(b);
+                throw Np2Error(e.code, path + ": " + e.what());
+            }
+            p.n = fill, p.last = pos >= file_len;
+            {
+                std::lock_guard<std::mutex> l(mu);
+                ready.push_back(std::move(p));
+            }
+            cv.notify_all();
+        }
+    }
     void run() {
         try {
             if (paths.empty()) {
@@ -226,6 +316,10 @@ struct Reader {
                 one_file(src, 0);
             }
             for (size_t i = 0; i < paths.size(); ++i) {
+                if (i < is_bam.size() && is_bam[i]) {
+                    one_bam(paths[i], (int)i);
+                    continue;
+                }
                 Source src;
                 src.open(paths[i]);
                 one_file(src, (int)i);
@@ -304,6 +398,18 @@ struct Build {
     np2h::PinnedBuf pin;
     np2h::DevEvent e0, e1, e_mid;
     float lines_ms = 0;    // k_sam_lines alone, of parse_ms
+    // a BAM's pieces: the file bytes, the block table with the CRC32 words behind it, the blocks' status words and the count of
+    // failed ones, the inflated stream of this piece and of the one before (whose unfinished record is copied over), the walk
+    DevBuf<uint8_t> d_comp, d_inf[2];
+    DevBuf<np2::InfBlock> d_blk;
+    DevBuf<uint32_t> d_status, d_starts, d_info;
+    DevBuf<np2::BaminCtr> d_bctr;
+    np2h::PinnedBuf pin_tab;
+    np2h::DevEvent e_b0, e_b1, e_b2;
+    int cur = 0;             // d_inf[cur] takes this piece
+    uint32_t carry_at = 0, carry_n = 0; // the unfinished record: bytes [carry_at, carry_at + carry_n) of d_inf[cur ^ 1]
+    int bam_file = -1;       // the file whose pieces are coming in
+    uint64_t file_recs = 0;  // records of that file before this piece
     uint64_t text_bytes = 0;
 
     Build(np2_ctx *c, np2_sam &s) : cx(c), sam(s), st(c->stream) {
@@ -311,8 +417,9 @@ struct Build {
         d_text.cached = d_tmp.cached = d_end.cached = d_kept.cached = d_ncig.cached = d_nseq.cached = d_koff.cached = d_coff.cached = true;
         d_soff.cached = d_lines.cached = d_ctr.cached = d_slot.cached = d_noff.cached = d_names.cached = true;
         nref_in.cached = d_nname.cached = d_nmoff.cached = d_nbad.cached = true;
+        d_comp.cached = d_inf[0].cached = d_inf[1].cached = d_blk.cached = d_status.cached = d_starts.cached = d_info.cached = d_bctr.cached = true;
         tref_in.cached = d_tsize.cached = d_taux.cached = d_toff.cached = true;
-        e0.make(), e1.make(), e_mid.make(), e_t0.make(), e_t1.make();
+        e0.make(), e1.make(), e_mid.make(), e_t0.make(), e_t1.make(), e_b0.make(), e_b1.make(), e_b2.make();
     }
     ~Build() { (void)hipStreamSynchronize(st); }
 
@@ -459,6 +566,146 @@ struct Build {
         n_recs += kept, n_cigar += n_cig, seq_bytes += n_seq, name_bytes += n_name, tail_bytes += n_tail;
     }
 
+    // One piece of a BAM: `comp` (pinned) holds the file's bytes from p.file_off on, p.blks the blocks in them that hold bytes.
+    void bam_piece(const uint8_t *comp, const Piece &p, const std::string &where, const std::function<void()> &comp_copied) {
+        namespace bi = np2bamin;
+        if (p.file != bam_file) bam_file = p.file, file_recs = 0, carry_n = 0;
+        const size_t n_blk = p.blks.size();
+        const uint64_t inflated = n_blk ? p.blks.back().out_off + p.blks.back().isize : 0, n = carry_n + inflated;
+        if (n >= (1ull << 31)) throw Np2Error(NP2_E_UNSUPPORTED, "a piece of BAM records of 2 GiB or more");
+        const uint32_t n_ref = (uint32_t)sam.refs.names.size();
+        const uint32_t flags = (keep_all ? bi::KEEP_ALL : 0u) | (keep_names ? bi::KEEP_NAMES : 0u);
+        uint8_t *inf = d_inf[cur].ensure(n + np2::BAMIN_PAD);
+        if (carry_n) HIPCHK(hipMemcpyAsync(inf, d_inf[cur ^ 1].p + carry_at, carry_n, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemsetAsync(inf + n, 0, np2::BAMIN_PAD, st));
+        sam.bamin.blocks += p.n_blocks, sam.bamin.comp_bytes += p.n, sam.bamin.inflated_bytes += inflated;
+        uint32_t *h_words = (uint32_t *)pin.ensure(256);
+        bool copied = false;
+        if (n_blk) {
+            d_comp.ensure(p.n + 64), d_blk.ensure(n_blk + (n_blk * 4 + sizeof(np2::InfBlock) - 1) / sizeof(np2::InfBlock)), d_status.ensure(n_blk + 2);
+            np2::InfBlock *h_tb = (np2::InfBlock *)pin_tab.ensure(n_blk * (sizeof(np2::InfBlock) + 4));
+            uint32_t *h_crc = (uint32_t *)(h_tb + n_blk); // (the CRC32 words travel behind the table, in the same copy)
+            for (size_t i = 0; i < n_blk; ++i) {
+                const np2h::BgzfBlock &b = p.blks[i];
+                h_tb[i] = np2::InfBlock{b.file_off - p.file_off + b.hdr_len, carry_n + b.out_off, b.clen, b.isize};
+                h_crc[i] = b.crc;
+            }
+            HIPCHK(hipMemcpyAsync(d_comp.p, comp, p.n, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(d_blk.p, h_tb, n_blk * (sizeof(np2::InfBlock) + 4), hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemsetAsync(d_status.p, 0, (n_blk + 2) * 4, st));
+            HIPCHK(hipEventRecord(e_b0.e, st));
+            np2::launch_bgzf_inflate(st, d_blk.p, (uint32_t)n_blk, d_comp.p, inf, d_status.p, d_status.p + n_blk);
+            HIPCHK(hipEventRecord(e_b1.e, st));
+            const bool crc = np2h::bgzf_crc_on();
+            if (crc) np2::launch_bgzf_crc32(st, d_blk.p, (uint32_t)n_blk, (const uint32_t *)(d_blk.p + n_blk), inf, d_status.p, d_status.p + n_blk);
+            HIPCHK(hipEventRecord(e_b2.e, st));
+            HIPCHK(hipMemcpyAsync(h_words, d_status.p + n_blk, 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            HIPCHK(hipGetLastError());
+            comp_copied(), copied = true; // the pinned buffer goes back to the reader
+            sam.bamin.inflate_ms += elapsed(e_b0, e_b1);
+            if (crc) sam.bamin.crc_ms += elapsed(e_b1, e_b2);
+            if (h_words[0]) { // the first block that failed speaks
+                std::vector<uint32_t> stv(n_blk);
+                HIPCHK(hipMemcpy(stv.data(), d_status.p, n_blk * 4, hipMemcpyDeviceToHost));
+                for (size_t i = 0; i < n_blk; ++i)
+                    if (stv[i] != np2inf::ST_OK)
+                        throw Np2Error(NP2_E_ARG, where + ": " + (stv[i] == np2inf::ST_CRC_MISMATCH ? np2h::crc_msg(p.blks[i].file_off) :
+                                                                  "BGZF inflate failed (block at file offset " + std::to_string(p.blks[i].file_off) + ")"));
+                throw Np2Error(NP2_E_DEVICE, "np2_sam: the count of failed BGZF blocks has no block to it");
+            }
+        }
+        if (!copied) comp_copied();
+        // the walk
+        d_starts.ensure(n / 36 + 2), d_bctr.ensure(1);
+        np2::BaminCtr *h = (np2::BaminCtr *)h_words;
+        uint32_t *h_tot = (uint32_t *)(h + 1);
+        h->count = 0, h->flags = 0, h->first_err = 0xFFFFFFFFu, h->tail_at = 0;
+        HIPCHK(hipMemcpyAsync(d_bctr.p, h, sizeof *h, hipMemcpyHostToDevice, st));
+        HIPCHK(hipEventRecord(e0.e, st));
+        np2::launch_bamin_walk(st, inf, p.skip, (uint32_t)n, (uint32_t)std::min<size_t>(hooks.piece, 1u << 30), d_starts.p, d_bctr.p);
+        HIPCHK(hipEventRecord(e1.e, st));
+        HIPCHK(hipMemcpyAsync(h, d_bctr.p, sizeof *h, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipGetLastError());
+        sam.bamin.walk_ms += elapsed(e0, e1);
+        const uint32_t count = h->count, walk_flags = h->flags, tail_at = h->tail_at;
+        if (count > n / 36 + 1 || tail_at > n) throw Np2Error(NP2_E_DEVICE, "np2_sam: record walk out of range");
+        uint64_t kept = 0, n_cig = 0, n_seq = 0, n_name = 0, n_tail = 0;
+        if (count) {
+            const size_t m = (size_t)count + 1;
+            d_info.ensure(m), d_kept.ensure(m), d_ncig.ensure(m), d_nseq.ensure(m), d_koff.ensure(m), d_coff.ensure(m), d_soff.ensure(m);
+            if (keep_names) d_nname.ensure(m), d_nmoff.ensure(m);
+            if (keep_all) d_tsize.ensure(m), d_toff.ensure(m);
+            const size_t tmp_bytes = np2::prim_temp_bytes(m);
+            d_tmp.ensure(tmp_bytes);
+            HIPCHK(hipEventRecord(e0.e, st));
+            np2::launch_bamin_fields(st, inf, d_starts.p, count, walk_flags, n_ref, flags, d_info.p, d_kept.p, d_ncig.p, d_nseq.p, d_nname.p, d_tsize.p, d_bctr.p);
+            if (np2::prim_exclusive_sum_u32(st, d_tmp.p, tmp_bytes, d_kept.p, d_koff.p, m) ||
+                np2::prim_exclusive_sum_u32(st, d_tmp.p, tmp_bytes, d_ncig.p, d_coff.p, m) ||
+                np2::prim_exclusive_sum_u32(st, d_tmp.p, tmp_bytes, d_nseq.p, d_soff.p, m) ||
+                (keep_names && np2::prim_exclusive_sum_u32(st, d_tmp.p, tmp_bytes, d_nname.p, d_nmoff.p, m)) ||
+                (keep_all && np2::prim_exclusive_sum_u32(st, d_tmp.p, tmp_bytes, d_tsize.p, d_toff.p, m)))
+                throw Np2Error(NP2_E_DEVICE, "rocprim exclusive_scan failed");
+            HIPCHK(hipEventRecord(e1.e, st));
+            h_tot[3] = h_tot[4] = 0;
+            HIPCHK(hipMemcpyAsync(h, d_bctr.p, sizeof *h, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(h_tot + 0, d_koff.p + count, 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(h_tot + 1, d_coff.p + count, 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(h_tot + 2, d_soff.p + count, 4, hipMemcpyDeviceToHost, st));
+            if (keep_names) HIPCHK(hipMemcpyAsync(h_tot + 3, d_nmoff.p + count, 4, hipMemcpyDeviceToHost, st));
+            if (keep_all) HIPCHK(hipMemcpyAsync(h_tot + 4, d_toff.p + count, 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            HIPCHK(hipGetLastError());
+            sam.bamin.fields_ms += elapsed(e0, e1);
+            if (h->first_err != 0xFFFFFFFFu) { // the first refused record of the first offending piece
+                if (h->first_err >= count) throw Np2Error(NP2_E_DEVICE, "np2_sam: refused record out of range");
+                HIPCHK(hipMemcpyAsync(h_tot + 8, d_info.p + h->first_err, 4, hipMemcpyDeviceToHost, st));
+                HIPCHK(hipStreamSynchronize(st));
+                const uint32_t w = h_tot[8] & 255u;
+                std::string msg = where + ": " + bi::record_message(file_recs + h->first_err, w);
+                if (w == bi::W_PIECE) msg += " of " + std::to_string(hooks.piece) + " bytes";
+                throw Np2Error(bi::where_status(w), msg);
+            }
+            kept = h_tot[0], n_cig = h_tot[1], n_seq = h_tot[2], n_name = h_tot[3], n_tail = h_tot[4];
+            if (kept > count || n_cig > n / 4 || n_seq > n || n_name > kept * 254u || n_tail % 4u || n_tail > n + kept * (np2tail::HEAD_BYTES + 4ull))
+                throw Np2Error(NP2_E_DEVICE, "np2_sam: record counters out of range");
+            if (n_recs + kept >= (1ull << 31)) throw Np2Error(NP2_E_UNSUPPORTED, "a SAM input of 2^31 alignment records or more");
+            if (n_cigar + n_cig >= 0xFFFF0000ull) throw Np2Error(NP2_E_UNSUPPORTED, "a SAM input of more than 4294901760 CIGAR operations");
+        }
+        if (kept) {
+            if (keep_names) {
+                grow(nref_in, n_recs, n_recs + kept, st, "names");
+                grow(sam.names, name_bytes, name_bytes + n_name + 1, st, "names");
+            }
+            if (keep_all) {
+                grow(tref_in, n_recs, n_recs + kept, st, "tails");
+                grow(sam.tails, tail_bytes, tail_bytes + n_tail + 16, st, "quality bytes and optional fields");
+            }
+            grow(recs_in, n_recs * np2::SAM_REC_WORDS, (n_recs + kept) * np2::SAM_REC_WORDS, st, "records");
+            grow(tids_in, n_recs, n_recs + kept, st, "records");
+            grow(keys_in, n_recs, n_recs + kept, st, "sort keys");
+            grow(cigar_in, n_cigar, n_cigar + n_cig + 1, st, "CIGAR words");
+            grow(sam.seq4, seq_bytes, seq_bytes + n_seq + 16, st, "packed SEQ");
+            const np2::BaminOut out{d_koff.p, d_coff.p, d_soff.p, d_nmoff.p, d_toff.p, n_recs, n_cigar, seq_bytes, name_bytes, tail_bytes, recs_in.p,
+                                    tids_in.p, keys_in.p, cigar_in.p, sam.seq4.p, sam.names.p, nref_in.p, sam.tails.p, tref_in.p};
+            HIPCHK(hipEventRecord(e0.e, st));
+            np2::launch_bamin_pack(st, inf, d_starts.p, d_info.p, count, n_ref, flags, tie, out);
+            HIPCHK(hipEventRecord(e1.e, st));
+            HIPCHK(hipStreamSynchronize(st));
+            HIPCHK(hipGetLastError());
+            sam.bamin.pack_ms += elapsed(e0, e1);
+        }
+        n_records += count, file_recs += count, sam.bamin.records += count;
+        n_recs += kept, n_cigar += n_cig, seq_bytes += n_seq, name_bytes += n_name, tail_bytes += n_tail;
+        carry_at = tail_at, carry_n = (uint32_t)n - tail_at, cur ^= 1;
+        if (p.last && carry_n) {
+            const uint32_t w = carry_n < 4u ? bi::W_GARBAGE : bi::W_TRUNC;
+            carry_n = 0;
+            throw Np2Error(NP2_E_ARG, where + ": " + bi::record_message(file_recs, w));
+        }
+    }
+
     // Line `r` of the piece (n bytes, still in d_text) has a bad name or a bad tail: the host reads the line and walks it with the
     // one-lane text of the rule to say which field.  Returns when the tail is good (the name is what is wrong).
     void bad_tail(uint32_t r, size_t n, const std::string &at) {
@@ -548,11 +795,12 @@ void build(np2_ctx *cx, np2_sam &sam, Reader &rd, const np2_sam_opts_t *opts, si
             std::lock_guard<std::mutex> l(rd.mu);
             sam.refs = rd.refs;
         }
-        if (!b.have_nt) b.name_table(sam.refs);
+        if (!b.have_nt && !p.bam) b.name_table(sam.refs); // (a BAM's records carry numbers, not names)
         const std::string where = rd.paths.empty() ? "the text" : rd.paths[p.file] == "-" ? "standard input" : rd.paths[p.file];
         bool back = false;
         try {
-            b.piece(rd.pin[p.buf] + p.off, p.n, where, p.first_line, [&] { rd.release(p.buf), back = true; });
+            if (p.bam) b.bam_piece(rd.pin[p.buf], p, where, [&] { rd.release(p.buf), back = true; });
+            else b.piece(rd.pin[p.buf] + p.off, p.n, where, p.first_line, [&] { rd.release(p.buf), back = true; });
         } catch (...) {
             if (!back) {
                 (void)hipStreamSynchronize(cx->stream); // (the copy out of the pinned buffer may be in flight)
@@ -565,7 +813,8 @@ void build(np2_ctx *cx, np2_sam &sam, Reader &rd, const np2_sam_opts_t *opts, si
         std::lock_guard<std::mutex> l(rd.mu);
         if (rd.err_code) throw Np2Error(rd.err_code, rd.err_msg);
         sam.refs = rd.refs;
-        sam.stats.lines = rd.lines;
+        sam.stats.lines = rd.lines + sam.bamin.records;
+        sam.bamin.files = rd.bam_files;
         if (b.keep_all)
             for (const std::string &l : rd.extra) sam.extra_header += l + "\n";
     }
@@ -623,6 +872,7 @@ int np2_sam_open_ex(np2_ctx_t *cx, const char *const *paths, int n_paths, const 
         for (int i = 0; i < n_paths; ++i) {
             if (!paths[i]) throw Np2Error(NP2_E_ARG, "np2_sam_open: a path is NULL");
             rd.paths.push_back(paths[i]);
+            rd.is_bam.push_back(0);
             if (rd.paths.back() == "-") {
                 if (++n_stdin > 1) throw Np2Error(NP2_E_ARG, "np2_sam_open: standard input is given twice");
                 continue;
@@ -630,6 +880,7 @@ int np2_sam_open_ex(np2_ctx_t *cx, const char *const *paths, int n_paths, const 
             FILE *f = fopen(paths[i], "rb");
             if (!f) throw Np2Error(NP2_E_ARG, std::string("cannot open ") + paths[i] + (flags & NP2_SAM_KEEP_ALL ? " (np2_sam_open_ex, flag NP2_SAM_KEEP_ALL)" : ""));
             fclose(f);
+            rd.is_bam.back() = np2h::is_bam_file(paths[i]) ? 1 : 0;
         }
         touched = true;
         std::unique_ptr<np2_sam> sam(new np2_sam());

@@ -24,7 +24,7 @@ IO_SYMBOLS = ["np2_fasta_open", "np2_fasta_next", "np2_fasta_close", "np2_yak_lo
               "np2_kcount_files_to_dumps_ad", "np2_ctx_create_from_reads_ad", "np2_bgzf_deflate_device", "np2_bgzf_deflate_host",
               "np2_bgzf_writer_open", "np2_bgzf_writer_write", "np2_bgzf_writer_close", "np2_sam_open_ex", "np2_sam_write_bam",
               "np2_sam_bam_stream", "np2_bamout_host", "np2_sam_export_names", "np2_sam_export_tails", "np2_sam_header_text",
-              "np2_sam_tail_stats", "np2_bamout_host_full", "np2_sam_tails_host"]
+              "np2_sam_tail_stats", "np2_bamout_host_full", "np2_sam_tails_host", "np2_sam_bamin_stats", "np2_bamin_host"]
 
 
 class np2_front_opts_t(C.Structure):
@@ -53,6 +53,11 @@ class np2_sam_stats_t(C.Structure):
 class np2_bamout_stats_t(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("records", "stream_bytes", "file_bytes", "blocks", "bins", "chunks")] + \
                [(n, C.c_float) for n in ("sizes_ms", "emit_ms", "deflate_ms", "index_ms")]
+
+
+class np2_bamin_stats_t(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("files", "blocks", "comp_bytes", "inflated_bytes", "records")] + \
+               [(n, C.c_float) for n in ("inflate_ms", "crc_ms", "walk_ms", "fields_ms", "pack_ms")]
 
 
 NP2_SAM_KEEP_NAMES = 1
@@ -329,6 +334,9 @@ def _bind_sam(L):
     L.np2_bamout_host_full.argtypes = [vp, vp, vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, vp, C.c_uint64, vp, vp, C.c_uint64, vp, vp, C.c_uint64,
                                        C.POINTER(C.c_char_p), vp, C.c_int, C.c_char_p, C.c_char_p, C.POINTER(vp), u64p, bs]
     L.np2_sam_tails_host.argtypes = [vp, C.c_uint64, C.POINTER(vp), u64p, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), u64p, C.POINTER(vp), u64p]
+    L.np2_sam_bamin_stats.argtypes = [vp, C.POINTER(np2_bamin_stats_t)]
+    pvp = C.POINTER(vp)
+    L.np2_bamin_host.argtypes = [vp, C.c_uint64, C.c_uint32, so, pvp, pvp, u64p, pvp, pvp, pvp, u64p, pvp, u64p, pvp, u64p, pvp, pvp, u64p, pvp, u64p]
 
 
 def _bind_kcount(L):
@@ -753,7 +761,8 @@ def _sam_stats_dict(st):
 
 
 class Sam:
-    """np2_sam_open: the mapper's SAM text (one or more files, plain or gzip; "-" is standard input) parsed and
+    """np2_sam_open: the mapper's SAM text (one or more files, plain or gzip; "-" is standard input) or BAM files (sorted or
+    not, no index is read; each path is sniffed on its own, and both kinds may be mixed), parsed or unpacked and
     coordinate-sorted on the device of Polisher `pol`, the sorted records, their CIGAR words and the packed SEQ left resident
     there (include/np2_io.h has the rule).  tie: "strand" orders records at one position by strand, as samtools sort does;
     "input" leaves them in input order.  Read-only once open: contig_from_sam may be called from several threads, each with
@@ -840,6 +849,13 @@ class Sam:
         _io_check(_bind().np2_sam_header_text(self._h, C.byref(p), C.byref(n)))
         return C.string_at(p.value, n.value)
 
+    def bamin_stats(self):
+        """np2_sam_bamin_stats: of the inputs that were BAM: files, blocks, comp_bytes, inflated_bytes, records, and the HIP-event
+        times inflate_ms, crc_ms, walk_ms, fields_ms, pack_ms summed over the pieces (zeros when no input was a BAM)"""
+        st = np2_bamin_stats_t()
+        _io_check(_bind().np2_sam_bamin_stats(self._h, C.byref(st)))
+        return {n: (int if t is C.c_uint64 else float)(getattr(st, n)) for n, t in np2_bamin_stats_t._fields_}
+
     def tail_stats(self):
         """np2_sam_tail_stats: {tail_len_ms, tail_emit_ms, tail_bytes} of the two kernels keep_all=True adds"""
         a, b, n = C.c_float(), C.c_float(), C.c_uint64()
@@ -921,6 +937,37 @@ def sam_tails_host(text):
     finally:
         for p in (pt, pr, ps, pw, ph):
             L.np2_free(p)
+
+
+def bamin_host(stream, keep_names=False, keep_all=False, tie="strand"):
+    """np2_bamin_host (no device): an inflated BAM stream (bytes, header included) walked by the one-lane text of the rule.
+    -> dict: status (int32) and where (uint32) per record in input order; of the kept records, in input order, recs
+    (BAMREC_DTYPE), tids, cigar, seq4, names, name_ref, tails, tail_ref; code and message: 0 and "" when no record is refused,
+    else the status and message of the first refused one.  A bad header raises Np2Error."""
+    L = _bind()
+    buf = np.frombuffer(bytes(stream), dtype=np.uint8)
+    o = _sam_opts(tie)
+    flags = NP2_SAM_KEEP_ALL if keep_all else NP2_SAM_KEEP_NAMES if keep_names else 0
+    p = {k: C.c_void_p() for k in ("status", "where", "recs", "tids", "cigar", "seq4", "names", "name_ref", "tails", "tail_ref")}
+    n = {k: C.c_uint64() for k in ("records", "cigar", "seq4", "names", "tails", "kept")}
+    rc = L.np2_bamin_host(buf.ctypes.data if len(buf) else None, len(buf), flags, C.byref(o), C.byref(p["status"]), C.byref(p["where"]),
+                          C.byref(n["records"]), C.byref(p["recs"]), C.byref(p["tids"]), C.byref(p["cigar"]), C.byref(n["cigar"]),
+                          C.byref(p["seq4"]), C.byref(n["seq4"]), C.byref(p["names"]), C.byref(n["names"]), C.byref(p["name_ref"]),
+                          C.byref(p["tails"]), C.byref(n["tails"]), C.byref(p["tail_ref"]), C.byref(n["kept"]))
+    if rc and not n["records"].value:
+        _io_check(rc)
+    try:
+        take = lambda k, count, dt: (np.frombuffer(C.string_at(p[k].value, count * np.dtype(dt).itemsize), dtype=dt).copy()
+                                     if count and p[k].value else np.zeros(0, dt))
+        nr, nk = n["records"].value, n["kept"].value
+        return dict(status=take("status", nr, np.int32), where=take("where", nr, np.uint32), recs=take("recs", nk, BAMREC_DTYPE),
+                    tids=take("tids", nk, np.int32), cigar=take("cigar", n["cigar"].value, np.uint32), seq4=take("seq4", n["seq4"].value, np.uint8),
+                    names=take("names", n["names"].value, np.uint8), name_ref=take("name_ref", nk if flags else 0, np.uint64),
+                    tails=take("tails", n["tails"].value, np.uint8), tail_ref=take("tail_ref", nk if keep_all else 0, np.uint64), code=rc,
+                    message=L.np2_io_last_error().decode(errors="replace") if rc else "")
+    finally:
+        for v in p.values():
+            L.np2_free(v)
 
 
 def _sam_arrays(L, pr, pt, pc, ps, n, stats):
