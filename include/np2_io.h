@@ -417,6 +417,91 @@ int np2_rep_bytes(int device, const uint8_t *seq, uint64_t n, const np2_rep_opts
 int np2_rep_files(int device, const char *const *paths, int n_paths, const np2_rep_opts_t *opts, const char *out_path,
                   int both_strands, np2_rep_stats_t *stats);
 
+/* ---- HiFi reads mapped to the assembly: minimizer seeds chained into PAF (the reference's README, "General usage" step 2:
+ * winnowmap -W repetitive_k15.txt -ax map-pb asm.fa.gz hifi.fa.gz; here the seed-and-chain half, as `minimap2 -x map-hifi`
+ * without -a prints it) ------------------------------------------------------------------------------------------------------
+ * THE RULE IS DEFINED HERE, on minimap2's published algorithm (Li 2018, Bioinformatics 34:3094; the integer chaining score of
+ * minimap2 <= 2.17).  No minimap2 binary was at hand: equality with its output is not claimed and not tested.
+ *   Options (np2_map_opts_t; defaults in brackets): k [19], w [19], max_occ [200], lookback [64], max_gap [10000], bandwidth
+ *     [500], min_cnt [3], min_score [40].  11 <= k <= 28, 1 <= w <= 64, 1 <= lookback <= 64, anything else is
+ *     NP2_E_UNSUPPORTED; max_occ 1 .. 2^20, max_gap 1 .. 2^30, bandwidth <= 2^20, min_cnt and min_score <= 2^30, anything else
+ *     is NP2_E_ARG.  An index is built with k and w; mapping against it with another k or w is NP2_E_ARG.
+ *   Sketch (assembly and reads alike).  Bases: ACGT in either case are 0..3; every other byte (N, U, separators, bytes >= 0x80)
+ *     ends the run of bases.  The k-mer ending at byte i has the forward word fw and the reverse-complement word rv, first base
+ *     most significant; its strand bit is fw > rv and its hash h = yak_hash64(min(fw, rv), 2k-bit mask) (minimap2's hash64).  A
+ *     k-mer with fw == rv (even k only) is never chosen, but it does not end the run.  A window is w consecutive k-mer end
+ *     positions inside one run of bases.  Position i is a minimizer if and only if some window holds it and (h_i, i) is the
+ *     lexicographic minimum of that window over its k-mers with fw != rv: the leftmost of equal hashes wins.  A run with fewer
+ *     than w k-mers has no minimizer.
+ *   Index.  The assembly's minimizers (h, tid, end position, strand), stably sorted by h from (tid, position) order; occ(h) is
+ *     the length of the run of equal h.  It stays in device memory behind the handle.
+ *   Seeds.  Every read minimizer with 1 <= occ <= max_occ gives one anchor per index entry: rel = read strand ^ assembly
+ *     strand, r = the entry's end position, q = the read k-mer's end position if rel == 0, else qlen - 1 - (end - (k - 1)): its
+ *     end on the reverse-complemented read.  A read's anchors are ordered by (rel, tid, r, q).  A minimizer with occ > max_occ
+ *     is dropped (and counted), not down-weighted.
+ *   Chain.  For anchor i and each j in [max(0, i - lookback), i): j is admissible when it has i's rel and tid, 0 < dr = r_i -
+ *     r_j <= max_gap, 0 < dq = q_i - q_j <= max_gap and dd = |dr - dq| <= bandwidth; sc = min(dr, dq, k) - (dd * k / 100 +
+ *     (dd > 0 ? ilog2(dd) >> 1 : 0)) in integers with floor division; f[i] = max(k, max_j f[j] + sc); p[i] is the best j, of
+ *     equal candidates the largest, and -1 when no candidate exceeds k.  The primary chain ends at the smallest i with the
+ *     largest f (s1) and is followed back through p; its anchors are marked.  One forward sweep over the unmarked anchors:
+ *     base[i] = 0 if p[i] < 0, f[p[i]] if p[i] is marked, else base[p[i]]; s2 = max(f[i] - base[i]) over them, 0 if there is
+ *     none.  With n the chain's anchors, mapq = min(60, (60 * (s1 - s2) / s1) * min(n, 10) / 10), integer divisions in that
+ *     order.  A read with n < min_cnt or s1 < min_score is unmapped (tid -1).
+ *   Hit.  On the chain's strand the chain covers q' in [q_first - k + 1, q_last + 1) and t in [r_first - k + 1, r_last + 1);
+ *     for rel == 1, qs = qlen - q'_end and qe = qlen - q'_start.  matches (PAF column 10) is k for the first anchor plus
+ *     min(k, dr, dq) for each later one; block (column 11) is max(qe - qs, te - ts).  A PAF line is
+ *     qname qlen qs qe +/- tname tlen ts te matches block mapq tp:A:P cm:i:n s1:i:s1 s2:i:s2, tab-separated, one per mapped
+ *     read in read order; a name is the header up to the first whitespace (a record without one: its 1-based number).
+ *   Not built: base-level alignment, CIGAR, SAM / BAM output; secondary and supplementary chains; winnowmap's -W weighting;
+ *     -f occurrence fractions; homopolymer compression; several devices; an index beyond one device's memory.  NP2_E_UNSUPPORTED:
+ *     an assembly of 2^32 bytes or more, a sequence or read longer than 2^31 - 1, a single read with more anchors than the
+ *     device budget (2^25).
+ * Every argument is checked before the first device call.  Errors: np2_io_last_error().  Test hooks, read once per call:
+ * NP2_MAP_TEST_PIECE (bytes; a batch of reads goes up and is sketched in pieces of 8 MiB, eight pieces a batch, wherever the
+ * boundary falls in a read) and NP2_MAP_TEST_BUDGET (anchors; a batch beyond it is chained in groups of whole reads). */
+typedef struct np2_map_opts {
+    uint32_t k, w, max_occ, lookback, max_gap, bandwidth, min_cnt, min_score;
+} np2_map_opts_t;
+typedef struct np2_map_hit {
+    int32_t tid;                     /* -1: unmapped (only qlen is set then) */
+    uint32_t qlen, qs, qe, rev;      /* rev: rel of the chain, 1 = the read's reverse complement matches */
+    uint32_t ts, te, matches, block, mapq;
+    uint32_t n, s1, s2;              /* cm:i, s1:i, s2:i */
+} np2_map_hit_t;
+typedef struct np2_map_stats {
+    uint64_t reads, mapped, unmapped;
+    uint64_t minimizers;             /* of the reads */
+    uint64_t anchors, dropped_occ;   /* dropped_occ: read minimizers with occ > max_occ */
+    uint64_t index_minimizers;
+    uint32_t pieces, groups;
+    float sketch_ms, seed_ms, sort_ms, chain_ms; /* the stages' HIP events, summed over batches; 0 from np2_map_host */
+    float read_ms, write_ms;         /* np2_map_files: the device thread's wait for its readers, and formatting and writing the PAF */
+} np2_map_stats_t;
+typedef struct np2_map_index np2_map_index_t;
+/* An assembly -> its index on `device`; opts gives k and w (the other options are checked too).  From a separator stream in
+ * host memory (every sequence followed by '\n'); names: the sequences' names, each followed by '\n', or NULL (1-based
+ * numbers).  From FASTA files, plain or gzip, in the order given. */
+int np2_map_index_bytes(int device, const uint8_t *stream, uint64_t n, const char *names, const np2_map_opts_t *opts, np2_map_index_t **out);
+int np2_map_index_files(int device, const char *const *paths, int n_paths, const np2_map_opts_t *opts, np2_map_index_t **out);
+void np2_map_index_free(np2_map_index_t *ix);
+/* any of the outputs may be NULL; build_ms: the build's kernels and sorts (HIP events) */
+int np2_map_index_info(const np2_map_index_t *ix, uint32_t *k, uint32_t *w, uint64_t *n_seqs, uint64_t *n_minimizers, float *build_ms);
+int np2_map_index_seq(const np2_map_index_t *ix, uint64_t i, const char **name /* the handle's */, uint64_t *len);
+/* Reads as a separator stream of n_reads sequences -> hits[n_reads].  With chain and chain_off (both or neither):
+ * chain_off[n_reads + 1] (the caller's) and *chain (np2_free), the primary chains' anchors as (r, q) pairs of uint32 on the
+ * chain's strand, first to last: read i's are pairs chain_off[i] .. chain_off[i + 1]. */
+int np2_map_bytes(const np2_map_index_t *ix, const uint8_t *reads, uint64_t n, uint64_t n_reads, const np2_map_opts_t *opts,
+                  np2_map_hit_t *hits, uint32_t **chain, uint64_t *chain_off);
+/* read files (FASTA / FASTQ, plain or gzip, through the read binner's reader threads) -> the PAF file out_path; a path ending
+ * in .gz or .bgz is written as BGZF, compressed on the index's device.  stats may be NULL. */
+int np2_map_files(const np2_map_index_t *ix, const char *const *paths, int n_paths, const np2_map_opts_t *opts, const char *out_path,
+                  np2_map_stats_t *stats);
+/* host only, no device: the same rule from the same arithmetic (csrc/np2_map_core.hpp), one read at a time */
+int np2_map_host(const uint8_t *asm_stream, uint64_t n_asm, const uint8_t *reads, uint64_t n, uint64_t n_reads, const np2_map_opts_t *opts,
+                 np2_map_hit_t *hits, uint32_t **chain, uint64_t *chain_off);
+/* the counts and stage times of the last np2_map_bytes / np2_map_files / np2_map_host call on this thread */
+int np2_map_last_stats(np2_map_stats_t *stats);
+
 /* ---- the mapper's SAM, parsed and coordinate-sorted on the device (the reference's recipe: `| samtools sort -o ... ;
  * samtools index ...`, which exist only so that an indexed reader can fetch one contig's records in coordinate order) -------
  * THE RULE IS DEFINED HERE, on the SAM specification section 1.4 and on what samtools' coordinate comparison is understood to

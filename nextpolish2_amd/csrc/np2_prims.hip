@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
 #include "np2_kernels.hpp"
+#include "np2_map.hpp"
 
 namespace np2 {
 
@@ -43,6 +44,19 @@ int prim_inclusive_sum_i32(hipStream_t s, void *tmp, size_t tmp_bytes, const int
 int prim_inclusive_min_i32(hipStream_t s, void *tmp, size_t tmp_bytes, const int32_t *in, int32_t *out, size_t n) {
     if (n == 0) return 0;
     return (int)rocprim::inclusive_scan(tmp, tmp_bytes, in, out, n, rocprim::minimum<int32_t>(), s);
+}
+// (key, value) pairs of 64 bits each: the mapper's index and its two-pass anchor sort (np2_map_host.cpp)
+size_t prim_pairs64_temp_bytes(size_t n) {
+    size_t b = 0;
+    if (n == 0) n = 1;
+    (void)rocprim::radix_sort_pairs(nullptr, b, (const uint64_t *)nullptr, (uint64_t *)nullptr, (const uint64_t *)nullptr,
+                              (uint64_t *)nullptr, n, 0, 64, (hipStream_t)0);
+    return b + 256;
+}
+int prim_sort_pairs_u64_u64(hipStream_t s, void *tmp, size_t tmp_bytes, const uint64_t *kin, uint64_t *kout, const uint64_t *vin,
+                            uint64_t *vout, size_t n, unsigned end_bit) {
+    if (n == 0) return 0;
+    return (int)rocprim::radix_sort_pairs(tmp, tmp_bytes, kin, kout, vin, vout, n, 0, end_bit, s);
 }
 
 } // namespace np2

@@ -64,6 +64,22 @@ NP2_SAM_KEEP_NAMES = 1
 NP2_SAM_KEEP_ALL = 2
 
 
+class np2_map_opts_t(C.Structure):
+    _fields_ = [(f, C.c_uint32) for f in ("k", "w", "max_occ", "lookback", "max_gap", "bandwidth", "min_cnt", "min_score")]
+
+
+class np2_map_stats_t(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("reads", "mapped", "unmapped", "minimizers", "anchors", "dropped_occ", "index_minimizers")] + \
+               [("pieces", C.c_uint32), ("groups", C.c_uint32)] + [(f, C.c_float) for f in ("sketch_ms", "seed_ms", "sort_ms", "chain_ms", "read_ms", "write_ms")]
+
+
+assert C.sizeof(np2_map_opts_t) == 32 and C.sizeof(np2_map_stats_t) == 88
+MAP_DEFAULTS = dict(k=19, w=19, max_occ=200, lookback=64, max_gap=10000, bandwidth=500, min_cnt=3, min_score=40)
+# np2_map_hit_t
+MAP_HIT_DTYPE = np.dtype([("tid", "<i4")] + [(f, "<u4") for f in ("qlen", "qs", "qe", "rev", "ts", "te", "matches", "block", "mapq", "n", "s1", "s2")])
+assert MAP_HIT_DTYPE.itemsize == 52
+
+
 class FrontOpts:
     """Read-admission options with the reference defaults (src/utils/option.rs:267-292; -a 500.5 splits into
     min_map_len = 500 and min_map_fra = 0.5, option.rs:232,258-259)."""
@@ -297,6 +313,21 @@ def _bind_locked(L):
         _bind_shard(L)
         _bind_kcount(L)
         _bind_sam(L)
+        _bind_map(L)
+
+
+def _bind_map(L):
+    vp, u64, mo = C.c_void_p, C.c_uint64, C.POINTER(np2_map_opts_t)
+    L.np2_map_index_bytes.argtypes = [C.c_int, vp, u64, C.c_char_p, mo, C.POINTER(vp)]
+    L.np2_map_index_files.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.c_int, mo, C.POINTER(vp)]
+    L.np2_map_index_free.argtypes = [vp]
+    L.np2_map_index_free.restype = None
+    L.np2_map_index_info.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_float)]
+    L.np2_map_index_seq.argtypes = [vp, u64, C.POINTER(C.c_char_p), C.POINTER(u64)]
+    L.np2_map_bytes.argtypes = [vp, vp, u64, u64, mo, vp, C.POINTER(vp), vp]
+    L.np2_map_files.argtypes = [vp, C.POINTER(C.c_char_p), C.c_int, mo, C.c_char_p, C.POINTER(np2_map_stats_t)]
+    L.np2_map_host.argtypes = [vp, u64, vp, u64, u64, mo, vp, C.POINTER(vp), vp]
+    L.np2_map_last_stats.argtypes = [C.POINTER(np2_map_stats_t)]
 
 
 def _bind_shard(L):
@@ -1241,3 +1272,132 @@ def crc32_device(pol, data, offsets):
     if rc != 0:
         raise Np2Error(rc, "np2_crc32_device: " + (L.np2_io_last_error() or b"").decode())
     return out[:n_pieces].copy(), float(ms.value)
+
+
+# ---- the mapper (include/np2_io.h: np2_map_*) -------------------------------------------------------------------------------
+def map_opts(**kw):
+    """np2_map_opts_t from keyword options; what is not given takes its default (MAP_DEFAULTS)"""
+    unknown = set(kw) - set(MAP_DEFAULTS)
+    if unknown:
+        raise TypeError(f"unknown mapping option(s): {sorted(unknown)}")
+    vals = {**MAP_DEFAULTS, **{k: v for k, v in kw.items() if v is not None}}
+    for k, v in vals.items():
+        if not 0 <= int(v) <= 0xFFFFFFFF:
+            raise ValueError(f"{k}: 0 .. 2^32 - 1")
+    return np2_map_opts_t(*[int(vals[f]) for f, _ in np2_map_opts_t._fields_])
+
+
+def _map_stats_dict(st):
+    return {f: getattr(st, f) for f, _ in np2_map_stats_t._fields_}
+
+
+def map_last_stats():
+    """counts and stage times (HIP events, ms) of this thread's last mapping call"""
+    st = np2_map_stats_t()
+    _io_check(_bind().np2_map_last_stats(C.byref(st)))
+    return _map_stats_dict(st)
+
+
+def _stream_of(seqs):
+    """a separator stream (bytes) or a list of sequences -> (uint8 array, number of sequences)"""
+    if isinstance(seqs, (bytes, bytearray, memoryview, np.ndarray)):
+        s = np.frombuffer(bytes(seqs), dtype=np.uint8) if not isinstance(seqs, np.ndarray) else np.ascontiguousarray(seqs, np.uint8)
+        return s, int(np.count_nonzero(s == 10))
+    seqs = [bytes(x) if not isinstance(x, str) else x.encode() for x in seqs]
+    return np.frombuffer(b"".join(x + b"\n" for x in seqs), dtype=np.uint8), len(seqs)
+
+
+def _map_result(L, call, s, n, want_chains):
+    hits = np.zeros(n, MAP_HIT_DTYPE)
+    if not want_chains:
+        _io_check(call(s.ctypes.data if len(s) else None, len(s), n, hits.ctypes.data if n else None, None, None))
+        return hits, None, None
+    pc, off = C.c_void_p(), np.zeros(n + 1, np.uint64)
+    _io_check(call(s.ctypes.data if len(s) else None, len(s), n, hits.ctypes.data if n else None, C.byref(pc), off.ctypes.data))
+    try:
+        m = int(off[n])
+        from .api import _Raw
+        chain = np.asarray(_Raw(pc.value, 2 * m, "<u4")).copy().reshape(m, 2) if m else np.zeros((0, 2), np.uint32)
+    finally:
+        L.np2_free(pc)
+    return hits, chain, off
+
+
+class MapIndex:
+    """An assembly's minimizer index, resident on `device` (np2_map_index_*).  `asm`: a FASTA path or a list of paths, or
+    (with stream=True) a separator stream / a list of sequences in memory, with `names` or numbered from 1."""
+
+    def __init__(self, asm, k=19, w=19, device=0, stream=False, names=None):
+        L = _bind()
+        self._L, self._h = L, C.c_void_p()
+        o = map_opts(k=k, w=w)
+        if stream:
+            s, n = _stream_of(asm)
+            nm = None if names is None else "".join(x + "\n" for x in names).encode()
+            _io_check(L.np2_map_index_bytes(device, s.ctypes.data if len(s) else None, len(s), nm, C.byref(o), C.byref(self._h)))
+        else:
+            arr, n = _paths(asm)
+            _io_check(L.np2_map_index_files(device, arr, n, C.byref(o), C.byref(self._h)))
+        k_, w_, ns, nm_, ms = C.c_uint32(), C.c_uint32(), C.c_uint64(), C.c_uint64(), C.c_float()
+        _io_check(L.np2_map_index_info(self._h, C.byref(k_), C.byref(w_), C.byref(ns), C.byref(nm_), C.byref(ms)))
+        self.k, self.w, self.n_minimizers, self.build_ms, self.device = k_.value, w_.value, nm_.value, ms.value, device
+        self.names, self.lens = [], []
+        for i in range(ns.value):
+            name, ln = C.c_char_p(), C.c_uint64()
+            _io_check(L.np2_map_index_seq(self._h, i, C.byref(name), C.byref(ln)))
+            self.names.append(name.value.decode()), self.lens.append(ln.value)
+
+    def close(self):
+        if self._h:
+            self._L.np2_map_index_free(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _opts(self, kw):
+        return map_opts(k=self.k, w=self.w, **kw)
+
+    def map(self, reads, chains=False, **kw):
+        """map_reads(self, ...)"""
+        return map_reads(self, reads, chains=chains, **kw)
+
+
+def map_reads(index, reads, chains=False, **kw):
+    """np2_map_bytes: reads (a separator stream or a list of sequences) against a MapIndex -> hits, a MAP_HIT_DTYPE array
+    with one entry per read (tid -1: unmapped); with chains=True -> (hits, chain, chain_off): the primary chains' anchors
+    (r, q) as a uint32 [m, 2] array and read i's rows chain_off[i] .. chain_off[i + 1].  Options: MAP_DEFAULTS."""
+    L = _bind()
+    s, n = _stream_of(reads)
+    o = index._opts(kw)
+    hits, chain, off = _map_result(L, lambda *a: L.np2_map_bytes(index._h, a[0], a[1], a[2], C.byref(o), a[3], a[4], a[5]), s, n, chains)
+    return (hits, chain, off) if chains else hits
+
+
+def map_files(index, paths, out_path, **kw):
+    """np2_map_files: read files -> the PAF file out_path (BGZF when it ends in .gz / .bgz) -> the stats dict"""
+    L = _bind()
+    arr, n = _paths(paths)
+    o, st = index._opts(kw), np2_map_stats_t()
+    _io_check(L.np2_map_files(index._h, arr, n, C.byref(o), None if out_path is None else os.fspath(out_path).encode(), C.byref(st)))
+    return _map_stats_dict(st)
+
+
+def map_host(asm, reads, chains=False, **kw):
+    """np2_map_host (no device): the same rule on the CPU -> what map_reads returns"""
+    L = _bind()
+    a, _ = _stream_of(asm)
+    s, n = _stream_of(reads)
+    o = map_opts(**kw)
+    hits, chain, off = _map_result(L, lambda *x: L.np2_map_host(a.ctypes.data if len(a) else None, len(a), x[0], x[1], x[2], C.byref(o), x[3],
+                                                                 x[4], x[5]), s, n, chains)
+    return (hits, chain, off) if chains else hits
