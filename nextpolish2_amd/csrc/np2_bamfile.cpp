@@ -1,6 +1,7 @@
 // The indexed BAM on the host: BGZF + BAI on zlib or libdeflate, the handle's entry points, the -S pass over the primaries' SEQ
 // and the record reader of the host pool.
 #include "np2_bamfile.hpp"
+#include "np2_bai_core.hpp"
 
 #include <zlib.h>
 #include <dlfcn.h>
@@ -76,7 +77,6 @@ struct Inflater {
         return (uint32_t)crc32(crc32(0L, Z_NULL, 0), d, (uInt)n);
     }
 };
-uint64_t le64(const uint8_t *p) { return (uint64_t)le32(p) | ((uint64_t)le32(p + 4) << 32); }
 
 } // namespace
 
@@ -256,14 +256,7 @@ void load_secondary_seqs(np2_bam *bam) {
 }
 } // namespace
 
-uint64_t zone_start_offset(const np2_bam *bam, int tid, uint32_t zone_lo) {
-    const std::vector<uint64_t> &lin = bam->lin[tid];
-    const uint64_t first = bam->ref_start[tid];
-    if (first == ~0ull || zone_lo == 0 || lin.empty()) return first;
-    size_t w = std::min<size_t>(zone_lo >> 14, lin.size() - 1);
-    while (w + 1 < lin.size() && lin[w] == 0) ++w;
-    return lin[w] != 0 ? lin[w] : first;
-}
+uint64_t zone_start_offset(const np2_bam *bam, int tid, uint32_t zone_lo) { return bai_zone_start(bam->lin[tid], bam->ref_start[tid], zone_lo); }
 
 void fetch_records(np2_bam *bam, int tid, uint32_t L, uint32_t zone_lo, uint32_t zone_hi, const np2_front_opts_t *opts,
                    std::vector<np2_bamrec_t> &recs, std::vector<uint32_t> &cigar, std::vector<uint64_t> *voffs,
@@ -477,34 +470,9 @@ int np2_bam_open(const char *path, np2_bam_t **out) {
         fseeko(fi.get(), 0, SEEK_SET);
         if (fread(idx.data(), 1, idx.size(), fi.get()) != idx.size()) throw np2h::Np2Error(NP2_E_ARG, "cannot read the .bai index");
         fi.reset();
-        if (idx.size() < 8 || memcmp(idx.data(), "BAI\1", 4) != 0) throw np2h::Np2Error(NP2_E_ARG, "bad .bai magic");
-        size_t p = 4;
-        const uint32_t n_ref_i = le32(idx.data() + p);
-        p += 4;
-        for (uint32_t r = 0; r < n_ref_i && r < n_ref; ++r) {
-            if (p + 4 > idx.size()) throw np2h::Np2Error(NP2_E_ARG, "truncated .bai");
-            const uint32_t n_bin = le32(idx.data() + p);
-            p += 4;
-            uint64_t best = ~0ull, last = 0;
-            for (uint32_t bi = 0; bi < n_bin; ++bi) {
-                const uint32_t bin = le32(idx.data() + p), n_chunk = le32(idx.data() + p + 4);
-                p += 8;
-                for (uint32_t ci = 0; ci < n_chunk; ++ci) {
-                    const uint64_t beg = le64(idx.data() + p), end = le64(idx.data() + p + 8);
-                    p += 16;
-                    if (bin != 37450 && beg < best) best = beg; // 37450 = metadata pseudo-bin
-                    if (bin != 37450 && end > last) last = end;
-                }
-            }
-            b->ref_end[r] = last;
-            const uint32_t n_intv = le32(idx.data() + p);
-            p += 4;
-            if (p + (size_t)n_intv * 8 > idx.size()) throw np2h::Np2Error(NP2_E_ARG, "truncated .bai");
-            b->lin[r].resize(n_intv);
-            for (uint32_t w = 0; w < n_intv; ++w) b->lin[r][w] = le64(idx.data() + p + (size_t)w * 8);
-            p += (size_t)n_intv * 8;
-            b->ref_start[r] = best;
-        }
+        np2h::BaiIndex bi;
+        if (const char *why = np2h::bai_parse(idx.data(), idx.size(), n_ref, bi)) throw np2h::Np2Error(NP2_E_ARG, why);
+        b->ref_start = std::move(bi.ref_start), b->ref_end = std::move(bi.ref_end), b->lin = std::move(bi.lin);
         *out = b.release();
         return NP2_OK;
     }, np2h::io_set_error);

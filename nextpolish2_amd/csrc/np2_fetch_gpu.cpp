@@ -409,8 +409,9 @@ FetchNext fetch_count_and_judge(FetchJob &j, const std::vector<uint64_t> &starts
         }
     }
     const uint32_t flags = tailw[1];
-    if (flags & np2::WALK_BAD) throw np2h::Np2Error(NP2_E_ARG, "BAM/SAM parsing failed!");
+    // (first: a chain that starts inside a record reads payload bytes as a length and reports a bad or cut-off record of its own)
     if (flags & np2::WALK_MISALIGNED) return FETCH_HOST;
+    if (flags & np2::WALK_BAD) throw np2h::Np2Error(NP2_E_ARG, "BAM/SAM parsing failed!");
     if ((flags & (np2::WALK_TAIL | np2::WALK_AT_END)) && !j.eof) { // the reference's records go on beyond the index's end: further
         if (!j.held_err.empty()) throw np2h::Np2Error(NP2_E_ARG, j.held_err); // (into the damaged block)
         j.extra = std::max<size_t>((size_t)1 << 20, j.extra * 2 + j.c_bytes / 4);

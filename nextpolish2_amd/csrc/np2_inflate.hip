@@ -410,18 +410,21 @@ __device__ __forceinline__ void bam_chain(const uint8_t *__restrict__ st, const 
     uint32_t n_rec = 0, n_cig = 0;
     uint32_t ro = 0, co = 0;
     if (WRITE) ro = chain_off[c].x, co = chain_off[c].y;
-    bool other = false;
+    bool other = false, hit_tail = false, hit_bad = false; // (what THIS chain met: the flags word is every chain's)
     while (p < stop) {
         if (p + 4 > end) { // (the length field itself is cut off)
+            hit_tail = true;
             if (!WRITE) atomicOr(flags, WALK_TAIL), atomicMin(tail_at, (unsigned long long)p);
             break;
         }
         const uint32_t bs = ld32(st + p);
         if (bs < 32) {
+            hit_bad = true;
             if (!WRITE) atomicOr(flags, WALK_BAD);
             break;
         }
         if (p + 4 + bs > end) { // the record continues beyond the inflated range: the host inflates further and walks again
+            hit_tail = true;
             if (!WRITE) atomicOr(flags, WALK_TAIL), atomicMin(tail_at, (unsigned long long)p);
             break;
         }
@@ -446,6 +449,7 @@ __device__ __forceinline__ void bam_chain(const uint8_t *__restrict__ st, const 
             continue;
         }
         if ((uint64_t)32 + l_name + (uint64_t)nc * 4 + ((uint64_t)l_seq + 1) / 2 > bs) {
+            hit_bad = true;
             if (!WRITE) atomicOr(flags, WALK_BAD);
             break;
         }
@@ -481,7 +485,9 @@ __device__ __forceinline__ void bam_chain(const uint8_t *__restrict__ st, const 
     if (!WRITE) {
         chain_info[c] = make_uint2(n_rec, n_cig);
         // a chain must end exactly where the next one begins (the index names record starts), unless the contig ended in it
-        if (!last && !other && p != stop && !(*flags & (WALK_TAIL | WALK_BAD))) atomicOr(flags, WALK_MISALIGNED);
+        // or it stopped at a record it could not read (a chain that STARTS inside a record stops so, and says nothing here:
+        // the chain before it does)
+        if (!last && !other && p != stop && !hit_tail && !hit_bad) atomicOr(flags, WALK_MISALIGNED);
         if (last && !other && p >= end) atomicOr(flags, WALK_AT_END); // ran into the end of the inflated range on a record boundary
         if (other && !last) atomicOr(flags, WALK_EARLY_END);          // (later chains then hold no record of the contig: fine)
     }
