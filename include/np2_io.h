@@ -452,10 +452,10 @@ int np2_rep_files(int device, const char *const *paths, int n_paths, const np2_r
  *     min(k, dr, dq) for each later one; block (column 11) is max(qe - qs, te - ts).  A PAF line is
  *     qname qlen qs qe +/- tname tlen ts te matches block mapq tp:A:P cm:i:n s1:i:s1 s2:i:s2, tab-separated, one per mapped
  *     read in read order; a name is the header up to the first whitespace (a record without one: its 1-based number).
- *   Not built: base-level alignment, CIGAR, SAM / BAM output; secondary and supplementary chains; winnowmap's -W weighting;
- *     -f occurrence fractions; homopolymer compression; several devices; an index beyond one device's memory.  NP2_E_UNSUPPORTED:
- *     an assembly of 2^32 bytes or more, a sequence or read longer than 2^31 - 1, a single read with more anchors than the
- *     device budget (2^25).
+ *   Not built: secondary and supplementary chains; winnowmap's -W weighting; -f occurrence fractions; homopolymer compression;
+ *     several devices; an index beyond one device's memory (base-level alignment and SAM: np2_map_align_*, below).
+ *     NP2_E_UNSUPPORTED: an assembly of 2^32 bytes or more, a sequence or read longer than 2^31 - 1, a single read with more
+ *     anchors than the device budget (2^25).
  * Every argument is checked before the first device call.  Errors: np2_io_last_error().  Test hooks, read once per call:
  * NP2_MAP_TEST_PIECE (bytes; a batch of reads goes up and is sketched in pieces of 8 MiB, eight pieces a batch, wherever the
  * boundary falls in a read) and NP2_MAP_TEST_BUDGET (anchors; a batch beyond it is chained in groups of whole reads). */
@@ -501,6 +501,80 @@ int np2_map_host(const uint8_t *asm_stream, uint64_t n_asm, const uint8_t *reads
                  np2_map_hit_t *hits, uint32_t **chain, uint64_t *chain_off);
 /* the counts and stage times of the last np2_map_bytes / np2_map_files / np2_map_host call on this thread */
 int np2_map_last_stats(np2_map_stats_t *stats);
+
+/* ---- the primary chain as a base-level alignment: chains to SAM (the recipe's `winnowmap -ax` / `minimap2 -a`, whose SAM the
+ * polisher reads) ----------------------------------------------------------------------------------------------------------------
+ * THE RULE IS DEFINED HERE, in the manner of minimap2's alignment between chained anchors with one affine piece (-A1 -B4 -O6
+ * -E2).  No minimap2 binary was at hand: equality with its CIGARs is not claimed and not tested.  The fine points (tie orders,
+ * the matrix' coordinates, the limits' reasons) stand beside the arithmetic in csrc/np2_align_core.hpp.
+ *   Options (np2_align_opts_t; defaults in brackets): match [1], mismatch [4], gap_open [6], gap_ext [2], band [32], end_bonus
+ *     [5], ext_max [2048], max_cells [2^23].  A gap of length g costs gap_open + g * gap_ext.  match 1 .. 15, mismatch <= 31,
+ *     gap_open <= 255, gap_ext 1 .. 15, band <= 1023, end_bonus <= 2^16, ext_max 1 .. 2^20, max_cells 1 .. 2^24; anything else
+ *     is NP2_E_ARG.
+ *   Bases.  Two bytes match if and only if both are ACGT in either case and the same base; N matches nothing.  A reverse-strand
+ *     read is aligned as its reverse complement; positions are on that strand, as the chain's q are.
+ *   Pins.  Walking the primary chain first to last, the first anchor is a pin; a later anchor is a pin if and only if its k-mer
+ *     starts at or after the previous pin's end in both r and q (r - k + 1 > r_prev and q - k + 1 > q_prev).  A pin is k match
+ *     columns.
+ *   Segments.  The bases between two consecutive pins, tl >= 0 of the reference and ql >= 0 of the read.  tl == ql and every
+ *     pair matching: all match columns ("equal").  Otherwise the longest matching common prefix, then the longest matching
+ *     common suffix of what remains, are match columns and what is left is the core: an empty side is one gap ("pure gap"), 1 x 1
+ *     is one mismatch ("snv"), anything else is a global affine alignment (Gotoh's H, E, F) inside the band of diagonals
+ *     min(0, d) - band .. max(0, d) + band, d = tl - ql of the core; the optimum inside the band is the answer.  Traceback
+ *     prefers the diagonal, then the deletion, then the insertion, and continues an open gap rather than opening another.
+ *     A core whose (ql + 1) * band width exceeds max_cells, or whose band is wider than 2048 diagonals, makes the read unaligned:
+ *     flag 4, counted in overflow.  (Defaults: max_gap 10000, bandwidth 500, band 32 give at most 10001 * 565 = 5.65 M cells.)
+ *   Ends.  The head (the read before the first pin, aligned backwards) and the tail (after the last pin) use the same
+ *     recurrence from the pin outwards with the reference end free, in the band -band .. +band.  n = min(remainder, ext_max,
+ *     reference left + band) read bases and min(reference left, n + band) reference bases are considered.  The extension ends
+ *     at the read-end cell (the best cell of the last row, the smallest column of equal ones; it exists only when n is the
+ *     whole remainder) when its score + end_bonus >= the best cell's score, otherwise at the best cell (the largest score; of
+ *     equal cells the smallest row, then the smallest column).  Everything beyond the chosen cell is soft-clipped.  An insertion
+ *     next to a clip becomes part of it, a deletion next to a clip is dropped.
+ *   CIGAR.  Words len << 4 | op with M = 0, I = 1, D = 2, S = 4 only; adjacent equal ops are merged.  Then every gap, left to
+ *     right, is left-aligned: it moves one column left while the column before it is a match column whose base equals the
+ *     gap's last base; it stops at a mismatch column, at another gap, or when one M column would be left at the start.  Pins do
+ *     not stop it.  Gaps of one kind that meet are merged and move on as one.
+ *   Record (np2_align_rec_t).  tid and mapq from the hit; pos the first M column's reference position (0-based), end one past
+ *     the last; flag 0, 16 or 4; NM = mismatches + gap bases; AS = the final columns' score under the options (pins and trimmed
+ *     matches count as matches).  An unmapped or overflowed read has tid -1, flag 4 and no CIGAR.
+ *   SAM.  @HD VN:1.6 SO:unsorted, one @SQ SN: LN: per sequence in index order, one @PG; then one line per read in read order:
+ *     qname flag rname pos+1 mapq CIGAR * 0 0 SEQ * NM:i: AS:i: cm:i: s1:i: s2:i: (SEQ reverse-complemented with flag 16: ACGT
+ *     in their case, any other byte kept), or qname 4 * 0 0 * * 0 0 SEQ * for an unmapped or overflowed read.  QUAL is always *.
+ *   Not built: the second affine piece (-O26 -E1); z-drop and supplementary records; = / X ops; MD; base qualities; direct BAM
+ *     output; handing the records to the polisher without SAM text.
+ * The index keeps the assembly's bytes on the device for this (one byte per assembly base more than the minimizers).  Traceback
+ * bits take one byte per matrix cell in a device buffer budgeted per group of whole reads (2^30 bytes; test hook
+ * NP2_ALIGN_TEST_BUDGET, bytes); NP2_ALIGN_TEST_CELLS lowers max_cells.  Both are read once per call.  np2_map_stats_t.groups
+ * counts these groups when aligning. */
+typedef struct np2_align_opts {
+    uint32_t match, mismatch, gap_open, gap_ext, band, end_bonus, ext_max, max_cells;
+} np2_align_opts_t;
+typedef struct np2_align_rec {
+    int32_t tid;                     /* -1: unmapped or overflowed (flag 4) */
+    uint32_t flag, pos, end, mapq, n_cigar, nm;
+    int32_t as;
+} np2_align_rec_t;
+typedef struct np2_align_stats {
+    uint64_t pins, segments, equal, pure_gap, snv, cores;
+    uint64_t cells;                  /* matrix cells within the limits, cores and end extensions */
+    uint64_t clipped_bases, overflow;
+    float pins_ms, classify_ms, dp_ms, assemble_ms; /* HIP events, summed over groups; 0 from np2_map_align_host */
+    float write_ms;                  /* np2_map_align_files: formatting and writing the SAM */
+} np2_align_stats_t;
+/* np2_map_bytes and the alignment: recs[n_reads]; with cigar and cigar_off (both or neither): cigar_off[n_reads + 1] (the
+ * caller's) and *cigar (np2_free), read i's words cigar_off[i] .. cigar_off[i + 1].  hits may be NULL. */
+int np2_map_align_bytes(const np2_map_index_t *ix, const uint8_t *reads, uint64_t n, uint64_t n_reads, const np2_map_opts_t *map_opts,
+                        const np2_align_opts_t *align_opts, np2_map_hit_t *hits, np2_align_rec_t *recs, uint32_t **cigar, uint64_t *cigar_off);
+/* read files -> the SAM file out_path (a path ending in .gz or .bgz: BGZF).  stats (the mapper's) may be NULL. */
+int np2_map_align_files(const np2_map_index_t *ix, const char *const *paths, int n_paths, const np2_map_opts_t *map_opts,
+                        const np2_align_opts_t *align_opts, const char *out_path, np2_map_stats_t *stats);
+/* host only, no device: the same rule from the same arithmetic (csrc/np2_align_core.hpp) */
+int np2_map_align_host(const uint8_t *asm_stream, uint64_t n_asm, const uint8_t *reads, uint64_t n, uint64_t n_reads,
+                       const np2_map_opts_t *map_opts, const np2_align_opts_t *align_opts, np2_map_hit_t *hits, np2_align_rec_t *recs,
+                       uint32_t **cigar, uint64_t *cigar_off);
+/* the alignment counts and stage times of the last np2_map_align_* call on this thread */
+int np2_map_align_last_stats(np2_align_stats_t *stats);
 
 /* ---- the mapper's SAM, parsed and coordinate-sorted on the device (the reference's recipe: `| samtools sort -o ... ;
  * samtools index ...`, which exist only so that an indexed reader can fetch one contig's records in coordinate order) -------

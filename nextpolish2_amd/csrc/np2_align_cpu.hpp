@@ -1,0 +1,158 @@
+// The aligner on the CPU, one read at a time, from the rule's arithmetic in np2_align_core.hpp: what np2_map_align_host runs and
+// what tests/tools/align_core_test.cpp builds with a plain C++ compiler; and the SAM text both the host and the device paths
+// write.  No HIP here.
+#pragma once
+#include <cstdio>
+#include <string>
+#include <vector>
+
+#include "np2_align_core.hpp"
+#include "np2_map_cpu.hpp"
+
+namespace np2aln {
+
+// one slot's matrix, row by row: tb gets its cells' bits (rows x W bytes); rem: the read bases beyond the slot's start
+inline Res dp_slot(const Seqs &s, const Slot &x, uint32_t rem, const Opts &o, uint8_t *tb, std::vector<int32_t> &H, std::vector<int32_t> &F) {
+    const uint32_t W = x.W;
+    H.assign((size_t)W + 1, NEG), F.assign((size_t)W + 1, NEG);
+    for (uint32_t L = 0; L < W; ++L) {
+        const int64_t j = (int64_t)x.lo + L;
+        const bool in = j >= 0 && j <= (int64_t)x.tl;
+        if (in) H[L] = row0_h((uint32_t)j, o);
+        tb[L] = in ? (uint8_t)row0_tb((uint32_t)j) : 0;
+    }
+    int32_t bh = 0, eh = NEG;
+    uint32_t bi = 0, bj = 0, ej = 0;
+    for (uint32_t i = 1; i <= x.ql; ++i) {
+        int32_t hl = NEG, el = NEG;
+        const uint32_t qb = slot_q(s, x, i - 1);
+        for (uint32_t L = 0; L < W; ++L) {
+            const int64_t j = (int64_t)i + x.lo + L;
+            int32_t h = NEG, e = NEG, f = NEG;
+            uint32_t bits = 0;
+            if (j >= 0 && j <= (int64_t)x.tl) {
+                uint32_t ce, cf, src;
+                const int32_t d = j > 0 ? H[L] + sub_score(slot_t(s, x, (uint32_t)j - 1), qb, o) : NEG;
+                e = gap_of(hl, el, o, &ce), f = gap_of(H[L + 1], F[L + 1], o, &cf);
+                h = h_of(d, e, f, &src);
+                bits = src | ce << 2 | cf << 3;
+                if (h > bh) bh = h, bi = i, bj = (uint32_t)j;
+                if (i == x.ql && h > eh) eh = h, ej = (uint32_t)j;
+            }
+            tb[(size_t)i * W + L] = (uint8_t)bits;
+            H[L] = h, F[L] = f, hl = h, el = e;
+        }
+    }
+    if (x.kind == K_CORE) return Res{H[(uint32_t)((int32_t)x.tl - (int32_t)x.ql - x.lo)], x.ql, x.tl};
+    return choose_end(bh, bi, bj, slot_has_end(x, rem), eh, ej, x.ql, o);
+}
+
+struct Scratch {
+    std::vector<uint8_t> pin, tb;
+    std::vector<Slot> slots;
+    std::vector<Res> res;
+    std::vector<uint64_t> tb_off;
+    std::vector<int32_t> H, F;
+    std::vector<uint32_t> a, b;
+};
+
+// One mapped read (hit.tid >= 0) with its chain of hit.n pairs against contig t of tlen bases -> the record, its CIGAR appended
+// to `cigar`, the counts added to c[C_N].  An overflowed read is unaligned_rec().
+inline Rec align_read(const uint8_t *t, uint32_t tlen, const uint8_t *q, const np2map::Hit &hit, const uint32_t *chain, uint32_t k, const Opts &o,
+                      uint32_t max_cells, Scratch &w, std::vector<uint32_t> &cigar, uint64_t *c) {
+    const Seqs s{t, tlen, q, hit.qlen, hit.rev};
+    w.pin.resize(hit.n);
+    const uint32_t np = mark_pins(chain, hit.n, k, w.pin.data()), ns = np + 1;
+    w.slots.resize(ns), w.res.assign(ns, Res{}), w.tb_off.assign((size_t)ns + 1, 0);
+    plan_read(chain, hit.n, k, w.pin.data(), tlen, hit.qlen, o, w.slots.data());
+    c[C_PINS] += np, c[C_SEGMENTS] += np - 1;
+    bool over = false;
+    for (uint32_t i = 0; i < ns; ++i) {
+        Slot &x = w.slots[i];
+        const uint64_t cells = classify(s, x, o, max_cells);
+        w.tb_off[i + 1] = w.tb_off[i] + cells;
+        over |= x.over != 0;
+        if (x.kind <= K_CORE) ++c[C_EQUAL + x.kind];
+        c[C_CELLS] += cells;
+    }
+    if (over) {
+        ++c[C_OVERFLOW];
+        return unaligned_rec();
+    }
+    w.tb.resize(w.tb_off[ns] + 1);
+    for (uint32_t i = 0; i < ns; ++i)
+        if (w.tb_off[i + 1] > w.tb_off[i]) {
+            const Slot &x = w.slots[i];
+            const uint32_t rem = x.kind == K_HEAD ? x.q0 : x.kind == K_TAIL ? hit.qlen - x.q0 : 0;
+            w.res[i] = dp_slot(s, x, rem, o, w.tb.data() + w.tb_off[i], w.H, w.F);
+        }
+    const ReadIn in{s, chain, w.pin.data(), hit.n, k, w.slots.data(), w.res.data(), w.tb_off.data(), w.tb.data(), 0, ns};
+    uint32_t t_start = 0;
+    const uint32_t n_raw = raw_ops(in, nullptr, &t_start);
+    w.a.resize((size_t)n_raw + 1), w.b.resize(2 * (size_t)n_raw + 2);
+    raw_ops(in, w.a.data(), &t_start);
+    Rec rec{};
+    rec.tid = hit.tid, rec.flag = hit.rev ? 16u : 0u, rec.mapq = hit.mapq;
+    c[C_CLIPPED] += finish_ops(s, w.a.data(), n_raw, t_start, o, w.b.data(), &rec);
+    score_ops(s, w.b.data(), rec.n_cigar, rec.pos, o, 0, 1, &rec.nm, &rec.as, &rec.end);
+    cigar.insert(cigar.end(), w.b.begin(), w.b.begin() + rec.n_cigar);
+    return rec;
+}
+
+// ---- SAM text ----------------------------------------------------------------------------------------------------------------
+inline void sam_header(std::string &out, const std::vector<std::string> &names, const std::vector<uint64_t> &lens) {
+    out += "@HD\tVN:1.6\tSO:unsorted\n";
+    for (size_t i = 0; i < names.size(); ++i) out += "@SQ\tSN:" + names[i] + "\tLN:" + std::to_string(lens[i]) + "\n";
+    out += "@PG\tID:nextpolish2_amd.map\tPN:nextpolish2_amd.map\n";
+}
+
+// SEQ: the read's bytes; with flag 16 reversed, ACGT complemented in their case, any other byte kept
+inline void sam_seq(std::string &out, const uint8_t *q, uint32_t n, bool rev) {
+    if (n == 0) {
+        out += '*';
+        return;
+    }
+    if (!rev) {
+        out.append((const char *)q, n);
+        return;
+    }
+    static const struct Comp { // ACGT complemented in their case; any other byte itself
+        char t[256];
+        Comp() {
+            for (int i = 0; i < 256; ++i) t[i] = (char)i;
+            const char *a = "ACGTacgt", *b = "TGCAtgca";
+            for (int i = 0; a[i]; ++i) t[(uint8_t)a[i]] = b[i];
+        }
+    } comp;
+    const size_t at = out.size();
+    out.resize(at + n);
+    char *w = &out[at];
+    for (uint32_t i = 0; i < n; ++i) w[i] = comp.t[q[n - 1u - i]];
+}
+
+inline void sam_line(std::string &out, const char *qname, size_t qname_n, const Rec &rec, const np2map::Hit &hit, const uint32_t *cigar,
+                     const uint8_t *q, uint32_t qlen, const std::string *tname) {
+    char num[160];
+    out.append(qname, qname_n);
+    if (rec.tid < 0) {
+        out += "\t4\t*\t0\t0\t*\t*\t0\t0\t";
+        sam_seq(out, q, qlen, false);
+        out += "\t*\n";
+        return;
+    }
+    int m = snprintf(num, sizeof num, "\t%u\t", rec.flag);
+    out.append(num, (size_t)m);
+    out += *tname;
+    m = snprintf(num, sizeof num, "\t%u\t%u\t", rec.pos + 1, rec.mapq);
+    out.append(num, (size_t)m);
+    for (uint32_t i = 0; i < rec.n_cigar; ++i) {
+        m = snprintf(num, sizeof num, "%u%c", cigar[i] >> 4, "MIDNS"[cigar[i] & 15u]);
+        out.append(num, (size_t)m);
+    }
+    out += "\t*\t0\t0\t";
+    sam_seq(out, q, qlen, (rec.flag & 16u) != 0);
+    m = snprintf(num, sizeof num, "\t*\tNM:i:%u\tAS:i:%d\tcm:i:%u\ts1:i:%u\ts2:i:%u\n", rec.nm, rec.as, hit.n, hit.s1, hit.s2);
+    out.append(num, (size_t)m);
+}
+
+} // namespace np2aln

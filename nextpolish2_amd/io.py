@@ -80,6 +80,22 @@ MAP_HIT_DTYPE = np.dtype([("tid", "<i4")] + [(f, "<u4") for f in ("qlen", "qs", 
 assert MAP_HIT_DTYPE.itemsize == 52
 
 
+class np2_align_opts_t(C.Structure):
+    _fields_ = [(f, C.c_uint32) for f in ("match", "mismatch", "gap_open", "gap_ext", "band", "end_bonus", "ext_max", "max_cells")]
+
+
+class np2_align_stats_t(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("pins", "segments", "equal", "pure_gap", "snv", "cores", "cells", "clipped_bases", "overflow")] + \
+               [(f, C.c_float) for f in ("pins_ms", "classify_ms", "dp_ms", "assemble_ms", "write_ms")]
+
+
+assert C.sizeof(np2_align_opts_t) == 32 and C.sizeof(np2_align_stats_t) == 96
+ALIGN_DEFAULTS = dict(match=1, mismatch=4, gap_open=6, gap_ext=2, band=32, end_bonus=5, ext_max=2048, max_cells=1 << 23)
+# np2_align_rec_t
+ALIGN_REC_DTYPE = np.dtype([("tid", "<i4")] + [(f, "<u4") for f in ("flag", "pos", "end", "mapq", "n_cigar", "nm")] + [("as", "<i4")])
+assert ALIGN_REC_DTYPE.itemsize == 32
+
+
 class FrontOpts:
     """Read-admission options with the reference defaults (src/utils/option.rs:267-292; -a 500.5 splits into
     min_map_len = 500 and min_map_fra = 0.5, option.rs:232,258-259)."""
@@ -328,6 +344,11 @@ def _bind_map(L):
     L.np2_map_files.argtypes = [vp, C.POINTER(C.c_char_p), C.c_int, mo, C.c_char_p, C.POINTER(np2_map_stats_t)]
     L.np2_map_host.argtypes = [vp, u64, vp, u64, u64, mo, vp, C.POINTER(vp), vp]
     L.np2_map_last_stats.argtypes = [C.POINTER(np2_map_stats_t)]
+    ao = C.POINTER(np2_align_opts_t)
+    L.np2_map_align_bytes.argtypes = [vp, vp, u64, u64, mo, ao, vp, vp, C.POINTER(vp), vp]
+    L.np2_map_align_files.argtypes = [vp, C.POINTER(C.c_char_p), C.c_int, mo, ao, C.c_char_p, C.POINTER(np2_map_stats_t)]
+    L.np2_map_align_host.argtypes = [vp, u64, vp, u64, u64, mo, ao, vp, vp, C.POINTER(vp), vp]
+    L.np2_map_align_last_stats.argtypes = [C.POINTER(np2_align_stats_t)]
 
 
 def _bind_shard(L):
@@ -1371,6 +1392,16 @@ class MapIndex:
         """map_reads(self, ...)"""
         return map_reads(self, reads, chains=chains, **kw)
 
+    def align(self, reads, **kw):
+        """np2_map_align_bytes: reads (a separator stream or a list of sequences) -> (hits, recs, cigar, cigar_off): recs an
+        ALIGN_REC_DTYPE array, read i's CIGAR words (len << 4 | op) cigar[cigar_off[i] : cigar_off[i + 1]].  Options: MAP_DEFAULTS
+        and ALIGN_DEFAULTS."""
+        L = self._L
+        s, n = _stream_of(reads)
+        akw = {f: kw.pop(f) for f in list(kw) if f in ALIGN_DEFAULTS}
+        o, ao = self._opts(kw), align_opts(**akw)
+        return _align_result(L, lambda *a: L.np2_map_align_bytes(self._h, a[0], a[1], a[2], C.byref(o), C.byref(ao), a[3], a[4], a[5], a[6]), s, n)
+
 
 def map_reads(index, reads, chains=False, **kw):
     """np2_map_bytes: reads (a separator stream or a list of sequences) against a MapIndex -> hits, a MAP_HIT_DTYPE array
@@ -1401,3 +1432,59 @@ def map_host(asm, reads, chains=False, **kw):
     hits, chain, off = _map_result(L, lambda *x: L.np2_map_host(a.ctypes.data if len(a) else None, len(a), x[0], x[1], x[2], C.byref(o), x[3],
                                                                  x[4], x[5]), s, n, chains)
     return (hits, chain, off) if chains else hits
+
+
+# ---- the aligner (include/np2_io.h: np2_map_align_*) --------------------------------------------------------------------------
+def align_opts(**kw):
+    """np2_align_opts_t from keyword options; what is not given takes its default (ALIGN_DEFAULTS)"""
+    unknown = set(kw) - set(ALIGN_DEFAULTS)
+    if unknown:
+        raise TypeError(f"unknown alignment option(s): {sorted(unknown)}")
+    vals = {**ALIGN_DEFAULTS, **{k: v for k, v in kw.items() if v is not None}}
+    for k, v in vals.items():
+        if not 0 <= int(v) <= 0xFFFFFFFF:
+            raise ValueError(f"{k}: 0 .. 2^32 - 1")
+    return np2_align_opts_t(*[int(vals[f]) for f, _ in np2_align_opts_t._fields_])
+
+
+def align_last_stats():
+    """alignment counts and stage times (HIP events, ms) of this thread's last np2_map_align_* call"""
+    st = np2_align_stats_t()
+    _io_check(_bind().np2_map_align_last_stats(C.byref(st)))
+    return {f: getattr(st, f) for f, _ in np2_align_stats_t._fields_}
+
+
+def _align_result(L, call, s, n):
+    hits, recs = np.zeros(n, MAP_HIT_DTYPE), np.zeros(n, ALIGN_REC_DTYPE)
+    pc, off = C.c_void_p(), np.zeros(n + 1, np.uint64)
+    _io_check(call(s.ctypes.data if len(s) else None, len(s), n, hits.ctypes.data if n else None, recs.ctypes.data if n else None, C.byref(pc),
+                   off.ctypes.data))
+    try:
+        m = int(off[n])
+        from .api import _Raw
+        cigar = np.asarray(_Raw(pc.value, m, "<u4")).copy() if m else np.zeros(0, np.uint32)
+    finally:
+        L.np2_free(pc)
+    return hits, recs, cigar, off
+
+
+def map_align_files(index, paths, out_path, **kw):
+    """np2_map_align_files: read files -> the SAM file out_path (BGZF when it ends in .gz / .bgz) -> the mapper's stats dict"""
+    L = _bind()
+    arr, n = _paths(paths)
+    akw = {f: kw.pop(f) for f in list(kw) if f in ALIGN_DEFAULTS}
+    o, ao, st = index._opts(kw), align_opts(**akw), np2_map_stats_t()
+    _io_check(L.np2_map_align_files(index._h, arr, n, C.byref(o), C.byref(ao), None if out_path is None else os.fspath(out_path).encode(),
+                                    C.byref(st)))
+    return _map_stats_dict(st)
+
+
+def map_align_host(asm, reads, **kw):
+    """np2_map_align_host (no device): the same rule on the CPU -> what MapIndex.align returns"""
+    L = _bind()
+    a, _ = _stream_of(asm)
+    s, n = _stream_of(reads)
+    akw = {f: kw.pop(f) for f in list(kw) if f in ALIGN_DEFAULTS}
+    o, ao = map_opts(**kw), align_opts(**akw)
+    return _align_result(L, lambda *x: L.np2_map_align_host(a.ctypes.data if len(a) else None, len(a), x[0], x[1], x[2], C.byref(o), C.byref(ao),
+                                                            x[3], x[4], x[5], x[6]), s, n)
