@@ -739,7 +739,7 @@ inline void recorder_sync(Recorder *r) {
 // The commands recorded so far are to be issued (with the rest of the batch group's), but the caller goes on with host
 // work that does not need their results: no wait for the device, nothing released.  Without a recorder the launches
 // went straight to the stream: nothing to do.
-np2_ctx *ctx_create_slot(np2_ctx *parent, hipStream_t s, uint32_t *mbox_host, uint32_t *mbox_dev); // (np2_host.cpp)
+np2_ctx *ctx_create_slot(np2_ctx *parent, hipStream_t s, uint32_t *mbox_host, uint32_t *mbox_dev); // (np2_ctx.cpp)
 void ctx_slot_set_stream(np2_ctx *cx, hipStream_t s);
 inline void op_submit(np2_ctx *cx) {
     (void)cx;

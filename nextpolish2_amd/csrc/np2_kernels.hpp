@@ -6,6 +6,7 @@
 #include "../../include/np2.h"
 #include "np2_lookback.hpp"
 #include "np2_launch.hpp"
+#include "np2_vote_band.hpp"
 
 namespace np2 {
 
@@ -329,8 +330,8 @@ void launch_vote_phase(hipStream_t s, const RegionTables &rt, bool asref, bool u
 void launch_vote_counts(hipStream_t s, const uint32_t *first_reg, const uint8_t *bad, uint32_t R, uint32_t *out);
 void launch_edges_write(hipStream_t s, const RegionTables &rt, const uint8_t *reg_lable, const uint8_t *grp,
                         const uint32_t *ecount, const uint32_t *eoff, uint64_t *ekey, uint32_t *eval);
-// banded pair accumulator (np2_regions.hip): EDGE_BAND partners per read, 256 = one uint4 per lane of a wavefront
-static constexpr uint32_t EDGE_BAND = 256;
+// banded pair accumulator (np2_regions.hip): EDGE_BAND partners per read (np2_vote_band.hpp)
+static_assert(EDGE_BAND == 4 * 64, "the band kernels move a read's row as one uint4 per lane of a wavefront");
 // pj / pcount: the region interval every read spans (candidate extraction); rows of reads without partners stay unwritten
 void launch_edges_row(hipStream_t s, const RegionTables &rt, const uint8_t *grp, const uint32_t *ecount, const uint32_t *pj,
                       const uint32_t *pcount, const uint8_t *alive, uint32_t R, uint32_t *band, uint32_t *row_n, uint32_t *ovf);

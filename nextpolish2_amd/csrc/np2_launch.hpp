@@ -127,7 +127,7 @@ struct Recorder {
         arena.clear();
     }
 };
-Recorder *&tl_recorder(); // this thread's recorder (nullptr = launches go straight to their stream); np2_host.cpp
+Recorder *&tl_recorder(); // this thread's recorder (nullptr = launches go straight to their stream); np2_ctx.cpp
 
 template <class S> struct Sig;
 template <class... A> struct Sig<void (*)(uint32_t, uint32_t, A...)> {

@@ -243,7 +243,7 @@ def _non_acgt(k=21):
 def _bucket(k=21):
     """tn <= bucket_cap: a mismatch files three records (its column and the two behind it), two adjacent ones four.  Tile 0 holds
     4 x 3 = 12 records, tile 1 3 x 3 + 4 = 13 (test_cand_cases_cpu.py counts them in the oracle's graph).  A contig with a
-    tile over its bucket takes the device-wide sort, which leaves no record index (run_diff, np2_host.cpp): under
+    tile over its bucket takes the device-wide sort, which leaves no record index (run_diff, np2_polish.cpp): under
     NP2_TILE_CAP = 13 both regions take the shortcut, under 12 tile 1 spills and neither does — the kernel's own test of
     tile_n restates that tile by tile.  The device test runs the caps 11 .. 14."""
     L = 2100

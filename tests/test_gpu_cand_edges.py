@@ -33,7 +33,7 @@ def guarded(what, fn, *a, **kw):
 
 
 def untraced(what, pu, yaks, opts, ref):
-    """Polisher.polish without set_trace (trace mode changes allocation and pass reuse in np2_host.cpp) against the oracle's answer"""
+    """Polisher.polish without set_trace (trace mode changes allocation and pass reuse in np2_polish.cpp) against the oracle's answer"""
     gb, gp = guarded(what, lambda: Polisher(yaks).polish(pu, opts))
     assert np.array_equal(gb, ref[1]) and np.array_equal(gp, ref[2]), what
 

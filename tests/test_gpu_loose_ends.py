@@ -304,7 +304,7 @@ def test_next_pass_started_before_the_vote_is_decided(monkeypatch, small_diploid
 
 @pytest.mark.parametrize("env", [dict(NP2_DENSE_PRECOUNT="1"), dict(NP2_TEST_DENSE_LB_FAIL="1")], ids=["precount", "after-a-wait-that-gave-up"])
 def test_dense_pass_with_its_chunk_counts_from_a_pre_pass(env):
-    """run_diff (csrc/np2_host.cpp): the chunks' column counts from launch_chunk_counts — for a process that shares its GPU
+    """run_diff (csrc/np2_polish.cpp): the chunks' column counts from launch_chunk_counts — for a process that shares its GPU
     (NP2_DENSE_PRECOUNT) and as the second attempt after a chunk's wait gave up (test hook: the first attempt is declared
     failed, so cursors, scalars and the status epoch must start over cleanly).  Same results as ever: random contig mixes
     through the batch driver and plain contexts against the oracle, in a process of its own (the switches are read once)."""
@@ -352,7 +352,7 @@ def test_dense_passes_of_two_streams_of_one_process_side_by_side():
 
 
 def test_candidate_strings_sized_by_a_read_back():
-    """extract_candidates (csrc/np2_host.cpp): a chromosome-sized contig sizes its candidate strings by the exact byte count
+    """extract_candidates (csrc/np2_polish.cpp): a chromosome-sized contig sizes its candidate strings by the exact byte count
     read back after the offsets scan instead of by the pileup's column count.  With the threshold lowered to nothing
     (NP2_CAND_EXACT_FROM, read once per process) random contig mixes through the batch driver and plain contexts are the
     oracle's as ever."""

@@ -326,7 +326,7 @@ def test_identical_pass_reuse_and_bases_only_output(small_haploid, small_diploid
 
 
 # (contig length asked of the generator, seed) -> a contig of exactly 2047, 2048 and 2049 tiles of 1024 positions: from
-# 2048 tiles on, k_tile_layout, and k_tile_offsets in both pass fronts, are the look-back kernels (np2_host.cpp: `wide`);
+# 2048 tiles on, k_tile_layout, and k_tile_offsets in both pass fronts, are the look-back kernels (np2_polish.cpp: `wide`);
 # 2049 tiles = 3 look-back blocks
 WIDE_SWITCH = {2047 * 1024: (2_096_106, 41), 2047 * 1024 + 1: (2_096_156, 42), 2048 * 1024 + 1: (2_097_140, 43)}
 
