@@ -542,7 +542,7 @@ int np2_map_last_stats(np2_map_stats_t *stats);
  *     qname flag rname pos+1 mapq CIGAR * 0 0 SEQ * NM:i: AS:i: cm:i: s1:i: s2:i: (SEQ reverse-complemented with flag 16: ACGT
  *     in their case, any other byte kept), or qname 4 * 0 0 * * 0 0 SEQ * for an unmapped or overflowed read.  QUAL is always *.
  *   Not built: the second affine piece (-O26 -E1); z-drop and supplementary records; = / X ops; MD; base qualities; direct BAM
- *     output; handing the records to the polisher without SAM text.
+ *     output.  (The records reach the polisher without SAM text through np2_sam_from_reads, below.)
  * The index keeps the assembly's bytes on the device for this (one byte per assembly base more than the minimizers).  Traceback
  * bits take one byte per matrix cell in a device buffer budgeted per group of whole reads (2^30 bytes; test hook
  * NP2_ALIGN_TEST_BUDGET, bytes); NP2_ALIGN_TEST_CELLS lowers max_cells.  Both are read once per call.  np2_map_stats_t.groups
@@ -645,6 +645,56 @@ int np2_sam_parse_bytes(int device, const uint8_t *text, uint64_t n, const np2_s
 /* the same four arrays of a resident SAM copied back to the host (parity tests of np2_sam_open; np2_sam_stats has the sizes) */
 int np2_sam_export(np2_ctx_t *ctx, np2_sam_t *sam, np2_bamrec_t **recs, int32_t **tids, uint32_t **cigar, uint8_t **seq4,
                    uint64_t *n_recs);
+
+/* ---- the resident SAM straight from reads: the aligner's records stay on the device (one process, no SAM text) --------------
+ * THE RULE IS ONE SENTENCE: the handle holds exactly what np2_sam_open (np2_sam_open_ex with NP2_SAM_KEEP_NAMES) would hold
+ * after reading the SAM that np2_map_align_files writes for the same index, files, mapper options and aligner options: recs
+ * (cigar_off in sorted order, seq_off in the order the reads were met), tids, cigar, seq4, with NP2_SAM_KEEP_NAMES names and
+ * name_ref, refs and the sorted keys, array for array.  What follows from it, written out (the arithmetic:
+ * csrc/np2_alnpack_core.hpp, which the kernels of csrc/np2_alnpack.hip and the host twin below both compile):
+ *   Kept reads: a read whose record has tid >= 0 and flag & 4 == 0.  Unmapped and overflowed reads are counted in
+ *     stats.unmapped and leave nothing behind.  stats.records is the number of reads, stats.lines that plus the header lines the
+ *     text would have (@HD, one @SQ per sequence, @PG).
+ *   Record words (np2_bamrec_t): pos, flag | mapq << 16, n_cigar, l_seq = the read's length; seq_off starts every record at a
+ *     byte; the pad words are zero.
+ *   Key: (tid, pos + 1, s) with s = (flag >> 4) & 1 under tie_by_strand and 0 without, as for the text; equal keys keep read
+ *     order, files in argument order.  The sort and the gather are the text door's own.
+ *   SEQ: the read's bytes as the SAM line prints them: with flag 16 reversed, ACGT complemented in their case and every other
+ *     byte kept as it is.  Each byte maps through BAM's "=ACMGRSVTWYHKDBN" in either case, any other byte to 15; two bases a
+ *     byte, high nibble first, the low nibble of an odd read's last byte 0.
+ *   Names (NP2_SAM_KEEP_NAMES): the bytes `map -a` prints as QNAME (the header line up to the first white space; np2_sam_from_
+ *     read_bytes: names, or the reads' numbers from 1).  A kept read whose name is empty or longer than 254 bytes is NP2_E_ARG,
+ *     "QNAME is empty or longer than 254 bytes", naming the read.
+ *   NP2_SAM_KEEP_ALL is NP2_E_UNSUPPORTED: the NM, AS, cm, s1 and s2 fields are not kept as binary tails.  The way round: write
+ *     the text (`map -a -o map.sam.gz`), then `samsort --full`.  -S, several ranks and inputs beyond one device's memory are out
+ *     of scope as for the SAM door.
+ *   Errors: option errors are those of np2_map_align_*, checked first; then a NULL argument, unknown flag bits, an index on
+ *     another device than the context, a sequence name the index holds twice (as a duplicate @SQ SN is in the text): NP2_E_ARG.
+ *     All are checked, and every file is opened once, before the first device call.
+ *   Memory: beside the index and the mapper's batch buffers, half a byte a base plus 40 bytes and the CIGAR words a record stay
+ *     resident, the records and words twice over while they are sorted; a shortfall is NP2_E_NOMEM and says how much was needed.
+ * The mapper works on a stream of its own; the pack kernels and the sort run on that stream too and the call returns once it
+ * is drained, so the handle is ready for any context of the device.  Nothing per read comes back to the host beside the
+ * mapper's hits: per sub-group of the aligner only the totals that size the arrays.  After a call np2_map_last_stats and
+ * np2_map_align_last_stats report it on the calling thread; in np2_sam_stats_t parse_ms is 0, pack_ms the HIP-event time of
+ * k_alnpack_sizes, its scans and k_alnpack, read_ms the wait for the read-file readers.  k_alnpack_sizes and its scans run
+ * between the events that bracket assemble_ms in np2_align_stats_t; their time is taken out of assemble_ms again, so that for
+ * this door assemble_ms is the ops' count, scan and emit as for np2_map_align_* (without their copies to the host) and pack_ms
+ * alone carries the pack kernels.
+ * Every reader of a handle works on this one unchanged: np2_contig_from_sam, np2_sam_export, np2_sam_stats, and with
+ * NP2_SAM_KEEP_NAMES np2_sam_write_bam, np2_sam_bam_stream (lean) and np2_sam_export_names. */
+int np2_sam_from_reads(np2_ctx_t *ctx, const np2_map_index_t *ix, const char *const *paths, int n_paths, const np2_map_opts_t *map_opts,
+                       const np2_align_opts_t *align_opts, const np2_sam_opts_t *sam_opts, uint32_t flags, np2_sam_t **out);
+/* reads in memory: the stream np2_map_align_bytes takes; names NULL (1, 2, ...) or '\n'-terminated */
+int np2_sam_from_read_bytes(np2_ctx_t *ctx, const np2_map_index_t *ix, const uint8_t *reads, uint64_t n, uint64_t n_reads,
+                            const char *names, const np2_map_opts_t *map_opts, const np2_align_opts_t *align_opts,
+                            const np2_sam_opts_t *sam_opts, uint32_t flags, np2_sam_t **out);
+/* host only, no device: aligner output (np2_map_align_bytes or np2_map_align_host: recs, cigar, cigar_off[n_reads + 1]) and the
+ * read stream -> the four arrays as np2_sam_export returns them, from the same rule text as the kernel.  sam_opts may be NULL.
+ * Release the four with np2_free; each is NULL when it would be empty. */
+int np2_align_pack_host(const np2_align_rec_t *recs, const uint32_t *cigar, const uint64_t *cigar_off, const uint8_t *reads, uint64_t n,
+                        uint64_t n_reads, const np2_sam_opts_t *sam_opts, np2_bamrec_t **out_recs, int32_t **tids, uint32_t **out_cigar,
+                        uint8_t **seq4, uint64_t *n_recs);
 
 /* ---- the sorted BAM and its .bai, written from a resident SAM (the reference's recipe: `samtools sort -o hifi.map.sort.bam -`
  * and `samtools index`) ---------------------------------------------------------------------------------------------------

@@ -51,7 +51,7 @@ IO_ABI_SYMBOLS = [
     "np2_map_files", "np2_map_host", "np2_map_last_stats",
     "np2_map_align_bytes", "np2_map_align_files", "np2_map_align_host", "np2_map_align_last_stats",
     "np2_sam_open", "np2_sam_close", "np2_sam_n_refs", "np2_sam_ref_name", "np2_sam_stats", "np2_contig_from_sam",
-    "np2_sam_parse_bytes", "np2_sam_export",
+    "np2_sam_parse_bytes", "np2_sam_export", "np2_sam_from_reads", "np2_sam_from_read_bytes", "np2_align_pack_host",
     "np2_sam_open_ex", "np2_sam_write_bam", "np2_sam_bam_stream", "np2_bamout_host", "np2_sam_export_names",
     "np2_sam_export_tails", "np2_sam_header_text", "np2_sam_tail_stats", "np2_bamout_host_full", "np2_sam_tails_host", "np2_sam_bamin_stats", "np2_bamin_host",
 ]

@@ -54,6 +54,16 @@ def build_parser():
                    help="HiFi-to-ref mapping file in sorted BAM format, or the mapper's SAM text, unsorted ([GZIP]; - is standard input)")
     p.add_argument("--sam_tie", choices=np2io.SAM_TIES, default="strand",
                    help="SAM input: records at one position are ordered by strand, as samtools sort orders them, or stay in input order [strand]")
+    p.add_argument("--from_reads", action="store_true",
+                   help="the first positional is the HiFi reads themselves ([GZIP] FASTA or FASTQ; not sniffed: give the flag): they are "
+                        "mapped and aligned against genome.fa on the GPU and the records stay there, no SAM text is written or read "
+                        "(what `python -m nextpolish2_amd.map -a` piped into this program computes, in one process; --sam_tie and "
+                        "--sorted_bam work, no -S, no --sorted_bam_full, single rank)")
+    p.add_argument("--more_reads", type=_existing, action="append", default=[], metavar="FILE",
+                   help="--from_reads: a further read file behind the first (repeatable)")
+    p.add_argument("--map_opts", type=np2io.map_opts_arg, default={}, metavar="KEY=VAL,...",
+                   help="--from_reads: mapper and aligner options, the keys of python -m nextpolish2_amd.map (" +
+                        " ".join(list(np2io.MAP_DEFAULTS) + list(np2io.ALIGN_DEFAULTS)) + ")")
     p.add_argument("fa", type=_existing, metavar="genome.fa[.gz]", help="genome assembly file in [GZIP] FASTA format")
     p.add_argument("yak", type=_existing, nargs="*", metavar="short.read.yak", help="one or more k-mer dataset in yak format")
     p.add_argument("--sr", type=_existing, action="append", default=[], metavar="FILE",
@@ -405,10 +415,26 @@ def main(argv=None):
         parser.error("--edits_min_count: 0 .. 1023")
     if a.model.lower() not in ("ref", "len"):
         raise SystemExit("error: invalid value for --model (ref|len)")
-    try:  # (a look at the file's first bytes; standard input cannot be looked at twice and is SAM text)
-        a.sam = a.bam == "-" or np2io.mapping_kind(a.bam) == "sam"
-    except (ValueError, OSError) as e:
-        raise SystemExit(f"Error: {e}")
+    if (a.more_reads or a.map_opts) and not a.from_reads:
+        parser.error("--more_reads and --map_opts go with --from_reads")
+    if a.from_reads:  # every refusal before any device work, one line each
+        if a.bam == "-":
+            raise SystemExit("Error: --from_reads takes read files, not standard input: its reader threads open each file themselves")
+        if a.bam_unsorted:
+            raise SystemExit("Error: --bam_unsorted says how a BAM is read; --from_reads gives reads, not a mapping")
+        if a.sorted_bam_full:
+            raise SystemExit("Error: --sorted_bam_full needs the SAM text (NM, AS, cm, s1, s2 are not kept with --from_reads): write it with "
+                             "python -m nextpolish2_amd.map -a -o map.sam.gz, then python -m nextpolish2_amd.samsort --full")
+        if a.use_secondary:
+            raise SystemExit("Error: -S needs secondary records, and the mapper behind --from_reads writes primary ones only")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1 and "RANK" in os.environ:
+            raise SystemExit("Error: --from_reads runs on one rank: interval sharding reads the .bai of a sorted BAM")
+        a.sam = True  # the handle is an ordinary resident SAM: every rule of SAM input below holds
+    else:
+        try:  # (a look at the file's first bytes; standard input cannot be looked at twice and is SAM text)
+            a.sam = a.bam == "-" or np2io.mapping_kind(a.bam) == "sam"
+        except (ValueError, OSError) as e:
+            raise SystemExit(f"Error: {e}")
     if a.bam_unsorted:
         if a.sam:
             raise SystemExit("Error: --bam_unsorted says how a BAM is read; the mapping given is SAM text")
@@ -522,7 +548,12 @@ def main(argv=None):
         t_s = time.time()
         spol = Polisher([], device=a.device)
         try:
-            sam = np2io.Sam(spol, [a.bam], tie=a.sam_tie, keep_names=a.sorted_bam is not None, keep_all=a.sorted_bam_full)
+            if a.from_reads:  # reads -> index -> mapped, aligned, packed and sorted where they lie; the index goes once that is done
+                mo = dict(a.map_opts)
+                with np2io.MapIndex(a.fa, k=mo.pop("k", np2io.MAP_DEFAULTS["k"]), w=mo.pop("w", np2io.MAP_DEFAULTS["w"]), device=a.device) as ix:
+                    sam = np2io.Sam.from_reads(spol, ix, [a.bam] + a.more_reads, tie=a.sam_tie, keep_names=a.sorted_bam is not None, **mo)
+            else:
+                sam = np2io.Sam(spol, [a.bam], tie=a.sam_tie, keep_names=a.sorted_bam is not None, keep_all=a.sorted_bam_full)
             if a.sorted_bam is not None:  # the mapping is kept from this one pass over a stream that cannot be read twice
                 st = sam.write_bam(spol, a.sorted_bam)
                 if prof:

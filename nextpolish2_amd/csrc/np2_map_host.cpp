@@ -21,11 +21,18 @@
 // worked off in sub-groups of whole reads.  Per sub-group: the DP kernel over its slots, the ops' count, a scan, the ops' emit;
 // records and CIGARs come back and are packed in read order.
 //
+// The resident SAM straight from reads (np2_sam_from_reads, np2_sam_from_read_bytes; the rule: np2_io.h; kernels:
+// np2_alnpack.hip).  The same batches, groups and sub-groups, but records and CIGARs do not come back: per sub-group the sizes of
+// what is kept are scanned behind the ops' emit, their totals ride with the wait that is there anyway, the host makes room in
+// the handle's input-order arrays (np2_sam_accum.hpp) and the pack kernel follows on the mapper's stream; after the last batch
+// the SAM door's own sort and gather run there too.
+//
 // np2_map_files feeds batches from the reader threads np2_bin_files uses (np2_pieces.hpp, np2_seqreader.hpp): their pieces
 // are cut at byte counts, the device thread joins them into batches at read boundaries and writes the PAF lines.
 #include "../../include/np2_io.h"
 #include "np2_align.hpp"
 #include "np2_align_cpu.hpp"
+#include "np2_alnpack.hpp"
 #include "np2_ctx.hpp"
 #include "np2_kcount.hpp"
 #include "np2_kernel_timer.hpp"
@@ -34,8 +41,10 @@
 #include "np2_map_core.hpp"
 #include "np2_map_cpu.hpp"
 #include "np2_pieces.hpp"
+#include "np2_sam_accum.hpp"
 #include "np2_seqreader.hpp"
 
+#include <algorithm>
 #include <chrono>
 
 namespace {
@@ -240,6 +249,108 @@ np2_map_index *build_index(int device, const uint8_t *stream, uint64_t n, std::v
     return ix.release();
 }
 
+// np2_sam_from_reads: a sub-group's records, CIGAR words and read bytes go from where k_align_ops_emit left them into the
+// input-order arrays of a resident SAM handle (np2_sam_accum.hpp), on the mapper's stream.  Only the totals come to the host.
+struct PackSink {
+    np2h::SamAccum acc;
+    uint32_t tie;
+    DevBuf<uint32_t> d_kept, d_ncig, d_nseq, d_nname, d_koff, d_coff, d_soff, d_nmoff, d_nbad, d_name_at;
+    DevBuf<uint8_t> d_names_in;
+    np2h::PinnedBuf pin_tot, pin_names;
+    DevEvent p0, p1, p2, p3;
+    np2::AlnPackJob job{};
+    bool pending = false;       // p2, p3 bracket a launch whose time has not been read
+    uint64_t reads_before = 0;  // reads of the batches before this one
+    uint32_t batch_reads = 0;
+    float pack_ms = 0.f;
+
+    PackSink(np2_sam &sam, hipStream_t st, bool keep_names, uint32_t tie_by_strand) : acc(sam, st), tie(tie_by_strand) {
+        acc.keep_names = keep_names;
+        d_kept.cached = d_ncig.cached = d_nseq.cached = d_nname.cached = d_koff.cached = d_coff.cached = d_soff.cached = true;
+        d_nmoff.cached = d_nbad.cached = d_name_at.cached = d_names_in.cached = true;
+        p0.make(), p1.make(), p2.make(), p3.make();
+    }
+    // k_alnpack is launched without a wait: when an error unwinds the call, it may still read the scans' outputs, the names and the
+    // mapper's buffers, which go back to the block cache right after this (the mapper is destroyed after its sink)
+    ~PackSink() { (void)hipStreamSynchronize(acc.st); }
+    // the batch's names ('\n' after each of its n_reads reads) go up once
+    void begin_batch(const char *names, size_t names_n, uint32_t n_reads) {
+        batch_reads = n_reads;
+        if (!acc.keep_names) return;
+        hipStream_t st = acc.st;
+        uint32_t *at = (uint32_t *)pin_names.ensure(((size_t)n_reads + 1) * 4 + names_n + 64);
+        uint8_t *bytes = (uint8_t *)(at + n_reads + 1);
+        size_t from = 0;
+        for (uint32_t i = 0; i < n_reads; ++i) {
+            const char *e = from < names_n ? (const char *)memchr(names + from, '\n', names_n - from) : nullptr;
+            if (!e) throw Np2Error(NP2_E_ARG, "np2_sam_from_reads: fewer names than reads");
+            at[i] = (uint32_t)from, from = (size_t)(e - names) + 1;
+        }
+        at[n_reads] = (uint32_t)from;
+        memcpy(bytes, names, from);
+        d_name_at.ensure((size_t)n_reads + 1), d_names_in.ensure(from + 1), d_nbad.ensure(1);
+        HIPCHK(hipMemcpyAsync(d_name_at.p, at, ((size_t)n_reads + 1) * 4, hipMemcpyHostToDevice, st));
+        if (from) HIPCHK(hipMemcpyAsync(d_names_in.p, bytes, from, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemsetAsync(d_nbad.p, 0xFF, 4, st));
+    }
+    void end_batch() { reads_before += batch_reads, acc.n_records += batch_reads; }
+
+    // after launch_align_ops_emit of reads [g0, g1): the sizes, their scans and the totals' copies.  `tmp` serves the scans.
+    void sizes(const np2::AlignJob &c, uint32_t g0, uint32_t g1, void *tmp, size_t tmp_bytes) {
+        hipStream_t st = acc.st;
+        const uint32_t ng = g1 - g0;
+        const size_t m = (size_t)ng + 1;
+        d_kept.ensure(m), d_ncig.ensure(m), d_nseq.ensure(m), d_koff.ensure(m), d_coff.ensure(m), d_soff.ensure(m);
+        if (acc.keep_names) d_nname.ensure(m), d_nmoff.ensure(m);
+        job = np2::AlnPackJob{c.recs, c.rd_seq, c.rd_ends, c.b, c.ooff, c.r0, g0, g1, acc.keep_names ? d_name_at.p : nullptr, d_names_in.p,
+                              d_kept.p, d_ncig.p, d_nseq.p, d_nname.p, d_koff.p, d_coff.p, d_soff.p, d_nmoff.p};
+        uint32_t *h = (uint32_t *)pin_tot.ensure(64);
+        h[3] = 0, h[4] = 0xFFFFFFFFu;
+        HIPCHK(hipEventRecord(p0.e, st));
+        np2::launch_alnpack_sizes(st, job, d_nbad.p);
+        if (np2::prim_exclusive_sum_u32(st, tmp, tmp_bytes, d_kept.p, d_koff.p, m) || np2::prim_exclusive_sum_u32(st, tmp, tmp_bytes, d_ncig.p, d_coff.p, m) ||
+            np2::prim_exclusive_sum_u32(st, tmp, tmp_bytes, d_nseq.p, d_soff.p, m) ||
+            (acc.keep_names && np2::prim_exclusive_sum_u32(st, tmp, tmp_bytes, d_nname.p, d_nmoff.p, m)))
+            throw Np2Error(NP2_E_DEVICE, "rocprim exclusive_scan failed");
+        HIPCHK(hipEventRecord(p1.e, st));
+        HIPCHK(hipMemcpyAsync(h + 0, d_koff.p + ng, 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(h + 1, d_coff.p + ng, 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(h + 2, d_soff.p + ng, 4, hipMemcpyDeviceToHost, st));
+        if (acc.keep_names) {
+            HIPCHK(hipMemcpyAsync(h + 3, d_nmoff.p + ng, 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(h + 4, d_nbad.p, 4, hipMemcpyDeviceToHost, st));
+        }
+    }
+    // ... and once the stream has been drained: room for the totals, then the pack kernel, which nobody waits for here.
+    // Returns the HIP-event time of sizes().
+    float pack() {
+        hipStream_t st = acc.st;
+        const float ms = elapsed(p0, p1);
+        pack_ms += ms;
+        const uint32_t *h = (const uint32_t *)pin_tot.p;
+        const uint64_t kept = h[0], n_cig = h[1], n_seq = h[2], n_name = h[3];
+        if (h[4] != 0xFFFFFFFFu)
+            throw Np2Error(NP2_E_ARG, "np2_sam_from_reads: read " + std::to_string(reads_before + h[4] + 1) + ": QNAME is empty or longer than 254 bytes");
+        if (kept > job.g1 - job.g0 || n_name > kept * 254u) throw Np2Error(NP2_E_DEVICE, "np2_sam_from_reads: record counters out of range");
+        acc.check_room(kept, n_cig);
+        if (kept) {
+            acc.reserve(kept, n_cig, n_seq, n_name, 0);
+            const np2::AlnPackOut o{acc.n_recs, acc.n_cigar, acc.seq_bytes, acc.name_bytes, tie, acc.recs_in.p, acc.tids_in.p, acc.keys_in.p,
+                                    acc.cigar_in.p, acc.sam.seq4.p, acc.sam.names.p, acc.nref_in.p};
+            HIPCHK(hipEventRecord(p2.e, st));
+            np2::launch_alnpack(st, job, o);
+            HIPCHK(hipEventRecord(p3.e, st));
+            pending = true;
+        }
+        acc.advance(kept, n_cig, n_seq, n_name, 0);
+        return ms;
+    }
+    void collect() { // (the stream has been drained since pack())
+        if (pending) pack_ms += elapsed(p2, p3);
+        pending = false;
+    }
+};
+
 // batches of reads against one index
 struct Mapper {
     const np2_map_index &ix;
@@ -270,6 +381,7 @@ struct Mapper {
     std::vector<uint64_t> h_rcells;
     std::vector<uint32_t> h_soff, h_ooff, h_b;
     std::vector<np2aln::Rec> h_recs;
+    PackSink *pk = nullptr; // np2_sam_from_reads: records and CIGAR words stay on the device (recs and cigar are null then)
 
     void align_with(const np2aln::Opts &a) {
         ao_v = a, ao = &ao_v;
@@ -358,7 +470,7 @@ struct Mapper {
         launch_map_chain(st, c);
         HIPCHK(hipMemcpyAsync(hits + r0, d_hits.p + r0, (size_t)n_reads * sizeof(Hit), hipMemcpyDeviceToHost, st));
         stats.chain_ms += s.end();
-        if (ao)
+        if (ao && recs)
             for (uint32_t i = r0; i < r1; ++i) recs[i] = np2aln::unaligned_rec();
         if (!chain && !ao) return;
         h_coff.resize(n_reads);
@@ -425,6 +537,7 @@ struct Mapper {
             s.begin();
             launch_align_dp(st, c, h_soff[g0], h_soff[g1], tb_base);
             astats.dp_ms += s.end();
+            if (pk) pk->collect();
             const uint32_t ng = g1 - g0;
             s.begin();
             launch_align_ops_count(st, c, g0, g1, tb_base);
@@ -435,6 +548,15 @@ struct Mapper {
             const size_t n_ops = h_ooff[ng], n_b = 2 * n_ops + 2 * (size_t)ng;
             d_a.ensure(n_ops + 1), d_b.ensure(n_b + 1);
             c.a = d_a.p, c.b = d_b.p;
+            if (pk) { // the sub-group's records go on into the handle: the sizes now, the pack behind the one wait there is
+                s.begin();
+                launch_align_ops_emit(st, c, g0, g1, tb_base);
+                pk->sizes(c, g0, g1, s.tmp.p, scan_tmp);
+                astats.assemble_ms += s.end();
+                astats.assemble_ms -= pk->pack();
+                g0 = g1;
+                continue;
+            }
             h_b.resize(n_b + 1);
             s.begin();
             launch_align_ops_emit(st, c, g0, g1, tb_base);
@@ -453,6 +575,7 @@ struct Mapper {
         unsigned long long ctr[np2aln::C_N];
         HIPCHK(hipMemcpyAsync(ctr, d_actr.p, sizeof ctr, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
+        if (pk) pk->collect();
         add_counts(astats, ctr);
     }
 };
@@ -564,6 +687,60 @@ void write_sam(np2h::OutFile &out, const np2_map_index &ix, const BatchBuf &b, c
     out.put(text.data(), text.size());
 }
 
+// the read files of a call, each opened once before the first device call
+std::vector<std::string> checked_files(const char *const *paths, int n_paths, const std::string &who) {
+    if (!paths || n_paths < 1) throw Np2Error(NP2_E_ARG, who + ": no read file given");
+    std::vector<std::string> files;
+    for (int i = 0; i < n_paths; ++i) {
+        if (!paths[i]) throw Np2Error(NP2_E_ARG, who + ": a read file path is NULL");
+        FILE *f = fopen(paths[i], "rb");
+        if (!f) throw Np2Error(NP2_E_ARG, who + ": cannot open " + paths[i]);
+        fclose(f);
+        files.push_back(paths[i]);
+    }
+    return files;
+}
+
+// The files' reads in file order as batches of whole reads, hooks.batch_bytes() at the most (a file's last batch may be
+// smaller): flush(b) works a batch off, its closed reads are dropped afterwards.  Reader threads parse ahead.
+template <class Flush> void read_batches(const std::vector<std::string> &files, const Hooks &hooks, const std::string &who, Flush &&flush) {
+    const size_t cap = hooks.piece;
+    const size_t n_threads = std::min<size_t>(files.size(), 16);
+    std::vector<MapQueue> queues(n_threads);
+    std::vector<MapPiece> pieces(2 * n_threads);
+    np2h::PinnedBlocks pinned;
+    for (size_t i = 0; i < pieces.size(); ++i) {
+        pieces[i].buf = pinned.get(np2h::HALO + cap + 64);
+        queues[i / 2].idle.push_back(&pieces[i]);
+    }
+    auto readers = np2h::run_readers(n_threads, queues, [&](size_t ti) {
+        for (size_t fi = ti; fi < files.size(); fi += n_threads) {
+            MapWriter w(queues[ti], cap);
+            np2seq::parse_file(files[fi], [&](const uint8_t *p, size_t n) { w.put(p, n); }, [&] { return w.w.dead; },
+                               [&](const uint8_t *p, size_t n, bool begin) { w.names(p, n, begin); });
+            w.finish();
+            if (w.w.dead) break;
+        }
+    });
+    BatchBuf b;
+    for (size_t fi = 0; fi < files.size(); ++fi) {
+        MapQueue &q = queues[fi % n_threads];
+        for (bool last = false; !last;) {
+            const auto t0 = std::chrono::steady_clock::now();
+            MapPiece *p = q.take_full();
+            tl_stats.read_ms += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            if (!p) throw Np2Error(q.err_code != NP2_OK ? q.err_code : NP2_E_ARG, q.err_code != NP2_OK ? q.err : who + ": a reader stopped early");
+            last = p->last;
+            b.add(*p);
+            q.give_idle(p);
+            if ((b.closed() >= hooks.batch_bytes() || last) && !b.ends.empty()) { // (a file's last read ends with its separator)
+                flush(b);
+                b.drop_closed();
+            }
+        }
+    }
+}
+
 // np2_map_files (aopts null: PAF) and np2_map_align_files (SAM)
 int map_files_impl(const np2_map_index_t *ix, const char *const *paths, int n_paths, const np2_map_opts_t *opts, const np2_align_opts_t *aopts,
                    bool align, const char *out_path, np2_map_stats_t *stats, const std::string who) {
@@ -574,37 +751,11 @@ int map_files_impl(const np2_map_index_t *ix, const char *const *paths, int n_pa
         check_index_opts(ix, o, who.c_str());
         if (!paths || n_paths < 1) throw Np2Error(NP2_E_ARG, who + ": no read file given");
         if (!out_path) throw Np2Error(NP2_E_ARG, who + ": out_path is NULL");
-        std::vector<std::string> files;
-        for (int i = 0; i < n_paths; ++i) {
-            if (!paths[i]) throw Np2Error(NP2_E_ARG, who + ": a read file path is NULL");
-            FILE *f = fopen(paths[i], "rb");
-            if (!f) throw Np2Error(NP2_E_ARG, who + ": cannot open " + paths[i]);
-            fclose(f);
-            files.push_back(paths[i]);
-        }
+        const std::vector<std::string> files = checked_files(paths, n_paths, who);
         Mapper m(*ix, o);
         if (align) m.align_with(ao);
         np2h::OutFile out;
         out.open(out_path, ix->device);
-        const size_t cap = m.hooks.piece;
-        const size_t n_threads = std::min<size_t>(files.size(), 16);
-        std::vector<MapQueue> queues(n_threads);
-        std::vector<MapPiece> pieces(2 * n_threads);
-        np2h::PinnedBlocks pinned;
-        for (size_t i = 0; i < pieces.size(); ++i) {
-            pieces[i].buf = pinned.get(np2h::HALO + cap + 64);
-            queues[i / 2].idle.push_back(&pieces[i]);
-        }
-        auto readers = np2h::run_readers(n_threads, queues, [&](size_t ti) {
-            for (size_t fi = ti; fi < files.size(); fi += n_threads) {
-                MapWriter w(queues[ti], cap);
-                np2seq::parse_file(files[fi], [&](const uint8_t *p, size_t n) { w.put(p, n); }, [&] { return w.w.dead; },
-                                   [&](const uint8_t *p, size_t n, bool begin) { w.names(p, n, begin); });
-                w.finish();
-                if (w.w.dead) break;
-            }
-        });
-        BatchBuf b;
         std::vector<Hit> hits;
         std::string text;
         std::vector<np2aln::Rec> recs;
@@ -613,8 +764,7 @@ int map_files_impl(const np2_map_index_t *ix, const char *const *paths, int n_pa
             np2aln::sam_header(text, ix->names, ix->lens);
             out.put(text.data(), text.size());
         }
-        auto flush = [&] {
-            if (b.ends.empty()) return;
+        read_batches(files, m.hooks, who, [&](const BatchBuf &b) {
             hits.resize(b.ends.size());
             if (align) recs.resize(b.ends.size()), cigar.clear();
             m.batch(b.bytes.data(), b.closed(), b.ends.data(), (uint32_t)b.ends.size(), hits.data(), nullptr, align ? recs.data() : nullptr,
@@ -625,25 +775,72 @@ int map_files_impl(const np2_map_index_t *ix, const char *const *paths, int n_pa
             const float ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
             tl_stats.write_ms += ms;
             if (align) tl_astats.write_ms += ms;
-            b.drop_closed();
-        };
-        for (size_t fi = 0; fi < files.size(); ++fi) {
-            MapQueue &q = queues[fi % n_threads];
-            for (bool last = false; !last;) {
-                const auto t0 = std::chrono::steady_clock::now();
-                MapPiece *p = q.take_full();
-                tl_stats.read_ms += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-                if (!p) throw Np2Error(q.err_code != NP2_OK ? q.err_code : NP2_E_ARG, q.err_code != NP2_OK ? q.err : who + ": a reader stopped early");
-                last = p->last;
-                b.add(*p);
-                q.give_idle(p);
-                if (b.closed() >= m.hooks.batch_bytes() || last) flush(); // (a file's last read ends with its separator)
-            }
-        }
+        });
         out.close();
         fill_stats(stats);
         return NP2_OK;
     }, np2h::io_set_error);
+}
+
+// ---- np2_sam_from_reads, np2_sam_from_read_bytes: the aligner's records into a resident SAM handle -----------------------------
+// What both check before the first device call, in this order: the options as np2_map_align_* do, then the rest.
+struct FromReads {
+    np2map::Opts o;
+    np2aln::Opts ao;
+    uint32_t tie;
+    bool keep_names;
+    FromReads(np2_ctx *cx, const np2_map_index_t *ix, const np2_map_opts_t *map_opts, const np2_align_opts_t *align_opts, const np2_sam_opts_t *sam_opts,
+              uint32_t flags, np2_sam_t **out, const char *who) {
+        o = checked(map_opts, who);
+        ao = checked_align(align_opts, who);
+        check_index_opts(ix, o, who);
+        if (!cx || !out) throw Np2Error(NP2_E_ARG, std::string(who) + ": NULL argument");
+        if (flags & ~(uint32_t)(NP2_SAM_KEEP_NAMES | NP2_SAM_KEEP_ALL)) throw Np2Error(NP2_E_ARG, std::string(who) + ": unknown flag bits");
+        if (flags & NP2_SAM_KEEP_ALL)
+            throw Np2Error(NP2_E_UNSUPPORTED, std::string(who) + ": NP2_SAM_KEEP_ALL needs the SAM text (its NM, AS, cm, s1 and s2 fields are not kept "
+                                              "as binary tails here): write it with `map -a -o map.sam.gz`, then `samsort --full`");
+        if (ix->device != cx->device) throw Np2Error(NP2_E_ARG, std::string(who) + ": the index is on another device than the context");
+        std::vector<std::string> sorted_names(ix->names);
+        std::sort(sorted_names.begin(), sorted_names.end());
+        const auto twice = std::adjacent_find(sorted_names.begin(), sorted_names.end());
+        if (twice != sorted_names.end()) throw Np2Error(NP2_E_ARG, std::string(who) + ": the @SQ name " + *twice + " is given twice");
+        tie = sam_opts ? (sam_opts->tie_by_strand ? 1u : 0u) : 1u;
+        keep_names = (flags & NP2_SAM_KEEP_NAMES) != 0;
+    }
+};
+
+// the mapper, the sink and the handle of one call; batches go in through batch(), finish() sorts and hands the handle over
+struct FromReadsRun {
+    std::unique_ptr<np2_sam> sam;
+    Mapper m;
+    PackSink pk;
+    std::vector<Hit> hits;
+    FromReadsRun(np2_ctx *cx, const np2_map_index_t *ix, const FromReads &a) : sam(new np2_sam()), m(*ix, a.o), pk(*sam, m.s.st, a.keep_names, a.tie) {
+        sam->device = cx->device;
+        for (size_t i = 0; i < ix->names.size(); ++i) sam->refs.names.push_back(ix->names[i]), sam->refs.lens.push_back((uint32_t)ix->lens[i]);
+        m.align_with(a.ao);
+        m.pk = &pk;
+    }
+    void batch(const uint8_t *bytes, uint64_t n, const uint32_t *ends, uint32_t n_reads, const char *names, size_t names_n) {
+        hits.resize(n_reads);
+        pk.begin_batch(names, names_n, n_reads);
+        m.batch(bytes, n, ends, n_reads, hits.data(), nullptr, nullptr, nullptr);
+        pk.end_batch();
+    }
+    np2_sam_t *finish() {
+        pk.acc.finish();
+        np2_sam_stats_t &st = sam->stats;
+        st.lines = st.records + sam->refs.names.size() + 2; // (as the text would have: @HD, the @SQ lines, @PG, a line a read)
+        st.parse_ms = 0.f, st.pack_ms = pk.pack_ms, st.read_ms = tl_stats.read_ms;
+        return sam.release();
+    }
+};
+
+template <class Body> int from_reads_guard(np2_ctx *cx, bool &touched, Body &&body) {
+    return np2h::abi_guard(body, [&](int code, const std::string &msg) {
+        if (touched) cx->err = msg; // (the call's own stream was drained when its PackSink went: the context's was never used)
+        np2h::io_set_error(code, msg);
+    });
 }
 
 } // namespace
@@ -883,6 +1080,72 @@ int np2_map_align_host(const uint8_t *asm_stream, uint64_t n_asm, const uint8_t 
         }
         return NP2_OK;
     }, np2h::io_set_error);
+}
+
+int np2_sam_from_reads(np2_ctx_t *cx, const np2_map_index_t *ix, const char *const *paths, int n_paths, const np2_map_opts_t *map_opts,
+                       const np2_align_opts_t *align_opts, const np2_sam_opts_t *sam_opts, uint32_t flags, np2_sam_t **out) {
+    if (out) *out = nullptr;
+    bool touched = false;
+    return from_reads_guard(cx, touched, [&] {
+        const char *who = "np2_sam_from_reads";
+        const FromReads a(cx, ix, map_opts, align_opts, sam_opts, flags, out, who);
+        const std::vector<std::string> files = checked_files(paths, n_paths, who);
+        touched = true;
+        FromReadsRun run(cx, ix, a);
+        read_batches(files, run.m.hooks, who, [&](const BatchBuf &b) {
+            run.batch(b.bytes.data(), b.closed(), b.ends.data(), (uint32_t)b.ends.size(), b.names.data(), b.names.size());
+        });
+        *out = run.finish();
+        return NP2_OK;
+    });
+}
+
+int np2_sam_from_read_bytes(np2_ctx_t *cx, const np2_map_index_t *ix, const uint8_t *reads, uint64_t n, uint64_t n_reads, const char *names,
+                            const np2_map_opts_t *map_opts, const np2_align_opts_t *align_opts, const np2_sam_opts_t *sam_opts, uint32_t flags,
+                            np2_sam_t **out) {
+    if (out) *out = nullptr;
+    bool touched = false;
+    return from_reads_guard(cx, touched, [&] {
+        const char *who = "np2_sam_from_read_bytes";
+        const FromReads a(cx, ix, map_opts, align_opts, sam_opts, flags, out, who);
+        const std::vector<uint64_t> ends = ends_of(reads, n, who, "the read stream");
+        if (ends.size() != n_reads)
+            throw Np2Error(NP2_E_ARG, std::string(who) + ": n_reads is " + std::to_string(n_reads) + ", the stream holds " + std::to_string(ends.size()) + " newlines");
+        std::vector<size_t> name_at; // where each read's name begins, and the end of the last
+        if (names && a.keep_names) {
+            const char *p = names;
+            for (uint64_t i = 0; i < n_reads; ++i) {
+                const char *e = strchr(p, '\n');
+                if (!e) throw Np2Error(NP2_E_ARG, std::string(who) + ": names holds fewer than n_reads newline-terminated names");
+                name_at.push_back((size_t)(p - names)), p = e + 1;
+            }
+            name_at.push_back((size_t)(p - names));
+        }
+        touched = true;
+        FromReadsRun run(cx, ix, a);
+        std::vector<uint32_t> local;
+        std::string numbered;
+        for (uint64_t r0 = 0; r0 < n_reads;) { // batches: whole reads, batch_bytes() at the most, one read at the least
+            const uint64_t from = r0 ? ends[r0 - 1] + 1 : 0;
+            uint64_t r1 = r0 + 1;
+            while (r1 < n_reads && ends[r1] + 1 - from <= run.m.hooks.batch_bytes()) ++r1;
+            local.clear();
+            for (uint64_t i = r0; i < r1; ++i) local.push_back((uint32_t)(ends[i] - from));
+            const char *nm = nullptr;
+            size_t nm_n = 0;
+            if (a.keep_names && names) {
+                nm = names + name_at[r0], nm_n = name_at[r1] - name_at[r0];
+            } else if (a.keep_names) { // numbered from 1
+                numbered.clear();
+                for (uint64_t i = r0; i < r1; ++i) numbered += std::to_string(i + 1) + "\n";
+                nm = numbered.data(), nm_n = numbered.size();
+            }
+            run.batch(reads + from, ends[r1 - 1] + 1 - from, local.data(), (uint32_t)(r1 - r0), nm, nm_n);
+            r0 = r1;
+        }
+        *out = run.finish();
+        return NP2_OK;
+    });
 }
 
 int np2_map_align_last_stats(np2_align_stats_t *stats) {

@@ -20,6 +20,7 @@
 #include "np2_kcount.hpp"
 #include "np2_kernel_timer.hpp"
 #include "np2_sam.hpp"
+#include "np2_sam_accum.hpp"
 #include "np2_sam_handle.hpp"
 
 #include <fcntl.h>
@@ -338,55 +339,18 @@ struct Reader {
 
 using np2h::elapsed;
 
-// room for `bytes` more on the device, or NP2_E_NOMEM saying how much was needed
-void need_device(size_t bytes, const char *what) {
-    np2h::need_device_bytes(bytes, (size_t)64 << 20, [&](size_t fr) {
-        return std::string("the SAM's ") + what + " need a block of " + std::to_string(bytes) + " bytes, and the device has " +
-               std::to_string(fr) + " bytes free: the packed SEQ, the CIGAR words and the records of a SAM input must fit one device's memory";
-    });
-}
-template <class T> void take_over(DevBuf<T> &a, DevBuf<T> &b) { // a <- b's block, b <- a's
-    std::swap(a.p, b.p), std::swap(a.cap, b.cap), std::swap(a.cached, b.cached), std::swap(a.cache_bytes, b.cache_bytes),
-        std::swap(a.slab_bytes, b.slab_bytes);
-}
-// `b` holds `used` elements and gets room for `need`: a larger block and a device-to-device copy, as SeqStream::push grows
-template <class T> void grow(DevBuf<T> &b, size_t used, size_t need, hipStream_t st, const char *what) {
-    if (need <= b.cap) return;
-    const size_t want = std::max(need, b.cap + b.cap / 2);
-    need_device((want + want / 8 + 64) * sizeof(T), what);
-    DevBuf<T> nb;
-    nb.cached = true;
-    nb.ensure(want);
-    if (used) HIPCHK(hipMemcpyAsync(nb.p, b.p, used * sizeof(T), hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipStreamSynchronize(st)); // (the old block goes back to the cache: nothing may still read it)
-    take_over(b, nb);
-}
-
 // text -> the handle's resident arrays
-struct Build {
+struct Build : np2h::SamAccum { // (the input-order arrays, their growth and finish(): np2_sam_accum.hpp)
     np2_ctx *cx;
-    np2_sam &sam;
     Hooks hooks;
     uint32_t tie = 1;
-    hipStream_t st;
-    // input order, while the pieces come in
-    DevBuf<uint32_t> recs_in, cigar_in;
-    DevBuf<int32_t> tids_in;
-    DevBuf<uint64_t> keys_in;
-    uint64_t n_recs = 0, n_cigar = 0, seq_bytes = 0, n_records = 0;
-    // NP2_SAM_KEEP_NAMES: offset << 8 | length of each record's name, input order; the lengths of a piece, their scan, the first bad line
-    bool keep_names = false;
-    DevBuf<uint64_t> nref_in;
+    // NP2_SAM_KEEP_NAMES: the lengths of a piece's names, their scan, the first bad line
     DevBuf<uint32_t> d_nname, d_nmoff, d_nbad;
-    uint64_t name_bytes = 0;
-    // NP2_SAM_KEEP_ALL: offset << 1 | has_qual of each record's tail, input order; the sizes of a piece's tails and their scan
-    bool keep_all = false;
-    DevBuf<uint64_t> tref_in;
+    // NP2_SAM_KEEP_ALL: the sizes of a piece's tails and their scan
     DevBuf<uint32_t> d_tsize, d_taux, d_toff;
-    uint64_t tail_bytes = 0;
     np2h::DevEvent e_t0, e_t1;
     // one piece
-    DevBuf<uint8_t> d_text, d_tmp;
+    DevBuf<uint8_t> d_text;
     DevBuf<uint32_t> d_end, d_kept, d_ncig, d_nseq, d_koff, d_coff, d_soff;
     DevBuf<np2sam::Line> d_lines;
     DevBuf<np2::SamCtr> d_ctr;
@@ -396,7 +360,7 @@ struct Build {
     np2sam::NameTab nt{};
     bool have_nt = false;
     np2h::PinnedBuf pin;
-    np2h::DevEvent e0, e1, e_mid;
+    np2h::DevEvent e_mid;
     float lines_ms = 0;    // k_sam_lines alone, of parse_ms
     // a BAM's pieces: the file bytes, the block table with the CRC32 words behind it, the blocks' status words and the count of
     // failed ones, the inflated stream of this piece and of the one before (whose unfinished record is copied over), the walk
@@ -412,14 +376,13 @@ struct Build {
     uint64_t file_recs = 0;  // records of that file before this piece
     uint64_t text_bytes = 0;
 
-    Build(np2_ctx *c, np2_sam &s) : cx(c), sam(s), st(c->stream) {
-        recs_in.cached = cigar_in.cached = tids_in.cached = keys_in.cached = true; // (every release below follows a drained stream)
-        d_text.cached = d_tmp.cached = d_end.cached = d_kept.cached = d_ncig.cached = d_nseq.cached = d_koff.cached = d_coff.cached = true;
+    Build(np2_ctx *c, np2_sam &s) : np2h::SamAccum(s, c->stream), cx(c) {
+        d_text.cached = d_end.cached = d_kept.cached = d_ncig.cached = d_nseq.cached = d_koff.cached = d_coff.cached = true;
         d_soff.cached = d_lines.cached = d_ctr.cached = d_slot.cached = d_noff.cached = d_names.cached = true;
-        nref_in.cached = d_nname.cached = d_nmoff.cached = d_nbad.cached = true;
+        d_nname.cached = d_nmoff.cached = d_nbad.cached = true;
         d_comp.cached = d_inf[0].cached = d_inf[1].cached = d_blk.cached = d_status.cached = d_starts.cached = d_info.cached = d_bctr.cached = true;
-        tref_in.cached = d_tsize.cached = d_taux.cached = d_toff.cached = true;
-        e0.make(), e1.make(), e_mid.make(), e_t0.make(), e_t1.make(), e_b0.make(), e_b1.make(), e_b2.make();
+        d_tsize.cached = d_taux.cached = d_toff.cached = true;
+        e_mid.make(), e_t0.make(), e_t1.make(), e_b0.make(), e_b1.make(), e_b2.make();
     }
     ~Build() { (void)hipStreamSynchronize(st); }
 
@@ -493,8 +456,7 @@ struct Build {
         const uint64_t kept = h_tot[0], n_cig = h_tot[1], n_seq = h_tot[2];
         if (h->n_empty > n_lines || kept > n_lines - h->n_empty) throw Np2Error(NP2_E_DEVICE, "np2_sam: record counters out of range");
         n_records += n_lines - h->n_empty;
-        if (n_recs + kept >= (1ull << 31)) throw Np2Error(NP2_E_UNSUPPORTED, "a SAM input of 2^31 alignment records or more");
-        if (n_cigar + n_cig >= 0xFFFF0000ull) throw Np2Error(NP2_E_UNSUPPORTED, "a SAM input of more than 4294901760 CIGAR operations");
+        check_room(kept, n_cig);
         uint64_t n_name = 0, n_tail = 0;
         if (keep_names && kept) { // the names' lengths and where they go; a bad one speaks after every other error of the piece
             uint32_t *h_name = h_tot + 16; // [0]: the first bad line, [1]: the bytes of all names
@@ -531,19 +493,7 @@ struct Build {
             }
         }
         if (kept) {
-            if (keep_names) {
-                grow(nref_in, n_recs, n_recs + kept, st, "names");
-                grow(sam.names, name_bytes, name_bytes + n_name + 1, st, "names");
-            }
-            if (keep_all) {
-                grow(tref_in, n_recs, n_recs + kept, st, "tails");
-                grow(sam.tails, tail_bytes, tail_bytes + n_tail + 16, st, "quality bytes and optional fields");
-            }
-            grow(recs_in, n_recs * np2::SAM_REC_WORDS, (n_recs + kept) * np2::SAM_REC_WORDS, st, "records");
-            grow(tids_in, n_recs, n_recs + kept, st, "records");
-            grow(keys_in, n_recs, n_recs + kept, st, "sort keys");
-            grow(cigar_in, n_cigar, n_cigar + n_cig + 1, st, "CIGAR words");
-            grow(sam.seq4, seq_bytes, seq_bytes + n_seq + 16, st, "packed SEQ");
+            reserve(kept, n_cig, n_seq, n_name, n_tail);
             HIPCHK(hipEventRecord(e0.e, st));
             np2::launch_sam_pack(st, d_text.p, d_lines.p, n_lines, d_koff.p, d_coff.p, d_soff.p, n_recs, n_cigar, seq_bytes, tie, recs_in.p,
                                  tids_in.p, keys_in.p, cigar_in.p, sam.seq4.p);
@@ -563,7 +513,7 @@ struct Build {
                 sam.tail_emit_ms += elapsed(e_t0, e_t1);
             }
         }
-        n_recs += kept, n_cigar += n_cig, seq_bytes += n_seq, name_bytes += n_name, tail_bytes += n_tail;
+        advance(kept, n_cig, n_seq, n_name, n_tail);
     }
 
     // One piece of a BAM: `comp` (pinned) holds the file's bytes from p.file_off on, p.blks the blocks in them that hold bytes.
@@ -670,23 +620,10 @@ struct Build {
             kept = h_tot[0], n_cig = h_tot[1], n_seq = h_tot[2], n_name = h_tot[3], n_tail = h_tot[4];
             if (kept > count || n_cig > n / 4 || n_seq > n || n_name > kept * 254u || n_tail % 4u || n_tail > n + kept * (np2tail::HEAD_BYTES + 4ull))
                 throw Np2Error(NP2_E_DEVICE, "np2_sam: record counters out of range");
-            if (n_recs + kept >= (1ull << 31)) throw Np2Error(NP2_E_UNSUPPORTED, "a SAM input of 2^31 alignment records or more");
-            if (n_cigar + n_cig >= 0xFFFF0000ull) throw Np2Error(NP2_E_UNSUPPORTED, "a SAM input of more than 4294901760 CIGAR operations");
+            check_room(kept, n_cig);
         }
         if (kept) {
-            if (keep_names) {
-                grow(nref_in, n_recs, n_recs + kept, st, "names");
-                grow(sam.names, name_bytes, name_bytes + n_name + 1, st, "names");
-            }
-            if (keep_all) {
-                grow(tref_in, n_recs, n_recs + kept, st, "tails");
-                grow(sam.tails, tail_bytes, tail_bytes + n_tail + 16, st, "quality bytes and optional fields");
-            }
-            grow(recs_in, n_recs * np2::SAM_REC_WORDS, (n_recs + kept) * np2::SAM_REC_WORDS, st, "records");
-            grow(tids_in, n_recs, n_recs + kept, st, "records");
-            grow(keys_in, n_recs, n_recs + kept, st, "sort keys");
-            grow(cigar_in, n_cigar, n_cigar + n_cig + 1, st, "CIGAR words");
-            grow(sam.seq4, seq_bytes, seq_bytes + n_seq + 16, st, "packed SEQ");
+            reserve(kept, n_cig, n_seq, n_name, n_tail);
             const np2::BaminOut out{d_koff.p, d_coff.p, d_soff.p, d_nmoff.p, d_toff.p, n_recs, n_cigar, seq_bytes, name_bytes, tail_bytes, recs_in.p,
                                     tids_in.p, keys_in.p, cigar_in.p, sam.seq4.p, sam.names.p, nref_in.p, sam.tails.p, tref_in.p};
             HIPCHK(hipEventRecord(e0.e, st));
@@ -697,7 +634,7 @@ struct Build {
             sam.bamin.pack_ms += elapsed(e0, e1);
         }
         n_records += count, file_recs += count, sam.bamin.records += count;
-        n_recs += kept, n_cigar += n_cig, seq_bytes += n_seq, name_bytes += n_name, tail_bytes += n_tail;
+        advance(kept, n_cig, n_seq, n_name, n_tail);
         carry_at = tail_at, carry_n = (uint32_t)n - tail_at, cur ^= 1;
         if (p.last && carry_n) {
             const uint32_t w = carry_n < 4u ? bi::W_GARBAGE : bi::W_TRUNC;
@@ -724,51 +661,6 @@ struct Build {
         np2h::throw_tail_error(line.data(), e, nth.view(), at);
     }
 
-    // after the last piece: input order -> sorted order
-    void finish() {
-        const uint32_t n = (uint32_t)n_recs;
-        sam.n_recs = n_recs, sam.n_cigar = n_cigar, sam.seq_bytes = seq_bytes;
-        sam.has_names = keep_names, sam.name_bytes = name_bytes;
-        sam.has_tails = keep_all, sam.tail_bytes = tail_bytes;
-        if (tail_bytes) HIPCHK(hipMemsetAsync(sam.tails.p + tail_bytes, 0, 16, st)); // (the encoder reads whole words)
-        sam.stats.records = n_records, sam.stats.kept = n_recs, sam.stats.unmapped = n_records - n_recs;
-        sam.stats.cigar_words = n_cigar, sam.stats.seq_bytes = seq_bytes;
-        if (seq_bytes) HIPCHK(hipMemsetAsync(sam.seq4.p + seq_bytes, 0, 16, st)); // (what records_to_arrays appends, for a reader of 16-byte words)
-        if (n == 0) {
-            HIPCHK(hipStreamSynchronize(st));
-            return;
-        }
-        const size_t tmp_bytes = np2::prim_temp_bytes((size_t)n + 1);
-        need_device((size_t)n * (8 + 4 + 4 + 4 + 4 + 4 + 40 + (keep_names ? 8 : 0) + (keep_all ? 8 : 0)) + (n_cigar + 1) * 4 + tmp_bytes, "sorted records and CIGAR words");
-        DevBuf<uint64_t> keys_out;
-        DevBuf<uint32_t> vals_in, vals_out, sizes, offs;
-        keys_out.cached = vals_in.cached = vals_out.cached = sizes.cached = offs.cached = true; // (released after the last synchronisation below)
-        keys_out.ensure(n), vals_in.ensure(n), vals_out.ensure(n), sizes.ensure((size_t)n + 1), offs.ensure((size_t)n + 1);
-        d_tmp.ensure(tmp_bytes);
-        sam.recs.ensure((size_t)n * np2::SAM_REC_WORDS), sam.tids.ensure(n), sam.cigar.ensure(n_cigar + 1);
-        HIPCHK(hipEventRecord(e0.e, st));
-        np2::launch_sam_iota(st, vals_in.p, n);
-        if (np2::prim_sort_pairs_u64_u32(st, d_tmp.p, tmp_bytes, keys_in.p, keys_out.p, vals_in.p, vals_out.p, n, 64))
-            throw Np2Error(NP2_E_DEVICE, "rocprim radix_sort_pairs failed");
-        np2::launch_sam_sorted_sizes(st, recs_in.p, vals_out.p, n, sizes.p);
-        if (np2::prim_exclusive_sum_u32(st, d_tmp.p, tmp_bytes, sizes.p, offs.p, (size_t)n + 1))
-            throw Np2Error(NP2_E_DEVICE, "rocprim exclusive_scan failed");
-        np2::launch_sam_gather(st, recs_in.p, tids_in.p, cigar_in.p, vals_out.p, offs.p, n, sam.recs.p, sam.tids.p, sam.cigar.p);
-        if (keep_names) {
-            sam.name_ref.ensure(n);
-            np2::launch_sam_gather_u64(st, nref_in.p, vals_out.p, n, sam.name_ref.p);
-        }
-        if (keep_all) {
-            sam.tail_ref.ensure(n);
-            np2::launch_sam_gather_u64(st, tref_in.p, vals_out.p, n, sam.tail_ref.p);
-        }
-        HIPCHK(hipEventRecord(e1.e, st));
-        sam.keys.resize(n);
-        HIPCHK(hipMemcpyAsync(sam.keys.data(), keys_out.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        HIPCHK(hipGetLastError());
-        sam.stats.sort_ms = elapsed(e0, e1);
-    }
     void report() const {
         if (!hooks.profile) return;
         fprintf(stderr, "np2_sam: %llu bytes of alignment lines: k_sam_lines %.3f ms, k_sam_fields + scans %.3f ms, k_sam_pack %.3f ms, sort + k_sam_gather %.3f ms, waited for the reader %.3f ms\n",

@@ -349,6 +349,10 @@ def _bind_map(L):
     L.np2_map_align_files.argtypes = [vp, C.POINTER(C.c_char_p), C.c_int, mo, ao, C.c_char_p, C.POINTER(np2_map_stats_t)]
     L.np2_map_align_host.argtypes = [vp, u64, vp, u64, u64, mo, ao, vp, vp, C.POINTER(vp), vp]
     L.np2_map_align_last_stats.argtypes = [C.POINTER(np2_align_stats_t)]
+    so, pvp = C.POINTER(np2_sam_opts_t), C.POINTER(vp)
+    L.np2_sam_from_reads.argtypes = [vp, vp, C.POINTER(C.c_char_p), C.c_int, mo, ao, so, C.c_uint32, pvp]
+    L.np2_sam_from_read_bytes.argtypes = [vp, vp, vp, u64, u64, C.c_char_p, mo, ao, so, C.c_uint32, pvp]
+    L.np2_align_pack_host.argtypes = [vp, vp, vp, vp, u64, u64, so, pvp, pvp, pvp, pvp, C.POINTER(u64)]
 
 
 def _bind_shard(L):
@@ -834,6 +838,34 @@ class Sam:
         else:
             _io_check(L.np2_sam_open(pol._h, arr, n, C.byref(o), C.byref(self._h)))
 
+    @classmethod
+    def from_reads(cls, pol, index, paths_or_reads, tie="strand", keep_names=False, names=None, **map_and_align_kw):
+        """np2_sam_from_reads / np2_sam_from_read_bytes: HiFi reads mapped and aligned against the MapIndex `index` (on pol's
+        device), the records packed and coordinate-sorted where they lie: an ordinary Sam that holds what Sam(pol, [the SAM
+        map_align_files writes for the same call]) would hold, without the text.  paths_or_reads: a list of read files (FASTA or
+        FASTQ, plain or gzip), or a list of sequences (bytes) / a separator stream as MapIndex.align takes, then with `names` (one
+        per read) or numbered from 1.  Options: MAP_DEFAULTS and ALIGN_DEFAULTS."""
+        L = _bind()
+        kw = dict(map_and_align_kw)
+        akw = {f: kw.pop(f) for f in list(kw) if f in ALIGN_DEFAULTS}
+        o, ao, so = index._opts(kw), align_opts(**akw), _sam_opts(tie)
+        flags = NP2_SAM_KEEP_NAMES if keep_names else 0
+        self = cls.__new__(cls)
+        self._h = C.c_void_p()
+        in_memory = isinstance(paths_or_reads, (bytes, bytearray, memoryview, np.ndarray)) or (
+            len(paths_or_reads) > 0 and all(isinstance(x, (bytes, bytearray)) for x in paths_or_reads))
+        if in_memory:
+            s, n = _stream_of(paths_or_reads)
+            nm = None if names is None else "".join(x + "\n" for x in names).encode()
+            _io_check(L.np2_sam_from_read_bytes(pol._h, index._h, s.ctypes.data if len(s) else None, len(s), n, nm, C.byref(o), C.byref(ao),
+                                                C.byref(so), flags, C.byref(self._h)))
+        else:
+            if names is not None:
+                raise TypeError("names go with reads in memory: read files carry their own")
+            arr, n = _paths(paths_or_reads)
+            _io_check(L.np2_sam_from_reads(pol._h, index._h, arr, n, C.byref(o), C.byref(ao), C.byref(so), flags, C.byref(self._h)))
+        return self
+
     def refs(self):
         L = _bind()
         out = []
@@ -1308,6 +1340,21 @@ def map_opts(**kw):
     return np2_map_opts_t(*[int(vals[f]) for f, _ in np2_map_opts_t._fields_])
 
 
+def map_opts_arg(text):
+    """argparse type of --map_opts KEY=VAL,...: the keys of map_opts and align_opts (MAP_DEFAULTS, ALIGN_DEFAULTS) with
+    non-negative integer values -> a dict; an unknown key or a bad value ends the parser (exit 2) before the library is loaded"""
+    import argparse
+    out = {}
+    for item in filter(None, (x.strip() for x in text.split(","))):
+        key, eq, val = item.partition("=")
+        if key not in MAP_DEFAULTS and key not in ALIGN_DEFAULTS:
+            raise argparse.ArgumentTypeError(f"unknown key {key!r} (the keys: {' '.join(list(MAP_DEFAULTS) + list(ALIGN_DEFAULTS))})")
+        if not eq or not val.isdigit() or int(val) > 0xFFFFFFFF:
+            raise argparse.ArgumentTypeError(f"{key}: a whole number in 0 .. 2^32 - 1 is expected, as in {key}={({**MAP_DEFAULTS, **ALIGN_DEFAULTS})[key]}")
+        out[key] = int(val)
+    return out
+
+
 def _map_stats_dict(st):
     return {f: getattr(st, f) for f, _ in np2_map_stats_t._fields_}
 
@@ -1477,6 +1524,26 @@ def map_align_files(index, paths, out_path, **kw):
     _io_check(L.np2_map_align_files(index._h, arr, n, C.byref(o), C.byref(ao), None if out_path is None else os.fspath(out_path).encode(),
                                     C.byref(st)))
     return _map_stats_dict(st)
+
+
+def align_pack_host(recs, cigar, cigar_off, reads, tie="strand"):
+    """np2_align_pack_host (no device): the aligner's output for `reads` (what MapIndex.align or map_align_host returns: recs,
+    cigar, cigar_off) -> (recs as a BAMREC_DTYPE array in sorted order, tids, cigar in sorted order, seq4 as the reads were met):
+    what Sam.from_reads(...).export() returns, from the same rule text as the kernels."""
+    L = _bind()
+    s, n = _stream_of(reads)
+    recs = np.ascontiguousarray(recs, ALIGN_REC_DTYPE)
+    cigar, off = np.ascontiguousarray(cigar, np.uint32), np.ascontiguousarray(cigar_off, np.uint64)
+    if len(recs) != n or len(off) != n + 1:
+        raise ValueError(f"{n} reads, {len(recs)} records and {len(off)} CIGAR offsets")
+    o = _sam_opts(tie)
+    pr, pt, pc, ps, m = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64()
+    _io_check(L.np2_align_pack_host(recs.ctypes.data if n else None, cigar.ctypes.data if len(cigar) else None, off.ctypes.data,
+                                    s.ctypes.data if len(s) else None, len(s), n, C.byref(o), C.byref(pr), C.byref(pt), C.byref(pc), C.byref(ps),
+                                    C.byref(m)))
+    out = np.frombuffer(C.string_at(pr.value, m.value * BAMREC_DTYPE.itemsize), dtype=BAMREC_DTYPE) if m.value else np.zeros(0, BAMREC_DTYPE)
+    sizes = {"cigar_words": int(out["n_cigar"].sum()), "seq_bytes": int(((out["l_seq"].astype(np.int64) + 1) // 2).sum())}
+    return _sam_arrays(L, pr, pt, pc, ps, m.value, sizes)
 
 
 def map_align_host(asm, reads, **kw):
