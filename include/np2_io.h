@@ -452,13 +452,32 @@ int np2_rep_files(int device, const char *const *paths, int n_paths, const np2_r
  *     min(k, dr, dq) for each later one; block (column 11) is max(qe - qs, te - ts).  A PAF line is
  *     qname qlen qs qe +/- tname tlen ts te matches block mapq tp:A:P cm:i:n s1:i:s1 s2:i:s2, tab-separated, one per mapped
  *     read in read order; a name is the header up to the first whitespace (a record without one: its 1-based number).
- *   Not built: secondary and supplementary chains; winnowmap's -W weighting; -f occurrence fractions; homopolymer compression;
+ *   Weights (winnowmap -W; the _w entries below).  THE RULE IS DEFINED HERE, on winnowmap's published weighted minimizer
+ *     sampling (Jain et al. 2020, Bioinformatics 36:i111); no winnowmap binary was at hand and equality with it is not claimed.
+ *     A weight set is (kw, L): L a set of canonical k-mer indices v = min(fw, rv) of length kw, in np2_rep_*'s encoding (A=0
+ *     C=1 G=2 T=3, first base most significant), 11 <= kw <= 15; a non-empty set with another kw is NP2_E_UNSUPPORTED (16 <= k
+ *     <= 28 would need more than a direct-addressed bitmap).  An index built with weights requires opts.k == kw, otherwise
+ *     NP2_E_ARG with both values in the message.  An empty set has kw = 0, fits any k and is the unweighted mapper.
+ *     Order.  M = 4^k - 1, h the k-mer's hash as above (k <= 15: h < 2^30).  A k-mer not in L has key = h.  A k-mer in L has
+ *     y = M - h, s(y) = (y * y) >> 2k, y8 = s(s(s(y))) and key = M - y8: the fixed-point form of winnowmap's x -> x^8, mirrored
+ *     because the smallest hash wins here; the products fit 64 bits and no floating point is used.  Position i is a minimizer
+ *     if and only if some window holds it and (key_i, h_i, i) is the lexicographic minimum of that window over its k-mers with
+ *     fw != rv: equal keys (y8 collapses) are broken by h, then by leftmost.  A palindrome is never chosen, listed or not.  A
+ *     minimizer's identity in the index and in seeding stays h.  max_occ, seeding, chaining, mapq and alignment are untouched.
+ *     The assembly and the reads are sketched under the same weights: they belong to the index, which copies what it needs.
+ *     List file.  One k-mer a line, KMER or KMER<TAB>anything; ACGT in either case, U read as T; all lines of one length, kw;
+ *     \n and \r\n end a line; a k-mer given in either or both orientations sets the one canonical bit; duplicates are
+ *     allowed; a bad letter or a line of another length is NP2_E_ARG with the 1-based line number; an empty file is the empty
+ *     set; plain text or gzip.  (python -m nextpolish2_amd.repkmers writes such a list.)
+ *   Not built: secondary and supplementary chains; -f occurrence fractions; homopolymer compression; weights for k >= 16 or
+ *     per-k-mer weights other than the eighth power;
  *     several devices; an index beyond one device's memory (base-level alignment and SAM: np2_map_align_*, below).
  *     NP2_E_UNSUPPORTED: an assembly of 2^32 bytes or more, a sequence or read longer than 2^31 - 1, a single read with more
  *     anchors than the device budget (2^25).
  * Every argument is checked before the first device call.  Errors: np2_io_last_error().  Test hooks, read once per call:
  * NP2_MAP_TEST_PIECE (bytes; a batch of reads goes up and is sketched in pieces of 8 MiB, eight pieces a batch, wherever the
- * boundary falls in a read) and NP2_MAP_TEST_BUDGET (anchors; a batch beyond it is chained in groups of whole reads). */
+ * boundary falls in a read), NP2_MAP_TEST_BUDGET (anchors; a batch beyond it is chained in groups of whole reads) and
+ * NP2_MAP_TEST_COARSE (0: an index built with weights goes without the coarse level of its bitmap; the results are the same). */
 typedef struct np2_map_opts {
     uint32_t k, w, max_occ, lookback, max_gap, bandwidth, min_cnt, min_score;
 } np2_map_opts_t;
@@ -501,6 +520,26 @@ int np2_map_host(const uint8_t *asm_stream, uint64_t n_asm, const uint8_t *reads
                  np2_map_hit_t *hits, uint32_t **chain, uint64_t *chain_off);
 /* the counts and stage times of the last np2_map_bytes / np2_map_files / np2_map_host call on this thread */
 int np2_map_last_stats(np2_map_stats_t *stats);
+/* Weights (the rule: above).  A weight set lives in host memory only.  From canonical indices in any order, duplicates allowed
+ * (an index beyond 4^k - 1 or a non-canonical one is NP2_E_ARG; n == 0 is the empty set whatever k says), or from a list file.
+ * info: k (0 for the empty set) and the number of distinct listed k-mers; either output may be NULL. */
+typedef struct np2_map_weights np2_map_weights_t;
+int np2_map_weights_from_indices(uint32_t k, const uint32_t *index, uint64_t n, np2_map_weights_t **out);
+int np2_map_weights_from_file(const char *path, np2_map_weights_t **out);
+int np2_map_weights_info(const np2_map_weights_t *w, uint32_t *k, uint64_t *n_listed);
+void np2_map_weights_free(np2_map_weights_t *w);
+/* np2_map_index_bytes / np2_map_index_files under weights: w NULL or empty makes them their plain twins.  The index keeps a
+ * bitmap of 4^k bits on the device (128 MiB at k = 15) and every door that takes the index (np2_map_bytes, np2_map_files,
+ * np2_map_align_*, np2_sam_from_reads*) sketches the reads under it; w may be freed right after the call. */
+int np2_map_index_bytes_w(int device, const uint8_t *stream, uint64_t n, const char *names, const np2_map_opts_t *opts,
+                          const np2_map_weights_t *w, np2_map_index_t **out);
+int np2_map_index_files_w(int device, const char *const *paths, int n_paths, const np2_map_opts_t *opts, const np2_map_weights_t *w,
+                          np2_map_index_t **out);
+/* the weights an index was built with: 0, 0 for an unweighted one; either output may be NULL */
+int np2_map_index_weights(const np2_map_index_t *ix, uint32_t *k, uint64_t *n_listed);
+/* np2_map_host under weights (host only, no device) */
+int np2_map_host_w(const uint8_t *asm_stream, uint64_t n_asm, const uint8_t *reads, uint64_t n, uint64_t n_reads, const np2_map_opts_t *opts,
+                   const np2_map_weights_t *w, np2_map_hit_t *hits, uint32_t **chain, uint64_t *chain_off);
 
 /* ---- the primary chain as a base-level alignment: chains to SAM (the recipe's `winnowmap -ax` / `minimap2 -a`, whose SAM the
  * polisher reads) ----------------------------------------------------------------------------------------------------------------
@@ -573,6 +612,10 @@ int np2_map_align_files(const np2_map_index_t *ix, const char *const *paths, int
 int np2_map_align_host(const uint8_t *asm_stream, uint64_t n_asm, const uint8_t *reads, uint64_t n, uint64_t n_reads,
                        const np2_map_opts_t *map_opts, const np2_align_opts_t *align_opts, np2_map_hit_t *hits, np2_align_rec_t *recs,
                        uint32_t **cigar, uint64_t *cigar_off);
+/* np2_map_align_host under weights (np2_map_weights_t, above); w NULL or empty: np2_map_align_host */
+int np2_map_align_host_w(const uint8_t *asm_stream, uint64_t n_asm, const uint8_t *reads, uint64_t n, uint64_t n_reads,
+                         const np2_map_opts_t *map_opts, const np2_align_opts_t *align_opts, const np2_map_weights_t *w, np2_map_hit_t *hits,
+                         np2_align_rec_t *recs, uint32_t **cigar, uint64_t *cigar_off);
 /* the alignment counts and stage times of the last np2_map_align_* call on this thread */
 int np2_map_align_last_stats(np2_align_stats_t *stats);
 

@@ -64,6 +64,10 @@ def build_parser():
     p.add_argument("--map_opts", type=np2io.map_opts_arg, default={}, metavar="KEY=VAL,...",
                    help="--from_reads: mapper and aligner options, the keys of python -m nextpolish2_amd.map (" +
                         " ".join(list(np2io.MAP_DEFAULTS) + list(np2io.ALIGN_DEFAULTS)) + ")")
+    p.add_argument("--map_weights", default=None, metavar="FILE|auto",
+                   help="--from_reads: down-weight repetitive k-mers in the mapper's minimizer sampling (winnowmap -W): a list file as "
+                        "python -m nextpolish2_amd.repkmers writes it, or `auto`: the assembly's own, counted here (distinct=0.9998, "
+                        "k = 15); without k in --map_opts, k is the list's")
     p.add_argument("fa", type=_existing, metavar="genome.fa[.gz]", help="genome assembly file in [GZIP] FASTA format")
     p.add_argument("yak", type=_existing, nargs="*", metavar="short.read.yak", help="one or more k-mer dataset in yak format")
     p.add_argument("--sr", type=_existing, action="append", default=[], metavar="FILE",
@@ -417,6 +421,20 @@ def main(argv=None):
         raise SystemExit("error: invalid value for --model (ref|len)")
     if (a.more_reads or a.map_opts) and not a.from_reads:
         parser.error("--more_reads and --map_opts go with --from_reads")
+    if a.map_weights is not None and not a.from_reads:
+        parser.error("--map_weights goes with --from_reads")
+    if a.map_weights is not None:  # the mapper's k rule (python -m nextpolish2_amd.map, -W and --rep), before any device work
+        from . import map as np2mapcli
+        wk = np2mapcli.REP_K if "k" not in a.map_opts else a.map_opts["k"]
+        if a.map_weights != "auto":
+            try:
+                wk = np2mapcli.list_k(a.map_weights)
+            except OSError as e:
+                raise SystemExit(f"Error: --map_weights: {e}")
+        k, bad = np2mapcli.resolve_k(a.map_opts.get("k"), wk, np2io.MAP_DEFAULTS["k"], flag="--map_opts k=")
+        if bad:
+            raise SystemExit(f"Error: {bad}")
+        a.map_opts = dict(a.map_opts, k=k)
     if a.from_reads:  # every refusal before any device work, one line each
         if a.bam == "-":
             raise SystemExit("Error: --from_reads takes read files, not standard input: its reader threads open each file themselves")
@@ -550,7 +568,15 @@ def main(argv=None):
         try:
             if a.from_reads:  # reads -> index -> mapped, aligned, packed and sorted where they lie; the index goes once that is done
                 mo = dict(a.map_opts)
-                with np2io.MapIndex(a.fa, k=mo.pop("k", np2io.MAP_DEFAULTS["k"]), w=mo.pop("w", np2io.MAP_DEFAULTS["w"]), device=a.device) as ix:
+                k = mo.pop("k", np2io.MAP_DEFAULTS["k"])
+                weights = None
+                if a.map_weights == "auto":
+                    weights = np2io.MapWeights.from_assembly(a.fa, k=k, device=a.device)
+                elif a.map_weights is not None:
+                    weights = np2io.MapWeights(a.map_weights)
+                with np2io.MapIndex(a.fa, k=k, w=mo.pop("w", np2io.MAP_DEFAULTS["w"]), device=a.device, weights=weights) as ix:
+                    if weights is not None:
+                        weights.close()
                     sam = np2io.Sam.from_reads(spol, ix, [a.bam] + a.more_reads, tie=a.sam_tie, keep_names=a.sorted_bam is not None, **mo)
             else:
                 sam = np2io.Sam(spol, [a.bam], tie=a.sam_tie, keep_names=a.sorted_bam is not None, keep_all=a.sorted_bam_full)

@@ -11,6 +11,10 @@
 //     Emit writes at tile_off[tile] + rank with rank below the tile's own count, taken by the count pass with the same test
 //     from the same bytes; the arrays hold tile_off[n_tiles] entries.  The sequence of a position is the number of
 //     separators before it, below n_ends because the stream ends in a separator.
+//     Weighted: a k-mer's canonical index v is masked to 2k bits, v <= M = 4^k - 1, so its bitmap word v >> 6 < 4^k / 64, the
+//     words the index handle allocates (k >= 11: 4^k is a multiple of 64); the coarse level's word v >> 12 < 4^k / 4096, its
+//     words (1024 bits at k = 11).  The warm-up bytes are pushed without a lookup.
+//   k_map_weights_set: entry i < n of the uploaded list; the host has checked idx[i] <= M, so both words are inside their levels.
 //   k_map_seed_count: two binary searches over idx_h[0 .. idx_n); lo + occ <= idx_n.
 //   k_map_read_ranges: a binary search over mz_x[0 .. n_mz); first[r] <= n_mz, and off has n_mz + 1 entries.
 //   k_map_seed_emit: minimizer m writes cnt[m] anchors at off[m] - off[m0], below off[m1] - off[m0], the arrays' size; it reads
@@ -27,11 +31,16 @@
 
 namespace np2 {
 
-template <bool EMIT>
+// WEIGHTED: a k-mer's word carries its ordering key above its hash (np2map::push_w); whether it is listed is a load from the
+// index's bitmap (bit v of 4^k, 64 to a word), in the count pass and in the emit pass alike.  With `coarse` (one bit per word of
+// the bitmap: 2 MiB at k = 15, which an XCD's L2 holds, where the bitmap's 128 MiB are random loads from beyond it) that bit is
+// tested first and the bitmap is read only where a word has a listed k-mer.
+template <bool EMIT, bool WEIGHTED>
 __global__ __launch_bounds__(MAP_BLOCK) void k_map_sketch(const uint8_t *__restrict__ seq, uint64_t n, uint64_t base, uint64_t len, uint32_t k,
                                                           uint32_t w, uint32_t tile0, uint32_t *__restrict__ tile_cnt,
                                                           const uint32_t *__restrict__ tile_off, const uint32_t *__restrict__ ends,
-                                                          uint32_t n_ends, uint64_t *__restrict__ mz_h, uint64_t *__restrict__ mz_x) {
+                                                          uint32_t n_ends, uint64_t *__restrict__ mz_h, uint64_t *__restrict__ mz_x,
+                                                          const uint64_t *__restrict__ listed, const uint64_t *__restrict__ coarse) {
     __shared__ uint4 tile[MAP_TILE_BYTES / 16];
     __shared__ uint64_t words[MAP_WORDS];
     __shared__ uint32_t sh[MAP_BLOCK / 64];
@@ -55,7 +64,16 @@ __global__ __launch_bounds__(MAP_BLOCK) void k_map_sketch(const uint8_t *__restr
         for (uint32_t d = 0; d < MAP_STRETCH / 4; ++d) {
             const uint32_t x = lw[MAP_WARM / 4 + d];
 #pragma unroll
-            for (uint32_t j = 0; j < 4; ++j) words[threadIdx.x * MAP_STRETCH + d * 4 + j] = np2map::push(r, (uint8_t)(x >> (8 * j)), k, mask);
+            for (uint32_t j = 0; j < 4; ++j) {
+                uint64_t word;
+                if (WEIGHTED)
+                    word = np2map::push_w(r, (uint8_t)(x >> (8 * j)), k, mask, [&](uint64_t v) {
+                        if (coarse && !((coarse[v >> 12] >> ((v >> 6) & 63u)) & 1u)) return false;
+                        return ((listed[v >> 6] >> (v & 63u)) & 1u) != 0;
+                    });
+                else word = np2map::push(r, (uint8_t)(x >> (8 * j)), k, mask);
+                words[threadIdx.x * MAP_STRETCH + d * 4 + j] = word;
+            }
         }
     }
     __syncthreads();
@@ -82,7 +100,7 @@ __global__ __launch_bounds__(MAP_BLOCK) void k_map_sketch(const uint8_t *__restr
                     else b = m;
                 }
                 const uint64_t start = a ? (uint64_t)ends[a - 1] + 1 : 0;
-                mz_h[place] = word >> 1;
+                mz_h[place] = WEIGHTED ? np2map::word_hash(word, np2map::kmer_mask(k)) : word >> 1;
                 mz_x[place] = np2map::mz_x(a, (uint32_t)(pos - start), (uint32_t)(word & 1u));
             }
             place0 += total;
@@ -94,6 +112,16 @@ __global__ __launch_bounds__(MAP_BLOCK) void k_map_sketch(const uint8_t *__restr
         __syncthreads();
         if (threadIdx.x == 0) tile_cnt[tile0 + blockIdx.x] = s_total;
     }
+}
+
+// the listed indices (any order, duplicates allowed) -> their bits in the zeroed bitmap and, with `coarse`, in the zeroed coarse level
+__global__ __launch_bounds__(256) void k_map_weights_set(const uint32_t *__restrict__ idx, uint64_t n, unsigned long long *__restrict__ bitmap,
+                                                         unsigned long long *__restrict__ coarse) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t v = idx[i];
+    atomicOr(&bitmap[v >> 6], 1ull << (v & 63u));
+    if (coarse) atomicOr(&coarse[v >> 12], 1ull << ((v >> 6) & 63u));
 }
 
 __global__ __launch_bounds__(256) void k_map_seed_count(const uint64_t *__restrict__ mz_h, uint32_t n_mz, const uint64_t *__restrict__ idx_h,
@@ -209,16 +237,30 @@ __global__ __launch_bounds__(256) void k_map_chain_export(MapChain c, const uint
 }
 
 void launch_map_sketch_count(hipStream_t s, const uint8_t *seq, uint64_t n, uint64_t base, uint64_t len, uint32_t k, uint32_t w,
-                             uint32_t tile0, uint32_t *tile_cnt) {
+                             uint32_t tile0, uint32_t *tile_cnt, const uint64_t *listed, const uint64_t *coarse) {
     if (len == 0) return;
-    hipLaunchKernelGGL(k_map_sketch<false>, dim3(map_tiles(len)), dim3(MAP_BLOCK), 0, s, seq, n, base, len, k, w, tile0, tile_cnt, nullptr,
-                       nullptr, 0u, nullptr, nullptr);
+    if (listed)
+        hipLaunchKernelGGL((k_map_sketch<false, true>), dim3(map_tiles(len)), dim3(MAP_BLOCK), 0, s, seq, n, base, len, k, w, tile0, tile_cnt,
+                           nullptr, nullptr, 0u, nullptr, nullptr, listed, coarse);
+    else
+        hipLaunchKernelGGL((k_map_sketch<false, false>), dim3(map_tiles(len)), dim3(MAP_BLOCK), 0, s, seq, n, base, len, k, w, tile0, tile_cnt,
+                           nullptr, nullptr, 0u, nullptr, nullptr, nullptr, nullptr);
 }
 void launch_map_sketch_emit(hipStream_t s, const uint8_t *seq, uint64_t n, uint64_t base, uint64_t len, uint32_t k, uint32_t w,
-                            uint32_t tile0, const uint32_t *tile_off, const uint32_t *ends, uint32_t n_ends, uint64_t *mz_h, uint64_t *mz_x) {
+                            uint32_t tile0, const uint32_t *tile_off, const uint32_t *ends, uint32_t n_ends, uint64_t *mz_h, uint64_t *mz_x,
+                            const uint64_t *listed, const uint64_t *coarse) {
     if (len == 0) return;
-    hipLaunchKernelGGL(k_map_sketch<true>, dim3(map_tiles(len)), dim3(MAP_BLOCK), 0, s, seq, n, base, len, k, w, tile0, nullptr, tile_off,
-                       ends, n_ends, mz_h, mz_x);
+    if (listed)
+        hipLaunchKernelGGL((k_map_sketch<true, true>), dim3(map_tiles(len)), dim3(MAP_BLOCK), 0, s, seq, n, base, len, k, w, tile0, nullptr,
+                           tile_off, ends, n_ends, mz_h, mz_x, listed, coarse);
+    else
+        hipLaunchKernelGGL((k_map_sketch<true, false>), dim3(map_tiles(len)), dim3(MAP_BLOCK), 0, s, seq, n, base, len, k, w, tile0, nullptr,
+                           tile_off, ends, n_ends, mz_h, mz_x, nullptr, nullptr);
+}
+void launch_map_weights_set(hipStream_t s, const uint32_t *idx, uint64_t n, uint64_t *bitmap, uint64_t *coarse) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_map_weights_set, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, idx, n, reinterpret_cast<unsigned long long *>(bitmap),
+                       reinterpret_cast<unsigned long long *>(coarse));
 }
 void launch_map_seed_count(hipStream_t s, const uint64_t *mz_h, uint32_t n_mz, const uint64_t *idx_h, uint32_t idx_n, uint32_t max_occ,
                            uint32_t *lo, uint32_t *cnt, unsigned long long *ctr) {

@@ -27,10 +27,19 @@ inline uint32_t map_tiles(uint64_t len) { return (uint32_t)((len + MAP_TILE - 1)
 // One piece [base, base + len) of a resident separator stream of n bytes.  `seq` points at the stream's first byte; the
 // MAP_FRONT bytes before it are separators, the buffer is readable up to the next multiple of 16 after n, and base is a
 // multiple of 16.  counts: per tile (tile0 + block) the minimizers it owns; emit: their (h, x) at tile_off[tile0 + block] on.
+// listed: null for the unweighted sketch, otherwise the weight set's bitmap (map_weight_words(k) words, np2map::push_w), and
+// coarse: null or its coarse level (map_weight_coarse_words(k) words).
 void launch_map_sketch_count(hipStream_t s, const uint8_t *seq, uint64_t n, uint64_t base, uint64_t len, uint32_t k, uint32_t w,
-                             uint32_t tile0, uint32_t *tile_cnt);
+                             uint32_t tile0, uint32_t *tile_cnt, const uint64_t *listed = nullptr, const uint64_t *coarse = nullptr);
 void launch_map_sketch_emit(hipStream_t s, const uint8_t *seq, uint64_t n, uint64_t base, uint64_t len, uint32_t k, uint32_t w,
-                            uint32_t tile0, const uint32_t *tile_off, const uint32_t *ends, uint32_t n_ends, uint64_t *mz_h, uint64_t *mz_x);
+                            uint32_t tile0, const uint32_t *tile_off, const uint32_t *ends, uint32_t n_ends, uint64_t *mz_h, uint64_t *mz_x,
+                            const uint64_t *listed = nullptr, const uint64_t *coarse = nullptr);
+// The weight set on the device: one bit per canonical k-mer index, 4^k bits as 64-bit words (128 MiB at k = 15, 512 KiB at
+// k = 11), and the coarse level: one bit per word of the bitmap, set where the word is not zero (2 MiB at k = 15).  Both are
+// zeroed on the stream first; every idx[i] <= 4^k - 1.  coarse may be null.
+inline size_t map_weight_words(uint32_t k) { return (size_t)1 << (2u * k - 6u); }
+inline size_t map_weight_coarse_words(uint32_t k) { return (size_t)1 << (2u * k - 12u); }
+void launch_map_weights_set(hipStream_t s, const uint32_t *idx, uint64_t n, uint64_t *bitmap, uint64_t *coarse);
 // per read minimizer: its run [lo, lo + occ) in the index's sorted hashes; cnt = occ when 1 <= occ <= max_occ, else 0;
 // ctr[0] += minimizers dropped by occurrence
 void launch_map_seed_count(hipStream_t s, const uint64_t *mz_h, uint32_t n_mz, const uint64_t *idx_h, uint32_t idx_n, uint32_t max_occ,

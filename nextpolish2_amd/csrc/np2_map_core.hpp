@@ -26,7 +26,8 @@ struct Hit {
 
 // ---- sketch ----------------------------------------------------------------------------------------------------------------
 // A byte's word: h << 1 | strand of the k-mer that ends there, W_PAL where that k-mer is its own reverse complement (in the
-// run, never chosen), W_BREAK where no k-mer ends (no window holds the byte).  A hash has 2k <= 56 bits.
+// run, never chosen), W_BREAK where no k-mer ends (no window holds the byte).  A hash has 2k <= 56 bits.  (Under weights the
+// word carries an ordering key above the hash: push_w, below.)
 static constexpr uint64_t W_BREAK = ~0ULL, W_PAL = ~0ULL - 1;
 
 NP2_KC_HD uint32_t code(uint8_t ch) { // ACGT in either case; every other byte 4
@@ -55,6 +56,39 @@ NP2_KC_HD uint64_t push(Roll &r, uint8_t ch, uint32_t k, uint64_t mask) {
     if (r.l < k) return W_BREAK;
     if (r.fw == r.rv) return W_PAL;
     return np2kc::hash64(r.fw < r.rv ? r.fw : r.rv, mask) << 1 | (r.fw > r.rv ? 1u : 0u);
+}
+
+// ---- weighted sketch (winnowmap -W) ----------------------------------------------------------------------------------------
+// A weight set is a k-mer length kw in [KW_MIN, KW_MAX] and a set of canonical indices v = min(fw, rv).  A listed k-mer keeps
+// its hash as its identity but is ordered by key = M - s(s(s(M - h))), s(y) = y * y >> 2k, M = 4^k - 1: the fixed-point form
+// of x -> x^8 on [0, 1), mirrored because the smallest hash wins.  y <= M < 2^30, so y * y < 2^60 and s(y) <= M.
+static constexpr uint32_t KW_MIN = 11, KW_MAX = 15;
+
+NP2_KC_HD uint64_t weighted_key(uint64_t h, uint32_t k, uint64_t mask) {
+    uint64_t y = mask - h;
+    for (int i = 0; i < 3; ++i) y = (y * y) >> (2u * k);
+    return mask - y;
+}
+// A byte's word under weights: key << (2k + 1) | h << 1 | strand.  key, h <= M < 2^30, so a word is below 2^(4k + 1) <= 2^61,
+// under W_PAL and W_BREAK; is_minimizer's comparison of word >> 1 is the comparison of (key, h).
+static_assert(4 * KW_MAX + 1 <= 61 && (1ULL << 61) < W_PAL, "a weighted word stays below W_PAL and W_BREAK");
+NP2_KC_HD uint64_t word_hash(uint64_t word, uint64_t mask) { return (word >> 1) & mask; }
+
+// listed(v): is the canonical index v in the set
+template <class Listed> NP2_KC_HD uint64_t push_w(Roll &r, uint8_t ch, uint32_t k, uint64_t mask, Listed listed) {
+    const uint32_t c = code(ch);
+    if (c >= 4u) {
+        r.l = 0;
+        return W_BREAK;
+    }
+    r.fw = ((r.fw << 2) | (uint64_t)c) & mask;
+    r.rv = (r.rv >> 2) | ((uint64_t)(3u - c) << (2u * (k - 1u)));
+    if (r.l < k) ++r.l;
+    if (r.l < k) return W_BREAK;
+    if (r.fw == r.rv) return W_PAL;
+    const uint64_t v = r.fw < r.rv ? r.fw : r.rv, h = np2kc::hash64(v, mask);
+    const uint64_t key = listed(v) ? weighted_key(h, k, mask) : h;
+    return key << (2u * k + 1u) | h << 1 | (r.fw > r.rv ? 1u : 0u);
 }
 
 // at(d): the word of the byte d places from the candidate (d in [-(w - 1), w - 1]; W_BREAK beyond the sequence).  The

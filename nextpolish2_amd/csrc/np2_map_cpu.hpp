@@ -28,31 +28,44 @@ inline bool stream_ends(const uint8_t *s, uint64_t n, std::vector<uint64_t> &end
     return true;
 }
 
-// the minimizers of one sequence in ascending position, appended to `out` as (h, x) with x naming sequence `seq`
-inline void sketch_seq(const uint8_t *s, uint32_t n, uint32_t seq, uint32_t k, uint32_t w, std::vector<uint64_t> &words, std::vector<Minimizer> &out) {
+// a weight set in host memory: the listed canonical indices of k-mers of length k, ascending and unique (k = 0: empty)
+struct WeightSet {
+    uint32_t k = 0;
+    std::vector<uint32_t> idx;
+    bool empty() const { return idx.empty(); }
+    bool listed(uint64_t v) const { return std::binary_search(idx.begin(), idx.end(), (uint32_t)v); }
+};
+
+// the minimizers of one sequence in ascending position, appended to `out` as (h, x) with x naming sequence `seq`; under a
+// non-empty weight set `ws` (of length k) the window order is push_w's
+inline void sketch_seq(const uint8_t *s, uint32_t n, uint32_t seq, uint32_t k, uint32_t w, std::vector<uint64_t> &words, std::vector<Minimizer> &out,
+                       const WeightSet *ws = nullptr) {
     words.resize(n);
     Roll r;
     const uint64_t mask = kmer_mask(k);
-    for (uint32_t i = 0; i < n; ++i) words[i] = push(r, s[i], k, mask);
+    if (ws && ws->empty()) ws = nullptr;
+    for (uint32_t i = 0; i < n; ++i)
+        words[i] = ws ? push_w(r, s[i], k, mask, [&](uint64_t v) { return ws->listed(v); }) : push(r, s[i], k, mask);
     for (uint32_t i = 0; i < n; ++i) {
         auto at = [&](int32_t d) {
             const int64_t j = (int64_t)i + d;
             return j < 0 || j >= (int64_t)n ? W_BREAK : words[(size_t)j];
         };
-        if (is_minimizer(at, w)) out.push_back({words[i] >> 1, mz_x(seq, i, (uint32_t)(words[i] & 1u))});
+        if (is_minimizer(at, w)) out.push_back({ws ? word_hash(words[i], mask) : words[i] >> 1, mz_x(seq, i, (uint32_t)(words[i] & 1u))});
     }
 }
 
 struct HostIndex {
     uint32_t k = 0, w = 0;
     std::vector<Minimizer> mz; // stably sorted by h from (sequence, position) order
-    void build(const uint8_t *stream, const std::vector<uint64_t> &ends, uint32_t k_, uint32_t w_) {
-        k = k_, w = w_;
+    const WeightSet *ws = nullptr; // the caller's; reads are sketched under it too
+    void build(const uint8_t *stream, const std::vector<uint64_t> &ends, uint32_t k_, uint32_t w_, const WeightSet *ws_ = nullptr) {
+        k = k_, w = w_, ws = ws_;
         mz.clear();
         std::vector<uint64_t> words;
         uint64_t from = 0;
         for (size_t t = 0; t < ends.size(); ++t) {
-            sketch_seq(stream + from, (uint32_t)(ends[t] - from), (uint32_t)t, k, w, words, mz);
+            sketch_seq(stream + from, (uint32_t)(ends[t] - from), (uint32_t)t, k, w, words, mz, ws);
             from = ends[t] + 1;
         }
         std::stable_sort(mz.begin(), mz.end(), [](const Minimizer &a, const Minimizer &b) { return a.h < b.h; });
@@ -67,7 +80,7 @@ struct ReadCounts {
 inline void map_read(const HostIndex &ix, const uint8_t *s, uint32_t qlen, const Opts &o, Hit *hit, std::vector<uint32_t> *chain, ReadCounts *counts) {
     std::vector<uint64_t> words;
     std::vector<Minimizer> mz;
-    sketch_seq(s, qlen, 0, o.k, o.w, words, mz);
+    sketch_seq(s, qlen, 0, o.k, o.w, words, mz, ix.ws);
     std::vector<std::pair<uint64_t, uint64_t>> an; // (hi, lo)
     for (const Minimizer &m : mz) {
         auto lo = std::lower_bound(ix.mz.begin(), ix.mz.end(), m.h, [](const Minimizer &a, uint64_t h) { return a.h < h; });

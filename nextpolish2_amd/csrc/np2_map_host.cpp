@@ -4,6 +4,11 @@
 // (rocPRIM, np2_prims.hip) from (sequence, position) order.  The two sorted arrays stay in device memory behind the handle, and
 // so does the assembly's text for the aligner (one byte per base).  A lookup is two binary searches.
 //
+// Weights (np2_map_weights_*, the _w entries; the rule: np2_io.h, "Weights").  A weight set is host memory: the listed canonical
+// indices, ascending and unique.  An index built with one owns a bitmap of 4^k bits and its coarse level on the device, zeroed and
+// set on the build's stream before the assembly is sketched; the Sketcher of every later call against the index takes the two
+// pointers, so reads are sketched under the same weights with no new argument.  Null pointers select the unweighted launches.
+//
 // Reads.  A BATCH is consecutive whole reads, MAP_BATCH_PIECES pieces of bytes at the most (one read when a read is longer).
 // Its bytes go to the device PIECE by piece (8 MiB; NP2_MAP_TEST_PIECE) and each piece is sketched by launches of its own:
 // the count pass once every piece has arrived, one scan over all the batch's tiles, the emit pass.  A piece boundary may fall
@@ -94,12 +99,14 @@ struct Hooks {
     uint64_t budget = 1ull << 25;
     uint64_t align_budget = 1ull << 30; // traceback bytes of a sub-group
     uint32_t align_cells = 1u << 24;    // a cap on max_cells
+    bool coarse = true;                 // an index built with weights keeps the bitmap's coarse level
     Hooks() { // read once per call, like the other NP2_* switches
         piece = (size_t)np2h::test_hook("NP2_MAP_TEST_PIECE", 64, (long long)1 << 30, (long long)piece);
         piece = (piece + 15) & ~(size_t)15; // (tiles are staged with aligned 16-byte loads)
         budget = (uint64_t)np2h::test_hook("NP2_MAP_TEST_BUDGET", 1, (long long)1 << 28, (long long)budget);
         align_budget = (uint64_t)np2h::test_hook("NP2_ALIGN_TEST_BUDGET", 1, (long long)1 << 34, (long long)align_budget);
         align_cells = (uint32_t)np2h::test_hook("NP2_ALIGN_TEST_CELLS", 1, (long long)1 << 24, (long long)align_cells);
+        coarse = np2h::test_hook("NP2_MAP_TEST_COARSE", 0, 1, 1) != 0;
     }
     size_t batch_bytes() const { return piece * MAP_BATCH_PIECES; }
 };
@@ -150,6 +157,7 @@ struct Sketcher {
     DevBuf<uint32_t> d_ends, d_cnt, d_off;
     DevBuf<uint64_t> mz_h, mz_x;
     uint32_t n_mz = 0, pieces = 0;
+    const uint64_t *listed = nullptr, *coarse = nullptr; // the index's weight bitmap and its coarse level; null: the unweighted launches
     Sketcher() { d_seq.cached = d_ends.cached = d_cnt.cached = d_off.cached = mz_h.cached = mz_x.cached = true; }
 
     float run(Stream &s, const uint8_t *bytes, uint64_t n, const uint32_t *ends, uint32_t n_ends, size_t piece, uint32_t k, uint32_t w) {
@@ -173,7 +181,7 @@ struct Sketcher {
         uint32_t tile0 = 0;
         for (uint64_t base = 0; base < n; base += piece) {
             const uint64_t len = std::min<uint64_t>(piece, n - base);
-            launch_map_sketch_count(st, seq, n, base, len, k, w, tile0, d_cnt.p);
+            launch_map_sketch_count(st, seq, n, base, len, k, w, tile0, d_cnt.p, listed, coarse);
             tile0 += map_tiles(len);
         }
         if (prim_exclusive_sum_u32(st, s.tmp.p, tmp_bytes, d_cnt.p, d_off.p, (size_t)n_tiles + 1))
@@ -186,7 +194,7 @@ struct Sketcher {
         tile0 = 0;
         for (uint64_t base = 0; base < n; base += piece) {
             const uint64_t len = std::min<uint64_t>(piece, n - base);
-            launch_map_sketch_emit(st, seq, n, base, len, k, w, tile0, d_off.p, d_ends.p, n_ends, mz_h.p, mz_x.p);
+            launch_map_sketch_emit(st, seq, n, base, len, k, w, tile0, d_off.p, d_ends.p, n_ends, mz_h.p, mz_x.p, listed, coarse);
             tile0 += map_tiles(len);
         }
         ms += s.end();
@@ -202,6 +210,10 @@ uint32_t bits_for(uint64_t n) { // key bits that tell 0 .. n - 1 apart
 
 } // namespace
 
+struct np2_map_weights { // host memory only
+    np2map::WeightSet ws;
+};
+
 struct np2_map_index {
     int device = 0;
     uint32_t k = 0, w = 0, n = 0;
@@ -211,12 +223,47 @@ struct np2_map_index {
     std::vector<std::string> names;
     std::vector<uint64_t> lens;
     float build_ms = 0.f;
-    np2_map_index() { h.cached = x.cached = seq.cached = ends.cached = true; }
+    // the weights the index was built with (0, 0: none): one bit per canonical k-mer index, set for the listed ones; reads are
+    // sketched under it too
+    uint32_t weights_k = 0;
+    uint64_t n_listed = 0;
+    DevBuf<uint64_t> listed; // 4^k / 64 words, then (unless NP2_MAP_TEST_COARSE=0) the coarse level's 4^k / 4096
+    bool has_coarse = false;
+    np2_map_index() { h.cached = x.cached = seq.cached = ends.cached = listed.cached = true; }
+    const uint64_t *bitmap() const { return n_listed ? listed.p : nullptr; }
+    const uint64_t *coarse() const { return n_listed && has_coarse ? listed.p + np2::map_weight_words(weights_k) : nullptr; }
 };
 
 namespace {
 
-np2_map_index *build_index(int device, const uint8_t *stream, uint64_t n, std::vector<std::string> names, const np2map::Opts &o, const char *who) {
+// a non-empty weight set's k: the membership test is a direct-addressed bitmap of 4^k bits
+void check_weights_k(uint32_t k, const char *who) {
+    if (k < np2map::KW_MIN || k > np2map::KW_MAX)
+        throw Np2Error(NP2_E_UNSUPPORTED, std::string(who) + ": weights are built for 11 <= k <= 15, the list has k = " + std::to_string(k) +
+                                              " (16 <= k <= 28 would need more than a direct-addressed bitmap)");
+}
+uint64_t revcomp_index(uint64_t v, uint32_t k) {
+    uint64_t r = 0;
+    for (uint32_t i = 0; i < k; ++i) r = r << 2 | (3u - ((v >> (2u * i)) & 3u));
+    return r;
+}
+void seal_weights(np2map::WeightSet &ws, uint32_t k) { // ascending and unique
+    std::sort(ws.idx.begin(), ws.idx.end());
+    ws.idx.erase(std::unique(ws.idx.begin(), ws.idx.end()), ws.idx.end());
+    ws.k = k;
+}
+
+// the weights of a _w call: null for none or an empty set; a set of another k than the options' is NP2_E_ARG
+const np2map::WeightSet *checked_weights(const np2_map_weights_t *w, const np2map::Opts &o, const char *who) {
+    if (!w || w->ws.empty()) return nullptr;
+    if (w->ws.k != o.k)
+        throw Np2Error(NP2_E_ARG, std::string(who) + ": the weights list k-mers of length " + std::to_string(w->ws.k) + ", the options say k = " +
+                                      std::to_string(o.k) + " (an index built with weights needs k equal to the list's)");
+    return &w->ws;
+}
+
+np2_map_index *build_index(int device, const uint8_t *stream, uint64_t n, std::vector<std::string> names, const np2map::Opts &o, const char *who,
+                           const np2map::WeightSet *ws = nullptr) {
     const std::vector<uint64_t> e64 = ends_of(stream, n, who, "the assembly stream");
     if (n > MAP_MAX_STREAM) throw Np2Error(NP2_E_UNSUPPORTED, std::string(who) + ": an assembly of 2^32 bytes or more");
     if (e64.size() > np2map::MAX_TID) throw Np2Error(NP2_E_UNSUPPORTED, std::string(who) + ": more than 2^31 - 1 sequences");
@@ -233,7 +280,21 @@ np2_map_index *build_index(int device, const uint8_t *stream, uint64_t n, std::v
     const Hooks hooks;
     Stream s(device);
     Sketcher sk;
-    ix->build_ms = sk.run(s, stream, n, ends.data(), (uint32_t)ends.size(), hooks.piece, o.k, o.w);
+    DevBuf<uint32_t> d_idx;
+    d_idx.cached = true;
+    if (ws) { // the bitmap: zeroed here, never assumed zero, then one bit per listed index
+        const size_t fine = np2::map_weight_words(o.k), words = fine + (hooks.coarse ? np2::map_weight_coarse_words(o.k) : 0);
+        ix->listed.ensure(words), d_idx.ensure(ws->idx.size());
+        ix->has_coarse = hooks.coarse;
+        HIPCHK(hipMemcpyAsync(d_idx.p, ws->idx.data(), ws->idx.size() * 4, hipMemcpyHostToDevice, s.st));
+        s.begin();
+        HIPCHK(hipMemsetAsync(ix->listed.p, 0, words * 8, s.st));
+        np2::launch_map_weights_set(s.st, d_idx.p, ws->idx.size(), ix->listed.p, hooks.coarse ? ix->listed.p + fine : nullptr);
+        ix->build_ms = s.end();
+        ix->weights_k = ws->k, ix->n_listed = ws->idx.size();
+        sk.listed = ix->bitmap(), sk.coarse = ix->coarse();
+    }
+    ix->build_ms += sk.run(s, stream, n, ends.data(), (uint32_t)ends.size(), hooks.piece, o.k, o.w);
     ix->n = sk.n_mz;
     ix->seq.ensure(n + 64), ix->ends.ensure(ends.size() + 1);
     // (the sketcher holds both on the device already; its buffers go with it)
@@ -398,6 +459,7 @@ struct Mapper {
         d_end.cached = d_mark.cached = d_hits.cached = true;
         stats = np2_map_stats_t{};
         stats.index_minimizers = ix.n;
+        sk.listed = ix.bitmap(), sk.coarse = ix.coarse();
     }
 
     // reads as a stream of n bytes with n_reads separators at ends[]: hits[0 .. n_reads); with `chain`, the primary chains'
@@ -847,45 +909,157 @@ template <class Body> int from_reads_guard(np2_ctx *cx, bool &touched, Body &&bo
 
 extern "C" {
 
-int np2_map_index_bytes(int device, const uint8_t *stream, uint64_t n, const char *names, const np2_map_opts_t *opts, np2_map_index_t **out) {
+int np2_map_weights_from_indices(uint32_t k, const uint32_t *index, uint64_t n, np2_map_weights_t **out) {
     return np2h::abi_guard([&] {
-        // every argument is checked before the first device call
-        if (!out) throw Np2Error(NP2_E_ARG, "np2_map_index_bytes: out is NULL");
+        const char *who = "np2_map_weights_from_indices";
+        if (!out) throw Np2Error(NP2_E_ARG, std::string(who) + ": out is NULL");
         *out = nullptr;
-        const np2map::Opts o = checked(opts, "np2_map_index_bytes");
-        std::vector<std::string> nm;
-        if (names)
-            for (const char *p = names; *p;) {
-                const char *e = strchr(p, '\n');
-                if (!e) throw Np2Error(NP2_E_ARG, "np2_map_index_bytes: names does not end in a newline");
-                nm.emplace_back(p, e), p = e + 1;
+        if (n && !index) throw Np2Error(NP2_E_ARG, std::string(who) + ": index is NULL with a length");
+        if (n) check_weights_k(k, who);
+        std::unique_ptr<np2_map_weights> w(new np2_map_weights());
+        if (n) {
+            const uint64_t mask = np2map::kmer_mask(k);
+            for (uint64_t i = 0; i < n; ++i) {
+                const uint64_t v = index[i];
+                if (v > mask) throw Np2Error(NP2_E_ARG, std::string(who) + ": index[" + std::to_string(i) + "] = " + std::to_string(v) + " is beyond 4^k - 1");
+                if (revcomp_index(v, k) < v)
+                    throw Np2Error(NP2_E_ARG, std::string(who) + ": index[" + std::to_string(i) + "] = " + std::to_string(v) +
+                                                  " is not canonical (its reverse complement is smaller)");
             }
-        *out = build_index(device, stream, n, std::move(nm), o, "np2_map_index_bytes");
+            w->ws.idx.assign(index, index + n);
+            seal_weights(w->ws, k);
+        }
+        *out = w.release();
         return NP2_OK;
     }, np2h::io_set_error);
 }
 
-int np2_map_index_files(int device, const char *const *paths, int n_paths, const np2_map_opts_t *opts, np2_map_index_t **out) {
+int np2_map_weights_from_file(const char *path, np2_map_weights_t **out) {
     return np2h::abi_guard([&] {
-        if (!out) throw Np2Error(NP2_E_ARG, "np2_map_index_files: out is NULL");
+        const std::string who = "np2_map_weights_from_file";
+        if (!out) throw Np2Error(NP2_E_ARG, who + ": out is NULL");
         *out = nullptr;
-        const np2map::Opts o = checked(opts, "np2_map_index_files");
-        if (!paths || n_paths < 1) throw Np2Error(NP2_E_ARG, "np2_map_index_files: no assembly file given");
+        if (!path) throw Np2Error(NP2_E_ARG, who + ": path is NULL");
+        std::unique_ptr<np2_map_weights> w(new np2_map_weights());
+        // a line: KMER or KMER<TAB>anything, ended by \n or \r\n (a last line may go without)
+        uint64_t line_no = 1, fw = 0, rv = 0;
+        uint32_t len = 0, k = 0;
+        bool in_kmer = true, any = false; // any: the line has a byte
+        auto bad = [&](const std::string &what) { return Np2Error(NP2_E_ARG, who + ": " + path + ": line " + std::to_string(line_no) + ": " + what); };
+        auto end_line = [&] {
+            if (k == 0) {
+                if (len < 1 || len > 31) throw bad("a k-mer of 1 .. 31 letters is expected");
+                k = len;
+                check_weights_k(k, who.c_str());
+            } else if (len != k) {
+                throw bad("a k-mer of " + std::to_string(len) + " letters, the lines before have " + std::to_string(k));
+            }
+            w->ws.idx.push_back((uint32_t)std::min(fw, rv >> (62u - 2u * len)));
+            fw = rv = 0, len = 0, in_kmer = true, any = false, ++line_no;
+        };
+        np2seq::read_chunks(path, nullptr, [&](const uint8_t *p, size_t m) {
+            for (size_t i = 0; i < m; ++i) {
+                const uint8_t ch = p[i];
+                if (ch == '\n') {
+                    end_line();
+                    continue;
+                }
+                any = true;
+                if (!in_kmer) continue;
+                if (ch == '\t') {
+                    in_kmer = false;
+                    continue;
+                }
+                if (ch == '\r' && (i + 1 < m ? p[i + 1] == '\n' : true)) { // (a lone \r at a chunk's end is taken for a line end too)
+                    in_kmer = false;
+                    continue;
+                }
+                const uint32_t c = np2map::code(ch == 'U' || ch == 'u' ? (uint8_t)'T' : ch);
+                if (c >= 4u) throw bad("a letter that is not one of ACGTU");
+                if (++len > 31) throw bad("a k-mer of more than 31 letters");
+                fw = fw << 2 | c, rv = rv >> 2 | (uint64_t)(3u - c) << 60;
+            }
+        });
+        if (any) end_line();
+        if (!w->ws.idx.empty()) seal_weights(w->ws, k);
+        *out = w.release();
+        return NP2_OK;
+    }, np2h::io_set_error);
+}
+
+int np2_map_weights_info(const np2_map_weights_t *w, uint32_t *k, uint64_t *n_listed) {
+    if (!w) return np2h::io_set_error(NP2_E_ARG, "np2_map_weights_info: the weights are NULL");
+    if (k) *k = w->ws.k;
+    if (n_listed) *n_listed = w->ws.idx.size();
+    return NP2_OK;
+}
+
+void np2_map_weights_free(np2_map_weights_t *w) { delete w; }
+
+static int index_bytes_impl(int device, const uint8_t *stream, uint64_t n, const char *names, const np2_map_opts_t *opts, const np2_map_weights_t *w,
+                            np2_map_index_t **out, const std::string who) {
+    return np2h::abi_guard([&] {
+        // every argument is checked before the first device call
+        if (!out) throw Np2Error(NP2_E_ARG, who + ": out is NULL");
+        *out = nullptr;
+        const np2map::Opts o = checked(opts, who.c_str());
+        const np2map::WeightSet *ws = checked_weights(w, o, who.c_str());
+        std::vector<std::string> nm;
+        if (names)
+            for (const char *p = names; *p;) {
+                const char *e = strchr(p, '\n');
+                if (!e) throw Np2Error(NP2_E_ARG, who + ": names does not end in a newline");
+                nm.emplace_back(p, e), p = e + 1;
+            }
+        *out = build_index(device, stream, n, std::move(nm), o, who.c_str(), ws);
+        return NP2_OK;
+    }, np2h::io_set_error);
+}
+int np2_map_index_bytes(int device, const uint8_t *stream, uint64_t n, const char *names, const np2_map_opts_t *opts, np2_map_index_t **out) {
+    return index_bytes_impl(device, stream, n, names, opts, nullptr, out, "np2_map_index_bytes");
+}
+int np2_map_index_bytes_w(int device, const uint8_t *stream, uint64_t n, const char *names, const np2_map_opts_t *opts, const np2_map_weights_t *w,
+                          np2_map_index_t **out) {
+    return index_bytes_impl(device, stream, n, names, opts, w, out, "np2_map_index_bytes_w");
+}
+
+static int index_files_impl(int device, const char *const *paths, int n_paths, const np2_map_opts_t *opts, const np2_map_weights_t *w,
+                            np2_map_index_t **out, const std::string who) {
+    return np2h::abi_guard([&] {
+        if (!out) throw Np2Error(NP2_E_ARG, who + ": out is NULL");
+        *out = nullptr;
+        const np2map::Opts o = checked(opts, who.c_str());
+        const np2map::WeightSet *ws = checked_weights(w, o, who.c_str());
+        if (!paths || n_paths < 1) throw Np2Error(NP2_E_ARG, who + ": no assembly file given");
         for (int i = 0; i < n_paths; ++i)
-            if (!paths[i]) throw Np2Error(NP2_E_ARG, "np2_map_index_files: an assembly file path is NULL");
+            if (!paths[i]) throw Np2Error(NP2_E_ARG, who + ": an assembly file path is NULL");
         std::vector<uint8_t> stream;
         std::vector<std::string> names;
         for (int i = 0; i < n_paths; ++i) {
             np2seq::NameCollector nc;
             np2seq::parse_file(paths[i], [&](const uint8_t *p, size_t m) {
                 if (m == 1 && *p == SEP) names.push_back(nc.close());
-                if (stream.size() + m > MAP_MAX_STREAM) throw Np2Error(NP2_E_UNSUPPORTED, "np2_map_index_files: an assembly of 2^32 bytes or more");
+                if (stream.size() + m > MAP_MAX_STREAM) throw Np2Error(NP2_E_UNSUPPORTED, who + ": an assembly of 2^32 bytes or more");
                 stream.insert(stream.end(), p, p + m);
             }, nullptr, [&](const uint8_t *p, size_t m, bool begin) { nc(p, m, begin); });
         }
-        *out = build_index(device, stream.data(), stream.size(), std::move(names), o, "np2_map_index_files");
+        *out = build_index(device, stream.data(), stream.size(), std::move(names), o, who.c_str(), ws);
         return NP2_OK;
     }, np2h::io_set_error);
+}
+int np2_map_index_files(int device, const char *const *paths, int n_paths, const np2_map_opts_t *opts, np2_map_index_t **out) {
+    return index_files_impl(device, paths, n_paths, opts, nullptr, out, "np2_map_index_files");
+}
+int np2_map_index_files_w(int device, const char *const *paths, int n_paths, const np2_map_opts_t *opts, const np2_map_weights_t *w,
+                          np2_map_index_t **out) {
+    return index_files_impl(device, paths, n_paths, opts, w, out, "np2_map_index_files_w");
+}
+
+int np2_map_index_weights(const np2_map_index_t *ix, uint32_t *k, uint64_t *n_listed) {
+    if (!ix) return np2h::io_set_error(NP2_E_ARG, "np2_map_index_weights: the index is NULL");
+    if (k) *k = ix->weights_k;
+    if (n_listed) *n_listed = ix->n_listed;
+    return NP2_OK;
 }
 
 void np2_map_index_free(np2_map_index_t *ix) {
@@ -956,19 +1130,21 @@ int np2_map_align_files(const np2_map_index_t *ix, const char *const *paths, int
     return map_files_impl(ix, paths, n_paths, map_opts, align_opts, true, out_path, stats, "np2_map_align_files");
 }
 
-int np2_map_host(const uint8_t *asm_stream, uint64_t n_asm, const uint8_t *reads, uint64_t n, uint64_t n_reads, const np2_map_opts_t *opts,
-                 np2_map_hit_t *hits, uint32_t **chain, uint64_t *chain_off) {
+static int map_host_impl(const uint8_t *asm_stream, uint64_t n_asm, const uint8_t *reads, uint64_t n, uint64_t n_reads, const np2_map_opts_t *opts,
+                         const np2_map_weights_t *w, np2_map_hit_t *hits, uint32_t **chain, uint64_t *chain_off, const std::string name) {
     return np2h::abi_guard([&] {
+        const char *who = name.c_str();
         if (chain) *chain = nullptr;
-        const np2map::Opts o = checked(opts, "np2_map_host");
-        if (n_reads && !hits) throw Np2Error(NP2_E_ARG, "np2_map_host: hits is NULL");
-        if ((chain == nullptr) != (chain_off == nullptr)) throw Np2Error(NP2_E_ARG, "np2_map_host: chain and chain_off go together");
-        const std::vector<uint64_t> a_ends = ends_of(asm_stream, n_asm, "np2_map_host", "the assembly stream");
-        const std::vector<uint64_t> ends = ends_of(reads, n, "np2_map_host", "the read stream");
+        const np2map::Opts o = checked(opts, who);
+        const np2map::WeightSet *ws = checked_weights(w, o, who);
+        if (n_reads && !hits) throw Np2Error(NP2_E_ARG, name + ": hits is NULL");
+        if ((chain == nullptr) != (chain_off == nullptr)) throw Np2Error(NP2_E_ARG, name + ": chain and chain_off go together");
+        const std::vector<uint64_t> a_ends = ends_of(asm_stream, n_asm, who, "the assembly stream");
+        const std::vector<uint64_t> ends = ends_of(reads, n, who, "the read stream");
         if (ends.size() != n_reads)
-            throw Np2Error(NP2_E_ARG, "np2_map_host: n_reads is " + std::to_string(n_reads) + ", the stream holds " + std::to_string(ends.size()) + " newlines");
+            throw Np2Error(NP2_E_ARG, name + ": n_reads is " + std::to_string(n_reads) + ", the stream holds " + std::to_string(ends.size()) + " newlines");
         np2map::HostIndex hx;
-        hx.build(asm_stream, a_ends, o.k, o.w);
+        hx.build(asm_stream, a_ends, o.k, o.w, ws);
         np2_map_stats_t &st = tl_stats;
         st = np2_map_stats_t{};
         st.index_minimizers = hx.mz.size();
@@ -989,6 +1165,14 @@ int np2_map_host(const uint8_t *asm_stream, uint64_t n_asm, const uint8_t *reads
         }
         return NP2_OK;
     }, np2h::io_set_error);
+}
+int np2_map_host(const uint8_t *asm_stream, uint64_t n_asm, const uint8_t *reads, uint64_t n, uint64_t n_reads, const np2_map_opts_t *opts,
+                 np2_map_hit_t *hits, uint32_t **chain, uint64_t *chain_off) {
+    return map_host_impl(asm_stream, n_asm, reads, n, n_reads, opts, nullptr, hits, chain, chain_off, "np2_map_host");
+}
+int np2_map_host_w(const uint8_t *asm_stream, uint64_t n_asm, const uint8_t *reads, uint64_t n, uint64_t n_reads, const np2_map_opts_t *opts,
+                   const np2_map_weights_t *w, np2_map_hit_t *hits, uint32_t **chain, uint64_t *chain_off) {
+    return map_host_impl(asm_stream, n_asm, reads, n, n_reads, opts, w, hits, chain, chain_off, "np2_map_host_w");
 }
 
 int np2_map_align_bytes(const np2_map_index_t *ix, const uint8_t *reads, uint64_t n, uint64_t n_reads, const np2_map_opts_t *map_opts,
@@ -1028,23 +1212,25 @@ int np2_map_align_bytes(const np2_map_index_t *ix, const uint8_t *reads, uint64_
     }, np2h::io_set_error);
 }
 
-int np2_map_align_host(const uint8_t *asm_stream, uint64_t n_asm, const uint8_t *reads, uint64_t n, uint64_t n_reads,
-                       const np2_map_opts_t *map_opts, const np2_align_opts_t *align_opts, np2_map_hit_t *hits, np2_align_rec_t *recs,
-                       uint32_t **cigar, uint64_t *cigar_off) {
+static int map_align_host_impl(const uint8_t *asm_stream, uint64_t n_asm, const uint8_t *reads, uint64_t n, uint64_t n_reads,
+                               const np2_map_opts_t *map_opts, const np2_align_opts_t *align_opts, const np2_map_weights_t *wts, np2_map_hit_t *hits,
+                               np2_align_rec_t *recs, uint32_t **cigar, uint64_t *cigar_off, const std::string name) {
     return np2h::abi_guard([&] {
+        const char *who = name.c_str();
         if (cigar) *cigar = nullptr;
-        const np2map::Opts o = checked(map_opts, "np2_map_align_host");
-        np2aln::Opts ao = checked_align(align_opts, "np2_map_align_host");
-        if (n_reads && !recs) throw Np2Error(NP2_E_ARG, "np2_map_align_host: recs is NULL");
-        if ((cigar == nullptr) != (cigar_off == nullptr)) throw Np2Error(NP2_E_ARG, "np2_map_align_host: cigar and cigar_off go together");
-        const std::vector<uint64_t> a_ends = ends_of(asm_stream, n_asm, "np2_map_align_host", "the assembly stream");
-        const std::vector<uint64_t> ends = ends_of(reads, n, "np2_map_align_host", "the read stream");
+        const np2map::Opts o = checked(map_opts, who);
+        np2aln::Opts ao = checked_align(align_opts, who);
+        const np2map::WeightSet *ws = checked_weights(wts, o, who);
+        if (n_reads && !recs) throw Np2Error(NP2_E_ARG, name + ": recs is NULL");
+        if ((cigar == nullptr) != (cigar_off == nullptr)) throw Np2Error(NP2_E_ARG, name + ": cigar and cigar_off go together");
+        const std::vector<uint64_t> a_ends = ends_of(asm_stream, n_asm, who, "the assembly stream");
+        const std::vector<uint64_t> ends = ends_of(reads, n, who, "the read stream");
         if (ends.size() != n_reads)
-            throw Np2Error(NP2_E_ARG, "np2_map_align_host: n_reads is " + std::to_string(n_reads) + ", the stream holds " + std::to_string(ends.size()) + " newlines");
+            throw Np2Error(NP2_E_ARG, name + ": n_reads is " + std::to_string(n_reads) + ", the stream holds " + std::to_string(ends.size()) + " newlines");
         const Hooks hooks;
         if (ao.max_cells > hooks.align_cells) ao.max_cells = hooks.align_cells;
         np2map::HostIndex hx;
-        hx.build(asm_stream, a_ends, o.k, o.w);
+        hx.build(asm_stream, a_ends, o.k, o.w, ws);
         np2_map_stats_t &st = tl_stats;
         st = np2_map_stats_t{};
         st.index_minimizers = hx.mz.size();
@@ -1080,6 +1266,18 @@ int np2_map_align_host(const uint8_t *asm_stream, uint64_t n_asm, const uint8_t 
         }
         return NP2_OK;
     }, np2h::io_set_error);
+}
+int np2_map_align_host(const uint8_t *asm_stream, uint64_t n_asm, const uint8_t *reads, uint64_t n, uint64_t n_reads,
+                       const np2_map_opts_t *map_opts, const np2_align_opts_t *align_opts, np2_map_hit_t *hits, np2_align_rec_t *recs,
+                       uint32_t **cigar, uint64_t *cigar_off) {
+    return map_align_host_impl(asm_stream, n_asm, reads, n, n_reads, map_opts, align_opts, nullptr, hits, recs, cigar, cigar_off,
+                               "np2_map_align_host");
+}
+int np2_map_align_host_w(const uint8_t *asm_stream, uint64_t n_asm, const uint8_t *reads, uint64_t n, uint64_t n_reads,
+                         const np2_map_opts_t *map_opts, const np2_align_opts_t *align_opts, const np2_map_weights_t *w, np2_map_hit_t *hits,
+                         np2_align_rec_t *recs, uint32_t **cigar, uint64_t *cigar_off) {
+    return map_align_host_impl(asm_stream, n_asm, reads, n, n_reads, map_opts, align_opts, w, hits, recs, cigar, cigar_off,
+                               "np2_map_align_host_w");
 }
 
 int np2_sam_from_reads(np2_ctx_t *cx, const np2_map_index_t *ix, const char *const *paths, int n_paths, const np2_map_opts_t *map_opts,

@@ -344,11 +344,21 @@ def _bind_map(L):
     L.np2_map_files.argtypes = [vp, C.POINTER(C.c_char_p), C.c_int, mo, C.c_char_p, C.POINTER(np2_map_stats_t)]
     L.np2_map_host.argtypes = [vp, u64, vp, u64, u64, mo, vp, C.POINTER(vp), vp]
     L.np2_map_last_stats.argtypes = [C.POINTER(np2_map_stats_t)]
+    L.np2_map_weights_from_indices.argtypes = [C.c_uint32, vp, u64, C.POINTER(vp)]
+    L.np2_map_weights_from_file.argtypes = [C.c_char_p, C.POINTER(vp)]
+    L.np2_map_weights_info.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(u64)]
+    L.np2_map_weights_free.argtypes = [vp]
+    L.np2_map_weights_free.restype = None
+    L.np2_map_index_bytes_w.argtypes = [C.c_int, vp, u64, C.c_char_p, mo, vp, C.POINTER(vp)]
+    L.np2_map_index_files_w.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.c_int, mo, vp, C.POINTER(vp)]
+    L.np2_map_index_weights.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(u64)]
+    L.np2_map_host_w.argtypes = [vp, u64, vp, u64, u64, mo, vp, vp, C.POINTER(vp), vp]
     ao = C.POINTER(np2_align_opts_t)
     L.np2_map_align_bytes.argtypes = [vp, vp, u64, u64, mo, ao, vp, vp, C.POINTER(vp), vp]
     L.np2_map_align_files.argtypes = [vp, C.POINTER(C.c_char_p), C.c_int, mo, ao, C.c_char_p, C.POINTER(np2_map_stats_t)]
     L.np2_map_align_host.argtypes = [vp, u64, vp, u64, u64, mo, ao, vp, vp, C.POINTER(vp), vp]
     L.np2_map_align_last_stats.argtypes = [C.POINTER(np2_align_stats_t)]
+    L.np2_map_align_host_w.argtypes = [vp, u64, vp, u64, u64, mo, ao, vp, vp, vp, C.POINTER(vp), vp]
     so, pvp = C.POINTER(np2_sam_opts_t), C.POINTER(vp)
     L.np2_sam_from_reads.argtypes = [vp, vp, C.POINTER(C.c_char_p), C.c_int, mo, ao, so, C.c_uint32, pvp]
     L.np2_sam_from_read_bytes.argtypes = [vp, vp, vp, u64, u64, C.c_char_p, mo, ao, so, C.c_uint32, pvp]
@@ -1391,21 +1401,98 @@ def _map_result(L, call, s, n, want_chains):
     return hits, chain, off
 
 
+class MapWeights:
+    """A weight set of the mapper (np2_map_weights_*; winnowmap -W): the repetitive k-mers that are made less likely to win a
+    minimizer window.  `source`: a list file (one k-mer a line, as python -m nextpolish2_amd.repkmers writes it; plain or
+    gzip), or canonical k-mer indices (api.rep_bytes' `index`) with their `k`.  Host memory only; `.k` (0: the empty set) and
+    `.n_listed`.  A context manager."""
+
+    def __init__(self, source, k=None):
+        L = _bind()
+        self._L, self._h = L, C.c_void_p()
+        if isinstance(source, (str, bytes, os.PathLike)):
+            if k is not None:
+                raise TypeError("k is the list file's own: it is given with indices only")
+            _io_check(L.np2_map_weights_from_file(os.fsencode(source), C.byref(self._h)))
+        else:
+            if k is None:
+                raise TypeError("indices need their k")
+            v = np.asarray(source)
+            if v.size and (v.min() < 0 or v.max() > 0xFFFFFFFF):
+                raise ValueError("an index is 0 .. 2^32 - 1")
+            v = np.ascontiguousarray(v, np.uint32)
+            _io_check(L.np2_map_weights_from_indices(int(k), v.ctypes.data if len(v) else None, len(v), C.byref(self._h)))
+        k_, n_ = C.c_uint32(), C.c_uint64()
+        _io_check(L.np2_map_weights_info(self._h, C.byref(k_), C.byref(n_)))
+        self.k, self.n_listed = k_.value, n_.value
+
+    @classmethod
+    def from_assembly(cls, asm, k=15, distinct=0.9998, min_count=None, device=0):
+        """the assembly's own repetitive k-mers, counted on `device` with repkmers' rule (api.rep_bytes).  asm: a FASTA path or
+        a list of paths, or a separator stream (bytes) / a list of sequences in memory"""
+        from . import api
+        if isinstance(asm, (str, os.PathLike)):
+            asm = [asm]
+        if isinstance(asm, (list, tuple)) and asm and all(isinstance(x, (str, os.PathLike)) for x in asm):
+            stream = b"".join(bytes(seqfile_stream(p)) for p in asm)
+        else:
+            stream = bytes(_stream_of(asm)[0])
+        index, _, _ = api.rep_bytes(stream, k=k, distinct=distinct, min_count=min_count, device=device)
+        return cls(index, k=k)
+
+    def close(self):
+        if self._h:
+            self._L.np2_map_weights_free(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _weights_handle(weights):
+    if weights is None:
+        return None
+    if not isinstance(weights, MapWeights):
+        raise TypeError("weights: a MapWeights is expected")
+    return weights._h
+
+
 class MapIndex:
     """An assembly's minimizer index, resident on `device` (np2_map_index_*).  `asm`: a FASTA path or a list of paths, or
-    (with stream=True) a separator stream / a list of sequences in memory, with `names` or numbered from 1."""
+    (with stream=True) a separator stream / a list of sequences in memory, with `names` or numbered from 1.  `weights`: a
+    MapWeights; the index copies what it needs and sketches the assembly and every read under it (`.weights_k`,
+    `.weights_listed`; 0, 0 without)."""
 
-    def __init__(self, asm, k=19, w=19, device=0, stream=False, names=None):
+    def __init__(self, asm, k=19, w=19, device=0, stream=False, names=None, weights=None):
         L = _bind()
         self._L, self._h = L, C.c_void_p()
         o = map_opts(k=k, w=w)
+        wh = _weights_handle(weights)
         if stream:
             s, n = _stream_of(asm)
             nm = None if names is None else "".join(x + "\n" for x in names).encode()
-            _io_check(L.np2_map_index_bytes(device, s.ctypes.data if len(s) else None, len(s), nm, C.byref(o), C.byref(self._h)))
+            if wh is None:
+                _io_check(L.np2_map_index_bytes(device, s.ctypes.data if len(s) else None, len(s), nm, C.byref(o), C.byref(self._h)))
+            else:
+                _io_check(L.np2_map_index_bytes_w(device, s.ctypes.data if len(s) else None, len(s), nm, C.byref(o), wh, C.byref(self._h)))
         else:
             arr, n = _paths(asm)
-            _io_check(L.np2_map_index_files(device, arr, n, C.byref(o), C.byref(self._h)))
+            if wh is None:
+                _io_check(L.np2_map_index_files(device, arr, n, C.byref(o), C.byref(self._h)))
+            else:
+                _io_check(L.np2_map_index_files_w(device, arr, n, C.byref(o), wh, C.byref(self._h)))
+        wk, wn = C.c_uint32(), C.c_uint64()
+        _io_check(L.np2_map_index_weights(self._h, C.byref(wk), C.byref(wn)))
+        self.weights_k, self.weights_listed = wk.value, wn.value
         k_, w_, ns, nm_, ms = C.c_uint32(), C.c_uint32(), C.c_uint64(), C.c_uint64(), C.c_float()
         _io_check(L.np2_map_index_info(self._h, C.byref(k_), C.byref(w_), C.byref(ns), C.byref(nm_), C.byref(ms)))
         self.k, self.w, self.n_minimizers, self.build_ms, self.device = k_.value, w_.value, nm_.value, ms.value, device
@@ -1470,14 +1557,19 @@ def map_files(index, paths, out_path, **kw):
     return _map_stats_dict(st)
 
 
-def map_host(asm, reads, chains=False, **kw):
-    """np2_map_host (no device): the same rule on the CPU -> what map_reads returns"""
+def map_host(asm, reads, chains=False, weights=None, **kw):
+    """np2_map_host / np2_map_host_w (no device): the same rule on the CPU -> what map_reads returns.  weights: a MapWeights"""
     L = _bind()
     a, _ = _stream_of(asm)
     s, n = _stream_of(reads)
     o = map_opts(**kw)
-    hits, chain, off = _map_result(L, lambda *x: L.np2_map_host(a.ctypes.data if len(a) else None, len(a), x[0], x[1], x[2], C.byref(o), x[3],
-                                                                 x[4], x[5]), s, n, chains)
+    wh = _weights_handle(weights)
+    ap = a.ctypes.data if len(a) else None
+    if wh is None:
+        call = lambda *x: L.np2_map_host(ap, len(a), x[0], x[1], x[2], C.byref(o), x[3], x[4], x[5])
+    else:
+        call = lambda *x: L.np2_map_host_w(ap, len(a), x[0], x[1], x[2], C.byref(o), wh, x[3], x[4], x[5])
+    hits, chain, off = _map_result(L, call, s, n, chains)
     return (hits, chain, off) if chains else hits
 
 
@@ -1546,12 +1638,16 @@ def align_pack_host(recs, cigar, cigar_off, reads, tie="strand"):
     return _sam_arrays(L, pr, pt, pc, ps, m.value, sizes)
 
 
-def map_align_host(asm, reads, **kw):
-    """np2_map_align_host (no device): the same rule on the CPU -> what MapIndex.align returns"""
+def map_align_host(asm, reads, weights=None, **kw):
+    """np2_map_align_host / np2_map_align_host_w (no device): the same rule on the CPU -> what MapIndex.align returns"""
     L = _bind()
     a, _ = _stream_of(asm)
     s, n = _stream_of(reads)
     akw = {f: kw.pop(f) for f in list(kw) if f in ALIGN_DEFAULTS}
     o, ao = map_opts(**kw), align_opts(**akw)
+    wh = _weights_handle(weights)
+    if wh is not None:
+        return _align_result(L, lambda *x: L.np2_map_align_host_w(a.ctypes.data if len(a) else None, len(a), x[0], x[1], x[2], C.byref(o),
+                                                                  C.byref(ao), wh, x[3], x[4], x[5], x[6]), s, n)
     return _align_result(L, lambda *x: L.np2_map_align_host(a.ctypes.data if len(a) else None, len(a), x[0], x[1], x[2], C.byref(o), C.byref(ao),
                                                             x[3], x[4], x[5], x[6]), s, n)

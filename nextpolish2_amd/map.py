@@ -4,6 +4,7 @@ by base and written as SAM (the recipe's `winnowmap -ax` step; its SAM pipes int
     python -m nextpolish2_amd.map asm.fa[.gz] hifi.fa[.gz] [more reads ...] [-o map.paf[.gz]] [-k 19] [-w 19] [--max_occ 200]
                                   [--lookback 64] [--max_gap 10000] [--bandwidth 500] [--min_cnt 3] [--min_score 40] [--stats FILE]
                                   [-a [-A 1] [-B 4] [-O 6] [-E 2] [--band 32] [--end_bonus 5] [--ext_max 2048] [--max_cells N]]
+                                  [-W repetitive_k15.txt | --rep [distinct=0.9998 | min_count=N]]
 
 One line per mapped read, in read order: qname qlen qs qe strand tname tlen ts te matches block mapq tp:A:P cm:i: s1:i: s2:i:
 (the rule: include/np2_io.h, np2_map_*; it follows minimap2's published seed-and-chain algorithm and is not pinned against
@@ -12,6 +13,11 @@ the minimap2 binary).  An output path ending in .gz / .bgz is written as BGZF, c
 With -a: a SAM header and one line per read, in read order: qname flag rname pos mapq CIGAR * 0 0 SEQ * NM:i: AS:i: cm:i: s1:i:
 s2:i: (the rule: np2_map_align_*; M, I, D and S only, gaps left-aligned; an unmapped read has flag 4).  --stats then writes a
 second header and row, ALIGN_STATS_HEADER.
+
+With -W FILE (winnowmap's -W): the k-mers of the list (one a line, as python -m nextpolish2_amd.repkmers or meryl print
+writes it; plain or gzip) are made less likely to win a minimizer window, so that the unique k-mers inside repeats become
+the seeds (the rule: np2_map_*, "Weights"; 11 <= k <= 15).  --rep counts the assembly's own repetitive k-mers in this process
+with repkmers' rule instead, and no list file is written.  With either and no -k, k is the list's (15 for --rep).
 """
 import argparse
 import os
@@ -23,12 +29,56 @@ STATS_HEADER = ("reads", "mapped", "unmapped", "minimizers", "anchors", "dropped
                 "sketch_ms", "seed_ms", "sort_ms", "chain_ms", "read_ms", "write_ms")
 
 
-def stats_row(stats, index_ms):
-    """--stats: a header line and one TSV row (counts, then times in ms with three decimals)"""
+WEIGHTS_HEADER = ("weights_k", "weights_listed")
+
+
+def stats_row(stats, index_ms, weights=None):
+    """--stats: a header line and one TSV row (counts, then times in ms with three decimals); with `weights` (k, listed) the
+    columns WEIGHTS_HEADER behind them, as the command line writes it (0, 0 for an unweighted run)"""
     st = dict(stats, index_ms=index_ms)
     cells = [str(int(st[f])) for f in STATS_HEADER[:9]] + ["%.3f" % float(st[f]) for f in STATS_HEADER[9:]]
-    return "\t".join(STATS_HEADER) + "\n" + "\t".join(cells) + "\n"
+    head = STATS_HEADER
+    if weights is not None:
+        head, cells = head + WEIGHTS_HEADER, cells + [str(int(weights[0])), str(int(weights[1]))]
+    return "\t".join(head) + "\n" + "\t".join(cells) + "\n"
 
+
+def rep_arg(text):
+    """argparse type of --rep [distinct=F | min_count=N] -> the keywords of api.rep_bytes"""
+    key, eq, val = text.partition("=")
+    try:
+        if key == "distinct" and eq:
+            f = float(val)
+            if 0.0 <= f <= 1.0:
+                return dict(distinct=f)
+        elif key == "min_count" and eq and val.isdigit() and int(val) <= 0xFFFFFFFF:
+            return dict(min_count=int(val))
+    except ValueError:
+        pass
+    raise argparse.ArgumentTypeError(f"{text!r}: distinct=F with 0 <= F <= 1, or min_count=N, is expected")
+
+
+def list_k(path):
+    """the length of a list file's first k-mer (plain or gzip; 0 for an empty file), read without the library so that a -k that
+    contradicts it is refused first; the library checks every line"""
+    import gzip
+    with open(path, "rb") as f:
+        gz = f.read(2) == b"\x1f\x8b"
+    with (gzip.open if gz else open)(path, "rb") as f:
+        line = f.readline()
+    return len(line.split(b"\t", 1)[0].rstrip(b"\r\n"))
+
+
+def resolve_k(k, weights_k, default, flag="-k "):
+    """-k beside a weight list of k-mer length weights_k (0: none or empty) -> (k, error text or None)"""
+    if k is None:
+        return (weights_k or default), None
+    if weights_k and k != weights_k:
+        return k, f"{flag}{k} contradicts the weight list, whose k-mers have {weights_k} letters (leave it out: k is the list's)"
+    return k, None
+
+
+REP_K = 15  # --rep without -k: the recipe's meryl k
 
 ALIGN_STATS_HEADER = ("pins", "segments", "equal", "pure_gap", "snv", "cores", "cells", "clipped_bases", "overflow", "pins_ms",
                       "classify_ms", "dp_ms", "assemble_ms", "write_ms")
@@ -48,7 +98,7 @@ def build_parser():
     p = argparse.ArgumentParser(prog="nextpolish2_amd.map", description="map long reads to an assembly: minimizer seeds and chains to PAF")
     p.add_argument("asm", metavar="asm.fa[.gz]", help="assembly in [GZIP] FASTA format")
     p.add_argument("reads", nargs="+", metavar="hifi.fa[.gz]", help="reads in [GZIP] FASTA / FASTQ format")
-    p.add_argument("-k", type=int, default=D["k"], metavar="K", help="k-mer size, 11 .. 28 [19]")
+    p.add_argument("-k", type=int, default=None, metavar="K", help="k-mer size, 11 .. 28 [19; with -W the list's; with --rep 15]")
     p.add_argument("-w", type=int, default=D["w"], metavar="W", help="minimizer window, 1 .. 64 [19]")
     p.add_argument("--max_occ", type=int, default=D["max_occ"], metavar="N", help="drop minimizers that occur more often in the assembly [200]")
     p.add_argument("--lookback", type=int, default=D["lookback"], metavar="N", help="chain predecessors tried per anchor, 1 .. 64 [64]")
@@ -65,6 +115,11 @@ def build_parser():
                  ext_max="read bases an end extension considers", max_cells="largest matrix; a read beyond it is written unmapped")
     for f, flag in ALIGN_FLAGS:
         p.add_argument(flag, dest=f, type=int, default=AD[f], metavar="N", help=f"with -a: {helps[f]} [{AD[f]}]")
+    g = p.add_mutually_exclusive_group()
+    g.add_argument("-W", dest="weights", default=None, metavar="FILE",
+                   help="down-weight the k-mers of this list in minimizer sampling (winnowmap -W; one k-mer a line, [GZIP]; 11 <= k <= 15)")
+    g.add_argument("--rep", nargs="?", const=dict(distinct=0.9998), default=None, type=rep_arg, metavar="distinct=F|min_count=N",
+                   help="down-weight the assembly's own repetitive k-mers, counted here with repkmers' rule [distinct=0.9998]")
     return p
 
 
@@ -72,6 +127,17 @@ def main(argv=None):
     from . import api
     from . import io as np2io
     a = build_parser().parse_args(argv)
+    wk = 0
+    if a.weights is not None:
+        try:
+            wk = list_k(a.weights)
+        except OSError as e:
+            raise SystemExit(f"Error: -W: {e}")
+    elif a.rep is not None:
+        wk = REP_K if a.k is None else a.k  # (the k-mers are counted at the k that is mapped with)
+    a.k, bad = resolve_k(a.k, wk, np2io.MAP_DEFAULTS["k"])
+    if bad:
+        raise SystemExit(f"Error: {bad}")
     kw = {f: getattr(a, f) for f in np2io.MAP_DEFAULTS}
     for f, v in kw.items():
         if not 0 <= v <= 0xFFFFFFFF:
@@ -90,14 +156,21 @@ def main(argv=None):
             out = tmp
         try:
             np2io.map_opts(k=k, w=w, **kw)
-            with np2io.MapIndex(a.asm, k=k, w=w, device=a.device) as ix:
+            weights = None
+            if a.weights is not None:
+                weights = np2io.MapWeights(a.weights)
+            elif a.rep is not None:
+                weights = np2io.MapWeights.from_assembly(a.asm, k=k, device=a.device, **a.rep)
+            with np2io.MapIndex(a.asm, k=k, w=w, device=a.device, weights=weights) as ix:
+                if weights is not None:
+                    weights.close()
                 if a.sam:
                     np2io.align_opts(**akw)
                     stats = np2io.map_align_files(ix, a.reads, out, **kw, **akw)
                     align_stats = np2io.align_last_stats()
                 else:
                     stats = np2io.map_files(ix, a.reads, out, **kw)
-                index_ms = ix.build_ms
+                index_ms, wstats = ix.build_ms, (ix.weights_k, ix.weights_listed)
         except (api.Np2Error, ImportError) as e:
             raise SystemExit(f"Error: {e}")
         if tmp is not None:
@@ -106,7 +179,7 @@ def main(argv=None):
             sys.stdout.flush()
         if a.stats is not None:
             with open(a.stats, "w") as f:
-                f.write(stats_row(stats, index_ms))
+                f.write(stats_row(stats, index_ms, wstats))
                 if a.sam:
                     f.write(align_stats_row(align_stats))
     finally:
