@@ -579,9 +579,10 @@ int np2_map_host_w(const uint8_t *asm_stream, uint64_t n_asm, const uint8_t *rea
  *     matches count as matches).  An unmapped or overflowed read has tid -1, flag 4 and no CIGAR.
  *   SAM.  @HD VN:1.6 SO:unsorted, one @SQ SN: LN: per sequence in index order, one @PG; then one line per read in read order:
  *     qname flag rname pos+1 mapq CIGAR * 0 0 SEQ * NM:i: AS:i: cm:i: s1:i: s2:i: (SEQ reverse-complemented with flag 16: ACGT
- *     in their case, any other byte kept), or qname 4 * 0 0 * * 0 0 SEQ * for an unmapped or overflowed read.  QUAL is always *.
- *   Not built: the second affine piece (-O26 -E1); z-drop and supplementary records; = / X ops; MD; base qualities; direct BAM
- *     output.  (The records reach the polisher without SAM text through np2_sam_from_reads, below.)
+ *     in their case, any other byte kept), or qname 4 * 0 0 * * 0 0 SEQ * for an unmapped or overflowed read.  QUAL is * unless
+ *     NP2_ALN_QUAL asks for it (Tags, below).
+ *   Not built: the second affine piece (-O26 -E1); z-drop and supplementary records; direct BAM output.  (The records reach the
+ *     polisher without SAM text through np2_sam_from_reads, below.)
  * The index keeps the assembly's bytes on the device for this (one byte per assembly base more than the minimizers).  Traceback
  * bits take one byte per matrix cell in a device buffer budgeted per group of whole reads (2^30 bytes; test hook
  * NP2_ALIGN_TEST_BUDGET, bytes); NP2_ALIGN_TEST_CELLS lowers max_cells.  Both are read once per call.  np2_map_stats_t.groups
@@ -618,6 +619,76 @@ int np2_map_align_host_w(const uint8_t *asm_stream, uint64_t n_asm, const uint8_
                          np2_align_rec_t *recs, uint32_t **cigar, uint64_t *cigar_off);
 /* the alignment counts and stage times of the last np2_map_align_* call on this thread */
 int np2_map_align_last_stats(np2_align_stats_t *stats);
+
+/* ---- Tags: base qualities, MD, cs and = / X, the aligner's opt-in outputs (what a variant caller or a genome browser reads from
+ * the BAM that samsort --full makes of the mapper's SAM) ------------------------------------------------------------------------
+ * THE RULE IS DEFINED HERE, on the SAM specification (SAMv1 section 1.4, SAMtags MD) and minimap2's documented short cs form;
+ * no minimap2 / samtools binary at hand, equality not claimed.  Its arithmetic: csrc/np2_aligntags_core.hpp, shared by the
+ * kernels (csrc/np2_aligntags.hip: k_align_tags_size, scans, k_align_tags_emit, one wavefront per read, launched per sub-group
+ * right behind k_align_ops_emit and only when a flag asks), the host twin and a stand-alone program.  Each output is off by
+ * default (out_flags, a sum of NP2_ALN_*); with none every entry point launches what it launched before and writes the same
+ * bytes.
+ *   The walk is over a read's final CIGAR, after left-alignment and clip handling, from rec.pos.  t: the assembly's bytes from
+ *     pos on.  q: the read as aligned, its reverse complement for flag 16 (ACGT complemented in their case, any other byte
+ *     kept); index 0 is the first CIGAR column, soft clips included.  A column of an M word is a match if and only if both bytes
+ *     are ACGT in either case and the same base (N matches nothing): the predicate NM and AS are computed with, so NM = X
+ *     columns + I bases + D bases.
+ *   NP2_ALN_EQX.  Every M word is replaced, in place and in order, by the maximal runs of match columns (=, op 7) and mismatch
+ *     columns (X, op 8) inside it; other words are untouched, lengths are preserved.  n_cigar and cigar_off describe the split
+ *     CIGAR; pos, end, nm and as are unchanged.
+ *   NP2_ALN_MD.  A counter c = 0.  M columns: a match does ++c; a mismatch emits dec(c), L(t), then c = 0.  A D word: dec(c),
+ *     '^', L(t) for each deleted base, then c = 0.  I and S words: nothing (the counter runs on across an insertion).  At the
+ *     end: dec(c).  L(t): A-Z kept, a-z upper-cased, any other byte N.  (A mismatch right after a deletion reads ^AC0T.)
+ *   NP2_ALN_CS, the short form.  A maximal run of match columns inside one M word: ':' dec(length).  A mismatch: '*' l(t) l(q).
+ *     An I word: '+', then l(q) per base.  A D word: '-', then l(t) per base.  S: nothing.  l: letters lower-cased, any other
+ *     byte n.
+ *   NP2_ALN_QUAL.  A read has qualities when its file is FASTQ, or when the caller's quality stream gives them (quals: the
+ *     shape of reads, a newline where reads has one; a read whose first quality byte is 0xFF has none).  SAM QUAL is then the
+ *     read's quality bytes, reversed (not complemented) with flag 16; a read without qualities keeps *.  A quality line whose
+ *     length differs from its sequence's, or that holds a byte outside '!' .. '~', is NP2_E_ARG naming the file and the 1-based
+ *     record; without the flag the quality lines stay unread.  An unmapped or overflowed read (flag 4) has no MD / cs and an
+ *     empty CIGAR; its qualities are written forward.  Qualities stay on the host: the text SAM needs them nowhere else.
+ *   SAM line.  The fields above in their order; QUAL takes the place of *, the CIGAR may hold = and X; MD:Z: then cs:Z: follow
+ *     s2:i:.  A line without flags is the line above byte for byte, and the header is the same.
+ *   Doors.  np2_map_align_bytes_x, _files_x, _host_x: the calls above with out_flags; md / md_off and cs / cs_off (each pair
+ *     both or neither, required by its flag): *md, *cs (np2_free) and md_off[n_reads + 1], cs_off[n_reads + 1], read i's text
+ *     md[md_off[i] .. md_off[i + 1]) (empty for flag 4).  np2_align_tags_device, _host run the walk on the caller's records:
+ *     record i's reference columns begin at ref + t_off[i], its read, already oriented, at reads + q_off[i] (first column,
+ *     clips included), its words are cigar[cigar_off[i] .. cigar_off[i + 1]) (M, I, D, S only; none: no text at all); outputs
+ *     as above plus *eqx (np2_free) and eqx_off[n_recs + 1].  A record whose columns reach beyond either buffer is NP2_E_ARG;
+ *     2^30 columns or more in a record, 2^32 in a call: NP2_E_UNSUPPORTED.  Unknown flag bits are NP2_E_ARG (NP2_ALN_QUAL is
+ *     unknown to _host_x and the two tag doors); every argument is checked before the first device call.
+ *   Stats (np2_map_align_last_tag_stats; this thread's last _x or tag call): bytes and words written, reads that had
+ *     qualities, and tags_ms, the HIP-event time of the two kernels, their scans and the copies of their outputs to the host
+ *     (0 without a flag and from the host doors).  np2_align_stats_t keeps its layout.
+ *   Not built: the long cs form; MD / cs in PAF; qualities or tags through np2_sam_from_reads* (the lean handle has no place for
+ *     them; a full BAM from reads goes through the SAM text); the second affine piece, z-drop, secondary or supplementary
+ *     records; a CG tag. */
+#define NP2_ALN_QUAL 1u
+#define NP2_ALN_MD 2u
+#define NP2_ALN_CS 4u
+#define NP2_ALN_EQX 8u
+typedef struct np2_align_tag_stats {
+    uint64_t md_bytes, cs_bytes, eqx_words, qual_reads;
+    float tags_ms;
+} np2_align_tag_stats_t;
+int np2_map_align_bytes_x(const np2_map_index_t *ix, const uint8_t *reads, const uint8_t *quals /* NULL: none */, uint64_t n, uint64_t n_reads,
+                          const np2_map_opts_t *map_opts, const np2_align_opts_t *align_opts, uint32_t out_flags, np2_map_hit_t *hits,
+                          np2_align_rec_t *recs, uint32_t **cigar, uint64_t *cigar_off, char **md, uint64_t *md_off, char **cs, uint64_t *cs_off);
+int np2_map_align_files_x(const np2_map_index_t *ix, const char *const *paths, int n_paths, const np2_map_opts_t *map_opts,
+                          const np2_align_opts_t *align_opts, uint32_t out_flags, const char *out_path, np2_map_stats_t *stats);
+/* host only, no device: the same rule text */
+int np2_map_align_host_x(const uint8_t *asm_stream, uint64_t n_asm, const uint8_t *reads, uint64_t n, uint64_t n_reads,
+                         const np2_map_opts_t *map_opts, const np2_align_opts_t *align_opts, const np2_map_weights_t *w /* NULL ok */,
+                         uint32_t out_flags, np2_map_hit_t *hits, np2_align_rec_t *recs, uint32_t **cigar, uint64_t *cigar_off, char **md,
+                         uint64_t *md_off, char **cs, uint64_t *cs_off);
+int np2_align_tags_device(int device, const uint8_t *ref, uint64_t n_ref, const uint8_t *reads, uint64_t n_read_bytes, uint64_t n_recs,
+                          const uint64_t *t_off, const uint64_t *q_off, const uint32_t *cigar, const uint64_t *cigar_off, uint32_t out_flags, char **md,
+                          uint64_t *md_off, char **cs, uint64_t *cs_off, uint32_t **eqx, uint64_t *eqx_off);
+int np2_align_tags_host(const uint8_t *ref, uint64_t n_ref, const uint8_t *reads, uint64_t n_read_bytes, uint64_t n_recs, const uint64_t *t_off,
+                        const uint64_t *q_off, const uint32_t *cigar, const uint64_t *cigar_off, uint32_t out_flags, char **md, uint64_t *md_off,
+                        char **cs, uint64_t *cs_off, uint32_t **eqx, uint64_t *eqx_off);
+int np2_map_align_last_tag_stats(np2_align_tag_stats_t *stats);
 
 /* ---- the mapper's SAM, parsed and coordinate-sorted on the device (the reference's recipe: `| samtools sort -o ... ;
  * samtools index ...`, which exist only so that an indexed reader can fetch one contig's records in coordinate order) -------

@@ -19,21 +19,6 @@
 namespace np2 {
 using namespace np2aln;
 
-namespace {
-
-__device__ __forceinline__ Seqs seqs_of(const AlignJob &c, uint32_t i) {
-    const uint32_t rd = c.r0 + i;
-    const np2map::Hit &h = c.hits[rd];
-    const uint32_t q_at = rd ? c.rd_ends[rd - 1] + 1u : 0u;
-    const uint32_t t_at = h.tid > 0 ? c.asm_ends[h.tid - 1] + 1u : 0u;
-    Seqs s;
-    s.t = c.asm_seq + t_at, s.tlen = c.asm_ends[h.tid] - t_at;
-    s.q = c.rd_seq + q_at, s.qlen = h.qlen, s.rev = h.rev;
-    return s;
-}
-
-} // namespace
-
 __global__ __launch_bounds__(64) void k_align_pins(AlignJob c) {
     const uint32_t i = blockIdx.x * 64 + threadIdx.x;
     if (i > c.n_reads) return;

@@ -34,6 +34,18 @@ struct AlignJob {
     np2aln::Rec *recs;        // [i]
 };
 
+// read i of the group and the contig its hit names (the aligner's kernels and the tag kernels, np2_aligntags.hip)
+__device__ __forceinline__ np2aln::Seqs seqs_of(const AlignJob &c, uint32_t i) {
+    const uint32_t rd = c.r0 + i;
+    const np2map::Hit &h = c.hits[rd];
+    const uint32_t q_at = rd ? c.rd_ends[rd - 1] + 1u : 0u;
+    const uint32_t t_at = h.tid > 0 ? c.asm_ends[h.tid - 1] + 1u : 0u;
+    np2aln::Seqs s;
+    s.t = c.asm_seq + t_at, s.tlen = c.asm_ends[h.tid] - t_at;
+    s.q = c.rd_seq + q_at, s.qlen = h.qlen, s.rev = h.rev;
+    return s;
+}
+
 // pin flags and slot counts per read
 void launch_align_pins(hipStream_t s, const AlignJob &c);
 // the slots of every mapped read (head, raw segments, tail) at soff[i]

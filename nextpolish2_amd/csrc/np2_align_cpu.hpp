@@ -155,4 +155,58 @@ inline void sam_line(std::string &out, const char *qname, size_t qname_n, const 
     out.append(num, (size_t)m);
 }
 
+// what the opt-in outputs add to a line (np2_map_align_files_x): QUAL (null: *), and MD:Z: then cs:Z: behind s2:i: (0 bytes: none)
+struct SamExtra {
+    const uint8_t *qual;
+    const char *md, *cs;
+    uint32_t n_md, n_cs;
+};
+// sam_line with them: the CIGAR may hold = and X words; QUAL is reversed, not complemented, with flag 16, and written forward
+// for an unmapped or overflowed read
+inline void sam_line_x(std::string &out, const char *qname, size_t qname_n, const Rec &rec, const np2map::Hit &hit, const uint32_t *cigar,
+                       const uint8_t *q, uint32_t qlen, const std::string *tname, const SamExtra &x) {
+    char num[160];
+    const auto put_qual = [&](bool rev) {
+        if (!x.qual || qlen == 0) {
+            out += '*';
+            return;
+        }
+        if (!rev) {
+            out.append((const char *)x.qual, qlen);
+            return;
+        }
+        const size_t at = out.size();
+        out.resize(at + qlen);
+        char *w = &out[at];
+        for (uint32_t i = 0; i < qlen; ++i) w[i] = (char)x.qual[qlen - 1u - i];
+    };
+    out.append(qname, qname_n);
+    if (rec.tid < 0) {
+        out += "\t4\t*\t0\t0\t*\t*\t0\t0\t";
+        sam_seq(out, q, qlen, false);
+        out += '\t';
+        put_qual(false);
+        out += '\n';
+        return;
+    }
+    int m = snprintf(num, sizeof num, "\t%u\t", rec.flag);
+    out.append(num, (size_t)m);
+    out += *tname;
+    m = snprintf(num, sizeof num, "\t%u\t%u\t", rec.pos + 1, rec.mapq);
+    out.append(num, (size_t)m);
+    for (uint32_t i = 0; i < rec.n_cigar; ++i) {
+        m = snprintf(num, sizeof num, "%u%c", cigar[i] >> 4, "MIDNSHP=X"[cigar[i] & 15u]);
+        out.append(num, (size_t)m);
+    }
+    out += "\t*\t0\t0\t";
+    sam_seq(out, q, qlen, (rec.flag & 16u) != 0);
+    out += '\t';
+    put_qual((rec.flag & 16u) != 0);
+    m = snprintf(num, sizeof num, "\tNM:i:%u\tAS:i:%d\tcm:i:%u\ts1:i:%u\ts2:i:%u", rec.nm, rec.as, hit.n, hit.s1, hit.s2);
+    out.append(num, (size_t)m);
+    if (x.n_md) out += "\tMD:Z:", out.append(x.md, x.n_md);
+    if (x.n_cs) out += "\tcs:Z:", out.append(x.cs, x.n_cs);
+    out += '\n';
+}
+
 } // namespace np2aln

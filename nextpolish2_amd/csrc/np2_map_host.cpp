@@ -37,6 +37,7 @@
 #include "../../include/np2_io.h"
 #include "np2_align.hpp"
 #include "np2_align_cpu.hpp"
+#include "np2_aligntags.hpp"
 #include "np2_alnpack.hpp"
 #include "np2_ctx.hpp"
 #include "np2_kcount.hpp"
@@ -68,6 +69,9 @@ constexpr uint8_t SEP = '\n';
 
 thread_local np2_map_stats_t tl_stats{};
 thread_local np2_align_stats_t tl_astats{};
+thread_local np2_align_tag_stats_t tl_tstats{};
+static_assert(NP2_ALN_QUAL == np2aln::ALN_QUAL && NP2_ALN_MD == np2aln::ALN_MD && NP2_ALN_CS == np2aln::ALN_CS && NP2_ALN_EQX == np2aln::ALN_EQX,
+              "NP2_ALN_* are np2aln::ALN_*");
 static_assert(sizeof(np2_align_opts_t) == sizeof(np2aln::Opts), "np2_align_opts_t is np2aln::Opts");
 static_assert(sizeof(np2_align_rec_t) == sizeof(np2aln::Rec) && sizeof(np2aln::Rec) == 32, "np2_align_rec_t is np2aln::Rec");
 
@@ -412,6 +416,79 @@ struct PackSink {
     }
 };
 
+// The tag kernels around their scans, for the aligner's sub-groups and for np2_align_tags_device: sizes, three exclusive sums,
+// the texts and the split CIGAR, which come to the host with their offsets.  Returns the HIP-event time, copies included.
+struct TagRun {
+    DevBuf<uint32_t> d_n_md, d_n_cs, d_n_eqx, d_eqx_off, d_eqx;
+    DevBuf<uint64_t> d_md_off, d_cs_off;
+    DevBuf<uint8_t> d_md, d_cs;
+    std::vector<uint64_t> md_off, cs_off; // [n + 1]
+    std::vector<uint32_t> eqx_off, eqx;
+    std::vector<char> md, cs;
+    TagRun() {
+        d_n_md.cached = d_n_cs.cached = d_n_eqx.cached = d_eqx_off.cached = d_eqx.cached = d_md_off.cached = d_cs_off.cached = true;
+        d_md.cached = d_cs.cached = true;
+    }
+    float run(Stream &s, np2::TagJob j) {
+        using namespace np2;
+        hipStream_t st = s.st;
+        const size_t m = (size_t)j.n + 1;
+        d_n_md.ensure(m), d_n_cs.ensure(m), d_n_eqx.ensure(m), d_md_off.ensure(m), d_cs_off.ensure(m), d_eqx_off.ensure(m);
+        const size_t tmp_bytes = prim_temp_bytes(m);
+        s.tmp.ensure(tmp_bytes);
+        md_off.resize(m), cs_off.resize(m), eqx_off.resize(m);
+        j.n_md = d_n_md.p, j.n_cs = d_n_cs.p, j.n_eqx = d_n_eqx.p;
+        j.md_off = d_md_off.p, j.cs_off = d_cs_off.p, j.eqx_off = d_eqx_off.p;
+        s.begin();
+        launch_align_tags_size(st, j);
+        if (prim_exclusive_sum_u32_u64(st, s.tmp.p, tmp_bytes, d_n_md.p, d_md_off.p, m) ||
+            prim_exclusive_sum_u32_u64(st, s.tmp.p, tmp_bytes, d_n_cs.p, d_cs_off.p, m) ||
+            prim_exclusive_sum_u32(st, s.tmp.p, tmp_bytes, d_n_eqx.p, d_eqx_off.p, m))
+            throw Np2Error(NP2_E_DEVICE, "rocprim exclusive_scan failed");
+        HIPCHK(hipMemcpyAsync(md_off.data(), d_md_off.p, m * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(cs_off.data(), d_cs_off.p, m * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(eqx_off.data(), d_eqx_off.p, m * 4, hipMemcpyDeviceToHost, st));
+        float ms = s.end();
+        const uint64_t n_md = md_off[j.n], n_cs = cs_off[j.n], n_eqx = eqx_off[j.n];
+        d_md.ensure(n_md + 1), d_cs.ensure(n_cs + 1), d_eqx.ensure(n_eqx + 1);
+        md.resize(n_md), cs.resize(n_cs), eqx.resize(n_eqx);
+        j.md = (char *)d_md.p, j.cs = (char *)d_cs.p, j.eqx = d_eqx.p;
+        s.begin();
+        launch_align_tags_emit(st, j);
+        if (n_md) HIPCHK(hipMemcpyAsync(md.data(), d_md.p, n_md, hipMemcpyDeviceToHost, st));
+        if (n_cs) HIPCHK(hipMemcpyAsync(cs.data(), d_cs.p, n_cs, hipMemcpyDeviceToHost, st));
+        if (n_eqx) HIPCHK(hipMemcpyAsync(eqx.data(), d_eqx.p, n_eqx * 4, hipMemcpyDeviceToHost, st));
+        ms += s.end();
+        return ms;
+    }
+};
+
+// the MD and cs texts of a batch's reads: appended in read order, n_md[i], n_cs[i] bytes of read i (0: none)
+struct TagTexts {
+    std::vector<char> md, cs;
+    std::vector<uint32_t> n_md, n_cs;
+    void begin(size_t n_reads) { md.clear(), cs.clear(), n_md.assign(n_reads, 0), n_cs.assign(n_reads, 0); }
+};
+
+// the host twin of the tag kernels for one record: its texts appended to tt (read i of the batch), its split CIGAR to `eqx`
+void tags_of_record(const np2aln::TagIn &in, uint32_t flags, TagTexts &tt, size_t i, std::vector<uint32_t> *eqx) {
+    np2aln::TagOut sz{};
+    const auto one = [](bool b) { return (uint64_t)(b ? 1u : 0u); };
+    np2aln::tag_walk(in, sz, 0, 1, one);
+    np2aln::TagOut out{};
+    const size_t md_at = tt.md.size(), cs_at = tt.cs.size(), x_at = eqx ? eqx->size() : 0;
+    if (flags & NP2_ALN_MD) tt.md.resize(md_at + sz.n_md), tt.n_md[i] = sz.n_md, out.md = tt.md.data() + md_at;
+    if (flags & NP2_ALN_CS) tt.cs.resize(cs_at + sz.n_cs), tt.n_cs[i] = sz.n_cs, out.cs = tt.cs.data() + cs_at;
+    if (eqx && (flags & NP2_ALN_EQX)) eqx->resize(x_at + sz.n_eqx), out.eqx = eqx->data() + x_at;
+    np2aln::tag_walk(in, out, 0, 1, one);
+    if (out.n_md != sz.n_md || out.n_cs != sz.n_cs || out.n_eqx != sz.n_eqx) throw Np2Error(NP2_E_DEVICE, "the tag walk's two passes disagree");
+}
+
+uint32_t checked_out_flags(uint32_t flags, uint32_t allowed, const std::string &who) {
+    if (flags & ~allowed) throw Np2Error(NP2_E_ARG, who + ": unknown flag bits in out_flags");
+    return flags;
+}
+
 // batches of reads against one index
 struct Mapper {
     const np2_map_index &ix;
@@ -443,6 +520,10 @@ struct Mapper {
     std::vector<uint32_t> h_soff, h_ooff, h_b;
     std::vector<np2aln::Rec> h_recs;
     PackSink *pk = nullptr; // np2_sam_from_reads: records and CIGAR words stay on the device (recs and cigar are null then)
+    // the opt-in outputs (NP2_ALN_MD | NP2_ALN_CS | NP2_ALN_EQX): off while tag_flags is 0; tt takes a batch's texts
+    uint32_t tag_flags = 0;
+    TagRun tg;
+    TagTexts *tt = nullptr;
 
     void align_with(const np2aln::Opts &a) {
         ao_v = a, ao = &ao_v;
@@ -625,12 +706,24 @@ struct Mapper {
             HIPCHK(hipMemcpyAsync(h_recs.data() + g0, d_recs.p + g0, (size_t)ng * sizeof(np2aln::Rec), hipMemcpyDeviceToHost, st));
             HIPCHK(hipMemcpyAsync(h_b.data(), d_b.p, n_b * 4, hipMemcpyDeviceToHost, st));
             astats.assemble_ms += s.end();
-            for (uint32_t i = 0; i < ng; ++i) {
-                const np2aln::Rec &rc = h_recs[g0 + i];
-                recs[r0 + g0 + i] = rc;
-                const uint32_t *w = h_b.data() + 2 * (size_t)h_ooff[i] + 2 * (size_t)i;
-                if (cigar) cigar->insert(cigar->end(), w, w + rc.n_cigar);
+            if (tag_flags) { // right behind k_align_ops_emit, whose records and words are still where it left them
+                TagJob j{};
+                j.c = c, j.g0 = g0, j.from_aligner = 1, j.n = ng, j.flags = tag_flags;
+                tl_tstats.tags_ms += tg.run(s, j);
+                tl_tstats.md_bytes += tg.md.size(), tl_tstats.cs_bytes += tg.cs.size(), tl_tstats.eqx_words += tg.eqx.size();
             }
+            for (uint32_t i = 0; i < ng; ++i) {
+                np2aln::Rec rc = h_recs[g0 + i];
+                const uint32_t *w = h_b.data() + 2 * (size_t)h_ooff[i] + 2 * (size_t)i;
+                if ((tag_flags & NP2_ALN_EQX) && rc.tid >= 0) w = tg.eqx.data() + tg.eqx_off[i], rc.n_cigar = tg.eqx_off[i + 1] - tg.eqx_off[i];
+                recs[r0 + g0 + i] = rc;
+                if (cigar) cigar->insert(cigar->end(), w, w + rc.n_cigar);
+                if (tag_flags && tt) {
+                    tt->n_md[r0 + g0 + i] = (uint32_t)(tg.md_off[i + 1] - tg.md_off[i]);
+                    tt->n_cs[r0 + g0 + i] = (uint32_t)(tg.cs_off[i + 1] - tg.cs_off[i]);
+                }
+            }
+            if (tag_flags && tt) tt->md.insert(tt->md.end(), tg.md.begin(), tg.md.end()), tt->cs.insert(tt->cs.end(), tg.cs.begin(), tg.cs.end());
             g0 = g1;
         }
         if (n_sub > 1) stats.groups += n_sub - 1;
@@ -667,6 +760,7 @@ struct MapPiece {
     size_t n = 0;
     std::vector<uint32_t> ends;
     std::string names; // of the reads that end in the piece, '\n' after each
+    std::vector<uint8_t> qual; // NP2_ALN_QUAL: n bytes beside the piece's, '\n' where it has one; 0xFF for a read without qualities
     bool last = false; // the file ends with this piece
 };
 using MapQueue = np2h::PieceQueue<MapPiece>;
@@ -678,7 +772,7 @@ struct MapWriter {
     MapWriter(MapQueue &q, size_t cap) : w(q, cap) {
         w.on_fresh = [](MapPiece &p) {
             p.last = false;
-            p.ends.clear(), p.names.clear();
+            p.ends.clear(), p.names.clear(), p.qual.clear();
         };
     }
     void finish() { // (a file without a byte still ends: with an empty piece)
@@ -698,22 +792,81 @@ struct MapWriter {
         }
         w.put(p, n);
     }
+    // NP2_ALN_QUAL: n bytes and the n quality bytes beside them (ql null: 0xFF, a read without qualities), cut at the same
+    // places; a separator is its own call with one beside it
+    void put_pair(const uint8_t *p, const uint8_t *ql, size_t n) {
+        while (n && !w.dead) {
+            if (!w.cur && !w.fresh()) return;
+            const size_t take_n = std::min(n, w.cap - w.cur->n);
+            if (ql) w.cur->qual.insert(w.cur->qual.end(), ql, ql + take_n), ql += take_n;
+            else w.cur->qual.insert(w.cur->qual.end(), take_n, (uint8_t)0xFF);
+            put(p, take_n); // (fills the piece at the most: one piece takes it)
+            p += take_n, n -= take_n;
+        }
+    }
 };
+
+// One file's records with NP2_ALN_QUAL.  A FASTQ record's sequence waits for its quality line, which is checked (as long as
+// the sequence, every byte in '!' .. '~'; NP2_E_ARG names the file and the 1-based record), and the two go into the pieces
+// together; a FASTA or one-sequence-per-line file's reads have no qualities.
+void parse_with_qual(const std::string &path, MapWriter &w) {
+    np2seq::SeqParser ps;
+    np2seq::RecordCheck chk;
+    chk.file_begin(path);
+    std::vector<uint8_t> seq, ql;
+    const auto put = [&](const uint8_t *p, size_t n) {
+        if (ps.fmt != np2seq::SeqParser::FASTQ) {
+            const bool sep = n == 1 && *p == SEP;
+            w.put_pair(p, sep ? &SEP : nullptr, n);
+        } else if (n == 1 && *p == SEP) {
+            chk.seq_end();
+        } else {
+            if (seq.size() + n > np2map::MAX_SEQ) throw Np2Error(NP2_E_UNSUPPORTED, "np2_map_align_files_x: a read longer than 2^31 - 1");
+            chk.seq_bytes(n), seq.insert(seq.end(), p, p + n);
+        }
+    };
+    const auto qual = [&](const uint8_t *p, size_t n) {
+        if (n == 1 && *p == SEP) {
+            chk.qual_end();
+            if (!seq.empty()) w.put_pair(seq.data(), ql.data(), seq.size());
+            w.put_pair(&SEP, &SEP, 1);
+            seq.clear(), ql.clear();
+            return;
+        }
+        chk.qual_bytes(n);
+        for (size_t i = 0; i < n; ++i)
+            if (p[i] < '!' || p[i] > '~')
+                throw Np2Error(NP2_E_ARG, path + ": record " + std::to_string(chk.record + 1) + ": the quality line holds a byte outside '!' .. '~'");
+        ql.insert(ql.end(), p, p + n);
+    };
+    const auto hdr = [&](const uint8_t *p, size_t n, bool begin) { w.names(p, n, begin); };
+    if (np2seq::read_chunks(path, [&] { return w.w.dead; }, [&](const uint8_t *p, size_t n) { ps.feed(p, n, put, hdr, qual); })) {
+        ps.finish(put, qual);
+        chk.file_end();
+    }
+}
 
 // whole reads gathered from pieces; what follows the last separator waits for the next piece
 struct BatchBuf {
     std::vector<uint8_t> bytes;
     std::vector<uint32_t> ends;
     std::string names;
+    std::vector<uint8_t> quals; // NP2_ALN_QUAL: beside bytes
+    bool with_qual = false;
     void add(const MapPiece &p) {
         const size_t at = bytes.size();
         if (at + p.n > MAP_MAX_STREAM) throw Np2Error(NP2_E_UNSUPPORTED, "np2_map_files: a batch of 2^32 bytes or more");
         bytes.insert(bytes.end(), p.buf + np2h::HALO, p.buf + np2h::HALO + p.n);
         for (uint32_t e : p.ends) ends.push_back((uint32_t)(at + e));
         names += p.names;
+        if (with_qual) {
+            if (p.qual.size() != p.n) throw Np2Error(NP2_E_DEVICE, "np2_map_align_files_x: a piece's quality bytes do not line up with its bases");
+            quals.insert(quals.end(), p.qual.begin(), p.qual.end());
+        }
     }
     size_t closed() const { return ends.empty() ? 0 : (size_t)ends.back() + 1; }
     void drop_closed() {
+        if (with_qual) quals.erase(quals.begin(), quals.begin() + (ptrdiff_t)closed());
         bytes.erase(bytes.begin(), bytes.begin() + (ptrdiff_t)closed());
         ends.clear(), names.clear();
     }
@@ -735,15 +888,26 @@ void fill_stats(np2_map_stats_t *stats) {
     if (stats) *stats = tl_stats;
 }
 
+// tt (may be null): the batch's MD and cs texts; b.quals, when the batch has them, become QUAL
 void write_sam(np2h::OutFile &out, const np2_map_index &ix, const BatchBuf &b, const std::vector<Hit> &hits, const std::vector<np2aln::Rec> &recs,
-               const std::vector<uint32_t> &cigar, std::string &text) {
+               const std::vector<uint32_t> &cigar, std::string &text, const TagTexts *tt = nullptr) {
     text.clear();
-    size_t name_at = 0, cig_at = 0, from = 0;
+    size_t name_at = 0, cig_at = 0, from = 0, md_at = 0, cs_at = 0;
     for (size_t i = 0; i < b.ends.size(); ++i) {
         const size_t name_end = b.names.find('\n', name_at);
         const np2aln::Rec &rc = recs[i];
-        np2aln::sam_line(text, b.names.data() + name_at, name_end - name_at, rc, hits[i], cigar.data() + cig_at, b.bytes.data() + from,
-                         (uint32_t)(b.ends[i] - from), rc.tid >= 0 ? &ix.names[(size_t)rc.tid] : nullptr);
+        const uint32_t qlen = (uint32_t)(b.ends[i] - from);
+        if (!tt && !b.with_qual) {
+            np2aln::sam_line(text, b.names.data() + name_at, name_end - name_at, rc, hits[i], cigar.data() + cig_at, b.bytes.data() + from, qlen,
+                             rc.tid >= 0 ? &ix.names[(size_t)rc.tid] : nullptr);
+        } else {
+            np2aln::SamExtra x{};
+            if (b.with_qual && qlen && b.quals[from] != 0xFF) x.qual = b.quals.data() + from, ++tl_tstats.qual_reads;
+            if (tt) x.md = tt->md.data() + md_at, x.n_md = tt->n_md[i], x.cs = tt->cs.data() + cs_at, x.n_cs = tt->n_cs[i];
+            np2aln::sam_line_x(text, b.names.data() + name_at, name_end - name_at, rc, hits[i], cigar.data() + cig_at, b.bytes.data() + from, qlen,
+                               rc.tid >= 0 ? &ix.names[(size_t)rc.tid] : nullptr, x);
+            md_at += x.n_md, cs_at += x.n_cs;
+        }
         cig_at += rc.n_cigar, name_at = name_end + 1, from = (size_t)b.ends[i] + 1;
     }
     out.put(text.data(), text.size());
@@ -765,7 +929,9 @@ std::vector<std::string> checked_files(const char *const *paths, int n_paths, co
 
 // The files' reads in file order as batches of whole reads, hooks.batch_bytes() at the most (a file's last batch may be
 // smaller): flush(b) works a batch off, its closed reads are dropped afterwards.  Reader threads parse ahead.
-template <class Flush> void read_batches(const std::vector<std::string> &files, const Hooks &hooks, const std::string &who, Flush &&flush) {
+// with_qual (NP2_ALN_QUAL): the batches carry the reads' quality bytes beside their bases.
+template <class Flush>
+void read_batches(const std::vector<std::string> &files, const Hooks &hooks, const std::string &who, Flush &&flush, bool with_qual = false) {
     const size_t cap = hooks.piece;
     const size_t n_threads = std::min<size_t>(files.size(), 16);
     std::vector<MapQueue> queues(n_threads);
@@ -778,13 +944,17 @@ template <class Flush> void read_batches(const std::vector<std::string> &files, 
     auto readers = np2h::run_readers(n_threads, queues, [&](size_t ti) {
         for (size_t fi = ti; fi < files.size(); fi += n_threads) {
             MapWriter w(queues[ti], cap);
-            np2seq::parse_file(files[fi], [&](const uint8_t *p, size_t n) { w.put(p, n); }, [&] { return w.w.dead; },
-                               [&](const uint8_t *p, size_t n, bool begin) { w.names(p, n, begin); });
+            if (with_qual)
+                parse_with_qual(files[fi], w);
+            else
+                np2seq::parse_file(files[fi], [&](const uint8_t *p, size_t n) { w.put(p, n); }, [&] { return w.w.dead; },
+                                   [&](const uint8_t *p, size_t n, bool begin) { w.names(p, n, begin); });
             w.finish();
             if (w.w.dead) break;
         }
     });
     BatchBuf b;
+    b.with_qual = with_qual;
     for (size_t fi = 0; fi < files.size(); ++fi) {
         MapQueue &q = queues[fi % n_threads];
         for (bool last = false; !last;) {
@@ -805,17 +975,24 @@ template <class Flush> void read_batches(const std::vector<std::string> &files, 
 
 // np2_map_files (aopts null: PAF) and np2_map_align_files (SAM)
 int map_files_impl(const np2_map_index_t *ix, const char *const *paths, int n_paths, const np2_map_opts_t *opts, const np2_align_opts_t *aopts,
-                   bool align, const char *out_path, np2_map_stats_t *stats, const std::string who) {
+                   bool align, const char *out_path, np2_map_stats_t *stats, const std::string who, uint32_t out_flags = 0) {
     return np2h::abi_guard([&] {
         const np2map::Opts o = checked(opts, who.c_str());
         np2aln::Opts ao{};
         if (align) ao = checked_align(aopts, who.c_str());
+        checked_out_flags(out_flags, NP2_ALN_QUAL | NP2_ALN_MD | NP2_ALN_CS | NP2_ALN_EQX, who);
+        tl_tstats = np2_align_tag_stats_t{};
+        const uint32_t tag_flags = out_flags & ~(uint32_t)NP2_ALN_QUAL;
+        const bool with_qual = (out_flags & NP2_ALN_QUAL) != 0;
+        TagTexts tt;
         check_index_opts(ix, o, who.c_str());
         if (!paths || n_paths < 1) throw Np2Error(NP2_E_ARG, who + ": no read file given");
         if (!out_path) throw Np2Error(NP2_E_ARG, who + ": out_path is NULL");
         const std::vector<std::string> files = checked_files(paths, n_paths, who);
         Mapper m(*ix, o);
         if (align) m.align_with(ao);
+        m.tag_flags = tag_flags;
+        if (tag_flags) m.tt = &tt;
         np2h::OutFile out;
         out.open(out_path, ix->device);
         std::vector<Hit> hits;
@@ -829,15 +1006,16 @@ int map_files_impl(const np2_map_index_t *ix, const char *const *paths, int n_pa
         read_batches(files, m.hooks, who, [&](const BatchBuf &b) {
             hits.resize(b.ends.size());
             if (align) recs.resize(b.ends.size()), cigar.clear();
+            if (tag_flags) tt.begin(b.ends.size());
             m.batch(b.bytes.data(), b.closed(), b.ends.data(), (uint32_t)b.ends.size(), hits.data(), nullptr, align ? recs.data() : nullptr,
                     align ? &cigar : nullptr);
             const auto t0 = std::chrono::steady_clock::now();
-            if (align) write_sam(out, *ix, b, hits, recs, cigar, text);
+            if (align) write_sam(out, *ix, b, hits, recs, cigar, text, tag_flags ? &tt : nullptr);
             else write_paf(out, *ix, b, hits, text);
             const float ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
             tl_stats.write_ms += ms;
             if (align) tl_astats.write_ms += ms;
-        });
+        }, with_qual);
         out.close();
         fill_stats(stats);
         return NP2_OK;
@@ -895,6 +1073,80 @@ struct FromReadsRun {
         st.lines = st.records + sam->refs.names.size() + 2; // (as the text would have: @HD, the @SQ lines, @PG, a line a read)
         st.parse_ms = 0.f, st.pack_ms = pk.pack_ms, st.read_ms = tl_stats.read_ms;
         return sam.release();
+    }
+};
+
+// ---- the opt-in outputs' doors -------------------------------------------------------------------------------------------------
+char *text_out(const std::vector<char> &t) { // a malloc block for the caller (np2_free); never NULL
+    char *p = (char *)malloc(std::max<size_t>(t.size(), 1));
+    if (!p) throw Np2Error(NP2_E_NOMEM, "out of memory for the tag texts");
+    if (!t.empty()) memcpy(p, t.data(), t.size());
+    return p;
+}
+
+// md / md_off and cs / cs_off of an _x call: each pair both or neither, and there when its flag asks for it
+void check_tag_pairs(uint32_t flags, char **md, uint64_t *md_off, char **cs, uint64_t *cs_off, const std::string &who) {
+    if (md) *md = nullptr;
+    if (cs) *cs = nullptr;
+    if ((md == nullptr) != (md_off == nullptr)) throw Np2Error(NP2_E_ARG, who + ": md and md_off go together");
+    if ((cs == nullptr) != (cs_off == nullptr)) throw Np2Error(NP2_E_ARG, who + ": cs and cs_off go together");
+    if ((flags & NP2_ALN_MD) && !md) throw Np2Error(NP2_E_ARG, who + ": NP2_ALN_MD without md and md_off");
+    if ((flags & NP2_ALN_CS) && !cs) throw Np2Error(NP2_E_ARG, who + ": NP2_ALN_CS without cs and cs_off");
+}
+
+void offsets_of(const std::vector<uint32_t> &n, uint64_t *off) { // off[0 .. n.size()]
+    off[0] = 0;
+    for (size_t i = 0; i < n.size(); ++i) off[i + 1] = off[i] + n[i];
+}
+
+// a quality stream beside a read stream: the same length and separators; a read has none (its first byte 0xFF) or every byte in
+// '!' .. '~'.  Returns the reads that have qualities.
+uint64_t check_quals(const uint8_t *quals, const std::vector<uint64_t> &ends, const std::string &who) {
+    uint64_t from = 0, have = 0;
+    for (size_t i = 0; i < ends.size(); ++i) {
+        if (quals[ends[i]] != SEP) throw Np2Error(NP2_E_ARG, who + ": read " + std::to_string(i + 1) + ": the quality stream has no newline where the read ends");
+        if (ends[i] > from && quals[from] != 0xFF) {
+            for (uint64_t x = from; x < ends[i]; ++x)
+                if (quals[x] < '!' || quals[x] > '~')
+                    throw Np2Error(NP2_E_ARG, who + ": read " + std::to_string(i + 1) + ": a quality byte outside '!' .. '~'");
+            ++have;
+        }
+        from = ends[i] + 1;
+    }
+    return have;
+}
+
+// np2_align_tags_host, np2_align_tags_device: what both check before any walk
+struct TagDoor {
+    uint32_t flags;
+    uint64_t n_words = 0;
+    TagDoor(const uint8_t *ref, uint64_t n_ref, const uint8_t *reads, uint64_t n_read_bytes, uint64_t n_recs, const uint64_t *t_off, const uint64_t *q_off,
+            const uint32_t *cigar, const uint64_t *cigar_off, uint32_t out_flags, char **md, uint64_t *md_off, char **cs, uint64_t *cs_off, uint32_t **eqx,
+            uint64_t *eqx_off, const std::string &who) {
+        flags = checked_out_flags(out_flags, NP2_ALN_MD | NP2_ALN_CS | NP2_ALN_EQX, who);
+        check_tag_pairs(flags, md, md_off, cs, cs_off, who);
+        if (eqx) *eqx = nullptr;
+        if ((eqx == nullptr) != (eqx_off == nullptr)) throw Np2Error(NP2_E_ARG, who + ": eqx and eqx_off go together");
+        if ((flags & NP2_ALN_EQX) && !eqx) throw Np2Error(NP2_E_ARG, who + ": NP2_ALN_EQX without eqx and eqx_off");
+        if ((n_ref && !ref) || (n_read_bytes && !reads)) throw Np2Error(NP2_E_ARG, who + ": a buffer is NULL with a length");
+        if (n_recs && (!t_off || !q_off)) throw Np2Error(NP2_E_ARG, who + ": t_off or q_off is NULL");
+        if (!cigar_off) throw Np2Error(NP2_E_ARG, who + ": cigar_off is NULL");
+        if (n_recs >= (1ull << 31)) throw Np2Error(NP2_E_UNSUPPORTED, who + ": 2^31 records or more");
+        uint64_t eqx_bound = 0;
+        for (uint64_t i = 0; i < n_recs; ++i) {
+            const std::string rec = who + ": record " + std::to_string(i);
+            if (cigar_off[i + 1] < cigar_off[i]) throw Np2Error(NP2_E_ARG, rec + ": cigar_off is descending");
+            const uint64_t nw = cigar_off[i + 1] - cigar_off[i];
+            if (nw && !cigar) throw Np2Error(NP2_E_ARG, who + ": cigar is NULL with words");
+            uint64_t ts = 0, qs = 0;
+            if (!np2aln::tag_cigar_spans(cigar + cigar_off[i], nw, &ts, &qs)) throw Np2Error(NP2_E_ARG, rec + ": a CIGAR word that is not M, I, D or S");
+            if (nw >= (1ull << 28) || ts >= (1ull << 30) || qs >= (1ull << 30)) throw Np2Error(NP2_E_UNSUPPORTED, rec + ": 2^30 columns or more");
+            if (t_off[i] > n_ref || ts > n_ref - t_off[i]) throw Np2Error(NP2_E_ARG, rec + ": its columns reach beyond the reference buffer");
+            if (q_off[i] > n_read_bytes || qs > n_read_bytes - q_off[i]) throw Np2Error(NP2_E_ARG, rec + ": its columns reach beyond the read buffer");
+            eqx_bound += nw + ts;
+        }
+        n_words = n_recs ? cigar_off[n_recs] - cigar_off[0] : 0;
+        if (eqx_bound >= (1ull << 32)) throw Np2Error(NP2_E_UNSUPPORTED, who + ": 2^32 columns or more in one call");
     }
 };
 
@@ -1175,20 +1427,33 @@ int np2_map_host_w(const uint8_t *asm_stream, uint64_t n_asm, const uint8_t *rea
     return map_host_impl(asm_stream, n_asm, reads, n, n_reads, opts, w, hits, chain, chain_off, "np2_map_host_w");
 }
 
-int np2_map_align_bytes(const np2_map_index_t *ix, const uint8_t *reads, uint64_t n, uint64_t n_reads, const np2_map_opts_t *map_opts,
-                        const np2_align_opts_t *align_opts, np2_map_hit_t *hits, np2_align_rec_t *recs, uint32_t **cigar, uint64_t *cigar_off) {
+// np2_map_align_bytes (out_flags 0, no texts) and np2_map_align_bytes_x
+static int map_align_bytes_impl(const np2_map_index_t *ix, const uint8_t *reads, const uint8_t *quals, uint64_t n, uint64_t n_reads,
+                                const np2_map_opts_t *map_opts, const np2_align_opts_t *align_opts, uint32_t out_flags, np2_map_hit_t *hits,
+                                np2_align_rec_t *recs, uint32_t **cigar, uint64_t *cigar_off, char **md, uint64_t *md_off, char **cs, uint64_t *cs_off,
+                                const std::string name) {
     return np2h::abi_guard([&] {
+        const char *who = name.c_str();
         if (cigar) *cigar = nullptr;
-        const np2map::Opts o = checked(map_opts, "np2_map_align_bytes");
-        const np2aln::Opts ao = checked_align(align_opts, "np2_map_align_bytes");
-        check_index_opts(ix, o, "np2_map_align_bytes");
-        if (n_reads && !recs) throw Np2Error(NP2_E_ARG, "np2_map_align_bytes: recs is NULL");
-        if ((cigar == nullptr) != (cigar_off == nullptr)) throw Np2Error(NP2_E_ARG, "np2_map_align_bytes: cigar and cigar_off go together");
-        const std::vector<uint64_t> ends = ends_of(reads, n, "np2_map_align_bytes", "the read stream");
+        const np2map::Opts o = checked(map_opts, who);
+        const np2aln::Opts ao = checked_align(align_opts, who);
+        check_index_opts(ix, o, who);
+        checked_out_flags(out_flags, NP2_ALN_QUAL | NP2_ALN_MD | NP2_ALN_CS | NP2_ALN_EQX, name);
+        check_tag_pairs(out_flags, md, md_off, cs, cs_off, name);
+        if (n_reads && !recs) throw Np2Error(NP2_E_ARG, name + ": recs is NULL");
+        if ((cigar == nullptr) != (cigar_off == nullptr)) throw Np2Error(NP2_E_ARG, name + ": cigar and cigar_off go together");
+        const std::vector<uint64_t> ends = ends_of(reads, n, who, "the read stream");
         if (ends.size() != n_reads)
-            throw Np2Error(NP2_E_ARG, "np2_map_align_bytes: n_reads is " + std::to_string(n_reads) + ", the stream holds " + std::to_string(ends.size()) + " newlines");
+            throw Np2Error(NP2_E_ARG, name + ": n_reads is " + std::to_string(n_reads) + ", the stream holds " + std::to_string(ends.size()) + " newlines");
+        tl_tstats = np2_align_tag_stats_t{};
+        if ((out_flags & NP2_ALN_QUAL) && quals) tl_tstats.qual_reads = check_quals(quals, ends, name);
+        const uint32_t tag_flags = out_flags & ~(uint32_t)NP2_ALN_QUAL;
+        TagTexts tt, all;
+        all.begin(n_reads);
         Mapper m(*ix, o);
         m.align_with(ao);
+        m.tag_flags = tag_flags;
+        if (tag_flags) m.tt = &tt;
         std::vector<uint32_t> cg, local;
         std::vector<Hit> own;
         if (!hits) own.resize(n_reads);
@@ -1200,7 +1465,13 @@ int np2_map_align_bytes(const np2_map_index_t *ix, const uint8_t *reads, uint64_
             while (r1 < n_reads && ends[r1] + 1 - from <= m.hooks.batch_bytes()) ++r1;
             local.clear();
             for (uint64_t i = r0; i < r1; ++i) local.push_back((uint32_t)(ends[i] - from));
+            if (tag_flags) tt.begin(r1 - r0);
             m.batch(reads + from, ends[r1 - 1] + 1 - from, local.data(), (uint32_t)(r1 - r0), out + r0, nullptr, rout + r0, &cg);
+            if (tag_flags) {
+                std::copy(tt.n_md.begin(), tt.n_md.end(), all.n_md.begin() + (ptrdiff_t)r0);
+                std::copy(tt.n_cs.begin(), tt.n_cs.end(), all.n_cs.begin() + (ptrdiff_t)r0);
+                all.md.insert(all.md.end(), tt.md.begin(), tt.md.end()), all.cs.insert(all.cs.end(), tt.cs.begin(), tt.cs.end());
+            }
             r0 = r1;
         }
         if (cigar) {
@@ -1208,19 +1479,43 @@ int np2_map_align_bytes(const np2_map_index_t *ix, const uint8_t *reads, uint64_
             for (uint64_t i = 0; i < n_reads; ++i) cigar_off[i + 1] = cigar_off[i] + rout[i].n_cigar;
             *cigar = chain_out(cg);
         }
+        if (md) offsets_of(all.n_md, md_off), *md = text_out(all.md);
+        if (cs) offsets_of(all.n_cs, cs_off), *cs = text_out(all.cs);
         return NP2_OK;
     }, np2h::io_set_error);
+}
+int np2_map_align_bytes(const np2_map_index_t *ix, const uint8_t *reads, uint64_t n, uint64_t n_reads, const np2_map_opts_t *map_opts,
+                        const np2_align_opts_t *align_opts, np2_map_hit_t *hits, np2_align_rec_t *recs, uint32_t **cigar, uint64_t *cigar_off) {
+    return map_align_bytes_impl(ix, reads, nullptr, n, n_reads, map_opts, align_opts, 0, hits, recs, cigar, cigar_off, nullptr, nullptr, nullptr, nullptr,
+                                "np2_map_align_bytes");
+}
+int np2_map_align_bytes_x(const np2_map_index_t *ix, const uint8_t *reads, const uint8_t *quals, uint64_t n, uint64_t n_reads,
+                          const np2_map_opts_t *map_opts, const np2_align_opts_t *align_opts, uint32_t out_flags, np2_map_hit_t *hits,
+                          np2_align_rec_t *recs, uint32_t **cigar, uint64_t *cigar_off, char **md, uint64_t *md_off, char **cs, uint64_t *cs_off) {
+    return map_align_bytes_impl(ix, reads, quals, n, n_reads, map_opts, align_opts, out_flags, hits, recs, cigar, cigar_off, md, md_off, cs, cs_off,
+                                "np2_map_align_bytes_x");
+}
+int np2_map_align_files_x(const np2_map_index_t *ix, const char *const *paths, int n_paths, const np2_map_opts_t *map_opts,
+                          const np2_align_opts_t *align_opts, uint32_t out_flags, const char *out_path, np2_map_stats_t *stats) {
+    return map_files_impl(ix, paths, n_paths, map_opts, align_opts, true, out_path, stats, "np2_map_align_files_x", out_flags);
 }
 
 static int map_align_host_impl(const uint8_t *asm_stream, uint64_t n_asm, const uint8_t *reads, uint64_t n, uint64_t n_reads,
                                const np2_map_opts_t *map_opts, const np2_align_opts_t *align_opts, const np2_map_weights_t *wts, np2_map_hit_t *hits,
-                               np2_align_rec_t *recs, uint32_t **cigar, uint64_t *cigar_off, const std::string name) {
+                               np2_align_rec_t *recs, uint32_t **cigar, uint64_t *cigar_off, const std::string name, uint32_t out_flags = 0,
+                               char **md = nullptr, uint64_t *md_off = nullptr, char **cs = nullptr, uint64_t *cs_off = nullptr) {
     return np2h::abi_guard([&] {
         const char *who = name.c_str();
         if (cigar) *cigar = nullptr;
         const np2map::Opts o = checked(map_opts, who);
         np2aln::Opts ao = checked_align(align_opts, who);
         const np2map::WeightSet *ws = checked_weights(wts, o, who);
+        checked_out_flags(out_flags, NP2_ALN_MD | NP2_ALN_CS | NP2_ALN_EQX, name);
+        check_tag_pairs(out_flags, md, md_off, cs, cs_off, name);
+        tl_tstats = np2_align_tag_stats_t{};
+        TagTexts tt;
+        tt.begin(n_reads);
+        std::vector<uint32_t> split;
         if (n_reads && !recs) throw Np2Error(NP2_E_ARG, name + ": recs is NULL");
         if ((cigar == nullptr) != (cigar_off == nullptr)) throw Np2Error(NP2_E_ARG, name + ": cigar and cigar_off go together");
         const std::vector<uint64_t> a_ends = ends_of(asm_stream, n_asm, who, "the assembly stream");
@@ -1254,6 +1549,16 @@ static int map_align_host_impl(const uint8_t *asm_stream, uint64_t n_asm, const 
                 rout[i] = np2aln::align_read(asm_stream + t_at, (uint32_t)(a_ends[(size_t)h.tid] - t_at), reads + from, h, ch.data(), o.k, ao,
                                              ao.max_cells, w, cg, c64);
                 for (int f = 0; f < np2aln::C_N; ++f) ctr[f] += c64[f];
+                if (out_flags && rout[i].tid >= 0) { // the same walk as the tag kernels', one caller
+                    const size_t cg_at = cg.size() - rout[i].n_cigar;
+                    const np2aln::TagIn in{asm_stream + t_at + rout[i].pos, reads + from, h.qlen, h.rev, cg.data() + cg_at, rout[i].n_cigar};
+                    split.clear();
+                    tags_of_record(in, out_flags, tt, i, &split);
+                    if (out_flags & NP2_ALN_EQX) {
+                        cg.resize(cg_at), cg.insert(cg.end(), split.begin(), split.end());
+                        rout[i].n_cigar = (uint32_t)split.size(), tl_tstats.eqx_words += split.size();
+                    }
+                }
             }
             from = ends[i] + 1;
         }
@@ -1264,6 +1569,9 @@ static int map_align_host_impl(const uint8_t *asm_stream, uint64_t n_asm, const 
             for (uint64_t i = 0; i < n_reads; ++i) cigar_off[i + 1] = cigar_off[i] + rout[i].n_cigar;
             *cigar = chain_out(cg);
         }
+        tl_tstats.md_bytes = tt.md.size(), tl_tstats.cs_bytes = tt.cs.size();
+        if (md) offsets_of(tt.n_md, md_off), *md = text_out(tt.md);
+        if (cs) offsets_of(tt.n_cs, cs_off), *cs = text_out(tt.cs);
         return NP2_OK;
     }, np2h::io_set_error);
 }
@@ -1278,6 +1586,79 @@ int np2_map_align_host_w(const uint8_t *asm_stream, uint64_t n_asm, const uint8_
                          np2_align_rec_t *recs, uint32_t **cigar, uint64_t *cigar_off) {
     return map_align_host_impl(asm_stream, n_asm, reads, n, n_reads, map_opts, align_opts, w, hits, recs, cigar, cigar_off,
                                "np2_map_align_host_w");
+}
+
+int np2_map_align_host_x(const uint8_t *asm_stream, uint64_t n_asm, const uint8_t *reads, uint64_t n, uint64_t n_reads,
+                         const np2_map_opts_t *map_opts, const np2_align_opts_t *align_opts, const np2_map_weights_t *w, uint32_t out_flags,
+                         np2_map_hit_t *hits, np2_align_rec_t *recs, uint32_t **cigar, uint64_t *cigar_off, char **md, uint64_t *md_off, char **cs,
+                         uint64_t *cs_off) {
+    return map_align_host_impl(asm_stream, n_asm, reads, n, n_reads, map_opts, align_opts, w, hits, recs, cigar, cigar_off, "np2_map_align_host_x",
+                               out_flags, md, md_off, cs, cs_off);
+}
+
+int np2_align_tags_host(const uint8_t *ref, uint64_t n_ref, const uint8_t *reads, uint64_t n_read_bytes, uint64_t n_recs, const uint64_t *t_off,
+                        const uint64_t *q_off, const uint32_t *cigar, const uint64_t *cigar_off, uint32_t out_flags, char **md, uint64_t *md_off,
+                        char **cs, uint64_t *cs_off, uint32_t **eqx, uint64_t *eqx_off) {
+    return np2h::abi_guard([&] {
+        const std::string who = "np2_align_tags_host";
+        const TagDoor d(ref, n_ref, reads, n_read_bytes, n_recs, t_off, q_off, cigar, cigar_off, out_flags, md, md_off, cs, cs_off, eqx, eqx_off, who);
+        TagTexts tt;
+        tt.begin(n_recs);
+        std::vector<uint32_t> split;
+        if (eqx) eqx_off[0] = 0;
+        for (uint64_t i = 0; i < n_recs; ++i) {
+            const np2aln::TagIn in{ref + t_off[i], reads + q_off[i], 0, 0, cigar + cigar_off[i], (uint32_t)(cigar_off[i + 1] - cigar_off[i])};
+            tags_of_record(in, d.flags, tt, i, &split);
+            if (eqx) eqx_off[i + 1] = split.size();
+        }
+        if (md) offsets_of(tt.n_md, md_off), *md = text_out(tt.md);
+        if (cs) offsets_of(tt.n_cs, cs_off), *cs = text_out(tt.cs);
+        if (eqx) *eqx = chain_out(split);
+        return NP2_OK;
+    }, np2h::io_set_error);
+}
+
+int np2_align_tags_device(int device, const uint8_t *ref, uint64_t n_ref, const uint8_t *reads, uint64_t n_read_bytes, uint64_t n_recs,
+                          const uint64_t *t_off, const uint64_t *q_off, const uint32_t *cigar, const uint64_t *cigar_off, uint32_t out_flags, char **md,
+                          uint64_t *md_off, char **cs, uint64_t *cs_off, uint32_t **eqx, uint64_t *eqx_off) {
+    return np2h::abi_guard([&] {
+        const std::string who = "np2_align_tags_device";
+        // every argument is checked before the first device call: a record's columns lie inside the two buffers
+        const TagDoor d(ref, n_ref, reads, n_read_bytes, n_recs, t_off, q_off, cigar, cigar_off, out_flags, md, md_off, cs, cs_off, eqx, eqx_off, who);
+        tl_tstats = np2_align_tag_stats_t{};
+        Stream s(device);
+        DevBuf<uint8_t> d_ref, d_reads;
+        DevBuf<uint64_t> d_t, d_q, d_co;
+        DevBuf<uint32_t> d_cig;
+        d_ref.cached = d_reads.cached = d_t.cached = d_q.cached = d_co.cached = d_cig.cached = true;
+        d_ref.ensure(n_ref + 1), d_reads.ensure(n_read_bytes + 1), d_t.ensure(n_recs + 1), d_q.ensure(n_recs + 1), d_co.ensure(n_recs + 1);
+        d_cig.ensure(d.n_words + 1);
+        std::vector<uint64_t> co(n_recs + 1); // (relative to the first record's words)
+        for (uint64_t i = 0; i <= n_recs; ++i) co[i] = cigar_off[i] - cigar_off[0];
+        if (n_ref) HIPCHK(hipMemcpyAsync(d_ref.p, ref, n_ref, hipMemcpyHostToDevice, s.st));
+        if (n_read_bytes) HIPCHK(hipMemcpyAsync(d_reads.p, reads, n_read_bytes, hipMemcpyHostToDevice, s.st));
+        if (n_recs) HIPCHK(hipMemcpyAsync(d_t.p, t_off, n_recs * 8, hipMemcpyHostToDevice, s.st));
+        if (n_recs) HIPCHK(hipMemcpyAsync(d_q.p, q_off, n_recs * 8, hipMemcpyHostToDevice, s.st));
+        HIPCHK(hipMemcpyAsync(d_co.p, co.data(), (n_recs + 1) * 8, hipMemcpyHostToDevice, s.st));
+        if (d.n_words) HIPCHK(hipMemcpyAsync(d_cig.p, cigar + cigar_off[0], d.n_words * 4, hipMemcpyHostToDevice, s.st));
+        HIPCHK(hipStreamSynchronize(s.st)); // (co is this call's own memory)
+        np2::TagJob j{};
+        j.ref = d_ref.p, j.reads = d_reads.p, j.t_off = d_t.p, j.q_off = d_q.p, j.cig_off = d_co.p, j.cigar = d_cig.p;
+        j.n = (uint32_t)n_recs, j.flags = d.flags;
+        TagRun tg;
+        tl_tstats.tags_ms = tg.run(s, j);
+        tl_tstats.md_bytes = tg.md.size(), tl_tstats.cs_bytes = tg.cs.size(), tl_tstats.eqx_words = tg.eqx.size();
+        if (md) std::copy(tg.md_off.begin(), tg.md_off.end(), md_off), *md = text_out(tg.md);
+        if (cs) std::copy(tg.cs_off.begin(), tg.cs_off.end(), cs_off), *cs = text_out(tg.cs);
+        if (eqx) std::copy(tg.eqx_off.begin(), tg.eqx_off.end(), eqx_off), *eqx = chain_out(tg.eqx);
+        return NP2_OK;
+    }, np2h::io_set_error);
+}
+
+int np2_map_align_last_tag_stats(np2_align_tag_stats_t *stats) {
+    if (!stats) return np2h::io_set_error(NP2_E_ARG, "np2_map_align_last_tag_stats: stats is NULL");
+    *stats = tl_tstats;
+    return NP2_OK;
 }
 
 int np2_sam_from_reads(np2_ctx_t *cx, const np2_map_index_t *ix, const char *const *paths, int n_paths, const np2_map_opts_t *map_opts,

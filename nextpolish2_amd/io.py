@@ -89,7 +89,12 @@ class np2_align_stats_t(C.Structure):
                [(f, C.c_float) for f in ("pins_ms", "classify_ms", "dp_ms", "assemble_ms", "write_ms")]
 
 
-assert C.sizeof(np2_align_opts_t) == 32 and C.sizeof(np2_align_stats_t) == 96
+class np2_align_tag_stats_t(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("md_bytes", "cs_bytes", "eqx_words", "qual_reads")] + [("tags_ms", C.c_float)]
+
+
+assert C.sizeof(np2_align_opts_t) == 32 and C.sizeof(np2_align_stats_t) == 96 and C.sizeof(np2_align_tag_stats_t) == 40
+ALN_QUAL, ALN_MD, ALN_CS, ALN_EQX = 1, 2, 4, 8  # NP2_ALN_*
 ALIGN_DEFAULTS = dict(match=1, mismatch=4, gap_open=6, gap_ext=2, band=32, end_bonus=5, ext_max=2048, max_cells=1 << 23)
 # np2_align_rec_t
 ALIGN_REC_DTYPE = np.dtype([("tid", "<i4")] + [(f, "<u4") for f in ("flag", "pos", "end", "mapq", "n_cigar", "nm")] + [("as", "<i4")])
@@ -359,6 +364,13 @@ def _bind_map(L):
     L.np2_map_align_host.argtypes = [vp, u64, vp, u64, u64, mo, ao, vp, vp, C.POINTER(vp), vp]
     L.np2_map_align_last_stats.argtypes = [C.POINTER(np2_align_stats_t)]
     L.np2_map_align_host_w.argtypes = [vp, u64, vp, u64, u64, mo, ao, vp, vp, vp, C.POINTER(vp), vp]
+    u32 = C.c_uint32
+    L.np2_map_align_bytes_x.argtypes = [vp, vp, vp, u64, u64, mo, ao, u32, vp, vp, C.POINTER(vp), vp, C.POINTER(vp), vp, C.POINTER(vp), vp]
+    L.np2_map_align_files_x.argtypes = [vp, C.POINTER(C.c_char_p), C.c_int, mo, ao, u32, C.c_char_p, C.POINTER(np2_map_stats_t)]
+    L.np2_map_align_host_x.argtypes = [vp, u64, vp, u64, u64, mo, ao, vp, u32, vp, vp, C.POINTER(vp), vp, C.POINTER(vp), vp, C.POINTER(vp), vp]
+    L.np2_align_tags_device.argtypes = [C.c_int, vp, u64, vp, u64, u64, vp, vp, vp, vp, u32] + [C.POINTER(vp), vp] * 3
+    L.np2_align_tags_host.argtypes = [vp, u64, vp, u64, u64, vp, vp, vp, vp, u32] + [C.POINTER(vp), vp] * 3
+    L.np2_map_align_last_tag_stats.argtypes = [C.POINTER(np2_align_tag_stats_t)]
     so, pvp = C.POINTER(np2_sam_opts_t), C.POINTER(vp)
     L.np2_sam_from_reads.argtypes = [vp, vp, C.POINTER(C.c_char_p), C.c_int, mo, ao, so, C.c_uint32, pvp]
     L.np2_sam_from_read_bytes.argtypes = [vp, vp, vp, u64, u64, C.c_char_p, mo, ao, so, C.c_uint32, pvp]
@@ -1536,6 +1548,25 @@ class MapIndex:
         o, ao = self._opts(kw), align_opts(**akw)
         return _align_result(L, lambda *a: L.np2_map_align_bytes(self._h, a[0], a[1], a[2], C.byref(o), C.byref(ao), a[3], a[4], a[5], a[6]), s, n)
 
+    def align_x(self, reads, quals=None, md=False, cs=False, eqx=False, **kw):
+        """np2_map_align_bytes_x: align() with the opt-in outputs (np2_io.h, "Tags") -> (hits, recs, cigar, cigar_off, md, cs): with
+        eqx the CIGAR words hold = (7) and X (8) in place of M; md and cs are lists of bytes, one per read (b"" for an unaligned
+        read), or None when not asked for.  quals: a quality stream of the reads' shape or a list with one entry per read (None or
+        b"": that read has none); it is checked, and counted in align_last_tag_stats()."""
+        L = self._L
+        s, n = _stream_of(reads)
+        akw = {f: kw.pop(f) for f in list(kw) if f in ALIGN_DEFAULTS}
+        o, ao = self._opts(kw), align_opts(**akw)
+        flags = (ALN_MD if md else 0) | (ALN_CS if cs else 0) | (ALN_EQX if eqx else 0)
+        qs = None
+        if quals is not None:
+            flags |= ALN_QUAL
+            qs = _qual_stream(quals, s, n)
+            if len(qs) != len(s):
+                raise ValueError(f"the quality stream has {len(qs)} bytes, the read stream {len(s)}")
+        return _align_result_x(L, lambda *a: L.np2_map_align_bytes_x(self._h, a[0], None if qs is None or not len(qs) else qs.ctypes.data, a[1], a[2],
+                                                                     C.byref(o), C.byref(ao), flags, *a[3:]), s, n, md, cs)
+
 
 def map_reads(index, reads, chains=False, **kw):
     """np2_map_bytes: reads (a separator stream or a list of sequences) against a MapIndex -> hits, a MAP_HIT_DTYPE array
@@ -1593,6 +1624,94 @@ def align_last_stats():
     return {f: getattr(st, f) for f, _ in np2_align_stats_t._fields_}
 
 
+def align_last_tag_stats():
+    """np2_map_align_last_tag_stats: bytes and words of the opt-in outputs, reads that had qualities and the tag kernels' time (HIP
+    events, ms) of this thread's last np2_map_align_*_x / np2_align_tags_* call"""
+    st = np2_align_tag_stats_t()
+    _io_check(_bind().np2_map_align_last_tag_stats(C.byref(st)))
+    return {f: getattr(st, f) for f, _ in np2_align_tag_stats_t._fields_}
+
+
+def _qual_stream(quals, s, n):
+    """a quality stream beside the read stream s: as it is, or from a list with one entry per read (None / b"": 0xFF bytes)"""
+    if not isinstance(quals, (list, tuple)):
+        return np.frombuffer(bytes(quals), np.uint8)
+    if len(quals) != n:
+        raise ValueError(f"{n} reads and {len(quals)} quality strings")
+    ends = np.flatnonzero(s == 10)
+    out, start = [], 0
+    for q, e in zip(quals, ends):
+        out.append(bytes(q) if q else b"\xff" * int(e - start))
+        out.append(b"\n")
+        start = int(e) + 1
+    return np.frombuffer(b"".join(out), np.uint8)
+
+
+def _texts(L, pc, off, n):
+    """a malloc'ed text block and its offsets -> a list of n bytes objects; the block is released"""
+    try:
+        whole = C.string_at(pc.value, int(off[n])) if int(off[n]) else b""
+    finally:
+        L.np2_free(pc)
+    return [whole[int(off[i]):int(off[i + 1])] for i in range(n)]
+
+
+def _align_result_x(L, call, s, n, md, cs):
+    hits, recs = np.zeros(n, MAP_HIT_DTYPE), np.zeros(n, ALIGN_REC_DTYPE)
+    pc, off = C.c_void_p(), np.zeros(n + 1, np.uint64)
+    pm, moff, px, xoff = C.c_void_p(), np.zeros(n + 1, np.uint64), C.c_void_p(), np.zeros(n + 1, np.uint64)
+    _io_check(call(s.ctypes.data if len(s) else None, len(s), n, hits.ctypes.data if n else None, recs.ctypes.data if n else None, C.byref(pc),
+                   off.ctypes.data, C.byref(pm) if md else None, moff.ctypes.data if md else None, C.byref(px) if cs else None,
+                   xoff.ctypes.data if cs else None))
+    try:
+        m = int(off[n])
+        from .api import _Raw
+        cigar = np.asarray(_Raw(pc.value, m, "<u4")).copy() if m else np.zeros(0, np.uint32)
+    finally:
+        L.np2_free(pc)
+    return hits, recs, cigar, off, (_texts(L, pm, moff, n) if md else None), (_texts(L, px, xoff, n) if cs else None)
+
+
+def _align_tags(L, call, ref, reads, t_off, q_off, cigars, md, cs, eqx):
+    ref, reads = np.frombuffer(bytes(ref), np.uint8), np.frombuffer(bytes(reads), np.uint8)
+    n = len(cigars)
+    t_off, q_off = np.ascontiguousarray(t_off, np.uint64), np.ascontiguousarray(q_off, np.uint64)
+    if len(t_off) != n or len(q_off) != n:
+        raise ValueError(f"{n} CIGARs, {len(t_off)} t_off and {len(q_off)} q_off")
+    coff = np.zeros(n + 1, np.uint64)
+    coff[1:] = np.cumsum([len(c) for c in cigars])
+    words = np.ascontiguousarray(np.concatenate([np.asarray(c, np.uint32).reshape(-1) for c in cigars]) if n else np.zeros(0), np.uint32)
+    flags = (ALN_MD if md else 0) | (ALN_CS if cs else 0) | (ALN_EQX if eqx else 0)
+    pm, moff, px, xoff, pe, eoff = C.c_void_p(), np.zeros(n + 1, np.uint64), C.c_void_p(), np.zeros(n + 1, np.uint64), C.c_void_p(), np.zeros(n + 1, np.uint64)
+    _io_check(call(ref.ctypes.data if len(ref) else None, len(ref), reads.ctypes.data if len(reads) else None, len(reads), n,
+                   t_off.ctypes.data if n else None, q_off.ctypes.data if n else None, words.ctypes.data if len(words) else None, coff.ctypes.data, flags,
+                   C.byref(pm) if md else None, moff.ctypes.data if md else None, C.byref(px) if cs else None, xoff.ctypes.data if cs else None,
+                   C.byref(pe) if eqx else None, eoff.ctypes.data if eqx else None))
+    split = None
+    if eqx:
+        try:
+            from .api import _Raw
+            whole = np.asarray(_Raw(pe.value, int(eoff[n]), "<u4")).copy() if int(eoff[n]) else np.zeros(0, np.uint32)
+        finally:
+            L.np2_free(pe)
+        split = [whole[int(eoff[i]):int(eoff[i + 1])] for i in range(n)]
+    return (_texts(L, pm, moff, n) if md else None), (_texts(L, px, xoff, n) if cs else None), split
+
+
+def align_tags_host(ref, reads, t_off, q_off, cigars, md=True, cs=True, eqx=True):
+    """np2_align_tags_host (no device): the tag walk on caller-built records -> (md, cs, eqx), each a list with one entry per
+    record (bytes, bytes, a uint32 array of CIGAR words) or None when not asked for.  ref, reads: byte buffers; record i's
+    reference columns begin at ref[t_off[i]], its read, already oriented, at reads[q_off[i]]; cigars[i]: its words (len << 4 | op)."""
+    L = _bind()
+    return _align_tags(L, L.np2_align_tags_host, ref, reads, t_off, q_off, cigars, md, cs, eqx)
+
+
+def align_tags_device(ref, reads, t_off, q_off, cigars, md=True, cs=True, eqx=True, device=0):
+    """np2_align_tags_device: align_tags_host's records through the tag kernels"""
+    L = _bind()
+    return _align_tags(L, lambda *a: L.np2_align_tags_device(device, *a), ref, reads, t_off, q_off, cigars, md, cs, eqx)
+
+
 def _align_result(L, call, s, n):
     hits, recs = np.zeros(n, MAP_HIT_DTYPE), np.zeros(n, ALIGN_REC_DTYPE)
     pc, off = C.c_void_p(), np.zeros(n + 1, np.uint64)
@@ -1607,12 +1726,19 @@ def _align_result(L, call, s, n):
     return hits, recs, cigar, off
 
 
-def map_align_files(index, paths, out_path, **kw):
-    """np2_map_align_files: read files -> the SAM file out_path (BGZF when it ends in .gz / .bgz) -> the mapper's stats dict"""
+def map_align_files(index, paths, out_path, qual=False, md=False, cs=False, eqx=False, **kw):
+    """np2_map_align_files: read files -> the SAM file out_path (BGZF when it ends in .gz / .bgz) -> the mapper's stats dict.
+    With qual / md / cs / eqx (np2_map_align_files_x; np2_io.h, "Tags"): QUAL from FASTQ input, MD:Z: and cs:Z: behind s2:i:,
+    = and X in the CIGAR."""
     L = _bind()
     arr, n = _paths(paths)
     akw = {f: kw.pop(f) for f in list(kw) if f in ALIGN_DEFAULTS}
     o, ao, st = index._opts(kw), align_opts(**akw), np2_map_stats_t()
+    flags = (ALN_QUAL if qual else 0) | (ALN_MD if md else 0) | (ALN_CS if cs else 0) | (ALN_EQX if eqx else 0)
+    if flags:
+        _io_check(L.np2_map_align_files_x(index._h, arr, n, C.byref(o), C.byref(ao), flags, None if out_path is None else os.fspath(out_path).encode(),
+                                          C.byref(st)))
+        return _map_stats_dict(st)
     _io_check(L.np2_map_align_files(index._h, arr, n, C.byref(o), C.byref(ao), None if out_path is None else os.fspath(out_path).encode(),
                                     C.byref(st)))
     return _map_stats_dict(st)
@@ -1651,3 +1777,16 @@ def map_align_host(asm, reads, weights=None, **kw):
                                                                   C.byref(ao), wh, x[3], x[4], x[5], x[6]), s, n)
     return _align_result(L, lambda *x: L.np2_map_align_host(a.ctypes.data if len(a) else None, len(a), x[0], x[1], x[2], C.byref(o), C.byref(ao),
                                                             x[3], x[4], x[5], x[6]), s, n)
+
+
+def map_align_host_x(asm, reads, weights=None, md=False, cs=False, eqx=False, **kw):
+    """np2_map_align_host_x (no device): map_align_host with the opt-in outputs -> what MapIndex.align_x returns"""
+    L = _bind()
+    a, _ = _stream_of(asm)
+    s, n = _stream_of(reads)
+    akw = {f: kw.pop(f) for f in list(kw) if f in ALIGN_DEFAULTS}
+    o, ao = map_opts(**kw), align_opts(**akw)
+    wh = _weights_handle(weights)
+    flags = (ALN_MD if md else 0) | (ALN_CS if cs else 0) | (ALN_EQX if eqx else 0)
+    return _align_result_x(L, lambda *x: L.np2_map_align_host_x(a.ctypes.data if len(a) else None, len(a), x[0], x[1], x[2], C.byref(o), C.byref(ao),
+                                                                wh, flags, *x[3:]), s, n, md, cs)

@@ -3,7 +3,8 @@ by base and written as SAM (the recipe's `winnowmap -ax` step; its SAM pipes int
 
     python -m nextpolish2_amd.map asm.fa[.gz] hifi.fa[.gz] [more reads ...] [-o map.paf[.gz]] [-k 19] [-w 19] [--max_occ 200]
                                   [--lookback 64] [--max_gap 10000] [--bandwidth 500] [--min_cnt 3] [--min_score 40] [--stats FILE]
-                                  [-a [-A 1] [-B 4] [-O 6] [-E 2] [--band 32] [--end_bonus 5] [--ext_max 2048] [--max_cells N]]
+                                  [-a [-A 1] [-B 4] [-O 6] [-E 2] [--band 32] [--end_bonus 5] [--ext_max 2048] [--max_cells N]
+                                      [--qual] [--MD] [--cs] [--eqx]]
                                   [-W repetitive_k15.txt | --rep [distinct=0.9998 | min_count=N]]
 
 One line per mapped read, in read order: qname qlen qs qe strand tname tlen ts te matches block mapq tp:A:P cm:i: s1:i: s2:i:
@@ -13,6 +14,12 @@ the minimap2 binary).  An output path ending in .gz / .bgz is written as BGZF, c
 With -a: a SAM header and one line per read, in read order: qname flag rname pos mapq CIGAR * 0 0 SEQ * NM:i: AS:i: cm:i: s1:i:
 s2:i: (the rule: np2_map_align_*; M, I, D and S only, gaps left-aligned; an unmapped read has flag 4).  --stats then writes a
 second header and row, ALIGN_STATS_HEADER.
+
+With -a and --qual / --MD / --cs / --eqx (the rule: np2_map_align_*, "Tags"): QUAL carries a FASTQ read's base qualities
+(reversed with flag 16), MD:Z: and the short cs:Z: follow s2:i:, and M becomes = and X.  `map -a --qual --MD hifi.fastq.gz |
+samsort - --full -o hifi.map.sort.bam` is the `minimap2 -a ... | samtools sort` of the reference's benchmark recipe (step 5:
+the BAM a variant caller reads).  (-Q is not used: minimap2 gives it the opposite meaning.)  --stats then gains a third header
+and row, TAG_STATS_HEADER.
 
 With -W FILE (winnowmap's -W): the k-mers of the list (one a line, as python -m nextpolish2_amd.repkmers or meryl print
 writes it; plain or gzip) are made less likely to win a minimizer window, so that the unique k-mers inside repeats become
@@ -92,6 +99,16 @@ def align_stats_row(stats):
     return "\t".join(ALIGN_STATS_HEADER) + "\n" + "\t".join(cells) + "\n"
 
 
+TAG_STATS_HEADER = ("md_bytes", "cs_bytes", "eqx_words", "qual_reads", "tags_ms")
+TAG_FLAGS = (("qual", "--qual"), ("md", "--MD"), ("cs", "--cs"), ("eqx", "--eqx"))
+
+
+def tag_stats_row(stats):
+    """--stats with -a and one of TAG_FLAGS: a third header line and TSV row"""
+    cells = [str(int(stats[f])) for f in TAG_STATS_HEADER[:4]] + ["%.3f" % float(stats["tags_ms"])]
+    return "\t".join(TAG_STATS_HEADER) + "\n" + "\t".join(cells) + "\n"
+
+
 def build_parser():
     from .io import ALIGN_DEFAULTS as AD
     from .io import MAP_DEFAULTS as D
@@ -115,6 +132,10 @@ def build_parser():
                  ext_max="read bases an end extension considers", max_cells="largest matrix; a read beyond it is written unmapped")
     for f, flag in ALIGN_FLAGS:
         p.add_argument(flag, dest=f, type=int, default=AD[f], metavar="N", help=f"with -a: {helps[f]} [{AD[f]}]")
+    p.add_argument("--qual", dest="qual", action="store_true", help="with -a: write a FASTQ read's base qualities as QUAL")
+    p.add_argument("--MD", dest="md", action="store_true", help="with -a: write the MD:Z: tag")
+    p.add_argument("--cs", dest="cs", action="store_true", help="with -a: write the short cs:Z: tag")
+    p.add_argument("--eqx", dest="eqx", action="store_true", help="with -a: write = and X in place of M")
     g = p.add_mutually_exclusive_group()
     g.add_argument("-W", dest="weights", default=None, metavar="FILE",
                    help="down-weight the k-mers of this list in minimizer sampling (winnowmap -W; one k-mer a line, [GZIP]; 11 <= k <= 15)")
@@ -126,7 +147,12 @@ def build_parser():
 def main(argv=None):
     from . import api
     from . import io as np2io
-    a = build_parser().parse_args(argv)
+    parser = build_parser()
+    a = parser.parse_args(argv)
+    tags = {f: getattr(a, f) for f, _ in TAG_FLAGS}
+    for f, flag in TAG_FLAGS:
+        if tags[f] and not a.sam:
+            parser.error(f"{flag} needs -a (it is an output of the base-level alignment)")
     wk = 0
     if a.weights is not None:
         try:
@@ -166,8 +192,9 @@ def main(argv=None):
                     weights.close()
                 if a.sam:
                     np2io.align_opts(**akw)
-                    stats = np2io.map_align_files(ix, a.reads, out, **kw, **akw)
+                    stats = np2io.map_align_files(ix, a.reads, out, **tags, **kw, **akw)
                     align_stats = np2io.align_last_stats()
+                    tag_stats = np2io.align_last_tag_stats() if any(tags.values()) else None
                 else:
                     stats = np2io.map_files(ix, a.reads, out, **kw)
                 index_ms, wstats = ix.build_ms, (ix.weights_k, ix.weights_listed)
@@ -182,6 +209,8 @@ def main(argv=None):
                 f.write(stats_row(stats, index_ms, wstats))
                 if a.sam:
                     f.write(align_stats_row(align_stats))
+                    if tag_stats is not None:
+                        f.write(tag_stats_row(tag_stats))
     finally:
         if tmp is not None and os.path.exists(tmp):
             os.remove(tmp)
