@@ -469,7 +469,7 @@ int np2_rep_files(int device, const char *const *paths, int n_paths, const np2_r
  *     \n and \r\n end a line; a k-mer given in either or both orientations sets the one canonical bit; duplicates are
  *     allowed; a bad letter or a line of another length is NP2_E_ARG with the 1-based line number; an empty file is the empty
  *     set; plain text or gzip.  (python -m nextpolish2_amd.repkmers writes such a list.)
- *   Not built: secondary and supplementary chains; -f occurrence fractions; homopolymer compression; weights for k >= 16 or
+ *   Not built: -f occurrence fractions (secondary and supplementary chains: "More chains", below); homopolymer compression; weights for k >= 16 or
  *     per-k-mer weights other than the eighth power;
  *     several devices; an index beyond one device's memory (base-level alignment and SAM: np2_map_align_*, below).
  *     NP2_E_UNSUPPORTED: an assembly of 2^32 bytes or more, a sequence or read longer than 2^31 - 1, a single read with more
@@ -541,6 +541,84 @@ int np2_map_index_weights(const np2_map_index_t *ix, uint32_t *k, uint64_t *n_li
 int np2_map_host_w(const uint8_t *asm_stream, uint64_t n_asm, const uint8_t *reads, uint64_t n, uint64_t n_reads, const np2_map_opts_t *opts,
                    const np2_map_weights_t *w, np2_map_hit_t *hits, uint32_t **chain, uint64_t *chain_off);
 
+/* ---- More chains: supplementary and secondary chains of a read, to PAF (what `minimap2 --secondary=yes -N` and its
+ * supplementary lines report; the polisher's -s and -S doors read such records) ------------------------------------------------
+ * THE RULE IS DEFINED HERE, on minimap2's published chain selection (mm_chain_backtrack, mm_set_parent, mm_select_sub).  No
+ * minimap2 binary was at hand: equality with its output is not claimed and not tested.  No floating point is used.
+ *   Options (np2_map_multi_opts_t; defaults in brackets): max_chains 1 .. 16 [1] selections per read, the primary among them (1
+ *     is the mapper above: no further kernel is launched); supplementary 0 / 1 [0] report supplementary chains; secondary_n
+ *     0 .. 15 [0] secondaries kept per parent; mask_pm 1 .. 1000 [500] the overlap threshold and pri_pm 0 .. 1000 [800] the
+ *     secondary-to-parent score ratio, both per mille.  Anything else is NP2_E_ARG, before the first device call.
+ *   Selection.  f, p, the primary chain, its marks, base[] and the primary's hit are exactly those of the chain rule above.  Then
+ *     up to max_chains - 1 further selections.  In each, over the unmarked anchors, score(i) = f[i] - base[i], base as the sweep
+ *     above defines it against the current marks; the largest score is taken and, of equal scores, the smallest i; a score
+ *     below min_score ends the selections (so does a read with no unmarked anchor, or an unmapped primary).  The chain runs from
+ *     i back through p while anchors are unmarked; its anchors are marked and base is swept again.  A chain with fewer than
+ *     min_cnt anchors is dropped, but it stays marked and has used up a selection.  f is not monotone along p (f[i] only has to
+ *     exceed k), so scores need not fall from one selection to the next: the rule is this procedure.  The first further
+ *     selection's score is the primary's s2 whenever s2 >= min_score.
+ *   Hit of a further chain.  As the primary's, from the chain's own anchors: interval, rev, tid, matches (k plus min(k, dr, dq)
+ *     per later anchor), block and n; s1 is its score.
+ *   Classes, in selection order over the chains that were not dropped; the primary is the first parent.  On forward read
+ *     coordinates [qs, qe), with ov the overlap of c and P: c is SECONDARY to the first earlier parent P with ov * 1000 >
+ *     mask_pm * min(len_c, len_P) (strict); with no such P it is a parent itself and SUPPLEMENTARY.  A secondary is kept when
+ *     s1_c * 1000 >= pri_pm * s1_P, P has fewer than secondary_n kept secondaries, and P itself is reported; a supplementary is
+ *     kept (reported) only with supplementary = 1, but is a parent either way.  A chain that is classed but not kept still
+ *     counts toward its parent's s2.
+ *   mapq.  The primary keeps its s2 and mapq in every bit.  A supplementary has s2 = the largest s1 among the chains classed
+ *     secondary to it (0 if none) and mapq = the formula above on (s1, s2, n).  A secondary has s2 = 0 and mapq 0.
+ *   Units.  A read's units are its primary (mapped or not: unit 0 is the hit of the plain doors) and its kept further chains in
+ *     selection order: cls 0 primary, 1 supplementary, 2 secondary; parent is the read-local unit a secondary belongs to, and a
+ *     parent's own place otherwise.
+ *   PAF.  A read's lines are the primary's first, byte for byte the plain line, then the kept others in selection order, with
+ *     tp:A:P for a supplementary and tp:A:S for a secondary.
+ *   Alignment (np2_map_align_*_m).  The aligner's rule (below) is unchanged and runs once per unit: a read together with one
+ *     kept chain, aligned with that chain's hit and that chain's exported anchors (the job's optional unit_read indirection,
+ *     csrc/np2_align.hpp; null is the plain doors' read-indexed job).  Then a read's units are settled: if its primary is
+ *     unmapped or overflows max_cells the read is written as the plain doors write it and its other units are dropped; a
+ *     further unit that overflows is dropped, and so is a secondary whose parent was dropped; parents are renumbered.  Every
+ *     further unit dropped here is counted in overflow_units.
+ *   SAM.  A read's records are adjacent: the primary, then the kept others in selection order.  FLAG gets | 2048 for a
+ *     supplementary and | 256 for a secondary record.  Clips are always soft and every record carries the full SEQ and, with
+ *     NP2_ALN_QUAL, the full QUAL: what `minimap2 -Y --secondary-seq` writes.  NP2_ALN_MD, _CS and _EQX apply to every record
+ *     through the one tag walk.  When a read has two or more aligned parent-class records (primary, supplementary), each of
+ *     them gets SA:Z: as its last field, after cs:Z:, with rname,pos1,+|-,CIGAR,mapq,NM; for each other parent-class record,
+ *     the primary first, then selection order; that CIGAR is in M / I / D / S form even under NP2_ALN_EQX.  With max_chains = 1
+ *     the text is np2_map_align_files_x's bytes.
+ *   Not built: hard clips and SEQ * for supplementary and secondary records; units through np2_sam_from_reads* / k_alnpack (cli
+ *     --from_reads keeps refusing multi-chain mapping) and the polisher's -S through the SAM door (it reads secondaries from a
+ *     BAM: samsort --full writes one).  The scratch of a group of reads is (max_chains - 1) slots of 64 bytes a read.
+ * Stats: np2_map_last_multi_stats, this thread's last _m call; more_ms is the HIP-event time of the selection kernel, its scan
+ * and the units' packing (0 from the host twins and with max_chains = 1). */
+typedef struct np2_map_multi_opts {
+    uint32_t max_chains, supplementary, secondary_n, mask_pm, pri_pm;
+} np2_map_multi_opts_t;
+typedef struct np2_map_multi_stats {
+    uint64_t units;                  /* all units, the primaries (mapped or not) among them */
+    uint64_t selections;             /* further selections that took a chain */
+    uint64_t dropped_min_cnt;        /* ... dropped with fewer than min_cnt anchors */
+    uint64_t dropped_secondary;      /* ... classed secondary and not kept (pri_pm, secondary_n, or a parent that is not reported) */
+    uint64_t kept_supplementary, kept_secondary;
+    uint64_t overflow_units;         /* np2_map_align_*_m: further units dropped when the read's units were settled */
+    float more_ms;
+} np2_map_multi_stats_t;
+/* np2_map_bytes per unit.  unit_off[n_reads + 1] is the caller's: read i's units are unit_off[i] .. unit_off[i + 1], one at
+ * the least.  *hits, *cls, *parent (np2_free) have unit_off[n_reads] entries.  With chain and chain_off (both or neither):
+ * *chain_off (np2_free) has one entry more than there are units, *chain the units' anchors as np2_map_bytes gives the
+ * primaries'.  With max_chains = 1 the arrays are np2_map_bytes' and no further kernel is launched. */
+int np2_map_bytes_m(const np2_map_index_t *ix, const uint8_t *reads, uint64_t n, uint64_t n_reads, const np2_map_opts_t *opts,
+                    const np2_map_multi_opts_t *multi, uint64_t *unit_off, np2_map_hit_t **hits, uint8_t **cls, uint32_t **parent,
+                    uint32_t **chain, uint64_t **chain_off);
+/* np2_map_files with the further chains' lines */
+int np2_map_files_m(const np2_map_index_t *ix, const char *const *paths, int n_paths, const np2_map_opts_t *opts,
+                    const np2_map_multi_opts_t *multi, const char *out_path, np2_map_stats_t *stats);
+/* host only, no device: np2_map_host_w per unit (w NULL or empty: unweighted) */
+int np2_map_host_m(const uint8_t *asm_stream, uint64_t n_asm, const uint8_t *reads, uint64_t n, uint64_t n_reads, const np2_map_opts_t *opts,
+                   const np2_map_multi_opts_t *multi, const np2_map_weights_t *w, uint64_t *unit_off, np2_map_hit_t **hits, uint8_t **cls,
+                   uint32_t **parent, uint32_t **chain, uint64_t **chain_off);
+int np2_map_last_multi_stats(np2_map_multi_stats_t *stats);
+/* (the units aligned: np2_map_align_*_m, behind np2_map_align_last_tag_stats below) */
+
 /* ---- the primary chain as a base-level alignment: chains to SAM (the recipe's `winnowmap -ax` / `minimap2 -a`, whose SAM the
  * polisher reads) ----------------------------------------------------------------------------------------------------------------
  * THE RULE IS DEFINED HERE, in the manner of minimap2's alignment between chained anchors with one affine piece (-A1 -B4 -O6
@@ -581,7 +659,8 @@ int np2_map_host_w(const uint8_t *asm_stream, uint64_t n_asm, const uint8_t *rea
  *     qname flag rname pos+1 mapq CIGAR * 0 0 SEQ * NM:i: AS:i: cm:i: s1:i: s2:i: (SEQ reverse-complemented with flag 16: ACGT
  *     in their case, any other byte kept), or qname 4 * 0 0 * * 0 0 SEQ * for an unmapped or overflowed read.  QUAL is * unless
  *     NP2_ALN_QUAL asks for it (Tags, below).
- *   Not built: the second affine piece (-O26 -E1); z-drop and supplementary records; direct BAM output.  (The records reach the
+ *   Not built: the second affine piece (-O26 -E1); z-drop; direct BAM output (supplementary and secondary records:
+ *     np2_map_align_*_m, "More chains" above).  (The records reach the
  *     polisher without SAM text through np2_sam_from_reads, below.)
  * The index keeps the assembly's bytes on the device for this (one byte per assembly base more than the minimizers).  Traceback
  * bits take one byte per matrix cell in a device buffer budgeted per group of whole reads (2^30 bytes; test hook
@@ -689,6 +768,35 @@ int np2_align_tags_host(const uint8_t *ref, uint64_t n_ref, const uint8_t *reads
                         const uint64_t *q_off, const uint32_t *cigar, const uint64_t *cigar_off, uint32_t out_flags, char **md, uint64_t *md_off,
                         char **cs, uint64_t *cs_off, uint32_t **eqx, uint64_t *eqx_off);
 int np2_map_align_last_tag_stats(np2_align_tag_stats_t *stats);
+
+/* ---- More chains, aligned ---- */
+/* The units aligned (the rule: "More chains", Alignment and SAM).  Every pointer is np2_free-owned, one entry per unit unless it
+ * says otherwise; md / md_off and cs / cs_off are NULL unless out_flags asks for them (np2_map_align_bytes_x's flags). */
+typedef struct np2_map_units {
+    uint64_t n_units;
+    np2_map_hit_t *hits;
+    uint8_t *cls;
+    uint32_t *parent;
+    np2_align_rec_t *recs;           /* flag holds 16 only: a writer adds 2048 / 256 from cls */
+    uint32_t *cigar;
+    uint64_t *cigar_off;             /* [n_units + 1] */
+    char *md;
+    uint64_t *md_off;                /* [n_units + 1] */
+    char *cs;
+    uint64_t *cs_off;                /* [n_units + 1] */
+} np2_map_units_t;
+/* np2_map_align_bytes_x per unit; unit_off[n_reads + 1] is the caller's, *out is filled (zeroed first) */
+int np2_map_align_bytes_m(const np2_map_index_t *ix, const uint8_t *reads, const uint8_t *quals /* NULL: none */, uint64_t n, uint64_t n_reads,
+                          const np2_map_opts_t *map_opts, const np2_map_multi_opts_t *multi, const np2_align_opts_t *align_opts,
+                          uint32_t out_flags, uint64_t *unit_off, np2_map_units_t *out);
+/* np2_map_align_files_x with the further units' records */
+int np2_map_align_files_m(const np2_map_index_t *ix, const char *const *paths, int n_paths, const np2_map_opts_t *map_opts,
+                          const np2_map_multi_opts_t *multi, const np2_align_opts_t *align_opts, uint32_t out_flags, const char *out_path,
+                          np2_map_stats_t *stats);
+/* host only, no device: np2_map_align_host_x per unit (NP2_ALN_QUAL is not taken: there is no text to write) */
+int np2_map_align_host_m(const uint8_t *asm_stream, uint64_t n_asm, const uint8_t *reads, uint64_t n, uint64_t n_reads,
+                         const np2_map_opts_t *map_opts, const np2_map_multi_opts_t *multi, const np2_align_opts_t *align_opts,
+                         const np2_map_weights_t *w /* NULL ok */, uint32_t out_flags, uint64_t *unit_off, np2_map_units_t *out);
 
 /* ---- the mapper's SAM, parsed and coordinate-sorted on the device (the reference's recipe: `| samtools sort -o ... ;
  * samtools index ...`, which exist only so that an indexed reader can fetch one contig's records in coordinate order) -------

@@ -49,6 +49,8 @@ IO_ABI_SYMBOLS = [
     "np2_rep_bytes", "np2_rep_files",
     "np2_map_index_bytes", "np2_map_index_files", "np2_map_index_free", "np2_map_index_info", "np2_map_index_seq", "np2_map_bytes",
     "np2_map_files", "np2_map_host", "np2_map_last_stats",
+    "np2_map_bytes_m", "np2_map_files_m", "np2_map_host_m", "np2_map_last_multi_stats",
+    "np2_map_align_bytes_m", "np2_map_align_files_m", "np2_map_align_host_m",
     "np2_map_weights_from_indices", "np2_map_weights_from_file", "np2_map_weights_info", "np2_map_weights_free",
     "np2_map_index_bytes_w", "np2_map_index_files_w", "np2_map_index_weights", "np2_map_host_w", "np2_map_align_host_w",
     "np2_map_align_bytes", "np2_map_align_files", "np2_map_align_host", "np2_map_align_last_stats",

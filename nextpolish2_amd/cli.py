@@ -444,7 +444,9 @@ def main(argv=None):
             raise SystemExit("Error: --sorted_bam_full needs the SAM text (NM, AS, cm, s1, s2 are not kept with --from_reads): write it with "
                              "python -m nextpolish2_amd.map -a -o map.sam.gz, then python -m nextpolish2_amd.samsort --full")
         if a.use_secondary:
-            raise SystemExit("Error: -S needs secondary records, and the mapper behind --from_reads writes primary ones only")
+            raise SystemExit("Error: -S needs secondary records, and the mapper behind --from_reads writes primary ones only ; write them "
+                             "with python -m nextpolish2_amd.map -a --secondary 5 --qual ... | python -m nextpolish2_amd.samsort - --full -o x.bam, "
+                             "then polish with x.bam ... -S -q -1")
         if int(os.environ.get("WORLD_SIZE", "1")) > 1 and "RANK" in os.environ:
             raise SystemExit("Error: --from_reads runs on one rank: interval sharding reads the .bai of a sorted BAM")
         a.sam = True  # the handle is an ordinary resident SAM: every rule of SAM input below holds

@@ -24,7 +24,7 @@ __global__ __launch_bounds__(64) void k_align_pins(AlignJob c) {
     if (i > c.n_reads) return;
     uint32_t ns = 0;
     if (i < c.n_reads) {
-        const np2map::Hit &h = c.hits[c.r0 + i];
+        const np2map::Hit &h = hit_of(c, i);
         if (h.tid >= 0) ns = mark_pins(c.chain + 2 * (uint64_t)c.coff[i], h.n, c.k, c.pin + c.coff[i]) + 1u;
     }
     c.nslots[i] = ns;
@@ -35,7 +35,7 @@ __global__ __launch_bounds__(64) void k_align_plan(AlignJob c) {
     if (i >= c.n_reads) return;
     const uint32_t s0 = c.soff[i], s1 = c.soff[i + 1];
     if (s1 == s0) return;
-    const np2map::Hit &h = c.hits[c.r0 + i];
+    const np2map::Hit &h = hit_of(c, i);
     const uint32_t t_at = h.tid > 0 ? c.asm_ends[h.tid - 1] + 1u : 0u;
     plan_read(c.chain + 2 * (uint64_t)c.coff[i], h.n, c.k, c.pin + c.coff[i], c.asm_ends[h.tid] - t_at, h.qlen, c.o, c.slots + s0);
     for (uint32_t s = s0; s < s1; ++s) c.slot_read[s] = i;
@@ -158,7 +158,7 @@ __device__ __forceinline__ ReadIn read_in(const AlignJob &c, uint32_t i, uint64_
     ReadIn in;
     in.s = seqs_of(c, i);
     in.chain = c.chain + 2 * (uint64_t)c.coff[i], in.pin = c.pin + c.coff[i];
-    in.n = c.hits[c.r0 + i].n, in.k = c.k;
+    in.n = hit_of(c, i).n, in.k = c.k;
     in.slots = c.slots + s0, in.res = c.res + s0, in.tb_off = c.tb_off + s0, in.tb = c.tb, in.tb_base = tb_base;
     in.n_slots = c.soff[i + 1] - s0;
     return in;
@@ -194,7 +194,7 @@ __global__ __launch_bounds__(64) void k_align_ops_emit(AlignJob c, uint32_t g0, 
             uint32_t *a = c.a + c.ooff[i];
             uint32_t t_start;
             const uint32_t n = raw_ops(in, a, &t_start);
-            const np2map::Hit &h = c.hits[c.r0 + i];
+            const np2map::Hit &h = hit_of(c, i);
             rec.tid = h.tid, rec.flag = h.rev ? 16u : 0u, rec.mapq = h.mapq;
             const uint32_t clipped = finish_ops(in.s, a, n, t_start, c.o, c.b + 2 * (uint64_t)c.ooff[i] + 2 * (uint64_t)(i - g0), &rec);
             atomicAdd(&c.ctr[C_CLIPPED], (unsigned long long)clipped);

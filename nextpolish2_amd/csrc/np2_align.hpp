@@ -9,13 +9,14 @@
 
 namespace np2 {
 
-// One group of the mapper: reads [r0, r0 + n_reads) of the resident batch, their hits and exported primary chains.
+// One group of the mapper: reads [r0, r0 + n_reads) of the resident batch, their hits and exported primary chains (or, with
+// unit_read, the group's units).
 struct AlignJob {
     const uint8_t *asm_seq;   // the index's assembly stream and its separators
     const uint32_t *asm_ends;
     const uint8_t *rd_seq;    // the batch's read stream and its separators
     const uint32_t *rd_ends;
-    const np2map::Hit *hits;  // [r0 + i]
+    const np2map::Hit *hits;  // [r0 + i]; with unit_read: [i]
     const uint32_t *coff, *chain; // read i's (r, q) pairs at chain + 2 coff[i]
     uint32_t r0, n_reads, k, max_cells;
     np2aln::Opts o;
@@ -32,12 +33,18 @@ struct AlignJob {
     uint32_t *nops, *ooff;    // per read: raw ops, and their exclusive sums
     uint32_t *a, *b;          // raw ops at ooff[i] - ooff[g0]; the CIGAR at 2 (ooff[i] - ooff[g0]) + 2 (i - g0)
     np2aln::Rec *recs;        // [i]
+    // More chains (np2_io.h, "More chains"): null, or the jobs are units: a read together with one kept chain.  Job i is read
+    // r0 + unit_read[i] with the hit hits[i] and its own chain at coff[i]; n_reads counts the units, and every per-read array
+    // above is per unit.
+    const uint32_t *unit_read;
 };
+
+__device__ __forceinline__ const np2map::Hit &hit_of(const AlignJob &c, uint32_t i) { return c.unit_read ? c.hits[i] : c.hits[c.r0 + i]; }
 
 // read i of the group and the contig its hit names (the aligner's kernels and the tag kernels, np2_aligntags.hip)
 __device__ __forceinline__ np2aln::Seqs seqs_of(const AlignJob &c, uint32_t i) {
-    const uint32_t rd = c.r0 + i;
-    const np2map::Hit &h = c.hits[rd];
+    const uint32_t rd = c.r0 + (c.unit_read ? c.unit_read[i] : i);
+    const np2map::Hit &h = hit_of(c, i);
     const uint32_t q_at = rd ? c.rd_ends[rd - 1] + 1u : 0u;
     const uint32_t t_at = h.tid > 0 ? c.asm_ends[h.tid - 1] + 1u : 0u;
     np2aln::Seqs s;

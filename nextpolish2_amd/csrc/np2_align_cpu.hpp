@@ -160,7 +160,28 @@ struct SamExtra {
     const uint8_t *qual;
     const char *md, *cs;
     uint32_t n_md, n_cs;
+    // More chains (np2_io.h): bits added to FLAG (2048 supplementary, 256 secondary) and SA:Z:'s value (null: none), the last field
+    uint32_t flag_or;
+    const std::string *sa;
 };
+
+// One entry of SA:Z: for a record: rname,pos,strand,CIGAR,mapq,NM; with the CIGAR in M / I / D / S form whatever the record's own
+// is (= and X runs are joined into M again)
+inline void sa_entry(std::string &out, const Rec &rec, const uint32_t *cigar, const std::string &tname) {
+    char num[64];
+    out += tname;
+    int m = snprintf(num, sizeof num, ",%u,%c,", rec.pos + 1, (rec.flag & 16u) ? '-' : '+');
+    out.append(num, (size_t)m);
+    for (uint32_t i = 0; i < rec.n_cigar;) {
+        uint32_t op = cigar[i] & 15u, len = cigar[i] >> 4;
+        if (op == 7u || op == 8u) op = 0u;
+        for (++i; i < rec.n_cigar && op == 0u && ((cigar[i] & 15u) == 7u || (cigar[i] & 15u) == 8u || (cigar[i] & 15u) == 0u); ++i) len += cigar[i] >> 4;
+        m = snprintf(num, sizeof num, "%u%c", len, "MIDNS"[op]);
+        out.append(num, (size_t)m);
+    }
+    m = snprintf(num, sizeof num, ",%u,%u;", rec.mapq, rec.nm);
+    out.append(num, (size_t)m);
+}
 // sam_line with them: the CIGAR may hold = and X words; QUAL is reversed, not complemented, with flag 16, and written forward
 // for an unmapped or overflowed read
 inline void sam_line_x(std::string &out, const char *qname, size_t qname_n, const Rec &rec, const np2map::Hit &hit, const uint32_t *cigar,
@@ -189,7 +210,7 @@ inline void sam_line_x(std::string &out, const char *qname, size_t qname_n, cons
         out += '\n';
         return;
     }
-    int m = snprintf(num, sizeof num, "\t%u\t", rec.flag);
+    int m = snprintf(num, sizeof num, "\t%u\t", rec.flag | x.flag_or);
     out.append(num, (size_t)m);
     out += *tname;
     m = snprintf(num, sizeof num, "\t%u\t%u\t", rec.pos + 1, rec.mapq);
@@ -206,6 +227,7 @@ inline void sam_line_x(std::string &out, const char *qname, size_t qname_n, cons
     out.append(num, (size_t)m);
     if (x.n_md) out += "\tMD:Z:", out.append(x.md, x.n_md);
     if (x.n_cs) out += "\tcs:Z:", out.append(x.cs, x.n_cs);
+    if (x.sa) out += "\tSA:Z:", out += *x.sa;
     out += '\n';
 }
 

@@ -1,6 +1,7 @@
 // The mapper on the device (the rule: include/np2_io.h, np2_map_*; the arithmetic: np2_map_core.hpp): minimizer sketch of a
 // resident separator stream, the lookup of the reads' minimizers in the sorted index, the ordered emission of anchors, the
-// chaining recurrence with one wavefront per read, and the export of the primary chains.  Sorts and scans are rocPRIM's
+// chaining recurrence with one wavefront per read, the export of the primary chains and, on request, a read's further chains
+// (k_map_chain_more: np2_io.h, "More chains") with their packing and export per unit.  Sorts and scans are rocPRIM's
 // (np2_prims.hip); nothing is appended through an atomic counter, every order is part of the rule.
 //
 // Bounds.
@@ -22,6 +23,12 @@
 //   k_map_chain: read i's anchors are [aoff[r0 + i] - aoff[r0], aoff[r0 + i + 1] - aoff[r0]); candidates j lie in [max(0, i -
 //     lookback), i) and their f / keys in the 64-entry rings at j & 63, written for j before anchor j + 1 is scored.
 //     p[i] < i, so the walks of finish_read end.  k_map_chain_export writes hit.n entries at coff[i], walking p from chain_end.
+//   k_map_chain_more: the same anchor range; every index into f, p, mark and base is below n (an arg-max winner is an
+//     anchor a lane saw, a block's lane is live only with b + lane < n, a predecessor is p of such an anchor).  A read makes
+//     max_chains - 1 selections at the most, so it writes units 1 .. max_chains - 1 into its max_chains - 1 slots and the
+//     family holds 1 + (max_chains - 1) <= MAX_CHAINS parents.  LDS: s_ptr[ptr] with 0 <= ptr = p[i] - b < lane.
+//   k_map_units_pack: read i writes uoff[i + 1] - uoff[i] = ucnt[i] <= max_chains entries at uoff[i]; the arrays hold
+//     uoff[n_reads].  k_map_units_export: unit i < n_units writes hits[i].n pairs at coff[i], as k_map_chain_export does.
 #include <hip/hip_runtime.h>
 
 #include "np2_blockscan.hpp"
@@ -234,6 +241,129 @@ __global__ __launch_bounds__(256) void k_map_chain_export(MapChain c, const uint
         const uint64_t l = c.klo[a0 + a];
         out[2 * (uint64_t)(at + t)] = np2map::lo_r(l), out[2 * (uint64_t)(at + t) + 1] = np2map::lo_q(l);
     }
+}
+
+// More chains of a read (np2map::select_more is the same steps with one lane): one wavefront per read, on what k_map_chain left.
+// Per selection: the arg-max of f[i] - base[i] over the unmarked anchors is a wave reduction over lanes striding the anchors;
+// lane 0 follows the chain back, marks it, fills its hit and classes it (the walk is serial, as the primary's is); then base is
+// swept again from the chain's first anchor on in blocks of 64 anchors, a lane an anchor.  p[i] lies in [i - lookback, i) with
+// lookback <= 64, so a predecessor is in this block or in an earlier one: an earlier block's base is final and read from
+// memory, inside the block a lane follows p through LDS by pointer jumping (six rounds at the most).
+__global__ __launch_bounds__(64) void k_map_chain_more(MapChain c, MapMore mo) {
+    __shared__ np2map::Family fm;
+    __shared__ int32_t s_val[64], s_ptr[64];
+    __shared__ uint32_t s_first;
+    const uint32_t rd = c.r0 + blockIdx.x, lane = threadIdx.x, stride = mo.m.max_chains - 1u;
+    if (c.chain_end[blockIdx.x] < 0) { // an unmapped read is its one unit
+        if (lane == 0) mo.ucnt[blockIdx.x] = 1;
+        return;
+    }
+    const uint64_t a0 = c.aoff[rd] - c.aoff[c.r0];
+    const uint32_t n = (uint32_t)(c.aoff[rd + 1] - c.aoff[rd]);
+    const uint64_t *hi = c.khi + a0, *lo = c.klo + a0;
+    const int32_t *f = c.f + a0, *p = c.p + a0;
+    int32_t *base = c.base + a0;
+    uint8_t *mark = c.mark + a0;
+    const size_t slot = (size_t)blockIdx.x * stride;
+    const uint32_t qlen = c.ends[rd] - (rd ? c.ends[rd - 1] + 1u : 0u);
+    np2map::MoreCounts mc{};
+    if (lane == 0) np2map::family_begin(fm, c.hits[rd]);
+#pragma unroll 1
+    for (uint32_t sel = 1; sel < mo.m.max_chains; ++sel) {
+        int64_t best = np2map::NO_CAND;
+        for (uint32_t i = lane; i < n; i += 64) {
+            if (mark[i]) continue;
+            const int64_t key = np2map::more_key(f[i] - base[i], i);
+            best = key > best ? key : best;
+        }
+        for (int o = 32; o > 0; o >>= 1) {
+            const int64_t other = __shfl_xor(best, o);
+            best = other > best ? other : best;
+        }
+        if (best == np2map::NO_CAND) break;
+        int64_t score;
+        uint32_t end;
+        np2map::more_unkey(best, &score, &end);
+        if (score < (int64_t)c.o.min_score) break;
+        if (lane == 0) {
+            np2map::Hit h;
+            s_first = np2map::take_chain(hi, lo, p, mark, end, (uint32_t)score, qlen, c.o, &h);
+            np2map::place_chain(fm, h, end, c.o, mo.m, mo.uhits + slot, mo.ucls + slot, mo.upar + slot, mo.uend + slot, &mc);
+        }
+        __syncthreads(); // (the chain's marks and its first anchor are the wavefront's)
+        const uint32_t first = s_first;
+        for (uint32_t b = first & ~63u; b < n; b += 64) {
+            const uint32_t i = b + lane;
+            const bool live = i < n && !mark[i];
+            int32_t val = 0, ptr = -1; // ptr >= 0: base[i] is the base of anchor b + ptr, not known yet
+            if (live) {
+                const int32_t pi = p[i];
+                if (pi < 0 || mark[pi] || (uint32_t)pi < b) val = np2map::base_step(pi, mark, f, base);
+                else ptr = pi - (int32_t)b;
+            }
+            while (__any(ptr >= 0)) {
+                s_ptr[lane] = ptr, s_val[lane] = val;
+                __syncthreads();
+                if (ptr >= 0) {
+                    const int32_t t = s_ptr[ptr];
+                    if (t < 0) val = s_val[ptr], ptr = -1;
+                    else ptr = t;
+                }
+                __syncthreads();
+            }
+            if (live) base[i] = val;
+            __syncthreads(); // (the next block reads this one's base from memory)
+        }
+    }
+    if (lane == 0) {
+        np2map::family_end(fm, mo.uhits + slot);
+        mo.ucnt[blockIdx.x] = fm.n_units;
+        const uint32_t v[5] = {mc.selections, mc.dropped_cnt, mc.dropped_pri, mc.kept_supp, mc.kept_sec};
+        for (int t = 0; t < 5; ++t)
+            if (v[t]) atomicAdd(&mo.ctr[t], (unsigned long long)v[t]);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_map_units_pack(MapChain c, MapMore mo, MapUnits u) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= c.n_reads) return;
+    const uint32_t at = u.uoff[i], cnt = u.uoff[i + 1] - at;
+    const size_t slot = (size_t)i * (mo.m.max_chains - 1u);
+    u.hits[at] = c.hits[c.r0 + i], u.cls[at] = (uint8_t)np2map::CLS_PRIMARY, u.parent[at] = 0, u.end[at] = c.chain_end[i], u.read[at] = i;
+    for (uint32_t t = 1; t < cnt; ++t) {
+        u.hits[at + t] = mo.uhits[slot + t - 1], u.cls[at + t] = (uint8_t)mo.ucls[slot + t - 1], u.parent[at + t] = mo.upar[slot + t - 1];
+        u.end[at + t] = mo.uend[slot + t - 1], u.read[at + t] = i;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_map_units_export(MapChain c, MapUnits u, uint32_t n_units, const uint32_t *__restrict__ coff,
+                                                          uint32_t *__restrict__ out) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_units) return;
+    int32_t a = u.end[i];
+    if (a < 0) return;
+    const uint32_t rd = c.r0 + u.read[i];
+    const uint64_t a0 = c.aoff[rd] - c.aoff[c.r0];
+    uint32_t t = u.hits[i].n;
+    const uint32_t at = coff[i];
+    for (; a >= 0 && t > 0; a = c.p[a0 + a]) {
+        --t;
+        const uint64_t l = c.klo[a0 + a];
+        out[2 * (uint64_t)(at + t)] = np2map::lo_r(l), out[2 * (uint64_t)(at + t) + 1] = np2map::lo_q(l);
+    }
+}
+
+void launch_map_chain_more(hipStream_t s, const MapChain &c, const MapMore &mo) {
+    if (c.n_reads == 0) return;
+    hipLaunchKernelGGL(k_map_chain_more, dim3(c.n_reads), dim3(64), 0, s, c, mo);
+}
+void launch_map_units_pack(hipStream_t s, const MapChain &c, const MapMore &mo, const MapUnits &u) {
+    if (c.n_reads == 0) return;
+    hipLaunchKernelGGL(k_map_units_pack, dim3((c.n_reads + 255) / 256), dim3(256), 0, s, c, mo, u);
+}
+void launch_map_units_export(hipStream_t s, const MapChain &c, const MapUnits &u, uint32_t n_units, const uint32_t *coff, uint32_t *out) {
+    if (n_units == 0) return;
+    hipLaunchKernelGGL(k_map_units_export, dim3((n_units + 255) / 256), dim3(256), 0, s, c, u, n_units, coff, out);
 }
 
 void launch_map_sketch_count(hipStream_t s, const uint8_t *seq, uint64_t n, uint64_t base, uint64_t len, uint32_t k, uint32_t w,

@@ -66,6 +66,32 @@ void launch_map_chain(hipStream_t s, const MapChain &c);
 // the primary chains' anchors (r, q), first to last, at coff[i] on
 void launch_map_chain_export(hipStream_t s, const MapChain &c, const uint32_t *coff, uint32_t *out);
 
+// More chains (np2map::MultiOpts with max_chains > 1), right behind launch_map_chain on the f, p, mark and base it left: one
+// wavefront per read makes the further selections.  A read's kept further units go to its max_chains - 1 slots (unit u of
+// read i at i * (max_chains - 1) + u - 1), ucnt[i] is its units with the primary (1 for an unmapped read), ctr[0 .. 5) take
+// np2map::MoreCounts' sums.
+struct MapMore {
+    np2map::MultiOpts m;
+    np2map::Hit *uhits;
+    uint32_t *ucls, *upar;
+    int32_t *uend;
+    uint32_t *ucnt; // [n_reads]
+    unsigned long long *ctr;
+};
+void launch_map_chain_more(hipStream_t s, const MapChain &c, const MapMore &mo);
+// ... and after an exclusive scan of ucnt (uoff[n_reads + 1]): the units in read order, the primary first, then selection
+// order: hits, cls, parent, the chain's last anchor (read-local, -1 for an unmapped primary) and the read (group-local)
+struct MapUnits {
+    const uint32_t *uoff;
+    np2map::Hit *hits;
+    uint8_t *cls;
+    uint32_t *parent, *read;
+    int32_t *end;
+};
+void launch_map_units_pack(hipStream_t s, const MapChain &c, const MapMore &mo, const MapUnits &u);
+// the units' chains (r, q), first to last, at coff[unit] on: k_map_chain_export per unit, each chain ending after its own n anchors
+void launch_map_units_export(hipStream_t s, const MapChain &c, const MapUnits &u, uint32_t n_units, const uint32_t *coff, uint32_t *out);
+
 // rocPRIM's stable radix sort of (uint64 key, uint64 value) pairs over the key bits [0, end_bit) (np2_prims.hip)
 size_t prim_pairs64_temp_bytes(size_t n);
 int prim_sort_pairs_u64_u64(hipStream_t s, void *tmp, size_t tmp_bytes, const uint64_t *kin, uint64_t *kout, const uint64_t *vin,

@@ -1,6 +1,7 @@
 // The mapper's rule as plain integer arithmetic without HIP types (the rule's text: include/np2_io.h, np2_map_*): byte ->
 // 2-bit code -> rolled words -> (hash, strand) of the k-mer that ends at a byte, the minimizer test, an anchor's
-// coordinates and sort keys, the chaining score, the two linear sweeps behind the primary chain, and the mapping quality.
+// coordinates and sort keys, the chaining score, the two linear sweeps behind the primary chain, the mapping quality, and the
+// further chains of a read: their selection, hits and classes.
 // The same text is the kernels' inner step (np2_map.hip), the host mapper (np2_map_host: np2_map_host.cpp) and a
 // stand-alone program (tests/tools/map_core_test.cpp).
 #pragma once
@@ -211,6 +212,152 @@ NP2_KC_HD int32_t finish_read(const uint64_t *hi, const uint64_t *lo, const int3
     h.mapq = mapq_of(s1, (uint32_t)s2, n);
     *out = h;
     return (int32_t)end;
+}
+
+// ---- more chains of a read (the rule: include/np2_io.h, "More chains") --------------------------------------------------------
+// After finish_read: up to max_chains - 1 further selections over the unmarked anchors, each the largest f[i] - base[i] (of
+// equal scores the smallest i) followed back through p while anchors are unmarked; the kept chains are classed against the
+// parents before them on forward read coordinates.  The pieces below are what the kernel (k_map_chain_more: a wavefront's
+// arg-max and block-wise re-sweep around them) and the host twin (select_more, one lane) share.
+static constexpr uint32_t MAX_CHAINS = 16, NO_UNIT = 0xFFFFFFFFu;
+static constexpr uint32_t CLS_PRIMARY = 0, CLS_SUPP = 1, CLS_SEC = 2;
+struct MultiOpts {
+    uint32_t max_chains, supplementary, secondary_n, mask_pm, pri_pm;
+};
+struct MoreCounts {
+    uint32_t selections, dropped_cnt, dropped_pri, kept_supp, kept_sec;
+};
+
+NP2_KC_HD const char *check_multi(const MultiOpts &m) {
+    if (m.max_chains < 1 || m.max_chains > MAX_CHAINS) return "max_chains must lie in 1 .. 16";
+    if (m.supplementary > 1) return "supplementary must be 0 or 1";
+    if (m.secondary_n > MAX_CHAINS - 1) return "secondary_n must lie in 0 .. 15";
+    if (m.mask_pm < 1 || m.mask_pm > 1000) return "mask_pm must lie in 1 .. 1000";
+    if (m.pri_pm > 1000) return "pri_pm must lie in 0 .. 1000";
+    return nullptr;
+}
+
+// base of an unmarked anchor whose predecessor is pi, against the current marks (finish_read's sweep, one step)
+NP2_KC_HD int32_t base_step(int32_t pi, const uint8_t *mark, const int32_t *f, const int32_t *base) {
+    return pi < 0 ? 0 : mark[pi] ? f[pi] : base[pi];
+}
+// an unmarked anchor's selection key: the largest key is the largest score and, of equal scores, the smallest i
+NP2_KC_HD int64_t more_key(int32_t score, uint32_t i) { return (int64_t)score * ((int64_t)1 << 32) + (int64_t)(0xFFFFFFFFu - i); }
+NP2_KC_HD void more_unkey(int64_t key, int64_t *score, uint32_t *i) {
+    const int64_t low = key & 0xFFFFFFFFLL;
+    *score = (key - low) / ((int64_t)1 << 32), *i = 0xFFFFFFFFu - (uint32_t)low;
+}
+
+// The chain that ends at the unmarked anchor `end`, followed back through p while anchors are unmarked: its anchors are
+// marked, and the hit is filled as finish_read fills the primary's, from the chain's own anchors, with s1 = score (s2 and
+// mapq stay 0: classify and family_end set them).  Returns the chain's first anchor.
+NP2_KC_HD uint32_t take_chain(const uint64_t *hi, const uint64_t *lo, const int32_t *p, uint8_t *mark, uint32_t end, uint32_t score, uint32_t qlen,
+                              const Opts &o, Hit *out) {
+    Hit h{};
+    uint32_t n = 0, matches = o.k, first = end;
+    for (int32_t i = (int32_t)end; i >= 0 && !mark[i]; i = p[i]) {
+        mark[i] = 1, ++n, first = (uint32_t)i;
+        if (p[i] >= 0 && !mark[p[i]]) {
+            const uint32_t dr = lo_r(lo[i]) - lo_r(lo[p[i]]), dq = lo_q(lo[i]) - lo_q(lo[p[i]]);
+            const uint32_t m = dr < dq ? dr : dq;
+            matches += m < o.k ? m : o.k;
+        }
+    }
+    const uint32_t q0 = lo_q(lo[first]) - (o.k - 1u), q1 = lo_q(lo[end]) + 1u;
+    h.tid = (int32_t)hi_tid(hi[end]), h.qlen = qlen;
+    h.rev = hi_rel(hi[end]);
+    h.qs = h.rev ? qlen - q1 : q0, h.qe = h.rev ? qlen - q0 : q1;
+    h.ts = lo_r(lo[first]) - (o.k - 1u), h.te = lo_r(lo[end]) + 1u;
+    h.matches = matches;
+    h.block = h.qe - h.qs > h.te - h.ts ? h.qe - h.qs : h.te - h.ts;
+    h.n = n, h.s1 = score;
+    *out = h;
+    return first;
+}
+
+// A read's parents so far, the primary first: the interval on the forward read, the score, the largest score classed
+// secondary to it, its kept secondaries, and its place among the read's units (NO_UNIT: a supplementary that is not reported).
+struct Family {
+    uint32_t n_par, n_units;
+    uint32_t qs[MAX_CHAINS], qe[MAX_CHAINS], s1[MAX_CHAINS], s2[MAX_CHAINS], n_sec[MAX_CHAINS], unit[MAX_CHAINS];
+};
+NP2_KC_HD void family_begin(Family &fm, const Hit &primary) {
+    fm.n_par = 1, fm.n_units = 1;
+    fm.qs[0] = primary.qs, fm.qe[0] = primary.qe, fm.s1[0] = primary.s1, fm.s2[0] = primary.s2, fm.n_sec[0] = 0, fm.unit[0] = 0;
+}
+// A chain with min_cnt anchors or more, in selection order -> its class; *unit: its place among the read's units when it is
+// kept, else NO_UNIT; *parent: the unit it is secondary to, or its own.  At most MAX_CHAINS - 1 chains follow a family_begin.
+NP2_KC_HD uint32_t classify(Family &fm, const Hit &h, const MultiOpts &m, uint32_t *unit, uint32_t *parent) {
+    const uint32_t len_c = h.qe - h.qs;
+    for (uint32_t P = 0; P < fm.n_par; ++P) {
+        const uint32_t a = h.qs > fm.qs[P] ? h.qs : fm.qs[P], b = h.qe < fm.qe[P] ? h.qe : fm.qe[P];
+        const uint32_t ov = b > a ? b - a : 0, len_p = fm.qe[P] - fm.qs[P];
+        if ((uint64_t)ov * 1000u <= (uint64_t)m.mask_pm * (len_c < len_p ? len_c : len_p)) continue;
+        if (P > 0 && h.s1 > fm.s2[P]) fm.s2[P] = h.s1; // (the primary keeps finish_read's s2)
+        const bool keep = fm.unit[P] != NO_UNIT && (uint64_t)h.s1 * 1000u >= (uint64_t)m.pri_pm * fm.s1[P] && fm.n_sec[P] < m.secondary_n;
+        if (keep) ++fm.n_sec[P];
+        *unit = keep ? fm.n_units++ : NO_UNIT, *parent = fm.unit[P];
+        return CLS_SEC;
+    }
+    const uint32_t P = fm.n_par++;
+    fm.qs[P] = h.qs, fm.qe[P] = h.qe, fm.s1[P] = h.s1, fm.s2[P] = 0, fm.n_sec[P] = 0;
+    fm.unit[P] = m.supplementary ? fm.n_units++ : NO_UNIT;
+    *unit = *parent = fm.unit[P];
+    return CLS_SUPP;
+}
+// after the last selection: the reported supplementaries' s2 and mapq; uh[u - 1] is unit u's hit
+NP2_KC_HD void family_end(const Family &fm, Hit *uh) {
+    for (uint32_t P = 1; P < fm.n_par; ++P) {
+        if (fm.unit[P] == NO_UNIT) continue;
+        Hit &h = uh[fm.unit[P] - 1u];
+        h.s2 = fm.s2[P], h.mapq = mapq_of(h.s1, h.s2, h.n);
+    }
+}
+// one selected chain with its hit -> dropped, or classed and, when kept, written as the read's next unit.  uh, ucls, upar,
+// uend: max_chains - 1 entries each, unit u at u - 1.
+NP2_KC_HD void place_chain(Family &fm, const Hit &h, uint32_t end, const Opts &o, const MultiOpts &m, Hit *uh, uint32_t *ucls, uint32_t *upar,
+                           int32_t *uend, MoreCounts *mc) {
+    ++mc->selections;
+    if (h.n < o.min_cnt) {
+        ++mc->dropped_cnt;
+        return;
+    }
+    uint32_t unit, parent;
+    const uint32_t cls = classify(fm, h, m, &unit, &parent);
+    if (unit == NO_UNIT) {
+        if (cls == CLS_SEC) ++mc->dropped_pri;
+        return;
+    }
+    ++(cls == CLS_SEC ? mc->kept_sec : mc->kept_supp);
+    uh[unit - 1u] = h, ucls[unit - 1u] = cls, upar[unit - 1u] = parent, uend[unit - 1u] = (int32_t)end;
+}
+
+// The further selections of one mapped read, one lane (the host twin; the kernel runs the same steps with a wavefront's
+// arg-max and re-sweep): on the f, p, mark and base finish_read left.  Returns the read's units, the primary included.
+NP2_KC_HD uint32_t select_more(const uint64_t *hi, const uint64_t *lo, const int32_t *f, const int32_t *p, uint8_t *mark, int32_t *base,
+                               uint32_t n_anchors, uint32_t qlen, const Opts &o, const MultiOpts &m, const Hit &primary, Family &fm, Hit *uh,
+                               uint32_t *ucls, uint32_t *upar, int32_t *uend, MoreCounts *mc) {
+    family_begin(fm, primary);
+    for (uint32_t sel = 1; sel < m.max_chains; ++sel) {
+        int64_t best = NO_CAND;
+        for (uint32_t i = 0; i < n_anchors; ++i) {
+            if (mark[i]) continue;
+            const int64_t key = more_key(f[i] - base[i], i);
+            if (key > best) best = key;
+        }
+        if (best == NO_CAND) break;
+        int64_t score;
+        uint32_t end;
+        more_unkey(best, &score, &end);
+        if (score < (int64_t)o.min_score) break;
+        Hit h;
+        const uint32_t first = take_chain(hi, lo, p, mark, end, (uint32_t)score, qlen, o, &h);
+        for (uint32_t i = first; i < n_anchors; ++i)
+            if (!mark[i]) base[i] = base_step(p[i], mark, f, base);
+        place_chain(fm, h, end, o, m, uh, ucls, upar, uend, mc);
+    }
+    family_end(fm, uh);
+    return fm.n_units;
 }
 
 // the options' ranges; nullptr when they hold, otherwise what is wrong (unsupported: k, w, lookback; the others: argument)

@@ -76,8 +76,25 @@ struct ReadCounts {
     uint64_t minimizers = 0, anchors = 0, dropped_occ = 0;
 };
 
-// one read -> its hit (tid -1: unmapped) and, with `chain`, its primary chain's (r, q) pairs appended first to last
-inline void map_read(const HostIndex &ix, const uint8_t *s, uint32_t qlen, const Opts &o, Hit *hit, std::vector<uint32_t> *chain, ReadCounts *counts) {
+// one read's anchors in the rule's order, f and p of the recurrence, and the marks and bases finish_read leaves
+struct ReadChains {
+    std::vector<uint64_t> khi, klo;
+    std::vector<int32_t> f, p, base;
+    std::vector<uint8_t> mark;
+    // the (r, q) pairs of the n anchors that end at `last`, first to last, appended to `chain`
+    void append_chain(std::vector<uint32_t> &chain, int32_t last, uint32_t n) const {
+        const size_t at = chain.size();
+        chain.resize(at + 2 * (size_t)n);
+        uint32_t t = n;
+        for (int32_t a = last; a >= 0 && t > 0; a = p[a]) {
+            --t;
+            chain[at + 2 * (size_t)t] = lo_r(klo[a]), chain[at + 2 * (size_t)t + 1] = lo_q(klo[a]);
+        }
+    }
+};
+
+// one read -> its hit (tid -1: unmapped) and what the chaining left in `rc`; returns the primary chain's last anchor or -1
+inline int32_t chain_read(const HostIndex &ix, const uint8_t *s, uint32_t qlen, const Opts &o, Hit *hit, ReadChains &rc, ReadCounts *counts) {
     std::vector<uint64_t> words;
     std::vector<Minimizer> mz;
     sketch_seq(s, qlen, 0, o.k, o.w, words, mz, ix.ws);
@@ -97,10 +114,10 @@ inline void map_read(const HostIndex &ix, const uint8_t *s, uint32_t qlen, const
     counts->minimizers += mz.size(), counts->anchors += an.size();
     std::sort(an.begin(), an.end());
     const uint32_t n = (uint32_t)an.size();
-    std::vector<uint64_t> khi(n), klo(n);
+    std::vector<uint64_t> &khi = rc.khi, &klo = rc.klo;
+    std::vector<int32_t> &f = rc.f, &p = rc.p;
+    khi.resize(n), klo.resize(n), f.resize(n), p.resize(n), rc.base.resize(n), rc.mark.resize(n);
     for (uint32_t i = 0; i < n; ++i) khi[i] = an[i].first, klo[i] = an[i].second;
-    std::vector<int32_t> f(n), p(n), base(n);
-    std::vector<uint8_t> mark(n);
     int32_t best_f = 0;
     uint32_t end = 0;
     for (uint32_t i = 0; i < n; ++i) {
@@ -112,27 +129,45 @@ inline void map_read(const HostIndex &ix, const uint8_t *s, uint32_t qlen, const
         settle(best, o.k, &f[i], &p[i]);
         if (f[i] > best_f) best_f = f[i], end = i;
     }
-    const int32_t last = finish_read(khi.data(), klo.data(), f.data(), p.data(), mark.data(), base.data(), n, end, qlen, o, hit);
-    if (chain && last >= 0) {
-        const size_t at = chain->size();
-        chain->resize(at + 2 * (size_t)hit->n);
-        uint32_t t = hit->n;
-        for (int32_t a = last; a >= 0 && t > 0; a = p[a]) {
-            --t;
-            (*chain)[at + 2 * (size_t)t] = lo_r(klo[a]), (*chain)[at + 2 * (size_t)t + 1] = lo_q(klo[a]);
-        }
+    return finish_read(khi.data(), klo.data(), f.data(), p.data(), rc.mark.data(), rc.base.data(), n, end, qlen, o, hit);
+}
+
+// one read -> its hit (tid -1: unmapped) and, with `chain`, its primary chain's (r, q) pairs appended first to last
+inline void map_read(const HostIndex &ix, const uint8_t *s, uint32_t qlen, const Opts &o, Hit *hit, std::vector<uint32_t> *chain, ReadCounts *counts) {
+    ReadChains rc;
+    const int32_t last = chain_read(ix, s, qlen, o, hit, rc, counts);
+    if (chain && last >= 0) rc.append_chain(*chain, last, hit->n);
+}
+
+// one read -> its units (the rule: np2_io.h, "More chains"): hits[0] is map_read's hit, the kept further chains follow in
+// selection order with their classes and parents; with `chain`, every unit's (r, q) pairs appended; returns the units
+inline uint32_t map_read_m(const HostIndex &ix, const uint8_t *s, uint32_t qlen, const Opts &o, const MultiOpts &m, Hit *hits, uint32_t *cls,
+                           uint32_t *parent, std::vector<uint32_t> *chain, ReadCounts *counts, MoreCounts *mc) {
+    ReadChains rc;
+    const int32_t last = chain_read(ix, s, qlen, o, &hits[0], rc, counts);
+    cls[0] = CLS_PRIMARY, parent[0] = 0;
+    if (last < 0) return 1;
+    int32_t uend[MAX_CHAINS];
+    Family fm;
+    const uint32_t n = select_more(rc.khi.data(), rc.klo.data(), rc.f.data(), rc.p.data(), rc.mark.data(), rc.base.data(), (uint32_t)rc.khi.size(),
+                                   qlen, o, m, hits[0], fm, hits + 1, cls + 1, parent + 1, uend, mc);
+    if (chain) {
+        rc.append_chain(*chain, last, hits[0].n);
+        for (uint32_t u = 1; u < n; ++u) rc.append_chain(*chain, uend[u - 1], hits[u].n);
     }
+    return n;
 }
 
 // one mapped read's PAF line, appended to `out`: columns 1 .. 12 and the tags
-inline void paf_line(std::string &out, const char *qname, size_t qname_n, const Hit &h, const std::string &tname, uint64_t tlen) {
+// (tp: P for a primary and a supplementary chain, S for a secondary one)
+inline void paf_line(std::string &out, const char *qname, size_t qname_n, const Hit &h, const std::string &tname, uint64_t tlen, char tp = 'P') {
     char num[256];
     out.append(qname, qname_n);
     int m = snprintf(num, sizeof num, "\t%u\t%u\t%u\t%c\t", h.qlen, h.qs, h.qe, h.rev ? '-' : '+');
     out.append(num, (size_t)m);
     out += tname;
-    m = snprintf(num, sizeof num, "\t%llu\t%u\t%u\t%u\t%u\t%u\ttp:A:P\tcm:i:%u\ts1:i:%u\ts2:i:%u\n", (unsigned long long)tlen, h.ts, h.te,
-                 h.matches, h.block, h.mapq, h.n, h.s1, h.s2);
+    m = snprintf(num, sizeof num, "\t%llu\t%u\t%u\t%u\t%u\t%u\ttp:A:%c\tcm:i:%u\ts1:i:%u\ts2:i:%u\n", (unsigned long long)tlen, h.ts, h.te,
+                 h.matches, h.block, h.mapq, tp, h.n, h.s1, h.s2);
     out.append(num, (size_t)m);
 }
 

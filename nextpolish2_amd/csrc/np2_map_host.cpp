@@ -18,6 +18,12 @@
 // which come to the host: a batch whose anchors exceed the device budget (2^25; NP2_MAP_TEST_BUDGET) is worked off in GROUPS
 // of whole reads.  Per group: anchors emitted in minimizer order, two stable pair sorts (by r << 32 | q, then by read, rel,
 // tid), the chain kernel, the hits' read-back and, on request, the primary chains' export.
+// More chains (np2_map_*_m; the rule: np2_io.h, "More chains").  Only with max_chains > 1, inside a group right behind
+// k_map_chain: k_map_chain_more, a scan of the reads' unit counts, whose sums come to the host, k_map_units_pack, and the
+// units' hits, classes and parents in read order (Mapper::more_group); on request the units' chains.  With the aligner on
+// (np2_map_align_*_m) the group's units are its jobs: align_group runs on them through AlignJob::unit_read, each unit with its own
+// hit and chain, the arrays per unit; a batch's units are then settled on the host (Units::settle) and a read's records are
+// written together (write_sam_units), so SA:Z: sees all of them whatever groups and sub-groups the units fell into.
 //
 // Alignment (np2_map_align_*; the rule: np2_io.h; kernels: np2_align.hip).  The index keeps the assembly's bytes.  Inside a
 // group, after k_map_chain and the chains' export, with the batch's reads still resident: pins and slots per read (count, scan,
@@ -46,6 +52,7 @@
 #include "np2_map.hpp"
 #include "np2_map_core.hpp"
 #include "np2_map_cpu.hpp"
+#include "np2_map_units.hpp"
 #include "np2_pieces.hpp"
 #include "np2_sam_accum.hpp"
 #include "np2_seqreader.hpp"
@@ -58,6 +65,8 @@ using np2h::DevBuf;
 using np2h::DevEvent;
 using np2h::elapsed;
 using np2h::Np2Error;
+using np2aln::TagTexts;
+using np2aln::Units;
 using np2map::Hit;
 
 static_assert(sizeof(np2_map_hit_t) == sizeof(Hit) && sizeof(Hit) == 52, "np2_map_hit_t is np2map::Hit");
@@ -70,6 +79,8 @@ constexpr uint8_t SEP = '\n';
 thread_local np2_map_stats_t tl_stats{};
 thread_local np2_align_stats_t tl_astats{};
 thread_local np2_align_tag_stats_t tl_tstats{};
+thread_local np2_map_multi_stats_t tl_mstats{};
+static_assert(sizeof(np2_map_multi_opts_t) == sizeof(np2map::MultiOpts), "np2_map_multi_opts_t is np2map::MultiOpts");
 static_assert(NP2_ALN_QUAL == np2aln::ALN_QUAL && NP2_ALN_MD == np2aln::ALN_MD && NP2_ALN_CS == np2aln::ALN_CS && NP2_ALN_EQX == np2aln::ALN_EQX,
               "NP2_ALN_* are np2aln::ALN_*");
 static_assert(sizeof(np2_align_opts_t) == sizeof(np2aln::Opts), "np2_align_opts_t is np2aln::Opts");
@@ -463,13 +474,6 @@ struct TagRun {
     }
 };
 
-// the MD and cs texts of a batch's reads: appended in read order, n_md[i], n_cs[i] bytes of read i (0: none)
-struct TagTexts {
-    std::vector<char> md, cs;
-    std::vector<uint32_t> n_md, n_cs;
-    void begin(size_t n_reads) { md.clear(), cs.clear(), n_md.assign(n_reads, 0), n_cs.assign(n_reads, 0); }
-};
-
 // the host twin of the tag kernels for one record: its texts appended to tt (read i of the batch), its split CIGAR to `eqx`
 void tags_of_record(const np2aln::TagIn &in, uint32_t flags, TagTexts &tt, size_t i, std::vector<uint32_t> *eqx) {
     np2aln::TagOut sz{};
@@ -487,6 +491,17 @@ void tags_of_record(const np2aln::TagIn &in, uint32_t flags, TagTexts &tt, size_
 uint32_t checked_out_flags(uint32_t flags, uint32_t allowed, const std::string &who) {
     if (flags & ~allowed) throw Np2Error(NP2_E_ARG, who + ": unknown flag bits in out_flags");
     return flags;
+}
+
+np2map::MultiOpts checked_multi(const np2_map_multi_opts_t *m, const std::string &who) {
+    if (!m) throw Np2Error(NP2_E_ARG, who + ": multi is NULL");
+    np2map::MultiOpts r{m->max_chains, m->supplementary, m->secondary_n, m->mask_pm, m->pri_pm};
+    if (const char *bad = np2map::check_multi(r)) throw Np2Error(NP2_E_ARG, who + ": " + bad);
+    return r;
+}
+
+void add_more_counts(np2_map_multi_stats_t &st, const unsigned long long *c) {
+    st.selections += c[0], st.dropped_min_cnt += c[1], st.dropped_secondary += c[2], st.kept_supplementary += c[3], st.kept_secondary += c[4];
 }
 
 // batches of reads against one index
@@ -524,6 +539,22 @@ struct Mapper {
     uint32_t tag_flags = 0;
     TagRun tg;
     TagTexts *tt = nullptr;
+    // more chains: off while `units` is null (max_chains = 1 included: no further kernel is launched then)
+    np2map::MultiOpts mo{};
+    Units *units = nullptr;
+    bool unit_chains = false;
+    DevBuf<Hit> d_uh, d_phits;
+    DevBuf<uint32_t> d_ucls, d_upar, d_ucnt, d_uoff, d_ppar, d_pread;
+    DevBuf<int32_t> d_uend, d_pend;
+    DevBuf<uint8_t> d_pcls;
+    DevBuf<unsigned long long> d_mctr;
+    std::vector<uint32_t> h_uoff;
+
+    void more_with(const np2map::MultiOpts &m, Units *u, bool chains) {
+        mo = m, units = u, unit_chains = chains;
+        d_uh.cached = d_phits.cached = d_ucls.cached = d_upar.cached = d_ucnt.cached = d_uoff.cached = d_ppar.cached = d_pread.cached = true;
+        d_uend.cached = d_pend.cached = d_pcls.cached = d_mctr.cached = true;
+    }
 
     void align_with(const np2aln::Opts &a) {
         ao_v = a, ao = &ao_v;
@@ -613,6 +644,10 @@ struct Mapper {
         launch_map_chain(st, c);
         HIPCHK(hipMemcpyAsync(hits + r0, d_hits.p + r0, (size_t)n_reads * sizeof(Hit), hipMemcpyDeviceToHost, st));
         stats.chain_ms += s.end();
+        if (units) {
+            more_group(c);
+            return;
+        }
         if (ao && recs)
             for (uint32_t i = r0; i < r1; ++i) recs[i] = np2aln::unaligned_rec();
         if (!chain && !ao) return;
@@ -628,16 +663,78 @@ struct Mapper {
         launch_map_chain_export(st, c, d_coff.p, d_chain.p);
         if (chain) HIPCHK(hipMemcpyAsync(chain->data() + at, d_chain.p, 2 * total * 4, hipMemcpyDeviceToHost, st));
         stats.chain_ms += s.end();
-        if (ao) align_group(r0, n_reads, total, recs, cigar);
+        if (ao) align_group(r0, n_reads, total, recs, cigar, nullptr, nullptr, r0);
+    }
+
+    // More chains of the group's reads, right behind k_map_chain: the selections, a scan of the reads' unit counts, the units
+    // packed in read order; they come to the host and, when asked for, so do their chains.
+    void more_group(const np2::MapChain &c) {
+        using namespace np2;
+        hipStream_t st = s.st;
+        const uint32_t n_reads = c.n_reads;
+        const size_t slots = (size_t)n_reads * (mo.max_chains - 1u) + 1;
+        d_uh.ensure(slots), d_ucls.ensure(slots), d_upar.ensure(slots), d_uend.ensure(slots);
+        d_ucnt.ensure((size_t)n_reads + 1), d_uoff.ensure((size_t)n_reads + 1), d_mctr.ensure(8);
+        const size_t scan_tmp = prim_temp_bytes((size_t)n_reads + 1);
+        s.tmp.ensure(scan_tmp);
+        h_uoff.resize((size_t)n_reads + 1);
+        MapMore mm{mo, d_uh.p, d_ucls.p, d_upar.p, d_uend.p, d_ucnt.p, d_mctr.p};
+        HIPCHK(hipMemsetAsync(d_mctr.p, 0, 8 * 8, st));
+        HIPCHK(hipMemsetAsync(d_ucnt.p + n_reads, 0, 4, st));
+        s.begin();
+        launch_map_chain_more(st, c, mm);
+        if (prim_exclusive_sum_u32(st, s.tmp.p, scan_tmp, d_ucnt.p, d_uoff.p, (size_t)n_reads + 1))
+            throw Np2Error(NP2_E_DEVICE, "rocprim exclusive_scan failed");
+        HIPCHK(hipMemcpyAsync(h_uoff.data(), d_uoff.p, ((size_t)n_reads + 1) * 4, hipMemcpyDeviceToHost, st));
+        tl_mstats.more_ms += s.end();
+        const uint32_t n_units = h_uoff[n_reads];
+        if (n_units < n_reads || (uint64_t)n_units > (uint64_t)n_reads * mo.max_chains) throw Np2Error(NP2_E_DEVICE, "np2_map: unit counts out of range");
+        d_phits.ensure((size_t)n_units + 1), d_pcls.ensure((size_t)n_units + 1), d_ppar.ensure((size_t)n_units + 1);
+        d_pend.ensure((size_t)n_units + 1), d_pread.ensure((size_t)n_units + 1);
+        const MapUnits u{d_uoff.p, d_phits.p, d_pcls.p, d_ppar.p, d_pread.p, d_pend.p};
+        const size_t at = units->hits.size();
+        units->hits.resize(at + n_units), units->cls.resize(at + n_units), units->parent.resize(at + n_units);
+        unsigned long long ctr[8];
+        s.begin();
+        launch_map_units_pack(st, c, mm, u);
+        HIPCHK(hipMemcpyAsync(units->hits.data() + at, d_phits.p, (size_t)n_units * sizeof(Hit), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(units->cls.data() + at, d_pcls.p, n_units, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(units->parent.data() + at, d_ppar.p, (size_t)n_units * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(ctr, d_mctr.p, sizeof ctr, hipMemcpyDeviceToHost, st));
+        tl_mstats.more_ms += s.end();
+        add_more_counts(tl_mstats, ctr);
+        for (uint32_t i = 0; i < n_reads; ++i) units->n_units.push_back(h_uoff[i + 1] - h_uoff[i]);
+        if (ao) units->recs.resize(at + n_units, np2aln::unaligned_rec());
+        if (ao && tag_flags) units->tt.n_md.resize(at + n_units, 0), units->tt.n_cs.resize(at + n_units, 0);
+        if (!unit_chains && !ao) return;
+        h_coff.resize(n_units);
+        uint64_t total = 0;
+        for (uint32_t i = 0; i < n_units; ++i) {
+            const Hit &h = units->hits[at + i];
+            h_coff[i] = (uint32_t)total, total += h.tid >= 0 ? h.n : 0;
+        }
+        if (total == 0) return;
+        d_coff.ensure(n_units), d_chain.ensure(2 * total);
+        const size_t cat = units->chain.size();
+        if (unit_chains) units->chain.resize(cat + 2 * total);
+        HIPCHK(hipMemcpyAsync(d_coff.p, h_coff.data(), (size_t)n_units * 4, hipMemcpyHostToDevice, st));
+        s.begin();
+        launch_map_units_export(st, c, u, n_units, d_coff.p, d_chain.p);
+        if (unit_chains) HIPCHK(hipMemcpyAsync(units->chain.data() + cat, d_chain.p, 2 * total * 4, hipMemcpyDeviceToHost, st));
+        stats.chain_ms += s.end();
+        // the aligner serves units as it serves reads: the jobs are the group's units, each with its own hit and chain
+        if (ao) align_group(c.r0, n_units, total, units->recs.data(), &units->cigar, d_phits.p, d_pread.p, at);
     }
 
     // the group's mapped reads, their chains in d_chain at d_coff: recs[r0 + i] and the CIGAR words in read order
-    void align_group(uint32_t r0, uint32_t n_reads, uint64_t total_pairs, np2aln::Rec *recs, std::vector<uint32_t> *cigar) {
+    // job_hits, unit_read (both or neither): the jobs are units (np2_align.hpp); out0: the first job's place in recs and the texts
+    void align_group(uint32_t r0, uint32_t n_reads, uint64_t total_pairs, np2aln::Rec *recs, std::vector<uint32_t> *cigar, const Hit *job_hits,
+                     const uint32_t *unit_read, size_t out0) {
         using namespace np2;
         hipStream_t st = s.st;
         AlignJob c{};
         c.asm_seq = ix.seq.p, c.asm_ends = ix.ends.p, c.rd_seq = sk.d_seq.p + MAP_FRONT, c.rd_ends = sk.d_ends.p;
-        c.hits = d_hits.p, c.coff = d_coff.p, c.chain = d_chain.p;
+        c.hits = job_hits ? job_hits : d_hits.p, c.unit_read = unit_read, c.coff = d_coff.p, c.chain = d_chain.p;
         c.r0 = r0, c.n_reads = n_reads, c.k = o.k, c.max_cells = ao->max_cells, c.o = *ao;
         d_pin.ensure(total_pairs + 1), d_nslots.ensure((size_t)n_reads + 2), d_soff.ensure((size_t)n_reads + 2);
         d_rcells.ensure((size_t)n_reads + 2), d_nops.ensure((size_t)n_reads + 2), d_ooff.ensure((size_t)n_reads + 2);
@@ -716,11 +813,11 @@ struct Mapper {
                 np2aln::Rec rc = h_recs[g0 + i];
                 const uint32_t *w = h_b.data() + 2 * (size_t)h_ooff[i] + 2 * (size_t)i;
                 if ((tag_flags & NP2_ALN_EQX) && rc.tid >= 0) w = tg.eqx.data() + tg.eqx_off[i], rc.n_cigar = tg.eqx_off[i + 1] - tg.eqx_off[i];
-                recs[r0 + g0 + i] = rc;
+                recs[out0 + g0 + i] = rc;
                 if (cigar) cigar->insert(cigar->end(), w, w + rc.n_cigar);
                 if (tag_flags && tt) {
-                    tt->n_md[r0 + g0 + i] = (uint32_t)(tg.md_off[i + 1] - tg.md_off[i]);
-                    tt->n_cs[r0 + g0 + i] = (uint32_t)(tg.cs_off[i + 1] - tg.cs_off[i]);
+                    tt->n_md[out0 + g0 + i] = (uint32_t)(tg.md_off[i + 1] - tg.md_off[i]);
+                    tt->n_cs[out0 + g0 + i] = (uint32_t)(tg.cs_off[i + 1] - tg.cs_off[i]);
                 }
             }
             if (tag_flags && tt) tt->md.insert(tt->md.end(), tg.md.begin(), tg.md.end()), tt->cs.insert(tt->cs.end(), tg.cs.begin(), tg.cs.end());
@@ -1425,6 +1522,446 @@ int np2_map_host(const uint8_t *asm_stream, uint64_t n_asm, const uint8_t *reads
 int np2_map_host_w(const uint8_t *asm_stream, uint64_t n_asm, const uint8_t *reads, uint64_t n, uint64_t n_reads, const np2_map_opts_t *opts,
                    const np2_map_weights_t *w, np2_map_hit_t *hits, uint32_t **chain, uint64_t *chain_off) {
     return map_host_impl(asm_stream, n_asm, reads, n, n_reads, opts, w, hits, chain, chain_off, "np2_map_host_w");
+}
+
+// ---- More chains: the _m doors ------------------------------------------------------------------------------------------------
+extern "C++" {
+namespace {
+struct Freed {
+    void *p = nullptr;
+    ~Freed() { free(p); }
+    void *release() {
+        void *r = p;
+        p = nullptr;
+        return r;
+    }
+};
+template <class T> void malloc_copy(Freed &f, const T *src, size_t n) { // never NULL
+    f.p = malloc(std::max<size_t>(n, 1) * sizeof(T));
+    if (!f.p) throw Np2Error(NP2_E_NOMEM, "out of memory for the units");
+    if (n) memcpy(f.p, src, n * sizeof(T));
+}
+
+// unit_off[n_reads + 1] of the caller's from the units' per-read counts
+void fill_unit_off(const Units &u, uint64_t n_reads, uint64_t *unit_off) {
+    unit_off[0] = 0;
+    for (uint64_t i = 0; i < n_reads; ++i) unit_off[i + 1] = unit_off[i] + u.n_units[i];
+}
+
+struct UnitDoor { // the outputs the _bytes_m and _host_m doors share, checked and nulled first
+    uint64_t *unit_off;
+    np2_map_hit_t **hits;
+    uint8_t **cls;
+    uint32_t **parent, **chain;
+    uint64_t **chain_off;
+    void null_all() const {
+        for (void **p : {(void **)hits, (void **)cls, (void **)parent, (void **)chain, (void **)chain_off})
+            if (p) *p = nullptr;
+    }
+    void check(const std::string &who) const {
+        if (!unit_off || !hits || !cls || !parent) throw Np2Error(NP2_E_ARG, who + ": unit_off, hits, cls and parent are outputs: none may be NULL");
+        if ((chain == nullptr) != (chain_off == nullptr)) throw Np2Error(NP2_E_ARG, who + ": chain and chain_off go together");
+    }
+    void give(const Units &u, uint64_t n_reads) const {
+        if (u.n_units.size() != n_reads) throw Np2Error(NP2_E_DEVICE, "np2_map: the units do not cover the reads");
+        const size_t n = u.hits.size();
+        Freed fh, fc, fp, fch, fco;
+        malloc_copy(fh, u.hits.data(), n), malloc_copy(fc, u.cls.data(), n), malloc_copy(fp, u.parent.data(), n);
+        if (chain) {
+            std::vector<uint64_t> off(n + 1, 0);
+            for (size_t i = 0; i < n; ++i) off[i + 1] = off[i] + (u.hits[i].tid >= 0 ? u.hits[i].n : 0);
+            if (2 * off[n] != u.chain.size()) throw Np2Error(NP2_E_DEVICE, "np2_map: the units' chains do not add up");
+            malloc_copy(fch, u.chain.data(), u.chain.size()), malloc_copy(fco, off.data(), n + 1);
+        }
+        fill_unit_off(u, n_reads, unit_off);
+        *hits = (np2_map_hit_t *)fh.release(), *cls = (uint8_t *)fc.release(), *parent = (uint32_t *)fp.release();
+        if (chain) *chain = (uint32_t *)fch.release(), *chain_off = (uint64_t *)fco.release();
+        tl_mstats.units = n;
+    }
+};
+
+// a batch's PAF lines per unit: a read's primary line is np2_map_files', the kept others follow it
+void write_paf_units(np2h::OutFile &out, const np2_map_index &ix, const BatchBuf &b, const Units &u, std::string &text) {
+    text.clear();
+    size_t name_at = 0, at = 0;
+    for (size_t i = 0; i < b.ends.size(); ++i) {
+        const size_t name_end = b.names.find('\n', name_at);
+        for (uint32_t t = 0; t < u.n_units[i]; ++t, ++at) {
+            const Hit &h = u.hits[at];
+            if (h.tid >= 0)
+                np2map::paf_line(text, b.names.data() + name_at, name_end - name_at, h, ix.names[(size_t)h.tid], ix.lens[(size_t)h.tid],
+                                 u.cls[at] == np2map::CLS_SEC ? 'S' : 'P');
+        }
+        name_at = name_end + 1;
+    }
+    out.put(text.data(), text.size());
+}
+} // namespace
+} // extern "C++"
+
+int np2_map_bytes_m(const np2_map_index_t *ix, const uint8_t *reads, uint64_t n, uint64_t n_reads, const np2_map_opts_t *opts,
+                    const np2_map_multi_opts_t *multi, uint64_t *unit_off, np2_map_hit_t **hits, uint8_t **cls, uint32_t **parent,
+                    uint32_t **chain, uint64_t **chain_off) {
+    return np2h::abi_guard([&] {
+        const std::string who = "np2_map_bytes_m";
+        const UnitDoor door{unit_off, hits, cls, parent, chain, chain_off};
+        door.null_all();
+        const np2map::Opts o = checked(opts, who.c_str());
+        const np2map::MultiOpts mo = checked_multi(multi, who);
+        check_index_opts(ix, o, who.c_str());
+        door.check(who);
+        const std::vector<uint64_t> ends = ends_of(reads, n, who.c_str(), "the read stream");
+        if (ends.size() != n_reads)
+            throw Np2Error(NP2_E_ARG, who + ": n_reads is " + std::to_string(n_reads) + ", the stream holds " + std::to_string(ends.size()) + " newlines");
+        tl_mstats = np2_map_multi_stats_t{};
+        Mapper m(*ix, o);
+        Units u;
+        if (mo.max_chains > 1) m.more_with(mo, &u, chain != nullptr);
+        std::vector<uint32_t> local;
+        std::vector<Hit> prim(n_reads);
+        for (uint64_t r0 = 0; r0 < n_reads;) { // np2_map_bytes' batches
+            const uint64_t from = r0 ? ends[r0 - 1] + 1 : 0;
+            uint64_t r1 = r0 + 1;
+            while (r1 < n_reads && ends[r1] + 1 - from <= m.hooks.batch_bytes()) ++r1;
+            local.clear();
+            for (uint64_t i = r0; i < r1; ++i) local.push_back((uint32_t)(ends[i] - from));
+            m.batch(reads + from, ends[r1 - 1] + 1 - from, local.data(), (uint32_t)(r1 - r0), prim.data() + r0,
+                    mo.max_chains == 1 && chain ? &u.chain : nullptr);
+            r0 = r1;
+        }
+        if (mo.max_chains == 1) u.add_plain(prim.data(), n_reads);
+        door.give(u, n_reads);
+        return NP2_OK;
+    }, np2h::io_set_error);
+}
+
+int np2_map_files_m(const np2_map_index_t *ix, const char *const *paths, int n_paths, const np2_map_opts_t *opts,
+                    const np2_map_multi_opts_t *multi, const char *out_path, np2_map_stats_t *stats) {
+    return np2h::abi_guard([&] {
+        const std::string who = "np2_map_files_m";
+        const np2map::Opts o = checked(opts, who.c_str());
+        const np2map::MultiOpts mo = checked_multi(multi, who);
+        check_index_opts(ix, o, who.c_str());
+        if (!paths || n_paths < 1) throw Np2Error(NP2_E_ARG, who + ": no read file given");
+        if (!out_path) throw Np2Error(NP2_E_ARG, who + ": out_path is NULL");
+        const std::vector<std::string> files = checked_files(paths, n_paths, who);
+        tl_mstats = np2_map_multi_stats_t{};
+        Mapper m(*ix, o);
+        Units u;
+        if (mo.max_chains > 1) m.more_with(mo, &u, false);
+        np2h::OutFile out;
+        out.open(out_path, ix->device);
+        std::vector<Hit> hits;
+        std::string text;
+        read_batches(files, m.hooks, who, [&](const BatchBuf &b) {
+            hits.resize(b.ends.size());
+            u.clear();
+            m.batch(b.bytes.data(), b.closed(), b.ends.data(), (uint32_t)b.ends.size(), hits.data(), nullptr);
+            if (mo.max_chains == 1) u.add_plain(hits.data(), hits.size());
+            tl_mstats.units += u.hits.size();
+            const auto t0 = std::chrono::steady_clock::now();
+            write_paf_units(out, *ix, b, u, text);
+            tl_stats.write_ms += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        });
+        out.close();
+        fill_stats(stats);
+        return NP2_OK;
+    }, np2h::io_set_error);
+}
+
+int np2_map_host_m(const uint8_t *asm_stream, uint64_t n_asm, const uint8_t *reads, uint64_t n, uint64_t n_reads, const np2_map_opts_t *opts,
+                   const np2_map_multi_opts_t *multi, const np2_map_weights_t *w, uint64_t *unit_off, np2_map_hit_t **hits, uint8_t **cls,
+                   uint32_t **parent, uint32_t **chain, uint64_t **chain_off) {
+    return np2h::abi_guard([&] {
+        const std::string who = "np2_map_host_m";
+        const UnitDoor door{unit_off, hits, cls, parent, chain, chain_off};
+        door.null_all();
+        const np2map::Opts o = checked(opts, who.c_str());
+        const np2map::MultiOpts mo = checked_multi(multi, who);
+        const np2map::WeightSet *ws = checked_weights(w, o, who.c_str());
+        door.check(who);
+        const std::vector<uint64_t> a_ends = ends_of(asm_stream, n_asm, who.c_str(), "the assembly stream");
+        const std::vector<uint64_t> ends = ends_of(reads, n, who.c_str(), "the read stream");
+        if (ends.size() != n_reads)
+            throw Np2Error(NP2_E_ARG, who + ": n_reads is " + std::to_string(n_reads) + ", the stream holds " + std::to_string(ends.size()) + " newlines");
+        np2map::HostIndex hx;
+        hx.build(asm_stream, a_ends, o.k, o.w, ws);
+        np2_map_stats_t &st = tl_stats;
+        st = np2_map_stats_t{};
+        st.index_minimizers = hx.mz.size();
+        tl_mstats = np2_map_multi_stats_t{};
+        Units u;
+        np2map::ReadCounts rc;
+        np2map::MoreCounts mc{};
+        Hit uh[np2map::MAX_CHAINS];
+        uint32_t ucls[np2map::MAX_CHAINS], upar[np2map::MAX_CHAINS];
+        uint64_t from = 0;
+        for (uint64_t i = 0; i < n_reads; ++i) {
+            const uint32_t nu = np2map::map_read_m(hx, reads + from, (uint32_t)(ends[i] - from), o, mo, uh, ucls, upar, chain ? &u.chain : nullptr, &rc, &mc);
+            ++(uh[0].tid >= 0 ? st.mapped : st.unmapped);
+            u.n_units.push_back(nu);
+            for (uint32_t t = 0; t < nu; ++t) u.hits.push_back(uh[t]), u.cls.push_back((uint8_t)ucls[t]), u.parent.push_back(upar[t]);
+            from = ends[i] + 1;
+        }
+        st.reads = n_reads, st.minimizers = rc.minimizers, st.anchors = rc.anchors, st.dropped_occ = rc.dropped_occ;
+        const unsigned long long c[5] = {mc.selections, mc.dropped_cnt, mc.dropped_pri, mc.kept_supp, mc.kept_sec};
+        add_more_counts(tl_mstats, c);
+        door.give(u, n_reads);
+        return NP2_OK;
+    }, np2h::io_set_error);
+}
+
+// ---- More chains, aligned: np2_map_align_*_m ---------------------------------------------------------------------------------
+extern "C++" {
+namespace {
+// a batch's SAM lines per settled unit (np2aln::sam_units_of_read), a read after the other
+void write_sam_units(np2h::OutFile &out, const np2_map_index &ix, const BatchBuf &b, const Units &u, std::string &text, bool tags) {
+    text.clear();
+    size_t name_at = 0, from = 0;
+    np2aln::UnitAt at;
+    for (size_t i = 0; i < b.ends.size(); ++i) {
+        const size_t name_end = b.names.find('\n', name_at);
+        const uint32_t qlen = (uint32_t)(b.ends[i] - from);
+        const uint8_t *qual = nullptr;
+        if (b.with_qual && qlen && b.quals[from] != 0xFF) qual = b.quals.data() + from, ++tl_tstats.qual_reads;
+        np2aln::sam_units_of_read(text, b.names.data() + name_at, name_end - name_at, b.bytes.data() + from, qlen, qual, u, u.n_units[i], tags, ix.names, at);
+        name_at = name_end + 1, from = (size_t)b.ends[i] + 1;
+    }
+    out.put(text.data(), text.size());
+}
+
+// with max_chains = 1 through an aligned _m door: the plain door's arrays as units
+void plain_units(Units &u, const Hit *hits, const np2aln::Rec *recs, size_t n, const std::vector<uint32_t> &cigar, const TagTexts *tt) {
+    u.add_plain(hits, n);
+    u.recs.insert(u.recs.end(), recs, recs + n), u.cigar.insert(u.cigar.end(), cigar.begin(), cigar.end());
+    if (tt) {
+        u.tt.n_md.insert(u.tt.n_md.end(), tt->n_md.begin(), tt->n_md.end()), u.tt.n_cs.insert(u.tt.n_cs.end(), tt->n_cs.begin(), tt->n_cs.end());
+        u.tt.md.insert(u.tt.md.end(), tt->md.begin(), tt->md.end()), u.tt.cs.insert(u.tt.cs.end(), tt->cs.begin(), tt->cs.end());
+    }
+}
+
+void append_units(Units &all, const Units &u) {
+    all.hits.insert(all.hits.end(), u.hits.begin(), u.hits.end()), all.cls.insert(all.cls.end(), u.cls.begin(), u.cls.end());
+    all.parent.insert(all.parent.end(), u.parent.begin(), u.parent.end()), all.n_units.insert(all.n_units.end(), u.n_units.begin(), u.n_units.end());
+    all.recs.insert(all.recs.end(), u.recs.begin(), u.recs.end()), all.cigar.insert(all.cigar.end(), u.cigar.begin(), u.cigar.end());
+    all.tt.n_md.insert(all.tt.n_md.end(), u.tt.n_md.begin(), u.tt.n_md.end()), all.tt.n_cs.insert(all.tt.n_cs.end(), u.tt.n_cs.begin(), u.tt.n_cs.end());
+    all.tt.md.insert(all.tt.md.end(), u.tt.md.begin(), u.tt.md.end()), all.tt.cs.insert(all.tt.cs.end(), u.tt.cs.begin(), u.tt.cs.end());
+}
+
+// the aligned units of a call -> the caller's unit_off and the np2_free-owned arrays of *out
+void give_units(const Units &u, uint64_t n_reads, uint32_t out_flags, uint64_t *unit_off, np2_map_units_t *out) {
+    if (u.n_units.size() != n_reads) throw Np2Error(NP2_E_DEVICE, "np2_map_align: the units do not cover the reads");
+    const size_t n = u.hits.size();
+    Freed f[10];
+    std::vector<uint64_t> off(n + 1, 0), md_off(n + 1, 0), cs_off(n + 1, 0);
+    for (size_t i = 0; i < n; ++i) off[i + 1] = off[i] + u.recs[i].n_cigar;
+    if (off[n] != u.cigar.size()) throw Np2Error(NP2_E_DEVICE, "np2_map_align: the units' CIGARs do not add up");
+    malloc_copy(f[0], u.hits.data(), n), malloc_copy(f[1], u.cls.data(), n), malloc_copy(f[2], u.parent.data(), n);
+    malloc_copy(f[3], u.recs.data(), n), malloc_copy(f[4], u.cigar.data(), u.cigar.size()), malloc_copy(f[5], off.data(), n + 1);
+    const bool md = (out_flags & NP2_ALN_MD) != 0, cs = (out_flags & NP2_ALN_CS) != 0;
+    if (md || cs) {
+        for (size_t i = 0; i < n; ++i) md_off[i + 1] = md_off[i] + u.tt.n_md[i], cs_off[i + 1] = cs_off[i] + u.tt.n_cs[i];
+    }
+    if (md) malloc_copy(f[6], u.tt.md.data(), u.tt.md.size()), malloc_copy(f[7], md_off.data(), n + 1);
+    if (cs) malloc_copy(f[8], u.tt.cs.data(), u.tt.cs.size()), malloc_copy(f[9], cs_off.data(), n + 1);
+    fill_unit_off(u, n_reads, unit_off);
+    out->n_units = n;
+    out->hits = (np2_map_hit_t *)f[0].release(), out->cls = (uint8_t *)f[1].release(), out->parent = (uint32_t *)f[2].release();
+    out->recs = (np2_align_rec_t *)f[3].release(), out->cigar = (uint32_t *)f[4].release(), out->cigar_off = (uint64_t *)f[5].release();
+    out->md = (char *)f[6].release(), out->md_off = (uint64_t *)f[7].release();
+    out->cs = (char *)f[8].release(), out->cs_off = (uint64_t *)f[9].release();
+    tl_mstats.units = n;
+}
+} // namespace
+} // extern "C++"
+
+int np2_map_align_bytes_m(const np2_map_index_t *ix, const uint8_t *reads, const uint8_t *quals, uint64_t n, uint64_t n_reads,
+                          const np2_map_opts_t *map_opts, const np2_map_multi_opts_t *multi, const np2_align_opts_t *align_opts, uint32_t out_flags,
+                          uint64_t *unit_off, np2_map_units_t *out) {
+    return np2h::abi_guard([&] {
+        const std::string who = "np2_map_align_bytes_m";
+        if (out) *out = np2_map_units_t{};
+        const np2map::Opts o = checked(map_opts, who.c_str());
+        const np2map::MultiOpts mo = checked_multi(multi, who);
+        const np2aln::Opts ao = checked_align(align_opts, who.c_str());
+        check_index_opts(ix, o, who.c_str());
+        checked_out_flags(out_flags, NP2_ALN_QUAL | NP2_ALN_MD | NP2_ALN_CS | NP2_ALN_EQX, who);
+        if (!unit_off || !out) throw Np2Error(NP2_E_ARG, who + ": unit_off and out are outputs: neither may be NULL");
+        const std::vector<uint64_t> ends = ends_of(reads, n, who.c_str(), "the read stream");
+        if (ends.size() != n_reads)
+            throw Np2Error(NP2_E_ARG, who + ": n_reads is " + std::to_string(n_reads) + ", the stream holds " + std::to_string(ends.size()) + " newlines");
+        tl_tstats = np2_align_tag_stats_t{};
+        tl_mstats = np2_map_multi_stats_t{};
+        if ((out_flags & NP2_ALN_QUAL) && quals) tl_tstats.qual_reads = check_quals(quals, ends, who);
+        const uint32_t tag_flags = out_flags & ~(uint32_t)NP2_ALN_QUAL;
+        Mapper m(*ix, o);
+        m.align_with(ao);
+        m.tag_flags = tag_flags;
+        Units u, all;
+        TagTexts tt;
+        if (mo.max_chains > 1) m.more_with(mo, &u, false);
+        if (tag_flags) m.tt = mo.max_chains > 1 ? &u.tt : &tt;
+        std::vector<uint32_t> local, cg;
+        std::vector<Hit> prim(n_reads);
+        std::vector<np2aln::Rec> recs(n_reads);
+        for (uint64_t r0 = 0; r0 < n_reads;) { // np2_map_align_bytes' batches
+            const uint64_t from = r0 ? ends[r0 - 1] + 1 : 0;
+            uint64_t r1 = r0 + 1;
+            while (r1 < n_reads && ends[r1] + 1 - from <= m.hooks.batch_bytes()) ++r1;
+            local.clear();
+            for (uint64_t i = r0; i < r1; ++i) local.push_back((uint32_t)(ends[i] - from));
+            u.clear(), cg.clear();
+            if (tag_flags) tt.begin(r1 - r0);
+            m.batch(reads + from, ends[r1 - 1] + 1 - from, local.data(), (uint32_t)(r1 - r0), prim.data() + r0, nullptr, recs.data() + r0, &cg);
+            if (mo.max_chains == 1) plain_units(u, prim.data() + r0, recs.data() + r0, r1 - r0, cg, tag_flags ? &tt : nullptr);
+            else tl_mstats.overflow_units += u.settle();
+            append_units(all, u);
+            r0 = r1;
+        }
+        give_units(all, n_reads, out_flags, unit_off, out);
+        return NP2_OK;
+    }, np2h::io_set_error);
+}
+
+int np2_map_align_files_m(const np2_map_index_t *ix, const char *const *paths, int n_paths, const np2_map_opts_t *map_opts,
+                          const np2_map_multi_opts_t *multi, const np2_align_opts_t *align_opts, uint32_t out_flags, const char *out_path,
+                          np2_map_stats_t *stats) {
+    return np2h::abi_guard([&] {
+        const std::string who = "np2_map_align_files_m";
+        const np2map::Opts o = checked(map_opts, who.c_str());
+        const np2map::MultiOpts mo = checked_multi(multi, who);
+        const np2aln::Opts ao = checked_align(align_opts, who.c_str());
+        checked_out_flags(out_flags, NP2_ALN_QUAL | NP2_ALN_MD | NP2_ALN_CS | NP2_ALN_EQX, who);
+        tl_tstats = np2_align_tag_stats_t{};
+        tl_mstats = np2_map_multi_stats_t{};
+        const uint32_t tag_flags = out_flags & ~(uint32_t)NP2_ALN_QUAL;
+        const bool with_qual = (out_flags & NP2_ALN_QUAL) != 0;
+        check_index_opts(ix, o, who.c_str());
+        if (!paths || n_paths < 1) throw Np2Error(NP2_E_ARG, who + ": no read file given");
+        if (!out_path) throw Np2Error(NP2_E_ARG, who + ": out_path is NULL");
+        const std::vector<std::string> files = checked_files(paths, n_paths, who);
+        Mapper m(*ix, o);
+        m.align_with(ao);
+        m.tag_flags = tag_flags;
+        Units u;
+        TagTexts tt;
+        if (mo.max_chains > 1) m.more_with(mo, &u, false);
+        if (tag_flags) m.tt = mo.max_chains > 1 ? &u.tt : &tt;
+        np2h::OutFile out;
+        out.open(out_path, ix->device);
+        std::vector<Hit> hits;
+        std::string text;
+        std::vector<np2aln::Rec> recs;
+        std::vector<uint32_t> cigar;
+        np2aln::sam_header(text, ix->names, ix->lens);
+        out.put(text.data(), text.size());
+        read_batches(files, m.hooks, who, [&](const BatchBuf &b) {
+            hits.resize(b.ends.size()), recs.resize(b.ends.size()), cigar.clear(), u.clear();
+            if (tag_flags) tt.begin(b.ends.size());
+            m.batch(b.bytes.data(), b.closed(), b.ends.data(), (uint32_t)b.ends.size(), hits.data(), nullptr, recs.data(), &cigar);
+            const auto t0 = std::chrono::steady_clock::now();
+            if (mo.max_chains == 1) { // the plain door's writer: the parent's bytes
+                write_sam(out, *ix, b, hits, recs, cigar, text, tag_flags ? &tt : nullptr);
+                tl_mstats.units += hits.size();
+            } else {
+                tl_mstats.overflow_units += u.settle();
+                tl_mstats.units += u.hits.size();
+                write_sam_units(out, *ix, b, u, text, tag_flags != 0);
+            }
+            const float ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            tl_stats.write_ms += ms, tl_astats.write_ms += ms;
+        }, with_qual);
+        out.close();
+        fill_stats(stats);
+        return NP2_OK;
+    }, np2h::io_set_error);
+}
+
+int np2_map_align_host_m(const uint8_t *asm_stream, uint64_t n_asm, const uint8_t *reads, uint64_t n, uint64_t n_reads,
+                         const np2_map_opts_t *map_opts, const np2_map_multi_opts_t *multi, const np2_align_opts_t *align_opts,
+                         const np2_map_weights_t *wts, uint32_t out_flags, uint64_t *unit_off, np2_map_units_t *out) {
+    return np2h::abi_guard([&] {
+        const std::string who = "np2_map_align_host_m";
+        if (out) *out = np2_map_units_t{};
+        const np2map::Opts o = checked(map_opts, who.c_str());
+        const np2map::MultiOpts mo = checked_multi(multi, who);
+        np2aln::Opts ao = checked_align(align_opts, who.c_str());
+        const np2map::WeightSet *ws = checked_weights(wts, o, who.c_str());
+        checked_out_flags(out_flags, NP2_ALN_MD | NP2_ALN_CS | NP2_ALN_EQX, who);
+        if (!unit_off || !out) throw Np2Error(NP2_E_ARG, who + ": unit_off and out are outputs: neither may be NULL");
+        const std::vector<uint64_t> a_ends = ends_of(asm_stream, n_asm, who.c_str(), "the assembly stream");
+        const std::vector<uint64_t> ends = ends_of(reads, n, who.c_str(), "the read stream");
+        if (ends.size() != n_reads)
+            throw Np2Error(NP2_E_ARG, who + ": n_reads is " + std::to_string(n_reads) + ", the stream holds " + std::to_string(ends.size()) + " newlines");
+        const Hooks hooks;
+        if (ao.max_cells > hooks.align_cells) ao.max_cells = hooks.align_cells;
+        np2map::HostIndex hx;
+        hx.build(asm_stream, a_ends, o.k, o.w, ws);
+        np2_map_stats_t &st = tl_stats;
+        st = np2_map_stats_t{};
+        st.index_minimizers = hx.mz.size();
+        tl_astats = np2_align_stats_t{};
+        tl_tstats = np2_align_tag_stats_t{};
+        tl_mstats = np2_map_multi_stats_t{};
+        Units u;
+        np2map::ReadCounts rc;
+        np2map::MoreCounts mc{};
+        np2aln::Scratch w;
+        unsigned long long ctr[np2aln::C_N] = {};
+        Hit uh[np2map::MAX_CHAINS];
+        uint32_t ucls[np2map::MAX_CHAINS], upar[np2map::MAX_CHAINS];
+        std::vector<uint32_t> ch, split;
+        uint64_t from = 0;
+        for (uint64_t i = 0; i < n_reads; ++i) {
+            ch.clear();
+            const uint32_t nu = np2map::map_read_m(hx, reads + from, (uint32_t)(ends[i] - from), o, mo, uh, ucls, upar, &ch, &rc, &mc);
+            ++(uh[0].tid >= 0 ? st.mapped : st.unmapped);
+            u.n_units.push_back(nu);
+            size_t ch_at = 0;
+            for (uint32_t t = 0; t < nu; ++t) {
+                const Hit &h = uh[t];
+                const size_t at = u.hits.size();
+                u.hits.push_back(h), u.cls.push_back((uint8_t)ucls[t]), u.parent.push_back(upar[t]);
+                u.recs.push_back(np2aln::unaligned_rec());
+                if (out_flags) u.tt.n_md.push_back(0), u.tt.n_cs.push_back(0);
+                if (h.tid < 0) continue;
+                const uint64_t t_at = h.tid ? a_ends[(size_t)h.tid - 1] + 1 : 0;
+                uint64_t c64[np2aln::C_N] = {};
+                np2aln::Rec &r = u.recs[at];
+                r = np2aln::align_read(asm_stream + t_at, (uint32_t)(a_ends[(size_t)h.tid] - t_at), reads + from, h, ch.data() + ch_at, o.k, ao, ao.max_cells, w,
+                                       u.cigar, c64);
+                ch_at += 2 * (size_t)h.n;
+                for (int f = 0; f < np2aln::C_N; ++f) ctr[f] += c64[f];
+                if (out_flags && r.tid >= 0) {
+                    const size_t cg_at = u.cigar.size() - r.n_cigar;
+                    const np2aln::TagIn in{asm_stream + t_at + r.pos, reads + from, h.qlen, h.rev, u.cigar.data() + cg_at, r.n_cigar};
+                    split.clear();
+                    tags_of_record(in, out_flags, u.tt, at, &split);
+                    if (out_flags & NP2_ALN_EQX) {
+                        u.cigar.resize(cg_at), u.cigar.insert(u.cigar.end(), split.begin(), split.end());
+                        r.n_cigar = (uint32_t)split.size(), tl_tstats.eqx_words += split.size();
+                    }
+                }
+            }
+            from = ends[i] + 1;
+        }
+        st.reads = n_reads, st.minimizers = rc.minimizers, st.anchors = rc.anchors, st.dropped_occ = rc.dropped_occ;
+        add_counts(tl_astats, ctr);
+        const unsigned long long c5[5] = {mc.selections, mc.dropped_cnt, mc.dropped_pri, mc.kept_supp, mc.kept_sec};
+        add_more_counts(tl_mstats, c5);
+        tl_mstats.overflow_units = u.settle();
+        tl_tstats.md_bytes = u.tt.md.size(), tl_tstats.cs_bytes = u.tt.cs.size();
+        give_units(u, n_reads, out_flags, unit_off, out);
+        return NP2_OK;
+    }, np2h::io_set_error);
+}
+
+int np2_map_last_multi_stats(np2_map_multi_stats_t *stats) {
+    return np2h::abi_guard([&] {
+        if (!stats) throw Np2Error(NP2_E_ARG, "np2_map_last_multi_stats: stats is NULL");
+        *stats = tl_mstats;
+        return NP2_OK;
+    }, np2h::io_set_error);
 }
 
 // np2_map_align_bytes (out_flags 0, no texts) and np2_map_align_bytes_x

@@ -80,6 +80,20 @@ MAP_HIT_DTYPE = np.dtype([("tid", "<i4")] + [(f, "<u4") for f in ("qlen", "qs", 
 assert MAP_HIT_DTYPE.itemsize == 52
 
 
+class np2_map_multi_opts_t(C.Structure):
+    _fields_ = [(f, C.c_uint32) for f in ("max_chains", "supplementary", "secondary_n", "mask_pm", "pri_pm")]
+
+
+class np2_map_multi_stats_t(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("units", "selections", "dropped_min_cnt", "dropped_secondary", "kept_supplementary", "kept_secondary",
+                                          "overflow_units")] + [("more_ms", C.c_float)]
+
+
+assert C.sizeof(np2_map_multi_opts_t) == 20 and C.sizeof(np2_map_multi_stats_t) == 64
+MULTI_DEFAULTS = dict(max_chains=1, supplementary=0, secondary_n=0, mask_pm=500, pri_pm=800)
+MAP_CLS = ("primary", "supplementary", "secondary")  # a unit's cls
+
+
 class np2_align_opts_t(C.Structure):
     _fields_ = [(f, C.c_uint32) for f in ("match", "mismatch", "gap_open", "gap_ext", "band", "end_bonus", "ext_max", "max_cells")]
 
@@ -99,6 +113,11 @@ ALIGN_DEFAULTS = dict(match=1, mismatch=4, gap_open=6, gap_ext=2, band=32, end_b
 # np2_align_rec_t
 ALIGN_REC_DTYPE = np.dtype([("tid", "<i4")] + [(f, "<u4") for f in ("flag", "pos", "end", "mapq", "n_cigar", "nm")] + [("as", "<i4")])
 assert ALIGN_REC_DTYPE.itemsize == 32
+
+
+class np2_map_units_t(C.Structure):
+    _fields_ = [("n_units", C.c_uint64)] + [(f, C.c_void_p) for f in ("hits", "cls", "parent", "recs", "cigar", "cigar_off", "md", "md_off", "cs",
+                                                                      "cs_off")]
 
 
 class FrontOpts:
@@ -349,6 +368,11 @@ def _bind_map(L):
     L.np2_map_files.argtypes = [vp, C.POINTER(C.c_char_p), C.c_int, mo, C.c_char_p, C.POINTER(np2_map_stats_t)]
     L.np2_map_host.argtypes = [vp, u64, vp, u64, u64, mo, vp, C.POINTER(vp), vp]
     L.np2_map_last_stats.argtypes = [C.POINTER(np2_map_stats_t)]
+    mm, pvp = C.POINTER(np2_map_multi_opts_t), C.POINTER(vp)
+    L.np2_map_bytes_m.argtypes = [vp, vp, u64, u64, mo, mm, vp, pvp, pvp, pvp, pvp, pvp]
+    L.np2_map_files_m.argtypes = [vp, C.POINTER(C.c_char_p), C.c_int, mo, mm, C.c_char_p, C.POINTER(np2_map_stats_t)]
+    L.np2_map_host_m.argtypes = [vp, u64, vp, u64, u64, mo, mm, vp, vp, pvp, pvp, pvp, pvp, pvp]
+    L.np2_map_last_multi_stats.argtypes = [C.POINTER(np2_map_multi_stats_t)]
     L.np2_map_weights_from_indices.argtypes = [C.c_uint32, vp, u64, C.POINTER(vp)]
     L.np2_map_weights_from_file.argtypes = [C.c_char_p, C.POINTER(vp)]
     L.np2_map_weights_info.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(u64)]
@@ -367,6 +391,10 @@ def _bind_map(L):
     u32 = C.c_uint32
     L.np2_map_align_bytes_x.argtypes = [vp, vp, vp, u64, u64, mo, ao, u32, vp, vp, C.POINTER(vp), vp, C.POINTER(vp), vp, C.POINTER(vp), vp]
     L.np2_map_align_files_x.argtypes = [vp, C.POINTER(C.c_char_p), C.c_int, mo, ao, u32, C.c_char_p, C.POINTER(np2_map_stats_t)]
+    mm_, pu = C.POINTER(np2_map_multi_opts_t), C.POINTER(np2_map_units_t)
+    L.np2_map_align_bytes_m.argtypes = [vp, vp, vp, u64, u64, mo, mm_, ao, u32, vp, pu]
+    L.np2_map_align_files_m.argtypes = [vp, C.POINTER(C.c_char_p), C.c_int, mo, mm_, ao, u32, C.c_char_p, C.POINTER(np2_map_stats_t)]
+    L.np2_map_align_host_m.argtypes = [vp, u64, vp, u64, u64, mo, mm_, ao, vp, u32, vp, pu]
     L.np2_map_align_host_x.argtypes = [vp, u64, vp, u64, u64, mo, ao, vp, u32, vp, vp, C.POINTER(vp), vp, C.POINTER(vp), vp, C.POINTER(vp), vp]
     L.np2_align_tags_device.argtypes = [C.c_int, vp, u64, vp, u64, u64, vp, vp, vp, vp, u32] + [C.POINTER(vp), vp] * 3
     L.np2_align_tags_host.argtypes = [vp, u64, vp, u64, u64, vp, vp, vp, vp, u32] + [C.POINTER(vp), vp] * 3
@@ -1568,34 +1596,102 @@ class MapIndex:
                                                                      C.byref(o), C.byref(ao), flags, *a[3:]), s, n, md, cs)
 
 
-def map_reads(index, reads, chains=False, **kw):
+def multi_opts(multi=None, **kw):
+    """np2_map_multi_opts_t (np2_io.h, "More chains") from a dict and / or keyword options; what is not given takes its
+    default (MULTI_DEFAULTS: one chain per read, the plain mapper)"""
+    if isinstance(multi, np2_map_multi_opts_t):
+        return multi
+    kw = {**(multi or {}), **kw}
+    unknown = set(kw) - set(MULTI_DEFAULTS)
+    if unknown:
+        raise TypeError(f"unknown multi-chain option(s): {sorted(unknown)}")
+    vals = {**MULTI_DEFAULTS, **{k: v for k, v in kw.items() if v is not None}}
+    for k, v in vals.items():
+        if not 0 <= int(v) <= 0xFFFFFFFF:
+            raise ValueError(f"{k}: 0 .. 2^32 - 1")
+    return np2_map_multi_opts_t(*[int(vals[f]) for f, _ in np2_map_multi_opts_t._fields_])
+
+
+def multi_chains_default(supplementary, secondary_n):
+    """the command line's --max_chains when it is not given: 1 + N + 4 * supp, 16 at the most"""
+    return min(16, 1 + int(secondary_n) + 4 * int(bool(supplementary)))
+
+
+def map_last_multi_stats():
+    """counts and the selection kernels' time (HIP events, ms) of this thread's last call with multi="""
+    st = np2_map_multi_stats_t()
+    _io_check(_bind().np2_map_last_multi_stats(C.byref(st)))
+    return {f: getattr(st, f) for f, _ in np2_map_multi_stats_t._fields_}
+
+
+def _units_result(L, call, s, n, want_chains):
+    """an _m door's outputs -> (unit_off, hits, cls, parent[, chain, chain_off]): read i's units are unit_off[i] ..
+    unit_off[i + 1], the primary first; chain rows of unit u are chain_off[u] .. chain_off[u + 1]"""
+    from .api import _Raw
+    unit_off = np.zeros(n + 1, np.uint64)
+    ph, pc, pp, pch, pco = (C.c_void_p() for _ in range(5))
+    try:
+        _io_check(call(s.ctypes.data if len(s) else None, len(s), n, unit_off.ctypes.data, C.byref(ph), C.byref(pc), C.byref(pp),
+                       C.byref(pch) if want_chains else None, C.byref(pco) if want_chains else None))
+        m = int(unit_off[n])
+        take = lambda p, cnt, dt: np.asarray(_Raw(p.value, cnt, dt)).copy() if cnt else np.zeros(0, dt)
+        hits = take(ph, m * MAP_HIT_DTYPE.itemsize, "u1").view(MAP_HIT_DTYPE) if m else np.zeros(0, MAP_HIT_DTYPE)
+        cls, parent = take(pc, m, "u1"), take(pp, m, "<u4")
+        if not want_chains:
+            return unit_off, hits, cls, parent
+        off = take(pco, m + 1, "<u8")
+        rows = int(off[m])
+        chain = take(pch, 2 * rows, "<u4").reshape(rows, 2)
+        return unit_off, hits, cls, parent, chain, off
+    finally:
+        for p in (ph, pc, pp, pch, pco):
+            if p.value:
+                L.np2_free(p)
+
+
+def map_reads(index, reads, chains=False, multi=None, **kw):
     """np2_map_bytes: reads (a separator stream or a list of sequences) against a MapIndex -> hits, a MAP_HIT_DTYPE array
     with one entry per read (tid -1: unmapped); with chains=True -> (hits, chain, chain_off): the primary chains' anchors
-    (r, q) as a uint32 [m, 2] array and read i's rows chain_off[i] .. chain_off[i + 1].  Options: MAP_DEFAULTS."""
+    (r, q) as a uint32 [m, 2] array and read i's rows chain_off[i] .. chain_off[i + 1].  Options: MAP_DEFAULTS.
+    With multi= (a dict of MULTI_DEFAULTS' keys): np2_map_bytes_m, per unit -> (unit_off, hits, cls, parent[, chain,
+    chain_off]) as _units_result describes them."""
     L = _bind()
     s, n = _stream_of(reads)
     o = index._opts(kw)
+    if multi is not None:
+        m = multi_opts(multi)
+        return _units_result(L, lambda *a: L.np2_map_bytes_m(index._h, a[0], a[1], a[2], C.byref(o), C.byref(m), *a[3:]), s, n, chains)
     hits, chain, off = _map_result(L, lambda *a: L.np2_map_bytes(index._h, a[0], a[1], a[2], C.byref(o), a[3], a[4], a[5]), s, n, chains)
     return (hits, chain, off) if chains else hits
 
 
-def map_files(index, paths, out_path, **kw):
-    """np2_map_files: read files -> the PAF file out_path (BGZF when it ends in .gz / .bgz) -> the stats dict"""
+def map_files(index, paths, out_path, multi=None, **kw):
+    """np2_map_files: read files -> the PAF file out_path (BGZF when it ends in .gz / .bgz) -> the stats dict.  With multi=
+    (a dict of MULTI_DEFAULTS' keys): np2_map_files_m, the further chains' lines behind each read's primary line"""
     L = _bind()
     arr, n = _paths(paths)
     o, st = index._opts(kw), np2_map_stats_t()
-    _io_check(L.np2_map_files(index._h, arr, n, C.byref(o), None if out_path is None else os.fspath(out_path).encode(), C.byref(st)))
+    out = None if out_path is None else os.fspath(out_path).encode()
+    if multi is not None:
+        m = multi_opts(multi)
+        _io_check(L.np2_map_files_m(index._h, arr, n, C.byref(o), C.byref(m), out, C.byref(st)))
+    else:
+        _io_check(L.np2_map_files(index._h, arr, n, C.byref(o), out, C.byref(st)))
     return _map_stats_dict(st)
 
 
-def map_host(asm, reads, chains=False, weights=None, **kw):
-    """np2_map_host / np2_map_host_w (no device): the same rule on the CPU -> what map_reads returns.  weights: a MapWeights"""
+def map_host(asm, reads, chains=False, weights=None, multi=None, **kw):
+    """np2_map_host / np2_map_host_w (no device): the same rule on the CPU -> what map_reads returns.  weights: a MapWeights.
+    With multi=: np2_map_host_m, per unit, as map_reads returns it"""
     L = _bind()
     a, _ = _stream_of(asm)
     s, n = _stream_of(reads)
     o = map_opts(**kw)
     wh = _weights_handle(weights)
     ap = a.ctypes.data if len(a) else None
+    if multi is not None:
+        m = multi_opts(multi)
+        return _units_result(L, lambda *x: L.np2_map_host_m(ap, len(a), x[0], x[1], x[2], C.byref(o), C.byref(m), wh, *x[3:]), s, n, chains)
     if wh is None:
         call = lambda *x: L.np2_map_host(ap, len(a), x[0], x[1], x[2], C.byref(o), x[3], x[4], x[5])
     else:
@@ -1726,15 +1822,75 @@ def _align_result(L, call, s, n):
     return hits, recs, cigar, off
 
 
-def map_align_files(index, paths, out_path, qual=False, md=False, cs=False, eqx=False, **kw):
+def _aligned_units(L, call, n, md, cs):
+    """an aligned _m door's outputs -> a dict: unit_off, hits, cls, parent, recs, cigar, cigar_off and, when asked for, md and cs
+    as lists of bytes, one per unit"""
+    from .api import _Raw
+    unit_off, out = np.zeros(n + 1, np.uint64), np2_map_units_t()
+    try:
+        _io_check(call(unit_off.ctypes.data, C.byref(out)))
+        m = int(out.n_units)
+        take = lambda p, cnt, dt: np.asarray(_Raw(p, cnt, dt)).copy() if cnt else np.zeros(0, dt)
+        r = dict(unit_off=unit_off, hits=take(out.hits, m * MAP_HIT_DTYPE.itemsize, "u1").view(MAP_HIT_DTYPE),
+                 cls=take(out.cls, m, "u1"), parent=take(out.parent, m, "<u4"),
+                 recs=take(out.recs, m * ALIGN_REC_DTYPE.itemsize, "u1").view(ALIGN_REC_DTYPE), cigar_off=take(out.cigar_off, m + 1, "<u8"))
+        r["cigar"] = take(out.cigar, int(r["cigar_off"][m]), "<u4")
+        for key, want, p, po in (("md", md, out.md, out.md_off), ("cs", cs, out.cs, out.cs_off)):
+            r[key] = None
+            if want:
+                off = take(po, m + 1, "<u8")
+                text = bytes(take(p, int(off[m]), "u1"))
+                r[key] = [text[int(off[i]):int(off[i + 1])] for i in range(m)]
+        return r
+    finally:
+        for f, _ in np2_map_units_t._fields_[1:]:
+            if getattr(out, f):
+                L.np2_free(getattr(out, f))
+
+
+def map_align_reads_m(index, reads, multi, quals=None, md=False, cs=False, eqx=False, **kw):
+    """np2_map_align_bytes_m: MapIndex.align_x per unit (np2_io.h, "More chains") -> the dict of _aligned_units"""
+    L = _bind()
+    s, n = _stream_of(reads)
+    akw = {f: kw.pop(f) for f in list(kw) if f in ALIGN_DEFAULTS}
+    o, ao, m = index._opts(kw), align_opts(**akw), multi_opts(multi)
+    flags = (ALN_MD if md else 0) | (ALN_CS if cs else 0) | (ALN_EQX if eqx else 0)
+    qs = None
+    if quals is not None:
+        flags |= ALN_QUAL
+        qs = _qual_stream(quals, s, n)
+    return _aligned_units(L, lambda uo, out: L.np2_map_align_bytes_m(index._h, s.ctypes.data if len(s) else None,
+                                                                     None if qs is None or not len(qs) else qs.ctypes.data, len(s), n, C.byref(o),
+                                                                     C.byref(m), C.byref(ao), flags, uo, out), n, md, cs)
+
+
+def map_align_host_m(asm, reads, multi, weights=None, md=False, cs=False, eqx=False, **kw):
+    """np2_map_align_host_m (no device): map_align_host_x per unit -> the dict of _aligned_units"""
+    L = _bind()
+    a, _ = _stream_of(asm)
+    s, n = _stream_of(reads)
+    akw = {f: kw.pop(f) for f in list(kw) if f in ALIGN_DEFAULTS}
+    o, ao, m = map_opts(**kw), align_opts(**akw), multi_opts(multi)
+    flags = (ALN_MD if md else 0) | (ALN_CS if cs else 0) | (ALN_EQX if eqx else 0)
+    return _aligned_units(L, lambda uo, out: L.np2_map_align_host_m(a.ctypes.data if len(a) else None, len(a), s.ctypes.data if len(s) else None, len(s),
+                                                                    n, C.byref(o), C.byref(m), C.byref(ao), _weights_handle(weights), flags, uo, out),
+                          n, md, cs)
+
+
+def map_align_files(index, paths, out_path, qual=False, md=False, cs=False, eqx=False, multi=None, **kw):
     """np2_map_align_files: read files -> the SAM file out_path (BGZF when it ends in .gz / .bgz) -> the mapper's stats dict.
     With qual / md / cs / eqx (np2_map_align_files_x; np2_io.h, "Tags"): QUAL from FASTQ input, MD:Z: and cs:Z: behind s2:i:,
-    = and X in the CIGAR."""
+    = and X in the CIGAR.  With multi= (np2_map_align_files_m; "More chains"): the further units' records behind each primary."""
     L = _bind()
     arr, n = _paths(paths)
     akw = {f: kw.pop(f) for f in list(kw) if f in ALIGN_DEFAULTS}
     o, ao, st = index._opts(kw), align_opts(**akw), np2_map_stats_t()
     flags = (ALN_QUAL if qual else 0) | (ALN_MD if md else 0) | (ALN_CS if cs else 0) | (ALN_EQX if eqx else 0)
+    if multi is not None:
+        m = multi_opts(multi)
+        _io_check(L.np2_map_align_files_m(index._h, arr, n, C.byref(o), C.byref(m), C.byref(ao), flags,
+                                          None if out_path is None else os.fspath(out_path).encode(), C.byref(st)))
+        return _map_stats_dict(st)
     if flags:
         _io_check(L.np2_map_align_files_x(index._h, arr, n, C.byref(o), C.byref(ao), flags, None if out_path is None else os.fspath(out_path).encode(),
                                           C.byref(st)))

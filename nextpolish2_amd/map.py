@@ -6,6 +6,7 @@ by base and written as SAM (the recipe's `winnowmap -ax` step; its SAM pipes int
                                   [-a [-A 1] [-B 4] [-O 6] [-E 2] [--band 32] [--end_bonus 5] [--ext_max 2048] [--max_cells N]
                                       [--qual] [--MD] [--cs] [--eqx]]
                                   [-W repetitive_k15.txt | --rep [distinct=0.9998 | min_count=N]]
+                                  [--supp] [--secondary N | -N N] [--max_chains N] [--mask_level 0.5] [--pri_ratio 0.8]
 
 One line per mapped read, in read order: qname qlen qs qe strand tname tlen ts te matches block mapq tp:A:P cm:i: s1:i: s2:i:
 (the rule: include/np2_io.h, np2_map_*; it follows minimap2's published seed-and-chain algorithm and is not pinned against
@@ -25,6 +26,16 @@ With -W FILE (winnowmap's -W): the k-mers of the list (one a line, as python -m 
 writes it; plain or gzip) are made less likely to win a minimizer window, so that the unique k-mers inside repeats become
 the seeds (the rule: np2_map_*, "Weights"; 11 <= k <= 15).  --rep counts the assembly's own repetitive k-mers in this process
 with repkmers' rule instead, and no list file is written.  With either and no -k, k is the list's (15 for --rep).
+
+With --supp and / or --secondary N (the rule: np2_io.h, "More chains"): a read's further chains follow its primary line, a
+supplementary one (another part of the read, as across a misjoin) with tp:A:P, a secondary one (the same part of the read
+at another copy of a repeat) with tp:A:S, s2:i:0 and mapq 0.  --max_chains caps the selections per read, the primary among
+them [1 + N + 4 with --supp, 16 at the most]; --mask_level and --pri_ratio are minimap2's, kept per mille.  With -a every
+kept chain is aligned and written as a record of its own behind the read's primary: FLAG | 2048 (supplementary) or | 256
+(secondary), soft clips with the full SEQ (and QUAL with --qual), and SA:Z: as the last field of a read's primary and
+supplementary records when it has more than one.  `map -a --supp ... | cli - asm.fa.gz k21.yak k31.yak -s -c 100000` and
+`map -a --secondary 5 --qual ... | samsort - --full -o x.bam`, then `cli x.bam ... -S -q -1`, feed the polisher's -s and -S
+doors.  --stats then gains MULTI_STATS_HEADER and a row.
 """
 import argparse
 import os
@@ -109,6 +120,41 @@ def tag_stats_row(stats):
     return "\t".join(TAG_STATS_HEADER) + "\n" + "\t".join(cells) + "\n"
 
 
+MULTI_STATS_HEADER = ("units", "selections", "dropped_min_cnt", "dropped_secondary", "kept_supplementary", "kept_secondary", "overflow_units",
+                      "more_ms")
+
+
+def multi_stats_row(stats):
+    """--stats with --supp / --secondary / --max_chains: a further header line and TSV row"""
+    cells = [str(int(stats[f])) for f in MULTI_STATS_HEADER[:7]] + ["%.3f" % float(stats["more_ms"])]
+    return "\t".join(MULTI_STATS_HEADER) + "\n" + "\t".join(cells) + "\n"
+
+
+def per_mille(text):
+    """argparse type of --mask_level / --pri_ratio: a fraction in 0 .. 1, converted once to per mille by rounding"""
+    try:
+        f = float(text)
+    except ValueError:
+        f = -1.0
+    if not 0.0 <= f <= 1.0:
+        raise argparse.ArgumentTypeError(f"{text!r}: a fraction in 0 .. 1 is expected")
+    return int(f * 1000.0 + 0.5)
+
+
+def multi_of(a):
+    """the parsed arguments -> the multi-chain options as a dict, or None when none of them was given (the plain doors)"""
+    from .io import MULTI_DEFAULTS, multi_chains_default
+    if not a.supp and a.secondary is None and a.max_chains is None and a.mask_level is None and a.pri_ratio is None:
+        return None
+    n = a.secondary or 0
+    cap = a.max_chains
+    if cap is None:
+        cap = multi_chains_default(a.supp, n) if (a.supp or a.secondary is not None) else MULTI_DEFAULTS["max_chains"]
+    return dict(max_chains=cap, supplementary=int(a.supp), secondary_n=n,
+                mask_pm=MULTI_DEFAULTS["mask_pm"] if a.mask_level is None else a.mask_level,
+                pri_pm=MULTI_DEFAULTS["pri_pm"] if a.pri_ratio is None else a.pri_ratio)
+
+
 def build_parser():
     from .io import ALIGN_DEFAULTS as AD
     from .io import MAP_DEFAULTS as D
@@ -141,6 +187,12 @@ def build_parser():
                    help="down-weight the k-mers of this list in minimizer sampling (winnowmap -W; one k-mer a line, [GZIP]; 11 <= k <= 15)")
     g.add_argument("--rep", nargs="?", const=dict(distinct=0.9998), default=None, type=rep_arg, metavar="distinct=F|min_count=N",
                    help="down-weight the assembly's own repetitive k-mers, counted here with repkmers' rule [distinct=0.9998]")
+    p.add_argument("--supp", action="store_true", help="report supplementary chains: other parts of the read (tp:A:P)")
+    p.add_argument("--secondary", "-N", dest="secondary", type=int, default=None, metavar="N",
+                   help="report up to N secondary chains per parent: the same part of the read elsewhere (tp:A:S), 0 .. 15 [0]")
+    p.add_argument("--max_chains", type=int, default=None, metavar="N", help="selections per read, the primary among them, 1 .. 16 [1 + N + 4 with --supp]")
+    p.add_argument("--mask_level", type=per_mille, default=None, metavar="F", help="a chain that overlaps a parent by more than F of the shorter is secondary [0.5]")
+    p.add_argument("--pri_ratio", type=per_mille, default=None, metavar="F", help="keep a secondary chain that scores F of its parent or more [0.8]")
     return p
 
 
@@ -153,6 +205,11 @@ def main(argv=None):
     for f, flag in TAG_FLAGS:
         if tags[f] and not a.sam:
             parser.error(f"{flag} needs -a (it is an output of the base-level alignment)")
+    multi = multi_of(a)
+    if multi is not None:
+        for f, v in multi.items():
+            if not 0 <= v <= 0xFFFFFFFF:
+                raise SystemExit(f"Error: {f}: 0 .. 4294967295")
     wk = 0
     if a.weights is not None:
         try:
@@ -182,6 +239,7 @@ def main(argv=None):
             out = tmp
         try:
             np2io.map_opts(k=k, w=w, **kw)
+            multi_stats = None
             weights = None
             if a.weights is not None:
                 weights = np2io.MapWeights(a.weights)
@@ -192,11 +250,15 @@ def main(argv=None):
                     weights.close()
                 if a.sam:
                     np2io.align_opts(**akw)
-                    stats = np2io.map_align_files(ix, a.reads, out, **tags, **kw, **akw)
+                    stats = np2io.map_align_files(ix, a.reads, out, multi=multi, **tags, **kw, **akw)
+                    if multi is not None:
+                        multi_stats = np2io.map_last_multi_stats()
                     align_stats = np2io.align_last_stats()
                     tag_stats = np2io.align_last_tag_stats() if any(tags.values()) else None
                 else:
-                    stats = np2io.map_files(ix, a.reads, out, **kw)
+                    stats = np2io.map_files(ix, a.reads, out, multi=multi, **kw)
+                    if multi is not None:
+                        multi_stats = np2io.map_last_multi_stats()
                 index_ms, wstats = ix.build_ms, (ix.weights_k, ix.weights_listed)
         except (api.Np2Error, ImportError) as e:
             raise SystemExit(f"Error: {e}")
@@ -211,6 +273,8 @@ def main(argv=None):
                     f.write(align_stats_row(align_stats))
                     if tag_stats is not None:
                         f.write(tag_stats_row(tag_stats))
+                if multi_stats is not None:
+                    f.write(multi_stats_row(multi_stats))
     finally:
         if tmp is not None and os.path.exists(tmp):
             os.remove(tmp)
