@@ -698,6 +698,53 @@ int np2_map_align_host_w(const uint8_t *asm_stream, uint64_t n_asm, const uint8_
                          np2_align_rec_t *recs, uint32_t **cigar, uint64_t *cigar_off);
 /* the alignment counts and stage times of the last np2_map_align_* call on this thread */
 int np2_map_align_last_stats(np2_align_stats_t *stats);
+/* Caller-built chains: the aligner alone, on the caller's hits and chains (as np2_align_tags_device runs the tag walk on the
+ * caller's records).  Nothing is sketched, seeded or chained.  np2_align_chains_device runs the kernels np2_map_align_bytes
+ * runs behind its chaining, as one group, against the index's assembly; np2_align_chains_host runs the host aligner against
+ * asm_stream.  reads: a separator stream of n_reads reads; hits[n_reads] as the mapping doors return them (of a hit the aligner
+ * reads tid, rev, qlen, n and mapq; tid < 0: an unmapped read, flag 4); chain_off[n_reads + 1] and chain: read i's (r, q)
+ * pairs are chain_off[i] .. chain_off[i + 1], hits[i].n of them (none for an unmapped read).  recs, cigar and cigar_off as from
+ * np2_map_align_bytes; np2_map_align_last_stats has the counts (np2_map_last_stats: reads, mapped, unmapped and, from the
+ * device, groups).
+ *   Checked on the host before anything is uploaded, a violation being NP2_E_ARG with a message that names the read (and the
+ *   anchor): k is the index's (the host door: 11 .. 28); chain_off[0] is 0, chain_off ascends and chain_off[i + 1] -
+ *   chain_off[i] is hits[i].n for a mapped read and 0 for an unmapped one; for a mapped read tid names a contig, qlen is the
+ *   read's length, rev is 0 or 1 and n >= 1; for every anchor k - 1 <= r < the contig's length and k - 1 <= q < qlen.  Order
+ *   among the anchors is not checked: the pin rule ignores an anchor that is not k beyond the last pin on both axes.
+ *   probe (NULL: none), for tests: what the matrices held.  want is the caller's: NP2_PROBE_SLOTS asks for slot_off[n_reads +
+ *   1], slots and res (read i's slots slot_off[i] .. slot_off[i + 1]: head, segments, tail; none for an unmapped read; res of
+ *   a slot without a matrix is all zero); NP2_PROBE_TB for tb_off[n_slots + 1] and tb, one byte of traceback bits per cell of
+ *   every matrix, rows of W bytes (bits 0-1: H's source, 0 diagonal, 1 E, 2 F; bit 2: E continues a gap; bit 3: F continues a
+ *   gap; a slot outside the matrix: 0).  The arrays are np2_free-owned.  A read over the limits keeps its slots, and those of
+ *   its matrices that are within the limits are computed.  On the device the traceback buffer is reused per sub-group
+ *   (NP2_ALIGN_TEST_BUDGET), so its bytes are copied out per sub-group and appended. */
+typedef struct np2_align_slot {
+    uint32_t t0, q0, tl, ql, pre, suf, kind, W; /* kind: 0 equal, 1 pure gap, 2 snv, 3 core, 4 head, 5 tail, 6 nothing */
+    int32_t lo;                      /* the band: diagonals lo .. lo + W - 1 */
+    uint32_t over;
+} np2_align_slot_t;
+typedef struct np2_align_res {
+    int32_t score;
+    uint32_t ei, ej;                 /* the cell the walk starts from */
+} np2_align_res_t;
+#define NP2_PROBE_SLOTS 1u
+#define NP2_PROBE_TB 2u
+typedef struct np2_align_probe {
+    uint32_t want;                   /* in: a sum of NP2_PROBE_* */
+    uint32_t pad;
+    uint64_t n_slots;
+    uint64_t *slot_off;
+    np2_align_slot_t *slots;
+    np2_align_res_t *res;
+    uint64_t *tb_off;
+    uint8_t *tb;
+} np2_align_probe_t;
+int np2_align_chains_device(const np2_map_index_t *ix, const uint8_t *reads, uint64_t n, uint64_t n_reads, uint32_t k,
+                            const np2_map_hit_t *hits, const uint32_t *chain, const uint64_t *chain_off, const np2_align_opts_t *align_opts,
+                            np2_align_rec_t *recs, uint32_t **cigar, uint64_t *cigar_off, np2_align_probe_t *probe);
+int np2_align_chains_host(const uint8_t *asm_stream, uint64_t n_asm, const uint8_t *reads, uint64_t n, uint64_t n_reads, uint32_t k,
+                          const np2_map_hit_t *hits, const uint32_t *chain, const uint64_t *chain_off, const np2_align_opts_t *align_opts,
+                          np2_align_rec_t *recs, uint32_t **cigar, uint64_t *cigar_off, np2_align_probe_t *probe);
 
 /* ---- Tags: base qualities, MD, cs and = / X, the aligner's opt-in outputs (what a variant caller or a genome browser reads from
  * the BAM that samsort --full makes of the mapper's SAM) ------------------------------------------------------------------------

@@ -55,7 +55,7 @@ IO_ABI_SYMBOLS = [
     "np2_map_index_bytes_w", "np2_map_index_files_w", "np2_map_index_weights", "np2_map_host_w", "np2_map_align_host_w",
     "np2_map_align_bytes", "np2_map_align_files", "np2_map_align_host", "np2_map_align_last_stats",
     "np2_map_align_bytes_x", "np2_map_align_files_x", "np2_map_align_host_x", "np2_align_tags_device", "np2_align_tags_host",
-    "np2_map_align_last_tag_stats",
+    "np2_map_align_last_tag_stats", "np2_align_chains_device", "np2_align_chains_host",
     "np2_sam_open", "np2_sam_close", "np2_sam_n_refs", "np2_sam_ref_name", "np2_sam_stats", "np2_contig_from_sam",
     "np2_sam_parse_bytes", "np2_sam_export", "np2_sam_from_reads", "np2_sam_from_read_bytes", "np2_align_pack_host",
     "np2_sam_open_ex", "np2_sam_write_bam", "np2_sam_bam_stream", "np2_bamout_host", "np2_sam_export_names",

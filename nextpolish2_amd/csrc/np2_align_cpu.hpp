@@ -2,6 +2,7 @@
 // what tests/tools/align_core_test.cpp builds with a plain C++ compiler; and the SAM text both the host and the device paths
 // write.  No HIP here.
 #pragma once
+#include <cstddef>
 #include <cstdio>
 #include <string>
 #include <vector>
@@ -56,10 +57,29 @@ struct Scratch {
     std::vector<uint32_t> a, b;
 };
 
+// what np2_align_chains_* hand back for tests (np2_io.h, np2_align_probe_t): the reads' slots, the cells their walks start from and
+// the traceback bytes, in read order
+struct Probe {
+    bool want_tb = false;
+    std::vector<uint64_t> slot_off{0}, tb_off{0};
+    std::vector<Slot> slots;
+    std::vector<Res> res;
+    std::vector<uint8_t> tb;
+    void unmapped() { slot_off.push_back(slots.size()); }
+    void take(const Scratch &w, uint32_t ns) {
+        const uint64_t base = tb_off.back();
+        slots.insert(slots.end(), w.slots.begin(), w.slots.begin() + ns), res.insert(res.end(), w.res.begin(), w.res.begin() + ns);
+        for (uint32_t i = 0; i < ns; ++i) tb_off.push_back(base + w.tb_off[i + 1]);
+        if (want_tb) tb.insert(tb.end(), w.tb.begin(), w.tb.begin() + (std::ptrdiff_t)w.tb_off[ns]);
+        slot_off.push_back(slots.size());
+    }
+};
+
 // One mapped read (hit.tid >= 0) with its chain of hit.n pairs against contig t of tlen bases -> the record, its CIGAR appended
-// to `cigar`, the counts added to c[C_N].  An overflowed read is unaligned_rec().
+// to `cigar`, the counts added to c[C_N].  An overflowed read is unaligned_rec().  With a probe the read's slots, cells and bits
+// are appended to it, and an overflowed read's matrices within the limits are computed as the device computes them.
 inline Rec align_read(const uint8_t *t, uint32_t tlen, const uint8_t *q, const np2map::Hit &hit, const uint32_t *chain, uint32_t k, const Opts &o,
-                      uint32_t max_cells, Scratch &w, std::vector<uint32_t> &cigar, uint64_t *c) {
+                      uint32_t max_cells, Scratch &w, std::vector<uint32_t> &cigar, uint64_t *c, Probe *probe = nullptr) {
     const Seqs s{t, tlen, q, hit.qlen, hit.rev};
     w.pin.resize(hit.n);
     const uint32_t np = mark_pins(chain, hit.n, k, w.pin.data()), ns = np + 1;
@@ -75,7 +95,7 @@ inline Rec align_read(const uint8_t *t, uint32_t tlen, const uint8_t *q, const n
         if (x.kind <= K_CORE) ++c[C_EQUAL + x.kind];
         c[C_CELLS] += cells;
     }
-    if (over) {
+    if (over && !probe) {
         ++c[C_OVERFLOW];
         return unaligned_rec();
     }
@@ -86,6 +106,11 @@ inline Rec align_read(const uint8_t *t, uint32_t tlen, const uint8_t *q, const n
             const uint32_t rem = x.kind == K_HEAD ? x.q0 : x.kind == K_TAIL ? hit.qlen - x.q0 : 0;
             w.res[i] = dp_slot(s, x, rem, o, w.tb.data() + w.tb_off[i], w.H, w.F);
         }
+    if (probe) probe->take(w, ns);
+    if (over) {
+        ++c[C_OVERFLOW];
+        return unaligned_rec();
+    }
     const ReadIn in{s, chain, w.pin.data(), hit.n, k, w.slots.data(), w.res.data(), w.tb_off.data(), w.tb.data(), 0, ns};
     uint32_t t_start = 0;
     const uint32_t n_raw = raw_ops(in, nullptr, &t_start);

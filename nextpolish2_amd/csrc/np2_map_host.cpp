@@ -535,6 +535,7 @@ struct Mapper {
     std::vector<uint32_t> h_soff, h_ooff, h_b;
     std::vector<np2aln::Rec> h_recs;
     PackSink *pk = nullptr; // np2_sam_from_reads: records and CIGAR words stay on the device (recs and cigar are null then)
+    np2aln::Probe *probe = nullptr; // np2_align_chains_device: the slots, cells and traceback bytes come to the host as well
     // the opt-in outputs (NP2_ALN_MD | NP2_ALN_CS | NP2_ALN_EQX): off while tag_flags is 0; tt takes a batch's texts
     uint32_t tag_flags = 0;
     TagRun tg;
@@ -617,6 +618,34 @@ struct Mapper {
         }
         for (uint32_t i = 0; i < n_reads; ++i) ++(hits[i].tid >= 0 ? stats.mapped : stats.unmapped);
         stats.reads += n_reads;
+    }
+
+    // np2_align_chains_device: the caller's reads, hits and chains (checked: check_chains) take the places the sketcher, k_map_chain
+    // and k_map_chain_export fill for align_group; one group
+    void chains(const uint8_t *bytes, uint64_t n, const uint32_t *ends, uint32_t n_reads, const Hit *hits, const uint32_t *chain,
+                const uint64_t *chain_off, np2aln::Rec *recs, std::vector<uint32_t> *cigar) {
+        using namespace np2;
+        hipStream_t st = s.st;
+        for (uint32_t i = 0; i < n_reads; ++i) recs[i] = np2aln::unaligned_rec(), ++(hits[i].tid >= 0 ? stats.mapped : stats.unmapped);
+        stats.reads += n_reads;
+        const uint64_t total = n_reads ? chain_off[n_reads] : 0;
+        if (total == 0) {
+            if (probe) probe->slot_off.assign((size_t)n_reads + 1, 0);
+            return;
+        }
+        sk.d_seq.ensure(MAP_FRONT + n + 64), sk.d_ends.ensure((size_t)n_reads + 1);
+        d_hits.ensure(n_reads), d_coff.ensure(n_reads), d_chain.ensure(2 * total);
+        h_coff.resize(n_reads);
+        for (uint32_t i = 0; i < n_reads; ++i) h_coff[i] = (uint32_t)chain_off[i];
+        HIPCHK(hipMemsetAsync(sk.d_seq.p, SEP, MAP_FRONT, st));
+        HIPCHK(hipMemcpyAsync(sk.d_seq.p + MAP_FRONT, bytes, n, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(sk.d_ends.p, ends, (size_t)n_reads * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_hits.p, hits, (size_t)n_reads * sizeof(Hit), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_coff.p, h_coff.data(), (size_t)n_reads * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_chain.p, chain, 2 * total * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipStreamSynchronize(st));
+        align_group(0, n_reads, total, recs, cigar, nullptr, nullptr, 0);
+        ++stats.groups;
     }
 
     void group(uint32_t r0, uint32_t r1, Hit *hits, std::vector<uint32_t> *chain, np2aln::Rec *recs, std::vector<uint32_t> *cigar) {
@@ -767,6 +796,15 @@ struct Mapper {
         launch_align_read_cells(st, c);
         HIPCHK(hipMemcpyAsync(h_rcells.data(), d_rcells.p, ((size_t)n_reads + 1) * 8, hipMemcpyDeviceToHost, st));
         astats.classify_ms += s.end();
+        std::vector<uint64_t> p_tboff;
+        if (probe) { // the slots as k_align_classify left them, and where each matrix's bytes begin
+            probe->slots.resize(n_slots), p_tboff.resize((size_t)n_slots + 1);
+            if (n_slots) HIPCHK(hipMemcpyAsync(probe->slots.data(), d_slots.p, (size_t)n_slots * sizeof(np2aln::Slot), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(p_tboff.data(), d_tboff.p, ((size_t)n_slots + 1) * 8, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            probe->slot_off.assign(h_soff.begin(), h_soff.end()), probe->tb_off = p_tboff;
+            if (probe->want_tb) probe->tb.resize(p_tboff[n_slots]);
+        }
         uint32_t n_sub = 0;
         for (uint32_t g0 = 0; g0 < n_reads; ++n_sub) { // sub-groups of whole reads within the traceback budget, one read at the least
             uint32_t g1 = g0 + 1;
@@ -778,6 +816,10 @@ struct Mapper {
             launch_align_dp(st, c, h_soff[g0], h_soff[g1], tb_base);
             astats.dp_ms += s.end();
             if (pk) pk->collect();
+            if (probe && probe->want_tb && tb_bytes) { // (the buffer is the next sub-group's too)
+                HIPCHK(hipMemcpyAsync(probe->tb.data() + tb_base, d_tb.p, tb_bytes, hipMemcpyDeviceToHost, st));
+                HIPCHK(hipStreamSynchronize(st));
+            }
             const uint32_t ng = g1 - g0;
             s.begin();
             launch_align_ops_count(st, c, g0, g1, tb_base);
@@ -824,6 +866,13 @@ struct Mapper {
             g0 = g1;
         }
         if (n_sub > 1) stats.groups += n_sub - 1;
+        if (probe) { // a slot without a matrix has no cell: k_align_dp wrote none
+            probe->res.resize(n_slots);
+            if (n_slots) HIPCHK(hipMemcpyAsync(probe->res.data(), d_res.p, (size_t)n_slots * sizeof(np2aln::Res), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            for (uint32_t i = 0; i < n_slots; ++i)
+                if (p_tboff[i + 1] == p_tboff[i]) probe->res[i] = np2aln::Res{};
+        }
         unsigned long long ctr[np2aln::C_N];
         HIPCHK(hipMemcpyAsync(ctr, d_actr.p, sizeof ctr, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
@@ -2192,6 +2241,169 @@ int np2_align_tags_device(int device, const uint8_t *ref, uint64_t n_ref, const 
     }, np2h::io_set_error);
 }
 
+} // extern "C"
+
+// ---- np2_align_chains_device, np2_align_chains_host: the aligner on the caller's hits and chains ---------------------------------
+namespace {
+static_assert(sizeof(np2_align_slot_t) == sizeof(np2aln::Slot) && sizeof(np2aln::Slot) == 40, "np2_align_slot_t is np2aln::Slot");
+static_assert(sizeof(np2_align_res_t) == sizeof(np2aln::Res) && sizeof(np2aln::Res) == 12, "np2_align_res_t is np2aln::Res");
+
+// What both doors check before any walk and before anything is uploaded (np2_io.h): after it no anchor of a chain can become an
+// access outside its read or its contig.  Returns the reads' separators.
+std::vector<uint64_t> check_chains(const std::vector<uint64_t> &lens, const uint8_t *reads, uint64_t n, uint64_t n_reads, uint32_t k, const np2_map_hit_t *hits,
+                                   const uint32_t *chain, const uint64_t *chain_off, np2_align_rec_t *recs, uint32_t **cigar, uint64_t *cigar_off,
+                                   np2_align_probe_t *probe, const std::string &who) {
+    if (n_reads && !recs) throw Np2Error(NP2_E_ARG, who + ": recs is NULL");
+    if ((cigar == nullptr) != (cigar_off == nullptr)) throw Np2Error(NP2_E_ARG, who + ": cigar and cigar_off go together");
+    if (probe && (probe->want & ~(uint32_t)(NP2_PROBE_SLOTS | NP2_PROBE_TB))) throw Np2Error(NP2_E_ARG, who + ": unknown bits in probe->want");
+    if (n_reads && !hits) throw Np2Error(NP2_E_ARG, who + ": hits is NULL");
+    if (!chain_off) throw Np2Error(NP2_E_ARG, who + ": chain_off is NULL");
+    std::vector<uint64_t> ends = ends_of(reads, n, who.c_str(), "the read stream");
+    if (ends.size() != n_reads)
+        throw Np2Error(NP2_E_ARG, who + ": n_reads is " + std::to_string(n_reads) + ", the stream holds " + std::to_string(ends.size()) + " newlines");
+    if (n > MAP_MAX_STREAM || n_reads > np2map::MAX_SEQ) throw Np2Error(NP2_E_UNSUPPORTED, who + ": a read stream of 2^32 bytes or more");
+    if (chain_off[0] != 0) throw Np2Error(NP2_E_ARG, who + ": chain_off[0] is not 0");
+    uint64_t from = 0;
+    for (uint64_t i = 0; i < n_reads; ++i) {
+        const np2_map_hit_t &h = hits[i];
+        const std::string rd = who + ": read " + std::to_string(i);
+        if (chain_off[i + 1] < chain_off[i]) throw Np2Error(NP2_E_ARG, rd + ": chain_off descends");
+        const uint64_t pairs = chain_off[i + 1] - chain_off[i], qlen = ends[i] - from;
+        from = ends[i] + 1;
+        if (h.tid < 0) {
+            if (pairs) throw Np2Error(NP2_E_ARG, rd + " is unmapped, chain_off gives it " + std::to_string(pairs) + " anchors");
+            continue;
+        }
+        if ((uint64_t)h.tid >= lens.size()) throw Np2Error(NP2_E_ARG, rd + ": tid " + std::to_string(h.tid) + " names no contig of " + std::to_string(lens.size()));
+        if (h.qlen != qlen) throw Np2Error(NP2_E_ARG, rd + ": qlen is " + std::to_string(h.qlen) + ", the read has " + std::to_string(qlen) + " bases");
+        if (h.rev > 1) throw Np2Error(NP2_E_ARG, rd + ": rev is neither 0 nor 1");
+        if (h.n < 1) throw Np2Error(NP2_E_ARG, rd + ": a mapped read with n = 0 anchors");
+        if (pairs != h.n) throw Np2Error(NP2_E_ARG, rd + ": n is " + std::to_string(h.n) + ", chain_off gives it " + std::to_string(pairs) + " anchors");
+        if (chain_off[i + 1] > np2map::MAX_SEQ) throw Np2Error(NP2_E_UNSUPPORTED, who + ": more than 2^31 - 1 anchors in a call");
+        if (!chain) throw Np2Error(NP2_E_ARG, who + ": chain is NULL");
+        const uint64_t tlen = lens[(size_t)h.tid];
+        for (uint64_t a = 0; a < pairs; ++a) {
+            const uint64_t r = chain[2 * (chain_off[i] + a)], q = chain[2 * (chain_off[i] + a) + 1];
+            if (r + 1 < k || r >= tlen)
+                throw Np2Error(NP2_E_ARG, rd + ", anchor " + std::to_string(a) + ": r = " + std::to_string(r) + " is outside " + std::to_string(k - 1) +
+                                              " .. " + std::to_string(tlen) + " - 1 of contig " + std::to_string(h.tid));
+            if (q + 1 < k || q >= qlen)
+                throw Np2Error(NP2_E_ARG, rd + ", anchor " + std::to_string(a) + ": q = " + std::to_string(q) + " is outside " + std::to_string(k - 1) +
+                                              " .. " + std::to_string(qlen) + " - 1 of the read");
+        }
+    }
+    return ends;
+}
+
+template <class T> T *array_out(const std::vector<T> &v) { // a malloc block for the caller (np2_free); never NULL
+    T *p = (T *)malloc(std::max<size_t>(v.size(), 1) * sizeof(T));
+    if (!p) throw Np2Error(NP2_E_NOMEM, "out of memory for the probe");
+    if (!v.empty()) memcpy(p, v.data(), v.size() * sizeof(T));
+    return p;
+}
+
+void clear_probe(np2_align_probe_t *p) {
+    if (p) p->n_slots = 0, p->slot_off = nullptr, p->slots = nullptr, p->res = nullptr, p->tb_off = nullptr, p->tb = nullptr;
+}
+
+void probe_out(const np2aln::Probe &pr, np2_align_probe_t *p) {
+    if (!p) return;
+    std::unique_ptr<void, decltype(&free)> f[5] = {{nullptr, free}, {nullptr, free}, {nullptr, free}, {nullptr, free}, {nullptr, free}};
+    if (p->want & NP2_PROBE_SLOTS) {
+        f[0].reset(array_out(pr.slot_off)), f[1].reset(array_out(pr.slots)), f[2].reset(array_out(pr.res));
+    }
+    if (p->want & NP2_PROBE_TB) f[3].reset(array_out(pr.tb_off)), f[4].reset(array_out(pr.tb));
+    p->n_slots = pr.slots.size();
+    p->slot_off = (uint64_t *)f[0].release(), p->slots = (np2_align_slot_t *)f[1].release(), p->res = (np2_align_res_t *)f[2].release();
+    p->tb_off = (uint64_t *)f[3].release(), p->tb = (uint8_t *)f[4].release();
+}
+
+void cigars_out(const np2aln::Rec *rout, uint64_t n_reads, const std::vector<uint32_t> &cg, uint32_t **cigar, uint64_t *cigar_off) {
+    if (!cigar) return;
+    cigar_off[0] = 0;
+    for (uint64_t i = 0; i < n_reads; ++i) cigar_off[i + 1] = cigar_off[i] + rout[i].n_cigar;
+    *cigar = chain_out(cg);
+}
+} // namespace
+
+extern "C" {
+int np2_align_chains_device(const np2_map_index_t *ix, const uint8_t *reads, uint64_t n, uint64_t n_reads, uint32_t k, const np2_map_hit_t *hits,
+                            const uint32_t *chain, const uint64_t *chain_off, const np2_align_opts_t *align_opts, np2_align_rec_t *recs, uint32_t **cigar,
+                            uint64_t *cigar_off, np2_align_probe_t *probe) {
+    return np2h::abi_guard([&] {
+        const std::string who = "np2_align_chains_device";
+        if (cigar) *cigar = nullptr;
+        clear_probe(probe);
+        const np2aln::Opts ao = checked_align(align_opts, who.c_str());
+        if (!ix) throw Np2Error(NP2_E_ARG, who + ": the index is NULL");
+        if (k != ix->k) throw Np2Error(NP2_E_ARG, who + ": the index was built with k = " + std::to_string(ix->k) + ", the call says k = " + std::to_string(k));
+        const std::vector<uint64_t> ends = check_chains(ix->lens, reads, n, n_reads, k, hits, chain, chain_off, recs, cigar, cigar_off, probe, who);
+        np2map::Opts o{};
+        o.k = ix->k, o.w = ix->w;
+        Mapper m(*ix, o);
+        m.align_with(ao);
+        np2aln::Probe pr;
+        if (probe) pr.want_tb = (probe->want & NP2_PROBE_TB) != 0, m.probe = &pr;
+        const std::vector<uint32_t> local(ends.begin(), ends.end());
+        std::vector<uint32_t> cg;
+        np2aln::Rec *rout = reinterpret_cast<np2aln::Rec *>(recs);
+        m.chains(reads, n, local.data(), (uint32_t)n_reads, reinterpret_cast<const Hit *>(hits), chain, chain_off, rout, &cg);
+        cigars_out(rout, n_reads, cg, cigar, cigar_off);
+        probe_out(pr, probe);
+        return NP2_OK;
+    }, np2h::io_set_error);
+}
+
+int np2_align_chains_host(const uint8_t *asm_stream, uint64_t n_asm, const uint8_t *reads, uint64_t n, uint64_t n_reads, uint32_t k,
+                          const np2_map_hit_t *hits, const uint32_t *chain, const uint64_t *chain_off, const np2_align_opts_t *align_opts,
+                          np2_align_rec_t *recs, uint32_t **cigar, uint64_t *cigar_off, np2_align_probe_t *probe) {
+    return np2h::abi_guard([&] {
+        const std::string who = "np2_align_chains_host";
+        if (cigar) *cigar = nullptr;
+        clear_probe(probe);
+        np2aln::Opts ao = checked_align(align_opts, who.c_str());
+        if (k < np2map::K_MIN || k > np2map::K_MAX) throw Np2Error(NP2_E_ARG, who + ": k = " + std::to_string(k) + " is outside 11 .. 28");
+        const std::vector<uint64_t> a_ends = ends_of(asm_stream, n_asm, who.c_str(), "the assembly stream");
+        std::vector<uint64_t> lens;
+        for (size_t i = 0; i < a_ends.size(); ++i) lens.push_back(a_ends[i] - (i ? a_ends[i - 1] + 1 : 0));
+        const std::vector<uint64_t> ends = check_chains(lens, reads, n, n_reads, k, hits, chain, chain_off, recs, cigar, cigar_off, probe, who);
+        const Hooks hooks;
+        if (ao.max_cells > hooks.align_cells) ao.max_cells = hooks.align_cells;
+        np2_map_stats_t &st = tl_stats;
+        st = np2_map_stats_t{};
+        tl_astats = np2_align_stats_t{};
+        np2aln::Probe pr;
+        if (probe) pr.want_tb = (probe->want & NP2_PROBE_TB) != 0;
+        np2aln::Scratch w;
+        std::vector<uint32_t> cg;
+        uint64_t ctr[np2aln::C_N] = {};
+        np2aln::Rec *rout = reinterpret_cast<np2aln::Rec *>(recs);
+        uint64_t from = 0;
+        for (uint64_t i = 0; i < n_reads; ++i) {
+            const Hit &h = reinterpret_cast<const Hit *>(hits)[i];
+            ++(h.tid >= 0 ? st.mapped : st.unmapped);
+            rout[i] = np2aln::unaligned_rec();
+            if (h.tid >= 0) {
+                const uint64_t t_at = h.tid ? a_ends[(size_t)h.tid - 1] + 1 : 0;
+                rout[i] = np2aln::align_read(asm_stream + t_at, (uint32_t)lens[(size_t)h.tid], reads + from, h, chain + 2 * chain_off[i], k, ao, ao.max_cells, w,
+                                             cg, ctr, probe ? &pr : nullptr);
+            } else {
+                pr.unmapped();
+            }
+            from = ends[i] + 1;
+        }
+        st.reads = n_reads;
+        unsigned long long c[np2aln::C_N];
+        for (int f = 0; f < np2aln::C_N; ++f) c[f] = ctr[f];
+        add_counts(tl_astats, c);
+        cigars_out(rout, n_reads, cg, cigar, cigar_off);
+        probe_out(pr, probe);
+        return NP2_OK;
+    }, np2h::io_set_error);
+}
+} // extern "C"
+
+extern "C" {
 int np2_map_align_last_tag_stats(np2_align_tag_stats_t *stats) {
     if (!stats) return np2h::io_set_error(NP2_E_ARG, "np2_map_align_last_tag_stats: stats is NULL");
     *stats = tl_tstats;

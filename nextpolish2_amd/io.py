@@ -111,6 +111,18 @@ assert C.sizeof(np2_align_opts_t) == 32 and C.sizeof(np2_align_stats_t) == 96 an
 ALN_QUAL, ALN_MD, ALN_CS, ALN_EQX = 1, 2, 4, 8  # NP2_ALN_*
 ALIGN_DEFAULTS = dict(match=1, mismatch=4, gap_open=6, gap_ext=2, band=32, end_bonus=5, ext_max=2048, max_cells=1 << 23)
 # np2_align_rec_t
+# np2_align_slot_t, np2_align_res_t and np2_align_probe_t (np2_align_chains_*)
+ALIGN_SLOT_DTYPE = np.dtype([(f, "<u4") for f in ("t0", "q0", "tl", "ql", "pre", "suf", "kind", "W")] + [("lo", "<i4"), ("over", "<u4")])
+ALIGN_RES_DTYPE = np.dtype([("score", "<i4"), ("ei", "<u4"), ("ej", "<u4")])
+PROBE_SLOTS, PROBE_TB = 1, 2
+
+
+class np2_align_probe_t(C.Structure):
+    _fields_ = [("want", C.c_uint32), ("pad", C.c_uint32), ("n_slots", C.c_uint64), ("slot_off", C.c_void_p), ("slots", C.c_void_p),
+                ("res", C.c_void_p), ("tb_off", C.c_void_p), ("tb", C.c_void_p)]
+
+
+assert ALIGN_SLOT_DTYPE.itemsize == 40 and ALIGN_RES_DTYPE.itemsize == 12 and C.sizeof(np2_align_probe_t) == 56
 ALIGN_REC_DTYPE = np.dtype([("tid", "<i4")] + [(f, "<u4") for f in ("flag", "pos", "end", "mapq", "n_cigar", "nm")] + [("as", "<i4")])
 assert ALIGN_REC_DTYPE.itemsize == 32
 
@@ -399,6 +411,9 @@ def _bind_map(L):
     L.np2_align_tags_device.argtypes = [C.c_int, vp, u64, vp, u64, u64, vp, vp, vp, vp, u32] + [C.POINTER(vp), vp] * 3
     L.np2_align_tags_host.argtypes = [vp, u64, vp, u64, u64, vp, vp, vp, vp, u32] + [C.POINTER(vp), vp] * 3
     L.np2_map_align_last_tag_stats.argtypes = [C.POINTER(np2_align_tag_stats_t)]
+    pp = C.POINTER(np2_align_probe_t)
+    L.np2_align_chains_device.argtypes = [vp, vp, u64, u64, u32, vp, vp, vp, ao, vp, C.POINTER(vp), vp, pp]
+    L.np2_align_chains_host.argtypes = [vp, u64, vp, u64, u64, u32, vp, vp, vp, ao, vp, C.POINTER(vp), vp, pp]
     so, pvp = C.POINTER(np2_sam_opts_t), C.POINTER(vp)
     L.np2_sam_from_reads.argtypes = [vp, vp, C.POINTER(C.c_char_p), C.c_int, mo, ao, so, C.c_uint32, pvp]
     L.np2_sam_from_read_bytes.argtypes = [vp, vp, vp, u64, u64, C.c_char_p, mo, ao, so, C.c_uint32, pvp]
@@ -1806,6 +1821,83 @@ def align_tags_device(ref, reads, t_off, q_off, cigars, md=True, cs=True, eqx=Tr
     """np2_align_tags_device: align_tags_host's records through the tag kernels"""
     L = _bind()
     return _align_tags(L, lambda *a: L.np2_align_tags_device(device, *a), ref, reads, t_off, q_off, cigars, md, cs, eqx)
+
+
+def _chains_args(reads, hits, chains):
+    """reads, hits (a MAP_HIT_DTYPE array, or a list of dicts with None for an unmapped read) and chains (a list of (n, 2)
+    arrays, or the pair (chain, chain_off)) -> what np2_align_chains_* take"""
+    s, n = _stream_of(reads)
+    if not isinstance(hits, np.ndarray):
+        h = np.zeros(len(hits), MAP_HIT_DTYPE)
+        ends = np.flatnonzero(s == 10)
+        starts = np.concatenate([[0], ends[:-1] + 1]) if len(ends) else ends
+        for i, x in enumerate(hits):
+            if x is None:
+                h[i]["tid"], h[i]["qlen"] = -1, int(ends[i] - starts[i]) if i < len(ends) else 0
+                continue
+            for f in MAP_HIT_DTYPE.names:
+                if f in x:
+                    h[i][f] = x[f]
+        hits = h
+    hits = np.ascontiguousarray(hits, MAP_HIT_DTYPE)
+    if isinstance(chains, tuple):
+        chain, off = np.ascontiguousarray(chains[0], np.uint32).reshape(-1), np.ascontiguousarray(chains[1], np.uint64)
+    else:
+        parts = [np.asarray(c, np.uint32).reshape(-1, 2) for c in chains]
+        off = np.zeros(len(parts) + 1, np.uint64)
+        off[1:] = np.cumsum([len(c) for c in parts])
+        chain = np.ascontiguousarray(np.concatenate(parts).reshape(-1) if parts else np.zeros(0), np.uint32)
+    return s, n, hits, chain, off
+
+
+def _chains_result(L, call, s, n, hits, chain, off, k, ao, probe):
+    from .api import _Raw
+    recs = np.zeros(n, ALIGN_REC_DTYPE)
+    pc, coff = C.c_void_p(), np.zeros(n + 1, np.uint64)
+    want = 0 if not probe else PROBE_SLOTS | PROBE_TB if probe is True else int(probe)
+    pr = np2_align_probe_t(want=want)
+    _io_check(call(s.ctypes.data if len(s) else None, len(s), n, k, hits.ctypes.data if len(hits) else None, chain.ctypes.data if len(chain) else None,
+                   off.ctypes.data, C.byref(ao), recs.ctypes.data if n else None, C.byref(pc), coff.ctypes.data, C.byref(pr) if want else None))
+    owned = [pc.value, pr.slot_off, pr.slots, pr.res, pr.tb_off, pr.tb]
+    try:
+        take = lambda p, m, dt: np.asarray(_Raw(p, m, dt)).copy() if p and m else np.zeros(0, dt)
+        cigar = take(pc.value, int(coff[n]), "<u4")
+        out = None
+        if want:
+            out, ns = {}, int(pr.n_slots)
+            if want & PROBE_SLOTS:
+                out["slot_off"] = take(pr.slot_off, n + 1, "<u8")
+                out["slots"] = take(pr.slots, ns * 40, "|u1").view(ALIGN_SLOT_DTYPE)
+                out["res"] = take(pr.res, ns * 12, "|u1").view(ALIGN_RES_DTYPE)
+            if want & PROBE_TB:
+                out["tb_off"] = take(pr.tb_off, ns + 1, "<u8")
+                out["tb"] = take(pr.tb, int(out["tb_off"][ns]), "|u1")
+    finally:
+        for p in owned:
+            if p:
+                L.np2_free(C.c_void_p(p))
+    return (recs, cigar, coff, out) if want else (recs, cigar, coff)
+
+
+def align_chains_device(index, reads, hits, chains, probe=False, **kw):
+    """np2_align_chains_device: the aligner's kernels on caller-built hits and chains against the index's assembly; nothing is
+    sketched, seeded or chained -> (recs, cigar, cigar_off) and, with probe (True, or a sum of PROBE_SLOTS and PROBE_TB), a dict of
+    slot_off, slots (ALIGN_SLOT_DTYPE), res (ALIGN_RES_DTYPE), tb_off and tb.  hits, chains: see _chains_args.  Options:
+    ALIGN_DEFAULTS, and k (the index's)."""
+    L = index._L
+    k = int(kw.pop("k", index.k))
+    s, n, hits, chain, off = _chains_args(reads, hits, chains)
+    ao = align_opts(**kw)
+    return _chains_result(L, lambda *a: L.np2_align_chains_device(index._h, *a), s, n, hits, chain, off, k, ao, probe)
+
+
+def align_chains_host(asm, reads, hits, chains, k=19, probe=False, **kw):
+    """np2_align_chains_host (no device): align_chains_device through the host aligner, against an assembly in memory"""
+    L = _bind()
+    a, _ = _stream_of(asm)
+    s, n, hits, chain, off = _chains_args(reads, hits, chains)
+    ao = align_opts(**kw)
+    return _chains_result(L, lambda *x: L.np2_align_chains_host(a.ctypes.data if len(a) else None, len(a), *x), s, n, hits, chain, off, int(k), ao, probe)
 
 
 def _align_result(L, call, s, n):

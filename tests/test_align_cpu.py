@@ -238,20 +238,28 @@ def core_program(tmp_path_factory):
 
 
 def test_banded_scores_equal_a_full_matrix(core_program, tmp_path):
-    """The C++ recurrence (classify and dp_slot of the core text, through the stand-alone program's `core` mode; the host
-    library and the kernels run the same text) against a plain full-matrix affine DP written here, not against the model: every
-    core of the cases whose shorter side is <= band, where the band holds the whole matrix, and seeded random pairs of length
-    1 .. 40 under a band of 40."""
-    o = am.opts()
+    """The C++ recurrence (classify and dp_slot of the core text, through the stand-alone program's `core` mode, which is what
+    the host library runs) against a plain full-matrix affine DP written here, not against the model: every core of the cases
+    whose shorter side is <= band, where the band holds the whole matrix, and seeded random pairs of length 1 .. 40 under a band of
+    40; under the default scores and under the extremes of tests/alignchain_cases.py.
+
+    The kernels share classify, gap_of, h_of, choose_end and the walk with this text, but not the matrix loop: k_align_dp has its
+    own (a prefix maximum over the lanes for E, carries between the blocks of 64 lanes, the previous row in LDS).  It is held
+    to dp_slot cell by cell in tests/test_gpu_map_alignchain.py."""
+    import alignchain_cases as cc
     rng = np.random.default_rng(5)
     letters = b"ACGTN"
     pairs = [tuple(bytes(letters[i] for i in rng.integers(0, 4 if rng.random() < 0.9 else 5, int(rng.integers(1, 41)))) for _ in range(2))
              for _ in range(400)]
     segs = segments_of_cases(("band_65", "core_rows_1_2", "lower_case", "unmapped_between", "pure_gaps_snv", "n_bases", "cells_overflow"))
     n_cores = {}
-    for label, todo, band in (("random", pairs, 40), ("cases", segs, 32)):
+    runs = [("random", pairs, 40, None), ("cases", segs, 32, None)]
+    runs += [(sc, pairs, 40, cc.scoring(sc)) for sc in cc.OPTSETS] + [(sc + "/cases", segs, 32, cc.scoring(sc)) for sc in cc.OPTSETS]
+    for label, todo, band, scores in runs:
+        o = am.opts(**(scores or {}))
         (tmp_path / "pairs").write_bytes(b"".join(t + b" " + q + b"\n" for t, q in todo))
-        r = subprocess.run([core_program, "core", str(tmp_path / "pairs"), str(band)], capture_output=True, text=True, timeout=120)
+        r = subprocess.run([core_program, "core", str(tmp_path / "pairs"), str(band)] + [str(v) for v in (scores or {}).values()],
+                           capture_output=True, text=True, timeout=120)
         assert r.returncode == 0 and r.stderr == "", r.stderr[-3000:]
         lines = r.stdout.splitlines()
         assert len(lines) == len(todo)
@@ -270,6 +278,7 @@ def test_banded_scores_equal_a_full_matrix(core_program, tmp_path):
             n_cores[label] += 1
             assert score == full_affine(T[pre:len(T) - suf], Q[pre:len(Q) - suf], o), (t, q)
     assert n_cores["random"] > 350 and n_cores["cases"] >= 8
+    assert all(n_cores[sc] == n_cores["random"] and n_cores[sc + "/cases"] == n_cores["cases"] for sc in cc.OPTSETS)
 
 
 def test_planted_truths_as_literal_cigars():

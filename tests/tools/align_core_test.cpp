@@ -6,10 +6,15 @@
 //   align_core_test finish REFERENCE READ t_start RAW_CIGAR
 // runs the rule's last pass (ends, left-alignment, pos, NM, AS with the default scores) on a hand-made alignment of the whole
 // read to the reference from t_start on and prints "pos end nm as CIGAR".
-//   align_core_test core PAIRS_FILE band
+//   align_core_test core PAIRS_FILE band [match mismatch gap_open gap_ext]
 // treats each line "REFERENCE READ" of the file as the bases between two pins: the trim and the class (np2aln::classify) and,
-// for a core, the banded matrix (dp_slot) with the default scores; prints "kind over pre suf tl ql score" per line (tl, ql: the
-// core's sides; score 0 without a matrix).
+// for a core, the banded matrix (dp_slot) with the default scores or the given ones; prints "kind over pre suf tl ql score" per
+// line (tl, ql: the core's sides; score 0 without a matrix).
+//   align_core_test chains CASE_FILE
+// runs align_read on caller-built hits and chains, as np2_align_chains_host does behind its checks.  The file: a line "k match
+// mismatch gap_open gap_ext band end_bonus ext_max max_cells", a line with the number of contigs, one contig per line, a line
+// with the number of reads, then per read "SEQ tid rev mapq n r q r q ..." (tid -1 and n 0: unmapped).  Prints what the first
+// form prints.
 // With a last argument "sam" the first form prints the SAM text instead (reads named r0, r1, ..., sequences 1, 2, ...).
 #include <algorithm>
 #include <cstddef>
@@ -58,8 +63,12 @@ static int finish(char **argv) {
     return 0;
 }
 
-static int core(char **argv) {
+static int core(int argc, char **argv) {
     np2aln::Opts o{1, 4, 6, 2, (uint32_t)strtoul(argv[3], nullptr, 10), 5, 2048, 1u << 23};
+    if (argc == 8) {
+        uint32_t *f[4] = {&o.match, &o.mismatch, &o.gap_open, &o.gap_ext};
+        for (int i = 0; i < 4; ++i) *f[i] = (uint32_t)strtoul(argv[4 + i], nullptr, 10);
+    }
     if (const char *bad = np2aln::check_opts(o)) {
         fprintf(stderr, "argument: %s\n", bad);
         return 3;
@@ -90,9 +99,77 @@ static int core(char **argv) {
     return 0;
 }
 
+static void print_rec(std::string &out, const np2aln::Rec &rec, const std::vector<uint32_t> &cigar) {
+    char line[160];
+    snprintf(line, sizeof line, "%d %u %u %u %u %u %u %d ", rec.tid, rec.flag, rec.pos, rec.end, rec.mapq, rec.n_cigar, rec.nm, rec.as);
+    out += line + cigar_text(cigar.data(), rec.n_cigar) + "\n";
+}
+
+static int chains(char **argv) {
+    std::vector<uint8_t> text;
+    if (!slurp(argv[2], text)) {
+        fprintf(stderr, "cannot read the case\n");
+        return 2;
+    }
+    text.push_back(0);
+    const char *p = (const char *)text.data();
+    const auto number = [&]() { // the next whole number (a leading '-' allowed)
+        char *e;
+        const long long v = strtoll(p, &e, 10);
+        if (e == p) {
+            fprintf(stderr, "a number is missing\n");
+            exit(2);
+        }
+        p = e;
+        return v;
+    };
+    const auto word = [&]() {
+        while (*p == ' ' || *p == '\n') ++p;
+        const char *b = p;
+        while (*p && *p != ' ' && *p != '\n') ++p;
+        return std::string(b, p);
+    };
+    const uint32_t k = (uint32_t)number();
+    np2aln::Opts ao{};
+    uint32_t *afields[8] = {&ao.match, &ao.mismatch, &ao.gap_open, &ao.gap_ext, &ao.band, &ao.end_bonus, &ao.ext_max, &ao.max_cells};
+    for (int i = 0; i < 8; ++i) *afields[i] = (uint32_t)number();
+    if (const char *bad = np2aln::check_opts(ao)) {
+        fprintf(stderr, "argument: %s\n", bad);
+        return 3;
+    }
+    std::vector<std::string> contigs((size_t)number());
+    for (std::string &c : contigs) c = word();
+    const size_t n_reads = (size_t)number();
+    np2aln::Scratch w;
+    uint64_t c[np2aln::C_N] = {};
+    std::string out;
+    for (size_t i = 0; i < n_reads; ++i) {
+        const std::string seq = word();
+        np2map::Hit h{};
+        h.tid = (int32_t)number(), h.rev = (uint32_t)number(), h.mapq = (uint32_t)number(), h.n = (uint32_t)number();
+        h.qlen = (uint32_t)seq.size();
+        std::vector<uint32_t> chain(2 * (size_t)h.n), cigar;
+        for (uint32_t &x : chain) x = (uint32_t)number();
+        np2aln::Rec rec = np2aln::unaligned_rec();
+        if (h.tid >= 0) {
+            if ((size_t)h.tid >= contigs.size() || h.n < 1) return 2;
+            const std::string &t = contigs[(size_t)h.tid];
+            for (uint32_t a = 0; a < h.n; ++a)
+                if (chain[2 * a] + 1 < k || chain[2 * a] >= t.size() || chain[2 * a + 1] + 1 < k || chain[2 * a + 1] >= seq.size()) return 2;
+            rec = np2aln::align_read((const uint8_t *)t.data(), (uint32_t)t.size(), (const uint8_t *)seq.data(), h, chain.data(), k, ao, ao.max_cells, w,
+                                     cigar, c);
+        }
+        print_rec(out, rec, cigar);
+    }
+    for (int i = 0; i < np2aln::C_N; ++i) printf("%llu%c", (unsigned long long)c[i], i + 1 < np2aln::C_N ? ' ' : '\n');
+    fputs(out.c_str(), stdout);
+    return 0;
+}
+
 int main(int argc, char **argv) {
     if (argc == 6 && !strcmp(argv[1], "finish")) return finish(argv);
-    if (argc == 4 && !strcmp(argv[1], "core")) return core(argv);
+    if ((argc == 4 || argc == 8) && !strcmp(argv[1], "core")) return core(argc, argv);
+    if (argc == 3 && !strcmp(argv[1], "chains")) return chains(argv);
     const bool sam = argc == 20 && !strcmp(argv[19], "sam");
     if (argc != 19 && !sam) {
         fprintf(stderr, "usage: align_core_test ASM_STREAM READ_STREAM (8 mapping options) (8 alignment options)\n");
@@ -152,9 +229,7 @@ int main(int argc, char **argv) {
             continue;
         }
         from = r_ends[i] + 1;
-        char line[160];
-        snprintf(line, sizeof line, "%d %u %u %u %u %u %u %d ", rec.tid, rec.flag, rec.pos, rec.end, rec.mapq, rec.n_cigar, rec.nm, rec.as);
-        out += line + cigar_text(cigar.data(), rec.n_cigar) + "\n";
+        print_rec(out, rec, cigar);
     }
     if (!sam)
         for (int i = 0; i < np2aln::C_N; ++i) printf("%llu%c", (unsigned long long)c[i], i + 1 < np2aln::C_N ? ' ' : '\n');
