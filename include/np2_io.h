@@ -119,6 +119,89 @@ int np2_depth_from_records(np2_ctx_t *ctx, uint32_t L, const np2_bamrec_t *recs,
 int np2_depth_from_bam(np2_ctx_t *ctx, np2_bam_t *bam, const char *name, uint32_t L, const np2_depth_opts_t *opts,
                        uint32_t **starts, uint32_t **ends, uint32_t *n_runs, uint32_t *depth /* [L] or NULL */,
                        np2_depth_stats_t *stats /* or NULL */);
+/* ---- read-supported variants of a contig: pileup counts, left-aligned indel alleles, calls ------------------------------
+ * THE RULE IS THIS PROJECT'S OWN: counts and integer thresholds, no quality model.  Equality with DeepVariant, bcftools or any
+ * other caller is not claimed.  A site where nearly every read disagrees with the assembly (a homozygous call) is a potential
+ * error of the assembly.
+ * Inputs: ref[L], case-insensitive, A C G T = codes 0..3, anything else N; records, CIGAR words and 4-bit SEQ as
+ * np2_contig_from_records takes them (SEQ nibbles 1 2 4 8 = A C G T, every other nibble N).
+ * Admission: a record is counted iff the depth report's rule holds under these options ((flag & exclude_flags) == 0, mapq >=
+ *   min_mapq, n_cigar > 0, read_len > 0, not aligned / read_len < min_aligned_fra), 0 <= pos < L, it has no N operation
+ *   (else stats.records_skipped) and l_seq equals the sum of its M I S = X lengths (else — SEQ * too — stats.records_no_seq).
+ * cov[p]: counted records with pos <= p < min(pos + span, L), span as in the depth report.
+ * alt[4 p + b], b = A C G T: counted records with an M/=/X column at p < L whose read base is b, where ref[p] is A C G T and
+ *   differs from b.  A read N adds nothing; a reference N has no counts and no SNV.
+ * Indel event: an I or D operation of 1 <= n <= max_indel (<= 28) bases whose neighbours in the CIGAR are both M, = or X
+ *   (leading and trailing indels, indels next to a clip and adjacent I/D pairs are ignored), with a preceding run — the
+ *   consecutive M/=/X operations before it — of m >= 1 columns.  a = the reference position of the column before it, qa = that
+ *   column's query index.  D: a + n < L.  I: a + 1 < L and every inserted base is A C G T.
+ * Left shift: by the largest t <= m - 1 whose steps j = 0 .. t-1 all satisfy — I: read[qa-j+n] == read[qa-j], both A C G T;
+ *   D: ref[a-j] == ref[a-j+n] and read[qa-j] == ref[a-j], all A C G T.  These steps change no column's cov or alt.
+ * Allele key: (a' = a - t, kind DEL < INS, n, bases): I: read[qa-t+1 .. qa-t+n], 2 bits a base, the first base highest (numeric
+ *   order = lexicographic); D: 0.  An allele's count is the number of its events.
+ * Calls, all tests in integers (c * 1000 >= pm * d):
+ *   SNV at p: d = cov[p], the alt base of the greatest count (ties A < C < G < T), c its count.
+ *   Indel per (a', kind): the allele of the greatest count (ties: the smaller n, then the smaller bases),
+ *     d = min(cov[a'], cov[a'+1]).  A deletion and an insertion at one anchor are judged separately; the anchor's base may be N.
+ *   Called iff d >= min_depth, c >= min_alt and c * 1000 >= het_pm * d; hom iff c * 1000 >= hom_pm * d, else het.
+ *   het_pm = hom_pm: homozygous calls only.  Ascending by pos (the SNV's p, the indel's anchor); at one pos SNV, DEL, INS.
+ * Outputs: *calls (release with np2_free; NULL when there is none), *n_calls; cov (or NULL): the caller's L words; alt (or
+ *   NULL): the caller's 4 L words.
+ * NP2_E_ARG before anything is launched, the context stays usable: hom_pm > 1000, het_pm > hom_pm, max_indel outside 1..28,
+ * min_alt 0 (a call needs a read), min_aligned_fra outside [0, 1], a NULL argument, a record whose SEQ or CIGAR lies outside
+ * its buffer (np2_varcall_host, which is given the sizes; np2_varcall_from_records takes the buffers to end where the last
+ * record's data ends), a contig name the BAM header lacks.  L above 4294901760 is NP2_E_UNSUPPORTED. */
+typedef struct np2_varcall_opts {
+    double min_aligned_fra; /* --min_fra 0.0 */
+    uint32_t min_depth;     /* -d 8 */
+    uint32_t min_alt;       /* --min_alt 3 */
+    uint32_t hom_pm;        /* --hom 0.8 -> 800 */
+    uint32_t het_pm;        /* --het_frac 0.25 -> 250; = hom_pm: homozygous calls only */
+    uint32_t max_indel;     /* --max_indel 28 */
+    uint16_t exclude_flags; /* 0xF04: unmapped, secondary, QC fail, duplicate, supplementary */
+    uint8_t min_mapq;       /* -q 5 */
+} np2_varcall_opts_t;
+typedef struct np2_varcall {
+    uint32_t pos;     /* 0-based: the SNV's position, the indel's anchor (the base before it) */
+    uint32_t depth;   /* d */
+    uint32_t count;   /* c */
+    uint32_t pad0;
+    uint64_t bases;   /* INS: the inserted bases, 2 bits each, the first base highest; else 0 */
+    uint8_t kind;     /* 0 SNV, 1 DEL, 2 INS */
+    uint8_t gt;       /* 1 het, 2 hom */
+    uint8_t len;      /* SNV 1; indel: n */
+    uint8_t alt_code; /* SNV: the called base, A C G T = 0..3; else 0 */
+    uint32_t pad1;
+} np2_varcall_t;
+typedef struct np2_varcall_stats {
+    uint64_t records_seen;    /* handed in or fetched */
+    uint64_t records_counted;
+    uint64_t records_no_seq;  /* SEQ * or l_seq != the CIGAR's query length */
+    uint64_t records_skipped; /* with an N operation */
+    uint64_t events;          /* indel events of counted records */
+    uint64_t alleles;         /* distinct keys among them */
+    uint64_t callable;        /* positions with cov >= min_depth and an A C G T reference base */
+    uint64_t calls[6];        /* [kind * 2 + gt - 1]: SNV het, SNV hom, DEL het, DEL hom, INS het, INS hom */
+    float kernel_ms;          /* the kernels and sorts together (HIP events): the sum of stage_ms */
+    float stage_ms[6];        /* records, coverage scan, key sorts, alleles, calls counted, calls written */
+    uint32_t pad;
+} np2_varcall_stats_t;
+/* ref, recs, cigar, seq4 in host memory */
+int np2_varcall_from_records(np2_ctx_t *ctx, const uint8_t *ref, uint32_t L, const np2_bamrec_t *recs, uint32_t n_recs,
+                             const uint32_t *cigar, const uint8_t *seq4, const np2_varcall_opts_t *opts, np2_varcall_t **calls,
+                             uint32_t *n_calls, uint32_t *cov /* [L] or NULL */, uint32_t *alt /* [4 L] or NULL */,
+                             np2_varcall_stats_t *stats /* or NULL */);
+/* the same over the records of contig `name` of an indexed BAM, fetched the way np2_contig_from_bam fetches them: records, CIGAR
+ * words and SEQ stay where the reader left them (in HBM already on the device path; SEQ streamed there by the host pool) */
+int np2_varcall_from_bam(np2_ctx_t *ctx, np2_bam_t *bam, const char *name, const uint8_t *ref, uint32_t L,
+                         const np2_varcall_opts_t *opts, np2_varcall_t **calls, uint32_t *n_calls, uint32_t *cov /* [L] or NULL */,
+                         uint32_t *alt /* [4 L] or NULL */, np2_varcall_stats_t *stats /* or NULL */);
+/* the host twin: the same rule on one CPU thread, no device and no context (kernel_ms stays 0).  n_cigar_words and seq_bytes
+ * are the sizes of cigar and seq4: a record that reaches beyond either is NP2_E_ARG */
+int np2_varcall_host(const uint8_t *ref, uint32_t L, const np2_bamrec_t *recs, uint32_t n_recs, const uint32_t *cigar,
+                     uint64_t n_cigar_words, const uint8_t *seq4, uint64_t seq_bytes, const np2_varcall_opts_t *opts,
+                     np2_varcall_t **calls, uint32_t *n_calls, uint32_t *cov /* [L] or NULL */, uint32_t *alt /* [4 L] or NULL */,
+                     np2_varcall_stats_t *stats /* or NULL */);
 /* ---- one reference interval of a contig straight from the BAM (multi-GPU: every rank parses only its part) -----------
  * begin: fetch the records overlapping [own_lo - halo, own_hi + halo) through the .bai linear index, admit + columnarise
  *        them; returns the BGZF virtual offsets of the pushed records that START in [own_lo, own_hi) (file order).

@@ -42,6 +42,7 @@ IO_ABI_SYMBOLS = [
     "np2_kcount_files", "np2_kcount_bytes", "np2_kcount_files_to_dumps", "np2_ctx_create_from_reads", "np2_kcount_last_stats",
     "np2_seqfile_stream", "np2_bin_files", "np2_seqfile_reads",
     "np2_depth_from_records", "np2_depth_from_bam",
+    "np2_varcall_from_records", "np2_varcall_from_bam", "np2_varcall_host",
     "np2_srqc_bytes", "np2_srqc_files", "np2_srqc_last_stats", "np2_srqc_last_kernel_ms", "np2_kcount_files_qc",
     "np2_kcount_files_to_dumps_qc", "np2_ctx_create_from_reads_qc", "np2_seqfile_stream_qual",
     "np2_sradapt_bytes", "np2_sradapt_files", "np2_sradapt_last_stats", "np2_sradapt_last_kernel_ms", "np2_kcount_files_ad",
@@ -81,6 +82,25 @@ class np2_depth_stats_t(C.Structure):
 
 
 assert C.sizeof(np2_depth_opts_t) == 24 and C.sizeof(np2_depth_stats_t) == 56
+
+
+class np2_varcall_opts_t(C.Structure):
+    _fields_ = [("min_aligned_fra", C.c_double), ("min_depth", C.c_uint32), ("min_alt", C.c_uint32), ("hom_pm", C.c_uint32),
+                ("het_pm", C.c_uint32), ("max_indel", C.c_uint32), ("exclude_flags", C.c_uint16), ("min_mapq", C.c_uint8)]
+
+
+class np2_varcall_stats_t(C.Structure):
+    _fields_ = [("records_seen", C.c_uint64), ("records_counted", C.c_uint64), ("records_no_seq", C.c_uint64),
+                ("records_skipped", C.c_uint64), ("events", C.c_uint64), ("alleles", C.c_uint64), ("callable", C.c_uint64),
+                ("calls", C.c_uint64 * 6), ("kernel_ms", C.c_float), ("stage_ms", C.c_float * 6), ("pad", C.c_uint32)]
+
+
+VARCALL_DTYPE = np.dtype([("pos", "<u4"), ("depth", "<u4"), ("count", "<u4"), ("pad0", "<u4"), ("bases", "<u8"), ("kind", "u1"),
+                          ("gt", "u1"), ("len", "u1"), ("alt_code", "u1"), ("pad1", "<u4")])  # np2_varcall_t
+VARCALL_KINDS = ("SNV", "DEL", "INS")
+VARCALL_STAGES = ("records", "scan", "sorts", "alleles", "count", "emit")  # np2_varcall_stats_t.stage_ms
+VARCALL_CALLS = ("snv_het", "snv_hom", "del_het", "del_hom", "ins_het", "ins_hom")  # np2_varcall_stats_t.calls
+assert C.sizeof(np2_varcall_opts_t) == 32 and C.sizeof(np2_varcall_stats_t) == 136 and VARCALL_DTYPE.itemsize == 32
 
 
 class np2_rep_opts_t(C.Structure):
@@ -172,6 +192,10 @@ def _lib_locked():
                                              C.POINTER(u32), vp, C.POINTER(np2_depth_stats_t)]
         L.np2_depth_from_bam.argtypes = [vp, vp, C.c_char_p, u32, C.POINTER(np2_depth_opts_t), C.POINTER(vp), C.POINTER(vp),
                                          C.POINTER(u32), vp, C.POINTER(np2_depth_stats_t)]
+        vc_out = [C.POINTER(np2_varcall_opts_t), C.POINTER(vp), C.POINTER(u32), vp, vp, C.POINTER(np2_varcall_stats_t)]
+        L.np2_varcall_from_records.argtypes = [vp, vp, u32, vp, u32, vp, vp] + vc_out
+        L.np2_varcall_from_bam.argtypes = [vp, vp, C.c_char_p, vp, u32] + vc_out
+        L.np2_varcall_host.argtypes = [vp, u32, vp, u32, vp, u64, vp, u64] + vc_out
         L.np2_ctx_set_trace.argtypes = [vp, C.c_int]
         L.np2_ctx_set_timing.argtypes = [vp, C.c_int]
         L.np2_ctx_set_timing.restype = None
@@ -299,6 +323,72 @@ def depth_from_records(pol, L_, recs, cigar, **kw):
     L = lib()
     return depth_call(pol, L_, lambda *a: L.np2_depth_from_records(pol._h, int(L_), recs.ctypes.data if len(recs) else None, len(recs),
                                                                    cigar.ctypes.data if len(cigar) else None, *a), **kw)
+
+
+def varcall_call(check, L_, call, min_depth=8, min_alt=3, hom_pm=800, het_pm=250, max_indel=28, min_aligned_fra=0.0, exclude_flags=0xF04,
+                 min_mapq=5, want_counts=False):
+    """One np2_varcall_* call: `call(opts, calls, n_calls, cov, alt, stats)` is the entry point with its leading arguments
+    bound, `check` raises on its status -> (calls as a VARCALL_DTYPE array, stats dict — the six call totals under the names
+    of VARCALL_CALLS —, cov as uint32 [L] or None, alt as uint32 [L, 4] or None)."""
+    o = np2_varcall_opts_t(min_aligned_fra, min_depth, min_alt, hom_pm, het_pm, max_indel, exclude_flags, min_mapq)
+    pc, n, st = C.c_void_p(), C.c_uint32(), np2_varcall_stats_t()
+    n_pos = int(L_)
+    cov = np.zeros(max(n_pos, 1), dtype=np.uint32) if want_counts else None
+    alt = np.zeros((max(n_pos, 1), 4), dtype=np.uint32) if want_counts else None
+    try:
+        check(call(C.byref(o), C.byref(pc), C.byref(n), cov.ctypes.data if want_counts else None, alt.ctypes.data if want_counts else None,
+                   C.byref(st)))
+        calls = np.frombuffer(C.string_at(pc.value, n.value * VARCALL_DTYPE.itemsize), dtype=VARCALL_DTYPE) if n.value else np.zeros(0, VARCALL_DTYPE)
+    finally:
+        if pc.value:
+            lib().np2_free(pc)
+    stats = {f: getattr(st, f) for f, _ in np2_varcall_stats_t._fields_ if f not in ("calls", "stage_ms", "pad")}
+    stats.update({k: int(st.calls[i]) for i, k in enumerate(VARCALL_CALLS)})
+    stats["stage_ms"] = {k: float(st.stage_ms[i]) for i, k in enumerate(VARCALL_STAGES)}
+    return calls, stats, (cov[:n_pos] if want_counts else None), (alt[:n_pos] if want_counts else None)
+
+
+def _varcall_arrays(ref, recs, cigar, seq4):
+    ref = np.frombuffer(bytes(ref), dtype=np.uint8) if isinstance(ref, (bytes, bytearray)) else np.ascontiguousarray(ref, dtype=np.uint8)
+    recs = np.ascontiguousarray(recs)
+    if recs.ndim != 1 or (len(recs) and recs.dtype.itemsize != 40):
+        raise ValueError("recs must be a one-dimensional array of np2_bamrec_t (io.BAMREC_DTYPE)")
+    return ref, recs, np.ascontiguousarray(cigar, dtype=np.uint32), np.ascontiguousarray(seq4, dtype=np.uint8)
+
+
+def _ptr(a):
+    return a.ctypes.data if len(a) else None
+
+
+def varcall_from_records(pol, ref, recs, cigar, seq4, **kw):
+    """np2_varcall_from_records: the read-supported variants of the contig `ref` (bytes or uint8 array) from alignment records
+    (`recs`: np2_bamrec_t as io.BAMREC_DTYPE, `cigar`: the BAM CIGAR words, `seq4`: the BAM 4-bit SEQ bytes) on the device of
+    Polisher `pol`.  Keywords: min_depth=8, min_alt=3, hom_pm=800, het_pm=250, max_indel=28, min_aligned_fra=0.0,
+    exclude_flags=0xF04, min_mapq=5, want_counts=False.  The rule is include/np2_io.h's; see varcall_call for what comes back."""
+    ref, recs, cigar, seq4 = _varcall_arrays(ref, recs, cigar, seq4)
+    L = lib()
+    return varcall_call(pol._check, len(ref), lambda *a: L.np2_varcall_from_records(pol._h, _ptr(ref), len(ref), _ptr(recs), len(recs), _ptr(cigar),
+                                                                                      _ptr(seq4), *a), **kw)
+
+
+def varcall_from_bam(pol, bam, name, ref, **kw):
+    """np2_varcall_from_bam: the same over the records of contig `name` of the indexed BAM `bam` (io.Bam), read the way
+    io.contig_from_bam reads them (on the device with NP2_INFLATE=gpu, else by the host pool)."""
+    ref = _varcall_arrays(ref, np.zeros(0, dtype=[("x", "u1", 40)]), [], [])[0]
+    L = lib()
+    return varcall_call(pol._check, len(ref), lambda *a: L.np2_varcall_from_bam(pol._h, bam._h, name.encode(), _ptr(ref), len(ref), *a), **kw)
+
+
+def varcall_host(ref, recs, cigar, seq4, **kw):
+    """np2_varcall_host: the host twin of varcall_from_records — the same rule on one CPU thread, no device."""
+    ref, recs, cigar, seq4 = _varcall_arrays(ref, recs, cigar, seq4)
+    L = lib()
+
+    def check(rc):
+        if rc != 0:
+            raise Np2Error(rc, (L.np2_io_last_error() or b"").decode())
+    return varcall_call(check, len(ref), lambda *a: L.np2_varcall_host(_ptr(ref), len(ref), _ptr(recs), len(recs), _ptr(cigar), len(cigar),
+                                                                       _ptr(seq4), len(seq4), *a), **kw)
 
 
 def _pack_seqs(seqs, to_bytes=True):

@@ -5,6 +5,7 @@
 #include "np2_fetch_gpu.hpp"
 #include "np2_frontend.hpp"
 #include "np2_kernel_timer.hpp"
+#include "np2_varcall.hpp"
 
 namespace {
 
@@ -105,6 +106,44 @@ int np2_depth_from_bam(np2_ctx_t *cx, np2_bam_t *bam, const char *name, uint32_t
         upload(d_recs, rs.own_recs), upload(d_cigar, rs.own_cigar);
         np2h::depth_device(cx, L, rs.from_device ? rs.d_recs : d_recs.p, rs.n_recs, rs.from_device ? rs.d_cigar : d_cigar.p, rule, starts, ends, n_runs,
                            depth, stats);
+        return NP2_OK;
+    }, np2h::ctx_sink(cx));
+}
+
+// Read-supported variants of contig `name` (np2_varcall.hip).  The records come from the reader np2_contig_from_bam would
+// take, SEQ included: on the device path records, CIGAR words and SEQ are in HBM already; on the host path the pool has
+// streamed SEQ to the device, and positions, flags and CIGAR words are uploaded here.
+int np2_varcall_from_bam(np2_ctx_t *cx, np2_bam_t *bam, const char *name, const uint8_t *ref, uint32_t L, const np2_varcall_opts_t *opts,
+                         np2_varcall_t **calls, uint32_t *n_calls, uint32_t *cov, uint32_t *alt, np2_varcall_stats_t *stats) {
+    if (!cx) return NP2_E_ARG;
+    if (calls) *calls = nullptr;
+    if (n_calls) *n_calls = 0;
+    return np2h::abi_guard([&] {
+        // every argument is checked before anything is launched
+        const np2vc::Rule rule = np2h::varcall_rule(opts);
+        if (!bam || !name || !calls || !n_calls || (L && !ref)) throw np2h::Np2Error(NP2_E_ARG, "np2_varcall_from_bam: bam, name, ref, calls or n_calls is NULL");
+        const int tid = ref_id(bam, name);
+        HIPCHK(hipSetDevice(cx->device));
+        np2_front_opts_t fo;
+        memset(&fo, 0, sizeof fo); // (read admission plays no part; -S off: SEQ is every record's own)
+        const RecordSet rs = read_records(bam, tid, L, 0, L, &fo, cx->stream, WANT_SEQ);
+        uint64_t n_cig = rs.own_cigar.size();
+        if (rs.from_device)
+            for (uint32_t i = 0; i < rs.n_recs; ++i)
+                if (rs.recs[i].n_cigar) n_cig = std::max<uint64_t>(n_cig, rs.recs[i].cigar_off + rs.recs[i].n_cigar);
+        np2h::varcall_check_records(rs.recs, rs.n_recs, n_cig, rs.seq_bytes, "np2_varcall_from_bam");
+        if (rs.seq_bytes && !rs.d_seq) throw np2h::Np2Error(NP2_E_DEVICE, "np2_varcall_from_bam: the reader left no SEQ on the device");
+        np2h::DevBuf<np2_bamrec_t> d_recs;
+        np2h::DevBuf<uint32_t> d_cigar;
+        d_recs.cached = d_cigar.cached = true; // (released after varcall_device has drained the stream)
+        auto upload = [&](auto &buf, const auto &v) { // (the host reader's vectors: empty on the device path)
+            if (v.empty()) return;
+            buf.ensure(v.size());
+            HIPCHK(hipMemcpyAsync(buf.p, v.data(), v.size() * sizeof v[0], hipMemcpyHostToDevice, cx->stream));
+        };
+        upload(d_recs, rs.own_recs), upload(d_cigar, rs.own_cigar);
+        np2h::varcall_device(cx, ref, L, rs.from_device ? rs.d_recs : d_recs.p, rs.n_recs, rs.from_device ? rs.d_cigar : d_cigar.p, n_cig, rs.d_seq,
+                             rs.seq_bytes, rule, calls, n_calls, cov, alt, stats);
         return NP2_OK;
     }, np2h::ctx_sink(cx));
 }
