@@ -202,6 +202,95 @@ int np2_varcall_host(const uint8_t *ref, uint32_t L, const np2_bamrec_t *recs, u
                      uint64_t n_cigar_words, const uint8_t *seq4, uint64_t seq_bytes, const np2_varcall_opts_t *opts,
                      np2_varcall_t **calls, uint32_t *n_calls, uint32_t *cov /* [L] or NULL */, uint32_t *alt /* [4 L] or NULL */,
                      np2_varcall_stats_t *stats /* or NULL */);
+/* ---- an assembly's differences from a reference: alignments of its segments -> runs covered once (R) and calls (V) -------
+ * The third over-correction measure of the reference's README (minimap2 -cx asm10 --cs | sort | paftools.js call, then
+ * e_use_vcf.py), and the evaluation of a polish against a truth sequence.  THE RULE IS THIS PROJECT'S OWN: equality with
+ * minimap2, paftools or any other caller is not claimed (no asm10 scoring, no second affine piece, no shifting of events).
+ * Inputs, all in host memory: references T_0 .. T_{n-1} as bytes, case-insensitive, A C G T = codes 0..3, anything else N,
+ *   as one concatenation refs with ref_off[n_refs + 1] (ref_off[0] = 0, ascending; reference t is refs[ref_off[t] ..
+ *   ref_off[t + 1])); a query stream of bytes in the queries' FORWARD orientation; alignments (np2_asmaln_t) whose CIGAR
+ *   (BAM words len << 4 | op) is in SAM orientation: with flag 16 SAM base j is the complement of forward byte q_len - 1 - j
+ *   and the owned SAM interval is [q_len - own_hi, q_len - own_lo); otherwise both are the forward ones.
+ * Admission: an alignment is admitted iff flag & 4 == 0 and n_cigar > 0 (else stats.alns_unaligned), mapq >= min_mapq (else
+ *   stats.alns_low_mapq), every operation is M I D S = or X (an N, H or P operation or an operation code above 8:
+ *   stats.alns_skipped) and its reference span, the sum of its M D = X lengths, is at least min_aln (else stats.alns_short);
+ *   the first test that fails names the counter.
+ * Anchor: an M, = or X column is its own anchor.  An I or D operation's anchor is the last M, = or X column before it in the
+ *   CIGAR, however many I or D operations lie between; with no such column the operation is ignored, and so is an operation
+ *   of length 0.  A column or operation BELONGS to the alignment iff its anchor's SAM query index lies in the owned SAM
+ *   interval.
+ * Coverage: every belonging M = X column covers its reference position, every belonging D the n positions it deletes; they
+ *   form one interval per alignment, and cov[p] is the number of admitted alignments whose interval holds p.
+ * Events of admitted alignments, among belonging columns and operations, where the CIGAR has them (nothing is shifted: the
+ *   aligner left-aligns its gaps): SNV at p: an M or X column whose reference and query bases are both A C G T and differ.
+ *   DEL (a, n): a D of n bases with anchor position a.  INS (a, n): an I of n bases (any bytes) with anchor position a.
+ * Filter: an event is kept iff its whole footprint has cov == 1.  SNV: p.  DEL: a .. a + n.  INS: a, and a + 1 when
+ *   a + 1 < |T_tid|.
+ * R runs: the maximal runs of cov == 1 inside each reference (a run does not cross from one reference into the next).
+ * Order: runs by (tid, start); events by (tid, pos, kind) with SNV < DEL < INS, then alignment index, then CIGAR order.
+ * q_pos is a forward index in the alignment's query: SNV that base; INS the lowest forward index of the inserted bases; DEL
+ *   the first forward base after the gap, which may be q_len.
+ * Tiling (python -m nextpolish2_amd.asmcall, which cuts contigs into the queries): overlap is even, m = overlap / 2, step =
+ *   seg - overlap.  A contig of length Lc < seg is one segment; otherwise there are n = max(1, (Lc - overlap) / step) (rounded
+ *   down) segments, segment i is [i step, i step + seg) and the last one runs to Lc.  Segment i owns [i step + m, i step + seg
+ *   - m) in contig coordinates, the first from 0 and the last to Lc: the owned intervals tile the contig.  q_base is the
+ *   segment's start, own_lo / own_hi the owned interval minus q_base.
+ * Outputs: *runs and *vars (release with np2_free; NULL when there is none) with their counts; cov (or NULL): the caller's
+ *   ref_off[n_refs] words.
+ * Checked on the host before anything is launched, the context stays usable.  NP2_E_ARG: a NULL argument, ref_off not
+ *   ascending from 0, data outside its buffer (CIGAR words, query bytes), own_lo > own_hi or own_hi > q_len, and for an
+ *   alignment with flag & 4 == 0, n_cigar > 0 and no operation but M I D S = X: a tid outside the references, pos + span > |T_tid|, a CIGAR query
+ *   length (M I S = X) different from q_len.  NP2_E_UNSUPPORTED: total reference length above 4294901760, or query bytes +
+ *   CIGAR words (the bound of the events) above 4294901760.
+ * Not here: asm10's scoring and the second affine piece; segments that map across structural rearrangements (they fail
+ *   min_aln or mapq and leave coverage 0); VCF output; several ranks; references or assemblies beyond one device's memory. */
+typedef struct np2_asmaln {
+    int32_t tid;
+    uint32_t pos;              /* 0-based reference position of the first M = X column */
+    uint32_t flag;             /* bit 16: reverse, bit 4: unaligned */
+    uint32_t mapq, n_cigar;
+    uint32_t q_len;            /* the query's bytes in the stream */
+    uint32_t own_lo, own_hi;   /* the owned forward query interval, 0 <= own_lo <= own_hi <= q_len */
+    uint32_t q_id, q_base;     /* reporting only: which contig, and the contig coordinate of query byte 0 */
+    uint64_t cigar_off, q_off; /* first CIGAR word, first query byte */
+} np2_asmaln_t;
+typedef struct np2_asmcall_opts {
+    uint32_t min_mapq; /* -q 5 */
+    uint32_t min_aln;  /* --min_aln 5000 */
+} np2_asmcall_opts_t;
+typedef struct np2_asmrun {
+    uint32_t tid, start, end; /* [start, end) inside reference tid */
+} np2_asmrun_t;
+typedef struct np2_asmvar {
+    uint32_t tid;
+    uint32_t pos;      /* the SNV's position, the indel's anchor */
+    uint32_t aln;      /* index of the alignment */
+    uint32_t len;      /* SNV 1; indel: n */
+    uint32_t q_pos;    /* forward index in the alignment's query (above) */
+    uint8_t kind;      /* 0 SNV, 1 DEL, 2 INS */
+    uint8_t ref_code;  /* SNV: the reference base, A C G T = 0..3; else 0 */
+    uint8_t alt_code;  /* SNV: the query base in the reference's orientation; else 0 */
+    uint8_t rev;       /* 1: the alignment has flag 16 */
+} np2_asmvar_t;
+typedef struct np2_asmcall_stats {
+    uint64_t alns_seen, alns_admitted, alns_skipped, alns_low_mapq, alns_short, alns_unaligned;
+    uint64_t runs, r_bases;          /* R runs and the bases in them (cov == 1) */
+    uint64_t cov0_bases, cov2_bases; /* reference bases at coverage 0 and at coverage >= 2 */
+    uint64_t found[3], kept[3];      /* events by kind, before and after the filter */
+    uint64_t ins_bases, del_bases;   /* of the kept events */
+    float kernel_ms;                 /* the kernels and the sort together (HIP events): the sum of stage_ms */
+    float stage_ms[9];               /* walk counted, coverage scan, cov == 1 counts, event offsets, walk written, runs, filter,
+                                        sort, gather */
+} np2_asmcall_stats_t;
+int np2_asmcall(np2_ctx_t *ctx, const uint8_t *refs, const uint64_t *ref_off, uint32_t n_refs, const uint8_t *query,
+                uint64_t query_bytes, const np2_asmaln_t *alns, uint32_t n_alns, const uint32_t *cigar, uint64_t n_cigar_words,
+                const np2_asmcall_opts_t *opts, np2_asmrun_t **runs, uint32_t *n_runs, np2_asmvar_t **vars, uint32_t *n_vars,
+                uint32_t *cov /* [ref_off[n_refs]] or NULL */, np2_asmcall_stats_t *stats /* or NULL */);
+/* the host twin: the same rule on one CPU thread, no device and no context (kernel_ms stays 0) */
+int np2_asmcall_host(const uint8_t *refs, const uint64_t *ref_off, uint32_t n_refs, const uint8_t *query, uint64_t query_bytes,
+                     const np2_asmaln_t *alns, uint32_t n_alns, const uint32_t *cigar, uint64_t n_cigar_words,
+                     const np2_asmcall_opts_t *opts, np2_asmrun_t **runs, uint32_t *n_runs, np2_asmvar_t **vars, uint32_t *n_vars,
+                     uint32_t *cov /* [ref_off[n_refs]] or NULL */, np2_asmcall_stats_t *stats /* or NULL */);
 /* ---- one reference interval of a contig straight from the BAM (multi-GPU: every rank parses only its part) -----------
  * begin: fetch the records overlapping [own_lo - halo, own_hi + halo) through the .bai linear index, admit + columnarise
  *        them; returns the BGZF virtual offsets of the pushed records that START in [own_lo, own_hi) (file order).

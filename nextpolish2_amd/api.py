@@ -43,6 +43,7 @@ IO_ABI_SYMBOLS = [
     "np2_seqfile_stream", "np2_bin_files", "np2_seqfile_reads",
     "np2_depth_from_records", "np2_depth_from_bam",
     "np2_varcall_from_records", "np2_varcall_from_bam", "np2_varcall_host",
+    "np2_asmcall", "np2_asmcall_host",
     "np2_srqc_bytes", "np2_srqc_files", "np2_srqc_last_stats", "np2_srqc_last_kernel_ms", "np2_kcount_files_qc",
     "np2_kcount_files_to_dumps_qc", "np2_ctx_create_from_reads_qc", "np2_seqfile_stream_qual",
     "np2_sradapt_bytes", "np2_sradapt_files", "np2_sradapt_last_stats", "np2_sradapt_last_kernel_ms", "np2_kcount_files_ad",
@@ -101,6 +102,28 @@ VARCALL_KINDS = ("SNV", "DEL", "INS")
 VARCALL_STAGES = ("records", "scan", "sorts", "alleles", "count", "emit")  # np2_varcall_stats_t.stage_ms
 VARCALL_CALLS = ("snv_het", "snv_hom", "del_het", "del_hom", "ins_het", "ins_hom")  # np2_varcall_stats_t.calls
 assert C.sizeof(np2_varcall_opts_t) == 32 and C.sizeof(np2_varcall_stats_t) == 136 and VARCALL_DTYPE.itemsize == 32
+
+
+class np2_asmcall_opts_t(C.Structure):
+    _fields_ = [("min_mapq", C.c_uint32), ("min_aln", C.c_uint32)]
+
+
+class np2_asmcall_stats_t(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("alns_seen", "alns_admitted", "alns_skipped", "alns_low_mapq", "alns_short", "alns_unaligned", "runs",
+                                          "r_bases", "cov0_bases", "cov2_bases")] + \
+               [("found", C.c_uint64 * 3), ("kept", C.c_uint64 * 3), ("ins_bases", C.c_uint64), ("del_bases", C.c_uint64),
+                ("kernel_ms", C.c_float), ("stage_ms", C.c_float * 9)]
+
+
+ASMALN_DTYPE = np.dtype([("tid", "<i4")] + [(f, "<u4") for f in ("pos", "flag", "mapq", "n_cigar", "q_len", "own_lo", "own_hi", "q_id", "q_base")] +
+                        [("cigar_off", "<u8"), ("q_off", "<u8")])  # np2_asmaln_t
+ASMRUN_DTYPE = np.dtype([("tid", "<u4"), ("start", "<u4"), ("end", "<u4")])  # np2_asmrun_t
+ASMVAR_DTYPE = np.dtype([(f, "<u4") for f in ("tid", "pos", "aln", "len", "q_pos")] +
+                        [(f, "u1") for f in ("kind", "ref_code", "alt_code", "rev")])  # np2_asmvar_t
+ASMCALL_KINDS = ("SNV", "DEL", "INS")
+ASMCALL_STAGES = ("count", "cov_scan", "ones", "offsets", "emit", "runs", "filter", "sort", "gather")  # np2_asmcall_stats_t.stage_ms
+assert C.sizeof(np2_asmcall_opts_t) == 8 and C.sizeof(np2_asmcall_stats_t) == 184
+assert ASMALN_DTYPE.itemsize == 56 and ASMRUN_DTYPE.itemsize == 12 and ASMVAR_DTYPE.itemsize == 24
 
 
 class np2_rep_opts_t(C.Structure):
@@ -196,6 +219,10 @@ def _lib_locked():
         L.np2_varcall_from_records.argtypes = [vp, vp, u32, vp, u32, vp, vp] + vc_out
         L.np2_varcall_from_bam.argtypes = [vp, vp, C.c_char_p, vp, u32] + vc_out
         L.np2_varcall_host.argtypes = [vp, u32, vp, u32, vp, u64, vp, u64] + vc_out
+        ac = [vp, vp, u32, vp, u64, vp, u32, vp, u64, C.POINTER(np2_asmcall_opts_t), C.POINTER(vp), C.POINTER(u32), C.POINTER(vp), C.POINTER(u32), vp,
+              C.POINTER(np2_asmcall_stats_t)]
+        L.np2_asmcall.argtypes = [vp] + ac
+        L.np2_asmcall_host.argtypes = ac
         L.np2_ctx_set_trace.argtypes = [vp, C.c_int]
         L.np2_ctx_set_timing.argtypes = [vp, C.c_int]
         L.np2_ctx_set_timing.restype = None
@@ -389,6 +416,57 @@ def varcall_host(ref, recs, cigar, seq4, **kw):
             raise Np2Error(rc, (L.np2_io_last_error() or b"").decode())
     return varcall_call(check, len(ref), lambda *a: L.np2_varcall_host(_ptr(ref), len(ref), _ptr(recs), len(recs), _ptr(cigar), len(cigar),
                                                                        _ptr(seq4), len(seq4), *a), **kw)
+
+
+def _asmcall(check, call, refs, query, alns, cigar, min_mapq=5, min_aln=5000, want_cov=False):
+    """One np2_asmcall* call: `call(*arguments)` is the entry point with its context bound, `check` raises on its status.
+    refs: a list of reference sequences (bytes); query: the query stream (bytes or uint8 array); alns: an ASMALN_DTYPE array;
+    cigar: BAM CIGAR words -> (runs as an ASMRUN_DTYPE array, vars as an ASMVAR_DTYPE array, stats dict, cov as uint32 over the
+    concatenated references or None)."""
+    refs = [bytes(r) for r in refs]
+    ref_off = np.zeros(len(refs) + 1, dtype=np.uint64)
+    ref_off[1:] = np.cumsum([len(r) for r in refs], dtype=np.uint64)
+    cat = np.frombuffer(b"".join(refs), dtype=np.uint8)
+    query = np.frombuffer(bytes(query), dtype=np.uint8) if isinstance(query, (bytes, bytearray, memoryview)) else np.ascontiguousarray(query, dtype=np.uint8)
+    alns = np.ascontiguousarray(alns)
+    if alns.ndim != 1 or (len(alns) and alns.dtype.itemsize != ASMALN_DTYPE.itemsize):
+        raise ValueError("alns must be a one-dimensional array of np2_asmaln_t (api.ASMALN_DTYPE)")
+    cigar = np.ascontiguousarray(cigar, dtype=np.uint32)
+    o, st = np2_asmcall_opts_t(min_mapq, min_aln), np2_asmcall_stats_t()
+    pr, pv, nr, nv = C.c_void_p(), C.c_void_p(), C.c_uint32(), C.c_uint32()
+    cov = np.zeros(max(len(cat), 1), dtype=np.uint32) if want_cov else None
+    try:
+        check(call(_ptr(cat), ref_off.ctypes.data, len(refs), _ptr(query), len(query), _ptr(alns), len(alns), _ptr(cigar), len(cigar), C.byref(o),
+                   C.byref(pr), C.byref(nr), C.byref(pv), C.byref(nv), cov.ctypes.data if want_cov else None, C.byref(st)))
+        runs = np.frombuffer(C.string_at(pr.value, nr.value * ASMRUN_DTYPE.itemsize), dtype=ASMRUN_DTYPE) if nr.value else np.zeros(0, ASMRUN_DTYPE)
+        vars_ = np.frombuffer(C.string_at(pv.value, nv.value * ASMVAR_DTYPE.itemsize), dtype=ASMVAR_DTYPE) if nv.value else np.zeros(0, ASMVAR_DTYPE)
+    finally:
+        for p in (pr, pv):
+            if p.value:
+                lib().np2_free(p)
+    stats = {f: getattr(st, f) for f, _ in np2_asmcall_stats_t._fields_ if f not in ("found", "kept", "stage_ms")}
+    for i, k in enumerate(ASMCALL_KINDS):
+        stats["found_" + k.lower()], stats["kept_" + k.lower()] = int(st.found[i]), int(st.kept[i])
+    stats["stage_ms"] = {k: float(st.stage_ms[i]) for i, k in enumerate(ASMCALL_STAGES)}
+    return runs, vars_, stats, (cov[:len(cat)] if want_cov else None)
+
+
+def asmcall(pol, refs, query, alns, cigar, **kw):
+    """np2_asmcall: an assembly's differences from references, from the alignments of its segments, on the device of Polisher
+    `pol`: the runs covered exactly once and the SNV / DEL / INS events inside them.  Keywords: min_mapq=5, min_aln=5000,
+    want_cov=False.  The rule is include/np2_io.h's (this project's own); see _asmcall for the arguments and what comes back."""
+    L = lib()
+    return _asmcall(pol._check, lambda *a: L.np2_asmcall(pol._h, *a), refs, query, alns, cigar, **kw)
+
+
+def asmcall_host(refs, query, alns, cigar, **kw):
+    """np2_asmcall_host: the host twin of asmcall — the same rule on one CPU thread, no device."""
+    L = lib()
+
+    def check(rc):
+        if rc != 0:
+            raise Np2Error(rc, (L.np2_io_last_error() or b"").decode())
+    return _asmcall(check, lambda *a: L.np2_asmcall_host(*a), refs, query, alns, cigar, **kw)
 
 
 def _pack_seqs(seqs, to_bytes=True):
